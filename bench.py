@@ -26,6 +26,10 @@ One JSON line on stdout (rank 0).  Extra objects:
                the same instance on this box's host cores
   config.other_workloads  (outside the timed region) the other BASELINE configs on this GPU:
                digitinvader9, juggling_b5_f6, the time-boxed synthetic 64 x 32 instance
+
+--dump-outputs DIR writes the raw automaton of the last timed step (the arrays of include/stcsp_engine.h's
+stcsp_result; sharded runs: the shards merged on rank 0) as DIR/<name>.npy, numbered independently of scheduling
+(see canonical_outputs), at most DUMP_BYTES in all, so that two builds can be compared array for array.
 """
 import argparse
 import ctypes as C
@@ -44,6 +48,10 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 SYNTH = (64, 32, 602, 6, 20261003)  # BASELINE config 4: 64 vars x |D| = 32, 602 point + 6 next table constraints
 SYNTH_SHAPE = SYNTH  # --synthetic-shape (tests shrink it: the CPU stand-in engine manages ~3 k nodes/s on 64 x 32)
 REFERENCE_P14_NODES_PER_S = 10.9e3  # the reference itself, survey VM, 1 core
+DUMP_BYTES = 64_000_000  # --dump-outputs: size cap of all files together (64 MB)
+DUMP_SEED = 20261015  # --dump-outputs: the fixed sample of states / edges taken when the whole automaton exceeds the cap
+DUMP_SCALARS = ("n_states", "n_edges", "sig_len", "n_sig_vars", "n_until", "n_until_cons", "n_vars", "n_constraint_sets",
+                "root_final", "truncated")
 
 
 def free_port():
@@ -166,6 +174,80 @@ def alg_bytes(model, res_sig_len, nodes, leaves):
     b_node = 2 * N * K * W * 4
     b_leaf = 4 * (res_sig_len + 1) * 2 + 8 + 4 * N
     return nodes * b_node + leaves * b_leaf, b_node, b_leaf
+
+
+def canonical_outputs(d):
+    """The raw automaton `d` (sharded.result_to_numpy of a stcsp_result) as float arrays whose numbering does not depend on
+    scheduling: the engine numbers states and constraint sets in the order its search found them, which differs from run to
+    run.  States are renumbered breadth-first from the root, every state's out-edges taken in label order (the walk of
+    Automaton.canonical / tests/canon.py), and constraint sets by first visit on that walk (the root's id is not meaningful:
+    -1).  The states no edge reaches (failed ones) follow, sorted by (constraint set, signature); edges are listed by (source,
+    label).  scalars holds the DUMP_SCALARS fields in that order."""
+    import numpy as np
+    ns, ne, L, nv = d["n_states"], d["n_edges"], d["sig_len"], d["n_vars"]
+    sig = d["state_sig"].reshape(ns, L)
+    vals = d["edge_values"].reshape(ne, nv)
+
+    def by_source_label(src):
+        return np.lexsort(tuple(vals[:, i] for i in range(nv - 1, -1, -1)) + (src,))
+
+    e = by_source_label(d["edge_src"])
+    src, dst = d["edge_src"][e], d["edge_dst"][e]
+    off = np.searchsorted(src, np.arange(ns + 1))
+    num = np.full(ns, -1, np.int64)
+    num[0] = 0
+    levels, seen = [np.zeros(1, np.int64)], 1
+    while levels[-1].size:
+        front = levels[-1]
+        lens = off[front + 1] - off[front]
+        succ = dst[np.repeat(off[front] - (np.cumsum(lens) - lens), lens) + np.arange(lens.sum())]
+        succ = succ[num[succ] < 0]
+        u, first = np.unique(succ, return_index=True)
+        nxt = u[np.argsort(first)]  # first seen = first numbered
+        num[nxt] = np.arange(seen, seen + nxt.size)
+        seen += nxt.size
+        levels.append(nxt)
+    cid, cmap = d["state_cid"], {}
+    for c in cid[np.concatenate(levels)[1:]].tolist():
+        cmap.setdefault(c, len(cmap))
+    rest = np.flatnonzero(num < 0)
+    for _ in range(2):  # sets seen only here are numbered in (signature) order, then the rows sorted again
+        key = np.array([cmap.get(c, len(cmap)) for c in cid[rest].tolist()], np.int64)
+        rest = rest[np.lexsort(tuple(sig[rest, i] for i in range(L - 1, -1, -1)) + (key,))]
+        for c in cid[rest].tolist():
+            cmap.setdefault(c, len(cmap))
+    perm = np.concatenate(levels + [rest])
+    num[perm] = np.arange(ns)
+    s2, d2 = num[d["edge_src"]], num[d["edge_dst"]]
+    e2 = by_source_label(s2)
+    f32, f64 = np.float32, np.float64
+    return {"state_cid": np.array([-1] + [cmap[c] for c in cid[perm[1:]].tolist()], f64),
+            "state_sig": sig[perm].astype(f32), "state_fail": d["state_fail"][perm].astype(f32),
+            "edge_src": s2[e2].astype(f64), "edge_dst": d2[e2].astype(f64), "edge_values": vals[e2].astype(f32),
+            "var_is_signature": d["var_is_signature"].astype(f32),
+            "scalars": np.array([d[k] for k in DUMP_SCALARS], f64)}
+
+
+def dump_outputs(out, out_dir):
+    """Write `out` as out_dir/<name>.npy.  Over DUMP_BYTES, the same seeded fraction of the state rows and of the edge rows
+    is kept (fixed by the two row counts) and state_index.npy / edge_index.npy say which rows."""
+    import numpy as np
+    states, edges = ("state_cid", "state_sig", "state_fail"), ("edge_src", "edge_dst", "edge_values")
+    cap = DUMP_BYTES - 256 * (len(out) + 2)  # .npy headers
+    total = sum(a.nbytes for a in out.values())
+    if total > cap:
+        rows = sum(a.nbytes for k, a in out.items() if k in states + edges)
+        frac = (cap - (total - rows)) / (rows + 8 * (len(out["state_cid"]) + len(out["edge_src"])))
+        rng = np.random.default_rng(DUMP_SEED)
+        for group, index in ((states, "state_index"), (edges, "edge_index")):
+            n = len(out[group[0]])
+            keep = np.sort(rng.choice(n, int(n * frac), replace=False))
+            for k in group:
+                out[k] = out[k][keep]
+            out[index] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
 
 
 def other_workload(st, golden, name, device, repeats=3):
@@ -331,7 +413,11 @@ def main():
                          "native loop (stcsp_engine_solve_sharded over the RCCL transport of libstcsp_rccl.so)")
     ap.add_argument("--stepped", action="store_true",
                     help="N=1 only: run the sharded pipeline (size-1 RCCL group, STCSP_F_STEPPED) -- the N>1 code path on one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the automaton of the last timed step as DIR/<name>.npy (see canonical_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.synthetic_shape:
         global SYNTH_SHAPE
@@ -473,6 +559,11 @@ def main():
         nodes = sum(r[0] for r in rank_rows)
         leaves = sum(r[1] for r in rank_rows)
 
+    # the last timed step's arrays, copied before the export check below solves again on the same engine
+    dumped = None
+    if args.dump_outputs and rank == 0 and not stepped:
+        dumped = importlib.import_module("stcsp-solver_amd.sharded").result_to_numpy(res)
+
     # parity of the last timed step (outside the timed region)
     check = {}
     if not stepped:
@@ -483,6 +574,8 @@ def main():
             merged = sh.gather_and_merge(st, eng, rank, world, dev)
             if rank == 0:
                 _, mres = merged
+                if args.dump_outputs:
+                    dumped = sh.result_to_numpy(mres)
                 a = st.Automaton(model, mres).traverse().renumber()
                 check = {"states": a.n_live_states, "edges": a.n_live_edges, "canonical_sha256": a.canonical_sha256()}
         except Exception as ex:
@@ -631,12 +724,18 @@ def main():
         }
         if not args.no_cpu_baseline and world == 1 and not stepped:
             out["cpu_baseline"] = cpu_baseline(st, args.workload, args.cpu_seconds, args.cpu_threads or host_cpu_share()[1])
+        if args.dump_outputs and dumped is not None:
+            dump_outputs(canonical_outputs(dumped), args.dump_outputs)
         print(json.dumps(out), flush=True)
+    dump_missing = bool(args.dump_outputs) and rank == 0 and dumped is None
     if stepped:
         ok = torch.tensor([1 if parity_ok else 0], dtype=torch.int64, device=dev)
         dist.broadcast(ok, 0)
         parity_ok = bool(ok.item())
         dist.destroy_process_group()
+    if dump_missing:
+        print(f"bench.py: --dump-outputs: no automaton to write ({check.get('error')})", file=sys.stderr)
+        sys.exit(4)
     if not parity_ok:
         print("bench.py: PARITY FAILURE -- the automaton differs from the reference's recorded canonical sha256", file=sys.stderr)
         sys.exit(3)

@@ -74,6 +74,14 @@ def golden():
     return json.loads((REPO / "tests" / "golden" / "reference_golden.json").read_text())
 
 
+def visible_gpus() -> int:
+    """GPUs torch sees, asked in a child process: torch ships its own HIP runtime, and once it has started in the test
+    process after libstcsp_hip.so was loaded, the engine's runtime finds no device there."""
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"],
+                       capture_output=True, text=True, check=True, timeout=300)
+    return int(r.stdout.split()[-1])
+
+
 def finish(engine, result, adversarial=None):
     """solverSolve's tail (reference src/solveralgorithm.cpp:972-985) on an engine result."""
     a = engine.automaton(result)

@@ -59,8 +59,8 @@ def test_bench_time_boxed_synthetic_through_the_sharded_pipeline(oracle_lib):
 
 def test_bench_refuses_more_gpus_than_visible():
     """No GPU in the CPU container: --gpus 2 must exit non-zero with a message (not print an n_gpus = 1 line)."""
-    import torch
-    if torch.cuda.device_count() >= 2:
+    from conftest import visible_gpus
+    if visible_gpus() >= 2:
         pytest.skip("this box has the GPUs")
     r = run_bench("--gpus", "2", "--steps", "1", "--warmup", "0", timeout=120)
     assert r.returncode != 0
@@ -80,3 +80,50 @@ def test_bench_has_no_switch_that_replaces_the_engine():
     assert "--test-engine" not in src and "fmodel" not in src
     r = run_bench("--test-engine", "fmodel", timeout=120)
     assert r.returncode != 0 and "unrecognized arguments" in r.stderr
+
+
+def test_bench_dump_outputs(golden, tmp_path):
+    """--dump-outputs writes the last timed step's automaton (here the shards merged on rank 0) in a numbering that does not
+    depend on scheduling: one and two shards number their states differently and still write the same arrays."""
+    import numpy as np
+    import bench
+    dumps = []
+    for world in (1, 2):
+        out = tmp_path / f"dump{world}"
+        r = run_bench("--gpus", str(world), "--workload", "partialorder_10", "--steps", "3", "--warmup", "0",
+                      "--scalable-workload", "", "--synthetic-seconds", "0", "--dump-outputs", str(out), entry=CPU_ENTRY)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = last_json(r.stdout)
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["parity"]["ok"]
+        assert sum(p.stat().st_size for p in out.glob("*.npy")) <= bench.DUMP_BYTES
+        dumps.append({p.stem: np.load(p) for p in out.glob("*.npy")})
+    a, b = dumps
+    assert sorted(a) == sorted(b) == sorted(["state_cid", "state_sig", "state_fail", "edge_src", "edge_dst", "edge_values",
+                                             "var_is_signature", "scalars"])
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k
+    g = golden["partialorder_10"]
+    assert a["state_cid"].shape == (g["states"],) and a["edge_values"].shape[0] == g["edges"]
+    r = run_bench("--steps", "0", entry=CPU_ENTRY, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_dump_outputs_size_cap(tmp_path, monkeypatch):
+    """Over the cap, the same seeded rows are kept from run to run and their indices are written beside them."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 200_000)
+    rng = np.random.default_rng(1)
+    out = {"state_cid": np.arange(3000, dtype=np.float64), "state_sig": rng.random((3000, 4), dtype=np.float32),
+           "state_fail": np.zeros(3000, np.float32), "edge_src": np.arange(20000, dtype=np.float64),
+           "edge_dst": np.arange(20000, dtype=np.float64), "edge_values": rng.random((20000, 5), dtype=np.float32),
+           "var_is_signature": np.ones(5, np.float32), "scalars": np.zeros(10)}
+    for run in ("a", "b"):
+        bench.dump_outputs({k: v.copy() for k, v in out.items()}, str(tmp_path / run))
+    a = {p.name: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert sum(p.stat().st_size for p in (tmp_path / "a").glob("*.npy")) <= 200_000
+    assert all(np.array_equal(a[n], np.load(tmp_path / "b" / n)) for n in a)
+    for kind, n in (("state", 3000), ("edge", 20000)):
+        idx = a[f"{kind}_index.npy"].astype(np.int64)
+        assert 0 < idx.size < n and np.all(np.diff(idx) > 0)
+    assert np.array_equal(a["edge_src.npy"], a["edge_index.npy"]) and np.array_equal(a["edge_values.npy"], out["edge_values"][a["edge_index.npy"].astype(np.int64)])

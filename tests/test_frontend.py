@@ -5,7 +5,8 @@ from pathlib import Path
 
 import pytest
 
-REF_EXAMPLES = Path("/root/reference/examples")
+# the reference's 26 shipped example inputs, stored byte for byte (MIT licence alongside)
+REF_EXAMPLES = Path(__file__).resolve().parent / "golden" / "reference_examples"
 
 
 def test_model_shape_matches_reference_counts(stcsp, golden):
@@ -83,10 +84,10 @@ def test_error_behaviour(stcsp):
     assert m.n_constraints == 1
 
 
-@pytest.mark.skipif(not REF_EXAMPLES.exists(), reason="reference tree not present (GPU box)")
 def test_generated_instances_equal_reference_examples(stcsp):
     """instances.py regenerates the reference's examples: identical models (same variables,
     bounds, arrays and constraint trees in the same order) as parsing the shipped files."""
+    assert sorted(p.stem for p in REF_EXAMPLES.glob("*.csp")) == sorted(stcsp.instances.REFERENCE_EXAMPLES)
     for name in stcsp.instances.REFERENCE_EXAMPLES:
         a = stcsp.Model.from_name(name)
         b = stcsp.Model(path=str(REF_EXAMPLES / f"{name}.csp"))
