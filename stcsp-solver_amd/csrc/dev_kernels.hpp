@@ -46,7 +46,7 @@ extern __shared__ __attribute__((aligned(16))) int stcsp_lds[];
 #ifndef STCSP_FRESH_SEED
 #define STCSP_FRESH_SEED 1
 #endif
-template <int DR, int L, bool CS, bool LITE, int W = 1>
+template <int DR, int L, bool CS, bool LITE, int W = 1, int KR = 1>
 __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const Img<L> &P, int gw, int lane, int *lds_vals, int *lds_stk, int *ldom,
                             int sib_off, WaveEnv<DR> &env, bool dry = false) {
     const Ctx c0 = ctx_from(hot);
@@ -146,9 +146,9 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
         {
             const Ctx cn = ctx_from(hot);
             if constexpr (W > 1)
-                oc = process_node_wide<DR, W, L>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bow, lo);
+                oc = process_node_wide<DR, W, L, KR>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bow, lo);
             else
-                oc = process_node<DR, L, CS, LITE>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
+                oc = process_node<DR, L, CS, LITE, KR>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
         }
         const Ctx ce = ctx_from(hot);
         const Ctx &c = ce;
@@ -156,9 +156,9 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
         static_assert(W == 1, "tuning builds: one-word domains only");
         const Ctx ce = ctx_from(hot);
         const Ctx &c = ce;
-        const int oc = process_node<DR, L, CS, LITE>(c, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
+        const int oc = process_node<DR, L, CS, LITE, KR>(c, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
 #else
-        const int oc = process_node<DR, L, CS, LITE>(c, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
+        const int oc = process_node<DR, L, CS, LITE, KR>(c, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
 #endif
         const bool last = step >= chain || __builtin_amdgcn_s_memtime() - t_slot > chain_cycles;
         const unsigned long long t_c = PHASE_NOW();
@@ -288,6 +288,7 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
                           : (lane == 1 ? hd.h1
                           : (lane == 2 ? lo.next_tag : (lane == 3 ? lo.new_expire : (lane == 4 ? (uint32_t)lo.h : (uint32_t)(lo.h >> 32)))));
             if (lane >= 1 && lane <= c.sig_len) rec[kCandHdr + lane - 1] = lo.kw;
+            if (KR == 2 && lane + 64 <= c.sig_len) rec[kCandHdr + lane + 63] = lo.kw2;
             uint32_t *vals = rec + kCandHdr + c.sig_len;
             uint32_t *blk = vals + c.N;
 #pragma unroll
@@ -303,7 +304,7 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
 #ifdef STCSP_X_NOCOMMIT
         STCSP_PATH_END();
 #endif
-        CommitOut co = table_commit<DR>(c, lane, ro, lo.kw, lo.h, hd.h0, hd.h1, lo.next_set, lo.next_tag, lo.evals);
+        CommitOut co = table_commit<DR, KR>(c, lane, ro, lo.kw, lo.kw2, lo.h, hd.h0, hd.h1, lo.next_set, lo.next_tag, lo.evals);
         if (!co.ok) {
             env.err = max(env.err, co.err);
             return;
@@ -701,7 +702,7 @@ __global__ void k_close_segment(Ctx c) {
 #ifndef STCSP_BIG_WAVES
 #define STCSP_BIG_WAVES 16  // wavefronts of a big workgroup
 #endif
-template <int DR, int L, bool CS, bool LITE, bool BIG = false, int W = 1>
+template <int DR, int L, bool CS, bool LITE, bool BIG = false, int W = 1, int KR = 1>
 __global__ __launch_bounds__(BIG ? STCSP_BIG_WAVES * 64 : 256, BIG ? 1 : (STCSP_EXPAND_WAVES > 1 ? STCSP_EXPAND_WAVES : (LITE && DR == 1 ? STCSP_LITE_WAVES : (DR <= 2 ? STCSP_GEN_WAVES : STCSP_WIDE_WAVES)))) void k_expand(const Ctx *__restrict__ cp, const Plan *__restrict__ plan_arg, unsigned launch_id, uint32_t tab_gen) {
     const Ctx &c = *cp;
     extern __shared__ __attribute__((aligned(16))) int smem[];
@@ -775,7 +776,7 @@ __global__ __launch_bounds__(BIG ? STCSP_BIG_WAVES * 64 : 256, BIG ? 1 : (STCSP_
         if (lane == gw_) hot[0] = tab_gen;
     }
 #ifdef STCSP_STATIC_SLOTS
-    for (int gw = blockIdx.x * wpb + wib; gw < n_slots; gw += total_waves) expand_node<DR, L, CS, LITE, W>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env);
+    for (int gw = blockIdx.x * wpb + wib; gw < n_slots; gw += total_waves) expand_node<DR, L, CS, LITE, W, KR>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env);
 #else
     // Slots: the first one by position, every further one by ticket -- slots differ widely in cost (a chain of up to `chain`
     // expansions, each anything between a failed sweep and a leaf with a new state), and with a fixed stride the round waits for
@@ -789,7 +790,7 @@ __global__ __launch_bounds__(BIG ? STCSP_BIG_WAVES * 64 : 256, BIG ? 1 : (STCSP_
         for (int gw = blockIdx.x * wpb + wib; gw < n_slots;) {
             unsigned ticket = 0;
             if (lane == 0) ticket = atomicAdd(cursor, 1u);
-            expand_node<DR, L, CS, LITE, W>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
+            expand_node<DR, L, CS, LITE, W, KR>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
             gw = total_waves + (int)rflu(ticket) * ncur + cur;
         }
     }
@@ -833,6 +834,8 @@ __global__ __launch_bounds__(BIG ? STCSP_BIG_WAVES * 64 : 256, BIG ? 1 : (STCSP_
 // ------------------------------------------------------------------ k_probe (tests / diagnostics)
 // process_node on caller-provided blocks: the kernel-granularity check behind stcsp_engine_propagate.
 // One wavefront per block, every item dirty (seed 0); the propagated block and the outcome go back.
+// The leaf's key is not part of what goes back: keys of more than 64 words (only the words < 64 are built here, KR = 1)
+// need no kernel of their own.
 template <int DR, int L, bool CS, bool LITE>
 __global__ __launch_bounds__(256, (DR <= 2 ? 4 : 3)) void k_probe(const Ctx *__restrict__ cp, uint32_t *blocks, int n, int set, uint32_t expire,
                                                                   int *outcome) {
@@ -879,13 +882,14 @@ __global__ __launch_bounds__(256, (DR <= 2 ? 4 : 3)) void k_probe(const Ctx *__r
 }
 
 // ------------------------------------------------------------------ commit
-// Lookup-or-insert the state (set tag, signature) held lane-striped in `kw` (lane j = key word j)
+// Lookup-or-insert the state (set tag, signature) held lane-striped in `kw` (lane j = key word j; with KR == 2 also `kw2`,
+// lane j = key word 64 + j: keys of 65..126 words, which the 128-word entries hold next to their slot word)
 // and append the edge record (label `vals`, lane-striped like the domain block).
 // Role of vertexTableGetVertex / vertexNew + vertexTableAddVertex / edgeNew + vertexAddEdge
 // (reference src/graph.cpp:14-38, 78-89, 108-123).
-template <int DR>
-__device__ CommitOut table_commit(const Ctx &c, int lane, int ro, uint32_t kw, unsigned long long h, uint32_t s0, uint32_t s1,
-                                  int set, uint32_t tag, const uint32_t (&vals)[DR]) {
+template <int DR, int KR>
+__device__ CommitOut table_commit(const Ctx &c, int lane, int ro, uint32_t kw, uint32_t kw2, unsigned long long h, uint32_t s0,
+                                  uint32_t s1, int set, uint32_t tag, const uint32_t (&vals)[DR]) {
     const CtlLayout L(c.world);
     uint32_t *misc = c.ctl + L.misc0;
     CommitOut out;
@@ -909,8 +913,9 @@ __device__ CommitOut table_commit(const Ctx &c, int lane, int ro, uint32_t kw, u
         // publisher writes the key, drains its stores, then the index, so a reader that sees the index sees the key
         unsigned long long sv = 0;
         if (lane == 0) sv = __hip_atomic_load(sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint32_t other = 0;
+        uint32_t other = 0, other2 = 0;
         if (lane < c.KL) other = __hip_atomic_load(&ent[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (KR == 2 && lane + 64 < c.KL) other2 = __hip_atomic_load(&ent[lane + 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         uint32_t lo = rflu((uint32_t)sv), hi = rflu((uint32_t)(sv >> 32));
         if (hi != gen) {  // free (empty, or left over from an earlier solve): claim it
             bool claimed = false;
@@ -934,6 +939,10 @@ __device__ CommitOut table_commit(const Ctx &c, int lane, int ro, uint32_t kw, u
                 __hip_atomic_store(&ent[lane], kw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 c.state_keys[(size_t)ni * c.KL + lane] = kw;  // (read by later launches and the export kernels only)
             }
+            if (KR == 2 && lane + 64 < c.KL) {
+                __hip_atomic_store(&ent[lane + 64], kw2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                c.state_keys[(size_t)ni * c.KL + lane + 64] = kw2;
+            }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (lane == 0) __hip_atomic_store(sw, ((unsigned long long)gen << 32) | ni, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -948,13 +957,14 @@ __device__ CommitOut table_commit(const Ctx &c, int lane, int ro, uint32_t kw, u
             unsigned long long t = 0;
             if (lane == 0) t = __hip_atomic_load(sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (lane < c.KL) other = __hip_atomic_load(&ent[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (KR == 2 && lane + 64 < c.KL) other2 = __hip_atomic_load(&ent[lane + 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             lo = rflu((uint32_t)t);
             if (++spins > (1u << 22)) {
                 out.err = ERR_TABLE_SPIN;
                 return out;
             }
         }
-        if (!__ballot(lane < c.KL && other != kw)) {
+        if (!__ballot((lane < c.KL && other != kw) || (KR == 2 && lane + 64 < c.KL && other2 != kw2))) {  // (words j and 64 + j)
             idx = lo;
             break;
         }
@@ -962,7 +972,8 @@ __device__ CommitOut table_commit(const Ctx &c, int lane, int ro, uint32_t kw, u
         // duplicate state would be a wrong automaton, a second read of a colliding entry costs a round trip on a path that
         // tables at most half full rarely take.)
         if (lane < c.KL) other = __hip_atomic_load(&ent[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!__ballot(lane < c.KL && other != kw)) {
+        if (KR == 2 && lane + 64 < c.KL) other2 = __hip_atomic_load(&ent[lane + 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!__ballot((lane < c.KL && other != kw) || (KR == 2 && lane + 64 < c.KL && other2 != kw2))) {
             idx = lo;
             break;
         }
@@ -1025,7 +1036,7 @@ __device__ unsigned emit_state_node(const Ctx &c, int lane, int ro, uint32_t *ou
 }
 
 // ------------------------------------------------------------------ k_commit (sharded runs)
-template <int DR>
+template <int DR, int KR = 1>
 __global__ __launch_bounds__(256) void k_commit(Ctx c, CommitArgs a) {
     const int lane = threadIdx.x & 63, wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const long long gw = (long long)blockIdx.x * 4 + wib;
@@ -1036,9 +1047,10 @@ __global__ __launch_bounds__(256) void k_commit(Ctx c, CommitArgs a) {
     uint32_t hw = lane < 6 ? rec[lane] : 0u;  // one coalesced header read
     const uint32_t s0 = rdlane(hw, 0), s1 = rdlane(hw, 1), tag = rdlane(hw, 2), expire = rdlane(hw, 3);
     const unsigned long long h = ((unsigned long long)rdlane(hw, 5) << 32) | rdlane(hw, 4);  // computed by k_expand
-    uint32_t kw = 0;
+    uint32_t kw = 0, kw2 = 0;
     if (lane == 0) kw = tag;
     if (lane >= 1 && lane <= c.sig_len) kw = rec[kCandHdr + lane - 1];
+    if (KR == 2 && lane + 64 <= c.sig_len) kw2 = rec[kCandHdr + lane + 63];
     const uint32_t *pv = rec + kCandHdr + c.sig_len, *pb = pv + c.N;
     uint32_t vals[DR], blk[DR];
 #pragma unroll
@@ -1047,7 +1059,7 @@ __global__ __launch_bounds__(256) void k_commit(Ctx c, CommitArgs a) {
         vals[q] = k < c.N ? pv[k] : 0u;
         blk[q] = k < c.NK ? pb[k] : 0u;
     }
-    CommitOut co = table_commit<DR>(c, lane, ro, kw, h, s0, s1, -1, tag, vals);
+    CommitOut co = table_commit<DR, KR>(c, lane, ro, kw, kw2, h, s0, s1, -1, tag, vals);
     unsigned err = co.ok ? 0u : co.err;
     if (co.ok && co.is_new) {
         if (lane == 0) add_stats(c, (int)(gw & 0x7fffffff), ST_NEWSTATES, 1);

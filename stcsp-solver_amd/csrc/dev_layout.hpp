@@ -163,6 +163,7 @@ struct Ctx {
 };
 static_assert(offsetof(Ctx, budget_bitmap) <= 64 * 4, "the node loops' part of Ctx must fit one lane-striped register");
 __host__ __device__ inline int table_entry_shift(int KL) { return KL <= 30 ? 5 : (KL <= 62 ? 6 : 7); }  // 32 / 64 / 128 words per entry
+static_assert(kMaxKeyWords + 2 <= 128, "the longest key and the slot word fit a 128-word entry");
 
 struct ExpandArgs {  // per-round view, read from the device plan by every wavefront
     const uint32_t *in_base;

@@ -64,18 +64,28 @@ __global__ void k_kill_into_invalid(uint32_t E, const long long *src, const long
     if ((valid[u] || (root_rule && u == 0)) && !valid[dst[e]]) alive[e] = 0;
 }
 
+// The cover sets below are bitsets of CW = ceil(width / 32) words per state (per state and `ava` value for
+// adversarialTraverse2): value i of a variable is bit i % 32 of word i / 32. A set is full when its words 0 .. CW-2
+// are all ones and word CW-1 equals `last_full` (the low width - 32 (CW-1) bits; all ones when 32 divides width).
+__device__ inline bool cover_full(const uint32_t *c, int CW, uint32_t last_full) {
+    for (int w = 0; w + 1 < CW; w++)
+        if (c[w] != 0xffffffffu) return false;
+    return c[CW - 1] == last_full;
+}
+
 // adversarialTraverse: cover[v] = set of values of variable `var` on live edges into valid states.
 __global__ void k_adv_cover(uint32_t E, const long long *src, const long long *dst, const int32_t *values, int N, int var, int lb,
-                            const uint8_t *alive, const uint8_t *valid, uint32_t *cover) {
+                            int CW, const uint8_t *alive, const uint8_t *valid, uint32_t *cover) {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E || !alive[e] || !valid[dst[e]]) return;
-    atomicOr(&cover[src[e]], 1u << (values[(size_t)e * N + var] - lb));
+    const int i = values[(size_t)e * N + var] - lb;
+    atomicOr(&cover[(size_t)src[e] * CW + (i >> 5)], 1u << (i & 31));
 }
 // checkVertexOutEdge: a state stays valid only if every value of the variable is offered.
-__global__ void k_adv_check(uint32_t n_states, const uint32_t *cover, uint32_t full, uint8_t *valid, uint32_t *changed) {
+__global__ void k_adv_check(uint32_t n_states, const uint32_t *cover, int CW, uint32_t last_full, uint8_t *valid, uint32_t *changed) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_states) return;
-    if (valid[s] && cover[s] != full) {
+    if (valid[s] && !cover_full(cover + (size_t)s * CW, CW, last_full)) {
         valid[s] = 0;
         *changed = 1u;
     }
@@ -83,19 +93,20 @@ __global__ void k_adv_check(uint32_t n_states, const uint32_t *cover, uint32_t f
 
 // adversarialTraverse2: cover2[v][a] = set of values of `op` seen together with value a of `ava`.
 __global__ void k_adv2_cover(uint32_t E, const long long *src, const long long *dst, const int32_t *values, int N, int op, int ava,
-                             int lb_op, int lb_ava, int wa, const uint8_t *alive, const uint8_t *valid, uint32_t *cover2) {
+                             int lb_op, int lb_ava, int wa, int CW, const uint8_t *alive, const uint8_t *valid, uint32_t *cover2) {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E || !alive[e] || !valid[dst[e]]) return;
     const int32_t *row = values + (size_t)e * N;
-    atomicOr(&cover2[(size_t)src[e] * wa + (row[ava] - lb_ava)], 1u << (row[op] - lb_op));
+    const int i = row[op] - lb_op;
+    atomicOr(&cover2[((size_t)src[e] * wa + (row[ava] - lb_ava)) * CW + (i >> 5)], 1u << (i & 31));
 }
 // checkVertexOutEdge2, first half: the state is kept iff some value of `ava` sees every value of `op`.
-__global__ void k_adv2_check(uint32_t n_states, const uint32_t *cover2, int wa, uint32_t full, uint8_t *valid, uint8_t *node_ok,
-                             uint32_t *changed) {
+__global__ void k_adv2_check(uint32_t n_states, const uint32_t *cover2, int wa, int CW, uint32_t last_full, uint8_t *valid,
+                             uint8_t *node_ok, uint32_t *changed) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_states) return;
     bool any = false;
-    for (int a = 0; a < wa; a++) any |= cover2[(size_t)s * wa + a] == full;
+    for (int a = 0; a < wa; a++) any |= cover_full(cover2 + ((size_t)s * wa + a) * CW, CW, last_full);
     node_ok[s] = (uint8_t)any;
     if (!any && valid[s]) {
         valid[s] = 0;
@@ -104,12 +115,12 @@ __global__ void k_adv2_check(uint32_t n_states, const uint32_t *cover2, int wa, 
 }
 // second half: in a kept state the edges of the incomplete `ava` classes are removed (graph.cpp:231-241).
 __global__ void k_adv2_kill(uint32_t E, const long long *src, const long long *dst, const int32_t *values, int N, int ava, int lb_ava,
-                            int wa, uint32_t full, uint8_t *alive, const uint8_t *valid, const uint8_t *node_ok,
+                            int wa, int CW, uint32_t last_full, uint8_t *alive, const uint8_t *valid, const uint8_t *node_ok,
                             const uint32_t *cover2) {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E || !alive[e] || !valid[dst[e]]) return;
     const long long u = src[e];
-    if (node_ok[u] && cover2[(size_t)u * wa + (values[(size_t)e * N + ava] - lb_ava)] != full) alive[e] = 0;
+    if (node_ok[u] && !cover_full(cover2 + ((size_t)u * wa + (values[(size_t)e * N + ava] - lb_ava)) * CW, CW, last_full)) alive[e] = 0;
 }
 
 }  // namespace dev

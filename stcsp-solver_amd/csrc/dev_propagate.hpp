@@ -836,6 +836,7 @@ struct BranchOut {
 template <int DR>
 struct LeafOut {
     uint32_t kw;            // lane j: key word j = [next set tag, signature...]
+    uint32_t kw2;           // lane j: key word 64 + j (keys of more than 64 words: the KR = 2 kernels only)
     unsigned long long h;   // key hash
     int next_set, owner;
     uint32_t next_tag, new_expire;
@@ -848,9 +849,9 @@ struct CommitOut {
     int set;
     unsigned err;  // !ok: the MISC_ERROR code (the caller reports it)
 };
-template <int DR>
-__device__ CommitOut table_commit(const Ctx &c, int lane, int ro, uint32_t kw, unsigned long long h, uint32_t s0, uint32_t s1,
-                                  int set, uint32_t tag, const uint32_t (&vals)[DR]);
+template <int DR, int KR = 1>
+__device__ CommitOut table_commit(const Ctx &c, int lane, int ro, uint32_t kw, uint32_t kw2, unsigned long long h, uint32_t s0,
+                                  uint32_t s1, int set, uint32_t tag, const uint32_t (&vals)[DR]);
 template <int DR>
 __device__ unsigned emit_state_node(const Ctx &c, int lane, int ro, uint32_t *out_base, uint32_t out_cap, int parity,
                                     const CommitOut &co, uint32_t expire, const uint32_t (&blk)[DR], uint32_t seed);
@@ -1215,7 +1216,7 @@ __device__ int revise_batch(const Ctx &c, const Img<L> &G, WaveEnv<DR> &S, Dom<D
     return nb + __popcll(__ballot(noop));
 }
 
-template <int DR, int L, bool CS, bool LITE>
+template <int DR, int L, bool CS, bool LITE, int KR = 1>
 __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_vals, int *lds_stk, int *ldom, Dom<DR> &dom,
                             const NodeHdr &hd, int gw, WaveEnv<DR> &S, BranchOut &bo, LeafOut<DR> &lo) {
     const int set = hd.set;
@@ -1635,12 +1636,18 @@ __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_va
     const uint32_t next_tag = (uint32_t)P.u(c.o.sets + next_set * (int)(sizeof(SetDesc) / 4) + (int)(offsetof(SetDesc, tag) / 4));
     // (2) signature (:812-837): signature variables in queue order, then one sticky flag per until
     uint32_t new_expire = expire;
-    uint32_t kw = 0;  // lane j holds key word j: [tag, sig...]
+    uint32_t kw = 0, kw2 = 0;  // lane j holds key word j: [tag, sig...] (and word 64 + j in kw2 when KR == 2)
     {
         int sv = 0;
         if (lane >= 1 && lane <= c.n_sig) sv = P.v(c.o.sig_vars + lane - 1);
         uint32_t sd = dom.gather(sv);
         if (lane >= 1 && lane <= c.n_sig) kw = (uint32_t)(P.v(c.o.var_lb + sv) + __ffs((int)sd) - 1);
+        if constexpr (KR == 2) {
+            const bool s2 = lane + 64 <= c.n_sig;
+            const int sv2 = s2 ? P.v(c.o.sig_vars + lane + 63) : 0;
+            const uint32_t sd2 = dom.gather(sv2);
+            if (s2) kw2 = (uint32_t)(P.v(c.o.var_lb + sv2) + __ffs((int)sd2) - 1);
+        }
         for (int u = 0; u < c.n_until_cons; u++) {
             int y = P.u(c.o.until_y + u);
             uint32_t DY = dom.get(y);
@@ -1650,17 +1657,20 @@ __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_va
                 new_expire |= 1u << u;
             }
             if (lane == 1 + c.n_sig + u) kw = ex ? 1u : 0u;
+            if (KR == 2 && lane + 64 == 1 + c.n_sig + u) kw2 = ex ? 1u : 0u;
         }
         if (lane == 0) kw = next_tag;
     }
     // (3) owner shard = hash(key) % world
-    // lane j hashes key word j, the terms are XORed across the wavefront (key_hash, device_types.hpp)
+    // lane j hashes key word j (and 64 + j), the terms are XORed across the wavefront (key_hash, device_types.hpp)
     unsigned long long h;
     {
-        const unsigned long long t = lane < c.KL ? key_term(lane, kw) : 0ull;
+        unsigned long long t = lane < c.KL ? key_term(lane, kw) : 0ull;
+        if (KR == 2 && lane + 64 < c.KL) t ^= key_term(lane + 64, kw2);
         h = mix_final(kHashSeed ^ wave_xor64(t));
     }
     lo.kw = kw;
+    if constexpr (KR == 2) lo.kw2 = kw2;
     lo.h = h;
     lo.next_set = next_set;
     lo.next_tag = next_tag;

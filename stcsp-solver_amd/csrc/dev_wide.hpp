@@ -305,7 +305,7 @@ struct BranchOutWide {
     int bvar, mid;  // children: values at bit positions <= mid / > mid of variable bvar at point 0
 };
 
-template <int DR, int W, int L>
+template <int DR, int W, int L, int KR = 1>
 __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *lds_vals, int *lds_stk, int *ldom, Dom<DR> &dom, const NodeHdr &hd,
                                  int gw, WaveEnv<DR> &S, BranchOutWide &bo, LeafOut<DR> &lo) {
     const int set = hd.set;
@@ -459,12 +459,18 @@ __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *l
     }
     const uint32_t next_tag = (uint32_t)P.u(c.o.sets + next_set * (int)(sizeof(SetDesc) / 4) + (int)(offsetof(SetDesc, tag) / 4));
     uint32_t new_expire = expire;
-    uint32_t kw = 0;
+    uint32_t kw = 0, kw2 = 0;  // key words lane and 64 + lane (KR == 2 only), as in process_node
     {
         const bool sl = lane >= 1 && lane <= c.n_sig;
         const int sv = sl ? P.v(c.o.sig_vars + lane - 1) : 0;
         const int val = value_of(sv);
         if (sl) kw = (uint32_t)val;
+        if constexpr (KR == 2) {
+            const bool s2 = lane + 64 <= c.n_sig;
+            const int sv2 = s2 ? P.v(c.o.sig_vars + lane + 63) : 0;
+            const int val2 = value_of(sv2);
+            if (s2) kw2 = (uint32_t)val2;
+        }
         for (int u = 0; u < c.n_until_cons; u++) {
             const int y = P.u(c.o.until_y + u);
             const int vy = rfl(P.u(c.o.var_lb + y) + wload<W>(ldom, NK1, y).lowest());
@@ -474,15 +480,18 @@ __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *l
                 new_expire |= 1u << u;
             }
             if (lane == 1 + c.n_sig + u) kw = ex ? 1u : 0u;
+            if (KR == 2 && lane + 64 == 1 + c.n_sig + u) kw2 = ex ? 1u : 0u;
         }
         if (lane == 0) kw = next_tag;
     }
     unsigned long long h;
     {
-        const unsigned long long t = lane < c.KL ? key_term(lane, kw) : 0ull;
+        unsigned long long t = lane < c.KL ? key_term(lane, kw) : 0ull;
+        if (KR == 2 && lane + 64 < c.KL) t ^= key_term(lane + 64, kw2);
         h = mix_final(kHashSeed ^ wave_xor64(t));
     }
     lo.kw = kw;
+    if constexpr (KR == 2) lo.kw2 = kw2;
     lo.h = h;
     lo.next_set = next_set;
     lo.next_tag = next_tag;

@@ -16,6 +16,7 @@ namespace stcsp {
 
 constexpr int kRegions = 32;        // cursor shards per segment (spreads allocation atomics)
 constexpr int kMaxDomRegs = 4;      // N*K <= 64 * kMaxDomRegs words live in VGPRs, lane-striped
+constexpr int kMaxKeyWords = 126;   // state key [set tag, signature...]: two lane-striped registers, one 128-word table entry
 constexpr int kCompactSweepItems = 128;  // sets with more small items than this sweep over a compacted dirty list
 constexpr int kMaxLowVars = 6;      // lane-enumerated scope variables per revision (2^6 = 64; value bits packed 5 x 6 in a register)
 constexpr int kMaxScope = 64;       // scope variables per constraint (one lane each)

@@ -128,6 +128,10 @@ struct stcsp_engine {
     bool big = false;             // 1024-thread workgroups around one LDS copy of a LITE program: k_expand<.., true, .., true, true>
     int prefix_need = 0;          // image words that must be staged for the L = 2 kernels (0: not applicable)
     bool prefix_complete = false; // ... and they are: general program, everything but cons / tables in the staged prefix
+    // Keys of more than 64 words (set tag + signature): a lane holds key words j and 64 + j. Only the general, partly-staged
+    // kernels at DR = 4 get the second key register (k_expand<4, false, CS, false, false, W, 2>, k_commit<4, 2>), so the
+    // LITE / prefix kernels of the shipped programs (keys of at most 64 words) stay exactly as they are.
+    bool long_key() const { return ctx.KL > 64; }
     bool interpreted = false;     // some wavefront-revised constraint has no tuple bitmap (postfix interpreter: uniformly expensive nodes)
     bool wide_conditional = false;  // some conditional constraint spans more than kWideConditional tuples (the juggling family's `A == if B0 eq 1 then next B0 else if ...`)
     bool host_view_fresh = false;  // h_ctl / h_plan were read after the last device work (expand_local -> commit)
@@ -253,6 +257,7 @@ struct stcsp_engine {
             }
         if (const char *ev = getenv("STCSP_LITE")) lite = lite && atoi(ev) != 0;  // tuning switch
         if (mgr.W > 1) lite = false;  // (wide domains: every item is revised by dev_wide.hpp's bounds propagation)
+        if (long_key()) lite = false;
         // one contiguous image; every section starts on a 16-byte boundary
         std::vector<uint32_t> img;
         ImgOff o{};
@@ -431,7 +436,7 @@ struct stcsp_engine {
         const size_t scratch = (size_t)4 * wave_scratch_words(ctx.NK, ctx.stack_slots, lite, ctx.sib_depth) * sizeof(int);
         if (scratch > 160 * 1024) return fail(STCSP_E_UNSUPPORTED, "expression stack too deep for LDS");
         // stage the image in LDS when image + scratch leave room for >= 2 workgroups per CU
-        img_in_lds = (size_t)o.words * 4 + scratch <= 64 * 1024 && mgr.W == 1;  // (the wide kernels exist in the partly-staged form only)
+        img_in_lds = (size_t)o.words * 4 + scratch <= 64 * 1024 && mgr.W == 1 && !long_key();  // (the wide and long-key kernels exist in the partly-staged form only)
         if (const char *ev = getenv("STCSP_IMG_LDS")) img_in_lds = img_in_lds && atoi(ev) != 0;  // tuning switch
         ctx.stage_words = img_in_lds ? o.words : 0;
         lds_bytes = scratch + (size_t)ctx.stage_words * 4;
@@ -500,7 +505,7 @@ struct stcsp_engine {
                         ctx.stage_words = 0;
                 }
             }
-            prefix_complete = !lite && !img_in_lds && !big && !compact_sweeps && mgr.W == 1 && prefix_need > 0 && ctx.stage_words >= prefix_need &&
+            prefix_complete = !lite && !img_in_lds && !big && !compact_sweeps && mgr.W == 1 && !long_key() && prefix_need > 0 && ctx.stage_words >= prefix_need &&
                               !(getenv("STCSP_PREFIX_KERNEL") && atoi(getenv("STCSP_PREFIX_KERNEL")) == 0);
 #ifdef STCSP_PHASES
             if (DR == 4) prefix_complete = false;
@@ -560,7 +565,10 @@ struct stcsp_engine {
         if ((long long)N * K * W > 64 * kMaxDomRegs)
             return fail(STCSP_E_UNSUPPORTED, "N*K*W = %d*%d*%d exceeds the %d-word register-resident block", N, K, W, 64 * kMaxDomRegs);
         if (mgr.n_until_cons > 32) return fail(STCSP_E_UNSUPPORTED, "more than 32 until constraints");
-        if (1 + mgr.n_sig + mgr.n_until_cons > 64) return fail(STCSP_E_UNSUPPORTED, "signature longer than 63 words");
+        // the key [set tag, signature...] and the 64-bit slot word share one 128-word table entry (table_entry_shift)
+        if (1 + mgr.n_sig + mgr.n_until_cons > kMaxKeyWords)
+            return fail(STCSP_E_UNSUPPORTED, "signature of %d words (%d next variables, %d until flags): at most %d words (a state key of %d)",
+                        mgr.n_sig + mgr.n_until_cons, mgr.n_sig, mgr.n_until_cons, kMaxKeyWords - 1, kMaxKeyWords);
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(STCSP_E_DEVICE, "no HIP device available");
         device = opt.device;
@@ -625,7 +633,7 @@ struct stcsp_engine {
             }
         }
         DR = (N * K * W + 63) / 64;
-        if (DR == 3) DR = 4;
+        if (DR == 3 || ctx.KL > 64) DR = 4;  // (long keys: the KR = 2 kernels exist at DR = 4 only; the block needs no more than that)
         HIPCHK(d_arr_data.upload(mgr.array_data));
         ctx.arr_data = d_arr_data.p;
         rc = upload_program();
@@ -1152,6 +1160,13 @@ struct stcsp_engine {
     template <int DRT>
     const void *expand_fn() const {
         const void *fn = nullptr;
+        if constexpr (DRT == 4)
+            if (long_key()) {
+                if (mgr.W == 2) return (const void *)k_expand<4, false, false, false, false, 2, 2>;
+                if (mgr.W > 2) return (const void *)k_expand<4, false, false, false, false, 4, 2>;
+                if (compact_sweeps) return (const void *)k_expand<4, false, true, false, false, 1, 2>;
+                return (const void *)k_expand<4, false, false, false, false, 1, 2>;
+            }
         if (mgr.W == 2) return (const void *)k_expand<DRT, false, false, false, false, 2>;
         if (mgr.W > 2) return (const void *)k_expand<DRT, false, false, false, false, 4>;
 #ifdef STCSP_PHASES
@@ -1178,6 +1193,19 @@ struct stcsp_engine {
     template <int DRT>
     void launch_expand() {
         const Ctx *cp = (const Ctx *)d_ctx.p;
+        if constexpr (DRT == 4)
+            if (long_key()) {
+                const Plan *pp = (const Plan *)d_plan.p;
+                if (mgr.W == 2)
+                    hipLaunchKernelGGL((k_expand<4, false, false, false, false, 2, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+                else if (mgr.W > 2)
+                    hipLaunchKernelGGL((k_expand<4, false, false, false, false, 4, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+                else if (compact_sweeps)
+                    hipLaunchKernelGGL((k_expand<4, false, true, false, false, 1, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+                else
+                    hipLaunchKernelGGL((k_expand<4, false, false, false, false, 1, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+                return;
+            }
         if (mgr.W == 2) {
             hipLaunchKernelGGL((k_expand<DRT, false, false, false, false, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, (const Plan *)d_plan.p, launch_seq++, ctx.tab_gen);
             return;
@@ -1836,7 +1864,10 @@ struct stcsp_engine {
             switch (DR) {
                 case 1: hipLaunchKernelGGL((k_commit<1>), grid, block, 0, stream, ctx, ca); break;
                 case 2: hipLaunchKernelGGL((k_commit<2>), grid, block, 0, stream, ctx, ca); break;
-                default: hipLaunchKernelGGL((k_commit<4>), grid, block, 0, stream, ctx, ca); break;
+                default:
+                    if (long_key()) hipLaunchKernelGGL((k_commit<4, 2>), grid, block, 0, stream, ctx, ca);
+                    else hipLaunchKernelGGL((k_commit<4>), grid, block, 0, stream, ctx, ca);
+                    break;
             }
         }
         hipLaunchKernelGGL(k_close_segment, dim3(1), dim3(64), 0, stream, ctx);
@@ -1930,18 +1961,18 @@ struct stcsp_engine {
         const size_t E = exp_edges;
         const uint32_t S = n_states;
         auto width = [&](int v) { return mgr.ub[v] - mgr.lb[v] + 1; };
-        for (int v : {a1, op, ava})
-            if (v >= 0 && width(v) > 32)
-                return fail(STCSP_E_UNSUPPORTED, "device adversarial passes keep one 32-bit cover word per state: variable %d has %d values (use the host passes of stcsp_host.h)", v, width(v));
-        auto full_mask = [&](int v) { return width(v) >= 32 ? 0xffffffffu : ((1u << width(v)) - 1u); };
+        // cover sets of CW = ceil(width / 32) words (dev_postproc.hpp); widths are at most 128 (create() refuses wider)
+        auto cover_w = [&](int v) { return (width(v) + 31) / 32; };
+        auto last_full = [&](int v) { return width(v) % 32 == 0 ? 0xffffffffu : ((1u << (width(v) % 32)) - 1u); };
         const int wa = op >= 0 ? width(ava) : 0;
+        const int cw1 = a1 >= 0 ? cover_w(a1) : 1, cw2 = op >= 0 ? cover_w(op) : 1;
         if (d_pvalid.n < S) {
             const size_t cap = (size_t)S + S / 4 + 256;
             HIPCHK(d_pvalid.alloc(cap));
             HIPCHK(d_pfinal.alloc(cap));
             HIPCHK(d_pnodeok.alloc(cap));
         }
-        const size_t cover_words = (size_t)S * std::max(1, wa);
+        const size_t cover_words = (size_t)S * std::max(cw1, std::max(1, wa) * cw2);
         if (d_pcover.n < cover_words) HIPCHK(d_pcover.alloc(cover_words + cover_words / 4 + 256));
         if (d_palive.n < E + 1) HIPCHK(d_palive.alloc(E + E / 4 + 256));
         if (!d_post.p) HIPCHK(d_post.alloc(4));
@@ -1978,13 +2009,13 @@ struct stcsp_engine {
         int adver1 = -1, adver2 = -1;
         uint8_t root_valid = 0;
         if (a1 >= 0) {  // adversarialTraverse (src/graph.cpp:304-355)
-            const uint32_t full = full_mask(a1);
+            const uint32_t full = last_full(a1);
             int rc = fixpoint(rounds[1], [&] {
-                HIPCHK(hipMemsetAsync(d_pcover.p, 0, (size_t)S * sizeof(uint32_t), stream));
+                HIPCHK(hipMemsetAsync(d_pcover.p, 0, (size_t)S * cw1 * sizeof(uint32_t), stream));
                 if (E)
-                    hipLaunchKernelGGL(k_adv_cover, dim3(eb), dim3(256), 0, stream, (uint32_t)E, src, dst, val, N, a1, mgr.lb[a1],
+                    hipLaunchKernelGGL(k_adv_cover, dim3(eb), dim3(256), 0, stream, (uint32_t)E, src, dst, val, N, a1, mgr.lb[a1], cw1,
                                        (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_pcover.p);
-                hipLaunchKernelGGL(k_adv_check, dim3(sb), dim3(256), 0, stream, S, (const uint32_t *)d_pcover.p, full, d_pvalid.p, changed);
+                hipLaunchKernelGGL(k_adv_check, dim3(sb), dim3(256), 0, stream, S, (const uint32_t *)d_pcover.p, cw1, full, d_pvalid.p, changed);
                 return (int)STCSP_OK;
             });
             if (rc != STCSP_OK) return rc;
@@ -1994,15 +2025,16 @@ struct stcsp_engine {
             adver1 = root_valid;
         }
         if (op >= 0) {  // adversarialTraverse2 (src/graph.cpp:247-302)
-            const uint32_t full = full_mask(op);
+            const uint32_t full = last_full(op);
             int rc = fixpoint(rounds[2], [&] {
-                HIPCHK(hipMemsetAsync(d_pcover.p, 0, cover_words * sizeof(uint32_t), stream));
+                HIPCHK(hipMemsetAsync(d_pcover.p, 0, (size_t)S * wa * cw2 * sizeof(uint32_t), stream));
                 if (E)
                     hipLaunchKernelGGL(k_adv2_cover, dim3(eb), dim3(256), 0, stream, (uint32_t)E, src, dst, val, N, op, ava, mgr.lb[op], mgr.lb[ava],
-                                       wa, (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_pcover.p);
-                hipLaunchKernelGGL(k_adv2_check, dim3(sb), dim3(256), 0, stream, S, (const uint32_t *)d_pcover.p, wa, full, d_pvalid.p, d_pnodeok.p, changed);
+                                       wa, cw2, (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_pcover.p);
+                hipLaunchKernelGGL(k_adv2_check, dim3(sb), dim3(256), 0, stream, S, (const uint32_t *)d_pcover.p, wa, cw2, full, d_pvalid.p, d_pnodeok.p,
+                                   changed);
                 if (E)
-                    hipLaunchKernelGGL(k_adv2_kill, dim3(eb), dim3(256), 0, stream, (uint32_t)E, src, dst, val, N, ava, mgr.lb[ava], wa, full, d_palive.p,
+                    hipLaunchKernelGGL(k_adv2_kill, dim3(eb), dim3(256), 0, stream, (uint32_t)E, src, dst, val, N, ava, mgr.lb[ava], wa, cw2, full, d_palive.p,
                                        (const uint8_t *)d_pvalid.p, (const uint8_t *)d_pnodeok.p, (const uint32_t *)d_pcover.p);
                 return (int)STCSP_OK;
             });
