@@ -113,6 +113,8 @@ typedef struct stcsp_options {
 #define STCSP_F_STEPPED 8        /* run the sharded pipeline (leaves emit successor candidates, the
                                     owner commits them: begin/expand_local/outbox/commit/finish) even
                                     with world == 1 -- measures/tests that pipeline on a single GPU   */
+#define STCSP_F_INTERVAL_DOMAINS 16 /* hold every variable as an interval (lb, ub per time point) instead of
+                                    a bitset: any width in [INT_MIN, INT_MAX]; 2*N*K <= 256 block words */
 
 typedef struct stcsp_counters {
     int64_t search_nodes; /* node expansions = propagation-to-fixpoint + classification; the

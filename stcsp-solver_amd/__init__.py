@@ -87,6 +87,7 @@ F_KEEP_RAW_EDGES = 1
 F_NO_EXPORT = 2
 F_PROFILE = 4
 F_STEPPED = 8
+F_INTERVAL_DOMAINS = 16  # every variable held as an interval (any width in [INT_MIN, INT_MAX]); include/stcsp_engine.h
 GID_SHIFT = 40
 
 ENGINE_SYMBOLS = [

@@ -49,6 +49,28 @@ static bool tree_eq(const Tree *a, const Tree *b) {
     if (a->token != b->token || a->num != b->num || a->var != b->var) return false;
     return tree_eq(a->left, b->left) && tree_eq(a->right, b->right);
 }
+// Interval domains: is the point constraint v == e (or e == v) with v not in e and no array in the tree? Returns v's scope position
+// and sets `e`, else -1. (Every aux variable the frontend creates is defined this way: frontend.cpp add_var_eq_node.)
+static int defining_form(const HostCon &c, const Tree *&e) {
+    const Tree *t = c.root;
+    if (!t || t->token != STCSP_T_EQ_CON || !t->left || !t->right || tree_has_arr(t)) return -1;
+    for (int side = 0; side < 2; side++) {
+        const Tree *v = side == 0 ? t->left : t->right, *rest = side == 0 ? t->right : t->left;
+        if (v->token != STCSP_T_VAR) continue;
+        std::vector<int> sc;
+        collect_scope(rest, sc);
+        bool inside = false;
+        for (int x : sc) inside = inside || x == v->var;
+        if (inside) continue;
+        for (size_t j = 0; j < c.scope.size(); j++)
+            if (c.scope[j] == v->var) {
+                e = rest;
+                return (int)j;
+            }
+    }
+    return -1;
+}
+
 static bool set_eq(const HostSet &a, const HostSet &b) {  // constraintQueueEq (:564-576)
     if (a.cons.size() != b.cons.size()) return false;
     for (size_t i = 0; i < a.cons.size(); i++)
@@ -213,6 +235,7 @@ int SetManager::init(const stcsp_problem *p, bool sharded_tags) {
         long long widest = 1;
         for (int v = 0; v < N; v++) widest = std::max(widest, (long long)ub[v] - (long long)lb[v] + 1);
         W = widest <= 32 ? 1 : (widest <= 64 ? 2 : (widest <= 128 ? 4 : 0));
+        if (intervals) W = 2;
     }
     array_off.assign(1, 0);
     for (int a = 0; a < p->n_arrays; a++) {
@@ -328,6 +351,10 @@ int SetManager::pretranslate(long long max_tuples, int max_sets, long long max_t
         long long full = 1, tuples = 1;
         for (size_t k = 0; k < fv.size(); k++) {
             const int v = fv[k];
+            if ((long long)ub[v] - lb[v] + 1 > std::max<long long>(max_tuples, 4096)) {  // (interval domains: no value-by-value scan of a wide variable)
+                tuples = max_tuples + 1;
+                break;
+            }
             full *= (long long)ub[v] - lb[v] + 1;
             if (full > kDirectTransMax) full = kDirectTransMax + 1;
             for (int x = lb[v]; x <= ub[v]; x++) {
@@ -622,7 +649,9 @@ void SetManager::build_entry(const HostCon &c, TableEntry &e) {
     long long product = 1;
     const long long limit = device_tabulation ? kBitmapMaxBitsDevice : kBitmapMaxBits;
     for (int j = 0; j < s; j++) {
-        size[j] = ub[c.scope[j]] - lb[c.scope[j]] + 1;
+        const long long w = (long long)ub[c.scope[j]] - lb[c.scope[j]] + 1;  // (up to 2^32 with interval domains)
+        if (w > limit) return;
+        size[j] = (int)w;
         product *= size[j];
         if (product > limit) return;
     }
@@ -815,10 +844,10 @@ int SetManager::compile(FlatProgram &out) {
         sd.first_off = (int32_t)out.firstvars.size();
         out.firstvars.insert(out.firstvars.end(), s.first_vars.begin(), s.first_vars.end());
         {
-            int32_t st = 1;  // mixed radix over the captured variables, first one fastest
+            long long st = 1;  // mixed radix over the captured variables, first one fastest (only used while the product is a table's)
             for (int v : s.first_vars) {
-                out.fstrides.push_back(st);
-                st *= ub[v] - lb[v] + 1;
+                out.fstrides.push_back((int32_t)st);
+                st = std::min<long long>(st * ((long long)ub[v] - lb[v] + 1), kDirectTransMax + 1);
             }
         }
         long long direct_tuples = 1;
@@ -911,7 +940,10 @@ int SetManager::compile(FlatProgram &out) {
             cd.y = c.y;
             cd.until_ordinal = c.until_ordinal;
             cd.code_off = (int32_t)out.code.size();
+            int defpos = -1;  // interval domains: scope position of v when the constraint is v == e
             if (c.type == CT_POINT) {
+                const Tree *e = nullptr;
+                if (intervals) defpos = defining_form(c, e);
                 bool guards = tree_has_arr(c.root);
                 cd.uses_valid = guards;
                 // identical constraints (the same constraint in two sets) share their program
@@ -928,6 +960,16 @@ int SetManager::compile(FlatProgram &out) {
                     out.code.push_back(OP_END);
                     if (max_depth > out.max_stack) out.max_stack = max_depth;
                     cd.code_len = (int32_t)out.code.size() - cd.code_off;
+                    if (defpos >= 0) {  // [length of e's program, e's program] right after the constraint's (device: dev_wide.hpp)
+                        const size_t at = out.code.size();
+                        out.code.push_back(0);
+                        depth = max_depth = mask_depth = 0;
+                        rc = compile_expr(e, c.scope, false, out.code, depth, max_depth, mask_depth);
+                        if (rc != STCSP_OK) return rc;
+                        out.code.push_back(OP_END);
+                        if (max_depth > out.max_stack) out.max_stack = max_depth;
+                        out.code[at] = (int32_t)(out.code.size() - at - 1);
+                    }
                     code_cache.emplace(key, std::make_pair(cd.code_off, cd.code_len));
                 }
             } else {
@@ -966,8 +1008,8 @@ int SetManager::compile(FlatProgram &out) {
                     it.arity = 2;
                     it.idx[0] = p * N + c.x;
                     it.idx[1] = (p + 1) * N + c.y;
-                    it.aux = lb[c.x] - lb[c.y];
-                    if (W > 1) it.aux = std::max(-128, std::min(128, it.aux));  // (a shift beyond the widest domain empties both sides anyway)
+                    it.aux = (int32_t)std::max(-128ll, std::min(128ll, (long long)lb[c.x] - lb[c.y]));
+                    if (W == 1) it.aux = lb[c.x] - lb[c.y];  // (a shift beyond the widest domain empties both sides anyway)
                     (W > 1 ? wave_items : small_items).push_back(it);
                 }
             } else if (c.type == CT_UNTIL) {
@@ -1044,6 +1086,7 @@ int SetManager::compile(FlatProgram &out) {
                         it.toff = cd.code_off;
                         it.r1 = cd.uses_valid;
                         it.r2 = cd.code_len;
+                        it.aux = defpos + 1;
                     }
                     it.point = p;
                     it.con = con_abs;

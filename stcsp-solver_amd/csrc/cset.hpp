@@ -114,6 +114,10 @@ public:
     // Programs compiled for W > 1 have no lane-revised items and no eager arcs: X == next Y, until and point constraints are
     // all wavefront-revised items (device: dev_wide.hpp). 0: some variable is wider than 128 values (no bitset path).
     int W = 1;
+    // STCSP_F_INTERVAL_DOMAINS: every variable is an interval, word (0, p, v) = lb and word (1, p, v) = ub (dev_interval.hpp), so
+    // W = 2 chunks whatever the widths; programs are compiled as for W > 1, and a point constraint in the defining form v == e
+    // (v not in e, no array) carries 1 + v's scope position in ItemDesc::aux, its program followed by [length of e's program, e's program].
+    bool intervals = false;
     bool device_tabulation = false;  // products in (kBitmapMaxBits, kBitmapMaxBitsDevice] become bitmaps filled in by the device
     void store_tabulated(const std::vector<int32_t> &key, const uint32_t *words, size_t n, long long product);
 

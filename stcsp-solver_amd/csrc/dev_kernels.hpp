@@ -129,7 +129,7 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
     };
     for (int step = 1;; step++) {
         BranchOut bo;     // outputs of this expansion only (nothing of them is carried round the loop)
-        BranchOutWide bow;  // (W > 1: dev_wide.hpp)
+        BranchOutWide bow;  // (W > 1 and W = kWIntervals: dev_wide.hpp)
         LeafOut<DR> lo;
         sd = rfl(sd);
         // The header is wave-uniform, but values carried round a loop whose exits the compiler cannot
@@ -145,7 +145,7 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
         int oc;
         {
             const Ctx cn = ctx_from(hot);
-            if constexpr (W > 1)
+            if constexpr (W != 1)
                 oc = process_node_wide<DR, W, L, KR>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bow, lo);
             else
                 oc = process_node<DR, L, CS, LITE, KR>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
@@ -210,10 +210,14 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
     }
         if (oc == OC_FAIL) STCSP_PATH_END();
         if (oc == OC_BRANCH) {
-            const int bvar = W > 1 ? bow.bvar : bo.bvar;
+            const int bvar = W != 1 ? bow.bvar : bo.bvar;
             const uint32_t cw2 = (uint32_t)hd.set | ((uint32_t)(bvar + 1) << kSetBits);
             Dom<DR> child = dom;
-            if constexpr (W > 1) {
+            if constexpr (W == kWIntervals) {
+                // [lb, mid] stays, [mid + 1, ub] is the upper child: word (0, 0, bvar) = lb, word (1, 0, bvar) = ub
+                child.set(bvar, (uint32_t)(bow.mid + 1), lane);
+                dom.set(c.N * c.K + bvar, (uint32_t)bow.mid, lane);
+            } else if constexpr (W > 1) {
                 // the bisection point falls into one chunk of the variable: chunks below it go to the lower child whole, those above to the upper one
                 const int NK1 = c.N * c.K;
 #pragma unroll

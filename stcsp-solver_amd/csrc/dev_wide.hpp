@@ -14,7 +14,7 @@
 // items and no eager arcs (cset.cpp compile): X == next Y, until and point constraints are all revised one at a time by the
 // whole wavefront. Sound pruning + exact leaves => the same automaton as the reference.
 #pragma once
-#include "dev_propagate.hpp"
+#include "dev_interval.hpp"
 namespace stcsp {
 namespace dev {
 
@@ -302,8 +302,10 @@ __device__ bool revise_next_wide(const Ctx &c, int wx, int wy, int sh, int lane,
 }
 
 struct BranchOutWide {
-    int bvar, mid;  // children: values at bit positions <= mid / > mid of variable bvar at point 0
+    int bvar, mid;  // children: values at bit positions <= mid / > mid of variable bvar at point 0 (W = kWIntervals: values <= mid / > mid)
 };
+
+// W = kWIntervals: interval domains (dev_interval.hpp), the same node loop with bounds in place of bitsets
 
 template <int DR, int W, int L, int KR = 1>
 __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *lds_vals, int *lds_stk, int *ldom, Dom<DR> &dom, const NodeHdr &hd,
@@ -311,6 +313,7 @@ __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *l
     const int set = hd.set;
     const uint32_t seed = hd.seed, expire = hd.expire;
     const int NK1 = c.N * c.K;
+    constexpr bool IV = W == kWIntervals;
     if (set != S.set) load_env<DR, L>(c, P, set, lane, S);
     uint32_t dirtyw = 0;
     if (lane < S.iw) {
@@ -349,7 +352,10 @@ __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *l
         if (itype == IT_NEXT) {
             bool chx = false, chy = false;
             const int wx = STCSP_ID(idx[0]), wy = STCSP_ID(idx[1]);
-            consistent = revise_next_wide<W>(c, wx, wy, STCSP_ID(aux), lane, ldom, chx, chy);
+            if constexpr (IV)
+                consistent = revise_next_iv(c, wx, wy, lane, ldom, chx, chy);
+            else
+                consistent = revise_next_wide<W>(c, wx, wy, STCSP_ID(aux), lane, ldom, chx, chy);
             S.n_revs++;
             if (consistent) {
                 if (chx) mark_word(wx);
@@ -360,7 +366,10 @@ __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *l
             // X until Y (enforceUntilConsistency, :598-614): a check at point 0, never a pruning
             const int x = STCSP_ID(idx[0]), y = STCSP_ID(idx[1]), ord = STCSP_ID(aux);
             S.n_revs++;
-            if (!((expire >> ord) & 1u)) {
+            if constexpr (IV) {
+                if (!((expire >> ord) & 1u) && ldom[x] == ldom[NK1 + x] && ldom[y] == ldom[NK1 + y])
+                    if (rfl(ldom[x]) != 1 && rfl(ldom[y]) != 1) consistent = false;
+            } else if (!((expire >> ord) & 1u)) {
                 const WDom<W> DX = wload<W>(ldom, NK1, x), DY = wload<W>(ldom, NK1, y);
                 if (DX.count() == 1 && DY.count() == 1) {
                     const int vx = P.u(c.o.var_lb + x) + DX.lowest(), vy = P.u(c.o.var_lb + y) + DY.lowest();
@@ -378,7 +387,16 @@ __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *l
             C.uses_valid = STCSP_ID(r1);
             C.code_len = STCSP_ID(r2);
             unsigned long long changedm = 0;
-            consistent = revise_bounds_wide<W, L>(c, P, C, ipoint, lane, ldom, lds_vals, lds_stk, changedm, S.n_evals, S.n_skipped);
+            if constexpr (IV) {
+                // aux = 1 + scope position of v for a constraint v == e; the constraint's program is then followed by the length of
+                // e's program and e's program (cset.cpp compile)
+                const int defpos = STCSP_ID(aux) - 1;
+                const int e_len = defpos >= 0 ? P.v(c.o.code + C.code_off + C.code_len) : 0;
+                consistent = revise_bounds_iv<L>(c, P, C, defpos, C.code_off + C.code_len + 1, e_len, ipoint, lane, ldom, lds_vals, lds_stk, changedm,
+                                                 S.n_evals, S.n_skipped);
+            } else {
+                consistent = revise_bounds_wide<W, L>(c, P, C, ipoint, lane, ldom, lds_vals, lds_stk, changedm, S.n_evals, S.n_skipped);
+            }
             S.n_revs++;
             S.n_wave_revs++;
             for (unsigned long long m = changedm; consistent && m; m &= m - 1) {
@@ -407,11 +425,21 @@ __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *l
     int bvar = -1;
     for (int v0 = 0; v0 < c.N && bvar < 0; v0 += 64) {
         const int v = v0 + lane;
-        const bool open = v < c.N && wload<W>(ldom, NK1, v < c.N ? v : 0).count() > 1;
+        bool open;
+        if constexpr (IV)
+            open = v < c.N && ldom[v < c.N ? v : 0] < ldom[NK1 + (v < c.N ? v : 0)];
+        else
+            open = v < c.N && wload<W>(ldom, NK1, v < c.N ? v : 0).count() > 1;
         const unsigned long long m = __ballot(open);
         if (m) bvar = v0 + __ffsll((long long)m) - 1;
     }
     if (bvar >= 0) {
+        if constexpr (IV) {  // mid = lb + (ub - lb) / 2 in 64 bits (the reference's int arithmetic overflows beyond 2^31)
+            const int lo_ = rfl(ldom[bvar]), hi_ = rfl(ldom[NK1 + bvar]);
+            bo.bvar = bvar;
+            bo.mid = lo_ + (int)(((long long)hi_ - lo_) / 2);
+            return OC_BRANCH;
+        }
         // variableSplitLower/Upper (variable.cpp:52-67): [lb, lb + (ub - lb) / 2] and the rest
         const WDom<W> D = wload<W>(ldom, NK1, bvar);
         const int lo_ = rfl(D.lowest()), hi_ = rfl(D.highest());
@@ -421,12 +449,19 @@ __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *l
     }
     // ---- leaf (solveralgorithm.cpp:739-910): every variable has one time-0 value
     auto value_of = [&](int v) -> int {  // per lane: time-0 value of variable v
-        return P.v(c.o.var_lb + v) + wload<W>(ldom, NK1, v).lowest();
+        if constexpr (IV)
+            return ldom[v];
+        else
+            return P.v(c.o.var_lb + v) + wload<W>(ldom, NK1, v).lowest();
     };
     int next_set = set;
     if (!S.self_loop) {
         const int fv = lane < S.nfirst ? P.v(c.o.firstvars + S.first_off + lane) : 0;
-        const int fbit = wload<W>(ldom, NK1, fv).lowest();
+        int fbit;
+        if constexpr (IV)
+            fbit = ldom[fv] - P.v(c.o.var_lb + fv);
+        else
+            fbit = wload<W>(ldom, NK1, fv).lowest();
         const int fval = lane < S.nfirst ? P.v(c.o.var_lb + fv) + fbit : 0;
         next_set = -1;
         if (S.trans_count < 0) {
@@ -473,7 +508,11 @@ __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *l
         }
         for (int u = 0; u < c.n_until_cons; u++) {
             const int y = P.u(c.o.until_y + u);
-            const int vy = rfl(P.u(c.o.var_lb + y) + wload<W>(ldom, NK1, y).lowest());
+            int vy;
+            if constexpr (IV)
+                vy = rfl(ldom[y]);
+            else
+                vy = rfl(P.u(c.o.var_lb + y) + wload<W>(ldom, NK1, y).lowest());
             bool ex = (expire >> u) & 1u;
             if (!ex && vy == 1) {
                 ex = true;

@@ -58,6 +58,8 @@ using namespace stcsp;
 using namespace stcsp::dev;
 
 namespace {
+// widest adversarial variable the device post-processing passes take (cover sets of kPostMaxWidth / 32 words per state)
+constexpr long long kPostMaxWidth = 4096;
 // ------------------------------------------------------------------ host side
 template <typename T>
 struct DevBuf {
@@ -232,8 +234,9 @@ struct stcsp_engine {
         if (e_ != hipSuccess) return fail(STCSP_E_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 
-    // chunk c (values lb + 32 c ...) of variable v's initial domain [lb, ub]
+    // chunk c (values lb + 32 c ...) of variable v's initial domain [lb, ub]; interval domains: chunk 0 = lb, chunk 1 = ub
     uint32_t init_chunk(int v, int c) const {
+        if (mgr.intervals) return (uint32_t)(c == 0 ? mgr.lb[v] : mgr.ub[v]);
         const long long left = (long long)mgr.ub[v] - (long long)mgr.lb[v] + 1 - 32ll * c;
         return left >= 32 ? 0xffffffffu : (left > 0 ? ((1u << left) - 1u) : 0u);
     }
@@ -550,18 +553,25 @@ struct stcsp_engine {
                 fault_left = c2 == std::string::npos ? 1 : std::max(1, atoi(f.c_str() + c2 + 1));
             }
         }
+        // STCSP_INTERVAL_DOMAINS=1 sets STCSP_F_INTERVAL_DOMAINS (like the other STCSP_* knobs: drivers that pass no flags)
+        if (const char *ev = getenv("STCSP_INTERVAL_DOMAINS")) if (atoi(ev) == 1) opt.flags |= STCSP_F_INTERVAL_DOMAINS;
+        mgr.intervals = (opt.flags & STCSP_F_INTERVAL_DOMAINS) != 0;
         int rc = mgr.init(p, sharded);
         if (rc != STCSP_OK) return fail(rc, "%s", mgr.error.c_str());
         mgr.device_tabulation = !(getenv("STCSP_DEVICE_TABULATE") && atoi(getenv("STCSP_DEVICE_TABULATE")) == 0);
         const int N = mgr.N, K = mgr.K;
         // domains of up to 32 values take one bitset word per (variable, time point), up to 64 two, up to 128 four (W; one W
         // for the whole block: dev_wide.hpp); the block of N*K*W words lives in at most kMaxDomRegs registers per lane
-        for (int v = 0; v < N; v++) {
+        // (STCSP_F_INTERVAL_DOMAINS: two words, lb and ub, per variable and time point whatever the width -- dev_interval.hpp)
+        for (int v = 0; v < N && !mgr.intervals; v++) {
             long long width = (long long)mgr.ub[v] - (long long)mgr.lb[v] + 1;
             if (width > 128)
-                return fail(STCSP_E_UNSUPPORTED, "variable %d has %lld values; this engine packs at most 128 (four bitset words) per variable and time point", v, width);
+                return fail(STCSP_E_UNSUPPORTED, "variable %d has %lld values; this engine packs at most 128 (four bitset words) per variable and time point "
+                            "(STCSP_F_INTERVAL_DOMAINS takes any width)", v, width);
         }
         const int W = mgr.W;
+        if (mgr.intervals && 2ll * N * K > 64 * kMaxDomRegs)
+            return fail(STCSP_E_UNSUPPORTED, "interval domains: 2*N*K = 2*%d*%d exceeds the block limit of %d words (64 * kMaxDomRegs)", N, K, 64 * kMaxDomRegs);
         if ((long long)N * K * W > 64 * kMaxDomRegs)
             return fail(STCSP_E_UNSUPPORTED, "N*K*W = %d*%d*%d exceeds the %d-word register-resident block", N, K, W, 64 * kMaxDomRegs);
         if (mgr.n_until_cons > 32) return fail(STCSP_E_UNSUPPORTED, "more than 32 until constraints");
@@ -1162,11 +1172,13 @@ struct stcsp_engine {
         const void *fn = nullptr;
         if constexpr (DRT == 4)
             if (long_key()) {
+                if (mgr.intervals) return (const void *)k_expand<4, false, false, false, false, kWIntervals, 2>;
                 if (mgr.W == 2) return (const void *)k_expand<4, false, false, false, false, 2, 2>;
                 if (mgr.W > 2) return (const void *)k_expand<4, false, false, false, false, 4, 2>;
                 if (compact_sweeps) return (const void *)k_expand<4, false, true, false, false, 1, 2>;
                 return (const void *)k_expand<4, false, false, false, false, 1, 2>;
             }
+        if (mgr.intervals) return (const void *)k_expand<DRT, false, false, false, false, kWIntervals>;
         if (mgr.W == 2) return (const void *)k_expand<DRT, false, false, false, false, 2>;
         if (mgr.W > 2) return (const void *)k_expand<DRT, false, false, false, false, 4>;
 #ifdef STCSP_PHASES
@@ -1196,7 +1208,9 @@ struct stcsp_engine {
         if constexpr (DRT == 4)
             if (long_key()) {
                 const Plan *pp = (const Plan *)d_plan.p;
-                if (mgr.W == 2)
+                if (mgr.intervals)
+                    hipLaunchKernelGGL((k_expand<4, false, false, false, false, kWIntervals, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+                else if (mgr.W == 2)
                     hipLaunchKernelGGL((k_expand<4, false, false, false, false, 2, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
                 else if (mgr.W > 2)
                     hipLaunchKernelGGL((k_expand<4, false, false, false, false, 4, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
@@ -1206,6 +1220,10 @@ struct stcsp_engine {
                     hipLaunchKernelGGL((k_expand<4, false, false, false, false, 1, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
                 return;
             }
+        if (mgr.intervals) {
+            hipLaunchKernelGGL((k_expand<DRT, false, false, false, false, kWIntervals>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, (const Plan *)d_plan.p, launch_seq++, ctx.tab_gen);
+            return;
+        }
         if (mgr.W == 2) {
             hipLaunchKernelGGL((k_expand<DRT, false, false, false, false, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, (const Plan *)d_plan.p, launch_seq++, ctx.tab_gen);
             return;
@@ -1300,6 +1318,7 @@ struct stcsp_engine {
     }
     int propagate(int set, uint32_t expire, uint32_t *blocks, int64_t count, int32_t *outcome, int64_t *skipped) {
         if (sharded) return fail(STCSP_E_STATE, "propagate is for unsharded engines");
+        if (mgr.intervals) return fail(STCSP_E_UNSUPPORTED, "propagate: the node-level seam takes one-word blocks (no interval domains)");
         if (mgr.W > 1) return fail(STCSP_E_UNSUPPORTED, "propagate: the node-level seam takes one-word blocks (every domain <= 32 values)");
         if (set < 0 || set >= (int)prog.sets.size() || count < 0 || count > (1 << 24) || !blocks || !outcome)
             return fail(STCSP_E_INVALID, "propagate: bad arguments (set %d of %zu, count %lld)", set, prog.sets.size(), (long long)count);
@@ -1960,11 +1979,16 @@ struct stcsp_engine {
         auto t0 = std::chrono::steady_clock::now();
         const size_t E = exp_edges;
         const uint32_t S = n_states;
-        auto width = [&](int v) { return mgr.ub[v] - mgr.lb[v] + 1; };
-        // cover sets of CW = ceil(width / 32) words (dev_postproc.hpp); widths are at most 128 (create() refuses wider)
-        auto cover_w = [&](int v) { return (width(v) + 31) / 32; };
+        auto width = [&](int v) { return (long long)mgr.ub[v] - (long long)mgr.lb[v] + 1; };
+        // cover sets of CW = ceil(width / 32) words (dev_postproc.hpp); without interval domains widths are at most 128 (create()
+        // refuses wider), with them the adversarial variables may have at most kPostMaxWidth values
+        for (int v : {a1, op, op >= 0 ? ava : -1})
+            if (v >= 0 && width(v) > kPostMaxWidth)
+                return fail(STCSP_E_UNSUPPORTED, "postprocess: variable %d has %lld values; the device adversarial passes take at most %lld (%lld cover words per state)",
+                            v, width(v), kPostMaxWidth, kPostMaxWidth / 32);
+        auto cover_w = [&](int v) { return (int)((width(v) + 31) / 32); };
         auto last_full = [&](int v) { return width(v) % 32 == 0 ? 0xffffffffu : ((1u << (width(v) % 32)) - 1u); };
-        const int wa = op >= 0 ? width(ava) : 0;
+        const int wa = op >= 0 ? (int)width(ava) : 0;
         const int cw1 = a1 >= 0 ? cover_w(a1) : 1, cw2 = op >= 0 ? cover_w(op) : 1;
         if (d_pvalid.n < S) {
             const size_t cap = (size_t)S + S / 4 + 256;

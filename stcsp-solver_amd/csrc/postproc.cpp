@@ -185,7 +185,7 @@ struct Automaton {
 
     // checkVertexOutEdge (graph.cpp:167-189)
     bool covers_all_values(int64_t v, int i) const {
-        for (int c = var_lb[i]; c <= var_ub[i]; c++) {
+        for (long long c = var_lb[i]; c <= var_ub[i]; c++) {  // (64-bit: a bound may be INT_MAX)
             bool exist = false;
             for (int64_t k = out_off[v]; k < out_off[v + 1] && !exist; k++) {
                 int64_t e = out_edge[k];
@@ -221,7 +221,7 @@ struct Automaton {
     // checkVertexOutEdge2 (graph.cpp:193-244)
     bool simultaneous_check(int64_t v, int op, int ava) {
         std::map<int, std::set<int>> seen;
-        size_t op_nums = (size_t)(var_ub[op] - var_lb[op] + 1);
+        size_t op_nums = (size_t)((long long)var_ub[op] - var_lb[op] + 1);
         bool node_valid = false;
         for (int64_t k = out_off[v]; k < out_off[v + 1]; k++) {
             int64_t e = out_edge[k];

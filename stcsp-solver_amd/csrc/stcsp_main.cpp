@@ -2,7 +2,7 @@
 // (src/stcsp.y:180-219 main, src/solver.cpp:195-359 solve): same flags, same stdout contract,
 // same solutions.dot. The search itself runs on the MI355X engine behind the C-ABI.
 //
-//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] input.csp
+//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] input.csp
 //
 // --binary=<file> (not in the reference) additionally writes the printed automaton in the compact
 // binary form of include/stcsp_host.h.
@@ -10,6 +10,9 @@
 // engines -- one per GPU of the node, round robin when there are fewer GPUs than shards -- driven by N host threads through
 // stcsp_engine_solve_sharded() and the in-process transport (include/stcsp_sharded.h: records move between the GPUs with
 // hipMemcpyPeerAsync); the shards' automata are merged and post-processed on the host.
+// --intervals (not in the reference) holds every variable as an interval, like the reference does (STCSP_F_INTERVAL_DOMAINS):
+// domains of any width in [INT_MIN, INT_MAX], where the default bitset domains take at most 128 values. Works with --shards=N.
+// When an -a / -z variable is wider than the device post-processing passes take, the host passes run instead.
 //
 // Options must be glued to their value (-k3, not -k 3): like the reference, the first argument
 // that does not start with '-' is the input file (stcsp.y:199-206).
@@ -36,7 +39,7 @@ static double cpu_time() {  // cpuTime (util.cpp:149-155)
 }
 
 struct Flags {
-    bool print_solution = false, testing = false, adv1 = false, adv2 = false;
+    bool print_solution = false, testing = false, adv1 = false, adv2 = false, intervals = false;
     int prefix_k = 2, time_limit = 0, shards = 1;
     const char *file = nullptr;
     const char *binary = nullptr;
@@ -61,6 +64,7 @@ static int run_once(const Flags &f, bool print_line, double *total) {
     stcsp_options opt;
     memset(&opt, 0, sizeof opt);
     opt.world = 1;
+    opt.flags = f.intervals ? STCSP_F_INTERVAL_DOMAINS : 0;
     opt.time_limit_s = f.time_limit;  // -m: the reference exit(0)s silently on SIGALRM (solver.cpp:190-193)
     stcsp_engine *eng = nullptr;
     rc = stcsp_engine_create(p, &opt, &eng);
@@ -85,13 +89,18 @@ static int run_once(const Flags &f, bool print_line, double *total) {
     stcsp_post_options po = {f.adv1 ? 5 : -1, f.adv2 ? 5 : -1, f.adv2 ? 6 : -1, 0};
     stcsp_post_result post;
     rc = stcsp_engine_postprocess(eng, &po, &post);
-    if (rc != STCSP_OK) {
+    if (rc == STCSP_E_UNSUPPORTED) {  // an adversarial variable wider than the device passes take: the host passes
+        stcsp_automaton_traverse(a);
+        if (f.adv1) printf("adver1: %d; ", stcsp_automaton_adversarial(a, 5));
+        if (f.adv2) printf("adver2: %d\n", stcsp_automaton_adversarial2(a, 5, 6));
+    } else if (rc != STCSP_OK) {
         fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
         return 1;
+    } else {
+        stcsp_automaton_import_flags(a, post.state_valid, post.state_final, post.edge_alive);
+        if (f.adv1) printf("adver1: %d; ", post.adver1);
+        if (f.adv2) printf("adver2: %d\n", post.adver2);
     }
-    stcsp_automaton_import_flags(a, post.state_valid, post.state_final, post.edge_alive);
-    if (f.adv1) printf("adver1: %d; ", post.adver1);
-    if (f.adv2) printf("adver2: %d\n", post.adver2);
     if (f.print_solution || f.binary) stcsp_automaton_order_by_label(a);  // reproducible files whatever the GPU's scheduling
     stcsp_automaton_renumber(a);
     double proc_time = cpu_time() - t_proc;
@@ -137,6 +146,7 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
         opt.device = r % ndev;
         opt.rank = r;
         opt.world = world;
+        opt.flags = f.intervals ? STCSP_F_INTERVAL_DOMAINS : 0;
         opt.time_limit_s = f.time_limit;
         if (stcsp_engine_create(p, &opt, &eng[(size_t)r]) != STCSP_OK) {
             fprintf(stderr, "%s\n", stcsp_engine_last_error(nullptr));
@@ -213,6 +223,10 @@ int main(int argc, char **argv) {
         }
         if (strncmp(a, "--binary=", 9) == 0) {
             f.binary = a + 9;
+            continue;
+        }
+        if (strcmp(a, "--intervals") == 0) {
+            f.intervals = true;
             continue;
         }
         if (strncmp(a, "--shards=", 9) == 0) {
