@@ -145,7 +145,14 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
         int oc;
         {
             const Ctx cn = ctx_from(hot);
-            if constexpr (W != 1)
+            if constexpr (DR > 4) {
+                // (DR = 8: the node's block, its child and the leaf's block are 24 registers per lane. An outlined call passes them
+                // through scratch memory and saves the caller's registers there: ~1 KB per lane. Inlined, they stay in registers.)
+                if constexpr (W != 1)
+                    [[clang::always_inline]] oc = process_node_wide<DR, W, L, KR>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bow, lo);
+                else
+                    [[clang::always_inline]] oc = process_node<DR, L, CS, LITE, KR>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
+            } else if constexpr (W != 1)
                 oc = process_node_wide<DR, W, L, KR>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bow, lo);
             else
                 oc = process_node<DR, L, CS, LITE, KR>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
@@ -308,7 +315,11 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
 #ifdef STCSP_X_NOCOMMIT
         STCSP_PATH_END();
 #endif
-        CommitOut co = table_commit<DR, KR>(c, lane, ro, lo.kw, lo.kw2, lo.h, hd.h0, hd.h1, lo.next_set, lo.next_tag, lo.evals);
+        CommitOut co;
+        if constexpr (DR > 4)
+            [[clang::always_inline]] co = table_commit<DR, KR>(c, lane, ro, lo.kw, lo.kw2, lo.h, hd.h0, hd.h1, lo.next_set, lo.next_tag, lo.evals);
+        else
+            co = table_commit<DR, KR>(c, lane, ro, lo.kw, lo.kw2, lo.h, hd.h0, hd.h1, lo.next_set, lo.next_tag, lo.evals);
         if (!co.ok) {
             env.err = max(env.err, co.err);
             return;
@@ -316,8 +327,15 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
         if (!co.is_new) STCSP_PATH_END();
         env.n_new++;
         if (last) {
-            env.err = max(env.err, emit_state_node<DR>(c, lane, ro, a.out_base, a.out_cap, a.parity, co, lo.new_expire, lo.nblk,
-                                                       (STCSP_FRESH_SEED && W == 1 && co.set == hd.set) ? (uint32_t)(c.N * c.K + 1) : 0u));
+            if constexpr (DR > 4) {
+                unsigned er;
+                [[clang::always_inline]] er = emit_state_node<DR>(c, lane, ro, a.out_base, a.out_cap, a.parity, co, lo.new_expire, lo.nblk,
+                                                                  (STCSP_FRESH_SEED && W == 1 && co.set == hd.set) ? (uint32_t)(c.N * c.K + 1) : 0u);
+                env.err = max(env.err, er);
+            } else {
+                env.err = max(env.err, emit_state_node<DR>(c, lane, ro, a.out_base, a.out_cap, a.parity, co, lo.new_expire, lo.nblk,
+                                                           (STCSP_FRESH_SEED && W == 1 && co.set == hd.set) ? (uint32_t)(c.N * c.K + 1) : 0u));
+            }
             uint32_t fpos;
             flush_siblings(c, 0u, fpos);
             return;
@@ -703,11 +721,15 @@ __global__ void k_close_segment(Ctx c) {
 // BIG: one workgroup of 1024 threads (16 wavefronts = 4 per SIMD) per CU shares ONE staged copy of the program -- for LITE
 // programs whose tables do not fit beside four 256-thread workgroups' copies (the synthetic 64 x 32 family: 122 KB of sweep
 // records, dirty rows and tables). Same code; the workgroup size is read from blockDim.
+// DR = 8 (blocks of 257..512 words): a budget of its own, so that the DR = 4 kernels' STCSP_WIDE_WAVES stays what it is
+#ifndef STCSP_BLOCK8_WAVES
+#define STCSP_BLOCK8_WAVES 2
+#endif
 #ifndef STCSP_BIG_WAVES
 #define STCSP_BIG_WAVES 16  // wavefronts of a big workgroup
 #endif
 template <int DR, int L, bool CS, bool LITE, bool BIG = false, int W = 1, int KR = 1>
-__global__ __launch_bounds__(BIG ? STCSP_BIG_WAVES * 64 : 256, BIG ? 1 : (STCSP_EXPAND_WAVES > 1 ? STCSP_EXPAND_WAVES : (LITE && DR == 1 ? STCSP_LITE_WAVES : (DR <= 2 ? STCSP_GEN_WAVES : STCSP_WIDE_WAVES)))) void k_expand(const Ctx *__restrict__ cp, const Plan *__restrict__ plan_arg, unsigned launch_id, uint32_t tab_gen) {
+__global__ __launch_bounds__(BIG ? STCSP_BIG_WAVES * 64 : 256, BIG ? 1 : (STCSP_EXPAND_WAVES > 1 ? STCSP_EXPAND_WAVES : (LITE && DR == 1 ? STCSP_LITE_WAVES : (DR <= 2 ? STCSP_GEN_WAVES : (DR <= 4 ? STCSP_WIDE_WAVES : STCSP_BLOCK8_WAVES))))) void k_expand(const Ctx *__restrict__ cp, const Plan *__restrict__ plan_arg, unsigned launch_id, uint32_t tab_gen) {
     const Ctx &c = *cp;
     extern __shared__ __attribute__((aligned(16))) int smem[];
     // the planned round's gate in ONE 8-byte read (Plan::gate): is it this launch's round, and how many slots has it? The plan
@@ -794,7 +816,10 @@ __global__ __launch_bounds__(BIG ? STCSP_BIG_WAVES * 64 : 256, BIG ? 1 : (STCSP_
         for (int gw = blockIdx.x * wpb + wib; gw < n_slots;) {
             unsigned ticket = 0;
             if (lane == 0) ticket = atomicAdd(cursor, 1u);
-            expand_node<DR, L, CS, LITE, W, KR>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
+            if constexpr (DR > 4)
+                [[clang::always_inline]] expand_node<DR, L, CS, LITE, W, KR>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
+            else
+                expand_node<DR, L, CS, LITE, W, KR>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
             gw = total_waves + (int)rflu(ticket) * ncur + cur;
         }
     }

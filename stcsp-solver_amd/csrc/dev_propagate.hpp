@@ -97,6 +97,17 @@ template <int DR>
 struct Dom {
     uint32_t r[DR];
     __device__ __forceinline__ uint32_t get(int idx) const {  // idx wave-uniform
+        if constexpr (DR > 4) {
+            // select among the read-out words, not among the registers: a select chain over eight registers is turned into
+            // a load through a selected address, which moves the whole block to scratch memory (private-array demotion)
+            uint32_t v = 0;
+#pragma unroll
+            for (int q = 0; q < DR; q++) {
+                const uint32_t t = rdlane(r[q], idx & 63);
+                v = (idx >> 6) == q ? t : v;
+            }
+            return v;
+        }
         uint32_t v = r[0];
 #pragma unroll
         for (int q = 1; q < DR; q++)
@@ -943,7 +954,11 @@ constexpr int kBatchItems = 16, kBatchRec = 24, kBatchTuples = 256;  // tuples o
 static_assert(kBatchItems * kBatchRec <= kMaxLowVars * 64, "the batch records live in the lane-value scratch of the general revision");
 // record of one batch item (16-byte aligned parts, so that a tuple lane fetches it with four wide LDS reads)
 enum { BR_NOPEN = 0, BR_BASE = 1, BR_D0 = 2, BR_BITMAP = 3, BR_WPACK = 4 /* 2 words: block word of open variable q in byte q */, BR_SUP0 = 6,
-       BR_META = 7 /* w0 | tuples << 8 | eligible << 20 | no-op << 21 */, BR_STRIDE = 8, BR_SUP = 16 };
+       BR_META = 7 /* w0 | tuples << 8 | eligible << 20 | no-op << 21 */, BR_STRIDE = 8,
+       BR_WHIGH = 14 /* DR = 8 (blocks of more than 256 words) only: 2 words, the high bytes of BR_WPACK's; BR_META then holds w0 in 16 bits */,
+       BR_SUP = 16 };
+// BR_META's fields: the block word of variable 0 takes 8 bits, or 16 in the DR = 8 kernels
+template <int DR> constexpr int kMetaWordBits = DR > 4 ? 16 : 8;
 static_assert(kMaxLowVars <= 6, "batch record layout");
 // per lane: the bits of dirty word `lane` that belong to wavefront-revised items WITH a tuple bitmap and a scope of
 // at most kBatchArity variables (the only ones revise_batch can take); worked out once per constraint set
@@ -1052,12 +1067,14 @@ __device__ int revise_batch(const Ctx &c, const Img<L> &G, WaveEnv<DR> &S, Dom<D
         if (vs && j == 0) {  // the leader holds variable 0: D, w are its domain and block word
             *(uint4 *)&scr[rec + BR_NOPEN] = make_uint4((uint32_t)nopen, (uint32_t)base, D, (uint32_t)bm_off);
             scr[rec + BR_SUP0] = 0;
-            scr[rec + BR_META] = w | ((elig ? prod : 0) << 8) | ((elig ? 1 : 0) << 20) | ((noop ? 1 : 0) << 21);
+            constexpr int mb = kMetaWordBits<DR>;
+            scr[rec + BR_META] = w | ((elig ? prod : 0) << mb) | ((elig ? 1 : 0) << (mb + 12)) | ((noop ? 1 : 0) << (mb + 13));
             *(uint4 *)&scr[rec + BR_SUP] = make_uint4(0u, 0u, 0u, 0u);
             *(uint2 *)&scr[rec + BR_SUP + 4] = make_uint2(0u, 0u);
         }
         if (open && rank < kMaxLowVars) {
             ((unsigned char *)&scr[rec + BR_WPACK])[rank] = (unsigned char)w;
+            if constexpr (DR > 4) ((unsigned char *)&scr[rec + BR_WHIGH])[rank] = (unsigned char)(w >> 8);
             scr[rec + BR_STRIDE + rank] = st;
         }
         STCSP_REJOIN();
@@ -1081,14 +1098,15 @@ __device__ int revise_batch(const Ctx &c, const Img<L> &G, WaveEnv<DR> &S, Dom<D
     const uint4 my = *(const uint4 *)&scr[rec + BR_NOPEN];
     const uint2 mywp = *(const uint2 *)&scr[rec + BR_WPACK];
     const int meta = scr[rec + BR_META];
-    const int nopen = (int)my.x, w0 = meta & 255;
+    constexpr int mb = kMetaWordBits<DR>;
+    const int nopen = (int)my.x, w0 = meta & ((1 << mb) - 1);
     const uint32_t D0 = my.z, wp0 = mywp.x, wp1 = mywp.y;
-    const bool elig = cand && ((meta >> 20) & 1), noop = cand && ((meta >> 21) & 1);
+    const bool elig = cand && ((meta >> (mb + 12)) & 1), noop = cand && ((meta >> (mb + 13)) & 1);
 #ifdef STCSP_PHASES
     const unsigned long long t_b1 = PHASE_NOW();
     ws.cyc_batch_ab += t_b1 - t_b0;
 #endif
-    const int cnt = elig ? ((meta >> 8) & 4095) : 0;
+    const int cnt = elig ? ((meta >> mb) & 4095) : 0;
     const int incl = wave_scan_add(cnt), excl = incl - cnt;
     const bool inb = elig && incl <= kBatchTuples;
     const unsigned long long inbm = __ballot(inb);
@@ -1112,7 +1130,12 @@ __device__ int revise_batch(const Ctx &c, const Img<L> &G, WaveEnv<DR> &S, Dom<D
         const uint4 s03 = *(const uint4 *)&scr[rk + BR_STRIDE];
         const uint2 s45 = *(const uint2 *)&scr[rk + BR_STRIDE + 4];
         const int nop = tl ? (int)hd.x : 0;
-        const int wq[6] = {(int)(wp.x & 255u), (int)((wp.x >> 8) & 255u), (int)((wp.x >> 16) & 255u), (int)(wp.x >> 24), (int)(wp.y & 255u), (int)((wp.y >> 8) & 255u)};
+        int wq[6] = {(int)(wp.x & 255u), (int)((wp.x >> 8) & 255u), (int)((wp.x >> 16) & 255u), (int)(wp.x >> 24), (int)(wp.y & 255u), (int)((wp.y >> 8) & 255u)};
+        if constexpr (DR > 4) {
+            const uint2 wh = *(const uint2 *)&scr[rk + BR_WHIGH];
+#pragma unroll
+            for (int q = 0; q < 6; q++) wq[q] |= (int)((q < 4 ? wh.x >> (8 * q) : wh.y >> (8 * (q - 4))) & 255u) << 8;
+        }
         const int sq[6] = {(int)s03.x, (int)s03.y, (int)s03.z, (int)s03.w, (int)s45.x, (int)s45.y};
         uint32_t Dq[6];
 #pragma unroll
@@ -1157,7 +1180,12 @@ __device__ int revise_batch(const Ctx &c, const Img<L> &G, WaveEnv<DR> &S, Dom<D
     ws.cyc_batch_de += t_b2 - t_b1;
 #endif
     // ---- F: item lanes intersect the block with the supports
-    const int wo[6] = {(int)(wp0 & 255u), (int)((wp0 >> 8) & 255u), (int)((wp0 >> 16) & 255u), (int)(wp0 >> 24), (int)(wp1 & 255u), (int)((wp1 >> 8) & 255u)};
+    int wo[6] = {(int)(wp0 & 255u), (int)((wp0 >> 8) & 255u), (int)((wp0 >> 16) & 255u), (int)(wp0 >> 24), (int)(wp1 & 255u), (int)((wp1 >> 8) & 255u)};
+    if constexpr (DR > 4) {
+        const uint2 wh = *(const uint2 *)&scr[rec + BR_WHIGH];
+#pragma unroll
+        for (int q = 0; q < 6; q++) wo[q] |= (int)((q < 4 ? wh.x >> (8 * q) : wh.y >> (8 * (q - 4))) & 255u) << 8;
+    }
     bool nosup = false;
     uint32_t s0 = 0, sup[6] = {0, 0, 0, 0, 0, 0};
     if (inb) {
@@ -1335,6 +1363,10 @@ __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_va
                 it.idx[1] = (int)((sw.x >> 8) & 255u);
                 it.idx[2] = (int)((sw.x >> 16) & 255u);
                 it.idx[3] = (int)(sw.x >> 24);
+                if constexpr (DR > 4) {  // blocks of more than 256 words: the indices' high bytes
+#pragma unroll
+                    for (int k = 0; k < 4; k++) it.idx[k] |= (int)((sw.w >> (8 * k)) & 255u) << 8;
+                }
                 it.type = (int)(sw.y & 3u);
                 it.arity = (int)((sw.y >> 2) & 7u);
                 it.r1 = (int)((sw.y >> 5) & 63u);

@@ -15,7 +15,8 @@
 namespace stcsp {
 
 constexpr int kRegions = 32;        // cursor shards per segment (spreads allocation atomics)
-constexpr int kMaxDomRegs = 4;      // N*K <= 64 * kMaxDomRegs words live in VGPRs, lane-striped
+constexpr int kMaxDomRegs = 8;      // bitset blocks: N*K*W <= 64 * kMaxDomRegs words live in VGPRs, lane-striped (DR = 1, 2, 4, 8)
+constexpr int kMaxIntervalRegs = 4; // interval blocks (two words per variable and time point): 2*N*K <= 64 * kMaxIntervalRegs
 constexpr int kMaxKeyWords = 126;   // state key [set tag, signature...]: two lane-striped registers, one 128-word table entry
 constexpr int kCompactSweepItems = 128;  // sets with more small items than this sweep over a compacted dirty list
 constexpr int kMaxLowVars = 6;      // lane-enumerated scope variables per revision (2^6 = 64; value bits packed 5 x 6 in a register)
@@ -24,7 +25,7 @@ constexpr int kCursorStride = 16;   // words between cursors (64 B: one cursor p
 constexpr uint32_t kRootTag = 0x7fffffffu;
 // node header word 2 = constraint-set ordinal (low kSetBits bits) | dirty seed (the rest): seed 0 = revise every item (fresh state /
 // root), kSeedNone = nothing to revise (a re-queued fixpoint), else 1 + the variable whose time-0 domain the parent bisected
-// (N <= 256, so 12 bits hold it). 20 bits of ordinal: a million constraint sets (round 3: 16 / 16 bits, 65,535 sets).
+// (N*K + 1 <= 513, so 12 bits hold it). 20 bits of ordinal: a million constraint sets (round 3: 16 / 16 bits, 65,535 sets).
 constexpr int kSetBits = 20;
 constexpr uint32_t kSetMask = (1u << kSetBits) - 1u;
 constexpr uint32_t kSeedNone = (1u << (32 - kSetBits)) - 1u;
@@ -116,10 +117,11 @@ inline constexpr int small_row_stride(int r1) { return (r1 + 3) & ~3; }
 
 // What the lane-per-item sweep needs of an ItemDesc, packed into one 16-byte record so that a
 // lane fetches its item with a single 128-bit LDS read:
-//   x = idx[0] | idx[1] << 8 | idx[2] << 16 | idx[3] << 24      (block word indices, N*K <= 256)
+//   x = idx[0] | idx[1] << 8 | idx[2] << 16 | idx[3] << 24      (block word indices: their low bytes)
 //   y = type | arity << 2 | r1 << 5 | r2 << 11 | aux << 17       (aux signed: NEXT shift clamped to
 //                                                                  [-32, 32], UNTIL ordinal)
 //   z = toff
+//   w = the same four indices' high bytes (zero unless N*K > 256; read by the DR = 8 kernels alone)
 inline void pack_sweep_item(const ItemDesc &it, uint32_t out[4]) {
     auto byte = [](int32_t v) { return (uint32_t)(v < 0 ? 0 : v) & 0xffu; };
     out[0] = byte(it.idx[0]) | byte(it.idx[1]) << 8 | byte(it.idx[2]) << 16 | byte(it.idx[3]) << 24;
@@ -128,7 +130,8 @@ inline void pack_sweep_item(const ItemDesc &it, uint32_t out[4]) {
     out[1] = ((uint32_t)it.type & 3u) | ((uint32_t)it.arity & 7u) << 2 | ((uint32_t)it.r1 & 63u) << 5 | ((uint32_t)it.r2 & 63u) << 11 |
              (uint32_t)aux << 17;
     out[2] = (uint32_t)it.toff;
-    out[3] = 0u;
+    auto high = [](int32_t v) { return (uint32_t)(v < 0 ? 0 : v) >> 8 & 0xffu; };
+    out[3] = it.type == IT_WAVE ? 0u : high(it.idx[0]) | high(it.idx[1]) << 8 | high(it.idx[2]) << 16 | high(it.idx[3]) << 24;
 }
 
 struct SetDesc {          // one constraint set (entry of Solver::seenConstraints)

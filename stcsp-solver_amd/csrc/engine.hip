@@ -131,7 +131,7 @@ struct stcsp_engine {
     int prefix_need = 0;          // image words that must be staged for the L = 2 kernels (0: not applicable)
     bool prefix_complete = false; // ... and they are: general program, everything but cons / tables in the staged prefix
     // Keys of more than 64 words (set tag + signature): a lane holds key words j and 64 + j. Only the general, partly-staged
-    // kernels at DR = 4 get the second key register (k_expand<4, false, CS, false, false, W, 2>, k_commit<4, 2>), so the
+    // kernels at DR = 4 and 8 get the second key register (k_expand<DR, false, CS, false, false, W, 2>, k_commit<DR, 2>), so the
     // LITE / prefix kernels of the shipped programs (keys of at most 64 words) stay exactly as they are.
     bool long_key() const { return ctx.KL > 64; }
     bool interpreted = false;     // some wavefront-revised constraint has no tuple bitmap (postfix interpreter: uniformly expensive nodes)
@@ -261,6 +261,7 @@ struct stcsp_engine {
         if (const char *ev = getenv("STCSP_LITE")) lite = lite && atoi(ev) != 0;  // tuning switch
         if (mgr.W > 1) lite = false;  // (wide domains: every item is revised by dev_wide.hpp's bounds propagation)
         if (long_key()) lite = false;
+        if (DR > 4) lite = false;  // (blocks of more than 256 words: the general, partly-staged kernels only)
         // one contiguous image; every section starts on a 16-byte boundary
         std::vector<uint32_t> img;
         ImgOff o{};
@@ -436,10 +437,17 @@ struct stcsp_engine {
             max_nfirst = std::max(max_nfirst, sd.nfirst);
         }
         ctx.sib_depth = kSibDepth;
+        // DR = 8: node records of up to 516 words, 8 KB of sibling stack per wavefront at depth 4. The stack is as deep as the
+        // occupancy the kernels' registers allow (STCSP_BLOCK8_WAVES wavefronts per SIMD = as many 4-wavefront workgroups per CU) leaves
+        // room for in the 160 KB of a CU -- depth 4 at 2 wavefronts per SIMD -- and within the 64 KB a launch gets without asking.
+        if (DR > 4) {
+            auto wg_bytes = [&](int d) { return (size_t)4 * wave_scratch_words(ctx.NK, ctx.stack_slots, lite, d) * sizeof(int); };
+            while (ctx.sib_depth > 1 && (wg_bytes(ctx.sib_depth) > 64 * 1024 || (size_t)STCSP_BLOCK8_WAVES * wg_bytes(ctx.sib_depth) > 160 * 1024)) ctx.sib_depth--;
+        }
         const size_t scratch = (size_t)4 * wave_scratch_words(ctx.NK, ctx.stack_slots, lite, ctx.sib_depth) * sizeof(int);
         if (scratch > 160 * 1024) return fail(STCSP_E_UNSUPPORTED, "expression stack too deep for LDS");
         // stage the image in LDS when image + scratch leave room for >= 2 workgroups per CU
-        img_in_lds = (size_t)o.words * 4 + scratch <= 64 * 1024 && mgr.W == 1 && !long_key();  // (the wide and long-key kernels exist in the partly-staged form only)
+        img_in_lds = (size_t)o.words * 4 + scratch <= 64 * 1024 && mgr.W == 1 && !long_key() && DR <= 4;  // (the wide, long-key and DR = 8 kernels exist in the partly-staged form only)
         if (const char *ev = getenv("STCSP_IMG_LDS")) img_in_lds = img_in_lds && atoi(ev) != 0;  // tuning switch
         ctx.stage_words = img_in_lds ? o.words : 0;
         lds_bytes = scratch + (size_t)ctx.stage_words * 4;
@@ -478,15 +486,20 @@ struct stcsp_engine {
             switch (DR) {
                 case 1: fn = expand_fn<1>(); break;
                 case 2: fn = expand_fn<2>(); break;
-                default: fn = expand_fn<4>(); break;
+                case 4: fn = expand_fn<4>(); break;
+                case 8: fn = expand_fn<8>(); break;
+                default: return fail(STCSP_E_INTERNAL, "no expansion kernel for a block of %d registers", DR);
             }
+            if (!fn) return fail(STCSP_E_INTERNAL, "no expansion kernel for this program at DR = %d", DR);
             if (big) {
                 // more than 64 KB of dynamic LDS has to be asked for, per kernel (the probe kernel stages the same image)
                 const void *pf;
                 switch (DR) {
                     case 1: pf = probe_fn<1>(); break;
                     case 2: pf = probe_fn<2>(); break;
-                    default: pf = probe_fn<4>(); break;
+                    case 4: pf = probe_fn<4>(); break;
+                    case 8: pf = probe_fn<8>(); break;  // (not reached: DR = 8 has no big-workgroup kernels)
+                    default: return fail(STCSP_E_INTERNAL, "no probe kernel for a block of %d registers", DR);
                 }
                 HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
                 HIPCHK(hipFuncSetAttribute(pf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
@@ -508,7 +521,7 @@ struct stcsp_engine {
                         ctx.stage_words = 0;
                 }
             }
-            prefix_complete = !lite && !img_in_lds && !big && !compact_sweeps && mgr.W == 1 && !long_key() && prefix_need > 0 && ctx.stage_words >= prefix_need &&
+            prefix_complete = !lite && !img_in_lds && !big && !compact_sweeps && mgr.W == 1 && !long_key() && DR <= 4 && prefix_need > 0 && ctx.stage_words >= prefix_need &&
                               !(getenv("STCSP_PREFIX_KERNEL") && atoi(getenv("STCSP_PREFIX_KERNEL")) == 0);
 #ifdef STCSP_PHASES
             if (DR == 4) prefix_complete = false;
@@ -518,7 +531,9 @@ struct stcsp_engine {
                 switch (DR) {
                     case 1: f2 = expand_fn<1>(); break;
                     case 2: f2 = expand_fn<2>(); break;
-                    default: f2 = expand_fn<4>(); break;
+                    case 4: f2 = expand_fn<4>(); break;
+                    case 8: f2 = expand_fn<8>(); break;  // (not reached: DR = 8 has no prefix kernels)
+                    default: return fail(STCSP_E_INTERNAL, "no expansion kernel for a block of %d registers", DR);
                 }
                 int pc2 = 0;
                 if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc2, f2, 256, lds_bytes) == hipSuccess && pc2 > 0) per_cu = pc2;
@@ -562,7 +577,8 @@ struct stcsp_engine {
         const int N = mgr.N, K = mgr.K;
         // domains of up to 32 values take one bitset word per (variable, time point), up to 64 two, up to 128 four (W; one W
         // for the whole block: dev_wide.hpp); the block of N*K*W words lives in at most kMaxDomRegs registers per lane
-        // (STCSP_F_INTERVAL_DOMAINS: two words, lb and ub, per variable and time point whatever the width -- dev_interval.hpp)
+        // (STCSP_F_INTERVAL_DOMAINS: two words, lb and ub, per variable and time point whatever the width -- dev_interval.hpp --
+        // in at most kMaxIntervalRegs: the interval kernels exist up to DR = 4)
         for (int v = 0; v < N && !mgr.intervals; v++) {
             long long width = (long long)mgr.ub[v] - (long long)mgr.lb[v] + 1;
             if (width > 128)
@@ -570,8 +586,8 @@ struct stcsp_engine {
                             "(STCSP_F_INTERVAL_DOMAINS takes any width)", v, width);
         }
         const int W = mgr.W;
-        if (mgr.intervals && 2ll * N * K > 64 * kMaxDomRegs)
-            return fail(STCSP_E_UNSUPPORTED, "interval domains: 2*N*K = 2*%d*%d exceeds the block limit of %d words (64 * kMaxDomRegs)", N, K, 64 * kMaxDomRegs);
+        if (mgr.intervals && 2ll * N * K > 64 * kMaxIntervalRegs)
+            return fail(STCSP_E_UNSUPPORTED, "interval domains: 2*N*K = 2*%d*%d exceeds the block limit of %d words (64 * kMaxIntervalRegs)", N, K, 64 * kMaxIntervalRegs);
         if ((long long)N * K * W > 64 * kMaxDomRegs)
             return fail(STCSP_E_UNSUPPORTED, "N*K*W = %d*%d*%d exceeds the %d-word register-resident block", N, K, W, 64 * kMaxDomRegs);
         if (mgr.n_until_cons > 32) return fail(STCSP_E_UNSUPPORTED, "more than 32 until constraints");
@@ -642,8 +658,10 @@ struct stcsp_engine {
                 if (pre < 0) return fail(pre, "%s", mgr.error.c_str());
             }
         }
+        // block registers per lane: 1, 2, 4 or 8 (5..7 round up to 8); long keys: the KR = 2 kernels exist at DR = 4 and 8 only
         DR = (N * K * W + 63) / 64;
-        if (DR == 3 || ctx.KL > 64) DR = 4;  // (long keys: the KR = 2 kernels exist at DR = 4 only; the block needs no more than that)
+        if (DR > 4) DR = 8;
+        if (DR == 3 || ctx.KL > 64) DR = std::max(DR, 4);
         HIPCHK(d_arr_data.upload(mgr.array_data));
         ctx.arr_data = d_arr_data.p;
         rc = upload_program();
@@ -659,6 +677,8 @@ struct stcsp_engine {
         // Sharded engines: 256 k too -- their outboxes no longer grow with the batch (the planner bounds a round by the room
         // the outboxes have left: dev_kernels.hpp plan_next), so the time-boxed synthetic runs as fast sharded as unsharded.
         int batch = opt.batch_nodes > 0 ? opt.batch_nodes : (sharded ? 262144 : (ctx.NK <= 128 ? 1048576 : 262144));
+        // DR = 8: node records of up to 2 KB -- half the batch, so that a round's records take the memory a DR = 4 round's take
+        if (auto_batch && DR > 4) batch /= 2;
         if (const char *ev = getenv("STCSP_BATCH")) if (atoi(ev) > 0 && auto_batch) batch = atoi(ev);
         {
             size_t free_b = 0, total_b = 0;
@@ -712,6 +732,12 @@ struct stcsp_engine {
         // for 4,096 nodes per region and launch (world 8: 3.4 GB at 100-word records).
         if (chain_small_auto) chain_small = lite ? 4 : (wide_conditional ? 1 : (interpreted ? 2 : 16));  // (what begin() will plan with: the outboxes are sized for it)
         cand_cap = (uint32_t)(sharded ? std::max(std::max(8, std::max(chain_small, chain_big)) * std::min(chunk_r, 4096), 4096) : 64);
+        // DR = 8: candidate records of up to ~1.2 k words (2 * 512-word block parts + signature): the outboxes of one engine are capped
+        // at 4 GiB (65,536 records per region would be 19 GB at world 2); the planner bounds every round by the room they have left
+        if (sharded && DR > 4) {
+            const size_t per_record = (size_t)opt.world * R * ctx.CS * sizeof(uint32_t);
+            cand_cap = (uint32_t)std::min<size_t>(cand_cap, std::max<size_t>(((size_t)4 << 30) / per_record, (size_t)8 * std::max(chain_small, chain_big)));
+        }
         if (const char *ev = getenv("STCSP_CAND_CAP")) if (sharded && atoi(ev) > 0) cand_cap = (uint32_t)std::max(atoi(ev), 2 * std::max(chain_small, chain_big));  // tests: outboxes that fill up
         HIPCHK(d_cand.alloc((size_t)opt.world * R * cand_cap * ctx.CS));
         if (sharded) HIPCHK(d_pack.alloc((size_t)R * cand_cap * ctx.CS));
@@ -1167,8 +1193,36 @@ struct stcsp_engine {
             default: f(std::integral_constant<int, 7>{}); break;
         }
     }
+    // DR = 8 (blocks of 257..512 words) has the general, partly-staged kernels only: W = 1 (plain or compacted sweeps), 2 and 4,
+    // each with one or two key registers; no LITE, image-in-LDS, prefix or big-workgroup variants, no interval kernels
+    template <int KR>
+    const void *expand8_fn() const {
+        if (mgr.intervals) return nullptr;  // (create refuses interval blocks of more than 256 words)
+        if (mgr.W == 2) return (const void *)k_expand<8, false, false, false, false, 2, KR>;
+        if (mgr.W > 2) return (const void *)k_expand<8, false, false, false, false, 4, KR>;
+        if (compact_sweeps) return (const void *)k_expand<8, false, true, false, false, 1, KR>;
+        return (const void *)k_expand<8, false, false, false, false, 1, KR>;
+    }
+    template <int KR>
+    void launch_expand8() {
+        const Ctx *cp = (const Ctx *)d_ctx.p;
+        const Plan *pp = (const Plan *)d_plan.p;
+        if (mgr.W == 2)
+            hipLaunchKernelGGL((k_expand<8, false, false, false, false, 2, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+        else if (mgr.W > 2)
+            hipLaunchKernelGGL((k_expand<8, false, false, false, false, 4, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+        else if (compact_sweeps)
+            hipLaunchKernelGGL((k_expand<8, false, true, false, false, 1, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+        else
+            hipLaunchKernelGGL((k_expand<8, false, false, false, false, 1, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+    }
     template <int DRT>
     const void *expand_fn() const {
+        if constexpr (DRT == 8) return long_key() ? expand8_fn<2>() : expand8_fn<1>();
+        else return expand_fn_le4<DRT>();
+    }
+    template <int DRT>
+    const void *expand_fn_le4() const {
         const void *fn = nullptr;
         if constexpr (DRT == 4)
             if (long_key()) {
@@ -1195,15 +1249,28 @@ struct stcsp_engine {
     }
     template <int DRT>
     const void *probe_fn() const {
-        const void *fn = nullptr;
-        with_variant<DRT>([&](auto v) {
-            constexpr int V = STCSP_VARIANT(DRT, decltype(v)::value);
-            fn = (const void *)k_probe<DRT, (V & 4) != 0, (V & 2) != 0, (V & 1) != 0>;
-        });
-        return fn;
+        if constexpr (DRT == 8) {
+            return compact_sweeps ? (const void *)k_probe<8, false, true, false> : (const void *)k_probe<8, false, false, false>;
+        } else {
+            const void *fn = nullptr;
+            with_variant<DRT>([&](auto v) {
+                constexpr int V = STCSP_VARIANT(DRT, decltype(v)::value);
+                fn = (const void *)k_probe<DRT, (V & 4) != 0, (V & 2) != 0, (V & 1) != 0>;
+            });
+            return fn;
+        }
     }
     template <int DRT>
     void launch_expand() {
+        if constexpr (DRT == 8) {
+            if (long_key()) launch_expand8<2>();
+            else launch_expand8<1>();
+        } else {
+            launch_expand_le4<DRT>();
+        }
+    }
+    template <int DRT>
+    void launch_expand_le4() {
         const Ctx *cp = (const Ctx *)d_ctx.p;
         if constexpr (DRT == 4)
             if (long_key()) {
@@ -1283,7 +1350,9 @@ struct stcsp_engine {
             switch (DR) {
                 case 1: launch_probe<1>(grid, d_blk.p, ns, -1, 0xffffffffu, d_out.p); break;
                 case 2: launch_probe<2>(grid, d_blk.p, ns, -1, 0xffffffffu, d_out.p); break;
-                default: launch_probe<4>(grid, d_blk.p, ns, -1, 0xffffffffu, d_out.p); break;
+                case 4: launch_probe<4>(grid, d_blk.p, ns, -1, 0xffffffffu, d_out.p); break;
+                case 8: launch_probe<8>(grid, d_blk.p, ns, -1, 0xffffffffu, d_out.p); break;
+                default: return fail(STCSP_E_INTERNAL, "no probe kernel for a block of %d registers", DR);
             }
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(blocks.data(), d_blk.p, blocks.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -1310,11 +1379,18 @@ struct stcsp_engine {
     template <int DRT>
     void launch_probe(unsigned grid, uint32_t *blocks, int n, int set, uint32_t expire, int *outcome) {
         const Ctx *cp = (const Ctx *)d_ctx.p;
-        with_variant<DRT>([&](auto v) {
-            constexpr int V = STCSP_VARIANT(DRT, decltype(v)::value);
-            hipLaunchKernelGGL((k_probe<DRT, (V & 4) != 0, (V & 2) != 0, (V & 1) != 0>), dim3(grid), dim3(256), lds_bytes, stream, cp, blocks, n, set,
-                               expire, outcome);
-        });
+        if constexpr (DRT == 8) {
+            if (compact_sweeps)
+                hipLaunchKernelGGL((k_probe<8, false, true, false>), dim3(grid), dim3(256), lds_bytes, stream, cp, blocks, n, set, expire, outcome);
+            else
+                hipLaunchKernelGGL((k_probe<8, false, false, false>), dim3(grid), dim3(256), lds_bytes, stream, cp, blocks, n, set, expire, outcome);
+        } else {
+            with_variant<DRT>([&](auto v) {
+                constexpr int V = STCSP_VARIANT(DRT, decltype(v)::value);
+                hipLaunchKernelGGL((k_probe<DRT, (V & 4) != 0, (V & 2) != 0, (V & 1) != 0>), dim3(grid), dim3(256), lds_bytes, stream, cp, blocks, n, set,
+                                   expire, outcome);
+            });
+        }
     }
     int propagate(int set, uint32_t expire, uint32_t *blocks, int64_t count, int32_t *outcome, int64_t *skipped) {
         if (sharded) return fail(STCSP_E_STATE, "propagate is for unsharded engines");
@@ -1343,7 +1419,9 @@ struct stcsp_engine {
         switch (DR) {
             case 1: launch_probe<1>(grid, d_blk.p, (int)count, set, expire, d_out.p); break;
             case 2: launch_probe<2>(grid, d_blk.p, (int)count, set, expire, d_out.p); break;
-            default: launch_probe<4>(grid, d_blk.p, (int)count, set, expire, d_out.p); break;
+            case 4: launch_probe<4>(grid, d_blk.p, (int)count, set, expire, d_out.p); break;
+            case 8: launch_probe<8>(grid, d_blk.p, (int)count, set, expire, d_out.p); break;
+            default: return fail(STCSP_E_INTERNAL, "no probe kernel for a block of %d registers", DR);
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(blocks, d_blk.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -1567,7 +1645,9 @@ struct stcsp_engine {
                 switch (DR) {
                     case 1: launch_expand<1>(); break;
                     case 2: launch_expand<2>(); break;
-                    default: launch_expand<4>(); break;
+                    case 4: launch_expand<4>(); break;
+                    case 8: launch_expand<8>(); break;
+                    default: return fail(STCSP_E_INTERNAL, "no expansion kernel for a block of %d registers", DR);
                 }
                 HIPCHK(hipGetLastError());
                 expand_launches++;
@@ -1883,10 +1963,15 @@ struct stcsp_engine {
             switch (DR) {
                 case 1: hipLaunchKernelGGL((k_commit<1>), grid, block, 0, stream, ctx, ca); break;
                 case 2: hipLaunchKernelGGL((k_commit<2>), grid, block, 0, stream, ctx, ca); break;
-                default:
+                case 4:
                     if (long_key()) hipLaunchKernelGGL((k_commit<4, 2>), grid, block, 0, stream, ctx, ca);
                     else hipLaunchKernelGGL((k_commit<4>), grid, block, 0, stream, ctx, ca);
                     break;
+                case 8:
+                    if (long_key()) hipLaunchKernelGGL((k_commit<8, 2>), grid, block, 0, stream, ctx, ca);
+                    else hipLaunchKernelGGL((k_commit<8, 1>), grid, block, 0, stream, ctx, ca);
+                    break;
+                default: return fail(STCSP_E_INTERNAL, "no commit kernel for a block of %d registers", DR);
             }
         }
         hipLaunchKernelGGL(k_close_segment, dim3(1), dim3(64), 0, stream, ctx);
