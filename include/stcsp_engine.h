@@ -291,7 +291,8 @@ int stcsp_engine_sets_import(stcsp_engine *engine, const int32_t *words, int64_t
  * overwritten by their propagated form; outcome[i] = 0 wiped out, 1 branch node, 2 leaf whose
  * constraint-set translation is not known yet, 3 leaf. *skipped (may be NULL) receives the number of
  * revisions the device skipped for their enumeration budget (0 => every block is at its GAC fixpoint).
- * Unsharded engines, between solves. */
+ * `expire` holds one flag per until constraint: engines with more than 32 until constraints return
+ * STCSP_E_UNSUPPORTED. Unsharded engines, between solves. */
 int stcsp_engine_propagate(stcsp_engine *engine, int32_t set, uint32_t expire, uint32_t *blocks, int64_t count,
                            int32_t *outcome, int64_t *skipped);
 

@@ -46,7 +46,7 @@ extern __shared__ __attribute__((aligned(16))) int stcsp_lds[];
 #ifndef STCSP_FRESH_SEED
 #define STCSP_FRESH_SEED 1
 #endif
-template <int DR, int L, bool CS, bool LITE, int W = 1, int KR = 1>
+template <int DR, int L, bool CS, bool LITE, int W = 1, int KR = 1, int UW = 1>
 __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const Img<L> &P, int gw, int lane, int *lds_vals, int *lds_stk, int *ldom,
                             int sib_off, WaveEnv<DR> &env, bool dry = false) {
     const Ctx c0 = ctx_from(hot);
@@ -73,13 +73,19 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
     // item (fresh state / root), kSeedNone = nothing to revise (re-queued fixpoint), else 1 + the
     // variable whose time-0 domain the parent just bisected -- the parent block was at its
     // fixpoint, so only items reading that word can have lost supports
-    NodeHdr hd;
+    NodeHdrOf<UW> hd;
     hd.h0 = rflu(node[0]);
     hd.h1 = rflu(node[1]);
     const uint32_t w2 = rflu(node[2]);
     hd.set = (int)(w2 & kSetMask);
     hd.seed = w2 >> kSetBits;
     hd.expire = rflu(node[3]);
+    // more than 32 until constraints: expire words 1 .. nw-1 follow the block (node records, sibling entries, candidates)
+    const int nw = UW > 1 ? expire_words(c.n_until_cons) : 1;
+    if constexpr (UW > 1) load_expire_hi<UW>(hd.hi, node + 4 + c.NK, nw);
+    auto store_hi = [&](uint32_t *rec) {  // ... of a node record just stored
+        if constexpr (UW > 1) store_expire_hi<UW>(rec + 4 + c.NK, hd.hi, nw, lane);
+    };
     // A wavefront does not stop after one expansion: it keeps the lower child of a bisection (or the
     // first node of a state its leaf just opened) in registers and expands it too, up to `chain`
     // expansions per slot -- depth-first inside the slot, breadth-first across slots. The planner
@@ -130,7 +136,7 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
     for (int step = 1;; step++) {
         BranchOut bo;     // outputs of this expansion only (nothing of them is carried round the loop)
         BranchOutWide bow;  // (W > 1 and W = kWIntervals: dev_wide.hpp)
-        LeafOut<DR> lo;
+        LeafOutOf<DR, UW> lo;
         sd = rfl(sd);
         // The header is wave-uniform, but values carried round a loop whose exits the compiler cannot
         // prove uniform are treated as divergent (VGPRs, vector instead of scalar descriptor loads:
@@ -140,6 +146,7 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
         hd.set = rfl(hd.set);
         hd.seed = rflu(hd.seed);
         hd.expire = rflu(hd.expire);
+        if constexpr (UW > 1) hd.hi.uniform();
         const unsigned long long t_p = PHASE_NOW();
 #if STCSP_CTX_REBUILDS >= 2
         int oc;
@@ -149,13 +156,13 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
                 // (DR = 8: the node's block, its child and the leaf's block are 24 registers per lane. An outlined call passes them
                 // through scratch memory and saves the caller's registers there: ~1 KB per lane. Inlined, they stay in registers.)
                 if constexpr (W != 1)
-                    [[clang::always_inline]] oc = process_node_wide<DR, W, L, KR>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bow, lo);
+                    [[clang::always_inline]] oc = process_node_wide<DR, W, L, KR, UW>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bow, lo);
                 else
-                    [[clang::always_inline]] oc = process_node<DR, L, CS, LITE, KR>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
+                    [[clang::always_inline]] oc = process_node<DR, L, CS, LITE, KR, UW>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
             } else if constexpr (W != 1)
-                oc = process_node_wide<DR, W, L, KR>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bow, lo);
+                oc = process_node_wide<DR, W, L, KR, UW>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bow, lo);
             else
-                oc = process_node<DR, L, CS, LITE, KR>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
+                oc = process_node<DR, L, CS, LITE, KR, UW>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
         }
         const Ctx ce = ctx_from(hot);
         const Ctx &c = ce;
@@ -163,9 +170,9 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
         static_assert(W == 1, "tuning builds: one-word domains only");
         const Ctx ce = ctx_from(hot);
         const Ctx &c = ce;
-        const int oc = process_node<DR, L, CS, LITE, KR>(c, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
+        const int oc = process_node<DR, L, CS, LITE, KR, UW>(c, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
 #else
-        const int oc = process_node<DR, L, CS, LITE, KR>(c, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
+        const int oc = process_node<DR, L, CS, LITE, KR, UW>(c, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
 #endif
         const bool last = step >= chain || __builtin_amdgcn_s_memtime() - t_slot > chain_cycles;
         const unsigned long long t_c = PHASE_NOW();
@@ -202,6 +209,7 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
         hd.set = (int)(sw2 & kSetMask);                                                    \
         hd.seed = sw2 >> kSetBits;                                                         \
         hd.expire = rflu((uint32_t)stcsp_lds[sib + 3]);                                    \
+        if constexpr (UW > 1) load_expire_hi<UW>(hd.hi, stcsp_lds + sib + 4 + c.NK, nw);   \
         _Pragma("unroll") for (int q = 0; q < DR; q++) {                                   \
             const int idx = q * 64 + lane;                                                 \
             dom.r[q] = idx < c.NK ? (uint32_t)stcsp_lds[sib + 4 + idx] : 0u;               \
@@ -242,6 +250,7 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
             if (use_sib && !last && sd < c.sib_depth) {
                 const int sb = sib_off + sd * c.NS;
                 if (lane < 4) stcsp_lds[sb + lane] = (int)(lane == 0 ? hd.h0 : (lane == 1 ? hd.h1 : (lane == 2 ? cw2 : hd.expire)));
+                if constexpr (UW > 1) store_expire_hi<UW>(stcsp_lds + sb + 4 + c.NK, hd.hi, nw, lane);
 #pragma unroll
                 for (int q = 0; q < DR; q++) {
                     const int idx = q * 64 + lane;
@@ -257,6 +266,8 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
                 if (!flush_siblings(c, 2u, pos)) return;
                 store_node<DR>(out_region + (size_t)pos * c.NS, c, hd.h0, hd.h1, cw2, hd.expire, child, lane);
                 store_node<DR>(out_region + (size_t)(pos + 1) * c.NS, c, hd.h0, hd.h1, cw2, hd.expire, dom, lane);
+                store_hi(out_region + (size_t)pos * c.NS);
+                store_hi(out_region + (size_t)(pos + 1) * c.NS);
                 return;
             }
             uint32_t pos = 0;
@@ -267,6 +278,7 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
                 return;
             }
             store_node<DR>(out_region + (size_t)pos * c.NS, c, hd.h0, hd.h1, cw2, hd.expire, child, lane);
+            store_hi(out_region + (size_t)pos * c.NS);
             hd.seed = (uint32_t)(bvar + 1);
             continue;
         }
@@ -279,6 +291,7 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
                 return;
             }
             store_node<DR>(out_region + (size_t)pos * c.NS, c, hd.h0, hd.h1, (uint32_t)hd.set | (kSeedNone << kSetBits), hd.expire, dom, lane);
+            store_hi(out_region + (size_t)pos * c.NS);
             STCSP_PATH_END();
         }
         // leaf
@@ -309,6 +322,7 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
                 if (idx < c.NK) blk[idx] = lo.nblk[q];
             }
             STCSP_REJOIN();
+            if constexpr (UW > 1) store_expire_hi<UW>(blk + c.NK, lo.new_hi, nw, lane);
             STCSP_PATH_END();
         }
         // commit right here, the leaf's data never leaves the registers
@@ -327,7 +341,12 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
         if (!co.is_new) STCSP_PATH_END();
         env.n_new++;
         if (last) {
-            if constexpr (DR > 4) {
+            if constexpr (UW > 1) {
+                unsigned er;
+                [[clang::always_inline]] er = emit_state_node<DR, UW>(c, lane, ro, a.out_base, a.out_cap, a.parity, co, lo.new_expire, lo.new_hi, lo.nblk,
+                                                                      (STCSP_FRESH_SEED && W == 1 && co.set == hd.set) ? (uint32_t)(c.N * c.K + 1) : 0u);
+                env.err = max(env.err, er);
+            } else if constexpr (DR > 4) {
                 unsigned er;
                 [[clang::always_inline]] er = emit_state_node<DR>(c, lane, ro, a.out_base, a.out_cap, a.parity, co, lo.new_expire, lo.nblk,
                                                                   (STCSP_FRESH_SEED && W == 1 && co.set == hd.set) ? (uint32_t)(c.N * c.K + 1) : 0u);
@@ -349,6 +368,7 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
         hd.seed = (STCSP_FRESH_SEED && W == 1 && co.set == hd.set) ? (uint32_t)(c.N * c.K + 1) : 0u;
         hd.set = co.set;
         hd.expire = lo.new_expire;
+        if constexpr (UW > 1) hd.hi = lo.new_hi;
 #pragma unroll
         for (int q = 0; q < DR; q++) dom.r[q] = lo.nblk[q];
     }
@@ -730,134 +750,17 @@ __global__ void k_close_segment(Ctx c) {
 #endif
 template <int DR, int L, bool CS, bool LITE, bool BIG = false, int W = 1, int KR = 1>
 __global__ __launch_bounds__(BIG ? STCSP_BIG_WAVES * 64 : 256, BIG ? 1 : (STCSP_EXPAND_WAVES > 1 ? STCSP_EXPAND_WAVES : (LITE && DR == 1 ? STCSP_LITE_WAVES : (DR <= 2 ? STCSP_GEN_WAVES : (DR <= 4 ? STCSP_WIDE_WAVES : STCSP_BLOCK8_WAVES))))) void k_expand(const Ctx *__restrict__ cp, const Plan *__restrict__ plan_arg, unsigned launch_id, uint32_t tab_gen) {
-    const Ctx &c = *cp;
-    extern __shared__ __attribute__((aligned(16))) int smem[];
-    // the planned round's gate in ONE 8-byte read (Plan::gate): is it this launch's round, and how many slots has it? The plan
-    // pointer is a kernel argument of its own (not read through *cp), so this is the first and only load a workgroup without
-    // work waits for. A planner that stops (done, pool full, host needed) leaves the gate on the launch that has just run: the
-    // rest of the burst fails this test -- no separate look at the status word.
-    static_assert(offsetof(Plan, gate) == 0, "the gate is the plan's first word");
-    // ---- ONE batch of independent loads before anything is waited for: the gate, the plan words of the round (through the plan
-    // ARGUMENT, not through the pointer inside *cp), the context words the prologue needs and the register copy of the context.
-    // (Round 3's prologue was a chain of a dozen dependent scalar loads -- gate, then *cp, then cp->progress, then cp->plan, then
-    // plan->rounds, then stage_words, then img, ... -- eight of them first touches of a cache line after the launch boundary, on
-    // the critical path of every round. The empty asm below pins the batch in front of the gate test.)
-    const kptr pk = (kptr)(const __attribute__((address_space(1))) int *)plan_arg;
-    const unsigned long long gate = ((const __attribute__((address_space(4))) unsigned long long *)(const __attribute__((address_space(1))) unsigned long long *)plan_arg)[0];
-    auto pl = [&](size_t off) { return (uint32_t)pk[(int)(off / 4)]; };
-    const uint32_t p_in_lo = pl(offsetof(Plan, in_base)), p_in_hi = pl(offsetof(Plan, in_base) + 4);
-    const uint32_t p_out_lo = pl(offsetof(Plan, out_base)), p_out_hi = pl(offsetof(Plan, out_base) + 4);
-    const uint32_t p_in_cap = pl(offsetof(Plan, in_cap)), p_out_cap = pl(offsetof(Plan, out_cap)), p_cand_cap = pl(offsetof(Plan, cand_cap));
-    const uint32_t p_parity = pl(offsetof(Plan, parity)), p_rounds = pl(offsetof(Plan, rounds));
-    const int c_stage_words = c.stage_words, c_NK = c.NK, c_stack_slots = c.stack_slots, c_sib_depth = c.sib_depth, c_world = c.world;
-    const uint32_t *const c_img = c.img;
-    uint32_t *const c_arena = c.arena, *const c_cand = c.cand, *const c_ctl = c.ctl;
-    Progress *const c_progress = c.progress;
-    const int lane = threadIdx.x & 63, wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    uint32_t hot[2];
-#pragma unroll
-    for (int q = 0; q < 2; q++) hot[q] = q * 64 + lane < kCtxWords ? ((const uint32_t *)cp)[q * 64 + lane] : 0u;
-    asm volatile("" ::"s"(p_in_lo), "s"(p_in_hi), "s"(p_out_lo), "s"(p_out_hi), "s"(p_in_cap), "s"(p_out_cap), "s"(p_cand_cap), "s"(p_parity), "s"(p_rounds),
-                 "s"(c_stage_words), "s"(c_NK), "s"(c_stack_slots), "s"(c_sib_depth), "s"(c_world), "s"(c_img), "s"(c_arena), "s"(c_cand), "s"(c_ctl), "s"(c_progress));
-    if ((unsigned)(gate >> 32) != launch_id) return;  // another launch's round (this workgroup is late, or the burst ran past a stop)
-    const int n_slots = (int)(unsigned)gate;
-    const int wpb = BIG ? STCSP_BIG_WAVES : 4;  // wavefronts per workgroup
-    // workgroups without a node slot leave at once; the ticket below counts the working ones only
-    if ((int)blockIdx.x * wpb >= n_slots) return;
-    const unsigned n_working = (unsigned)min((n_slots + wpb - 1) / wpb, (int)gridDim.x);
-    if (blockIdx.x == 0 && threadIdx.x == 0 && c_progress)  // (the streaming export's "the round before this one has ended")
-        __hip_atomic_store(&c_progress->started, (unsigned long long)(p_rounds + 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    const int img_words = (c_stage_words + 3) & ~3;  // L: the whole image; else a prefix of hot sections (or 0)
-    const unsigned long long t_k0 = PHASE_NOW();
-    (void)t_k0;
-    if (img_words) {
-        const uint4 *src = (const uint4 *)c_img;
-        uint4 *dst = (uint4 *)smem;
-        for (int k = threadIdx.x; k < img_words / 4; k += (BIG ? STCSP_BIG_WAVES * 64 : 256)) dst[k] = src[k];
-        __syncthreads();
-    }
-    const int per_wave = wave_scratch_words(c_NK, c_stack_slots, LITE, c_sib_depth);
-    int *lds_vals = smem + img_words + wib * per_wave;
-    int *lds_stk = lds_vals + kMaxLowVars * 64;
-    int *ldom = LITE ? lds_vals : lds_stk + c_stack_slots * 64;  // NK-word AND-accumulator of this wavefront, then its counters
-    const int sib_off = img_words + wib * per_wave + wave_sib_offset(c_NK, c_stack_slots, LITE);  // word offset in the launch's LDS
-    Img<L> P{c_img, (const uint32_t *)smem, c_stage_words};
-    ExpandArgs a;
-    a.in_base = c_arena + ((unsigned long long)p_in_hi << 32 | p_in_lo);
-    a.in_cap = p_in_cap;
-    a.out_base = c_arena + ((unsigned long long)p_out_hi << 32 | p_out_lo);
-    a.out_cap = p_out_cap;
-    a.cand_base = c_cand;
-    a.cand_cap = p_cand_cap;
-    a.parity = (int)p_parity;
-    const int total_waves = gridDim.x * wpb;
-    const unsigned long long t_k1 = PHASE_NOW();
-    (void)t_k1;
-    WaveEnv<DR> env;
-    {
-        // the state table's generation changes with every solve; the device copy of the context does not have to: the launch
-        // brings it along and it goes straight into the register copy the node loops read
-        constexpr int gw_ = (int)(offsetof(Ctx, tab_gen) / 4);
-        static_assert(gw_ < 64, "tab_gen sits in the first register of the context copy");
-        if (lane == gw_) hot[0] = tab_gen;
-    }
-#ifdef STCSP_STATIC_SLOTS
-    for (int gw = blockIdx.x * wpb + wib; gw < n_slots; gw += total_waves) expand_node<DR, L, CS, LITE, W, KR>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env);
-#else
-    // Slots: the first one by position, every further one by ticket -- slots differ widely in cost (a chain of up to `chain`
-    // expansions, each anything between a failed sweep and a leaf with a new state), and with a fixed stride the round waits for
-    // the wavefront whose share happened to be the dearest. The ticket for the NEXT slot is requested before the current one is
-    // expanded (its latency disappears behind the node load); kSlotCursors counters deal interleaved tickets.
-    {
-        const CtlLayout L_(c_world);
-        const int ncur = min(kSlotCursors, (int)gridDim.x);  // (a grid smaller than the counters: every residue needs a workgroup)
-        const int cur = (int)blockIdx.x % ncur;
-        uint32_t *cursor = c_ctl + L_.slotcur0 + cur * CST;
-        for (int gw = blockIdx.x * wpb + wib; gw < n_slots;) {
-            unsigned ticket = 0;
-            if (lane == 0) ticket = atomicAdd(cursor, 1u);
-            if constexpr (DR > 4)
-                [[clang::always_inline]] expand_node<DR, L, CS, LITE, W, KR>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
-            else
-                expand_node<DR, L, CS, LITE, W, KR>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
-            gw = total_waves + (int)rflu(ticket) * ncur + cur;
-        }
-    }
-#endif
-    flush_env<DR>(c, env, blockIdx.x * wpb + wib, lane);
-    __syncthreads();
-#ifdef STCSP_PHASES
-    if (threadIdx.x == 0) {
-        add_stats(c, blockIdx.x, ST_CYC_STAGE, t_k1 - t_k0);
-        add_stats(c, blockIdx.x, ST_BLOCKS, 1);
-        add_stats(c, blockIdx.x, ST_CYC_BLOCK, PHASE_NOW() - t_k0);
-    }
-#endif
-    if (wib == 0) {
-        // No fence on either side of the ticket: what the finalizing wavefront reads of the other workgroups are cursors and
-        // counters, all of them written by returning agent-scope atomics that completed before the workgroup's barrier
-        // above; the node and edge records themselves are only read by LATER launches (a kernel boundary away). An
-        // agent-scope fence here costs 2-3.5 us on the critical path of every round (MI355X_MICROARCH.md, fence table).
-        unsigned t = 0;
-        if (lane == 0) t = atomicAdd(&c.plan->done_blocks, 1u);
-        if (rflu(t) == n_working - 1) {  // last working workgroup: every cursor of this round is final
-            if (lane == 0) __hip_atomic_store(&c.plan->done_blocks, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifndef STCSP_STATIC_SLOTS
-            // (every other wavefront of the launch has drawn its last ticket: the counters start the next round at zero)
-            if (lane < kSlotCursors) __hip_atomic_store(&c.ctl[CtlLayout(c.world).slotcur0 + lane * CST], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-            const unsigned long long t_k2 = PHASE_NOW();
-            (void)t_k2;
-            const Verdict vd = finalize_round(c, c.plan, lane, launch_id + 1u, a.parity);
-            mirror_plan(c, vd, lane);
-#ifdef STCSP_PHASES
-            if (lane == 0) {
-                add_stats(c, 0, ST_CYC_FINAL, PHASE_NOW() - t_k2);
-                add_stats(c, 0, ST_ROUNDS_FINAL, 1);
-            }
-#endif
-        }
-    }
+    constexpr int UW = 1;
+#include "dev_expand_kernel.inc"
+}
+// Models with more than 32 until constraints: the general, partly-staged kernels (DR = 4 and 8, like the long-key ones) with UW
+// expire words per node (UW = kMaxExpireWords: records carry expire_words(n_until_cons) of them, the rest are 0). CS: compacted sweeps.
+template <int DR, bool CS, int W, int KR, int UW>
+__global__ __launch_bounds__(256, (STCSP_EXPAND_WAVES > 1 ? STCSP_EXPAND_WAVES : (DR <= 4 ? STCSP_WIDE_WAVES : STCSP_BLOCK8_WAVES))) void k_expand_until(const Ctx *__restrict__ cp, const Plan *__restrict__ plan_arg, unsigned launch_id, uint32_t tab_gen) {
+    static_assert(DR >= 4 && UW > 1, "the until-heavy kernels are general DR = 4 / 8 kernels");
+    constexpr int L = 0;
+    constexpr bool LITE = false, BIG = false;
+#include "dev_expand_kernel.inc"
 }
 
 // ------------------------------------------------------------------ k_probe (tests / diagnostics)
@@ -1064,9 +967,31 @@ __device__ unsigned emit_state_node(const Ctx &c, int lane, int ro, uint32_t *ou
     return 0u;
 }
 
+// ... with expire words 1 .. UW-1 after the block (more than 32 until constraints)
+template <int DR, int UW>
+__device__ unsigned emit_state_node(const Ctx &c, int lane, int ro, uint32_t *out_base, uint32_t out_cap, int parity,
+                                    const CommitOut &co, uint32_t expire, ExpireHi<UW> hi, const uint32_t (&blk)[DR], uint32_t seed) {
+    const CtlLayout L(c.world);
+    uint32_t np = 0;
+    if (lane == 0) np = atomicAdd(&c.ctl[L.out(parity, ro)], 1u);
+    np = rflu(np);
+    if (np + 1 > out_cap) return ERR_OUT_OVERFLOW;
+    uint32_t *dst = out_base + ((size_t)ro * out_cap + np) * c.NS;
+    const unsigned long long gid = ((unsigned long long)c.rank << STCSP_GID_SHIFT) | co.idx;
+    if (lane < 4) dst[lane] = lane == 0 ? (uint32_t)gid : (lane == 1 ? (uint32_t)(gid >> 32) : (lane == 2 ? ((uint32_t)co.set | seed << kSetBits) : expire));
+#pragma unroll
+    for (int q = 0; q < DR; q++) {
+        int k = q * 64 + lane;
+        if (k < c.NK) dst[4 + k] = blk[q];
+    }
+    STCSP_REJOIN();
+    store_expire_hi<UW>(dst + 4 + c.NK, hi, expire_words(c.n_until_cons), lane);
+    return 0u;
+}
+
 // ------------------------------------------------------------------ k_commit (sharded runs)
-template <int DR, int KR = 1>
-__global__ __launch_bounds__(256) void k_commit(Ctx c, CommitArgs a) {
+template <int DR, int KR, int UW>
+__device__ __forceinline__ void commit_kernel(Ctx c, CommitArgs a) {
     const int lane = threadIdx.x & 63, wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const long long gw = (long long)blockIdx.x * 4 + wib;
     if (gw >= a.total) return;
@@ -1092,10 +1017,25 @@ __global__ __launch_bounds__(256) void k_commit(Ctx c, CommitArgs a) {
     unsigned err = co.ok ? 0u : co.err;
     if (co.ok && co.is_new) {
         if (lane == 0) add_stats(c, (int)(gw & 0x7fffffff), ST_NEWSTATES, 1);
-        err = emit_state_node<DR>(c, lane, ro, c.arena + p->out_base, p->out_cap, p->parity, co, expire, blk, 0u);
+        if constexpr (UW > 1) {
+            ExpireHi<UW> hi;
+            load_expire_hi<UW>(hi, pb + c.NK, expire_words(c.n_until_cons));
+            err = emit_state_node<DR, UW>(c, lane, ro, c.arena + p->out_base, p->out_cap, p->parity, co, expire, hi, blk, 0u);
+        } else {
+            err = emit_state_node<DR>(c, lane, ro, c.arena + p->out_base, p->out_cap, p->parity, co, expire, blk, 0u);
+        }
         if (err == ERR_OUT_OVERFLOW) err = ERR_COMMIT_OUT_OVERFLOW;
     }
     if (err && lane == 0) atomicMax(&c.ctl[CtlLayout(c.world).misc0 + MISC_ERROR * CST], (uint32_t)err);
+}
+template <int DR, int KR = 1>
+__global__ __launch_bounds__(256) void k_commit(Ctx c, CommitArgs a) {
+    commit_kernel<DR, KR, 1>(c, a);
+}
+// ... of candidates with UW expire words (more than 32 until constraints)
+template <int DR, int KR, int UW>
+__global__ __launch_bounds__(256) void k_commit_until(Ctx c, CommitArgs a) {
+    commit_kernel<DR, KR, UW>(c, a);
 }
 
 // gather the R regions of one owner's outbox into a contiguous array (for the all-to-all)
@@ -1158,7 +1098,8 @@ struct DonateArgs {
     int count[R], take[R];
     uint32_t pref[R + 1];         // prefix sums of take[]
 };
-__global__ __launch_bounds__(256) void k_donate(Ctx c, DonateArgs a, uint32_t *out) {
+template <bool XW>  // XW: more than 32 until constraints (k_donate_until)
+__device__ __forceinline__ void donate_kernel(Ctx c, DonateArgs a, uint32_t *out) {
     const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
     const uint32_t gw = blockIdx.x * 4 + wib;
     if (blockIdx.x == 0 && threadIdx.x < R) {  // account for what leaves
@@ -1178,9 +1119,16 @@ __global__ __launch_bounds__(256) void k_donate(Ctx c, DonateArgs a, uint32_t *o
     const uint32_t tag = (uint32_t)kload(c.img, c.o.sets + (int)(w2 & kSetMask) * (int)(sizeof(SetDesc) / 4) + (int)(offsetof(SetDesc, tag) / 4));
     if (lane < kXferHdr) rec[lane] = lane == 0 ? node[0] : (lane == 1 ? node[1] : (lane == 2 ? tag : (lane == 3 ? node[3] : (lane == 4 ? w2 >> kSetBits : 0u))));
     for (int k = lane; k < c.NK; k += 64) rec[kXferHdr + k] = node[4 + k];
+    if constexpr (XW) {  // expire words 1 .. nw-1, which follow the node's block, go to header words [5..7]
+        const int nw = expire_words(c.n_until_cons);
+        if (lane + 1 < nw) rec[kXferExpire + lane] = node[4 + c.NK + lane];
+    }
 }
+__global__ __launch_bounds__(256) void k_donate(Ctx c, DonateArgs a, uint32_t *out) { donate_kernel<false>(c, a, out); }
+__global__ __launch_bounds__(256) void k_donate_until(Ctx c, DonateArgs a, uint32_t *out) { donate_kernel<true>(c, a, out); }
 // k_adopt: received transfer records become open nodes of the segment k_open_segment has just opened
-__global__ __launch_bounds__(256) void k_adopt(Ctx c, const uint32_t *recs, long long total) {
+template <bool XW>  // (k_donate)
+__device__ __forceinline__ void adopt_kernel(Ctx c, const uint32_t *recs, long long total) {
     const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
     const long long gw = (long long)blockIdx.x * 4 + wib;
     if (gw >= total) return;
@@ -1203,7 +1151,13 @@ __global__ __launch_bounds__(256) void k_adopt(Ctx c, const uint32_t *recs, long
     uint32_t *dst = c.arena + p->out_base + ((size_t)ro * p->out_cap + np) * c.NS;
     if (lane < 4) dst[lane] = lane == 0 ? rec[0] : (lane == 1 ? rec[1] : (lane == 2 ? ((uint32_t)set | rec[4] << kSetBits) : rec[3]));
     for (int k = lane; k < c.NK; k += 64) dst[4 + k] = rec[kXferHdr + k];
+    if constexpr (XW) {
+        const int nw = expire_words(c.n_until_cons);
+        if (lane + 1 < nw) dst[4 + c.NK + lane] = rec[kXferExpire + lane];
+    }
 }
+__global__ __launch_bounds__(256) void k_adopt(Ctx c, const uint32_t *recs, long long total) { adopt_kernel<false>(c, recs, total); }
+__global__ __launch_bounds__(256) void k_adopt_until(Ctx c, const uint32_t *recs, long long total) { adopt_kernel<true>(c, recs, total); }
 
 // ------------------------------------------------------------------ k_tabulate
 // Tuple bitmap of one point constraint, filled in on the device: one THREAD per tuple of the full initial

@@ -31,8 +31,8 @@ constexpr int kSibDepth = 4;  // (default; Ctx::sib_depth is what a launch uses:
 __host__ __device__ inline int wave_sib_offset(int NK, int stack_slots, bool lite) {
     return (lite ? 0 : (kMaxLowVars + stack_slots) * 64) + ((NK + kLdsStatWords + 63) & ~63);
 }
-__host__ __device__ inline int wave_scratch_words(int NK, int stack_slots, bool lite, int sib_depth) {
-    return wave_sib_offset(NK, stack_slots, lite) + sib_depth * ((4 + NK + 3) & ~3);
+__host__ __device__ inline int wave_scratch_words(int NK, int stack_slots, bool lite, int sib_depth, int UW = 1) {
+    return wave_sib_offset(NK, stack_slots, lite) + sib_depth * node_stride(NK, 1, UW);  // (sibling entries: node records)
 }
 constexpr int kMissStride = 66;  // set, nfirst, 64 values
 constexpr uint32_t kPending = 0xffffffffu;

@@ -2,6 +2,7 @@
 // the wavefront-cooperative revision (revise_point), the lane-per-item sweep and node classification
 // (process_node). Included by engine.hip only.
 #pragma once
+#include <type_traits>
 #include "dev_layout.hpp"
 namespace stcsp {
 namespace dev {
@@ -854,6 +855,48 @@ struct LeafOut {
     uint32_t evals[DR];     // edge label (Edge::values), lane-striped
     uint32_t nblk[DR];      // time-advanced block, lane-striped
 };
+// More than 32 until constraints (the kernels with UW = kMaxExpireWords): expire words 1 .. UW-1 next to the header's word 0,
+// wave-uniform (scalar registers). A lane picks a word with a select chain: an indexed private array would live in scratch.
+// Words at and above the record's expire_words(n_until_cons) are 0.
+template <int UW>
+struct ExpireHi {
+    uint32_t w[UW - 1];
+    __device__ __forceinline__ uint32_t word(uint32_t w0, int i) const {  // expire word i, given word 0
+        uint32_t r = w0;
+#pragma unroll
+        for (int k = 1; k < UW; k++) r = i == k ? w[k - 1] : r;
+        return r;
+    }
+    __device__ __forceinline__ void uniform() {
+#pragma unroll
+        for (int k = 0; k < UW - 1; k++) w[k] = rflu(w[k]);
+    }
+};
+template <int UW>
+struct NodeHdrX : NodeHdr {
+    ExpireHi<UW> hi;
+};
+template <int DR, int UW>
+struct LeafOutX : LeafOut<DR> {
+    ExpireHi<UW> new_hi;
+};
+// UW = 1 (at most 32 until constraints): the plain header and leaf outputs
+template <int UW>
+using NodeHdrOf = std::conditional_t<(UW > 1), NodeHdrX<UW>, NodeHdr>;
+template <int DR, int UW>
+using LeafOutOf = std::conditional_t<(UW > 1), LeafOutX<DR, UW>, LeafOut<DR>>;
+// expire words 1 .. nw-1 of a record (device_types.hpp: after the block of node records, sibling entries and candidates)
+template <int UW, typename T>
+__device__ __forceinline__ void load_expire_hi(ExpireHi<UW> &hi, const T *src, int nw) {
+#pragma unroll
+    for (int k = 0; k < UW - 1; k++) hi.w[k] = rflu(k + 1 < nw ? (uint32_t)src[k] : 0u);
+}
+template <int UW, typename T>
+__device__ __forceinline__ void store_expire_hi(T *dst, const ExpireHi<UW> &hi, int nw, int lane) {
+    if (lane + 1 < nw) dst[lane] = (T)hi.word(0u, lane + 1);
+    STCSP_REJOIN();
+}
+
 struct CommitOut {
     uint32_t idx;  // local state index
     bool is_new, ok;
@@ -866,6 +909,9 @@ __device__ CommitOut table_commit(const Ctx &c, int lane, int ro, uint32_t kw, u
 template <int DR>
 __device__ unsigned emit_state_node(const Ctx &c, int lane, int ro, uint32_t *out_base, uint32_t out_cap, int parity,
                                     const CommitOut &co, uint32_t expire, const uint32_t (&blk)[DR], uint32_t seed);
+template <int DR, int UW>
+__device__ unsigned emit_state_node(const Ctx &c, int lane, int ro, uint32_t *out_base, uint32_t out_cap, int parity,
+                                    const CommitOut &co, uint32_t expire, ExpireHi<UW> hi, const uint32_t (&blk)[DR], uint32_t seed);
 
 // ------------------------------------------------------------------ one search node
 // Propagate the block in `dom` to its fixpoint under the node's constraint set and classify the
@@ -1244,9 +1290,24 @@ __device__ int revise_batch(const Ctx &c, const Img<L> &G, WaveEnv<DR> &S, Dom<D
     return nb + __popcll(__ballot(noop));
 }
 
-template <int DR, int L, bool CS, bool LITE, int KR = 1>
+// The leaf's until flags when there are more than 32 (UW > 1): f0 / f1 = ballots of the flags of until constraints 0..63 / 64..127
+// (expired before, or expiring at this leaf). They are the new expire words, and key words 1 + n_sig + u (lane j: word j, kw2: 64 + j).
+template <int UW, int KR>
+__device__ __forceinline__ void until_flags(const Ctx &c, int lane, unsigned long long f0, unsigned long long f1, uint32_t &new_expire,
+                                           ExpireHi<UW> &new_hi, uint32_t &kw, uint32_t &kw2) {
+    static_assert(UW >= 2 && UW <= kMaxExpireWords, "two ballots hold 128 flags");
+    new_expire = (uint32_t)f0;
+#pragma unroll
+    for (int k = 1; k < UW; k++) new_hi.w[k - 1] = k == 1 ? (uint32_t)(f0 >> 32) : (k == 2 ? (uint32_t)f1 : (uint32_t)(f1 >> 32));
+    const int nu = c.n_until_cons;
+    const int u0 = lane - 1 - c.n_sig, u1 = lane + 63 - c.n_sig;
+    if (u0 >= 0 && u0 < nu) kw = (uint32_t)((u0 < 64 ? f0 >> u0 : f1 >> (u0 - 64)) & 1ull);
+    if (KR == 2 && u1 >= 0 && u1 < nu) kw2 = (uint32_t)((u1 < 64 ? f0 >> u1 : f1 >> (u1 - 64)) & 1ull);
+}
+
+template <int DR, int L, bool CS, bool LITE, int KR = 1, int UW = 1>
 __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_vals, int *lds_stk, int *ldom, Dom<DR> &dom,
-                            const NodeHdr &hd, int gw, WaveEnv<DR> &S, BranchOut &bo, LeafOut<DR> &lo) {
+                            const NodeHdrOf<UW> &hd, int gw, WaveEnv<DR> &S, BranchOut &bo, LeafOutOf<DR, UW> &lo) {
     const int set = hd.set;
     const uint32_t seed = hd.seed, expire = hd.expire;
     if (set != S.set) {
@@ -1397,7 +1458,12 @@ __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_va
                         if (m != D0) atomicAnd((unsigned *)&ldom[it.idx[0]], m);
                         if (newY != D1) atomicAnd((unsigned *)&ldom[it.idx[1]], newY);
                     } else if (it.type == IT_UNTIL) {
-                        if (!((expire >> it.aux) & 1u) && __popc(D0) == 1 && __popc(D1) == 1) {
+                        bool live;  // until constraint it.aux has not expired (UW > 1: the lane's ordinal picks its word)
+                        if constexpr (UW == 1)
+                            live = !((expire >> it.aux) & 1u);
+                        else
+                            live = !((hd.hi.word(expire, it.aux >> 5) >> (it.aux & 31)) & 1u);
+                        if (live && __popc(D0) == 1 && __popc(D1) == 1) {
                             int vx = P.v(c.o.var_lb + it.idx[0]) + __ffs((int)D0) - 1, vy = P.v(c.o.var_lb + it.idx[1]) + __ffs((int)D1) - 1;
                             if (vx != 1 && vy != 1) lfail = true;
                         }
@@ -1680,16 +1746,28 @@ __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_va
             const uint32_t sd2 = dom.gather(sv2);
             if (s2) kw2 = (uint32_t)(P.v(c.o.var_lb + sv2) + __ffs((int)sd2) - 1);
         }
-        for (int u = 0; u < c.n_until_cons; u++) {
-            int y = P.u(c.o.until_y + u);
-            uint32_t DY = dom.get(y);
-            bool ex = (expire >> u) & 1u;
-            if (!ex && P.u(c.o.var_lb + y) + __ffs((int)DY) - 1 == 1) {
-                ex = true;
-                new_expire |= 1u << u;
+        if constexpr (UW > 1) {
+            // lane j takes until constraints j and 64 + j (gathers, like the signature variables); the flags come back as ballots
+            const int nu = c.n_until_cons;
+            const bool a0 = lane < nu, a1 = lane + 64 < nu;
+            const int y0 = P.v(c.o.until_y + (a0 ? lane : 0)), y1 = P.v(c.o.until_y + (a1 ? lane + 64 : 0));
+            const uint32_t d0 = dom.gather(y0), d1 = dom.gather(y1);
+            const bool e0 = (hd.hi.word(expire, lane >> 5) >> (lane & 31)) & 1u, e1 = (hd.hi.word(expire, 2 + (lane >> 5)) >> (lane & 31)) & 1u;
+            const unsigned long long f0 = __ballot(a0 && (e0 || P.v(c.o.var_lb + y0) + __ffs((int)d0) - 1 == 1));
+            const unsigned long long f1 = __ballot(a1 && (e1 || P.v(c.o.var_lb + y1) + __ffs((int)d1) - 1 == 1));
+            until_flags<UW, KR>(c, lane, f0, f1, new_expire, lo.new_hi, kw, kw2);
+        } else {
+            for (int u = 0; u < c.n_until_cons; u++) {
+                int y = P.u(c.o.until_y + u);
+                uint32_t DY = dom.get(y);
+                bool ex = (expire >> u) & 1u;
+                if (!ex && P.u(c.o.var_lb + y) + __ffs((int)DY) - 1 == 1) {
+                    ex = true;
+                    new_expire |= 1u << u;
+                }
+                if (lane == 1 + c.n_sig + u) kw = ex ? 1u : 0u;
+                if (KR == 2 && lane + 64 == 1 + c.n_sig + u) kw2 = ex ? 1u : 0u;
             }
-            if (lane == 1 + c.n_sig + u) kw = ex ? 1u : 0u;
-            if (KR == 2 && lane + 64 == 1 + c.n_sig + u) kw2 = ex ? 1u : 0u;
         }
         if (lane == 0) kw = next_tag;
     }

@@ -307,9 +307,9 @@ struct BranchOutWide {
 
 // W = kWIntervals: interval domains (dev_interval.hpp), the same node loop with bounds in place of bitsets
 
-template <int DR, int W, int L, int KR = 1>
-__device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *lds_vals, int *lds_stk, int *ldom, Dom<DR> &dom, const NodeHdr &hd,
-                                 int gw, WaveEnv<DR> &S, BranchOutWide &bo, LeafOut<DR> &lo) {
+template <int DR, int W, int L, int KR = 1, int UW = 1>
+__device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *lds_vals, int *lds_stk, int *ldom, Dom<DR> &dom, const NodeHdrOf<UW> &hd,
+                                 int gw, WaveEnv<DR> &S, BranchOutWide &bo, LeafOutOf<DR, UW> &lo) {
     const int set = hd.set;
     const uint32_t seed = hd.seed, expire = hd.expire;
     const int NK1 = c.N * c.K;
@@ -366,10 +366,15 @@ __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *l
             // X until Y (enforceUntilConsistency, :598-614): a check at point 0, never a pruning
             const int x = STCSP_ID(idx[0]), y = STCSP_ID(idx[1]), ord = STCSP_ID(aux);
             S.n_revs++;
+            bool live;  // until constraint `ord` has not expired (UW > 1: its word picked from the wave-uniform ones)
+            if constexpr (UW == 1)
+                live = !((expire >> ord) & 1u);
+            else
+                live = !((hd.hi.word(expire, ord >> 5) >> (ord & 31)) & 1u);
             if constexpr (IV) {
-                if (!((expire >> ord) & 1u) && ldom[x] == ldom[NK1 + x] && ldom[y] == ldom[NK1 + y])
+                if (live && ldom[x] == ldom[NK1 + x] && ldom[y] == ldom[NK1 + y])
                     if (rfl(ldom[x]) != 1 && rfl(ldom[y]) != 1) consistent = false;
-            } else if (!((expire >> ord) & 1u)) {
+            } else if (live) {
                 const WDom<W> DX = wload<W>(ldom, NK1, x), DY = wload<W>(ldom, NK1, y);
                 if (DX.count() == 1 && DY.count() == 1) {
                     const int vx = P.u(c.o.var_lb + x) + DX.lowest(), vy = P.u(c.o.var_lb + y) + DY.lowest();
@@ -506,20 +511,30 @@ __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *l
             const int val2 = value_of(sv2);
             if (s2) kw2 = (uint32_t)val2;
         }
-        for (int u = 0; u < c.n_until_cons; u++) {
-            const int y = P.u(c.o.until_y + u);
-            int vy;
-            if constexpr (IV)
-                vy = rfl(ldom[y]);
-            else
-                vy = rfl(P.u(c.o.var_lb + y) + wload<W>(ldom, NK1, y).lowest());
-            bool ex = (expire >> u) & 1u;
-            if (!ex && vy == 1) {
-                ex = true;
-                new_expire |= 1u << u;
+        if constexpr (UW > 1) {
+            // lane j takes until constraints j and 64 + j (process_node)
+            const int nu = c.n_until_cons;
+            const bool a0 = lane < nu, a1 = lane + 64 < nu;
+            const int v0 = value_of(P.v(c.o.until_y + (a0 ? lane : 0))), v1 = value_of(P.v(c.o.until_y + (a1 ? lane + 64 : 0)));
+            const bool e0 = (hd.hi.word(expire, lane >> 5) >> (lane & 31)) & 1u, e1 = (hd.hi.word(expire, 2 + (lane >> 5)) >> (lane & 31)) & 1u;
+            const unsigned long long f0 = __ballot(a0 && (e0 || v0 == 1)), f1 = __ballot(a1 && (e1 || v1 == 1));
+            until_flags<UW, KR>(c, lane, f0, f1, new_expire, lo.new_hi, kw, kw2);
+        } else {
+            for (int u = 0; u < c.n_until_cons; u++) {
+                const int y = P.u(c.o.until_y + u);
+                int vy;
+                if constexpr (IV)
+                    vy = rfl(ldom[y]);
+                else
+                    vy = rfl(P.u(c.o.var_lb + y) + wload<W>(ldom, NK1, y).lowest());
+                bool ex = (expire >> u) & 1u;
+                if (!ex && vy == 1) {
+                    ex = true;
+                    new_expire |= 1u << u;
+                }
+                if (lane == 1 + c.n_sig + u) kw = ex ? 1u : 0u;
+                if (KR == 2 && lane + 64 == 1 + c.n_sig + u) kw2 = ex ? 1u : 0u;
             }
-            if (lane == 1 + c.n_sig + u) kw = ex ? 1u : 0u;
-            if (KR == 2 && lane + 64 == 1 + c.n_sig + u) kw2 = ex ? 1u : 0u;
         }
         if (lane == 0) kw = next_tag;
     }

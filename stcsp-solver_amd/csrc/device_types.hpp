@@ -6,9 +6,12 @@
 //       word[p * N + v]  bit i  <=>  value (lb[v] + i) is in the domain of v at time point p
 // (|D| <= 32 => one word per (v,p); W = 1).  A node record is a 4-word header + the block:
 //       [0] src state id (low 32)   [1] src state id (high 32: owner rank in sharded mode)
-//       [2] constraint-set index     [3] until-expire bits (Constraint::expire, one per UNTIL)
+//       [2] constraint-set index     [3] until-expire bits (Constraint::expire, one per UNTIL): word 0
 //       [4 ...] block
+//       [4 + N*K ...] until-expire words 1 .. UW-1 (models with more than 32 until constraints only)
 // padded to a multiple of 4 words (16 B) so lanes can move it with aligned wide accesses.
+// UW = expire_words(n_until_cons): bit u of expire word u >> 5 is until constraint u's flag. At UW = 1 (at most 32 until
+// constraints) every record below is what it was before the extension, word for word.
 #pragma once
 #include <cstdint>
 
@@ -203,16 +206,24 @@ STCSP_HD int key_owner(unsigned long long h, int world, int kl, uint32_t tag) {
     return (int)((h >> 40) % (unsigned)world);
 }
 
-// record strides in words (all multiples of 4)
-STCSP_HD int node_stride(int N, int K) { return (4 + N * K + 3) & ~3; }
-STCSP_HD int cand_stride(int N, int K, int sig_len) { return (kCandHdr + sig_len + N + N * K + 3) & ~3; }
+// until-expire words of a record: one per 32 until constraints, at least one (the signature limit, 1 + n_sig + n_until_cons
+// <= kMaxKeyWords, keeps it at most kMaxExpireWords)
+constexpr int kMaxExpireWords = 4;
+STCSP_HD int expire_words(int n_until_cons) { return n_until_cons <= 32 ? 1 : (n_until_cons + 31) / 32; }
+
+// record strides in words (all multiples of 4). Expire words 1 .. UW-1 follow the block in node records (and in the sibling
+// stack entries, which are node records in LDS) and in candidate records; transfer records keep them in header words [5..7].
+STCSP_HD int node_stride(int N, int K, int UW = 1) { return (4 + N * K + (UW - 1) + 3) & ~3; }
+STCSP_HD int cand_stride(int N, int K, int sig_len, int UW = 1) { return (kCandHdr + sig_len + N + N * K + (UW - 1) + 3) & ~3; }
 STCSP_HD int edge_stride(int N) { return (4 + N + 3) & ~3; }
 // transfer record of an open search node (frontier redistribution between shards):
-//   [0,1] src state gid  [2] constraint-set TAG (ordinals differ between shards)  [3] until-expire bits
-//   [4] dirty seed  [5..7] spare  [8..) the N*K-word block
+//   [0,1] src state gid  [2] constraint-set TAG (ordinals differ between shards)  [3] until-expire word 0
+//   [4] dirty seed  [5..7] until-expire words 1..3 (0 beyond UW)  [8..) the N*K-word block
 constexpr int kXferHdr = 8;
-STCSP_HD int xfer_stride(int N, int K) { return (kXferHdr + N * K + 3) & ~3; }
-// candidate record: [0,1] src gid  [2] next set tag  [3] expire bits  [4,5] key hash  [6,7] spare
-//                   [8..) signature, then N edge-label values, then the N*K time-advanced block
+constexpr int kXferExpire = 5;  // header word of expire word 1
+static_assert(kXferExpire + kMaxExpireWords - 1 <= kXferHdr, "the transfer header holds every expire word");
+STCSP_HD int xfer_stride(int N, int K, int UW = 1) { return (void)UW, (kXferHdr + N * K + 3) & ~3; }
+// candidate record: [0,1] src gid  [2] next set tag  [3] expire word 0  [4,5] key hash  [6,7] spare
+//                   [8..) signature, then N edge-label values, then the N*K time-advanced block, then expire words 1 .. UW-1
 
 }  // namespace stcsp

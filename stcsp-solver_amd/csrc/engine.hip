@@ -134,6 +134,11 @@ struct stcsp_engine {
     // kernels at DR = 4 and 8 get the second key register (k_expand<DR, false, CS, false, false, W, 2>, k_commit<DR, 2>), so the
     // LITE / prefix kernels of the shipped programs (keys of at most 64 words) stay exactly as they are.
     bool long_key() const { return ctx.KL > 64; }
+    // More than 32 until constraints: records carry expire_words(n_until_cons) expire words (device_types.hpp). They run the
+    // k_expand_until / k_commit_until kernels with kMaxExpireWords words per node -- the general, partly-staged kernels at DR = 4
+    // and 8, with one or two key registers -- so the kernels of models with at most 32 until constraints stay exactly as they are.
+    bool many_until() const { return ctx.n_until_cons > 32; }
+    int expire_w() const { return expire_words(ctx.n_until_cons); }
     bool interpreted = false;     // some wavefront-revised constraint has no tuple bitmap (postfix interpreter: uniformly expensive nodes)
     bool wide_conditional = false;  // some conditional constraint spans more than kWideConditional tuples (the juggling family's `A == if B0 eq 1 then next B0 else if ...`)
     bool host_view_fresh = false;  // h_ctl / h_plan were read after the last device work (expand_local -> commit)
@@ -260,7 +265,7 @@ struct stcsp_engine {
             }
         if (const char *ev = getenv("STCSP_LITE")) lite = lite && atoi(ev) != 0;  // tuning switch
         if (mgr.W > 1) lite = false;  // (wide domains: every item is revised by dev_wide.hpp's bounds propagation)
-        if (long_key()) lite = false;
+        if (long_key() || many_until()) lite = false;
         if (DR > 4) lite = false;  // (blocks of more than 256 words: the general, partly-staged kernels only)
         // one contiguous image; every section starts on a 16-byte boundary
         std::vector<uint32_t> img;
@@ -441,13 +446,13 @@ struct stcsp_engine {
         // occupancy the kernels' registers allow (STCSP_BLOCK8_WAVES wavefronts per SIMD = as many 4-wavefront workgroups per CU) leaves
         // room for in the 160 KB of a CU -- depth 4 at 2 wavefronts per SIMD -- and within the 64 KB a launch gets without asking.
         if (DR > 4) {
-            auto wg_bytes = [&](int d) { return (size_t)4 * wave_scratch_words(ctx.NK, ctx.stack_slots, lite, d) * sizeof(int); };
+            auto wg_bytes = [&](int d) { return (size_t)4 * wave_scratch_words(ctx.NK, ctx.stack_slots, lite, d, expire_w()) * sizeof(int); };
             while (ctx.sib_depth > 1 && (wg_bytes(ctx.sib_depth) > 64 * 1024 || (size_t)STCSP_BLOCK8_WAVES * wg_bytes(ctx.sib_depth) > 160 * 1024)) ctx.sib_depth--;
         }
-        const size_t scratch = (size_t)4 * wave_scratch_words(ctx.NK, ctx.stack_slots, lite, ctx.sib_depth) * sizeof(int);
+        const size_t scratch = (size_t)4 * wave_scratch_words(ctx.NK, ctx.stack_slots, lite, ctx.sib_depth, expire_w()) * sizeof(int);
         if (scratch > 160 * 1024) return fail(STCSP_E_UNSUPPORTED, "expression stack too deep for LDS");
         // stage the image in LDS when image + scratch leave room for >= 2 workgroups per CU
-        img_in_lds = (size_t)o.words * 4 + scratch <= 64 * 1024 && mgr.W == 1 && !long_key() && DR <= 4;  // (the wide, long-key and DR = 8 kernels exist in the partly-staged form only)
+        img_in_lds = (size_t)o.words * 4 + scratch <= 64 * 1024 && mgr.W == 1 && !long_key() && !many_until() && DR <= 4;  // (the wide, long-key, until-heavy and DR = 8 kernels exist in the partly-staged form only)
         if (const char *ev = getenv("STCSP_IMG_LDS")) img_in_lds = img_in_lds && atoi(ev) != 0;  // tuning switch
         ctx.stage_words = img_in_lds ? o.words : 0;
         lds_bytes = scratch + (size_t)ctx.stage_words * 4;
@@ -521,7 +526,7 @@ struct stcsp_engine {
                         ctx.stage_words = 0;
                 }
             }
-            prefix_complete = !lite && !img_in_lds && !big && !compact_sweeps && mgr.W == 1 && !long_key() && DR <= 4 && prefix_need > 0 && ctx.stage_words >= prefix_need &&
+            prefix_complete = !lite && !img_in_lds && !big && !compact_sweeps && mgr.W == 1 && !long_key() && !many_until() && DR <= 4 && prefix_need > 0 && ctx.stage_words >= prefix_need &&
                               !(getenv("STCSP_PREFIX_KERNEL") && atoi(getenv("STCSP_PREFIX_KERNEL")) == 0);
 #ifdef STCSP_PHASES
             if (DR == 4) prefix_complete = false;
@@ -590,7 +595,6 @@ struct stcsp_engine {
             return fail(STCSP_E_UNSUPPORTED, "interval domains: 2*N*K = 2*%d*%d exceeds the block limit of %d words (64 * kMaxIntervalRegs)", N, K, 64 * kMaxIntervalRegs);
         if ((long long)N * K * W > 64 * kMaxDomRegs)
             return fail(STCSP_E_UNSUPPORTED, "N*K*W = %d*%d*%d exceeds the %d-word register-resident block", N, K, W, 64 * kMaxDomRegs);
-        if (mgr.n_until_cons > 32) return fail(STCSP_E_UNSUPPORTED, "more than 32 until constraints");
         // the key [set tag, signature...] and the 64-bit slot word share one 128-word table entry (table_entry_shift)
         if (1 + mgr.n_sig + mgr.n_until_cons > kMaxKeyWords)
             return fail(STCSP_E_UNSUPPORTED, "signature of %d words (%d next variables, %d until flags): at most %d words (a state key of %d)",
@@ -623,12 +627,12 @@ struct stcsp_engine {
         ctx.K = K;
         ctx.NK = N * K * W;  // block words (chunk-major for W > 1: word(c, p, v) = c*N*K + p*N + v)
         ctx.W = W;
-        ctx.NS = node_stride(N, K * W);
+        ctx.n_until_cons = mgr.n_until_cons;
+        ctx.NS = node_stride(N, K * W, expire_w());
         ctx.sig_len = mgr.n_sig + mgr.n_until_cons;
         ctx.n_sig = mgr.n_sig;
-        ctx.n_until_cons = mgr.n_until_cons;
         ctx.KL = 1 + ctx.sig_len;
-        ctx.CS = cand_stride(N, K * W, ctx.sig_len);
+        ctx.CS = cand_stride(N, K * W, ctx.sig_len, expire_w());
         ctx.ES = edge_stride(N);
         ctx.world = opt.world;
         ctx.sharded = sharded ? 1 : 0;
@@ -658,10 +662,11 @@ struct stcsp_engine {
                 if (pre < 0) return fail(pre, "%s", mgr.error.c_str());
             }
         }
-        // block registers per lane: 1, 2, 4 or 8 (5..7 round up to 8); long keys: the KR = 2 kernels exist at DR = 4 and 8 only
+        // block registers per lane: 1, 2, 4 or 8 (5..7 round up to 8); long keys: the KR = 2 kernels exist at DR = 4 and 8 only, and
+        // so do the kernels for more than 32 until constraints
         DR = (N * K * W + 63) / 64;
         if (DR > 4) DR = 8;
-        if (DR == 3 || ctx.KL > 64) DR = std::max(DR, 4);
+        if (DR == 3 || ctx.KL > 64 || many_until()) DR = std::max(DR, 4);
         HIPCHK(d_arr_data.upload(mgr.array_data));
         ctx.arr_data = d_arr_data.p;
         rc = upload_program();
@@ -1216,8 +1221,38 @@ struct stcsp_engine {
         else
             hipLaunchKernelGGL((k_expand<8, false, false, false, false, 1, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
     }
+    // more than 32 until constraints (DR = 4 or 8): W = 1 (plain or compacted sweeps), 2, 4 and, at DR = 4, interval domains
+    template <int DRT, int KR>
+    const void *until_fn() const {
+        constexpr int UW = kMaxExpireWords;
+        if (mgr.intervals) return DRT == 4 ? (const void *)k_expand_until<4, false, kWIntervals, KR, UW> : nullptr;
+        if (mgr.W == 2) return (const void *)k_expand_until<DRT, false, 2, KR, UW>;
+        if (mgr.W > 2) return (const void *)k_expand_until<DRT, false, 4, KR, UW>;
+        if (compact_sweeps) return (const void *)k_expand_until<DRT, true, 1, KR, UW>;
+        return (const void *)k_expand_until<DRT, false, 1, KR, UW>;
+    }
+    template <int DRT, int KR>
+    void launch_until() {
+        constexpr int UW = kMaxExpireWords;
+        const Ctx *cp = (const Ctx *)d_ctx.p;
+        const Plan *pp = (const Plan *)d_plan.p;
+        if (mgr.intervals) {
+            if constexpr (DRT == 4)
+                hipLaunchKernelGGL((k_expand_until<4, false, kWIntervals, KR, UW>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+        } else if (mgr.W == 2) {
+            hipLaunchKernelGGL((k_expand_until<DRT, false, 2, KR, UW>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+        } else if (mgr.W > 2) {
+            hipLaunchKernelGGL((k_expand_until<DRT, false, 4, KR, UW>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+        } else if (compact_sweeps) {
+            hipLaunchKernelGGL((k_expand_until<DRT, true, 1, KR, UW>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+        } else {
+            hipLaunchKernelGGL((k_expand_until<DRT, false, 1, KR, UW>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+        }
+    }
     template <int DRT>
     const void *expand_fn() const {
+        if constexpr (DRT >= 4)
+            if (many_until()) return long_key() ? until_fn<DRT, 2>() : until_fn<DRT, 1>();
         if constexpr (DRT == 8) return long_key() ? expand8_fn<2>() : expand8_fn<1>();
         else return expand_fn_le4<DRT>();
     }
@@ -1262,6 +1297,12 @@ struct stcsp_engine {
     }
     template <int DRT>
     void launch_expand() {
+        if constexpr (DRT >= 4)
+            if (many_until()) {
+                if (long_key()) launch_until<DRT, 2>();
+                else launch_until<DRT, 1>();
+                return;
+            }
         if constexpr (DRT == 8) {
             if (long_key()) launch_expand8<2>();
             else launch_expand8<1>();
@@ -1324,8 +1365,9 @@ struct stcsp_engine {
     // upload of a program with sets that have no row yet (creation, a translation stop, a set import).
     bool own_init_rows = false;
     std::map<int32_t, std::vector<uint32_t>> fresh_rows;  // set tag -> its row
+    // Models with more than 32 until constraints skip it (their sets keep the plain rows): the probe kernel takes one expire word.
     int fresh_init() {
-        if (!own_init_rows || mgr.W != 1) return STCSP_OK;
+        if (!own_init_rows || mgr.W != 1 || many_until()) return STCSP_OK;
         std::vector<int> todo;
         for (size_t si = 0; si < prog.sets.size(); si++)
             if (prog.set_fresh_init[si] && !fresh_rows.count(mgr.sets[si]->tag)) todo.push_back((int)si);
@@ -1396,6 +1438,8 @@ struct stcsp_engine {
         if (sharded) return fail(STCSP_E_STATE, "propagate is for unsharded engines");
         if (mgr.intervals) return fail(STCSP_E_UNSUPPORTED, "propagate: the node-level seam takes one-word blocks (no interval domains)");
         if (mgr.W > 1) return fail(STCSP_E_UNSUPPORTED, "propagate: the node-level seam takes one-word blocks (every domain <= 32 values)");
+        if (many_until())
+            return fail(STCSP_E_UNSUPPORTED, "propagate: the node-level seam takes one expire word, at most 32 until constraints (this model has %d)", ctx.n_until_cons);
         if (set < 0 || set >= (int)prog.sets.size() || count < 0 || count > (1 << 24) || !blocks || !outcome)
             return fail(STCSP_E_INVALID, "propagate: bad arguments (set %d of %zu, count %lld)", set, prog.sets.size(), (long long)count);
         if (count == 0) return STCSP_OK;
@@ -1960,15 +2004,21 @@ struct stcsp_engine {
         ca.total = count;
         {
             dim3 grid((unsigned)((count + 3) / 4)), block(256);
+            constexpr int UW = kMaxExpireWords;
+            if (many_until() && DR != 4 && DR != 8) return fail(STCSP_E_INTERNAL, "no commit kernel for %d until constraints at DR = %d", ctx.n_until_cons, DR);
             switch (DR) {
                 case 1: hipLaunchKernelGGL((k_commit<1>), grid, block, 0, stream, ctx, ca); break;
                 case 2: hipLaunchKernelGGL((k_commit<2>), grid, block, 0, stream, ctx, ca); break;
                 case 4:
-                    if (long_key()) hipLaunchKernelGGL((k_commit<4, 2>), grid, block, 0, stream, ctx, ca);
+                    if (many_until() && long_key()) hipLaunchKernelGGL((k_commit_until<4, 2, UW>), grid, block, 0, stream, ctx, ca);
+                    else if (many_until()) hipLaunchKernelGGL((k_commit_until<4, 1, UW>), grid, block, 0, stream, ctx, ca);
+                    else if (long_key()) hipLaunchKernelGGL((k_commit<4, 2>), grid, block, 0, stream, ctx, ca);
                     else hipLaunchKernelGGL((k_commit<4>), grid, block, 0, stream, ctx, ca);
                     break;
                 case 8:
-                    if (long_key()) hipLaunchKernelGGL((k_commit<8, 2>), grid, block, 0, stream, ctx, ca);
+                    if (many_until() && long_key()) hipLaunchKernelGGL((k_commit_until<8, 2, UW>), grid, block, 0, stream, ctx, ca);
+                    else if (many_until()) hipLaunchKernelGGL((k_commit_until<8, 1, UW>), grid, block, 0, stream, ctx, ca);
+                    else if (long_key()) hipLaunchKernelGGL((k_commit<8, 2>), grid, block, 0, stream, ctx, ca);
                     else hipLaunchKernelGGL((k_commit<8, 1>), grid, block, 0, stream, ctx, ca);
                     break;
                 default: return fail(STCSP_E_INTERNAL, "no commit kernel for a block of %d registers", DR);
@@ -1997,7 +2047,7 @@ struct stcsp_engine {
         if (sp <= 0) return STCSP_OK;
         h_stack.resize((size_t)sp);
         HIPCHK(hipMemcpy(h_stack.data(), &d_plan.p->stack[0], (size_t)sp * sizeof(DevSegment), hipMemcpyDeviceToHost));
-        const int TS = xfer_stride(ctx.N, ctx.K * ctx.W);
+        const int TS = xfer_stride(ctx.N, ctx.K * ctx.W, expire_w());
         if (d_xfer.n < (size_t)want * TS) HIPCHK(d_xfer.alloc((size_t)want * TS));
         if ((rc = flush_ctx())) return rc;
         int64_t done = 0;
@@ -2023,7 +2073,7 @@ struct stcsp_engine {
                 acc += (uint32_t)a.take[r];
             }
             a.pref[R] = acc;
-            hipLaunchKernelGGL(k_donate, dim3((acc + 3) / 4), dim3(256), 0, stream, ctx, a, d_xfer.p + (size_t)done * TS);
+            hipLaunchKernelGGL(many_until() ? k_donate_until : k_donate, dim3((acc + 3) / 4), dim3(256), 0, stream, ctx, a, d_xfer.p + (size_t)done * TS);
             HIPCHK(hipGetLastError());
             done += acc;
         }
@@ -2047,7 +2097,7 @@ struct stcsp_engine {
             if ((rc = grow_arena((size_t)h_plan->arena_top + (size_t)R * cap * ctx.NS))) return rc;
         if ((rc = push_caps())) return rc;
         hipLaunchKernelGGL(k_open_segment, dim3(1), dim3(64), 0, stream, ctx, cap);
-        hipLaunchKernelGGL(k_adopt, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, stream, ctx, (const uint32_t *)records, (long long)count);
+        hipLaunchKernelGGL(many_until() ? k_adopt_until : k_adopt, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, stream, ctx, (const uint32_t *)records, (long long)count);
         hipLaunchKernelGGL(k_close_segment, dim3(1), dim3(64), 0, stream, ctx);
         HIPCHK(hipGetLastError());
         return STCSP_OK;  // not waited for (like commit): `records` must stay valid until the next expand_local / finish
@@ -2554,7 +2604,7 @@ int stcsp_engine_set_expand_budget(stcsp_engine *e, int64_t max_rounds, int64_t 
     e->step_min_open = min_open;
     return STCSP_OK;
 }
-int stcsp_engine_node_bytes(const stcsp_engine *e) { return e ? xfer_stride(e->ctx.N, e->ctx.K * e->ctx.W) * 4 : STCSP_E_INVALID; }
+int stcsp_engine_node_bytes(const stcsp_engine *e) { return e ? xfer_stride(e->ctx.N, e->ctx.K * e->ctx.W, e->expire_w()) * 4 : STCSP_E_INVALID; }
 int stcsp_engine_donate(stcsp_engine *e, int64_t want, void **ptr, int64_t *count) {
     if (!e || !ptr || !count) return STCSP_E_INVALID;
     return e->donate(want, ptr, count);

@@ -70,7 +70,7 @@ inline int stcsp_solve_sharded_impl(stcsp_engine *e, const stcsp_transport *t, c
     const int64_t budget_rounds = o && o->budget_rounds > 0 ? o->budget_rounds : 8;
     const int64_t share_per_rank = o && o->share_per_rank > 0 ? o->share_per_rank : 64;
     const int64_t max_steps = o && o->max_supersteps > 0 ? o->max_supersteps : 1000000;
-    const int64_t csw = e->ctx.CS, nsw = xfer_stride(e->ctx.N, e->ctx.K * e->ctx.W);
+    const int64_t csw = e->ctx.CS, nsw = xfer_stride(e->ctx.N, e->ctx.K * e->ctx.W, e->expire_w());
     double t_coll = 0;
     stcsp_sharded_stats s{};
     int pending = STCSP_OK;  // this rank's engine error the peers have not heard of yet (e->err holds its text)
