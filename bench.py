@@ -16,16 +16,21 @@ as `search_only_nodes_per_s`.  The unit is the search-tree node = one propagatio
 classification, the engine's analogue of one solverSolveRe call (reference
 src/solveralgorithm.cpp:733); each implementation counts its own tree.
 
-The automaton of the last timed step is checked against the reference's recorded canonical sha256
-(tests/golden/reference_golden.json): a mismatch makes bench.py exit non-zero.
-
-One JSON line on stdout (rank 0).  Extra objects:
+One JSON line on stdout (rank 0).  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints
+the line; beside the headline it reports only what the timed steps' own counters give:
   roofline     dominant kernel k_expand: algorithmic bytes per launch / average launch duration,
                HIP events on the engine's stream, against the 8 TB/s HBM3E peak
+
+--full adds every check and measurement that takes work of its own, all outside the timed region:
+  parity       the automaton of the last timed step against the reference's recorded canonical sha256
+               (tests/golden/reference_golden.json), and N=1: one more solve through the compacting export
+               compared with the streamed one; a mismatch makes bench.py exit non-zero
   cpu_baseline oracle/ref_dfs.cpp (the reference's algorithm restated, 1 thread) time-boxed on
                the same instance on this box's host cores
-  config.other_workloads  (outside the timed region) the other BASELINE configs on this GPU:
-               digitinvader9, juggling_b5_f6, the time-boxed synthetic 64 x 32 instance
+  config.other_workloads  the other BASELINE configs on this GPU: digitinvader9, juggling_b5_f6, the
+               time-boxed synthetic 64 x 32 instance; config.without_pytorch_runtime (tools/bench_no_torch.py)
+  config.sharded.scalable_workloads  N>1 (and --stepped): --scalable-workload and the synthetic instance
+               through the sharded pipeline
 
 --dump-outputs DIR writes the raw automaton of the last timed step (the arrays of include/stcsp_engine.h's
 stcsp_result; sharded runs: the shards merged on rank 0) as DIR/<name>.npy, numbered independently of scheduling
@@ -397,6 +402,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default=WORKLOAD)
     ap.add_argument("--batch", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity checks, the CPU baselines and the other workloads (see the module docstring); "
+                         "the options below up to --scalable-workload only matter with --full")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0, help="workers of the all-cores CPU legs (default: min(affinity mask, cgroup CPU quota, 16 = the pool's share per GPU))")
@@ -564,28 +572,31 @@ def main():
     if args.dump_outputs and rank == 0 and not stepped:
         dumped = importlib.import_module("stcsp-solver_amd.sharded").result_to_numpy(res)
 
-    # parity of the last timed step (outside the timed region)
+    # parity of the last timed step (outside the timed region; --full). Sharded runs gather and merge the shards for
+    # --dump-outputs too.
     check = {}
     if not stepped:
-        a = eng.automaton(res).traverse().renumber()
-        check = {"states": a.n_live_states, "edges": a.n_live_edges, "canonical_sha256": a.canonical_sha256()}
-    else:
+        if args.full:
+            a = eng.automaton(res).traverse().renumber()
+            check = {"states": a.n_live_states, "edges": a.n_live_edges, "canonical_sha256": a.canonical_sha256()}
+    elif args.full or args.dump_outputs:
         try:  # gather the shards, merge, canonical hash
             merged = sh.gather_and_merge(st, eng, rank, world, dev)
             if rank == 0:
                 _, mres = merged
                 if args.dump_outputs:
                     dumped = sh.result_to_numpy(mres)
-                a = st.Automaton(model, mres).traverse().renumber()
-                check = {"states": a.n_live_states, "edges": a.n_live_edges, "canonical_sha256": a.canonical_sha256()}
+                if args.full:
+                    a = st.Automaton(model, mres).traverse().renumber()
+                    check = {"states": a.n_live_states, "edges": a.n_live_edges, "canonical_sha256": a.canonical_sha256()}
         except Exception as ex:
             check = {"error": f"{type(ex).__name__}: {ex}"}
     parity_ok = True
-    if rank == 0 and args.workload in golden:
+    if args.full and rank == 0 and args.workload in golden:
         check["golden_sha256"] = golden[args.workload]["canonical_sha256"]
         parity_ok = check.get("canonical_sha256") == check["golden_sha256"]
         check["ok"] = parity_ok
-    if not stepped:
+    if args.full and not stepped:
         # the streamed export (edge log shipped while the search runs, ordered by kernel boundaries: DESIGN 4.4) against
         # the compacting export of one more solve of the same engine (everything copied after the search has ended)
         prev = os.environ.get("STCSP_STREAM_EXPORT")
@@ -606,9 +617,9 @@ def main():
                 else:
                     os.environ["STCSP_STREAM_EXPORT"] = prev
 
-    # N>1 (and --stepped): workloads that CAN scale, through the same sharded pipeline, outside the timed region
+    # N>1 (and --stepped): workloads that CAN scale, through the same sharded pipeline, outside the timed region (--full)
     scalable = {}
-    if stepped and not args.no_other_workloads:
+    if args.full and stepped and not args.no_other_workloads:
         try:
             if args.scalable_workload:
                 exp = {"partialorder_16": 6112188, "partialorder_18": 27678644}.get(args.scalable_workload)
@@ -667,9 +678,10 @@ def main():
             cfg["sharded"] = {"rank_search_nodes_per_step": [r[0] // args.steps for r in rank_rows],
                               "nodes_donated": [r[2] for r in rank_rows], "nodes_adopted": [r[3] for r in rank_rows],
                               "supersteps_per_step": supersteps / args.steps,
-                              "ms_in_collectives_per_step": [r[4] / 1e3 / args.steps for r in rank_rows],
-                              "scalable_workloads": scalable}
-        if world == 1 and not stepped and not args.no_other_workloads:
+                              "ms_in_collectives_per_step": [r[4] / 1e3 / args.steps for r in rank_rows]}
+            if args.full:
+                cfg["sharded"]["scalable_workloads"] = scalable
+        if args.full and world == 1 and not stepped and not args.no_other_workloads:
             others = {}
             for name in ("digitinvader9", "juggling_b5_f6"):
                 try:
@@ -720,9 +732,10 @@ def main():
             "search_only_nodes_per_s": nodes / s_search if s_search > 0 else None,
             "search_ms": s_search / args.steps * 1e3,
             "export_ms": s_export / args.steps * 1e3,
-            "parity": check,
         }
-        if not args.no_cpu_baseline and world == 1 and not stepped:
+        if args.full:
+            out["parity"] = check
+        if args.full and not args.no_cpu_baseline and world == 1 and not stepped:
             out["cpu_baseline"] = cpu_baseline(st, args.workload, args.cpu_seconds, args.cpu_threads or host_cpu_share()[1])
         if args.dump_outputs and dumped is not None:
             dump_outputs(canonical_outputs(dumped), args.dump_outputs)

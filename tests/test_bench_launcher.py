@@ -27,7 +27,7 @@ def last_json(stdout):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_bench_starts_its_own_ranks(oracle_lib, golden, world):
-    r = run_bench("--gpus", str(world), "--workload", "partialorder_10", "--steps", "1", "--warmup", "0",
+    r = run_bench("--gpus", str(world), "--workload", "partialorder_10", "--steps", "1", "--warmup", "0", "--full",
                   "--scalable-workload", "juggling_b4_f5", "--synthetic-seconds", "0", entry=CPU_ENTRY)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json(r.stdout)
@@ -46,7 +46,7 @@ def test_bench_starts_its_own_ranks(oracle_lib, golden, world):
 def test_bench_time_boxed_synthetic_through_the_sharded_pipeline(oracle_lib):
     """The N>1 line carries the time-boxed synthetic workload through solve_sharded (here a 24 x 8 member of the family
     that never reaches a leaf either: the CPU stand-in manages ~3 k nodes/s on 64 x 32): every rank gets work."""
-    r = run_bench("--gpus", "2", "--workload", "juggling_b4_f5", "--steps", "1", "--warmup", "0",
+    r = run_bench("--gpus", "2", "--workload", "juggling_b4_f5", "--steps", "1", "--warmup", "0", "--full",
                   "--scalable-workload", "", "--synthetic-seconds", "20.0", "--synthetic-shape", "24,8,125,4,7",
                   "--budget-rounds", "1", "--share-per-rank", "2", entry=CPU_ENTRY)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -90,7 +90,7 @@ def test_bench_dump_outputs(golden, tmp_path):
     dumps = []
     for world in (1, 2):
         out = tmp_path / f"dump{world}"
-        r = run_bench("--gpus", str(world), "--workload", "partialorder_10", "--steps", "3", "--warmup", "0",
+        r = run_bench("--gpus", str(world), "--workload", "partialorder_10", "--steps", "3", "--warmup", "0", "--full",
                       "--scalable-workload", "", "--synthetic-seconds", "0", "--dump-outputs", str(out), entry=CPU_ENTRY)
         assert r.returncode == 0, r.stderr[-2000:]
         d = last_json(r.stdout)
@@ -106,6 +106,31 @@ def test_bench_dump_outputs(golden, tmp_path):
     assert a["state_cid"].shape == (g["states"],) and a["edge_values"].shape[0] == g["edges"]
     r = run_bench("--steps", "0", entry=CPU_ENTRY, timeout=120)
     assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_bench_plain_run_is_lean(golden, tmp_path):
+    """Without --full the run stops after the timed steps and --dump-outputs: no parity check, no scalable workloads (the
+    default partialorder_18 and the 2 s synthetic box would show in the line), and the dumped arrays equal --full's."""
+    import numpy as np
+    dumps = {}
+    for world, full in ((1, True), (1, False), (2, False)):
+        out = tmp_path / f"dump{world}{'full' if full else ''}"
+        r = run_bench("--gpus", str(world), "--workload", "partialorder_10", "--steps", "2", "--warmup", "1",
+                      "--dump-outputs", str(out), *(["--full", "--scalable-workload", "", "--synthetic-seconds", "0"] if full else []),
+                      entry=CPU_ENTRY)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = last_json(r.stdout)
+        assert d["metric"] == "search-tree nodes/sec on partialorder_10.csp" and d["unit"] == "search-tree nodes/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "u32" and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["config"]["nodes_per_step"] == 55636
+        assert ("parity" in d) == full and ("scalable_workloads" in d["config"]["sharded"]) == full
+        if full:
+            assert d["parity"]["ok"] and d["parity"]["canonical_sha256"] == golden["partialorder_10"]["canonical_sha256"]
+        dumps[(world, full)] = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    ref = dumps[(1, True)]
+    for key in ((1, False), (2, False)):
+        assert sorted(dumps[key]) == sorted(ref)
+        assert all(np.array_equal(dumps[key][k], ref[k]) for k in ref), key
 
 
 def test_dump_outputs_size_cap(tmp_path, monkeypatch):

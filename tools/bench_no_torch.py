@@ -1,6 +1,6 @@
 """The headline workload through the C-ABI from a process that never loads PyTorch: the engine then runs on the HIP
 runtime a C++ host linked against /opt/rocm gets (what the INTEGRATION.md binding and the `stcsp` CLI use), not on the
-one PyTorch bundles. bench.py starts this as a child process outside its timed region and puts the line into its own
+one PyTorch bundles. bench.py --full starts this as a child process outside its timed region and puts the line into its own
 (`config.without_pytorch_runtime`). usage: python tools/bench_no_torch.py [workload] [steps] [warmup]"""
 import ctypes as C
 import importlib

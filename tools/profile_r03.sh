@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 OUT=$R/gpurun_out/prof_r03
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp
-B="python3 $R/bench.py --no-cpu-baseline --no-other-workloads"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-other-workloads"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_p14 -- $B --steps 5 --warmup 2 > $OUT/stats_p14.json 2> $OUT/stats_p14.err
 echo "stats p14 done"
 # the same with the export's D2H traffic out of the way (under the tracer the copies of the streaming export run as blit

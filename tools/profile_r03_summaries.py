@@ -55,10 +55,10 @@ f, w, i, b = summ("pmc_FETCH_SIZE"), summ("pmc_WRITE_SIZE"), summ("pmc_SQ_INSTS_
 bench = bench_line(os.path.join(RAW, "pmc_FETCH_SIZE.json"))
 nodes, leaves = bench["config"]["nodes_per_step"], bench["config"]["leaves_per_step"]
 d = pmc_json("r03_p14_pmc.json", i, b, nodes,
-             src + ": rocprofv3 --pmc <list> --kernel-trace -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-other-workloads "
+             src + ": rocprofv3 --pmc <list> --kernel-trace -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-other-workloads "
                    "(two solves of partialorder_14: the timed one and the compacting-export comparison; counters summed over all k_expand dispatches "
                    "and divided by the nodes of both)", None)
-# (bench.py solves the instance twice per run since round 3: the timed step and the STCSP_STREAM_EXPORT=0 comparison)
+# (bench.py --full solves the instance twice per run (round 3 on): the timed step and the STCSP_STREAM_EXPORT=0 comparison)
 solves = 2
 for k in d["per_node"]:
     d["per_node"][k] /= solves
@@ -69,7 +69,7 @@ json.dump(d, open(os.path.join(OUT, "r03_p14_pmc.json"), "w"), indent=1)
 fetch_b, write_b = f["FETCH_SIZE"]["sum"] * 1024 / solves, w["WRITE_SIZE"]["sum"] * 1024 / solves
 alg = nodes * bench["roofline"]["bytes_per_node"] + leaves * bench["roofline"]["bytes_per_leaf"]
 json.dump({"_source": src + ": separate passes `rocprofv3 --pmc FETCH_SIZE --kernel-trace` and `--pmc WRITE_SIZE --kernel-trace` over `python3 bench.py "
-                      "--steps 1 --warmup 0 --no-cpu-baseline --no-other-workloads` (two solves of partialorder_14 per run, halved), summed over all k_expand "
+                      "--full --steps 1 --warmup 0 --no-cpu-baseline --no-other-workloads` (two solves of partialorder_14 per run, halved), summed over all k_expand "
                       "dispatches. FETCH_SIZE / WRITE_SIZE are KiB. gfx950 correction (MI355X_MICROARCH.md, HBM): FETCH_SIZE tallies 128-B requests at "
                       "64 B, so reads are doubled; our loads are 4 B per lane (a 248-B block per wavefront), which the guide calls uncalibrated -- the "
                       "doubled figure is the upper bound, the raw one the lower.",
@@ -89,7 +89,7 @@ def trace_summary(run, bench, table_name):
     are written out too (profiles/<table_name>), so the averages can be recomputed without the raw trace."""
     rows = list(csv.DictReader(open(newest(os.path.join(RAW, run, "**", "*_kernel_trace.csv")))))
     d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if "k_expand" in r["Kernel_Name"]]
-    # bench.py: warmup + steps timed-style solves, then ONE more solve (compacting-export comparison); every solve is one burst of 32 launches
+    # bench.py --full: warmup + steps timed-style solves, then ONE more solve (compacting-export comparison); every solve is one burst of 32 launches
     per_solve = bench["roofline"]["launches"] // bench["steps"]
     n_timed = bench["roofline"]["launches"]
     timed = d[-(n_timed + per_solve):-per_solve]
@@ -125,7 +125,7 @@ i9, b9c = summ("pmc_d9_SQ_INSTS_VALU"), summ("pmc_d9_SQ_BUSY_CYCLES")
 b9 = bench_line(os.path.join(RAW, "pmc_d9_SQ_INSTS_VALU.json"))
 n9 = b9["config"]["nodes_per_step"] * 2  # two solves per run (see above)
 d9 = pmc_json("r03_d9_pmc.json", i9, b9c, n9,
-              src + ": rocprofv3 --pmc <list> --kernel-trace -- python3 bench.py --workload digitinvader9 --steps 1 --warmup 0 (two solves), separate instruction "
+              src + ": rocprofv3 --pmc <list> --kernel-trace -- python3 bench.py --full --workload digitinvader9 --steps 1 --warmup 0 (two solves), separate instruction "
                     "and wait/busy passes, sums over the k_expand dispatches",
               {"bench_line_of_the_stats_run": bench_line(os.path.join(RAW, "stats_d9.json"))})
 print("d9 per node", {k: round(v, 1) for k, v in d9["per_node"].items()}, {k: round(v, 3) for k, v in d9.get("share_of_wave_cycles", {}).items()})
