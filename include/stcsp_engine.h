@@ -278,6 +278,9 @@ int stcsp_engine_donate(stcsp_engine *engine, int64_t want, void **device_ptr, i
 int stcsp_engine_adopt(stcsp_engine *engine, const void *device_records, int64_t count);
 /* counters of the last / current solve without exporting the automaton */
 int stcsp_engine_counters(stcsp_engine *engine, stcsp_counters *out);
+/* The expansion kernel the engine runs for its current program (tests, diagnostics): bit 0 a LITE kernel, bit 1 the
+ * one-register LITE shape kernel, bit 2 the image staged in LDS. */
+int stcsp_engine_expand_variant(const stcsp_engine *engine);
 /* Constraint-set registry exchange: every shard must know a set before it can open a state that
  * uses it. sets_blob returns this shard's registry serialised as int32 words (valid until the
  * next call); sets_import registers the sets of another shard's blob (idempotent). */

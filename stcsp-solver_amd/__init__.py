@@ -96,7 +96,7 @@ ENGINE_SYMBOLS = [
     "stcsp_engine_candidate_bytes", "stcsp_engine_outbox", "stcsp_engine_commit", "stcsp_engine_finish",
     "stcsp_engine_counters", "stcsp_engine_sets_blob", "stcsp_engine_sets_import", "stcsp_engine_postprocess",
     "stcsp_engine_propagate", "stcsp_engine_set_expand_budget", "stcsp_engine_node_bytes", "stcsp_engine_donate",
-    "stcsp_engine_adopt",
+    "stcsp_engine_adopt", "stcsp_engine_expand_variant",
 ]
 # include/stcsp_sharded.h: the superstep loop + in-process transport (libstcsp_hip.so), the RCCL transport (libstcsp_rccl.so)
 SHARDED_SYMBOLS_HIP = ["stcsp_engine_solve_sharded", "stcsp_local_group_create", "stcsp_local_group_transport", "stcsp_local_group_destroy"]
@@ -215,6 +215,8 @@ def bind_engine_api(lib: C.CDLL, prefix: str = "stcsp_engine") -> None:
         g("adopt").argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     if hasattr(lib, f"{prefix}_counters"):
         g("counters").argtypes = [C.c_void_p, C.POINTER(Counters)]
+    if hasattr(lib, f"{prefix}_expand_variant"):
+        g("expand_variant").argtypes = [C.c_void_p]
         g("sets_blob").argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int64)]
         g("sets_import").argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int64]
     if hasattr(lib, f"{prefix}_postprocess"):
@@ -485,6 +487,12 @@ class EngineBase:
         c = Counters()
         self._check(self._f("counters")(self._h, C.byref(c)))
         return c
+
+    def expand_variant(self) -> int:
+        """The expansion kernel of the current program: bit 0 LITE, bit 1 the one-register LITE shape, bit 2 image in LDS."""
+        v = self._f("expand_variant")(self._h)
+        self._check(min(v, 0))
+        return v
 
     def sets_blob(self):
         """This shard's constraint-set registry as a list of int32 words."""

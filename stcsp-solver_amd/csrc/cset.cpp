@@ -1116,6 +1116,11 @@ int SetManager::compile(FlatProgram &out) {
             return STCSP_E_UNSUPPORTED;
         }
         if (sd.iw > out.max_iw) out.max_iw = sd.iw;
+        out.max_nsmall = std::max(out.max_nsmall, sd.nsmall);
+        for (const ItemDesc &it : small_items) {
+            out.max_small_arity = std::max(out.max_small_arity, (int)it.arity);
+            out.any_until_item = out.any_until_item || it.type == IT_UNTIL;
+        }
         out.items.insert(out.items.end(), small_items.begin(), small_items.end());
         out.items.insert(out.items.end(), wave_items.begin(), wave_items.end());
         sd.itemrows_off = (int32_t)out.itemrows.size();

@@ -83,6 +83,12 @@ struct FlatProgram {
     int max_stack = 1;
     int max_cw = 1;
     int max_iw = 1;
+    // Shape facts over all sets (engine.hip: the one-register LITE kernel k_expand<1, true, false, true, .., true> runs a program
+    // only when every one of them holds): the widest lane-revised item, the most lane-revised items in one set, and whether
+    // any set has an until check item.
+    int max_small_arity = 0;
+    int max_nsmall = 0;
+    bool any_until_item = false;
 };
 
 class SetManager {

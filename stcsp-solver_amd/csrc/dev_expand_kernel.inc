@@ -1,5 +1,5 @@
 // dev_expand_kernel.inc -- the body of the expansion kernels, included by k_expand and k_expand_until (dev_kernels.hpp) with
-// DR, L, CS, LITE, BIG, W, KR and UW in scope. (A shared __forceinline__ function instead gives the shipped k_expand instances
+// DR, L, CS, LITE, BIG, W, KR, UW and SHP in scope. (A shared __forceinline__ function instead gives the shipped k_expand instances
 // other register allocations.)
     const Ctx &c = *cp;
     extern __shared__ __attribute__((aligned(16))) int smem[];
@@ -73,7 +73,7 @@
         if (lane == gw_) hot[0] = tab_gen;
     }
 #ifdef STCSP_STATIC_SLOTS
-    for (int gw = blockIdx.x * wpb + wib; gw < n_slots; gw += total_waves) expand_node<DR, L, CS, LITE, W, KR, UW>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env);
+    for (int gw = blockIdx.x * wpb + wib; gw < n_slots; gw += total_waves) expand_node<DR, L, CS, LITE, W, KR, UW, SHP>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env);
 #else
     // Slots: the first one by position, every further one by ticket -- slots differ widely in cost (a chain of up to `chain`
     // expansions, each anything between a failed sweep and a leaf with a new state), and with a fixed stride the round waits for
@@ -88,9 +88,9 @@
             unsigned ticket = 0;
             if (lane == 0) ticket = atomicAdd(cursor, 1u);
             if constexpr (DR > 4)
-                [[clang::always_inline]] expand_node<DR, L, CS, LITE, W, KR, UW>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
+                [[clang::always_inline]] expand_node<DR, L, CS, LITE, W, KR, UW, SHP>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
             else
-                expand_node<DR, L, CS, LITE, W, KR, UW>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
+                expand_node<DR, L, CS, LITE, W, KR, UW, SHP>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
             gw = total_waves + (int)rflu(ticket) * ncur + cur;
         }
     }

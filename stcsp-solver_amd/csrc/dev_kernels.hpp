@@ -46,7 +46,8 @@ extern __shared__ __attribute__((aligned(16))) int stcsp_lds[];
 #ifndef STCSP_FRESH_SEED
 #define STCSP_FRESH_SEED 1
 #endif
-template <int DR, int L, bool CS, bool LITE, int W = 1, int KR = 1, int UW = 1>
+// SHP: the one-register LITE shape (engine.hip shape1): unsharded, so every leaf commits in place.
+template <int DR, int L, bool CS, bool LITE, int W = 1, int KR = 1, int UW = 1, bool SHP = false>
 __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const Img<L> &P, int gw, int lane, int *lds_vals, int *lds_stk, int *ldom,
                             int sib_off, WaveEnv<DR> &env, bool dry = false) {
     const Ctx c0 = ctx_from(hot);
@@ -162,7 +163,7 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
             } else if constexpr (W != 1)
                 oc = process_node_wide<DR, W, L, KR, UW>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bow, lo);
             else
-                oc = process_node<DR, L, CS, LITE, KR, UW>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
+                oc = process_node<DR, L, CS, LITE, KR, UW, SHP>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
         }
         const Ctx ce = ctx_from(hot);
         const Ctx &c = ce;
@@ -298,7 +299,7 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
         // sharded runs: a leaf whose successor state belongs to another shard becomes a candidate
         // record for its owner (header, signature, edge label, block); one that belongs to this
         // shard is committed right here like in an unsharded run
-        if (c.sharded && (lo.owner != c.rank || c.sharded == 2)) {  // (2: tests send every leaf through the exchange, own ones too)
+        if (!SHP && c.sharded && (lo.owner != c.rank || c.sharded == 2)) {  // (2: tests send every leaf through the exchange, own ones too)
             uint32_t pos = 0;
             if (lane == 0) pos = atomicAdd(&c.ctl[L_.cand0 + (lo.owner * R + ro) * CST], 1u);
             pos = rflu(pos);
@@ -748,7 +749,8 @@ __global__ void k_close_segment(Ctx c) {
 #ifndef STCSP_BIG_WAVES
 #define STCSP_BIG_WAVES 16  // wavefronts of a big workgroup
 #endif
-template <int DR, int L, bool CS, bool LITE, bool BIG = false, int W = 1, int KR = 1>
+// SHP (DR = 1, L = 1, LITE only): the one-register LITE shape (engine.hip shape1, dev_propagate.hpp process_node)
+template <int DR, int L, bool CS, bool LITE, bool BIG = false, int W = 1, int KR = 1, bool SHP = false>
 __global__ __launch_bounds__(BIG ? STCSP_BIG_WAVES * 64 : 256, BIG ? 1 : (STCSP_EXPAND_WAVES > 1 ? STCSP_EXPAND_WAVES : (LITE && DR == 1 ? STCSP_LITE_WAVES : (DR <= 2 ? STCSP_GEN_WAVES : (DR <= 4 ? STCSP_WIDE_WAVES : STCSP_BLOCK8_WAVES))))) void k_expand(const Ctx *__restrict__ cp, const Plan *__restrict__ plan_arg, unsigned launch_id, uint32_t tab_gen) {
     constexpr int UW = 1;
 #include "dev_expand_kernel.inc"
@@ -759,7 +761,7 @@ template <int DR, bool CS, int W, int KR, int UW>
 __global__ __launch_bounds__(256, (STCSP_EXPAND_WAVES > 1 ? STCSP_EXPAND_WAVES : (DR <= 4 ? STCSP_WIDE_WAVES : STCSP_BLOCK8_WAVES))) void k_expand_until(const Ctx *__restrict__ cp, const Plan *__restrict__ plan_arg, unsigned launch_id, uint32_t tab_gen) {
     static_assert(DR >= 4 && UW > 1, "the until-heavy kernels are general DR = 4 / 8 kernels");
     constexpr int L = 0;
-    constexpr bool LITE = false, BIG = false;
+    constexpr bool LITE = false, BIG = false, SHP = false;
 #include "dev_expand_kernel.inc"
 }
 

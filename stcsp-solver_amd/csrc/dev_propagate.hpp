@@ -1305,10 +1305,14 @@ __device__ __forceinline__ void until_flags(const Ctx &c, int lane, unsigned lon
     if (KR == 2 && u1 >= 0 && u1 < nu) kw2 = (uint32_t)((u1 < 64 ? f0 >> u1 : f1 >> (u1 - 64)) & 1ull);
 }
 
-template <int DR, int L, bool CS, bool LITE, int KR = 1, int UW = 1>
+// SHP: the one-register LITE shape (engine.hip shape1) -- DR = 1, image in LDS, no until constraint, at most 64 lane-revised items
+// per set (one sweep pass) of at most three variables, unsharded. What only other programs need is compiled out: the pass loop of
+// the sweep, the fourth gather and the fourth table dimension, the until check items and the leaf's until flags.
+template <int DR, int L, bool CS, bool LITE, int KR = 1, int UW = 1, bool SHP = false>
 __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_vals, int *lds_stk, int *ldom, Dom<DR> &dom,
                             const NodeHdrOf<UW> &hd, int gw, WaveEnv<DR> &S, BranchOut &bo, LeafOutOf<DR, UW> &lo) {
     const int set = hd.set;
+    static_assert(!SHP || (DR == 1 && L == 1 && !CS && LITE && KR == 1 && UW == 1), "the one-register LITE shape");
     const uint32_t seed = hd.seed, expire = hd.expire;
     if (set != S.set) {
         load_env<DR, L>(c, P, set, lane, S);
@@ -1390,7 +1394,7 @@ __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_va
                 excl = incl - cnt;
                 total_dirty = (int)rdlane((uint32_t)incl, 63);
             }
-            const int npass = compact ? (total_dirty + 63) >> 6 : (S.nsmall + 63) >> 6;
+            const int npass = SHP ? 1 : (compact ? (total_dirty + 63) >> 6 : (S.nsmall + 63) >> 6);  // (SHP: nsmall <= 64)
             for (int t = 0; t < npass; t++) {
                 int item;
                 bool isd;
@@ -1442,7 +1446,7 @@ __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_va
                 if constexpr (DR == 1) {
                     // gathers are executed by every lane (cross-lane reads need the source lanes active)
                     D0 = dom.gather(it.idx[0]), D1 = dom.gather(it.idx[1]);
-                    D2 = dom.gather(it.idx[2]), D3 = dom.gather(it.idx[3]);
+                    D2 = dom.gather(it.idx[2]), D3 = SHP ? 1u : dom.gather(it.idx[3]);
                 } else {
                     D0 = (uint32_t)ldom[it.idx[0]], D1 = (uint32_t)ldom[it.idx[1]];
                     D2 = (uint32_t)ldom[it.idx[2]], D3 = (uint32_t)ldom[it.idx[3]];
@@ -1457,7 +1461,7 @@ __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_va
                         if (m == 0) lfail = true;
                         if (m != D0) atomicAnd((unsigned *)&ldom[it.idx[0]], m);
                         if (newY != D1) atomicAnd((unsigned *)&ldom[it.idx[1]], newY);
-                    } else if (it.type == IT_UNTIL) {
+                    } else if (!SHP && it.type == IT_UNTIL) {
                         bool live;  // until constraint it.aux has not expired (UW > 1: the lane's ordinal picks its word)
                         if constexpr (UW == 1)
                             live = !((expire >> it.aux) & 1u);
@@ -1474,7 +1478,7 @@ __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_va
                         // tuple of the other (<= 3) variables; scan the rows of the current product
                         if (it.arity < 2) D1 = 1u;
                         if (it.arity < 3) D2 = 1u;
-                        if (it.arity < 4) D3 = 1u;
+                        if (SHP || it.arity < 4) D3 = 1u;
                         uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0;
                         const int tab = c.o.stables + it.toff;  // (a section of its own: staged in LDS whenever it is small)
                         unsigned nev = 0;  // table rows this lane looks at
@@ -1531,7 +1535,7 @@ __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_va
                         if (s0 != D0) atomicAnd((unsigned *)&ldom[it.idx[0]], s0);
                         if (it.arity > 1 && s1 != D1) atomicAnd((unsigned *)&ldom[it.idx[1]], s1);
                         if (it.arity > 2 && s2 != D2) atomicAnd((unsigned *)&ldom[it.idx[2]], s2);
-                        if (it.arity > 3 && s3 != D3) atomicAnd((unsigned *)&ldom[it.idx[3]], s3);
+                        if (!SHP && it.arity > 3 && s3 != D3) atomicAnd((unsigned *)&ldom[it.idx[3]], s3);
                     }
 #endif
                 }
@@ -1757,7 +1761,7 @@ __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_va
             const unsigned long long f1 = __ballot(a1 && (e1 || P.v(c.o.var_lb + y1) + __ffs((int)d1) - 1 == 1));
             until_flags<UW, KR>(c, lane, f0, f1, new_expire, lo.new_hi, kw, kw2);
         } else {
-            for (int u = 0; u < c.n_until_cons; u++) {
+            for (int u = 0; u < (SHP ? 0 : c.n_until_cons); u++) {
                 int y = P.u(c.o.until_y + u);
                 uint32_t DY = dom.get(y);
                 bool ex = (expire >> u) & 1u;
@@ -1785,7 +1789,7 @@ __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_va
     lo.next_set = next_set;
     lo.next_tag = next_tag;
     lo.new_expire = new_expire;
-    lo.owner = key_owner(h, c.world, c.KL, next_tag);
+    lo.owner = SHP ? 0 : key_owner(h, c.world, c.KL, next_tag);  // (SHP: unsharded)
     // edge label (Edge::values) and the time-advanced block (variableAdvanceOneTimeStep,
     // variable.cpp:94-108: point p <- point p+1, last point <- [lb,ub]), lane-striped
 #pragma unroll

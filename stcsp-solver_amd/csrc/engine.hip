@@ -128,6 +128,10 @@ struct stcsp_engine {
     bool compact_sweeps = false;  // some set has more than kCompactSweepItems small items: k_expand<.., .., true, ..>
     bool lite = false;            // no constraint needs the general wavefront revision: k_expand<.., .., .., true>
     bool big = false;             // 1024-thread workgroups around one LDS copy of a LITE program: k_expand<.., true, .., true, true>
+    // The one-register LITE shape: k_expand<1, true, false, true, false, 1, 1, true> (dev_propagate.hpp process_node, SHP) for an
+    // unsharded LITE program with its image in LDS whose every set sweeps its lane-revised items in one pass (at most 64, none of
+    // them an until check or wider than three variables), with no until constraint and a key of at most 64 words.
+    bool shape1 = false;
     int prefix_need = 0;          // image words that must be staged for the L = 2 kernels (0: not applicable)
     bool prefix_complete = false; // ... and they are: general program, everything but cons / tables in the staged prefix
     // Keys of more than 64 words (set tag + signature): a lane holds key words j and 64 + j. Only the general, partly-staged
@@ -479,6 +483,9 @@ struct stcsp_engine {
                 lds_bytes = (size_t)tables_end * 4 + scratch_big;
             }
         }
+        shape1 = DR == 1 && lite && img_in_lds && !big && !compact_sweeps && mgr.W == 1 && !ctx.sharded && ctx.KL <= 64 && ctx.n_until_cons == 0 &&
+                 !prog.any_until_item && prog.max_small_arity <= 3 && prog.max_nsmall <= 64;
+        if (const char *ev = getenv("STCSP_LITE_SHAPE")) shape1 = shape1 && atoi(ev) != 0;  // tuning switch
         const bool try_prefix = !big && !img_in_lds && !(getenv("STCSP_IMG_LDS") && atoi(getenv("STCSP_IMG_LDS")) == 0);
         // Grid = exactly the workgroups that are resident at once: wavefronts take node slots with
         // a static grid stride, so a workgroup that has to wait for a free CU slot would start its
@@ -549,13 +556,15 @@ struct stcsp_engine {
                 max_blocks = per_cu * prop.multiProcessorCount;
             if (const char *ev = getenv("STCSP_BLOCKS")) if (atoi(ev) > 0) max_blocks = atoi(ev);
             if (getenv("STCSP_DEBUG")) {
+                fprintf(stderr, "[engine] shape facts: lite %d, DR %d, compacted sweeps %d, at most %d lane-revised items per set, widest %d, until items %d, until constraints %d, key %d words, sharded %d -> one-register LITE shape %d\n",
+                        (int)lite, DR, (int)compact_sweeps, prog.max_nsmall, prog.max_small_arity, (int)prog.any_until_item, ctx.n_until_cons, ctx.KL, ctx.sharded, (int)shape1);
                 fprintf(stderr, "[engine] staging cuts (words):");
                 for (int cut : hot_end) fprintf(stderr, " %d", cut);
                 fprintf(stderr, "\n");
             }
             if (getenv("STCSP_DEBUG"))
                 fprintf(stderr, "[engine] %s kernel, image %d words (%s: %d words staged), per-wavefront LDS scratch %zu B (stack slots %d), LDS/workgroup %zu B, %d workgroups/CU -> grid %d\n",
-                        big ? "LITE big-workgroup" : lite ? "LITE" : prefix_complete ? "general (descriptors in LDS, tables global)" : "general", o.words, img_in_lds || big ? "in LDS" : "global", ctx.stage_words, scratch / 4, ctx.stack_slots, lds_bytes, per_cu, max_blocks);
+                        big ? "LITE big-workgroup" : shape1 ? "LITE one-register shape" : lite ? "LITE" : prefix_complete ? "general (descriptors in LDS, tables global)" : "general", o.words, img_in_lds || big ? "in LDS" : "global", ctx.stage_words, scratch / 4, ctx.stack_slots, lds_bytes, per_cu, max_blocks);
         }
         return STCSP_OK;
     }
@@ -1279,6 +1288,8 @@ struct stcsp_engine {
             fn = (const void *)k_expand<DRT, (V & 4) != 0, (V & 2) != 0, (V & 1) != 0>;
             if constexpr ((V & 5) == 5)
                 if (big) fn = (const void *)k_expand<DRT, true, (V & 2) != 0, true, true>;
+            if constexpr (DRT == 1 && V == 5)
+                if (shape1) fn = (const void *)k_expand<1, true, false, true, false, 1, 1, true>;
         });
         return fn;
     }
@@ -1352,6 +1363,11 @@ struct stcsp_engine {
             if constexpr ((V & 5) == 5)
                 if (big) {
                     hipLaunchKernelGGL((k_expand<DRT, true, (V & 2) != 0, true, true>), dim3(max_blocks), dim3(STCSP_BIG_WAVES * 64), lds_bytes, stream, cp, (const Plan *)d_plan.p, launch_seq++, ctx.tab_gen);
+                    return;
+                }
+            if constexpr (DRT == 1 && V == 5)
+                if (shape1) {
+                    hipLaunchKernelGGL((k_expand<1, true, false, true, false, 1, 1, true>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, (const Plan *)d_plan.p, launch_seq++, ctx.tab_gen);
                     return;
                 }
             hipLaunchKernelGGL((k_expand<DRT, (V & 4) != 0, (V & 2) != 0, (V & 1) != 0>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, (const Plan *)d_plan.p, launch_seq++, ctx.tab_gen);
@@ -2610,6 +2626,9 @@ int stcsp_engine_donate(stcsp_engine *e, int64_t want, void **ptr, int64_t *coun
     return e->donate(want, ptr, count);
 }
 int stcsp_engine_adopt(stcsp_engine *e, const void *records, int64_t count) { return e ? e->adopt(records, count) : STCSP_E_INVALID; }
+int stcsp_engine_expand_variant(const stcsp_engine *e) {
+    return e ? (e->lite ? 1 : 0) | (e->shape1 ? 2 : 0) | (e->img_in_lds || e->big ? 4 : 0) : STCSP_E_INVALID;
+}
 int stcsp_engine_counters(stcsp_engine *e, stcsp_counters *out) {
     if (!e || !out) return STCSP_E_INVALID;
     if (!e->begun) return e->fail(STCSP_E_STATE, "counters before a solve");
