@@ -214,6 +214,14 @@ int SetManager::find_tag(int32_t tag) const {
     return -1;
 }
 
+int SetManager::widest_scope() const {
+    size_t w = 0;
+    for (const auto &s : sets)
+        for (const HostCon &c : s->cons)
+            if (c.type == CT_POINT) w = std::max(w, c.scope.size());
+    return (int)w;
+}
+
 int SetManager::init(const stcsp_problem *p, bool sharded_tags) {
     if (!p || p->n_vars <= 0 || p->prefix_k <= 0 || !p->var_lb || !p->var_ub || p->n_constraints < 0) {
         error = "invalid problem descriptor";
@@ -645,6 +653,7 @@ void SetManager::build_entry(const HostCon &c, TableEntry &e) {
     e = TableEntry();
     const int s = (int)c.scope.size();
     if (c.type != CT_POINT || s == 0) return;
+    if (s > kLaneScope) return;  // (the device reads a table's strides one scope lane each: wider constraints stay interpreted)
     std::vector<int> size(s);
     long long product = 1;
     const long long limit = device_tabulation ? kBitmapMaxBitsDevice : kBitmapMaxBits;
@@ -932,9 +941,10 @@ int SetManager::compile(FlatProgram &out) {
             cd.scope_off = (int32_t)out.scope.size();
             cd.scope_len = (int32_t)c.scope.size();
             if (cd.scope_len > kMaxScope) {
-                error = "constraint over more than 64 variables";
+                error = "constraint over more than 256 variables";
                 return STCSP_E_UNSUPPORTED;
             }
+            out.max_scope = std::max(out.max_scope, (int)cd.scope_len);
             out.scope.insert(out.scope.end(), c.scope.begin(), c.scope.end());
             cd.x = c.x;
             cd.y = c.y;

@@ -89,6 +89,7 @@ struct FlatProgram {
     int max_small_arity = 0;
     int max_nsmall = 0;
     bool any_until_item = false;
+    int max_scope = 0;  // the widest constraint's scope (more than kLaneScope: engine.hip runs the big-scope kernels)
 };
 
 class SetManager {
@@ -137,6 +138,8 @@ public:
     // arithmetic have |D| sets). Returns the number of transitions added, < 0 on error.
     int pretranslate(long long max_tuples, int max_sets, long long max_total_tuples = 0, double max_seconds = 0);
     int compile(FlatProgram &out);
+    // the widest scope of a point constraint in any set registered so far (translation never widens a scope)
+    int widest_scope() const;
     int find_tag(int32_t tag) const;
     // serialised registry exchange for sharded runs (every shard must know every set)
     std::vector<int32_t> serialise_set(int set) const;

@@ -1,5 +1,5 @@
 // dev_expand_kernel.inc -- the body of the expansion kernels, included by k_expand and k_expand_until (dev_kernels.hpp) with
-// DR, L, CS, LITE, BIG, W, KR, UW and SHP in scope. (A shared __forceinline__ function instead gives the shipped k_expand instances
+// DR, L, CS, LITE, BIG, W, KR, UW, SHP and BS in scope. (A shared __forceinline__ function instead gives the shipped k_expand instances
 // other register allocations.)
     const Ctx &c = *cp;
     extern __shared__ __attribute__((aligned(16))) int smem[];
@@ -47,11 +47,11 @@
         for (int k = threadIdx.x; k < img_words / 4; k += (BIG ? STCSP_BIG_WAVES * 64 : 256)) dst[k] = src[k];
         __syncthreads();
     }
-    const int per_wave = wave_scratch_words(c_NK, c_stack_slots, LITE, c_sib_depth, UW > 1 ? expire_words(c.n_until_cons) : 1);
-    int *lds_vals = smem + img_words + wib * per_wave;
+    const int per_wave = wave_scratch_words(c_NK, c_stack_slots, LITE, c_sib_depth, UW > 1 ? expire_words(c.n_until_cons) : 1, BS);
+    int *lds_vals = smem + img_words + wib * per_wave + (BS ? kBigScopeWords : 0);  // (BS: the big-scope table in front)
     int *lds_stk = lds_vals + kMaxLowVars * 64;
     int *ldom = LITE ? lds_vals : lds_stk + c_stack_slots * 64;  // NK-word AND-accumulator of this wavefront, then its counters
-    const int sib_off = img_words + wib * per_wave + wave_sib_offset(c_NK, c_stack_slots, LITE);  // word offset in the launch's LDS
+    const int sib_off = img_words + wib * per_wave + wave_sib_offset(c_NK, c_stack_slots, LITE, BS);  // word offset in the launch's LDS
     Img<L> P{c_img, (const uint32_t *)smem, c_stage_words};
     ExpandArgs a;
     a.in_base = c_arena + ((unsigned long long)p_in_hi << 32 | p_in_lo);
@@ -73,7 +73,7 @@
         if (lane == gw_) hot[0] = tab_gen;
     }
 #ifdef STCSP_STATIC_SLOTS
-    for (int gw = blockIdx.x * wpb + wib; gw < n_slots; gw += total_waves) expand_node<DR, L, CS, LITE, W, KR, UW, SHP>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env);
+    for (int gw = blockIdx.x * wpb + wib; gw < n_slots; gw += total_waves) expand_node<DR, L, CS, LITE, W, KR, UW, SHP, BS>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env);
 #else
     // Slots: the first one by position, every further one by ticket -- slots differ widely in cost (a chain of up to `chain`
     // expansions, each anything between a failed sweep and a leaf with a new state), and with a fixed stride the round waits for
@@ -88,9 +88,9 @@
             unsigned ticket = 0;
             if (lane == 0) ticket = atomicAdd(cursor, 1u);
             if constexpr (DR > 4)
-                [[clang::always_inline]] expand_node<DR, L, CS, LITE, W, KR, UW, SHP>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
+                [[clang::always_inline]] expand_node<DR, L, CS, LITE, W, KR, UW, SHP, BS>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
             else
-                expand_node<DR, L, CS, LITE, W, KR, UW, SHP>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
+                expand_node<DR, L, CS, LITE, W, KR, UW, SHP, BS>(hot, a, P, gw, lane, lds_vals, lds_stk, ldom, sib_off, env, n_slots <= total_waves);
             gw = total_waves + (int)rflu(ticket) * ncur + cur;
         }
     }

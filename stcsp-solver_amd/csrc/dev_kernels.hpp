@@ -47,7 +47,7 @@ extern __shared__ __attribute__((aligned(16))) int stcsp_lds[];
 #define STCSP_FRESH_SEED 1
 #endif
 // SHP: the one-register LITE shape (engine.hip shape1): unsharded, so every leaf commits in place.
-template <int DR, int L, bool CS, bool LITE, int W = 1, int KR = 1, int UW = 1, bool SHP = false>
+template <int DR, int L, bool CS, bool LITE, int W = 1, int KR = 1, int UW = 1, bool SHP = false, bool BS = false>
 __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const Img<L> &P, int gw, int lane, int *lds_vals, int *lds_stk, int *ldom,
                             int sib_off, WaveEnv<DR> &env, bool dry = false) {
     const Ctx c0 = ctx_from(hot);
@@ -157,13 +157,13 @@ __device__ void expand_node(const uint32_t (&hot)[2], const ExpandArgs &a, const
                 // (DR = 8: the node's block, its child and the leaf's block are 24 registers per lane. An outlined call passes them
                 // through scratch memory and saves the caller's registers there: ~1 KB per lane. Inlined, they stay in registers.)
                 if constexpr (W != 1)
-                    [[clang::always_inline]] oc = process_node_wide<DR, W, L, KR, UW>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bow, lo);
+                    [[clang::always_inline]] oc = process_node_wide<DR, W, L, KR, UW, BS>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bow, lo);
                 else
-                    [[clang::always_inline]] oc = process_node<DR, L, CS, LITE, KR, UW>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
+                    [[clang::always_inline]] oc = process_node<DR, L, CS, LITE, KR, UW, false, BS>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
             } else if constexpr (W != 1)
-                oc = process_node_wide<DR, W, L, KR, UW>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bow, lo);
+                oc = process_node_wide<DR, W, L, KR, UW, BS>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bow, lo);
             else
-                oc = process_node<DR, L, CS, LITE, KR, UW, SHP>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
+                oc = process_node<DR, L, CS, LITE, KR, UW, SHP, BS>(cn, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
         }
         const Ctx ce = ctx_from(hot);
         const Ctx &c = ce;
@@ -753,6 +753,7 @@ __global__ void k_close_segment(Ctx c) {
 template <int DR, int L, bool CS, bool LITE, bool BIG = false, int W = 1, int KR = 1, bool SHP = false>
 __global__ __launch_bounds__(BIG ? STCSP_BIG_WAVES * 64 : 256, BIG ? 1 : (STCSP_EXPAND_WAVES > 1 ? STCSP_EXPAND_WAVES : (LITE && DR == 1 ? STCSP_LITE_WAVES : (DR <= 2 ? STCSP_GEN_WAVES : (DR <= 4 ? STCSP_WIDE_WAVES : STCSP_BLOCK8_WAVES))))) void k_expand(const Ctx *__restrict__ cp, const Plan *__restrict__ plan_arg, unsigned launch_id, uint32_t tab_gen) {
     constexpr int UW = 1;
+    constexpr bool BS = false;
 #include "dev_expand_kernel.inc"
 }
 // Models with more than 32 until constraints: the general, partly-staged kernels (DR = 4 and 8, like the long-key ones) with UW
@@ -761,7 +762,16 @@ template <int DR, bool CS, int W, int KR, int UW>
 __global__ __launch_bounds__(256, (STCSP_EXPAND_WAVES > 1 ? STCSP_EXPAND_WAVES : (DR <= 4 ? STCSP_WIDE_WAVES : STCSP_BLOCK8_WAVES))) void k_expand_until(const Ctx *__restrict__ cp, const Plan *__restrict__ plan_arg, unsigned launch_id, uint32_t tab_gen) {
     static_assert(DR >= 4 && UW > 1, "the until-heavy kernels are general DR = 4 / 8 kernels");
     constexpr int L = 0;
-    constexpr bool LITE = false, BIG = false, SHP = false;
+    constexpr bool LITE = false, BIG = false, SHP = false, BS = false;
+#include "dev_expand_kernel.inc"
+}
+// Models with a constraint over more than kLaneScope variables (big scope): the general, partly-staged kernels at DR = 4 and 8 with
+// the big-scope revision (dev_propagate.hpp big_scope_prologue) and its kBigScopeWords of LDS per wavefront. CS: compacted sweeps.
+template <int DR, bool CS, int W, int KR>
+__global__ __launch_bounds__(256, (STCSP_EXPAND_WAVES > 1 ? STCSP_EXPAND_WAVES : (DR <= 4 ? STCSP_WIDE_WAVES : STCSP_BLOCK8_WAVES))) void k_expand_big(const Ctx *__restrict__ cp, const Plan *__restrict__ plan_arg, unsigned launch_id, uint32_t tab_gen) {
+    static_assert(DR >= 4 && W >= 1, "the big-scope kernels are general bitset DR = 4 / 8 kernels");
+    constexpr int L = 0, UW = 1;
+    constexpr bool LITE = false, BIG = false, SHP = false, BS = true;
 #include "dev_expand_kernel.inc"
 }
 
@@ -773,46 +783,16 @@ __global__ __launch_bounds__(256, (STCSP_EXPAND_WAVES > 1 ? STCSP_EXPAND_WAVES :
 template <int DR, int L, bool CS, bool LITE>
 __global__ __launch_bounds__(256, (DR <= 2 ? 4 : 3)) void k_probe(const Ctx *__restrict__ cp, uint32_t *blocks, int n, int set, uint32_t expire,
                                                                   int *outcome) {
-    const Ctx &c = *cp;
-    extern __shared__ __attribute__((aligned(16))) int smem[];
-    const int lane = threadIdx.x & 63, wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int img_words = (c.stage_words + 3) & ~3;
-    if (img_words) {
-        const uint4 *src = (const uint4 *)c.img;
-        uint4 *dst = (uint4 *)smem;
-        for (int k = threadIdx.x; k < img_words / 4; k += 256) dst[k] = src[k];
-        __syncthreads();
-    }
-    const int per_wave = wave_scratch_words(c.NK, c.stack_slots, LITE, c.sib_depth);
-    int *lds_vals = smem + img_words + wib * per_wave;
-    int *lds_stk = lds_vals + kMaxLowVars * 64;
-    int *ldom = LITE ? lds_vals : lds_stk + c.stack_slots * 64;
-    Img<L> P{c.img, (const uint32_t *)smem, c.stage_words};
-    WaveEnv<DR> env;
-    for (int gw = blockIdx.x * 4 + wib; gw < n; gw += gridDim.x * 4) {
-        uint32_t *blk = blocks + (size_t)gw * c.NK;
-        Dom<DR> dom;
-#pragma unroll
-        for (int q = 0; q < DR; q++) {
-            const int idx = q * 64 + lane;
-            dom.r[q] = idx < c.NK ? blk[idx] : 0u;
-        }
-        NodeHdr hd;
-        hd.h0 = hd.h1 = 0u;
-        hd.set = rfl(set >= 0 ? set : gw);  // (set < 0: block i under constraint set i, and no work counters -- engine.hip fresh_init)
-        hd.seed = 0u;
-        hd.expire = rflu(expire);
-        BranchOut bo;
-        LeafOut<DR> lo;
-        const int oc = process_node<DR, L, CS, LITE>(c, P, lane, lds_vals, lds_stk, ldom, dom, hd, gw, env, bo, lo);
-#pragma unroll
-        for (int q = 0; q < DR; q++) {
-            const int idx = q * 64 + lane;
-            if (idx < c.NK) blk[idx] = dom.r[q];
-        }
-        if (lane == 0) outcome[gw] = oc;
-    }
-    if (set >= 0) flush_env<DR>(c, env, blockIdx.x * 4 + wib, lane);
+    constexpr bool BS = false;
+#include "dev_probe_kernel.inc"
+}
+// ... with the big-scope revision, at DR = 4 and 8 (programs that run k_expand_big)
+template <int DR, bool CS>
+__global__ __launch_bounds__(256, 3) void k_probe_big(const Ctx *__restrict__ cp, uint32_t *blocks, int n, int set, uint32_t expire, int *outcome) {
+    static_assert(DR >= 4, "the big-scope kernels are DR = 4 / 8 kernels");
+    constexpr int L = 0;
+    constexpr bool LITE = false, BS = true;
+#include "dev_probe_kernel.inc"
 }
 
 // ------------------------------------------------------------------ commit

@@ -28,11 +28,14 @@ constexpr int kLdsStatWords = 12;
 // AND-accumulator copy of the block + the counters. LITE kernels (no general revision) keep the last part only.
 // ... + the sibling stack of the chained expansions (dev_kernels.hpp expand_node): kSibDepth node records.
 constexpr int kSibDepth = 4;  // (default; Ctx::sib_depth is what a launch uses: the big-workgroup variant trades depth for LDS)
-__host__ __device__ inline int wave_sib_offset(int NK, int stack_slots, bool lite) {
-    return (lite ? 0 : (kMaxLowVars + stack_slots) * 64) + ((NK + kLdsStatWords + 63) & ~63);
+// Big-scope kernels (constraints over more than kLaneScope variables, dev_propagate.hpp big_scope_prologue) put kBigScopeWords
+// in front of all that: the fixed values / compacted lanes of a revision's scope positions and the bitmap of its open positions.
+constexpr int kBigScopeWords = kMaxScope + kMaxScope / 32;
+__host__ __device__ inline int wave_sib_offset(int NK, int stack_slots, bool lite, bool bs = false) {
+    return (bs ? kBigScopeWords : 0) + (lite ? 0 : (kMaxLowVars + stack_slots) * 64) + ((NK + kLdsStatWords + 63) & ~63);
 }
-__host__ __device__ inline int wave_scratch_words(int NK, int stack_slots, bool lite, int sib_depth, int UW = 1) {
-    return wave_sib_offset(NK, stack_slots, lite) + sib_depth * node_stride(NK, 1, UW);  // (sibling entries: node records)
+__host__ __device__ inline int wave_scratch_words(int NK, int stack_slots, bool lite, int sib_depth, int UW = 1, bool bs = false) {
+    return wave_sib_offset(NK, stack_slots, lite, bs) + sib_depth * node_stride(NK, 1, UW);  // (sibling entries: node records)
 }
 constexpr int kMissStride = 66;  // set, nfirst, 64 values
 constexpr uint32_t kPending = 0xffffffffu;

@@ -174,9 +174,11 @@ struct WaveEnv {
 // reference src/solveralgorithm.cpp:336-424). varinfo/curval are per-lane registers indexed by
 // scope position: varinfo = 1 + slot for lane-enumerated variables (value in lds_vals), 0 for
 // wave-uniform ones (value in curval).
-template <int L>
+// BS (big-scope kernels): `bstab` != nullptr for a constraint over more than kLaneScope variables, whose scope lanes are the
+// COMPACTED open variables (big_scope_prologue); an OP_VAR then reads the scope position's fixed value or compacted lane there.
+template <int L, bool BS = false>
 __device__ int eval_program(const Ctx &c, const Img<L> &P, int pc0, int code_len, bool uses_valid, int lane, uint32_t varinfo, int curval,
-                            const int *lds_vals, int *lds_stk) {
+                            const int *lds_vals, int *lds_stk, const int *bstab = nullptr) {
     // Operand stack: the top in `t`, the three entries below it in registers (s1 = most recent), anything deeper in
     // LDS -- expressions rarely nest deeper, so a push / pop is a few register moves instead of an LDS round trip
     // per instruction (a dependent ds_read is ~100 cycles, and an instruction used to cost ~350).
@@ -222,6 +224,16 @@ __device__ int eval_program(const Ctx &c, const Img<L> &P, int pc0, int code_len
                 break;
             case OP_VAR: {
                 push();
+                if constexpr (BS) {
+                    if (bstab) {
+                        const int e = rfl(bstab[arg]);
+                        if (!((rflu((uint32_t)bstab[kMaxScope + (arg >> 5)]) >> (arg & 31)) & 1u)) {  // a fixed position: its value
+                            t = e;
+                            break;
+                        }
+                        arg = e;  // an open one: its compacted lane
+                    }
+                }
                 uint32_t info = rdlane(varinfo, arg);
                 if (info)
                     t = lds_vals[(info - 1) * 64 + lane];
@@ -353,20 +365,81 @@ __device__ __forceinline__ int small_div(int x, int d) {
     return (int)(((float)x + 0.5f) * __builtin_amdgcn_rcpf((float)d));
 }
 
+// Big-scope revisions (BS kernels; a constraint over more than kLaneScope variables, which never has a tuple bitmap). The scope is
+// read in chunks of 64 positions. Any empty domain is a wipe-out (-1). With more than kLaneScope open variables the product of the
+// open domains is at least 2^65, over every per-revision budget: the revision is skipped (0) before anything else is done.
+// Otherwise (1) every position goes into the wavefront's table `bstab` -- a fixed position's value, an open position's compacted
+// lane -- with bit `pos` of words bstab[kMaxScope ..] set for the open ones, and lane j < nopen gets the j-th open variable in
+// `cvar`: the callers then run their enumeration over the nopen compacted lanes (eval_program reads the table). `count` / `fixed`
+// take a block word index (p * N + variable) and give the domain size / the value of a singleton; every lane calls them (a gather
+// from a lane outside the exec mask reads 0). `scr`: 64 words of scratch.
+template <int L, typename Count, typename Fixed>
+__device__ int big_scope_prologue(const Ctx &c, const Img<L> &G, const ConDesc &C, int p, int lane, int *bstab, int *scr, Count count,
+                                  Fixed fixed, int &nopen, int &cvar) {
+    const int s = C.scope_len;
+    nopen = 0;
+    for (int k = 0; k < s; k += 64) {
+        const bool in = k + lane < s;
+        const int v = in ? G.v(c.o.scope + C.scope_off + k + lane) : 0;
+        const int cnt = count(p * c.N + v);
+        const int n = in ? cnt : 1;
+        if (__ballot(n == 0)) return -1;
+        nopen += __popcll(__ballot(n > 1));
+    }
+    if (nopen > kLaneScope) return 0;
+    int base = 0;
+    for (int k = 0; k < s; k += 64) {
+        const bool in = k + lane < s;
+        const int v = in ? G.v(c.o.scope + C.scope_off + k + lane) : 0;
+        const int cnt = count(p * c.N + v), val = fixed(p * c.N + v);
+        const int n = in ? cnt : 1;
+        const unsigned long long om = __ballot(n > 1);
+        const int j = base + __popcll(om & ((1ull << lane) - 1ull));
+        if (in) bstab[k + lane] = n > 1 ? j : val;
+        if (n > 1) scr[j] = v;
+        if (lane < 2) bstab[kMaxScope + (k >> 5) + lane] = (int)(uint32_t)(om >> (32 * lane));
+        base += __popcll(om);
+    }
+    STCSP_REJOIN();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    cvar = lane < nopen ? scr[lane] : 0;
+    return 1;
+}
+
 // Enforce one point constraint at one time point: afterwards every remaining value of every
 // scope variable has a supporting tuple (generalised arc consistency on this constraint; the
 // reference tightens bounds only, solveralgorithm.cpp:476-523 -- this prunes at least as much).
 // Returns false when a domain is wiped out. Rows of changed block words are OR-ed into `dirtyw`.
-template <int DR, int L, bool LITE>
+// BS: the big-scope kernels -- a constraint over more than kLaneScope variables has its open variables compacted into the scope
+// lanes first (big_scope_prologue; it has no tuple bitmap, so only the general path below sees it).
+template <int DR, int L, bool LITE, bool BS = false>
 __device__ bool revise_point(const Ctx &c, const Img<L> &G, WaveEnv<DR> &S, const ConDesc &C, int item, int p, Dom<DR> &dom,
                              int lane, uint32_t &dirtyw, int *lds_vals, int *lds_stk, int *ldom, WaveStats &ws, bool &pruned) {
     const unsigned long long(&pm)[DR] = S.pm;
     const unsigned long long t_rv0 = PHASE_NOW();
     (void)t_rv0;
-    const int s = C.scope_len;
+    int s = C.scope_len;
     // per-lane view of scope variable j = lane
     int var = 0;
-    if (lane < s) var = G.v(c.o.scope + C.scope_off + lane);
+    const int *bstab = nullptr;
+    if constexpr (BS) {
+        if (s > kLaneScope) {
+            int nopen = 0;
+            const int r = big_scope_prologue<L>(
+                c, G, C, p, lane, lds_vals - kBigScopeWords, lds_vals, [&](int w) { return __popc(dom.gather(w)); },
+                [&](int w) { return G.v(c.o.var_lb + w % c.N) + __ffs((int)dom.gather(w)) - 1; }, nopen, var);
+            if (r <= 0) {
+                if (r < 0) return false;
+                if (lane == (item >> 5)) dirtyw &= ~(1u << (item & 31));
+                S.n_skipped++;
+                return true;
+            }
+            s = nopen;
+            bstab = lds_vals - kBigScopeWords;
+        }
+    }
+    if (!bstab && lane < s) var = G.v(c.o.scope + C.scope_off + lane);
     uint32_t D = dom.gather(p * c.N + var);
     if (lane >= s) D = 0;
     const int n = lane < s ? __popc(D) : 1;
@@ -669,7 +742,7 @@ __device__ bool revise_point(const Ctx &c, const Img<L> &G, WaveEnv<DR> &S, cons
             acc0 |= sup0;
             res = sup0 != 0;
         } else {
-            res = eval_program<L>(c, G, C.code_off, C.code_len, C.uses_valid != 0, lane, varinfo, curval, lds_vals, lds_stk);
+            res = eval_program<L, BS>(c, G, C.code_off, C.code_len, C.uses_valid != 0, lane, varinfo, curval, lds_vals, lds_stk, bstab);
         }
         S.n_evals += (unsigned)Plow;
         const bool sat = active && res != 0;
@@ -1308,7 +1381,7 @@ __device__ __forceinline__ void until_flags(const Ctx &c, int lane, unsigned lon
 // SHP: the one-register LITE shape (engine.hip shape1) -- DR = 1, image in LDS, no until constraint, at most 64 lane-revised items
 // per set (one sweep pass) of at most three variables, unsharded. What only other programs need is compiled out: the pass loop of
 // the sweep, the fourth gather and the fourth table dimension, the until check items and the leaf's until flags.
-template <int DR, int L, bool CS, bool LITE, int KR = 1, int UW = 1, bool SHP = false>
+template <int DR, int L, bool CS, bool LITE, int KR = 1, int UW = 1, bool SHP = false, bool BS = false>
 __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_vals, int *lds_stk, int *ldom, Dom<DR> &dom,
                             const NodeHdrOf<UW> &hd, int gw, WaveEnv<DR> &S, BranchOut &bo, LeafOutOf<DR, UW> &lo) {
     const int set = hd.set;
@@ -1616,7 +1689,7 @@ __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_va
         C.code_len = STCSP_ID(r2);
 #undef STCSP_ID
         bool pruned = false;
-        consistent = revise_point<DR, L, LITE>(c, P, S, C, item, ipoint, dom, lane, dirtyw, lds_vals, lds_stk, ldom, ws, pruned);
+        consistent = revise_point<DR, L, LITE, BS>(c, P, S, C, item, ipoint, dom, lane, dirtyw, lds_vals, lds_stk, ldom, ws, pruned);
         need_close = pruned && S.next_abs >= 0;
         ws.cyc_wave += PHASE_NOW() - t_wv;
         if (++guard > (1u << 20)) {

@@ -103,9 +103,10 @@ __device__ __forceinline__ WDom<W> wbroadcast(const WDom<W> &d, int srclane) {  
 // enumerated across lanes -- the product of their sizes in trips of 64, every lane decoding its own tuple -- the others by a
 // wave-uniform odometer. Evaluation = tuple bitmap look-up or the postfix program. A search longer than `budget` trips is
 // given up as "supported" (never prune without proof; leaves are exact: their product is 1).
-template <int W, int L>
+// BS: `bstab` of a big-scope revision (revise_bounds_wide), whose scope lanes are its compacted open variables.
+template <int W, int L, bool BS = false>
 __device__ bool exists_support_wide(const Ctx &c, const Img<L> &G, const ConDesc &C, int lane, const WDom<W> &D, int vlb, int mystride,
-                                    int *lds_vals, int *lds_stk, unsigned long long &n_evals, bool &gave_up) {
+                                    int *lds_vals, int *lds_stk, unsigned long long &n_evals, bool &gave_up, const int *bstab = nullptr) {
     const int s = C.scope_len;
     const bool use_bitmap = C.bitmap_off >= 0;
     const int n = lane < s ? D.count() : 1;
@@ -163,7 +164,7 @@ __device__ bool exists_support_wide(const Ctx &c, const Img<L> &G, const ConDesc
                 const int bit = base_sum + lane_part;
                 res = active ? (int)((((uint32_t)G.vc(c.o.tables + C.bitmap_off + (bit >> 5))) >> (bit & 31)) & 1u) : 0;
             } else {
-                res = eval_program<L>(c, G, C.code_off, C.code_len, C.uses_valid != 0, lane, varinfo, curval, lds_vals, lds_stk);
+                res = eval_program<L, BS>(c, G, C.code_off, C.code_len, C.uses_valid != 0, lane, varinfo, curval, lds_vals, lds_stk, bstab);
             }
             n_evals += min(Plow - trip * 64u, 64u);
             if (__ballot(active && res != 0)) return true;
@@ -190,12 +191,20 @@ __device__ bool exists_support_wide(const Ctx &c, const Img<L> &G, const ConDesc
 
 // One point constraint at one time point, bounds consistency for every scope variable (enforcePointConsistencyAt,
 // src/solveralgorithm.cpp:476-523). Returns false on a wipe-out; `changedm`: scope positions whose domain shrank.
-template <int W, int L>
+// BS (big-scope kernels): `bstab` != nullptr -- C is a constraint over more than kLaneScope variables whose open variables
+// big_scope_prologue has compacted: scope lane j < C.scope_len revises variable `cvar` (changedm: a bit per compacted lane).
+template <int W, int L, bool BS = false>
 __device__ bool revise_bounds_wide(const Ctx &c, const Img<L> &G, const ConDesc &C, int p, int lane, int *ldom, int *lds_vals, int *lds_stk,
-                                   unsigned long long &changedm, unsigned long long &n_evals, unsigned &n_skipped) {
+                                   unsigned long long &changedm, unsigned long long &n_evals, unsigned &n_skipped, const int *bstab = nullptr,
+                                   int cvar = 0) {
     const int s = C.scope_len, NK1 = c.N * c.K;
     int var = 0;
-    if (lane < s) var = G.v(c.o.scope + C.scope_off + lane);
+    if constexpr (BS) {
+        if (bstab) var = cvar;
+        else if (lane < s) var = G.v(c.o.scope + C.scope_off + lane);
+    } else {
+        if (lane < s) var = G.v(c.o.scope + C.scope_off + lane);
+    }
     const int word = p * c.N + var;
     WDom<W> D = wload<W>(ldom, NK1, word);
     if (lane >= s)
@@ -207,7 +216,7 @@ __device__ bool revise_bounds_wide(const Ctx &c, const Img<L> &G, const ConDesc 
     bool gave_up = false;
     const unsigned long long openm = __ballot(lane < s && D.count() > 1);
     if (!openm) {  // every variable fixed: the single tuple is checked (this is what makes leaves exact)
-        const bool ok = exists_support_wide<W, L>(c, G, C, lane, D, vlb, mystride, lds_vals, lds_stk, n_evals, gave_up);
+        const bool ok = exists_support_wide<W, L, BS>(c, G, C, lane, D, vlb, mystride, lds_vals, lds_stk, n_evals, gave_up, bstab);
         changedm = 0;
         return ok;
     }
@@ -224,7 +233,7 @@ __device__ bool revise_bounds_wide(const Ctx &c, const Img<L> &G, const ConDesc 
                 WDom<W> T = D;
                 if (lane == j0) T.only(b);
                 gave_up = false;
-                const bool sup = exists_support_wide<W, L>(c, G, C, lane, T, vlb, mystride, lds_vals, lds_stk, n_evals, gave_up);
+                const bool sup = exists_support_wide<W, L, BS>(c, G, C, lane, T, vlb, mystride, lds_vals, lds_stk, n_evals, gave_up, bstab);
                 if (gave_up) n_skipped++;
                 if (sup) break;
                 if (lane == j0) D.clear(b);
@@ -307,7 +316,7 @@ struct BranchOutWide {
 
 // W = kWIntervals: interval domains (dev_interval.hpp), the same node loop with bounds in place of bitsets
 
-template <int DR, int W, int L, int KR = 1, int UW = 1>
+template <int DR, int W, int L, int KR = 1, int UW = 1, bool BS = false>
 __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *lds_vals, int *lds_stk, int *ldom, Dom<DR> &dom, const NodeHdrOf<UW> &hd,
                                  int gw, WaveEnv<DR> &S, BranchOutWide &bo, LeafOutOf<DR, UW> &lo) {
     const int set = hd.set;
@@ -400,7 +409,27 @@ __device__ int process_node_wide(const Ctx &c, const Img<L> &P, int lane, int *l
                 consistent = revise_bounds_iv<L>(c, P, C, defpos, C.code_off + C.code_len + 1, e_len, ipoint, lane, ldom, lds_vals, lds_stk, changedm,
                                                  S.n_evals, S.n_skipped);
             } else {
-                consistent = revise_bounds_wide<W, L>(c, P, C, ipoint, lane, ldom, lds_vals, lds_stk, changedm, S.n_evals, S.n_skipped);
+                bool done = false;
+                if constexpr (BS) {
+                    if (C.scope_len > kLaneScope) {  // a big scope: its open variables compacted into lanes first
+                        int nopen = 0, cvar = 0;
+                        int *const bstab = lds_vals - kBigScopeWords;
+                        const int r = big_scope_prologue<L>(
+                            c, P, C, ipoint, lane, bstab, lds_vals, [&](int w) { return wload<W>(ldom, NK1, w).count(); },
+                            [&](int w) { return P.v(c.o.var_lb + w % c.N) + wload<W>(ldom, NK1, w).lowest(); }, nopen, cvar);
+                        consistent = r >= 0;
+                        if (r == 0) S.n_skipped++;
+                        if (r > 0) {
+                            ConDesc Cc = C;
+                            Cc.scope_len = nopen;
+                            consistent = revise_bounds_wide<W, L, true>(c, P, Cc, ipoint, lane, ldom, lds_vals, lds_stk, changedm, S.n_evals, S.n_skipped, bstab, cvar);
+                            for (unsigned long long m = changedm; consistent && m; m &= m - 1) mark_word(ipoint * c.N + (int)rdlane((uint32_t)cvar, __ffsll((long long)m) - 1));
+                        }
+                        changedm = 0;
+                        done = true;
+                    }
+                }
+                if (!done) consistent = revise_bounds_wide<W, L>(c, P, C, ipoint, lane, ldom, lds_vals, lds_stk, changedm, S.n_evals, S.n_skipped);
             }
             S.n_revs++;
             S.n_wave_revs++;

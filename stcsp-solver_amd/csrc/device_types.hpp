@@ -23,7 +23,9 @@ constexpr int kMaxIntervalRegs = 4; // interval blocks (two words per variable a
 constexpr int kMaxKeyWords = 126;   // state key [set tag, signature...]: two lane-striped registers, one 128-word table entry
 constexpr int kCompactSweepItems = 128;  // sets with more small items than this sweep over a compacted dirty list
 constexpr int kMaxLowVars = 6;      // lane-enumerated scope variables per revision (2^6 = 64; value bits packed 5 x 6 in a register)
-constexpr int kMaxScope = 64;       // scope variables per constraint (one lane each)
+constexpr int kMaxScope = 256;      // scope variables per constraint
+constexpr int kLaneScope = 64;      // ... that one revision gives a lane each; wider constraints run the big-scope kernels, which
+                                    // compact a revision's open variables into lanes (dev_propagate.hpp big_scope_prologue)
 constexpr int kCursorStride = 16;   // words between cursors (64 B: one cursor per cache line)
 constexpr uint32_t kRootTag = 0x7fffffffu;
 // node header word 2 = constraint-set ordinal (low kSetBits bits) | dirty seed (the rest): seed 0 = revise every item (fresh state /

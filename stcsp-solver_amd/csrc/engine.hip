@@ -142,6 +142,11 @@ struct stcsp_engine {
     // k_expand_until / k_commit_until kernels with kMaxExpireWords words per node -- the general, partly-staged kernels at DR = 4
     // and 8, with one or two key registers -- so the kernels of models with at most 32 until constraints stay exactly as they are.
     bool many_until() const { return ctx.n_until_cons > 32; }
+    // A point constraint over more than kLaneScope (64) variables: the k_expand_big kernels (general, partly-staged, DR = 4 and 8,
+    // one or two key registers), whose revisions compact a scope's open variables into lanes, and k_probe_big<DR, CS>.
+    // Decided once, at creation, from the sets known then (translation never widens a scope: upload_program checks it).
+    bool big_scope_ = false;
+    bool big_scope() const { return big_scope_; }
     int expire_w() const { return expire_words(ctx.n_until_cons); }
     bool interpreted = false;     // some wavefront-revised constraint has no tuple bitmap (postfix interpreter: uniformly expensive nodes)
     bool wide_conditional = false;  // some conditional constraint spans more than kWideConditional tuples (the juggling family's `A == if B0 eq 1 then next B0 else if ...`)
@@ -252,6 +257,8 @@ struct stcsp_engine {
     int upload_program() {
         int rc = mgr.compile(prog);
         if (rc != STCSP_OK) return fail(rc, "%s", mgr.error.c_str());
+        if (prog.max_scope > kLaneScope && !big_scope())
+            return fail(STCSP_E_INTERNAL, "a constraint over %d variables appeared after the kernels were chosen", prog.max_scope);
         // node header word 2 = set ordinal (kSetBits bits) | dirty seed
         if (prog.sets.size() > (size_t)kSetMask) return fail(STCSP_E_UNSUPPORTED, "%zu constraint sets; node records address at most %u", prog.sets.size(), kSetMask);
         // LITE: every wavefront-revised constraint is a tuple bitmap with at most one violating tuple. Its
@@ -269,7 +276,7 @@ struct stcsp_engine {
             }
         if (const char *ev = getenv("STCSP_LITE")) lite = lite && atoi(ev) != 0;  // tuning switch
         if (mgr.W > 1) lite = false;  // (wide domains: every item is revised by dev_wide.hpp's bounds propagation)
-        if (long_key() || many_until()) lite = false;
+        if (long_key() || many_until() || big_scope()) lite = false;
         if (DR > 4) lite = false;  // (blocks of more than 256 words: the general, partly-staged kernels only)
         // one contiguous image; every section starts on a 16-byte boundary
         std::vector<uint32_t> img;
@@ -450,13 +457,13 @@ struct stcsp_engine {
         // occupancy the kernels' registers allow (STCSP_BLOCK8_WAVES wavefronts per SIMD = as many 4-wavefront workgroups per CU) leaves
         // room for in the 160 KB of a CU -- depth 4 at 2 wavefronts per SIMD -- and within the 64 KB a launch gets without asking.
         if (DR > 4) {
-            auto wg_bytes = [&](int d) { return (size_t)4 * wave_scratch_words(ctx.NK, ctx.stack_slots, lite, d, expire_w()) * sizeof(int); };
+            auto wg_bytes = [&](int d) { return (size_t)4 * wave_scratch_words(ctx.NK, ctx.stack_slots, lite, d, expire_w(), big_scope()) * sizeof(int); };
             while (ctx.sib_depth > 1 && (wg_bytes(ctx.sib_depth) > 64 * 1024 || (size_t)STCSP_BLOCK8_WAVES * wg_bytes(ctx.sib_depth) > 160 * 1024)) ctx.sib_depth--;
         }
-        const size_t scratch = (size_t)4 * wave_scratch_words(ctx.NK, ctx.stack_slots, lite, ctx.sib_depth, expire_w()) * sizeof(int);
+        const size_t scratch = (size_t)4 * wave_scratch_words(ctx.NK, ctx.stack_slots, lite, ctx.sib_depth, expire_w(), big_scope()) * sizeof(int);
         if (scratch > 160 * 1024) return fail(STCSP_E_UNSUPPORTED, "expression stack too deep for LDS");
         // stage the image in LDS when image + scratch leave room for >= 2 workgroups per CU
-        img_in_lds = (size_t)o.words * 4 + scratch <= 64 * 1024 && mgr.W == 1 && !long_key() && !many_until() && DR <= 4;  // (the wide, long-key, until-heavy and DR = 8 kernels exist in the partly-staged form only)
+        img_in_lds = (size_t)o.words * 4 + scratch <= 64 * 1024 && mgr.W == 1 && !long_key() && !many_until() && !big_scope() && DR <= 4;  // (the wide, long-key, until-heavy and DR = 8 kernels exist in the partly-staged form only)
         if (const char *ev = getenv("STCSP_IMG_LDS")) img_in_lds = img_in_lds && atoi(ev) != 0;  // tuning switch
         ctx.stage_words = img_in_lds ? o.words : 0;
         lds_bytes = scratch + (size_t)ctx.stage_words * 4;
@@ -503,14 +510,15 @@ struct stcsp_engine {
                 default: return fail(STCSP_E_INTERNAL, "no expansion kernel for a block of %d registers", DR);
             }
             if (!fn) return fail(STCSP_E_INTERNAL, "no expansion kernel for this program at DR = %d", DR);
-            if (big) {
-                // more than 64 KB of dynamic LDS has to be asked for, per kernel (the probe kernel stages the same image)
+            if (big || (big_scope() && lds_bytes > 64 * 1024)) {
+                // more than 64 KB of dynamic LDS has to be asked for, per kernel (the probe kernel stages the same image; the big-scope
+                // kernels ask when a deep expression stack takes them past 64 KB)
                 const void *pf;
                 switch (DR) {
                     case 1: pf = probe_fn<1>(); break;
                     case 2: pf = probe_fn<2>(); break;
                     case 4: pf = probe_fn<4>(); break;
-                    case 8: pf = probe_fn<8>(); break;  // (not reached: DR = 8 has no big-workgroup kernels)
+                    case 8: pf = probe_fn<8>(); break;  // (big scope only: DR = 8 has no big-workgroup kernels)
                     default: return fail(STCSP_E_INTERNAL, "no probe kernel for a block of %d registers", DR);
                 }
                 HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
@@ -533,7 +541,7 @@ struct stcsp_engine {
                         ctx.stage_words = 0;
                 }
             }
-            prefix_complete = !lite && !img_in_lds && !big && !compact_sweeps && mgr.W == 1 && !long_key() && !many_until() && DR <= 4 && prefix_need > 0 && ctx.stage_words >= prefix_need &&
+            prefix_complete = !lite && !img_in_lds && !big && !compact_sweeps && mgr.W == 1 && !long_key() && !many_until() && !big_scope() && DR <= 4 && prefix_need > 0 && ctx.stage_words >= prefix_need &&
                               !(getenv("STCSP_PREFIX_KERNEL") && atoi(getenv("STCSP_PREFIX_KERNEL")) == 0);
 #ifdef STCSP_PHASES
             if (DR == 4) prefix_complete = false;
@@ -608,6 +616,14 @@ struct stcsp_engine {
         if (1 + mgr.n_sig + mgr.n_until_cons > kMaxKeyWords)
             return fail(STCSP_E_UNSUPPORTED, "signature of %d words (%d next variables, %d until flags): at most %d words (a state key of %d)",
                         mgr.n_sig + mgr.n_until_cons, mgr.n_sig, mgr.n_until_cons, kMaxKeyWords - 1, kMaxKeyWords);
+        // constraints over more than 64 variables (up to 256: cset.cpp) run the bitset big-scope kernels only
+        if (const int ws = mgr.widest_scope(); ws > kLaneScope) {
+            if (mgr.intervals)
+                return fail(STCSP_E_UNSUPPORTED, "interval domains: a constraint over %d variables; the interval kernels take at most %d", ws, kLaneScope);
+            if (mgr.n_until_cons > 32)
+                return fail(STCSP_E_UNSUPPORTED, "a constraint over %d variables beside %d until constraints: models with a constraint over more than %d "
+                            "variables take at most 32 until constraints", ws, mgr.n_until_cons, kLaneScope);
+        }
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(STCSP_E_DEVICE, "no HIP device available");
         device = opt.device;
@@ -671,11 +687,12 @@ struct stcsp_engine {
                 if (pre < 0) return fail(pre, "%s", mgr.error.c_str());
             }
         }
+        big_scope_ = mgr.widest_scope() > kLaneScope;
         // block registers per lane: 1, 2, 4 or 8 (5..7 round up to 8); long keys: the KR = 2 kernels exist at DR = 4 and 8 only, and
-        // so do the kernels for more than 32 until constraints
+        // so do the kernels for more than 32 until constraints and for constraints over more than 64 variables
         DR = (N * K * W + 63) / 64;
         if (DR > 4) DR = 8;
-        if (DR == 3 || ctx.KL > 64 || many_until()) DR = std::max(DR, 4);
+        if (DR == 3 || ctx.KL > 64 || many_until() || big_scope()) DR = std::max(DR, 4);
         HIPCHK(d_arr_data.upload(mgr.array_data));
         ctx.arr_data = d_arr_data.p;
         rc = upload_program();
@@ -1258,8 +1275,31 @@ struct stcsp_engine {
             hipLaunchKernelGGL((k_expand_until<DRT, false, 1, KR, UW>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
         }
     }
+    // a constraint over more than 64 variables (DR = 4 or 8): W = 1 (plain or compacted sweeps), 2 and 4
+    template <int DRT, int KR>
+    const void *big_fn() const {
+        if (mgr.W == 2) return (const void *)k_expand_big<DRT, false, 2, KR>;
+        if (mgr.W > 2) return (const void *)k_expand_big<DRT, false, 4, KR>;
+        if (compact_sweeps) return (const void *)k_expand_big<DRT, true, 1, KR>;
+        return (const void *)k_expand_big<DRT, false, 1, KR>;
+    }
+    template <int DRT, int KR>
+    void launch_big() {
+        const Ctx *cp = (const Ctx *)d_ctx.p;
+        const Plan *pp = (const Plan *)d_plan.p;
+        if (mgr.W == 2)
+            hipLaunchKernelGGL((k_expand_big<DRT, false, 2, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+        else if (mgr.W > 2)
+            hipLaunchKernelGGL((k_expand_big<DRT, false, 4, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+        else if (compact_sweeps)
+            hipLaunchKernelGGL((k_expand_big<DRT, true, 1, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+        else
+            hipLaunchKernelGGL((k_expand_big<DRT, false, 1, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
+    }
     template <int DRT>
     const void *expand_fn() const {
+        if constexpr (DRT >= 4)
+            if (big_scope()) return long_key() ? big_fn<DRT, 2>() : big_fn<DRT, 1>();
         if constexpr (DRT >= 4)
             if (many_until()) return long_key() ? until_fn<DRT, 2>() : until_fn<DRT, 1>();
         if constexpr (DRT == 8) return long_key() ? expand8_fn<2>() : expand8_fn<1>();
@@ -1295,6 +1335,8 @@ struct stcsp_engine {
     }
     template <int DRT>
     const void *probe_fn() const {
+        if constexpr (DRT >= 4)
+            if (big_scope()) return compact_sweeps ? (const void *)k_probe_big<DRT, true> : (const void *)k_probe_big<DRT, false>;
         if constexpr (DRT == 8) {
             return compact_sweeps ? (const void *)k_probe<8, false, true, false> : (const void *)k_probe<8, false, false, false>;
         } else {
@@ -1308,6 +1350,12 @@ struct stcsp_engine {
     }
     template <int DRT>
     void launch_expand() {
+        if constexpr (DRT >= 4)
+            if (big_scope()) {
+                if (long_key()) launch_big<DRT, 2>();
+                else launch_big<DRT, 1>();
+                return;
+            }
         if constexpr (DRT >= 4)
             if (many_until()) {
                 if (long_key()) launch_until<DRT, 2>();
@@ -1437,6 +1485,14 @@ struct stcsp_engine {
     template <int DRT>
     void launch_probe(unsigned grid, uint32_t *blocks, int n, int set, uint32_t expire, int *outcome) {
         const Ctx *cp = (const Ctx *)d_ctx.p;
+        if constexpr (DRT >= 4)
+            if (big_scope()) {
+                if (compact_sweeps)
+                    hipLaunchKernelGGL((k_probe_big<DRT, true>), dim3(grid), dim3(256), lds_bytes, stream, cp, blocks, n, set, expire, outcome);
+                else
+                    hipLaunchKernelGGL((k_probe_big<DRT, false>), dim3(grid), dim3(256), lds_bytes, stream, cp, blocks, n, set, expire, outcome);
+                return;
+            }
         if constexpr (DRT == 8) {
             if (compact_sweeps)
                 hipLaunchKernelGGL((k_probe<8, false, true, false>), dim3(grid), dim3(256), lds_bytes, stream, cp, blocks, n, set, expire, outcome);
@@ -2627,7 +2683,7 @@ int stcsp_engine_donate(stcsp_engine *e, int64_t want, void **ptr, int64_t *coun
 }
 int stcsp_engine_adopt(stcsp_engine *e, const void *records, int64_t count) { return e ? e->adopt(records, count) : STCSP_E_INVALID; }
 int stcsp_engine_expand_variant(const stcsp_engine *e) {
-    return e ? (e->lite ? 1 : 0) | (e->shape1 ? 2 : 0) | (e->img_in_lds || e->big ? 4 : 0) : STCSP_E_INVALID;
+    return e ? (e->lite ? 1 : 0) | (e->shape1 ? 2 : 0) | (e->img_in_lds || e->big ? 4 : 0) | (e->big_scope() ? 8 : 0) : STCSP_E_INVALID;
 }
 int stcsp_engine_counters(stcsp_engine *e, stcsp_counters *out) {
     if (!e || !out) return STCSP_E_INVALID;
