@@ -222,6 +222,43 @@ typedef struct stcsp_post_result {
 
 int stcsp_engine_postprocess(stcsp_engine *engine, const stcsp_post_options *options, stcsp_post_result *out);
 
+/* ---- bisimulation quotient of the live automaton on the device (no reference counterpart) ---------
+ * The live automaton is what solutions.dot shows after stcsp_engine_postprocess(): the states with
+ * state_valid set that the root reaches over edges with edge_alive set (a valid root included), and
+ * those edges. The projected label of an edge is its `values` restricted to the observable variables.
+ * The result is the coarsest partition of the live states in which two states share a class only if
+ *   1. they have the same `final` flag, and
+ *   2. their live out-edges give the same SET of pairs (projected label, class of the destination):
+ * the largest bisimulation, which is unique. The root is an ordinary state; the quotient's root is its
+ * class. With every variable observable the live automaton is deterministic and the quotient is its
+ * minimal form. Under a projecting mask (the default hides the auxiliary `_V%d` variables of `next`,
+ * which carry look-ahead) the projected automaton is nondeterministic: the quotient still accepts the
+ * same language but is not guaranteed to be the smallest automaton that does.
+ * Valid after stcsp_engine_postprocess() (STCSP_E_STATE before it and after a truncated solve, whose open
+ * states have no known language), on unsharded engines (STCSP_E_UNSUPPORTED otherwise: run
+ * stcsp_automaton_bisimulation() of stcsp_host.h on the merged automaton). The flags used are the ones
+ * postprocess() last wrote, adversarial passes included. A state whose exact comparison with its class
+ * representative fails (a collision of the 128-bit signatures the rounds work with) gives
+ * STCSP_E_INTERNAL, never a wrong partition. */
+typedef struct stcsp_quotient_options {
+    const uint8_t *observable; /* [n_vars] nonzero = observable; NULL = every variable whose name does
+                                  not start with "_V"                                                  */
+    int32_t reserved[2];
+} stcsp_quotient_options;
+
+typedef struct stcsp_quotient_result {
+    int64_t n_states;           /* live states                                                         */
+    int64_t n_classes;
+    int64_t n_class_edges;      /* distinct (source class, projected label, destination class)         */
+    const int32_t *state_class; /* [stcsp_result::n_states] classes numbered by their least member's
+                                   state index (so the root's class is 0); -1 outside the live
+                                   automaton. Owned by the engine, valid until the next call on it      */
+    int32_t rounds;             /* refinement sweeps, the confirming one included: <= n_states + 1     */
+    double seconds;             /* wall time from the flags in HBM to state_class on the host          */
+} stcsp_quotient_result;
+
+int stcsp_engine_quotient(stcsp_engine *engine, const stcsp_quotient_options *options, stcsp_quotient_result *out);
+
 void stcsp_engine_destroy(stcsp_engine *engine);
 
 /* Message of the last error on this engine (or of the last failed create when engine==NULL). */

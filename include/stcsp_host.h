@@ -89,6 +89,27 @@ int64_t stcsp_automaton_num_states(const stcsp_automaton *a);      /* table size
 int64_t stcsp_automaton_num_live_states(const stcsp_automaton *a); /* reachable + printed        */
 int64_t stcsp_automaton_num_live_edges(const stcsp_automaton *a);
 
+/* ---- bisimulation quotient (definition: stcsp_engine.h, stcsp_engine_quotient) ----
+ * The exact CPU twin of the device pass, written as plain partition refinement with ordered containers: the
+ * checker of the device pass in the tests, and the path for automata whose flags live on the host (sharded
+ * runs, host adversarial passes). Uses the automaton's current flags (traverse / adversarial* / import_flags).
+ * observable: [n_vars], nonzero = observable; NULL = every variable whose name does not start with "_V".
+ * state_class_out: [num_states] classes numbered by their least member, -1 outside the live automaton.
+ * Returns the number of refinement rounds (>= 1) or a negative error. The mask is remembered for
+ * stcsp_automaton_quotient(). */
+int stcsp_automaton_bisimulation(stcsp_automaton *a, const uint8_t *observable, int32_t *state_class_out, int64_t *n_classes);
+/* Set the mask stcsp_automaton_quotient() projects with, when the partition comes from the device pass. */
+int stcsp_automaton_set_observable(stcsp_automaton *a, const uint8_t *observable);
+/* Build the quotient of `a` under a partition of its live states: one state per class, printed with the
+ * constraint id and signature of the member that the canonical numbering (breadth-first from the root,
+ * out-edges in label order) reaches first -- state indices depend on the search's scheduling, that
+ * numbering does not; one edge per distinct (source class, projected label, destination class), carrying
+ * the lexicographically least full label of the edges that project on it. The root is class 0; a
+ * partition without a live root gives the EMPTY automaton. Under a projecting mask the result is
+ * language-preserving, not necessarily minimal. write_dot, write_binary, canonical, renumber and
+ * order_by_label work on the result; free it with stcsp_automaton_free(). */
+int stcsp_automaton_quotient(const stcsp_automaton *a, const int32_t *state_class, int64_t n_classes, stcsp_automaton **out);
+
 /* Merge the per-shard results of a sharded run (global state ids, see stcsp_engine.h) into
  * one result with dense ids; runs the ok-fixpoint over the union. The merged result is owned
  * by the returned handle. */

@@ -83,6 +83,15 @@ class PostResult(C.Structure):
                 ("adver1", C.c_int32), ("adver2", C.c_int32), ("rounds", C.c_int32 * 3), ("seconds", C.c_double)]
 
 
+class QuotientOptions(C.Structure):
+    _fields_ = [("observable", C.POINTER(C.c_uint8)), ("reserved", C.c_int32 * 2)]
+
+
+class QuotientResult(C.Structure):
+    _fields_ = [("n_states", C.c_int64), ("n_classes", C.c_int64), ("n_class_edges", C.c_int64),
+                ("state_class", C.POINTER(C.c_int32)), ("rounds", C.c_int32), ("seconds", C.c_double)]
+
+
 F_KEEP_RAW_EDGES = 1
 F_NO_EXPORT = 2
 F_PROFILE = 4
@@ -96,7 +105,7 @@ ENGINE_SYMBOLS = [
     "stcsp_engine_candidate_bytes", "stcsp_engine_outbox", "stcsp_engine_commit", "stcsp_engine_finish",
     "stcsp_engine_counters", "stcsp_engine_sets_blob", "stcsp_engine_sets_import", "stcsp_engine_postprocess",
     "stcsp_engine_propagate", "stcsp_engine_set_expand_budget", "stcsp_engine_node_bytes", "stcsp_engine_donate",
-    "stcsp_engine_adopt", "stcsp_engine_expand_variant",
+    "stcsp_engine_adopt", "stcsp_engine_expand_variant", "stcsp_engine_quotient",
 ]
 # include/stcsp_sharded.h: the superstep loop + in-process transport (libstcsp_hip.so), the RCCL transport (libstcsp_rccl.so)
 SHARDED_SYMBOLS_HIP = ["stcsp_engine_solve_sharded", "stcsp_local_group_create", "stcsp_local_group_transport", "stcsp_local_group_destroy"]
@@ -110,6 +119,7 @@ HOST_SYMBOLS = [
     "stcsp_automaton_write_dot", "stcsp_automaton_canonical", "stcsp_automaton_num_states",
     "stcsp_automaton_num_live_states", "stcsp_automaton_num_live_edges",
     "stcsp_merge_shards", "stcsp_merged_result", "stcsp_merged_free", "stcsp_host_free",
+    "stcsp_automaton_bisimulation", "stcsp_automaton_set_observable", "stcsp_automaton_quotient",
 ]
 
 
@@ -178,6 +188,9 @@ def host_lib() -> C.CDLL:
         for f in ("stcsp_automaton_num_states", "stcsp_automaton_num_live_states", "stcsp_automaton_num_live_edges"):
             getattr(lib, f).argtypes = [C.c_void_p]
             getattr(lib, f).restype = C.c_int64
+        lib.stcsp_automaton_bisimulation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        lib.stcsp_automaton_set_observable.argtypes = [C.c_void_p, C.c_void_p]
+        lib.stcsp_automaton_quotient.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
         lib.stcsp_merge_shards.argtypes = [C.POINTER(C.POINTER(Result)), C.c_int, C.POINTER(C.c_void_p)]
         lib.stcsp_merged_result.argtypes = [C.c_void_p]
         lib.stcsp_merged_result.restype = C.POINTER(Result)
@@ -221,6 +234,8 @@ def bind_engine_api(lib: C.CDLL, prefix: str = "stcsp_engine") -> None:
         g("sets_import").argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int64]
     if hasattr(lib, f"{prefix}_postprocess"):
         g("postprocess").argtypes = [C.c_void_p, C.POINTER(PostOptions), C.POINTER(PostResult)]
+    if hasattr(lib, f"{prefix}_quotient"):
+        g("quotient").argtypes = [C.c_void_p, C.POINTER(QuotientOptions), C.POINTER(QuotientResult)]
     if hasattr(lib, f"{prefix}_propagate"):
         g("propagate").argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64)]
@@ -362,6 +377,50 @@ class Automaton:
         a = cls.__new__(cls)
         a._h, a._model, a._n_edges = h, None, 0
         return a
+
+    def _mask(self, observable):
+        """None (the default mask), "all", or a sequence of n_vars flags -> ctypes buffer or None."""
+        import numpy as np
+        if observable is None:
+            return None
+        nv = len(self._model.var_names) if self._model is not None else len(observable)
+        m = np.ones(nv, dtype=np.uint8) if isinstance(observable, str) and observable == "all" else np.ascontiguousarray(observable, dtype=np.uint8)
+        if m.shape != (nv,):
+            raise ValueError(f"observable must have one flag per variable ({nv})")
+        return m
+
+    def bisimulation(self, observable=None):
+        """The largest bisimulation of the live automaton under the labels projected on `observable` (None: every
+        variable whose name does not start with "_V"; "all"; or one flag per variable), by the host twin of
+        Engine.quotient(). Returns (state_class int32 ndarray, -1 outside the live automaton; n_classes; rounds)."""
+        import numpy as np
+        lib = host_lib()
+        m = self._mask(observable)
+        cls = np.full(max(self.n_states, 1), -1, dtype=np.int32)
+        n = C.c_int64()
+        rounds = lib.stcsp_automaton_bisimulation(self._h, m.ctypes.data if m is not None else None, cls.ctypes.data, C.byref(n))
+        if rounds < 0:
+            raise StcspError(rounds, "bisimulation failed")
+        return cls[:self.n_states], n.value, rounds
+
+    def quotient(self, state_class, observable=None) -> "Automaton":
+        """The quotient automaton under a partition of the live states (bisimulation() or Engine.quotient()): one
+        state per class, one edge per distinct (source class, projected label, destination class). `observable` is
+        the mask the partition was computed with (as in bisimulation())."""
+        import numpy as np
+        lib = host_lib()
+        cls = np.ascontiguousarray(state_class, dtype=np.int32)
+        if cls.shape != (self.n_states,):
+            raise ValueError("state_class must have one entry per state")
+        m = self._mask(observable)
+        lib.stcsp_automaton_set_observable(self._h, m.ctypes.data if m is not None else None)
+        h = C.c_void_p()
+        rc = lib.stcsp_automaton_quotient(self._h, cls.ctypes.data, int(cls.max(initial=-1)) + 1, C.byref(h))
+        if rc != 0:
+            raise StcspError(rc, "quotient failed: state_class is not a partition of the live states")
+        q = Automaton.__new__(Automaton)
+        q._h, q._model, q._n_edges = h, self._model, 0
+        return q
 
     def canonical(self) -> str:
         lib = host_lib()
@@ -518,6 +577,26 @@ class EngineBase:
         out = PostResult()
         self._check(self._f("postprocess")(self._h, C.byref(po), C.byref(out)))
         return out
+
+    def quotient(self, observable=None):
+        """Bisimulation quotient of the live automaton on the device, after postprocess(): the classes of the states
+        under the labels projected on `observable` (None: every variable whose name does not start with "_V"; "all";
+        or one flag per variable). Returns (state_class int32 ndarray with -1 outside the live automaton, n_classes,
+        rounds, seconds); the whole QuotientResult of the call is kept in self.quotient_result."""
+        import numpy as np
+        nv = self._model.n_vars
+        qo = QuotientOptions()
+        m = None
+        if observable is not None:
+            m = np.ones(nv, dtype=np.uint8) if isinstance(observable, str) and observable == "all" else np.ascontiguousarray(observable, dtype=np.uint8)
+            if m.shape != (nv,):
+                raise ValueError(f"observable must have one flag per variable ({nv})")
+            qo.observable = m.ctypes.data_as(C.POINTER(C.c_uint8))
+        out = QuotientResult()
+        self._check(self._f("quotient")(self._h, C.byref(qo), C.byref(out)))
+        self.quotient_result = out
+        cls = np.ctypeslib.as_array(out.state_class, shape=(max(self.result.n_states, 1),))[:self.result.n_states].copy()
+        return cls, out.n_classes, out.rounds, out.seconds
 
     def automaton(self, result: Result | None = None) -> Automaton:
         return Automaton(self._model, result if result is not None else self.result)

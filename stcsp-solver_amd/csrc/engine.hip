@@ -54,6 +54,7 @@ using namespace stcsp;
 
 #include "dev_kernels.hpp"
 #include "dev_postproc.hpp"
+#include "dev_quotient.hpp"
 
 using namespace stcsp::dev;
 
@@ -197,6 +198,15 @@ struct stcsp_engine {
     DevBuf<uint8_t> d_pvalid, d_pfinal, d_palive, d_pnodeok;
     DevBuf<uint32_t> d_pcover;
     std::vector<uint8_t> p_valid, p_final, p_alive;
+    // bisimulation quotient (dev_quotient.hpp) over the flags the last postprocess() left in d_pvalid / d_pfinal / d_palive
+    bool post_done = false;
+    std::vector<uint8_t> default_observable;  // [N] every variable whose name does not start with "_V"
+    DevBuf<uint8_t> d_qlive;
+    DevBuf<int32_t> d_qobs;
+    DevBuf<uint32_t> d_qsrc, d_qdst, d_qlid, d_qcls[2], d_qcnt, d_qtab_e, d_qtab_s, d_qctl;
+    DevBuf<unsigned long long> d_qacc[2];
+    std::vector<int32_t> q_class;
+    std::vector<uint32_t> q_raw, q_cnt;
 
     ~stcsp_engine() {
         // the device writes several of the pinned buffers freed below (progress mirror, streamed result arrays) from
@@ -595,6 +605,9 @@ struct stcsp_engine {
         mgr.intervals = (opt.flags & STCSP_F_INTERVAL_DOMAINS) != 0;
         int rc = mgr.init(p, sharded);
         if (rc != STCSP_OK) return fail(rc, "%s", mgr.error.c_str());
+        default_observable.assign((size_t)p->n_vars, 1);
+        for (int v = 0; v < p->n_vars; v++)
+            if (p->var_names && p->var_names[v] && strncmp(p->var_names[v], "_V", 2) == 0) default_observable[(size_t)v] = 0;
         mgr.device_tabulation = !(getenv("STCSP_DEVICE_TABULATE") && atoi(getenv("STCSP_DEVICE_TABULATE")) == 0);
         const int N = mgr.N, K = mgr.K;
         // domains of up to 32 values take one bitset word per (variable, time point), up to 64 two, up to 128 four (W; one W
@@ -1088,6 +1101,7 @@ struct stcsp_engine {
         translation_stops = 0;
         finished = false;
         exp_on_device = false;
+        post_done = false;
         ev_used = 0;
         seconds_expand_kernel = 0;
         expand_launches = 0;
@@ -2184,6 +2198,7 @@ struct stcsp_engine {
         if (a1 >= N || op >= N || ava >= N || a1 < -1 || op < -1 || (op >= 0 && ava < 0))
             return fail(STCSP_E_INVALID, "postprocess: variable index out of range");
         auto t0 = std::chrono::steady_clock::now();
+        post_done = false;
         const size_t E = exp_edges;
         const uint32_t S = n_states;
         auto width = [&](int v) { return (long long)mgr.ub[v] - (long long)mgr.lb[v] + 1; };
@@ -2294,6 +2309,147 @@ struct stcsp_engine {
         out->adver1 = adver1;
         out->adver2 = adver2;
         for (int i = 0; i < 3; i++) out->rounds[i] = rounds[i];
+        out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        post_done = true;
+        return STCSP_OK;
+    }
+
+    // Bisimulation quotient of the live automaton on the device (dev_quotient.hpp): classes of the
+    // states that are valid and reachable from the root over alive edges, under the labels projected on `observable`.
+    int quotient(const stcsp_quotient_options *qo, stcsp_quotient_result *out) {
+        if (sharded) return fail(STCSP_E_UNSUPPORTED, "the device quotient is for unsharded engines (stcsp_automaton_bisimulation on the merged automaton)");
+        if (!exp_on_device || !post_done) return fail(STCSP_E_STATE, "quotient needs the flags of postprocess() on the last solve");
+        if (truncated) return fail(STCSP_E_STATE, "quotient after a truncated solve: the open states of a partial automaton have no known language");
+        auto t0 = std::chrono::steady_clock::now();
+        const int N = ctx.N;
+        const uint32_t E = (uint32_t)exp_edges, S = n_states;
+        const uint8_t *mask = qo && qo->observable ? qo->observable : default_observable.data();
+        std::vector<int32_t> obs;
+        for (int v = 0; v < N; v++)
+            if (mask[v]) obs.push_back(v);
+        auto pow2 = [](size_t n) {
+            size_t c = 1024;
+            while (c < 2 * n) c <<= 1;
+            return c;
+        };
+        const size_t cap_e = pow2(E), cap_s = pow2(S);
+        if (cap_e > 0x80000000ull) return fail(STCSP_E_NOMEM, "edge list too large for the device quotient");
+        if (d_qlive.n < S) {
+            const size_t cap = (size_t)S + S / 4 + 256;
+            HIPCHK(d_qlive.alloc(cap));
+            HIPCHK(d_qcls[0].alloc(cap));
+            HIPCHK(d_qcls[1].alloc(cap));
+            HIPCHK(d_qcnt.alloc(cap));
+            HIPCHK(d_qacc[0].alloc(cap));
+            HIPCHK(d_qacc[1].alloc(cap));
+        }
+        if (d_qsrc.n < (size_t)E + 1) {
+            const size_t cap = (size_t)E + E / 4 + 256;
+            HIPCHK(d_qsrc.alloc(cap));
+            HIPCHK(d_qdst.alloc(cap));
+            HIPCHK(d_qlid.alloc(cap));
+        }
+        if (d_qtab_e.n < cap_e) HIPCHK(d_qtab_e.alloc(cap_e));
+        if (d_qtab_s.n < cap_s) HIPCHK(d_qtab_s.alloc(cap_s));
+        if (d_qobs.n < (size_t)N) HIPCHK(d_qobs.alloc((size_t)N));
+        if (!d_qctl.p) HIPCHK(d_qctl.alloc(Q_WORDS));
+        const unsigned eb = (E + 255) / 256, sb = (S + 255) / 256;
+        const uint32_t mask_e = (uint32_t)(cap_e - 1), mask_s = (uint32_t)(cap_s - 1);
+        uint32_t ctl[Q_WORDS] = {0, 0, 0, 0};
+        auto read_ctl = [&]() -> int {
+            HIPCHK(hipMemcpyAsync(ctl, d_qctl.p, sizeof ctl, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            return STCSP_OK;
+        };
+        auto check = [&]() -> int {
+            int rc = read_ctl();
+            if (rc != STCSP_OK) return rc;
+            if (ctl[Q_ERROR] & Q_ERR_TABLE_FULL) return fail(STCSP_E_INTERNAL, "quotient: a device table overflowed");
+            if (ctl[Q_ERROR]) return fail(STCSP_E_INTERNAL, "quotient: a state differs from its class representative (signature collision, flags %u)", ctl[Q_ERROR]);
+            return STCSP_OK;
+        };
+        int rc;
+        if (!obs.empty()) HIPCHK(hipMemcpyAsync(d_qobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemsetAsync(d_qctl.p, 0, sizeof ctl, stream));
+        // the live automaton: forward reachability from a valid root (what write_dot walks)
+        HIPCHK(hipMemsetAsync(d_qlive.p, 0, S, stream));
+        HIPCHK(hipMemcpyAsync(d_qlive.p, d_pvalid.p, 1, hipMemcpyDeviceToDevice, stream));
+        for (int sweeps = 0; E; sweeps++) {
+            HIPCHK(hipMemsetAsync(d_qctl.p + Q_CHANGED, 0, sizeof(uint32_t), stream));
+            hipLaunchKernelGGL(k_q_reach, dim3(eb), dim3(256), 0, stream, E, (const long long *)d_osrc.p, (const long long *)d_odst.p,
+                               (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_qlive.p, d_qctl.p);
+            if ((rc = read_ctl()) != STCSP_OK) return rc;
+            if (!ctl[Q_CHANGED]) break;
+            if (sweeps > (int)S + 8) return fail(STCSP_E_INTERNAL, "quotient: reachability did not converge");
+        }
+        // label ids (the one sweep over the label rows) and the 12-byte edge records of the rounds
+        if (E) {
+            HIPCHK(hipMemsetAsync(d_qtab_e.p, 0xff, cap_e * sizeof(uint32_t), stream));
+            hipLaunchKernelGGL(k_q_labels, dim3(eb), dim3(256), 0, stream, E, (const long long *)d_osrc.p, (const long long *)d_odst.p,
+                               (const int32_t *)d_oval.p, N, (const int32_t *)d_qobs.p, (int)obs.size(), (const uint8_t *)d_palive.p,
+                               (const uint8_t *)d_qlive.p, d_qtab_e.p, mask_e, d_qsrc.p, d_qdst.p, d_qlid.p, d_qctl.p);
+        }
+        // every live state starts in class 0; a round splits the classes by (final, set of (label id, class of destination))
+        HIPCHK(hipMemsetAsync(d_qcls[0].p, 0, (size_t)S * sizeof(uint32_t), stream));
+        int cur = 0, rounds = 0;
+        bool dedup = true;  // until round 1 has shown that no state has two edges with one projected label
+        auto edge_sweep = [&](bool dd) -> int {
+            hipLaunchKernelGGL(k_q_state_init, dim3(sb), dim3(256), 0, stream, S, (const uint8_t *)d_pfinal.p, d_qacc[0].p, d_qacc[1].p, d_qcnt.p);
+            if (!E) return STCSP_OK;
+            if (dd) HIPCHK(hipMemsetAsync(d_qtab_e.p, 0xff, cap_e * sizeof(uint32_t), stream));
+            hipLaunchKernelGGL(k_q_edges, dim3(eb), dim3(256), 0, stream, E, (const uint32_t *)d_qsrc.p, (const uint32_t *)d_qdst.p,
+                               (const uint32_t *)d_qlid.p, (const uint32_t *)d_qcls[cur].p, (int)dd, d_qtab_e.p, mask_e, d_qacc[0].p, d_qacc[1].p,
+                               d_qcnt.p, d_qctl.p);
+            return STCSP_OK;
+        };
+        for (uint32_t prev = 0;;) {
+            rounds++;
+            HIPCHK(hipMemsetAsync(d_qctl.p, 0, 2 * sizeof(uint32_t), stream));  // Q_CLASSES, Q_DUPS
+            if ((rc = edge_sweep(dedup)) != STCSP_OK) return rc;
+            HIPCHK(hipMemsetAsync(d_qtab_s.p, 0xff, cap_s * sizeof(uint32_t), stream));
+            hipLaunchKernelGGL(k_q_number, dim3(sb), dim3(256), 0, stream, S, (const uint8_t *)d_qlive.p, (const uint32_t *)d_qcls[cur].p,
+                               (const unsigned long long *)d_qacc[0].p, (const unsigned long long *)d_qacc[1].p, d_qtab_s.p, mask_s,
+                               d_qcls[1 - cur].p, d_qctl.p);
+            if ((rc = check()) != STCSP_OK) return rc;
+            cur = 1 - cur;
+            if (rounds == 1 && ctl[Q_DUPS] == 0) dedup = false;
+            if (ctl[Q_CLASSES] == prev) break;
+            prev = ctl[Q_CLASSES];
+            if ((uint32_t)rounds > S + 1) return fail(STCSP_E_INTERNAL, "quotient: refinement did not converge");
+        }
+        // exact verification against the class representatives; leaves the distinct pairs per state in d_qcnt
+        if ((rc = edge_sweep(true)) != STCSP_OK) return rc;
+        if (E)
+            hipLaunchKernelGGL(k_q_verify_edges, dim3(eb), dim3(256), 0, stream, E, (const uint32_t *)d_qsrc.p, (const uint32_t *)d_qdst.p,
+                               (const uint32_t *)d_qlid.p, (const uint32_t *)d_qcls[cur].p, (const uint32_t *)d_qtab_e.p, mask_e, d_qctl.p);
+        hipLaunchKernelGGL(k_q_verify_states, dim3(sb), dim3(256), 0, stream, S, (const uint8_t *)d_qlive.p, (const uint8_t *)d_pfinal.p,
+                           (const uint32_t *)d_qcls[cur].p, (const uint32_t *)d_qcnt.p, d_qctl.p);
+        HIPCHK(hipGetLastError());
+        q_raw.resize(S);
+        q_cnt.resize(S);
+        HIPCHK(hipMemcpyAsync(q_raw.data(), d_qcls[cur].p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(q_cnt.data(), d_qcnt.p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        if ((rc = check()) != STCSP_OK) return rc;
+        // canonical class numbers: by least member (the first state, in index order, that shows the class)
+        q_class.assign(S, -1);
+        std::vector<int32_t> number(S, -1);
+        int64_t n_live = 0, n_classes = 0, n_class_edges = 0;
+        for (uint32_t s = 0; s < S; s++) {
+            const uint32_t r = q_raw[s];
+            if (r == kQEmpty) continue;
+            n_live++;
+            if (number[r] < 0) {
+                number[r] = (int32_t)n_classes++;
+                n_class_edges += q_cnt[r];
+            }
+            q_class[s] = number[r];
+        }
+        memset(out, 0, sizeof *out);
+        out->n_states = n_live;
+        out->n_classes = n_classes;
+        out->n_class_edges = n_class_edges;
+        out->state_class = q_class.data();
+        out->rounds = rounds;
         out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         return STCSP_OK;
     }
@@ -2440,6 +2596,7 @@ struct stcsp_engine {
         E_out = live;
         exp_edges = live;
         exp_on_device = true;
+        post_done = false;
         return STCSP_OK;
     }
 
@@ -2655,6 +2812,11 @@ int stcsp_engine_export(stcsp_engine *e, stcsp_result *result) {
 int stcsp_engine_postprocess(stcsp_engine *e, const stcsp_post_options *options, stcsp_post_result *out) {
     if (!e || !out) return STCSP_E_INVALID;
     return e->postprocess(options, out);
+}
+
+int stcsp_engine_quotient(stcsp_engine *e, const stcsp_quotient_options *options, stcsp_quotient_result *out) {
+    if (!e || !out) return STCSP_E_INVALID;
+    return e->quotient(options, out);
 }
 
 void stcsp_engine_destroy(stcsp_engine *e) { delete e; }

@@ -724,6 +724,174 @@ struct Automaton {
         if (n_live_edges) *n_live_edges = ne;
         return out.take();
     }
+
+    // ---- bisimulation quotient (no reference counterpart; device twin: dev_quotient.hpp, definition: stcsp_engine.h) ----
+    std::vector<uint8_t> observable;  // [n_vars], empty = the default mask (every variable whose name does not start with "_V")
+    std::vector<uint8_t> observable_mask(const uint8_t *obs) const {
+        std::vector<uint8_t> m((size_t)n_vars, 1);
+        for (int v = 0; v < n_vars; v++) m[(size_t)v] = obs ? (uint8_t)(obs[v] != 0) : (uint8_t)(names[(size_t)v].compare(0, 2, "_V") != 0);
+        return m;
+    }
+    // the live automaton: valid states the (valid) root reaches over alive edges
+    std::vector<uint8_t> live_states() const {
+        std::vector<uint8_t> live((size_t)n_states, 0);
+        if (n_states == 0 || !valid[0]) return live;
+        std::vector<int64_t> stack{0};
+        live[0] = 1;
+        while (!stack.empty()) {
+            const int64_t u = stack.back();
+            stack.pop_back();
+            for (int64_t k = out_off[u]; k < out_off[u + 1]; k++) {
+                const int64_t e = out_edge[k], v = edst[e];
+                if (ealive[e] && valid[v] && !live[v]) {
+                    live[v] = 1;
+                    stack.push_back(v);
+                }
+            }
+        }
+        return live;
+    }
+    // tests/canon.py's numbering: breadth-first from the root, the live out-edges of a state in label order; -1 = not reached
+    std::vector<int64_t> canonical_numbers() const {
+        std::vector<int64_t> num((size_t)n_states, -1), order, edges;
+        if (n_states == 0 || !valid[0]) return num;
+        num[0] = 0;
+        order.push_back(0);
+        for (size_t q = 0; q < order.size(); q++) {
+            const int64_t u = order[q];
+            edges.clear();
+            for (int64_t k = out_off[u]; k < out_off[u + 1]; k++)
+                if (ealive[out_edge[k]]) edges.push_back(out_edge[k]);
+            std::sort(edges.begin(), edges.end(), [&](int64_t a, int64_t b) {
+                const int32_t *x = &eval[a * n_vars], *y = &eval[b * n_vars];
+                for (int i = 0; i < n_vars; i++)
+                    if (x[i] != y[i]) return x[i] < y[i];
+                return a < b;
+            });
+            for (int64_t e : edges)
+                if (num[(size_t)edst[e]] < 0) {
+                    num[(size_t)edst[e]] = (int64_t)order.size();
+                    order.push_back(edst[e]);
+                }
+        }
+        return num;
+    }
+    // Plain partition refinement with ordered containers: every round keys each live state by (its class, its final
+    // flag, the set of (projected label, class of destination) over its live out-edges) until the class count stops
+    // growing; classes are then numbered by their least member. Returns the number of rounds.
+    int bisimulation(const uint8_t *obs, int32_t *state_class, int64_t *n_classes) {
+        observable = observable_mask(obs);
+        const std::vector<uint8_t> live = live_states();
+        std::map<std::vector<int32_t>, int32_t> label_ids;
+        std::vector<int32_t> lid(esrc.size(), -1), proj;
+        for (size_t e = 0; e < esrc.size(); e++) {
+            if (!ealive[e] || !live[(size_t)esrc[e]] || !live[(size_t)edst[e]]) continue;
+            proj.clear();
+            for (int v = 0; v < n_vars; v++)
+                if (observable[(size_t)v]) proj.push_back(eval[e * n_vars + v]);
+            lid[e] = label_ids.emplace(proj, (int32_t)label_ids.size()).first->second;
+        }
+        std::vector<int32_t> cls((size_t)n_states, -1), next((size_t)n_states, -1);
+        for (int64_t s = 0; s < n_states; s++)
+            if (live[(size_t)s]) cls[(size_t)s] = 0;
+        typedef std::set<std::pair<int32_t, int32_t>> Pairs;
+        int rounds = 0;
+        for (size_t prev = 0;;) {
+            rounds++;
+            std::map<std::pair<std::pair<int32_t, int>, Pairs>, int32_t> ids;  // ((class, final), pairs) -> new class
+            for (int64_t s = 0; s < n_states; s++) {
+                if (!live[(size_t)s]) continue;
+                Pairs pairs;
+                for (int64_t k = out_off[s]; k < out_off[s + 1]; k++) {
+                    const int64_t e = out_edge[k];
+                    if (lid[(size_t)e] >= 0) pairs.insert({lid[(size_t)e], cls[(size_t)edst[e]]});
+                }
+                next[(size_t)s] = ids.emplace(std::make_pair(std::make_pair(cls[(size_t)s], (int)final_[(size_t)s]), std::move(pairs)), (int32_t)ids.size()).first->second;
+            }
+            cls.swap(next);
+            if (ids.size() == prev) break;
+            prev = ids.size();
+        }
+        std::map<int32_t, int32_t> number;  // states are visited in index order: a class is numbered when its least member is met
+        for (int64_t s = 0; s < n_states; s++) {
+            if (!live[(size_t)s]) {
+                state_class[s] = -1;
+                continue;
+            }
+            state_class[s] = number.emplace(cls[(size_t)s], (int32_t)number.size()).first->second;
+        }
+        if (n_classes) *n_classes = (int64_t)number.size();
+        return rounds;
+    }
+    // The quotient under a partition (state_class as bisimulation() or the device pass give it): one state per class,
+    // printed with the constraint id and signature of the member the canonical numbering reaches first; one edge per distinct (source class, projected
+    // label, destination class), carrying the lexicographically least full label among the edges that project on it.
+    int quotient(const int32_t *state_class, int64_t n_classes, Automaton &q) const {
+        if (n_classes < 0) return STCSP_E_INVALID;
+        const std::vector<uint8_t> mask = observable.empty() ? observable_mask(nullptr) : observable;
+        q.n_vars = n_vars;
+        q.sig_len = sig_len;
+        q.n_sig_vars = n_sig_vars;
+        q.n_until = n_until;
+        q.names = names;
+        q.is_sig = is_sig;
+        q.var_lb = var_lb;
+        q.var_ub = var_ub;
+        q.observable = observable;
+        const bool empty = n_classes == 0 || n_states == 0 || state_class[0] != 0;  // no live root: the EMPTY automaton
+        q.n_states = empty ? 1 : n_classes;
+        q.cid.assign((size_t)q.n_states, 0);
+        q.sig.assign((size_t)q.n_states * sig_len, 0);
+        q.fail.assign((size_t)q.n_states, 0);
+        q.valid.assign((size_t)q.n_states, empty ? 0 : 1);
+        q.final_.assign((size_t)q.n_states, 0);
+        q.id.resize((size_t)q.n_states);
+        for (int64_t c = 0; c < q.n_states; c++) q.id[(size_t)c] = c;
+        if (!empty) {
+            // the member a class is printed as: the one the canonical numbering reaches first (state indices depend on the
+            // search's scheduling, that numbering does not); the root for the root's class
+            const std::vector<int64_t> num = canonical_numbers();
+            std::vector<int64_t> rep((size_t)n_classes, -1);
+            auto before = [&](int64_t a, int64_t b) { return num[(size_t)a] >= 0 && (num[(size_t)b] < 0 || num[(size_t)a] < num[(size_t)b]); };
+            for (int64_t s = 0; s < n_states; s++) {
+                const int32_t c = state_class[s];
+                if (c < -1 || c >= n_classes) return STCSP_E_INVALID;
+                if (c < 0) continue;
+                int64_t &r = rep[(size_t)c];
+                if (r < 0 || before(s, r)) r = s;
+            }
+            for (int64_t c = 0; c < n_classes; c++) {
+                const int64_t s = rep[(size_t)c];
+                if (s < 0) return STCSP_E_INVALID;  // a class without a member
+                q.cid[(size_t)c] = cid[(size_t)s];
+                q.final_[(size_t)c] = final_[(size_t)s];
+                std::copy(sig.begin() + s * sig_len, sig.begin() + (s + 1) * sig_len, q.sig.begin() + c * sig_len);
+            }
+            typedef std::pair<std::pair<int32_t, int32_t>, std::vector<int32_t>> Key;  // ((source class, destination class), projected label)
+            std::map<Key, int64_t> least;                                              // -> edge with the least full label
+            Key key;
+            for (size_t e = 0; e < esrc.size(); e++) {
+                const int32_t cs = state_class[esrc[e]], cd = state_class[edst[e]];
+                if (!ealive[e] || cs < 0 || cd < 0) continue;
+                key.first = {cs, cd};
+                key.second.clear();
+                for (int v = 0; v < n_vars; v++)
+                    if (mask[(size_t)v]) key.second.push_back(eval[e * n_vars + v]);
+                auto it = least.emplace(key, (int64_t)e);
+                if (!it.second && std::lexicographical_compare(eval.begin() + e * n_vars, eval.begin() + (e + 1) * n_vars,
+                                                               eval.begin() + it.first->second * n_vars, eval.begin() + (it.first->second + 1) * n_vars))
+                    it.first->second = (int64_t)e;
+            }
+            for (const auto &kv : least) {
+                q.esrc.push_back(kv.first.first.first);
+                q.edst.push_back(kv.first.first.second);
+                q.eval.insert(q.eval.end(), eval.begin() + kv.second * n_vars, eval.begin() + (kv.second + 1) * n_vars);
+            }
+        }
+        q.ealive.assign(q.esrc.size(), 1);
+        q.build_csr();
+        return STCSP_OK;
+    }
 };
 
 struct Merged {
@@ -835,6 +1003,38 @@ int stcsp_automaton_read_binary(const char *path, stcsp_automaton **out) {
     } catch (...) {
         delete h;
         return STCSP_E_INVALID;
+    }
+    *out = h;
+    return STCSP_OK;
+}
+
+int stcsp_automaton_bisimulation(stcsp_automaton *a, const uint8_t *observable, int32_t *state_class_out, int64_t *n_classes) {
+    if (!a || !state_class_out) return STCSP_E_INVALID;
+    try {
+        return a->a.bisimulation(observable, state_class_out, n_classes);
+    } catch (const std::bad_alloc &) {
+        return STCSP_E_NOMEM;
+    }
+}
+int stcsp_automaton_set_observable(stcsp_automaton *a, const uint8_t *observable) {
+    if (!a) return STCSP_E_INVALID;
+    a->a.observable = a->a.observable_mask(observable);
+    return STCSP_OK;
+}
+int stcsp_automaton_quotient(const stcsp_automaton *a, const int32_t *state_class, int64_t n_classes, stcsp_automaton **out) {
+    if (!a || !state_class || !out) return STCSP_E_INVALID;
+    stcsp_automaton *h = nullptr;
+    try {
+        h = new stcsp_automaton();
+        const int rc = a->a.quotient(state_class, n_classes, h->a);
+        if (rc != STCSP_OK) {
+            delete h;
+            return rc;
+        }
+        h->root_final = h->a.final_[0];
+    } catch (const std::bad_alloc &) {
+        delete h;
+        return STCSP_E_NOMEM;
     }
     *out = h;
     return STCSP_OK;

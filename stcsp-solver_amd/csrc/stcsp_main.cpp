@@ -2,7 +2,7 @@
 // (src/stcsp.y:180-219 main, src/solver.cpp:195-359 solve): same flags, same stdout contract,
 // same solutions.dot. The search itself runs on the MI355X engine behind the C-ABI.
 //
-//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] input.csp
+//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] input.csp
 //
 // --binary=<file> (not in the reference) additionally writes the printed automaton in the compact
 // binary form of include/stcsp_host.h.
@@ -12,6 +12,11 @@
 // hipMemcpyPeerAsync); the shards' automata are merged and post-processed on the host.
 // --intervals (not in the reference) holds every variable as an interval, like the reference does (STCSP_F_INTERVAL_DOMAINS):
 // domains of any width in [INT_MIN, INT_MAX], where the default bitset domains take at most 128 values. Works with --shards=N.
+// --quotient (not in the reference) writes the bisimulation quotient of the automaton instead of the automaton itself: the states
+// that accept the same language over the observable variables are folded into one (include/stcsp_engine.h). Observable are the
+// variables whose name does not start with "_V"; --quotient=all makes every variable observable (the automaton is then deterministic
+// and the quotient is its minimal form). The stdout line is unchanged; "quotient: <live states> -> <classes>" goes to stderr. The
+// partition is computed on the device, or by the host twin where the flags live on the host (--shards=N, host adversarial passes).
 // When an -a / -z variable is wider than the device post-processing passes take, the host passes run instead.
 //
 // Options must be glued to their value (-k3, not -k 3): like the reference, the first argument
@@ -40,10 +45,34 @@ static double cpu_time() {  // cpuTime (util.cpp:149-155)
 
 struct Flags {
     bool print_solution = false, testing = false, adv1 = false, adv2 = false, intervals = false;
+    bool quotient = false, quotient_all = false;
     int prefix_k = 2, time_limit = 0, shards = 1;
     const char *file = nullptr;
     const char *binary = nullptr;
 };
+
+// --quotient: replace *a by its quotient under `state_class` (from the device pass), or under the host twin's partition when
+// state_class is NULL
+static int fold(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, const int32_t *state_class, int64_t n_live, int64_t n_classes) {
+    std::vector<uint8_t> all((size_t)p->n_vars, 1);
+    const uint8_t *mask = f.quotient_all ? all.data() : nullptr;
+    std::vector<int32_t> host_class;
+    if (!state_class) {
+        host_class.assign((size_t)stcsp_automaton_num_states(*a) + 1, -1);
+        if (stcsp_automaton_bisimulation(*a, mask, host_class.data(), &n_classes) < 0) return 1;
+        state_class = host_class.data();
+        n_live = 0;
+        for (int32_t c : host_class) n_live += c >= 0;
+    } else {
+        stcsp_automaton_set_observable(*a, mask);
+    }
+    stcsp_automaton *q = nullptr;
+    if (stcsp_automaton_quotient(*a, state_class, n_classes, &q) != STCSP_OK) return 1;
+    stcsp_automaton_free(*a);
+    *a = q;
+    fprintf(stderr, "quotient: %lld -> %lld\n", (long long)n_live, (long long)n_classes);
+    return 0;
+}
 
 static int run_once(const Flags &f, bool print_line, double *total) {
     double t_init = cpu_time();
@@ -93,6 +122,10 @@ static int run_once(const Flags &f, bool print_line, double *total) {
         stcsp_automaton_traverse(a);
         if (f.adv1) printf("adver1: %d; ", stcsp_automaton_adversarial(a, 5));
         if (f.adv2) printf("adver2: %d\n", stcsp_automaton_adversarial2(a, 5, 6));
+        if (f.quotient && fold(f, p, &a, nullptr, 0, 0)) {
+            fprintf(stderr, "the quotient could not be built\n");
+            return 1;
+        }
     } else if (rc != STCSP_OK) {
         fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
         return 1;
@@ -100,6 +133,19 @@ static int run_once(const Flags &f, bool print_line, double *total) {
         stcsp_automaton_import_flags(a, post.state_valid, post.state_final, post.edge_alive);
         if (f.adv1) printf("adver1: %d; ", post.adver1);
         if (f.adv2) printf("adver2: %d\n", post.adver2);
+        if (f.quotient) {
+            std::vector<uint8_t> all((size_t)p->n_vars, 1);
+            stcsp_quotient_options qo = {f.quotient_all ? all.data() : nullptr, {0, 0}};
+            stcsp_quotient_result qr;
+            if (stcsp_engine_quotient(eng, &qo, &qr) != STCSP_OK) {
+                fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
+                return 1;
+            }
+            if (fold(f, p, &a, qr.state_class, qr.n_states, qr.n_classes)) {
+                fprintf(stderr, "the quotient could not be built\n");
+                return 1;
+            }
+        }
     }
     if (f.print_solution || f.binary) stcsp_automaton_order_by_label(a);  // reproducible files whatever the GPU's scheduling
     stcsp_automaton_renumber(a);
@@ -191,6 +237,10 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
     stcsp_automaton_traverse(a);  // (host passes: the merged automaton lives on the host)
     if (f.adv1) printf("adver1: %d; ", stcsp_automaton_adversarial(a, 5));
     if (f.adv2) printf("adver2: %d\n", stcsp_automaton_adversarial2(a, 5, 6));
+    if (f.quotient && fold(f, p, &a, nullptr, 0, 0)) {  // (host twin: the merged automaton lives on the host)
+        fprintf(stderr, "the quotient could not be built\n");
+        return 1;
+    }
     if (f.print_solution || f.binary) stcsp_automaton_order_by_label(a);
     stcsp_automaton_renumber(a);
     double proc_time = cpu_time() - t_proc;
@@ -223,6 +273,11 @@ int main(int argc, char **argv) {
         }
         if (strncmp(a, "--binary=", 9) == 0) {
             f.binary = a + 9;
+            continue;
+        }
+        if (strcmp(a, "--quotient") == 0 || strcmp(a, "--quotient=all") == 0) {
+            f.quotient = true;
+            f.quotient_all = a[10] == '=';
             continue;
         }
         if (strcmp(a, "--intervals") == 0) {
