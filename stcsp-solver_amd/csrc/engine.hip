@@ -135,19 +135,15 @@ struct stcsp_engine {
     bool shape1 = false;
     int prefix_need = 0;          // image words that must be staged for the L = 2 kernels (0: not applicable)
     bool prefix_complete = false; // ... and they are: general program, everything but cons / tables in the staged prefix
-    // Keys of more than 64 words (set tag + signature): a lane holds key words j and 64 + j. Only the general, partly-staged
-    // kernels at DR = 4 and 8 get the second key register (k_expand<DR, false, CS, false, false, W, 2>, k_commit<DR, 2>), so the
-    // LITE / prefix kernels of the shipped programs (keys of at most 64 words) stay exactly as they are.
-    bool long_key() const { return ctx.KL > 64; }
-    // More than 32 until constraints: records carry expire_words(n_until_cons) expire words (device_types.hpp). They run the
-    // k_expand_until / k_commit_until kernels with kMaxExpireWords words per node -- the general, partly-staged kernels at DR = 4
-    // and 8, with one or two key registers -- so the kernels of models with at most 32 until constraints stay exactly as they are.
-    bool many_until() const { return ctx.n_until_cons > 32; }
-    // A point constraint over more than kLaneScope (64) variables: the k_expand_big kernels (general, partly-staged, DR = 4 and 8,
-    // one or two key registers), whose revisions compact a scope's open variables into lanes, and k_probe_big<DR, CS>.
-    // Decided once, at creation, from the sets known then (translation never widens a scope: upload_program checks it).
-    bool big_scope_ = false;
+    // The capacity features (which kernels they run: the table at select_kernels). create() raises DR to 4 for the last three.
+    bool long_key() const { return ctx.KL > 64; }               // key (set tag + signature) of more than 64 words: a lane holds words j and 64 + j
+    bool many_until() const { return ctx.n_until_cons > 32; }   // records carry expire_words(n_until_cons) expire words (device_types.hpp)
+    bool big_scope_ = false;  // a point constraint over more than kLaneScope (64) variables. Decided once, at creation, from the sets
+                              // known then (translation never widens a scope: upload_program checks it)
     bool big_scope() const { return big_scope_; }
+    // Wide or interval domains, blocks of more than 256 words and the three features above have only the general, partly-staged
+    // kernels: no LITE, image-in-LDS, prefix, big-workgroup or one-register-shape form (select_kernels says why)
+    bool general_only() const { return mgr.W > 1 || DR > 4 || long_key() || many_until() || big_scope(); }
     int expire_w() const { return expire_words(ctx.n_until_cons); }
     bool interpreted = false;     // some wavefront-revised constraint has no tuple bitmap (postfix interpreter: uniformly expensive nodes)
     bool wide_conditional = false;  // some conditional constraint spans more than kWideConditional tuples (the juggling family's `A == if B0 eq 1 then next B0 else if ...`)
@@ -285,9 +281,7 @@ struct stcsp_engine {
                 interpreted = interpreted || cd.bitmap_off < 0;
             }
         if (const char *ev = getenv("STCSP_LITE")) lite = lite && atoi(ev) != 0;  // tuning switch
-        if (mgr.W > 1) lite = false;  // (wide domains: every item is revised by dev_wide.hpp's bounds propagation)
-        if (long_key() || many_until() || big_scope()) lite = false;
-        if (DR > 4) lite = false;  // (blocks of more than 256 words: the general, partly-staged kernels only)
+        if (general_only()) lite = false;  // (wide domains, besides: every item is revised by dev_wide.hpp's bounds propagation)
         // one contiguous image; every section starts on a 16-byte boundary
         std::vector<uint32_t> img;
         ImgOff o{};
@@ -473,7 +467,7 @@ struct stcsp_engine {
         const size_t scratch = (size_t)4 * wave_scratch_words(ctx.NK, ctx.stack_slots, lite, ctx.sib_depth, expire_w(), big_scope()) * sizeof(int);
         if (scratch > 160 * 1024) return fail(STCSP_E_UNSUPPORTED, "expression stack too deep for LDS");
         // stage the image in LDS when image + scratch leave room for >= 2 workgroups per CU
-        img_in_lds = (size_t)o.words * 4 + scratch <= 64 * 1024 && mgr.W == 1 && !long_key() && !many_until() && !big_scope() && DR <= 4;  // (the wide, long-key, until-heavy and DR = 8 kernels exist in the partly-staged form only)
+        img_in_lds = (size_t)o.words * 4 + scratch <= 64 * 1024 && !general_only();
         if (const char *ev = getenv("STCSP_IMG_LDS")) img_in_lds = img_in_lds && atoi(ev) != 0;  // tuning switch
         ctx.stage_words = img_in_lds ? o.words : 0;
         lds_bytes = scratch + (size_t)ctx.stage_words * 4;
@@ -510,31 +504,16 @@ struct stcsp_engine {
         {
             int per_cu = 0;
             hipError_t e;
-            const void *fn;
             prefix_complete = false;  // (decided below, from what gets staged)
-            switch (DR) {
-                case 1: fn = expand_fn<1>(); break;
-                case 2: fn = expand_fn<2>(); break;
-                case 4: fn = expand_fn<4>(); break;
-                case 8: fn = expand_fn<8>(); break;
-                default: return fail(STCSP_E_INTERNAL, "no expansion kernel for a block of %d registers", DR);
-            }
-            if (!fn) return fail(STCSP_E_INTERNAL, "no expansion kernel for this program at DR = %d", DR);
+            if ((rc = select_kernels())) return rc;
+            const void *fn = (const void *)kernels.expand;
             if (big || (big_scope() && lds_bytes > 64 * 1024)) {
                 // more than 64 KB of dynamic LDS has to be asked for, per kernel (the probe kernel stages the same image; the big-scope
                 // kernels ask when a deep expression stack takes them past 64 KB)
-                const void *pf;
-                switch (DR) {
-                    case 1: pf = probe_fn<1>(); break;
-                    case 2: pf = probe_fn<2>(); break;
-                    case 4: pf = probe_fn<4>(); break;
-                    case 8: pf = probe_fn<8>(); break;  // (big scope only: DR = 8 has no big-workgroup kernels)
-                    default: return fail(STCSP_E_INTERNAL, "no probe kernel for a block of %d registers", DR);
-                }
                 HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                HIPCHK(hipFuncSetAttribute(pf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+                HIPCHK(hipFuncSetAttribute((const void *)kernels.probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
             }
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, big ? STCSP_BIG_WAVES * 64 : 256, lds_bytes);
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, (int)kernels.expand_threads, lds_bytes);
             if (big && (e != hipSuccess || per_cu < 1)) return fail(STCSP_E_INTERNAL, "big-workgroup kernel does not fit a CU (%zu B of LDS)", lds_bytes);
             if (try_prefix && e == hipSuccess && per_cu > 0) {
                 // the longest prefix of whole hot sections that costs no resident workgroup: the kernel's
@@ -551,23 +530,17 @@ struct stcsp_engine {
                         ctx.stage_words = 0;
                 }
             }
-            prefix_complete = !lite && !img_in_lds && !big && !compact_sweeps && mgr.W == 1 && !long_key() && !many_until() && !big_scope() && DR <= 4 && prefix_need > 0 && ctx.stage_words >= prefix_need &&
-                              !(getenv("STCSP_PREFIX_KERNEL") && atoi(getenv("STCSP_PREFIX_KERNEL")) == 0);
-#ifdef STCSP_PHASES
-            if (DR == 4) prefix_complete = false;
-#endif
+            prefix_complete = !lite && !img_in_lds && !big && !compact_sweeps && !general_only() && staged_general_exists(DR) && prefix_need > 0 &&
+                              ctx.stage_words >= prefix_need && !(getenv("STCSP_PREFIX_KERNEL") && atoi(getenv("STCSP_PREFIX_KERNEL")) == 0);
             if (prefix_complete) {  // the kernel that will run: its own occupancy
-                const void *f2;
-                switch (DR) {
-                    case 1: f2 = expand_fn<1>(); break;
-                    case 2: f2 = expand_fn<2>(); break;
-                    case 4: f2 = expand_fn<4>(); break;
-                    case 8: f2 = expand_fn<8>(); break;  // (not reached: DR = 8 has no prefix kernels)
-                    default: return fail(STCSP_E_INTERNAL, "no expansion kernel for a block of %d registers", DR);
-                }
+                if ((rc = select_kernels())) return rc;
                 int pc2 = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc2, f2, 256, lds_bytes) == hipSuccess && pc2 > 0) per_cu = pc2;
-                else prefix_complete = false;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc2, (const void *)kernels.expand, 256, lds_bytes) == hipSuccess && pc2 > 0) {
+                    per_cu = pc2;
+                } else {
+                    prefix_complete = false;
+                    if ((rc = select_kernels())) return rc;
+                }
             }
             hipDeviceProp_t prop;
             if (e == hipSuccess && per_cu > 0 && hipGetDeviceProperties(&prop, device) == hipSuccess)
@@ -1214,226 +1187,168 @@ struct stcsp_engine {
         return STCSP_OK;
     }
 
-    // kernel variant: whole image in LDS or not (L), compacted sweeps (sets with > kCompactSweepItems small
-    // items: CS), no general wavefront revision (LITE)
-    // (the instrumented build, -DSTCSP_PHASES, cannot be compiled for <4, image in LDS, general>: hipcc 7.2 stops with "Illegal
-    // instruction detected: V_CMP_NE_U32_e32 0, $src_shared_base" in those instantiations; there the same programs run the
-    // partly-staged kernels instead. The product build has them all.)
+    // ---- Which kernels this engine runs. Chosen here and nowhere else: select_kernels() walks the families below once and records
+    // the expansion, probe and commit kernel in `kernels`; upload_program sizes the grid and raises the dynamic-LDS limit for exactly
+    // these, and the solve loop, fresh_init, propagate and commit launch them. The choice is a pure function of the flags
+    // upload_program decides (lite, img_in_lds, big, shape1, compact_sweeps, prefix_complete) and of what create() fixed (DR, mgr.W,
+    // mgr.intervals, key length, until constraints, big scope), so whoever changes one of them selects again.
+    //
+    // k_expand, in order of preference (CS: compacted sweeps, a set with more than kCompactSweepItems small items; KR: key
+    // registers, 2 for a long key; "the four (CS, W)": W = 1 plain or compacted, W = 2, W = 4):
+    //   family              kernel                                                  chosen when
+    //   big scope           k_expand_big<DR, CS, W, KR>                             a constraint over more than 64 variables; DR = 4 / 8, the four
+    //                                                                               (CS, W). Revisions compact a scope's open variables into lanes.
+    //   until-heavy         k_expand_until<DR, CS, W, KR, kMaxExpireWords>          more than 32 until constraints; DR = 4 / 8, the four (CS, W)
+    //                                                                               and, at DR = 4, interval domains
+    //   large block         k_expand<8, false, CS, false, false, W, KR>             blocks of 257..512 words; the four (CS, W), no interval kernels
+    //   long key            k_expand<4, false, CS, false, false, W, 2>              DR = 4, key of more than 64 words; the four (CS, W), intervals
+    //   wide domains        k_expand<DR, false, false, false, false, W>             W = 2, 4 or kWIntervals at DR = 1 / 2 / 4
+    //   prefix              k_expand<DR, 2, false, false>                           prefix_complete: a general program whose descriptors fit LDS
+    //   (L, CS, LITE)       k_expand<DR, L, CS, LITE>                               everything else at DR = 1 / 2 / 4: L = whole image in LDS,
+    //                                                                               LITE = no general wavefront revision; refined to
+    //     big workgroup     k_expand<DR, true, CS, true, true>                      ... `big`: STCSP_BIG_WAVES wavefronts around one LDS copy
+    //     one-register      k_expand<1, true, false, true, false, 1, 1, true>       ... `shape1`
+    // k_probe: k_probe_big<DR, CS> under a big scope, else k_probe<DR, L, CS, LITE> (DR = 8: k_probe<8, false, CS, false>).
+    // k_commit: k_commit_until<DR, KR, kMaxExpireWords> with more than 32 until constraints, else k_commit<DR, KR>.
+    //
+    // Everything above the prefix row exists in the general, partly-staged form only (general_only()). Each capacity feature is
+    // a set of instantiations, or a kernel, of its own -- k_expand_until and k_expand_big are separate definitions because that is
+    // what keeps the shipped kernels' register allocation (dev_expand_kernel.inc) -- so the LITE / prefix / image-in-LDS kernels
+    // of the shipped programs (keys of at most 64 words, at most 32 until constraints, scopes of at most 64 variables) stay
+    // exactly as they are, and the build and the code object grow by the general form alone.
+    using ExpandFn = void (*)(const Ctx *, const Plan *, unsigned, uint32_t);
+    using ProbeFn = void (*)(const Ctx *, uint32_t *, int, int, uint32_t, int *);
+    using CommitFn = void (*)(Ctx, CommitArgs);
+    struct Kernels {
+        ExpandFn expand = nullptr;
+        ProbeFn probe = nullptr;
+        CommitFn commit = nullptr;
+        unsigned expand_threads = 256;  // workgroup size of `expand`
+    };
+    Kernels kernels;
+
+    // The instrumented build, -DSTCSP_PHASES, cannot be compiled for <4, image or prefix in LDS, general>: hipcc 7.2 stops with
+    // "Illegal instruction detected: V_CMP_NE_U32_e32 0, $src_shared_base" in those instantiations; there the same programs run
+    // the partly-staged kernels instead. The product build has them all up to DR = 4 (DR = 8 has none in either build).
+    static constexpr bool staged_general_exists(int dr) {
 #ifdef STCSP_PHASES
-#define STCSP_VARIANT(DRT, V) (((DRT) == 4 && ((V) & 5) == 4) ? ((V) & ~4) : (V))
+        return dr != 4;
 #else
-#define STCSP_VARIANT(DRT, V) (V)
+        return dr <= 4;
 #endif
-    template <int DRT, typename F>
-    void with_variant(F &&f) const {
-        const int v = (img_in_lds || big ? 4 : 0) | (compact_sweeps ? 2 : 0) | (lite ? 1 : 0);
-        switch (v) {
-            case 0: f(std::integral_constant<int, 0>{}); break;
-            case 1: f(std::integral_constant<int, 1>{}); break;
-            case 2: f(std::integral_constant<int, 2>{}); break;
-            case 3: f(std::integral_constant<int, 3>{}); break;
-            case 4: f(std::integral_constant<int, 4>{}); break;
-            case 5: f(std::integral_constant<int, 5>{}); break;
-            case 6: f(std::integral_constant<int, 6>{}); break;
-            default: f(std::integral_constant<int, 7>{}); break;
-        }
     }
-    // DR = 8 (blocks of 257..512 words) has the general, partly-staged kernels only: W = 1 (plain or compacted sweeps), 2 and 4,
-    // each with one or two key registers; no LITE, image-in-LDS, prefix or big-workgroup variants, no interval kernels
-    template <int KR>
-    const void *expand8_fn() const {
-        if (mgr.intervals) return nullptr;  // (create refuses interval blocks of more than 256 words)
-        if (mgr.W == 2) return (const void *)k_expand<8, false, false, false, false, 2, KR>;
-        if (mgr.W > 2) return (const void *)k_expand<8, false, false, false, false, 4, KR>;
-        if (compact_sweeps) return (const void *)k_expand<8, false, true, false, false, 1, KR>;
-        return (const void *)k_expand<8, false, false, false, false, 1, KR>;
-    }
-    template <int KR>
-    void launch_expand8() {
-        const Ctx *cp = (const Ctx *)d_ctx.p;
-        const Plan *pp = (const Plan *)d_plan.p;
-        if (mgr.W == 2)
-            hipLaunchKernelGGL((k_expand<8, false, false, false, false, 2, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-        else if (mgr.W > 2)
-            hipLaunchKernelGGL((k_expand<8, false, false, false, false, 4, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-        else if (compact_sweeps)
-            hipLaunchKernelGGL((k_expand<8, false, true, false, false, 1, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-        else
-            hipLaunchKernelGGL((k_expand<8, false, false, false, false, 1, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-    }
-    // more than 32 until constraints (DR = 4 or 8): W = 1 (plain or compacted sweeps), 2, 4 and, at DR = 4, interval domains
-    template <int DRT, int KR>
-    const void *until_fn() const {
-        constexpr int UW = kMaxExpireWords;
-        if (mgr.intervals) return DRT == 4 ? (const void *)k_expand_until<4, false, kWIntervals, KR, UW> : nullptr;
-        if (mgr.W == 2) return (const void *)k_expand_until<DRT, false, 2, KR, UW>;
-        if (mgr.W > 2) return (const void *)k_expand_until<DRT, false, 4, KR, UW>;
-        if (compact_sweeps) return (const void *)k_expand_until<DRT, true, 1, KR, UW>;
-        return (const void *)k_expand_until<DRT, false, 1, KR, UW>;
-    }
-    template <int DRT, int KR>
-    void launch_until() {
-        constexpr int UW = kMaxExpireWords;
-        const Ctx *cp = (const Ctx *)d_ctx.p;
-        const Plan *pp = (const Plan *)d_plan.p;
-        if (mgr.intervals) {
-            if constexpr (DRT == 4)
-                hipLaunchKernelGGL((k_expand_until<4, false, kWIntervals, KR, UW>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-        } else if (mgr.W == 2) {
-            hipLaunchKernelGGL((k_expand_until<DRT, false, 2, KR, UW>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-        } else if (mgr.W > 2) {
-            hipLaunchKernelGGL((k_expand_until<DRT, false, 4, KR, UW>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-        } else if (compact_sweeps) {
-            hipLaunchKernelGGL((k_expand_until<DRT, true, 1, KR, UW>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-        } else {
-            hipLaunchKernelGGL((k_expand_until<DRT, false, 1, KR, UW>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-        }
-    }
-    // a constraint over more than 64 variables (DR = 4 or 8): W = 1 (plain or compacted sweeps), 2 and 4
-    template <int DRT, int KR>
-    const void *big_fn() const {
-        if (mgr.W == 2) return (const void *)k_expand_big<DRT, false, 2, KR>;
-        if (mgr.W > 2) return (const void *)k_expand_big<DRT, false, 4, KR>;
-        if (compact_sweeps) return (const void *)k_expand_big<DRT, true, 1, KR>;
-        return (const void *)k_expand_big<DRT, false, 1, KR>;
-    }
-    template <int DRT, int KR>
-    void launch_big() {
-        const Ctx *cp = (const Ctx *)d_ctx.p;
-        const Plan *pp = (const Plan *)d_plan.p;
-        if (mgr.W == 2)
-            hipLaunchKernelGGL((k_expand_big<DRT, false, 2, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-        else if (mgr.W > 2)
-            hipLaunchKernelGGL((k_expand_big<DRT, false, 4, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-        else if (compact_sweeps)
-            hipLaunchKernelGGL((k_expand_big<DRT, true, 1, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-        else
-            hipLaunchKernelGGL((k_expand_big<DRT, false, 1, KR>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-    }
+    // the (L, CS, LITE) variant, as bits 4 / 2 / 1, that a block of DRT registers runs in place of variant v
     template <int DRT>
-    const void *expand_fn() const {
-        if constexpr (DRT >= 4)
-            if (big_scope()) return long_key() ? big_fn<DRT, 2>() : big_fn<DRT, 1>();
-        if constexpr (DRT >= 4)
-            if (many_until()) return long_key() ? until_fn<DRT, 2>() : until_fn<DRT, 1>();
-        if constexpr (DRT == 8) return long_key() ? expand8_fn<2>() : expand8_fn<1>();
-        else return expand_fn_le4<DRT>();
+    static constexpr int kept_variant(int v) {
+        if (DRT == 8) return v & 2;
+        return !staged_general_exists(DRT) && (v & 5) == 4 ? (v & ~4) : v;
     }
-    template <int DRT>
-    const void *expand_fn_le4() const {
-        const void *fn = nullptr;
-        if constexpr (DRT == 4)
-            if (long_key()) {
-                if (mgr.intervals) return (const void *)k_expand<4, false, false, false, false, kWIntervals, 2>;
-                if (mgr.W == 2) return (const void *)k_expand<4, false, false, false, false, 2, 2>;
-                if (mgr.W > 2) return (const void *)k_expand<4, false, false, false, false, 4, 2>;
-                if (compact_sweeps) return (const void *)k_expand<4, false, true, false, false, 1, 2>;
-                return (const void *)k_expand<4, false, false, false, false, 1, 2>;
-            }
-        if (mgr.intervals) return (const void *)k_expand<DRT, false, false, false, false, kWIntervals>;
-        if (mgr.W == 2) return (const void *)k_expand<DRT, false, false, false, false, 2>;
-        if (mgr.W > 2) return (const void *)k_expand<DRT, false, false, false, false, 4>;
-#ifdef STCSP_PHASES
-        if constexpr (DRT != 4)  // (see STCSP_VARIANT)
-#endif
-        if (prefix_complete) return (const void *)k_expand<DRT, 2, false, false>;
-        with_variant<DRT>([&](auto v) {
-            constexpr int V = STCSP_VARIANT(DRT, decltype(v)::value);
-            fn = (const void *)k_expand<DRT, (V & 4) != 0, (V & 2) != 0, (V & 1) != 0>;
-            if constexpr ((V & 5) == 5)
-                if (big) fn = (const void *)k_expand<DRT, true, (V & 2) != 0, true, true>;
-            if constexpr (DRT == 1 && V == 5)
-                if (shape1) fn = (const void *)k_expand<1, true, false, true, false, 1, 1, true>;
-        });
-        return fn;
-    }
-    template <int DRT>
-    const void *probe_fn() const {
-        if constexpr (DRT >= 4)
-            if (big_scope()) return compact_sweeps ? (const void *)k_probe_big<DRT, true> : (const void *)k_probe_big<DRT, false>;
-        if constexpr (DRT == 8) {
-            return compact_sweeps ? (const void *)k_probe<8, false, true, false> : (const void *)k_probe<8, false, false, false>;
-        } else {
-            const void *fn = nullptr;
-            with_variant<DRT>([&](auto v) {
-                constexpr int V = STCSP_VARIANT(DRT, decltype(v)::value);
-                fn = (const void *)k_probe<DRT, (V & 4) != 0, (V & 2) != 0, (V & 1) != 0>;
-            });
-            return fn;
-        }
-    }
-    template <int DRT>
-    void launch_expand() {
-        if constexpr (DRT >= 4)
-            if (big_scope()) {
-                if (long_key()) launch_big<DRT, 2>();
-                else launch_big<DRT, 1>();
-                return;
-            }
-        if constexpr (DRT >= 4)
-            if (many_until()) {
-                if (long_key()) launch_until<DRT, 2>();
-                else launch_until<DRT, 1>();
-                return;
-            }
-        if constexpr (DRT == 8) {
-            if (long_key()) launch_expand8<2>();
-            else launch_expand8<1>();
-        } else {
-            launch_expand_le4<DRT>();
-        }
-    }
-    template <int DRT>
-    void launch_expand_le4() {
-        const Ctx *cp = (const Ctx *)d_ctx.p;
-        if constexpr (DRT == 4)
-            if (long_key()) {
-                const Plan *pp = (const Plan *)d_plan.p;
-                if (mgr.intervals)
-                    hipLaunchKernelGGL((k_expand<4, false, false, false, false, kWIntervals, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-                else if (mgr.W == 2)
-                    hipLaunchKernelGGL((k_expand<4, false, false, false, false, 2, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-                else if (mgr.W > 2)
-                    hipLaunchKernelGGL((k_expand<4, false, false, false, false, 4, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-                else if (compact_sweeps)
-                    hipLaunchKernelGGL((k_expand<4, false, true, false, false, 1, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-                else
-                    hipLaunchKernelGGL((k_expand<4, false, false, false, false, 1, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, pp, launch_seq++, ctx.tab_gen);
-                return;
-            }
-        if (mgr.intervals) {
-            hipLaunchKernelGGL((k_expand<DRT, false, false, false, false, kWIntervals>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, (const Plan *)d_plan.p, launch_seq++, ctx.tab_gen);
-            return;
-        }
-        if (mgr.W == 2) {
-            hipLaunchKernelGGL((k_expand<DRT, false, false, false, false, 2>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, (const Plan *)d_plan.p, launch_seq++, ctx.tab_gen);
-            return;
-        }
-        if (mgr.W > 2) {
-            hipLaunchKernelGGL((k_expand<DRT, false, false, false, false, 4>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, (const Plan *)d_plan.p, launch_seq++, ctx.tab_gen);
-            return;
-        }
-#ifdef STCSP_PHASES
-        if constexpr (DRT != 4)
-#endif
-        if (prefix_complete) {
-            hipLaunchKernelGGL((k_expand<DRT, 2, false, false>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, (const Plan *)d_plan.p, launch_seq++, ctx.tab_gen);
-            return;
-        }
-        with_variant<DRT>([&](auto v) {
-            constexpr int V = STCSP_VARIANT(DRT, decltype(v)::value);
-            if constexpr ((V & 5) == 5)
+    template <int DRT, int V>
+    void select_variant(Kernels &k) const {
+        constexpr bool L = (V & 4) != 0, CS = (V & 2) != 0, LITE = (V & 1) != 0;
+        k.probe = k_probe<DRT, L, CS, LITE>;
+        if constexpr (DRT <= 4) {
+            k.expand = k_expand<DRT, L, CS, LITE>;
+            if constexpr (L && LITE)
                 if (big) {
-                    hipLaunchKernelGGL((k_expand<DRT, true, (V & 2) != 0, true, true>), dim3(max_blocks), dim3(STCSP_BIG_WAVES * 64), lds_bytes, stream, cp, (const Plan *)d_plan.p, launch_seq++, ctx.tab_gen);
-                    return;
+                    k.expand = k_expand<DRT, true, CS, true, true>;
+                    k.expand_threads = STCSP_BIG_WAVES * 64;
                 }
             if constexpr (DRT == 1 && V == 5)
-                if (shape1) {
-                    hipLaunchKernelGGL((k_expand<1, true, false, true, false, 1, 1, true>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, (const Plan *)d_plan.p, launch_seq++, ctx.tab_gen);
-                    return;
-                }
-            hipLaunchKernelGGL((k_expand<DRT, (V & 4) != 0, (V & 2) != 0, (V & 1) != 0>), dim3(max_blocks), dim3(256), lds_bytes, stream, cp, (const Plan *)d_plan.p, launch_seq++, ctx.tab_gen);
-        });
+                if (shape1) k.expand = k_expand<1, true, false, true, false, 1, 1, true>;
+        }
+    }
+    // one family's general, partly-staged kernels by domain form (nullptr: the family has no such kernel)
+    ExpandFn by_domain(ExpandFn plain, ExpandFn compact, ExpandFn w2, ExpandFn w4, ExpandFn intervals) const {
+        if (mgr.intervals) return intervals;
+        if (mgr.W == 2) return w2;
+        if (mgr.W > 2) return w4;
+        return compact_sweeps ? compact : plain;
+    }
+    template <int DRT, int KR>
+    ExpandFn expand_general() const {
+        ExpandFn iv = nullptr;  // (create refuses interval blocks of more than 256 words)
+        if constexpr (DRT <= 4) iv = k_expand<DRT, false, false, false, false, kWIntervals, KR>;
+        return by_domain(k_expand<DRT, false, false, false, false, 1, KR>, k_expand<DRT, false, true, false, false, 1, KR>,
+                         k_expand<DRT, false, false, false, false, 2, KR>, k_expand<DRT, false, false, false, false, 4, KR>, iv);
+    }
+    template <int DRT, int KR>
+    ExpandFn expand_keyed() const {  // the families with one or two key registers (DRT >= 4)
+        constexpr int UW = kMaxExpireWords;
+        if (big_scope())  // (create refuses interval domains beside a big scope)
+            return by_domain(k_expand_big<DRT, false, 1, KR>, k_expand_big<DRT, true, 1, KR>, k_expand_big<DRT, false, 2, KR>, k_expand_big<DRT, false, 4, KR>, nullptr);
+        if (many_until()) {
+            ExpandFn iv = nullptr;
+            if constexpr (DRT == 4) iv = k_expand_until<4, false, kWIntervals, KR, UW>;
+            return by_domain(k_expand_until<DRT, false, 1, KR, UW>, k_expand_until<DRT, true, 1, KR, UW>, k_expand_until<DRT, false, 2, KR, UW>,
+                             k_expand_until<DRT, false, 4, KR, UW>, iv);
+        }
+        return expand_general<DRT, KR>();
+    }
+    // the families that come before the (L, CS, LITE) variant. false: none applies
+    template <int DRT>
+    bool select_family(ExpandFn &fn) const {
+        if constexpr (DRT >= 4)
+            if (big_scope() || many_until() || DRT == 8 || long_key()) {
+                fn = long_key() ? expand_keyed<DRT, 2>() : expand_keyed<DRT, 1>();
+                return true;
+            }
+        if (mgr.W > 1) {
+            fn = expand_general<DRT, 1>();  // (its two W = 1 kernels are variants 0 and 2 below)
+            return true;
+        }
+        if constexpr (staged_general_exists(DRT))
+            if (prefix_complete) {
+                fn = k_expand<DRT, 2, false, false>;
+                return true;
+            }
+        return false;
+    }
+    template <int DRT>
+    CommitFn select_commit() const {
+        if constexpr (DRT >= 4) {
+            if (many_until()) return long_key() ? k_commit_until<DRT, 2, kMaxExpireWords> : k_commit_until<DRT, 1, kMaxExpireWords>;
+            if (long_key()) return k_commit<DRT, 2>;
+        }
+        return many_until() ? nullptr : k_commit<DRT, 1>;
+    }
+    template <int DRT>
+    Kernels select_for() const {
+        Kernels k;
+        const int v = kept_variant<DRT>((img_in_lds || big ? 4 : 0) | (compact_sweeps ? 2 : 0) | (lite ? 1 : 0));
+        switch (v) {
+            case 0: select_variant<DRT, kept_variant<DRT>(0)>(k); break;
+            case 1: select_variant<DRT, kept_variant<DRT>(1)>(k); break;
+            case 2: select_variant<DRT, kept_variant<DRT>(2)>(k); break;
+            case 3: select_variant<DRT, kept_variant<DRT>(3)>(k); break;
+            case 4: select_variant<DRT, kept_variant<DRT>(4)>(k); break;
+            case 5: select_variant<DRT, kept_variant<DRT>(5)>(k); break;
+            case 6: select_variant<DRT, kept_variant<DRT>(6)>(k); break;
+            default: select_variant<DRT, kept_variant<DRT>(7)>(k); break;
+        }
+        ExpandFn family = nullptr;
+        if (select_family<DRT>(family)) {
+            k.expand = family;
+            k.expand_threads = 256;
+        }
+        if constexpr (DRT >= 4)
+            if (big_scope()) k.probe = compact_sweeps ? k_probe_big<DRT, true> : k_probe_big<DRT, false>;
+        k.commit = select_commit<DRT>();
+        return k;
+    }
+    int select_kernels() {
+        Kernels k;
+        switch (DR) {
+            case 1: k = select_for<1>(); break;
+            case 2: k = select_for<2>(); break;
+            case 4: k = select_for<4>(); break;
+            case 8: k = select_for<8>(); break;
+        }
+        if (!k.expand || !k.probe || !k.commit)
+            return fail(STCSP_E_INTERNAL, "no %s kernel for a block of %d registers with W = %d, interval domains %d, a key of %d words, %d until constraints, big scope %d",
+                        !k.expand ? "expansion" : !k.probe ? "probe" : "commit", DR, mgr.W, (int)mgr.intervals, ctx.KL, ctx.n_until_cons, (int)big_scope());
+        kernels = k;
+        return STCSP_OK;
     }
 
     // The domains a fresh time point starts from, per constraint set (FlatProgram::set_fresh_init): the set's constraints applied
@@ -1467,13 +1382,7 @@ struct stcsp_engine {
             HIPCHK(d_blk.upload(blocks));
             HIPCHK(d_out.alloc((size_t)ns));
             const unsigned grid = (unsigned)std::min<int64_t>((ns + 3) / 4, max_blocks);
-            switch (DR) {
-                case 1: launch_probe<1>(grid, d_blk.p, ns, -1, 0xffffffffu, d_out.p); break;
-                case 2: launch_probe<2>(grid, d_blk.p, ns, -1, 0xffffffffu, d_out.p); break;
-                case 4: launch_probe<4>(grid, d_blk.p, ns, -1, 0xffffffffu, d_out.p); break;
-                case 8: launch_probe<8>(grid, d_blk.p, ns, -1, 0xffffffffu, d_out.p); break;
-                default: return fail(STCSP_E_INTERNAL, "no probe kernel for a block of %d registers", DR);
-            }
+            hipLaunchKernelGGL(kernels.probe, dim3(grid), dim3(256), lds_bytes, stream, (const Ctx *)d_ctx.p, d_blk.p, ns, -1, 0xffffffffu, d_out.p);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(blocks.data(), d_blk.p, blocks.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
             HIPCHK(hipMemcpyAsync(outcome.data(), d_out.p, (size_t)ns * sizeof(int), hipMemcpyDeviceToHost, stream));
@@ -1496,30 +1405,6 @@ struct stcsp_engine {
     }
 
     // stcsp_engine_propagate: process_node on caller-provided blocks (k_probe)
-    template <int DRT>
-    void launch_probe(unsigned grid, uint32_t *blocks, int n, int set, uint32_t expire, int *outcome) {
-        const Ctx *cp = (const Ctx *)d_ctx.p;
-        if constexpr (DRT >= 4)
-            if (big_scope()) {
-                if (compact_sweeps)
-                    hipLaunchKernelGGL((k_probe_big<DRT, true>), dim3(grid), dim3(256), lds_bytes, stream, cp, blocks, n, set, expire, outcome);
-                else
-                    hipLaunchKernelGGL((k_probe_big<DRT, false>), dim3(grid), dim3(256), lds_bytes, stream, cp, blocks, n, set, expire, outcome);
-                return;
-            }
-        if constexpr (DRT == 8) {
-            if (compact_sweeps)
-                hipLaunchKernelGGL((k_probe<8, false, true, false>), dim3(grid), dim3(256), lds_bytes, stream, cp, blocks, n, set, expire, outcome);
-            else
-                hipLaunchKernelGGL((k_probe<8, false, false, false>), dim3(grid), dim3(256), lds_bytes, stream, cp, blocks, n, set, expire, outcome);
-        } else {
-            with_variant<DRT>([&](auto v) {
-                constexpr int V = STCSP_VARIANT(DRT, decltype(v)::value);
-                hipLaunchKernelGGL((k_probe<DRT, (V & 4) != 0, (V & 2) != 0, (V & 1) != 0>), dim3(grid), dim3(256), lds_bytes, stream, cp, blocks, n, set,
-                                   expire, outcome);
-            });
-        }
-    }
     int propagate(int set, uint32_t expire, uint32_t *blocks, int64_t count, int32_t *outcome, int64_t *skipped) {
         if (sharded) return fail(STCSP_E_STATE, "propagate is for unsharded engines");
         if (mgr.intervals) return fail(STCSP_E_UNSUPPORTED, "propagate: the node-level seam takes one-word blocks (no interval domains)");
@@ -1546,13 +1431,7 @@ struct stcsp_engine {
         HIPCHK(hipMemsetAsync(d_ctl.p + L.misc0 + MISC_ERROR * CST, 0, sizeof(uint32_t), stream));
         HIPCHK(hipMemsetAsync(d_ctl.p + L.misc0 + MISC_NMISS * CST, 0, sizeof(uint32_t), stream));
         const unsigned grid = (unsigned)std::min<int64_t>((count + 3) / 4, max_blocks);
-        switch (DR) {
-            case 1: launch_probe<1>(grid, d_blk.p, (int)count, set, expire, d_out.p); break;
-            case 2: launch_probe<2>(grid, d_blk.p, (int)count, set, expire, d_out.p); break;
-            case 4: launch_probe<4>(grid, d_blk.p, (int)count, set, expire, d_out.p); break;
-            case 8: launch_probe<8>(grid, d_blk.p, (int)count, set, expire, d_out.p); break;
-            default: return fail(STCSP_E_INTERNAL, "no probe kernel for a block of %d registers", DR);
-        }
+        hipLaunchKernelGGL(kernels.probe, dim3(grid), dim3(256), lds_bytes, stream, (const Ctx *)d_ctx.p, d_blk.p, (int)count, set, expire, d_out.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(blocks, d_blk.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipMemcpyAsync(outcome, d_out.p, (size_t)count * sizeof(int), hipMemcpyDeviceToHost, stream));
@@ -1772,13 +1651,8 @@ struct stcsp_engine {
             tail_fresh = false;
             ctl_fresh = false;
             for (int k = 0; k < burst; k++) {
-                switch (DR) {
-                    case 1: launch_expand<1>(); break;
-                    case 2: launch_expand<2>(); break;
-                    case 4: launch_expand<4>(); break;
-                    case 8: launch_expand<8>(); break;
-                    default: return fail(STCSP_E_INTERNAL, "no expansion kernel for a block of %d registers", DR);
-                }
+                hipLaunchKernelGGL(kernels.expand, dim3(max_blocks), dim3(kernels.expand_threads), lds_bytes, stream, (const Ctx *)d_ctx.p, (const Plan *)d_plan.p,
+                                   launch_seq++, ctx.tab_gen);
                 HIPCHK(hipGetLastError());
                 expand_launches++;
             }
@@ -2088,28 +1962,7 @@ struct stcsp_engine {
         CommitArgs ca{};
         ca.cand_base = (const uint32_t *)records;
         ca.total = count;
-        {
-            dim3 grid((unsigned)((count + 3) / 4)), block(256);
-            constexpr int UW = kMaxExpireWords;
-            if (many_until() && DR != 4 && DR != 8) return fail(STCSP_E_INTERNAL, "no commit kernel for %d until constraints at DR = %d", ctx.n_until_cons, DR);
-            switch (DR) {
-                case 1: hipLaunchKernelGGL((k_commit<1>), grid, block, 0, stream, ctx, ca); break;
-                case 2: hipLaunchKernelGGL((k_commit<2>), grid, block, 0, stream, ctx, ca); break;
-                case 4:
-                    if (many_until() && long_key()) hipLaunchKernelGGL((k_commit_until<4, 2, UW>), grid, block, 0, stream, ctx, ca);
-                    else if (many_until()) hipLaunchKernelGGL((k_commit_until<4, 1, UW>), grid, block, 0, stream, ctx, ca);
-                    else if (long_key()) hipLaunchKernelGGL((k_commit<4, 2>), grid, block, 0, stream, ctx, ca);
-                    else hipLaunchKernelGGL((k_commit<4>), grid, block, 0, stream, ctx, ca);
-                    break;
-                case 8:
-                    if (many_until() && long_key()) hipLaunchKernelGGL((k_commit_until<8, 2, UW>), grid, block, 0, stream, ctx, ca);
-                    else if (many_until()) hipLaunchKernelGGL((k_commit_until<8, 1, UW>), grid, block, 0, stream, ctx, ca);
-                    else if (long_key()) hipLaunchKernelGGL((k_commit<8, 2>), grid, block, 0, stream, ctx, ca);
-                    else hipLaunchKernelGGL((k_commit<8, 1>), grid, block, 0, stream, ctx, ca);
-                    break;
-                default: return fail(STCSP_E_INTERNAL, "no commit kernel for a block of %d registers", DR);
-            }
-        }
+        hipLaunchKernelGGL(kernels.commit, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, stream, ctx, ca);
         hipLaunchKernelGGL(k_close_segment, dim3(1), dim3(64), 0, stream, ctx);
         HIPCHK(hipGetLastError());
         // not waited for: the next expand_local() (or finish()) synchronises and reads the cursors,
