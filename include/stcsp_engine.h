@@ -259,6 +259,72 @@ typedef struct stcsp_quotient_result {
 
 int stcsp_engine_quotient(stcsp_engine *engine, const stcsp_quotient_options *options, stcsp_quotient_result *out);
 
+/* ---- checking observed streams against the live automaton on the device (no reference counterpart) ----------
+ * Live automaton, projected label and default mask as in stcsp_engine_quotient(). A stream is a sequence of `len`
+ * steps, each one int32 per observable variable in variable order. With S_0 = {root} (empty without a live root) and
+ * S_{t+1} = the live states reached from a state of S_t over a live edge whose projected label equals step t, the
+ * answer for a stream is
+ *   accepted_len  the largest L <= len with S_L not empty: len exactly when the stream is a prefix of a solution stream
+ *                 under the mask (every live state is valid), else the index of the first violating step;
+ *   n_end         |S_accepted_len|: 1 for every stream when every variable is observable (the automaton is then
+ *                 deterministic), 0 only without a live root;
+ *   end_final     1 if some state of S_accepted_len has `final` set.
+ * All three are independent of the state numbering and of the GPU's scheduling. A step with a value no edge carries is
+ * an ordinary rejection. Both calls are valid where stcsp_engine_quotient() is (STCSP_E_STATE before postprocess() and
+ * after a truncated solve, STCSP_E_UNSUPPORTED on sharded engines: stcsp_automaton_check_streams() of stcsp_host.h
+ * takes the merged automaton).
+ *
+ * monitor_build() builds the look-up structures for one mask in HBM: exact ids of the projected labels, and a hash
+ * multimap (state, label id) -> destinations. They stay valid until the next solve(), export(), postprocess() or
+ * monitor_build() on the engine. monitor_check() walks the streams: one lane per stream while no (state, label) pair
+ * has two destinations, else one wavefront per stream with the state sets in LDS. A stream whose set outgrows
+ * set_capacity is finished by the host twin, never answered approximately: the result is always exact, and
+ * n_host_fallback says how many streams took that road. */
+typedef struct stcsp_monitor_options {
+    const uint8_t *observable; /* [n_vars] nonzero = observable; NULL = the default mask of stcsp_engine_quotient() */
+    int32_t reserved[2];
+} stcsp_monitor_options;
+
+typedef struct stcsp_monitor_info {
+    int64_t n_states;         /* live states                                                              */
+    int64_t n_edges;          /* live edges (entered in the multimap)                                     */
+    int64_t n_labels;         /* distinct projected labels                                                */
+    int64_t n_pairs;          /* distinct (state, label id) pairs                                         */
+    int64_t table_bytes;      /* HBM the look-up structures hold                                          */
+    int32_t n_observable;     /* values per step                                                          */
+    int32_t max_destinations; /* most distinct destinations of one pair: 1 = deterministic under this mask
+                                 (0 without a live edge)                                                  */
+    int32_t set_capacity;     /* states a stream's set may hold in the state-set kernel                   */
+    int32_t root_live;
+    double seconds;           /* wall time from the flags in HBM to the finished structures               */
+} stcsp_monitor_info;
+
+#define STCSP_MON_FORCE_SETS 1 /* (tests, measurements) run the state-set kernel under a deterministic mask too */
+
+typedef struct stcsp_monitor_streams {
+    int64_t n_streams;
+    const int64_t *offsets; /* [n_streams + 1] in steps: offsets[0] == 0, not decreasing, every stream < 2^31 steps */
+    const int32_t *values;  /* [offsets[n_streams] * n_observable]                                                  */
+    int32_t flags;          /* STCSP_MON_*                                                                          */
+    int32_t reserved;
+} stcsp_monitor_streams;
+
+typedef struct stcsp_monitor_result {
+    int64_t n_streams;
+    const int32_t *accepted_len; /* [n_streams] owned by the engine, valid until the next call on it   */
+    const int32_t *n_end;        /* [n_streams]                                                        */
+    const uint8_t *end_final;    /* [n_streams]                                                        */
+    int64_t n_host_fallback;     /* streams finished by the host twin                                  */
+    int32_t walk_kernel;         /* 0 none ran, 1 the deterministic walk, 2 the state-set walk         */
+    int32_t reserved;
+    double seconds;              /* wall time from the host input to the host output                   */
+    double seconds_labels;       /* HIP-event time of the step -> label id kernel                      */
+    double seconds_walk;         /* HIP-event time of the walk kernel                                  */
+} stcsp_monitor_result;
+
+int stcsp_engine_monitor_build(stcsp_engine *engine, const stcsp_monitor_options *options, stcsp_monitor_info *info);
+int stcsp_engine_monitor_check(stcsp_engine *engine, const stcsp_monitor_streams *streams, stcsp_monitor_result *result);
+
 void stcsp_engine_destroy(stcsp_engine *engine);
 
 /* Message of the last error on this engine (or of the last failed create when engine==NULL). */

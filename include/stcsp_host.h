@@ -110,6 +110,20 @@ int stcsp_automaton_set_observable(stcsp_automaton *a, const uint8_t *observable
  * order_by_label work on the result; free it with stcsp_automaton_free(). */
 int stcsp_automaton_quotient(const stcsp_automaton *a, const int32_t *state_class, int64_t n_classes, stcsp_automaton **out);
 
+/* ---- checking observed streams (definition: stcsp_engine.h, stcsp_engine_monitor_check) ----
+ * The same contract written plainly with ordered containers, on the automaton's current flags: the checker of the
+ * device pass in the tests, the road of the streams whose state set outgrows the device kernel's capacity, and the
+ * path for automata whose flags live on the host (sharded runs, host adversarial passes, read_binary).
+ * observable: as in stcsp_automaton_bisimulation(). offsets: [n_streams + 1] in steps, offsets[0] == 0, not
+ * decreasing; values: [offsets[n_streams] * (number of observable variables)]. accepted_len / n_end: [n_streams]
+ * int32, end_final: [n_streams] uint8. max_set_size (may be NULL) receives the largest |S_t| met over all streams.
+ * STCSP_E_INVALID on malformed offsets. */
+int stcsp_automaton_check_streams(const stcsp_automaton *a, const uint8_t *observable, int64_t n_streams, const int64_t *offsets,
+                                  const int32_t *values, int32_t *accepted_len, int32_t *n_end, uint8_t *end_final,
+                                  int64_t *max_set_size);
+/* Values per step under a mask: the number of observable variables (NULL = the default mask). */
+int stcsp_automaton_num_observable(const stcsp_automaton *a, const uint8_t *observable);
+
 /* Merge the per-shard results of a sharded run (global state ids, see stcsp_engine.h) into
  * one result with dense ids; runs the ok-fixpoint over the union. The merged result is owned
  * by the returned handle. */

@@ -92,6 +92,32 @@ class QuotientResult(C.Structure):
                 ("state_class", C.POINTER(C.c_int32)), ("rounds", C.c_int32), ("seconds", C.c_double)]
 
 
+class MonitorOptions(C.Structure):
+    _fields_ = [("observable", C.POINTER(C.c_uint8)), ("reserved", C.c_int32 * 2)]
+
+
+class MonitorInfo(C.Structure):
+    _fields_ = [("n_states", C.c_int64), ("n_edges", C.c_int64), ("n_labels", C.c_int64), ("n_pairs", C.c_int64),
+                ("table_bytes", C.c_int64), ("n_observable", C.c_int32), ("max_destinations", C.c_int32),
+                ("set_capacity", C.c_int32), ("root_live", C.c_int32), ("seconds", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class MonitorStreams(C.Structure):
+    _fields_ = [("n_streams", C.c_int64), ("offsets", C.POINTER(C.c_int64)), ("values", C.POINTER(C.c_int32)),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MonitorResult(C.Structure):
+    _fields_ = [("n_streams", C.c_int64), ("accepted_len", C.POINTER(C.c_int32)), ("n_end", C.POINTER(C.c_int32)),
+                ("end_final", C.POINTER(C.c_uint8)), ("n_host_fallback", C.c_int64), ("walk_kernel", C.c_int32),
+                ("reserved", C.c_int32), ("seconds", C.c_double), ("seconds_labels", C.c_double), ("seconds_walk", C.c_double)]
+
+
+MON_FORCE_SETS = 1  # check_streams(force_sets=True): the state-set kernel under a deterministic mask too (tests, measurements)
+
 F_KEEP_RAW_EDGES = 1
 F_NO_EXPORT = 2
 F_PROFILE = 4
@@ -106,6 +132,7 @@ ENGINE_SYMBOLS = [
     "stcsp_engine_counters", "stcsp_engine_sets_blob", "stcsp_engine_sets_import", "stcsp_engine_postprocess",
     "stcsp_engine_propagate", "stcsp_engine_set_expand_budget", "stcsp_engine_node_bytes", "stcsp_engine_donate",
     "stcsp_engine_adopt", "stcsp_engine_expand_variant", "stcsp_engine_quotient",
+    "stcsp_engine_monitor_build", "stcsp_engine_monitor_check",
 ]
 # include/stcsp_sharded.h: the superstep loop + in-process transport (libstcsp_hip.so), the RCCL transport (libstcsp_rccl.so)
 SHARDED_SYMBOLS_HIP = ["stcsp_engine_solve_sharded", "stcsp_local_group_create", "stcsp_local_group_transport", "stcsp_local_group_destroy"]
@@ -120,6 +147,7 @@ HOST_SYMBOLS = [
     "stcsp_automaton_num_live_states", "stcsp_automaton_num_live_edges",
     "stcsp_merge_shards", "stcsp_merged_result", "stcsp_merged_free", "stcsp_host_free",
     "stcsp_automaton_bisimulation", "stcsp_automaton_set_observable", "stcsp_automaton_quotient",
+    "stcsp_automaton_check_streams", "stcsp_automaton_num_observable",
 ]
 
 
@@ -191,6 +219,9 @@ def host_lib() -> C.CDLL:
         lib.stcsp_automaton_bisimulation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         lib.stcsp_automaton_set_observable.argtypes = [C.c_void_p, C.c_void_p]
         lib.stcsp_automaton_quotient.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+        lib.stcsp_automaton_check_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        lib.stcsp_automaton_num_observable.argtypes = [C.c_void_p, C.c_void_p]
         lib.stcsp_merge_shards.argtypes = [C.POINTER(C.POINTER(Result)), C.c_int, C.POINTER(C.c_void_p)]
         lib.stcsp_merged_result.argtypes = [C.c_void_p]
         lib.stcsp_merged_result.restype = C.POINTER(Result)
@@ -236,6 +267,9 @@ def bind_engine_api(lib: C.CDLL, prefix: str = "stcsp_engine") -> None:
         g("postprocess").argtypes = [C.c_void_p, C.POINTER(PostOptions), C.POINTER(PostResult)]
     if hasattr(lib, f"{prefix}_quotient"):
         g("quotient").argtypes = [C.c_void_p, C.POINTER(QuotientOptions), C.POINTER(QuotientResult)]
+    if hasattr(lib, f"{prefix}_monitor_build"):
+        g("monitor_build").argtypes = [C.c_void_p, C.POINTER(MonitorOptions), C.POINTER(MonitorInfo)]
+        g("monitor_check").argtypes = [C.c_void_p, C.POINTER(MonitorStreams), C.POINTER(MonitorResult)]
     if hasattr(lib, f"{prefix}_propagate"):
         g("propagate").argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64)]
@@ -309,6 +343,32 @@ class Model:
             self.close()
         except Exception:
             pass
+
+
+def pack_streams(streams, n_obs: int):
+    """A list of 2-D int arrays ([len, n_obs] each; an empty stream may be any empty array), or a pair (values, offsets)
+    with offsets in steps -> (values int32 [total_steps * n_obs], offsets int64 [n_streams + 1]), both contiguous."""
+    import numpy as np
+    if isinstance(streams, tuple) and len(streams) == 2:
+        values = np.ascontiguousarray(streams[0], dtype=np.int32).reshape(-1)
+        offsets = np.ascontiguousarray(streams[1], dtype=np.int64).reshape(-1)
+        if offsets.size == 0:
+            raise ValueError("offsets must have n_streams + 1 entries")
+        if values.size != max(int(offsets[-1]), 0) * n_obs and not (offsets[-1] < 0):
+            raise ValueError(f"values must hold offsets[-1] * {n_obs} entries")
+        return values, offsets
+    rows = []
+    offsets = np.zeros(len(streams) + 1, dtype=np.int64)
+    for i, s in enumerate(streams):
+        a = np.asarray(s, dtype=np.int32)
+        if a.size == 0 and (a.ndim != 2 or a.shape[1] != n_obs):
+            a = a.reshape(0, n_obs)
+        if a.ndim != 2 or a.shape[1] != n_obs:
+            raise ValueError(f"stream {i}: expected rows of {n_obs} observable values")
+        rows.append(a)
+        offsets[i + 1] = offsets[i] + a.shape[0]
+    values = np.concatenate(rows, axis=0).reshape(-1) if rows else np.zeros(0, dtype=np.int32)
+    return np.ascontiguousarray(values, dtype=np.int32), offsets
 
 
 # ------------------------------------------------------------------ automaton (post-processing)
@@ -421,6 +481,26 @@ class Automaton:
         q = Automaton.__new__(Automaton)
         q._h, q._model, q._n_edges = h, self._model, 0
         return q
+
+    def check_streams(self, streams, observable=None):
+        """Check observed streams against the live automaton by the host twin of Engine.check_streams() (contract:
+        include/stcsp_engine.h, stcsp_engine_monitor_check), on the automaton's current flags. `streams` as in
+        pack_streams(); `observable` as in bisimulation(). Returns (accepted_len int32, n_end int32, end_final uint8,
+        max_set_size): one entry per stream, and the largest state set met."""
+        import numpy as np
+        lib = host_lib()
+        m = self._mask(observable)
+        n_obs = lib.stcsp_automaton_num_observable(self._h, m.ctypes.data if m is not None else None)
+        values, offsets = pack_streams(streams, n_obs)
+        n = len(offsets) - 1
+        acc, nend, fin = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
+        largest = C.c_int64()
+        rc = lib.stcsp_automaton_check_streams(self._h, m.ctypes.data if m is not None else None, n, offsets.ctypes.data,
+                                               values.ctypes.data if values.size else None, acc.ctypes.data, nend.ctypes.data,
+                                               fin.ctypes.data, C.byref(largest))
+        if rc != 0:
+            raise StcspError(rc, "check_streams failed: malformed offsets")
+        return acc[:n], nend[:n], fin[:n], largest.value
 
     def canonical(self) -> str:
         lib = host_lib()
@@ -597,6 +677,42 @@ class EngineBase:
         self.quotient_result = out
         cls = np.ctypeslib.as_array(out.state_class, shape=(max(self.result.n_states, 1),))[:self.result.n_states].copy()
         return cls, out.n_classes, out.rounds, out.seconds
+
+    def monitor(self, observable=None) -> MonitorInfo:
+        """Build the stream monitor's look-up structures on the device for one mask, after postprocess() (`observable`
+        as in quotient()). They stay valid until the next solve / postprocess / monitor. Returns the MonitorInfo."""
+        import numpy as np
+        nv = self._model.n_vars
+        mo = MonitorOptions()
+        if observable is not None:
+            m = np.ones(nv, dtype=np.uint8) if isinstance(observable, str) and observable == "all" else np.ascontiguousarray(observable, dtype=np.uint8)
+            if m.shape != (nv,):
+                raise ValueError(f"observable must have one flag per variable ({nv})")
+            mo.observable = m.ctypes.data_as(C.POINTER(C.c_uint8))
+        info = MonitorInfo()
+        self._check(self._f("monitor_build")(self._h, C.byref(mo), C.byref(info)))
+        self.monitor_info = info
+        return info
+
+    def check_streams(self, streams, force_sets: bool = False):
+        """Check observed streams against the live automaton on the device, after monitor(). `streams`: a list of 2-D
+        int arrays, one row of the observable variables' values per step, or (values, offsets) as in pack_streams().
+        Returns (accepted_len int32, n_end int32, end_final uint8, n_host_fallback); the whole MonitorResult of the
+        call is kept in self.monitor_result. Always exact: see include/stcsp_engine.h."""
+        import numpy as np
+        if getattr(self, "monitor_info", None) is None:
+            raise StcspError(-6, "check_streams() needs monitor() first")
+        values, offsets = pack_streams(streams, self.monitor_info.n_observable)
+        n = len(offsets) - 1
+        ms = MonitorStreams(n, offsets.ctypes.data_as(C.POINTER(C.c_int64)),
+                            values.ctypes.data_as(C.POINTER(C.c_int32)) if values.size else None, MON_FORCE_SETS if force_sets else 0, 0)
+        out = MonitorResult()
+        self._check(self._f("monitor_check")(self._h, C.byref(ms), C.byref(out)))
+        self.monitor_result = out
+        if n == 0:
+            return np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint8), 0
+        return (np.ctypeslib.as_array(out.accepted_len, shape=(n,)).copy(), np.ctypeslib.as_array(out.n_end, shape=(n,)).copy(),
+                np.ctypeslib.as_array(out.end_final, shape=(n,)).copy(), out.n_host_fallback)
 
     def automaton(self, result: Result | None = None) -> Automaton:
         return Automaton(self._model, result if result is not None else self.result)

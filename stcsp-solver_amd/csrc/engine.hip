@@ -55,6 +55,8 @@ using namespace stcsp;
 #include "dev_kernels.hpp"
 #include "dev_postproc.hpp"
 #include "dev_quotient.hpp"
+#include "dev_monitor.hpp"
+#include "monitor_host.hpp"
 
 using namespace stcsp::dev;
 
@@ -203,6 +205,20 @@ struct stcsp_engine {
     DevBuf<unsigned long long> d_qacc[2];
     std::vector<int32_t> q_class;
     std::vector<uint32_t> q_raw, q_cnt;
+    // stream monitor (dev_monitor.hpp): the look-up structures of the last monitor_build(), valid while mon_built
+    bool mon_built = false, mon_root_live = false, mon_host_built = false;
+    int mon_n_obs = 0, mon_max_dst = 0;
+    uint32_t mon_mask = 0;
+    std::vector<uint8_t> mon_observable, mon_live;
+    stcsp::HostMonitor mon_host;  // built when the first stream falls back to the host twin
+    DevBuf<uint8_t> d_mlive, d_mfin;
+    DevBuf<int32_t> d_mobs, d_mrows, d_macc, d_mnend;
+    DevBuf<uint32_t> d_mltab, d_mhead, d_mdst0, d_mdst, d_mnext, d_mctl, d_mlid;
+    DevBuf<unsigned long long> d_mkeys;
+    DevBuf<long long> d_moff;
+    hipEvent_t ev_m[3] = {nullptr, nullptr, nullptr};
+    std::vector<int32_t> m_acc, m_nend;
+    std::vector<uint8_t> m_fin;
 
     ~stcsp_engine() {
         // the device writes several of the pinned buffers freed below (progress mirror, streamed result arrays) from
@@ -236,6 +252,8 @@ struct stcsp_engine {
         for (int i = 0; i < 2; i++)
             if (ev_c[i]) (void)hipEventDestroy(ev_c[i]);
         if (ev_k) (void)hipEventDestroy(ev_k);
+        for (int i = 0; i < 3; i++)
+            if (ev_m[i]) (void)hipEventDestroy(ev_m[i]);
         if (stream) (void)hipStreamDestroy(stream);
     }
 
@@ -1075,6 +1093,7 @@ struct stcsp_engine {
         finished = false;
         exp_on_device = false;
         post_done = false;
+        mon_built = false;
         ev_used = 0;
         seconds_expand_kernel = 0;
         expand_launches = 0;
@@ -2052,6 +2071,7 @@ struct stcsp_engine {
             return fail(STCSP_E_INVALID, "postprocess: variable index out of range");
         auto t0 = std::chrono::steady_clock::now();
         post_done = false;
+        mon_built = false;
         const size_t E = exp_edges;
         const uint32_t S = n_states;
         auto width = [&](int v) { return (long long)mgr.ub[v] - (long long)mgr.lb[v] + 1; };
@@ -2307,6 +2327,190 @@ struct stcsp_engine {
         return STCSP_OK;
     }
 
+    // Stream monitor, build (dev_monitor.hpp): label ids and the (state, label id) -> destinations
+    // multimap of the live automaton under one mask, from the flags the last postprocess() left in HBM.
+    int monitor_build(const stcsp_monitor_options *mo, stcsp_monitor_info *info) {
+        if (sharded) return fail(STCSP_E_UNSUPPORTED, "the device monitor is for unsharded engines (stcsp_automaton_check_streams on the merged automaton)");
+        if (!exp_on_device || !post_done) return fail(STCSP_E_STATE, "monitor_build needs the flags of postprocess() on the last solve");
+        if (truncated) return fail(STCSP_E_STATE, "monitor_build after a truncated solve: the open states of a partial automaton have no known language");
+        auto t0 = std::chrono::steady_clock::now();
+        mon_built = mon_host_built = false;
+        const int N = ctx.N;
+        const uint32_t E = (uint32_t)exp_edges, S = n_states;
+        const uint8_t *mask = mo && mo->observable ? mo->observable : default_observable.data();
+        mon_observable.assign((size_t)N, 0);
+        std::vector<int32_t> obs;
+        for (int v = 0; v < N; v++)
+            if (mask[v]) {
+                obs.push_back(v);
+                mon_observable[(size_t)v] = 1;
+            }
+        size_t cap = 1024;
+        while (cap < 2 * (size_t)E) cap <<= 1;
+        if (cap > 0x80000000ull) return fail(STCSP_E_NOMEM, "edge list too large for the device monitor");
+        if (d_mlive.n < S) HIPCHK(d_mlive.alloc((size_t)S + S / 4 + 256));
+        if (d_mdst.n < (size_t)E + 1) {
+            const size_t c = (size_t)E + E / 4 + 256;
+            HIPCHK(d_mdst.alloc(c));
+            HIPCHK(d_mnext.alloc(c));
+        }
+        if (d_mltab.n < cap) {
+            HIPCHK(d_mltab.alloc(cap));
+            HIPCHK(d_mhead.alloc(cap));
+            HIPCHK(d_mdst0.alloc(cap));
+            HIPCHK(d_mkeys.alloc(cap));
+        }
+        if (d_mobs.n < (size_t)N) HIPCHK(d_mobs.alloc((size_t)N));
+        if (!d_mctl.p) HIPCHK(d_mctl.alloc(M_WORDS));
+        const unsigned eb = (E + 255) / 256;
+        uint32_t ctl[M_WORDS] = {0};
+        if (!obs.empty()) HIPCHK(hipMemcpyAsync(d_mobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemsetAsync(d_mctl.p, 0, sizeof ctl, stream));
+        // the live automaton: forward reachability from a valid root, as the quotient does it
+        HIPCHK(hipMemsetAsync(d_mlive.p, 0, S, stream));
+        HIPCHK(hipMemcpyAsync(d_mlive.p, d_pvalid.p, 1, hipMemcpyDeviceToDevice, stream));
+        for (int sweeps = 0; E; sweeps++) {
+            HIPCHK(hipMemsetAsync(d_mctl.p + M_CHANGED, 0, sizeof(uint32_t), stream));
+            hipLaunchKernelGGL(k_q_reach, dim3(eb), dim3(256), 0, stream, E, (const long long *)d_osrc.p, (const long long *)d_odst.p,
+                               (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_mlive.p, d_mctl.p);
+            HIPCHK(hipMemcpyAsync(ctl, d_mctl.p, sizeof ctl, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            if (!ctl[M_CHANGED]) break;
+            if (sweeps > (int)S + 8) return fail(STCSP_E_INTERNAL, "monitor: reachability did not converge");
+        }
+        if (E) {
+            HIPCHK(hipMemsetAsync(d_mltab.p, 0xff, cap * sizeof(uint32_t), stream));
+            HIPCHK(hipMemsetAsync(d_mhead.p, 0xff, cap * sizeof(uint32_t), stream));
+            HIPCHK(hipMemsetAsync(d_mkeys.p, 0xff, cap * sizeof(unsigned long long), stream));
+            hipLaunchKernelGGL(k_m_build, dim3(eb), dim3(256), 0, stream, E, (const long long *)d_osrc.p, (const long long *)d_odst.p,
+                               (const int32_t *)d_oval.p, N, (const int32_t *)d_mobs.p, (int)obs.size(), (const uint8_t *)d_palive.p,
+                               (const uint8_t *)d_mlive.p, d_mltab.p, d_mkeys.p, d_mhead.p, (uint32_t)(cap - 1), d_mdst.p, d_mnext.p, d_mctl.p);
+            hipLaunchKernelGGL(k_m_finish, dim3((unsigned)(cap / 256)), dim3(256), 0, stream, (uint32_t)cap, (const unsigned long long *)d_mkeys.p,
+                               (const uint32_t *)d_mhead.p, d_mnext.p, (const uint32_t *)d_mdst.p, d_mdst0.p, d_mctl.p);
+            HIPCHK(hipGetLastError());
+        }
+        mon_live.resize(S);
+        HIPCHK(hipMemcpyAsync(mon_live.data(), d_mlive.p, S, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(ctl, d_mctl.p, sizeof ctl, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (ctl[M_ERROR]) return fail(STCSP_E_INTERNAL, "monitor: a device table overflowed");
+        int64_t n_live = 0;
+        for (uint32_t s = 0; s < S; s++) n_live += mon_live[s];
+        mon_root_live = S > 0 && mon_live[0];
+        mon_n_obs = (int)obs.size();
+        mon_max_dst = (int)std::max(ctl[M_MAXDST], ctl[M_PAIRS] ? 1u : 0u);
+        mon_mask = (uint32_t)(cap - 1);
+        mon_built = true;
+        memset(info, 0, sizeof *info);
+        info->n_states = n_live;
+        info->n_edges = ctl[M_EDGES];
+        info->n_labels = ctl[M_LABELS];
+        info->n_pairs = ctl[M_PAIRS];
+        info->table_bytes = (int64_t)(E ? cap * (3 * sizeof(uint32_t) + sizeof(unsigned long long)) + 2 * (size_t)E * sizeof(uint32_t) : 0) + S;
+        info->n_observable = mon_n_obs;
+        info->max_destinations = mon_max_dst;
+        info->set_capacity = kMonSetCap;
+        info->root_live = mon_root_live;
+        info->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return STCSP_OK;
+    }
+
+    // Stream monitor, check: every stream's accepted_len / n_end / end_final (contract: stcsp_engine.h). Exact always: the
+    // streams the state-set kernel marks as over its capacity are finished by the host twin (monitor_host.hpp).
+    int monitor_check(const stcsp_monitor_streams *ms, stcsp_monitor_result *out) {
+        if (sharded) return fail(STCSP_E_UNSUPPORTED, "the device monitor is for unsharded engines (stcsp_automaton_check_streams on the merged automaton)");
+        if (!exp_on_device || !post_done || truncated || !mon_built)
+            return fail(STCSP_E_STATE, "monitor_check needs monitor_build() after the last postprocess()");
+        if (!stcsp::monitor_offsets_ok(ms->n_streams, ms->offsets)) return fail(STCSP_E_INVALID, "monitor_check: malformed stream offsets");
+        auto t0 = std::chrono::steady_clock::now();
+        const size_t n = (size_t)ms->n_streams;
+        const size_t steps = n ? (size_t)ms->offsets[n] : 0;
+        if (steps && mon_n_obs && !ms->values) return fail(STCSP_E_INVALID, "monitor_check: no step values");
+        if (n >= 0x7fffffffull || steps >= 0x7fffffffull) return fail(STCSP_E_NOMEM, "monitor_check: too many streams or steps for one call");
+        m_acc.assign(n, 0);
+        m_nend.assign(n, 0);
+        m_fin.assign(n, 0);
+        memset(out, 0, sizeof *out);
+        out->n_streams = ms->n_streams;
+        out->accepted_len = m_acc.data();
+        out->n_end = m_nend.data();
+        out->end_final = m_fin.data();
+        if (n && mon_root_live) {
+            const bool sets = mon_max_dst > 1 || (ms->flags & STCSP_MON_FORCE_SETS);
+            const uint32_t E = (uint32_t)exp_edges;
+            if (d_moff.n < n + 1) {
+                const size_t c = n + n / 4 + 256;
+                HIPCHK(d_moff.alloc(c + 1));
+                HIPCHK(d_macc.alloc(c));
+                HIPCHK(d_mnend.alloc(c));
+                HIPCHK(d_mfin.alloc(c));
+            }
+            if (d_mlid.n < steps) HIPCHK(d_mlid.alloc(steps + steps / 4 + 256));
+            if (d_mrows.n < steps * mon_n_obs) HIPCHK(d_mrows.alloc(steps * mon_n_obs + steps * mon_n_obs / 4 + 256));
+            for (int i = 0; i < 3; i++)
+                if (!ev_m[i]) HIPCHK(hipEventCreate(&ev_m[i]));
+            HIPCHK(hipMemcpyAsync(d_moff.p, ms->offsets, (n + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
+            if (steps * mon_n_obs) HIPCHK(hipMemcpyAsync(d_mrows.p, ms->values, steps * mon_n_obs * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemsetAsync(d_mctl.p + M_OVERFLOW, 0, sizeof(uint32_t), stream));
+            HIPCHK(hipEventRecord(ev_m[0], stream));
+            if (steps) {
+                if (E)
+                    hipLaunchKernelGGL(k_m_steps, dim3((unsigned)((steps + 255) / 256)), dim3(256), 0, stream, (uint32_t)steps, (const int32_t *)d_mrows.p,
+                                       mon_n_obs, (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_mobs.p, (const uint32_t *)d_mltab.p, mon_mask,
+                                       d_mlid.p);
+                else  // no edge, no label: every step is a rejection
+                    HIPCHK(hipMemsetAsync(d_mlid.p, 0xff, steps * sizeof(uint32_t), stream));
+            }
+            HIPCHK(hipEventRecord(ev_m[1], stream));
+            if (sets)
+                hipLaunchKernelGGL(k_m_walk_sets, dim3((unsigned)n), dim3(64), 0, stream, (uint32_t)n, (const long long *)d_moff.p,
+                                   (const uint32_t *)d_mlid.p, (const unsigned long long *)d_mkeys.p, (const uint32_t *)d_mhead.p,
+                                   (const uint32_t *)d_mnext.p, (const uint32_t *)d_mdst.p, mon_mask, (const uint8_t *)d_pfinal.p, d_macc.p, d_mnend.p,
+                                   d_mfin.p, d_mctl.p);
+            else
+                hipLaunchKernelGGL(k_m_walk_det, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (uint32_t)n, (const long long *)d_moff.p,
+                                   (const uint32_t *)d_mlid.p, (const unsigned long long *)d_mkeys.p, (const uint32_t *)d_mdst0.p, mon_mask,
+                                   (const uint8_t *)d_pfinal.p, d_macc.p, d_mnend.p, d_mfin.p);
+            HIPCHK(hipEventRecord(ev_m[2], stream));
+            HIPCHK(hipGetLastError());
+            uint32_t over = 0;
+            HIPCHK(hipMemcpyAsync(m_acc.data(), d_macc.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(m_nend.data(), d_mnend.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(m_fin.data(), d_mfin.p, n, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(&over, d_mctl.p + M_OVERFLOW, sizeof over, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            float ms_l = 0, ms_w = 0;
+            HIPCHK(hipEventElapsedTime(&ms_l, ev_m[0], ev_m[1]));
+            HIPCHK(hipEventElapsedTime(&ms_w, ev_m[1], ev_m[2]));
+            out->seconds_labels = ms_l * 1e-3;
+            out->seconds_walk = ms_w * 1e-3;
+            out->walk_kernel = sets ? 2 : 1;
+            if (over) {
+                if (!mon_host_built) {
+                    stcsp::MonitorView v;
+                    v.n_vars = ctx.N;
+                    v.n_states = n_states;
+                    v.n_edges = (int64_t)exp_edges;
+                    v.src = (const int64_t *)h_osrc;
+                    v.dst = (const int64_t *)h_odst;
+                    v.values = h_oval;
+                    v.valid = p_valid.data();
+                    v.final_ = p_final.data();
+                    v.alive = p_alive.data();
+                    mon_host.build(v, mon_observable.data());
+                    mon_host_built = true;
+                }
+                for (size_t i = 0; i < n; i++)
+                    if (m_acc[i] < 0) {
+                        mon_host.check_one(ms->values + ms->offsets[i] * mon_n_obs, ms->offsets[i + 1] - ms->offsets[i], &m_acc[i], &m_nend[i], &m_fin[i]);
+                        out->n_host_fallback++;
+                    }
+            }
+        }
+        out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return STCSP_OK;
+    }
+
     // unsharded export: ok-fixpoint + compaction on the device, result arrays land in pinned memory
     int export_device(stcsp_result *res, stcsp_counters &ctr, size_t &E_out) {
         const int N = ctx.N;
@@ -2450,6 +2654,7 @@ struct stcsp_engine {
         exp_edges = live;
         exp_on_device = true;
         post_done = false;
+        mon_built = false;
         return STCSP_OK;
     }
 
@@ -2670,6 +2875,16 @@ int stcsp_engine_postprocess(stcsp_engine *e, const stcsp_post_options *options,
 int stcsp_engine_quotient(stcsp_engine *e, const stcsp_quotient_options *options, stcsp_quotient_result *out) {
     if (!e || !out) return STCSP_E_INVALID;
     return e->quotient(options, out);
+}
+
+int stcsp_engine_monitor_build(stcsp_engine *e, const stcsp_monitor_options *options, stcsp_monitor_info *info) {
+    if (!e || !info) return STCSP_E_INVALID;
+    return e->monitor_build(options, info);
+}
+
+int stcsp_engine_monitor_check(stcsp_engine *e, const stcsp_monitor_streams *streams, stcsp_monitor_result *result) {
+    if (!e || !streams || !result) return STCSP_E_INVALID;
+    return e->monitor_check(streams, result);
 }
 
 void stcsp_engine_destroy(stcsp_engine *e) { delete e; }

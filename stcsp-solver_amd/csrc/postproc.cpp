@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "monitor_host.hpp"
 #include "okfix.hpp"
 #include "stcsp_host.h"
 
@@ -1015,6 +1016,41 @@ int stcsp_automaton_bisimulation(stcsp_automaton *a, const uint8_t *observable, 
     } catch (const std::bad_alloc &) {
         return STCSP_E_NOMEM;
     }
+}
+int stcsp_automaton_check_streams(const stcsp_automaton *a, const uint8_t *observable, int64_t n_streams, const int64_t *offsets,
+                                  const int32_t *values, int32_t *accepted_len, int32_t *n_end, uint8_t *end_final,
+                                  int64_t *max_set_size) {
+    if (!a || !stcsp::monitor_offsets_ok(n_streams, offsets)) return STCSP_E_INVALID;
+    if (n_streams > 0 && (!accepted_len || !n_end || !end_final)) return STCSP_E_INVALID;
+    try {
+        const Automaton &g = a->a;
+        stcsp::MonitorView v;
+        v.n_vars = g.n_vars;
+        v.n_states = g.n_states;
+        v.n_edges = (int64_t)g.esrc.size();
+        v.src = g.esrc.data();
+        v.dst = g.edst.data();
+        v.values = g.eval.data();
+        v.valid = g.valid.data();
+        v.final_ = g.final_.data();
+        v.alive = g.ealive.data();
+        stcsp::HostMonitor mon;
+        mon.build(v, g.observable_mask(observable).data());
+        if (n_streams > 0 && offsets[n_streams] > 0 && mon.n_obs > 0 && !values) return STCSP_E_INVALID;
+        int64_t largest = mon.root_live ? 1 : 0;
+        for (int64_t i = 0; i < n_streams; i++)
+            largest = std::max(largest, mon.check_one(values + offsets[i] * mon.n_obs, offsets[i + 1] - offsets[i], &accepted_len[i], &n_end[i], &end_final[i]));
+        if (max_set_size) *max_set_size = largest;
+    } catch (const std::bad_alloc &) {
+        return STCSP_E_NOMEM;
+    }
+    return STCSP_OK;
+}
+int stcsp_automaton_num_observable(const stcsp_automaton *a, const uint8_t *observable) {
+    if (!a) return STCSP_E_INVALID;
+    int n = 0;
+    for (uint8_t m : a->a.observable_mask(observable)) n += m;
+    return n;
 }
 int stcsp_automaton_set_observable(stcsp_automaton *a, const uint8_t *observable) {
     if (!a) return STCSP_E_INVALID;

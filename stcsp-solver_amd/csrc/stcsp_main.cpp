@@ -2,7 +2,7 @@
 // (src/stcsp.y:180-219 main, src/solver.cpp:195-359 solve): same flags, same stdout contract,
 // same solutions.dot. The search itself runs on the MI355X engine behind the C-ABI.
 //
-//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] input.csp
+//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--check=<file>] input.csp
 //
 // --binary=<file> (not in the reference) additionally writes the printed automaton in the compact
 // binary form of include/stcsp_host.h.
@@ -19,15 +19,27 @@
 // partition is computed on the device, or by the host twin where the flags live on the host (--shards=N, host adversarial passes).
 // When an -a / -z variable is wider than the device post-processing passes take, the host passes run instead.
 //
+// --check=<file> (not in the reference) checks observed streams against the automaton: which prefix of each stream is a prefix
+// of a solution (include/stcsp_engine.h, stcsp_engine_monitor_check). The file is text: its first line "# name name ..." names
+// the observable variables, one column each, and thereby sets the mask; then one step per line, and a blank line ends a stream
+// (two blank lines in a row give an empty stream). stdout then holds one line per stream and nothing else,
+//     index accepted_len len n_end end_final
+// and the reference's statistics line (and "adver1: ..." of -a / -z) goes to stderr. The streams are checked on the device, or
+// by the host twin where the flags live on the host (--shards=N, host adversarial passes); with -a / -z the flags are the ones
+// those passes left. Combined with --quotient the streams are checked against the automaton before it is folded.
+//
 // Options must be glued to their value (-k3, not -k 3): like the reference, the first argument
 // that does not start with '-' is the input file (stcsp.y:199-206).
 #include <sys/times.h>
 #include <unistd.h>
 
+#include <cctype>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -49,7 +61,114 @@ struct Flags {
     int prefix_k = 2, time_limit = 0, shards = 1;
     const char *file = nullptr;
     const char *binary = nullptr;
+    const char *check = nullptr;
 };
+
+// --check=<file>: the streams of the file, columns reordered to variable order
+struct Streams {
+    std::vector<uint8_t> mask;
+    std::vector<int64_t> offsets{0};
+    std::vector<int32_t> values;
+};
+
+static int read_streams(const char *path, const stcsp_problem *p, Streams &out) {
+    FILE *fp = fopen(path, "r");
+    if (!fp) {
+        fprintf(stderr, "cannot read %s\n", path);
+        return 1;
+    }
+    out.mask.assign((size_t)p->n_vars, 0);
+    std::vector<int> col_var, col_pos;  // variable of a column; position of a column in a row in variable order
+    std::string line;
+    bool header = false;
+    int64_t steps = 0, lineno = 0;
+    for (int c = 0; c != EOF;) {
+        line.clear();
+        while ((c = fgetc(fp)) != EOF && c != '\n') line.push_back((char)c);
+        if (c == EOF && line.empty()) break;
+        lineno++;
+        std::vector<std::string> tok;
+        for (size_t i = 0; i < line.size();) {
+            while (i < line.size() && isspace((unsigned char)line[i])) i++;
+            size_t j = i;
+            while (j < line.size() && !isspace((unsigned char)line[j])) j++;
+            if (j > i) tok.push_back(line.substr(i, j - i));
+            i = j;
+        }
+        if (!header) {
+            if (tok.empty() || tok[0] != "#") {
+                fprintf(stderr, "%s: the first line must be \"# name name ...\"\n", path);
+                fclose(fp);
+                return 1;
+            }
+            for (size_t k = 1; k < tok.size(); k++) {
+                int v = -1;
+                for (int i = 0; i < p->n_vars; i++)
+                    if (p->var_names && p->var_names[i] && tok[k] == p->var_names[i]) v = i;
+                if (v < 0 || out.mask[(size_t)v]) {
+                    fprintf(stderr, "%s: %s variable %s\n", path, v < 0 ? "unknown" : "repeated", tok[k].c_str());
+                    fclose(fp);
+                    return 1;
+                }
+                out.mask[(size_t)v] = 1;
+                col_var.push_back(v);
+            }
+            for (int v : col_var) {
+                int pos = 0;
+                for (int i = 0; i < v; i++) pos += out.mask[(size_t)i];
+                col_pos.push_back(pos);
+            }
+            header = true;
+            continue;
+        }
+        if (tok.empty()) {  // a blank line ends the stream
+            out.offsets.push_back(steps);
+            continue;
+        }
+        if (tok.size() != col_var.size()) {
+            fprintf(stderr, "%s:%lld: expected %zu values\n", path, (long long)lineno, col_var.size());
+            fclose(fp);
+            return 1;
+        }
+        const size_t base = out.values.size();
+        out.values.resize(base + col_var.size());
+        for (size_t k = 0; k < tok.size(); k++) {
+            char *end = nullptr;
+            const long long x = strtoll(tok[k].c_str(), &end, 10);
+            if (end == tok[k].c_str() || *end || x < INT32_MIN || x > INT32_MAX) {
+                fprintf(stderr, "%s:%lld: not an int32: %s\n", path, (long long)lineno, tok[k].c_str());
+                fclose(fp);
+                return 1;
+            }
+            out.values[base + (size_t)col_pos[k]] = (int32_t)x;
+        }
+        steps++;
+    }
+    fclose(fp);
+    if (!header) {
+        fprintf(stderr, "%s: the first line must be \"# name name ...\"\n", path);
+        return 1;
+    }
+    if (steps > out.offsets.back()) out.offsets.push_back(steps);
+    return 0;
+}
+
+static void print_streams(const Streams &st, const int32_t *acc, const int32_t *n_end, const uint8_t *fin) {
+    for (size_t i = 0; i + 1 < st.offsets.size(); i++)
+        printf("%zu %d %lld %d %d\n", i, acc[i], (long long)(st.offsets[i + 1] - st.offsets[i]), n_end[i], (int)fin[i]);
+    fflush(stdout);
+}
+
+// --check on the host twin: the automaton's current flags
+static int check_on_host(const Streams &st, const stcsp_automaton *a) {
+    const size_t n = st.offsets.size() - 1;
+    std::vector<int32_t> acc(n + 1), n_end(n + 1);
+    std::vector<uint8_t> fin(n + 1);
+    if (stcsp_automaton_check_streams(a, st.mask.data(), (int64_t)n, st.offsets.data(), st.values.data(), acc.data(), n_end.data(), fin.data(), nullptr) != STCSP_OK)
+        return 1;
+    print_streams(st, acc.data(), n_end.data(), fin.data());
+    return 0;
+}
 
 // --quotient: replace *a by its quotient under `state_class` (from the device pass), or under the host twin's partition when
 // state_class is NULL
@@ -89,6 +208,9 @@ static int run_once(const Flags &f, bool print_line, double *total) {
         return 1;
     }
     const stcsp_problem *p = stcsp_model_problem(model);
+    Streams streams;
+    if (f.check && read_streams(f.check, p, streams)) return 1;
+    FILE *info = f.check ? stderr : stdout;  // --check: stdout holds the answers only
     double init_time = cpu_time() - t_init;
     stcsp_options opt;
     memset(&opt, 0, sizeof opt);
@@ -120,8 +242,12 @@ static int run_once(const Flags &f, bool print_line, double *total) {
     rc = stcsp_engine_postprocess(eng, &po, &post);
     if (rc == STCSP_E_UNSUPPORTED) {  // an adversarial variable wider than the device passes take: the host passes
         stcsp_automaton_traverse(a);
-        if (f.adv1) printf("adver1: %d; ", stcsp_automaton_adversarial(a, 5));
-        if (f.adv2) printf("adver2: %d\n", stcsp_automaton_adversarial2(a, 5, 6));
+        if (f.adv1) fprintf(info, "adver1: %d; ", stcsp_automaton_adversarial(a, 5));
+        if (f.adv2) fprintf(info, "adver2: %d\n", stcsp_automaton_adversarial2(a, 5, 6));
+        if (f.check && check_on_host(streams, a)) {
+            fprintf(stderr, "the streams could not be checked\n");
+            return 1;
+        }
         if (f.quotient && fold(f, p, &a, nullptr, 0, 0)) {
             fprintf(stderr, "the quotient could not be built\n");
             return 1;
@@ -131,8 +257,19 @@ static int run_once(const Flags &f, bool print_line, double *total) {
         return 1;
     } else {
         stcsp_automaton_import_flags(a, post.state_valid, post.state_final, post.edge_alive);
-        if (f.adv1) printf("adver1: %d; ", post.adver1);
-        if (f.adv2) printf("adver2: %d\n", post.adver2);
+        if (f.adv1) fprintf(info, "adver1: %d; ", post.adver1);
+        if (f.adv2) fprintf(info, "adver2: %d\n", post.adver2);
+        if (f.check) {  // on the device, over the flags postprocess() has just left
+            stcsp_monitor_options mo = {streams.mask.data(), {0, 0}};
+            stcsp_monitor_info mi;
+            stcsp_monitor_streams ms = {(int64_t)streams.offsets.size() - 1, streams.offsets.data(), streams.values.data(), 0, 0};
+            stcsp_monitor_result mr;
+            if (stcsp_engine_monitor_build(eng, &mo, &mi) != STCSP_OK || stcsp_engine_monitor_check(eng, &ms, &mr) != STCSP_OK) {
+                fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
+                return 1;
+            }
+            print_streams(streams, mr.accepted_len, mr.n_end, mr.end_final);
+        }
         if (f.quotient) {
             std::vector<uint8_t> all((size_t)p->n_vars, 1);
             stcsp_quotient_options qo = {f.quotient_all ? all.data() : nullptr, {0, 0}};
@@ -154,9 +291,9 @@ static int run_once(const Flags &f, bool print_line, double *total) {
     if (f.binary && stcsp_automaton_write_binary(a, f.binary) != STCSP_OK) fprintf(stderr, "cannot write %s\n", f.binary);
     if (print_line) {
         // init_time, var, con, dom, node, fail, solve_time, processTime (solveralgorithm.cpp:1001)
-        printf("%.2f\t%d\t%d\t%d\t%d\t%d\t%.2f\t%.5f\n", init_time, p->n_vars, p->n_constraints, (int)res.counters.dominance,
+        fprintf(info, "%.2f\t%d\t%d\t%d\t%d\t%d\t%.2f\t%.5f\n", init_time, p->n_vars, p->n_constraints, (int)res.counters.dominance,
                (int)res.n_states, (int)res.counters.fails, solve_time, proc_time);
-        fflush(stdout);
+        fflush(info);
     }
     if (total) *total = solve_time + proc_time;
     stcsp_automaton_free(a);
@@ -178,6 +315,9 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
         return 1;
     }
     const stcsp_problem *p = stcsp_model_problem(model);
+    Streams streams;
+    if (f.check && read_streams(f.check, p, streams)) return 1;
+    FILE *info = f.check ? stderr : stdout;  // --check: stdout holds the answers only
     double init_time = cpu_time() - t_init;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
@@ -235,8 +375,12 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
     stcsp_automaton *a = nullptr;
     stcsp_automaton_build(p, merged, &a);
     stcsp_automaton_traverse(a);  // (host passes: the merged automaton lives on the host)
-    if (f.adv1) printf("adver1: %d; ", stcsp_automaton_adversarial(a, 5));
-    if (f.adv2) printf("adver2: %d\n", stcsp_automaton_adversarial2(a, 5, 6));
+    if (f.adv1) fprintf(info, "adver1: %d; ", stcsp_automaton_adversarial(a, 5));
+    if (f.adv2) fprintf(info, "adver2: %d\n", stcsp_automaton_adversarial2(a, 5, 6));
+    if (f.check && check_on_host(streams, a)) {  // (host twin: the merged automaton lives on the host)
+        fprintf(stderr, "the streams could not be checked\n");
+        return 1;
+    }
     if (f.quotient && fold(f, p, &a, nullptr, 0, 0)) {  // (host twin: the merged automaton lives on the host)
         fprintf(stderr, "the quotient could not be built\n");
         return 1;
@@ -247,9 +391,9 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
     if (f.print_solution) stcsp_automaton_write_dot(a, "solutions.dot");
     if (f.binary && stcsp_automaton_write_binary(a, f.binary) != STCSP_OK) fprintf(stderr, "cannot write %s\n", f.binary);
     if (print_line) {
-        printf("%.2f\t%d\t%d\t%d\t%d\t%d\t%.2f\t%.5f\n", init_time, p->n_vars, p->n_constraints, (int)merged->counters.dominance,
-               (int)merged->n_states, (int)merged->counters.fails, solve_time, proc_time);
-        fflush(stdout);
+        fprintf(info, "%.2f\t%d\t%d\t%d\t%d\t%d\t%.2f\t%.5f\n", init_time, p->n_vars, p->n_constraints, (int)merged->counters.dominance,
+                (int)merged->n_states, (int)merged->counters.fails, solve_time, proc_time);
+        fflush(info);
     }
     if (total) *total = solve_time + proc_time;
     stcsp_automaton_free(a);
@@ -278,6 +422,10 @@ int main(int argc, char **argv) {
         if (strcmp(a, "--quotient") == 0 || strcmp(a, "--quotient=all") == 0) {
             f.quotient = true;
             f.quotient_all = a[10] == '=';
+            continue;
+        }
+        if (strncmp(a, "--check=", 8) == 0) {
+            f.check = a + 8;
             continue;
         }
         if (strcmp(a, "--intervals") == 0) {
