@@ -325,6 +325,86 @@ typedef struct stcsp_monitor_result {
 int stcsp_engine_monitor_build(stcsp_engine *engine, const stcsp_monitor_options *options, stcsp_monitor_info *info);
 int stcsp_engine_monitor_check(stcsp_engine *engine, const stcsp_monitor_streams *streams, stcsp_monitor_result *result);
 
+/* ---- counting, enumerating and sampling solution prefixes on the device (no reference counterpart) -----------
+ * The converse of the monitor. Live automaton and default mask as in stcsp_engine_quotient().
+ *
+ * Canonical order. The live out-edges of a state are ordered lexicographically by their full value row (edge_values,
+ * all n_vars, variable order), ties broken by edge index. The order does not depend on state or edge numbers, so
+ * nothing below does.
+ *
+ * Weights. W_0(s) = 1, or final[s] (0 or 1) with STCSP_GEN_END_FINAL. W_{t+1}(s) = the sum over the live out-edges of
+ * s, in canonical order, of W_t(dst): IEEE doubles, added one after the other in that order, starting from 0.
+ * count[t] = W_t(root) for t = 0 .. horizon, all 0 without a live root. While a value is below 2^53 it is the exact
+ * number of live paths of that length (ending in a final state with STCSP_GEN_END_FINAL), whatever the order of the
+ * sums; beyond that it is the double the fixed order gives. If a count[t] is not finite, generator_build() returns
+ * STCSP_E_UNSUPPORTED.
+ *
+ * A stream of length L <= horizon. Start at s = root. For t = 0 .. L-1, with r = L - t and a target tau: go over the
+ * live out-edges of s in canonical order with a running sum that starts at 0 and adds W_{r-1}(dst) per edge; take the
+ * first edge after whose addition the sum exceeds tau (if rounding lets none exceed it, the last edge of non-zero
+ * weight); emit that edge's row projected on the observable variables, in variable order; s = its destination.
+ *   sample  (ranks == NULL): tau = u * W_r(s) with u = (double)(z >> 11) * 2^-53 and
+ *               z = mix(mix(mix(seed + 0x9e3779b97f4a7c15) + i) + t)                    (i: index of the stream; mod 2^64)
+ *               mix(x): x ^= x >> 30; x *= 0xbf58476d1ce4e5b9; x ^= x >> 27; x *= 0x94d049bb133111eb; x ^= x >> 31
+ *           (the splitmix64 finaliser). Nothing is carried from step to step. Every path of length L is drawn with
+ *           probability 1 / count[L] while count[L] < 2^53: uniform over PATHS; under a hiding mask two paths may
+ *           project on the same stream.
+ *   unrank  (ranks[i] given): tau = (double)ranks[i] at t = 0; after each step tau -= the running sum before the
+ *           chosen edge. Needs count[L] < 2^53 and ranks[i] < count[L] (else STCSP_E_INVALID). The answer is the
+ *           ranks[i]-th path of length L in lexicographic order of its sequence of full rows.
+ * A length with count[L] == 0 gives STCSP_E_INVALID. end_final[i] = final[the state stream i ends in].
+ *
+ * Every floating-point step above is one addition, one subtraction, one multiplication or one comparison of doubles:
+ * no fused multiply-add, no reassociation. The device, the host twin (stcsp_automaton_generate() of stcsp_host.h) and
+ * any IEEE implementation of this text therefore agree bit for bit, beyond 2^53 too.
+ *
+ * generator_build() builds, in HBM, the live edges by source in canonical order and the (horizon + 1) x n_states table
+ * of weights (STCSP_E_NOMEM if it cannot be allocated). They stay valid until the next solve(), export(),
+ * postprocess() or generator_build() on the engine, and live apart from the monitor's structures. Both calls are valid
+ * where stcsp_engine_monitor_build() is: STCSP_E_STATE before postprocess(), after a truncated solve and for
+ * generate() without valid structures; STCSP_E_UNSUPPORTED on sharded and stepped engines. */
+#define STCSP_GEN_END_FINAL 1 /* count and generate only the prefixes that end in a final state */
+
+typedef struct stcsp_generator_options {
+    const uint8_t *observable; /* [n_vars] nonzero = observable; NULL = the default mask of stcsp_engine_quotient() */
+    int32_t horizon;           /* >= 0: the longest stream generate() may be asked for                              */
+    int32_t flags;             /* STCSP_GEN_*                                                                       */
+    int32_t reserved[2];
+} stcsp_generator_options;
+
+typedef struct stcsp_generator_info {
+    int64_t n_states;       /* live states                                                       */
+    int64_t n_edges;        /* live edges                                                        */
+    int64_t table_bytes;    /* HBM the structures hold                                           */
+    const double *count;    /* [horizon + 1] owned by the engine, valid until the next build     */
+    int32_t n_observable;   /* values per step                                                   */
+    int32_t horizon;
+    int32_t max_out_degree; /* most live out-edges of one state                                  */
+    int32_t root_live;
+    double seconds;         /* wall time from the flags in HBM to the finished structures        */
+} stcsp_generator_info;
+
+typedef struct stcsp_generate_request {
+    int64_t n_streams;
+    const uint64_t *ranks; /* [n_streams] unrank these; NULL = sample */
+    uint64_t seed;         /* sample only                             */
+    int32_t len;           /* steps per stream, 0 .. horizon          */
+    int32_t reserved;
+} stcsp_generate_request;
+
+typedef struct stcsp_generate_result {
+    int64_t n_streams;
+    const int32_t *values;    /* [n_streams * len * n_observable] owned by the engine, valid until the next call on it */
+    const uint8_t *end_final; /* [n_streams]                                                                            */
+    int32_t len;
+    int32_t n_observable;
+    double seconds;           /* wall time from the request to the host output */
+    double seconds_kernel;    /* HIP-event time of the generate kernel         */
+} stcsp_generate_result;
+
+int stcsp_engine_generator_build(stcsp_engine *engine, const stcsp_generator_options *options, stcsp_generator_info *info);
+int stcsp_engine_generate(stcsp_engine *engine, const stcsp_generate_request *request, stcsp_generate_result *result);
+
 void stcsp_engine_destroy(stcsp_engine *engine);
 
 /* Message of the last error on this engine (or of the last failed create when engine==NULL). */

@@ -124,6 +124,18 @@ int stcsp_automaton_check_streams(const stcsp_automaton *a, const uint8_t *obser
 /* Values per step under a mask: the number of observable variables (NULL = the default mask). */
 int stcsp_automaton_num_observable(const stcsp_automaton *a, const uint8_t *observable);
 
+/* ---- counting, enumerating and sampling solution prefixes (definition: stcsp_engine.h, stcsp_engine_generate) ----
+ * The same contract written plainly, on the automaton's current flags: the checker of the device pass in the tests, and
+ * the path for automata whose flags live on the host (sharded runs, host adversarial passes, read_binary). One call
+ * builds the canonical order and the weights and generates. observable: as in stcsp_automaton_bisimulation(); flags:
+ * STCSP_GEN_*; ranks: [n_streams] to unrank, NULL to sample with `seed`. count (may be NULL): [horizon + 1];
+ * values: [n_streams * len * (number of observable variables)]; end_final: [n_streams]. count is filled whenever the
+ * weights are finite, also when the request itself is then refused. STCSP_E_INVALID and STCSP_E_UNSUPPORTED as there. */
+int stcsp_automaton_generate(const stcsp_automaton *a, const uint8_t *observable, int32_t horizon, int32_t flags, int64_t n_streams,
+                             int32_t len, uint64_t seed, const uint64_t *ranks, double *count, int32_t *values, uint8_t *end_final);
+/* count[t], t = 0 .. horizon, alone. */
+int stcsp_automaton_count_streams(const stcsp_automaton *a, int32_t horizon, int32_t flags, double *count);
+
 /* Merge the per-shard results of a sharded run (global state ids, see stcsp_engine.h) into
  * one result with dense ids; runs the ok-fixpoint over the union. The merged result is owned
  * by the returned handle. */

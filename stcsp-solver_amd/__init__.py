@@ -118,6 +118,33 @@ class MonitorResult(C.Structure):
 
 MON_FORCE_SETS = 1  # check_streams(force_sets=True): the state-set kernel under a deterministic mask too (tests, measurements)
 
+
+class GeneratorOptions(C.Structure):
+    _fields_ = [("observable", C.POINTER(C.c_uint8)), ("horizon", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class GeneratorInfo(C.Structure):
+    _fields_ = [("n_states", C.c_int64), ("n_edges", C.c_int64), ("table_bytes", C.c_int64), ("_count", C.POINTER(C.c_double)),
+                ("n_observable", C.c_int32), ("horizon", C.c_int32), ("max_out_degree", C.c_int32), ("root_live", C.c_int32),
+                ("seconds", C.c_double)]
+    count = None  # numpy float64 [horizon + 1], a copy (Engine.generator() sets it)
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
+
+
+class GenerateRequest(C.Structure):
+    _fields_ = [("n_streams", C.c_int64), ("ranks", C.POINTER(C.c_uint64)), ("seed", C.c_uint64), ("len", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class GenerateResult(C.Structure):
+    _fields_ = [("n_streams", C.c_int64), ("values", C.POINTER(C.c_int32)), ("end_final", C.POINTER(C.c_uint8)), ("len", C.c_int32),
+                ("n_observable", C.c_int32), ("seconds", C.c_double), ("seconds_kernel", C.c_double)]
+
+
+GEN_END_FINAL = 1  # generator(end_final=True): only the prefixes that end in a final state
+
 F_KEEP_RAW_EDGES = 1
 F_NO_EXPORT = 2
 F_PROFILE = 4
@@ -132,7 +159,7 @@ ENGINE_SYMBOLS = [
     "stcsp_engine_counters", "stcsp_engine_sets_blob", "stcsp_engine_sets_import", "stcsp_engine_postprocess",
     "stcsp_engine_propagate", "stcsp_engine_set_expand_budget", "stcsp_engine_node_bytes", "stcsp_engine_donate",
     "stcsp_engine_adopt", "stcsp_engine_expand_variant", "stcsp_engine_quotient",
-    "stcsp_engine_monitor_build", "stcsp_engine_monitor_check",
+    "stcsp_engine_monitor_build", "stcsp_engine_monitor_check", "stcsp_engine_generator_build", "stcsp_engine_generate",
 ]
 # include/stcsp_sharded.h: the superstep loop + in-process transport (libstcsp_hip.so), the RCCL transport (libstcsp_rccl.so)
 SHARDED_SYMBOLS_HIP = ["stcsp_engine_solve_sharded", "stcsp_local_group_create", "stcsp_local_group_transport", "stcsp_local_group_destroy"]
@@ -147,7 +174,7 @@ HOST_SYMBOLS = [
     "stcsp_automaton_num_live_states", "stcsp_automaton_num_live_edges",
     "stcsp_merge_shards", "stcsp_merged_result", "stcsp_merged_free", "stcsp_host_free",
     "stcsp_automaton_bisimulation", "stcsp_automaton_set_observable", "stcsp_automaton_quotient",
-    "stcsp_automaton_check_streams", "stcsp_automaton_num_observable",
+    "stcsp_automaton_check_streams", "stcsp_automaton_num_observable", "stcsp_automaton_generate", "stcsp_automaton_count_streams",
 ]
 
 
@@ -222,6 +249,9 @@ def host_lib() -> C.CDLL:
         lib.stcsp_automaton_check_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         lib.stcsp_automaton_num_observable.argtypes = [C.c_void_p, C.c_void_p]
+        lib.stcsp_automaton_generate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_uint64, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.stcsp_automaton_count_streams.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         lib.stcsp_merge_shards.argtypes = [C.POINTER(C.POINTER(Result)), C.c_int, C.POINTER(C.c_void_p)]
         lib.stcsp_merged_result.argtypes = [C.c_void_p]
         lib.stcsp_merged_result.restype = C.POINTER(Result)
@@ -270,6 +300,9 @@ def bind_engine_api(lib: C.CDLL, prefix: str = "stcsp_engine") -> None:
     if hasattr(lib, f"{prefix}_monitor_build"):
         g("monitor_build").argtypes = [C.c_void_p, C.POINTER(MonitorOptions), C.POINTER(MonitorInfo)]
         g("monitor_check").argtypes = [C.c_void_p, C.POINTER(MonitorStreams), C.POINTER(MonitorResult)]
+    if hasattr(lib, f"{prefix}_generator_build"):
+        g("generator_build").argtypes = [C.c_void_p, C.POINTER(GeneratorOptions), C.POINTER(GeneratorInfo)]
+        g("generate").argtypes = [C.c_void_p, C.POINTER(GenerateRequest), C.POINTER(GenerateResult)]
     if hasattr(lib, f"{prefix}_propagate"):
         g("propagate").argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64)]
@@ -502,6 +535,42 @@ class Automaton:
             raise StcspError(rc, "check_streams failed: malformed offsets")
         return acc[:n], nend[:n], fin[:n], largest.value
 
+    def generate(self, n, length, seed=0, ranks=None, observable=None, horizon=None, end_final=False):
+        """Sample (ranks=None) or unrank `n` solution prefixes of `length` steps by the host twin of Engine.generate()
+        (contract: include/stcsp_engine.h, stcsp_engine_generate), on the automaton's current flags. `observable` as in
+        bisimulation(); `horizon` defaults to `length`. Returns (values int32 [n, length, n_observable], end_final uint8 [n],
+        count float64 [horizon + 1])."""
+        import numpy as np
+        lib = host_lib()
+        m = self._mask(observable)
+        mp = m.ctypes.data if m is not None else None
+        n_obs = lib.stcsp_automaton_num_observable(self._h, mp)
+        horizon = length if horizon is None else horizon
+        rk = None
+        if ranks is not None:
+            rk = np.ascontiguousarray(ranks, dtype=np.uint64)
+            if rk.shape != (n,):
+                raise ValueError("ranks must have one entry per stream")
+        values = np.zeros((max(n, 0), max(length, 0), n_obs), np.int32)
+        fin = np.zeros(max(n, 1), np.uint8)
+        count = np.zeros(max(horizon, 0) + 1, np.float64)
+        rc = lib.stcsp_automaton_generate(self._h, mp, horizon, GEN_END_FINAL if end_final else 0, n, length, seed,
+                                          rk.ctypes.data if rk is not None and rk.size else None, count.ctypes.data,
+                                          values.ctypes.data if values.size else None, fin.ctypes.data)
+        if rc != 0:
+            raise StcspError(rc, "generate failed: a length without a prefix or beyond the horizon, a rank that is not below count[length] < 2^53, "
+                                 "or a count that overflows a double")
+        return values, fin[:n], count
+
+    def count_streams(self, horizon, end_final=False):
+        """count[t], t = 0 .. horizon: the number of solution prefixes of length t (float64; exact below 2^53)."""
+        import numpy as np
+        count = np.zeros(max(horizon, 0) + 1, np.float64)
+        rc = host_lib().stcsp_automaton_count_streams(self._h, horizon, GEN_END_FINAL if end_final else 0, count.ctypes.data)
+        if rc != 0:
+            raise StcspError(rc, "count_streams failed")
+        return count
+
     def canonical(self) -> str:
         lib = host_lib()
         n = C.c_size_t()
@@ -713,6 +782,51 @@ class EngineBase:
             return np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint8), 0
         return (np.ctypeslib.as_array(out.accepted_len, shape=(n,)).copy(), np.ctypeslib.as_array(out.n_end, shape=(n,)).copy(),
                 np.ctypeslib.as_array(out.end_final, shape=(n,)).copy(), out.n_host_fallback)
+
+    def generator(self, observable=None, horizon=64, end_final=False) -> GeneratorInfo:
+        """Build the stream generator's structures on the device for one mask and horizon, after postprocess() (`observable`
+        as in quotient()). They stay valid until the next solve / postprocess / generator. Returns the GeneratorInfo; its
+        .count is a numpy float64 array [horizon + 1]: the number of solution prefixes of every length."""
+        import numpy as np
+        nv = self._model.n_vars
+        go = GeneratorOptions()
+        go.horizon = horizon
+        go.flags = GEN_END_FINAL if end_final else 0
+        if observable is not None:
+            m = np.ones(nv, dtype=np.uint8) if isinstance(observable, str) and observable == "all" else np.ascontiguousarray(observable, dtype=np.uint8)
+            if m.shape != (nv,):
+                raise ValueError(f"observable must have one flag per variable ({nv})")
+            go.observable = m.ctypes.data_as(C.POINTER(C.c_uint8))
+        info = GeneratorInfo()
+        self.generator_info = None
+        self._check(self._f("generator_build")(self._h, C.byref(go), C.byref(info)))
+        info.count = np.ctypeslib.as_array(info._count, shape=(info.horizon + 1,)).copy()
+        self.generator_info = info
+        return info
+
+    def generate(self, n, length, seed=0, ranks=None):
+        """`n` solution prefixes of `length` steps from the device, after generator(): sampled with `seed` (uniform over the
+        paths of that length), or the ranks[i]-th in lexicographic order. Returns (values int32 [n, length, n_observable],
+        end_final uint8 [n]); the whole GenerateResult of the call is kept in self.generate_result."""
+        import numpy as np
+        if getattr(self, "generator_info", None) is None:
+            raise StcspError(-6, "generate() needs generator() first")
+        rq = GenerateRequest(n, None, seed, length, 0)
+        if ranks is not None:
+            rk = np.ascontiguousarray(ranks, dtype=np.uint64)
+            if rk.shape != (n,):
+                raise ValueError("ranks must have one entry per stream")
+            if n == 0:
+                rk = np.zeros(1, np.uint64)
+            rq.ranks = rk.ctypes.data_as(C.POINTER(C.c_uint64))
+        out = GenerateResult()
+        self._check(self._f("generate")(self._h, C.byref(rq), C.byref(out)))
+        self.generate_result = out
+        n_obs = out.n_observable
+        cells = n * length * n_obs
+        values = np.ctypeslib.as_array(out.values, shape=(cells,)).copy() if cells else np.zeros(0, np.int32)
+        fin = np.ctypeslib.as_array(out.end_final, shape=(n,)).copy() if n else np.zeros(0, np.uint8)
+        return values.reshape(n, length, n_obs), fin
 
     def automaton(self, result: Result | None = None) -> Automaton:
         return Automaton(self._model, result if result is not None else self.result)

@@ -57,6 +57,8 @@ using namespace stcsp;
 #include "dev_quotient.hpp"
 #include "dev_monitor.hpp"
 #include "monitor_host.hpp"
+#include "dev_generate.hpp"
+#include "generate_host.hpp"
 
 using namespace stcsp::dev;
 
@@ -219,6 +221,19 @@ struct stcsp_engine {
     hipEvent_t ev_m[3] = {nullptr, nullptr, nullptr};
     std::vector<int32_t> m_acc, m_nend;
     std::vector<uint8_t> m_fin;
+    // stream generator (dev_generate.hpp): the structures of the last generator_build(), valid while gen_built
+    bool gen_built = false, gen_root_live = false;
+    int gen_n_obs = 0, gen_horizon = 0;
+    std::vector<double> gen_count;
+    std::vector<uint8_t> gen_live;
+    DevBuf<uint8_t> d_glive, d_gfin;
+    DevBuf<int32_t> d_gobs, d_gout;
+    DevBuf<uint32_t> d_goff, d_gcur, d_gseg, d_geid, d_gdst, d_gtile, d_gctl;
+    DevBuf<double> d_gw, d_gcount;
+    DevBuf<unsigned long long> d_granks;
+    hipEvent_t ev_g[2] = {nullptr, nullptr};
+    std::vector<int32_t> g_values;
+    std::vector<uint8_t> g_fin;
 
     ~stcsp_engine() {
         // the device writes several of the pinned buffers freed below (progress mirror, streamed result arrays) from
@@ -254,6 +269,8 @@ struct stcsp_engine {
         if (ev_k) (void)hipEventDestroy(ev_k);
         for (int i = 0; i < 3; i++)
             if (ev_m[i]) (void)hipEventDestroy(ev_m[i]);
+        for (int i = 0; i < 2; i++)
+            if (ev_g[i]) (void)hipEventDestroy(ev_g[i]);
         if (stream) (void)hipStreamDestroy(stream);
     }
 
@@ -1094,6 +1111,7 @@ struct stcsp_engine {
         exp_on_device = false;
         post_done = false;
         mon_built = false;
+        gen_built = false;
         ev_used = 0;
         seconds_expand_kernel = 0;
         expand_launches = 0;
@@ -2072,6 +2090,7 @@ struct stcsp_engine {
         auto t0 = std::chrono::steady_clock::now();
         post_done = false;
         mon_built = false;
+        gen_built = false;
         const size_t E = exp_edges;
         const uint32_t S = n_states;
         auto width = [&](int v) { return (long long)mgr.ub[v] - (long long)mgr.lb[v] + 1; };
@@ -2511,6 +2530,166 @@ struct stcsp_engine {
         return STCSP_OK;
     }
 
+    // Stream generator, build (dev_generate.hpp): the live edges by source in canonical order and the
+    // weights W_0 .. W_horizon of every state, from the flags the last postprocess() left in HBM.
+    int generator_build(const stcsp_generator_options *go, stcsp_generator_info *info) {
+        if (sharded) return fail(STCSP_E_UNSUPPORTED, "the device generator is for unsharded engines (stcsp_automaton_generate on the merged automaton)");
+        if (!exp_on_device || !post_done) return fail(STCSP_E_STATE, "generator_build needs the flags of postprocess() on the last solve");
+        if (truncated) return fail(STCSP_E_STATE, "generator_build after a truncated solve: the open states of a partial automaton have no known language");
+        if (!go || go->horizon < 0) return fail(STCSP_E_INVALID, "generator_build: the horizon must not be negative");
+        auto t0 = std::chrono::steady_clock::now();
+        gen_built = false;
+        const int N = ctx.N, H = go->horizon;
+        const uint32_t E = (uint32_t)exp_edges, S = n_states;
+        if ((size_t)exp_edges > 0x7fffffffull) return fail(STCSP_E_NOMEM, "edge list too large for the device generator");
+        const uint8_t *mask = go->observable ? go->observable : default_observable.data();
+        std::vector<int32_t> obs;
+        for (int v = 0; v < N; v++)
+            if (mask[v]) obs.push_back(v);
+        const uint32_t n_tiles = (S + kGenScanTile - 1) / kGenScanTile;
+        if (d_glive.n < S) {
+            const size_t c = (size_t)S + S / 4 + 256;
+            HIPCHK(d_glive.alloc(c));
+            HIPCHK(d_goff.alloc(c + 1));
+            HIPCHK(d_gcur.alloc(c));
+            HIPCHK(d_gtile.alloc(c / kGenScanTile + 2));
+        }
+        if (d_gseg.n < E) {
+            const size_t c = (size_t)E + E / 4 + 256;
+            HIPCHK(d_gseg.alloc(c));
+            HIPCHK(d_geid.alloc(c));
+            HIPCHK(d_gdst.alloc(c));
+        }
+        const size_t table = ((size_t)H + 1) * S;
+        if (d_gw.n < table && d_gw.alloc(table) != hipSuccess) {
+            (void)hipGetLastError();
+            d_gw.release();
+            return fail(STCSP_E_NOMEM, "generator_build: no room for the %d x %u table of weights", H + 1, S);
+        }
+        if (d_gcount.n < (size_t)H + 1) HIPCHK(d_gcount.alloc((size_t)H + 1));
+        if (d_gobs.n < (size_t)N) HIPCHK(d_gobs.alloc((size_t)N));
+        if (!d_gctl.p) HIPCHK(d_gctl.alloc(G_WORDS));
+        const unsigned eb = (E + 255) / 256, sb = (S + 255) / 256;
+        uint32_t ctl[G_WORDS] = {0}, total = 0;
+        if (!obs.empty()) HIPCHK(hipMemcpyAsync(d_gobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemsetAsync(d_gctl.p, 0, sizeof ctl, stream));
+        // the live automaton: forward reachability from a valid root, as the quotient does it
+        HIPCHK(hipMemsetAsync(d_glive.p, 0, S, stream));
+        HIPCHK(hipMemcpyAsync(d_glive.p, d_pvalid.p, 1, hipMemcpyDeviceToDevice, stream));
+        for (int sweeps = 0; E; sweeps++) {
+            HIPCHK(hipMemsetAsync(d_gctl.p + G_CHANGED, 0, sizeof(uint32_t), stream));
+            hipLaunchKernelGGL(k_q_reach, dim3(eb), dim3(256), 0, stream, E, (const long long *)d_osrc.p, (const long long *)d_odst.p,
+                               (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_glive.p, d_gctl.p);
+            HIPCHK(hipMemcpyAsync(ctl, d_gctl.p, sizeof ctl, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            if (!ctl[G_CHANGED]) break;
+            if (sweeps > (int)S + 8) return fail(STCSP_E_INTERNAL, "generator: reachability did not converge");
+        }
+        // live edges by source: histogram, exclusive scan over the states, fill through a cursor, canonical order
+        HIPCHK(hipMemsetAsync(d_gcur.p, 0, (size_t)S * sizeof(uint32_t), stream));
+        if (E)
+            hipLaunchKernelGGL(k_g_degree, dim3(eb), dim3(256), 0, stream, E, (const long long *)d_osrc.p, (const long long *)d_odst.p,
+                               (const uint8_t *)d_palive.p, (const uint8_t *)d_glive.p, d_gcur.p);
+        hipLaunchKernelGGL(k_g_scan_tiles, dim3(n_tiles), dim3(256), 0, stream, S, (const uint32_t *)d_gcur.p, d_gtile.p);
+        hipLaunchKernelGGL(k_g_scan_sums, dim3(1), dim3(256), 0, stream, n_tiles, d_gtile.p);
+        hipLaunchKernelGGL(k_g_scan_write, dim3(n_tiles), dim3(256), 0, stream, S, (const uint32_t *)d_gcur.p, (const uint32_t *)d_gtile.p, n_tiles,
+                           d_goff.p, d_gcur.p);
+        if (E) {
+            hipLaunchKernelGGL(k_g_fill, dim3(eb), dim3(256), 0, stream, E, (const long long *)d_osrc.p, (const long long *)d_odst.p,
+                               (const uint8_t *)d_palive.p, (const uint8_t *)d_glive.p, d_gcur.p, d_gseg.p);
+            hipLaunchKernelGGL(k_g_order, dim3((S + 3) / 4), dim3(256), 0, stream, S, (const uint32_t *)d_goff.p, d_gseg.p, (const long long *)d_odst.p,
+                               (const int32_t *)d_oval.p, N, d_geid.p, d_gdst.p, d_gctl.p);
+        }
+        // the weights, one launch per level
+        hipLaunchKernelGGL(k_g_level0, dim3(sb), dim3(256), 0, stream, S, (const uint8_t *)d_glive.p, (const uint8_t *)d_pfinal.p,
+                           (go->flags & STCSP_GEN_END_FINAL) ? 1 : 0, d_gw.p, d_gcount.p);
+        for (int t = 0; t < H; t++)
+            hipLaunchKernelGGL(k_g_weights, dim3(sb), dim3(256), 0, stream, S, (const uint32_t *)d_goff.p, (const uint32_t *)d_gdst.p,
+                               (const double *)(d_gw.p + (size_t)t * S), d_gw.p + (size_t)(t + 1) * S, d_gcount.p + t + 1);
+        HIPCHK(hipGetLastError());
+        gen_live.resize(S);
+        gen_count.assign((size_t)H + 1, 0.0);
+        HIPCHK(hipMemcpyAsync(gen_live.data(), d_glive.p, S, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(gen_count.data(), d_gcount.p, ((size_t)H + 1) * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(&total, d_goff.p + S, sizeof total, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(ctl, d_gctl.p, sizeof ctl, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        int64_t n_live = 0;
+        for (uint32_t s = 0; s < S; s++) n_live += gen_live[s];
+        gen_root_live = S > 0 && gen_live[0];
+        for (double c : gen_count)
+            if (!std::isfinite(c)) return fail(STCSP_E_UNSUPPORTED, "generator_build: the number of prefixes of length %d overflows a double", H);
+        gen_n_obs = (int)obs.size();
+        gen_horizon = H;
+        gen_built = true;
+        memset(info, 0, sizeof *info);
+        info->n_states = n_live;
+        info->n_edges = total;
+        info->table_bytes = (int64_t)(table * sizeof(double) + 3 * (size_t)E * sizeof(uint32_t) + (2 * (size_t)S + 1) * sizeof(uint32_t) + S);
+        info->count = gen_count.data();
+        info->n_observable = gen_n_obs;
+        info->horizon = H;
+        info->max_out_degree = (int32_t)ctl[G_MAXDEG];
+        info->root_live = gen_root_live;
+        info->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return STCSP_OK;
+    }
+
+    // Stream generator, generate: n_streams prefixes of one length, sampled or unranked (contract: stcsp_engine.h).
+    int generate(const stcsp_generate_request *rq, stcsp_generate_result *out) {
+        if (sharded) return fail(STCSP_E_UNSUPPORTED, "the device generator is for unsharded engines (stcsp_automaton_generate on the merged automaton)");
+        if (!exp_on_device || !post_done || truncated || !gen_built)
+            return fail(STCSP_E_STATE, "generate needs generator_build() after the last postprocess()");
+        if (!stcsp::generate_request_ok(gen_count, rq->n_streams, rq->len, rq->n_streams > 0 ? rq->ranks : nullptr))
+            return fail(STCSP_E_INVALID, "generate: a length outside 0 .. horizon or without a prefix, or a rank that is not below count[len] < 2^53");
+        auto t0 = std::chrono::steady_clock::now();
+        const size_t n = (size_t)rq->n_streams, len = (size_t)rq->len;
+        const size_t cells = n * len * (size_t)gen_n_obs;
+        if (n >= 0x7fffffffull) return fail(STCSP_E_NOMEM, "generate: too many streams for one call");
+        g_values.assign(cells, 0);
+        g_fin.assign(n, 0);
+        memset(out, 0, sizeof *out);
+        out->n_streams = rq->n_streams;
+        out->values = g_values.data();
+        out->end_final = g_fin.data();
+        out->len = rq->len;
+        out->n_observable = gen_n_obs;
+        if (n) {  // (count[len] > 0: the root is live)
+            if (d_gfin.n < n) HIPCHK(d_gfin.alloc(n + n / 4 + 256));
+            if (d_gout.n < cells) HIPCHK(d_gout.alloc(cells + cells / 4 + 256));
+            if (rq->ranks && d_granks.n < n) HIPCHK(d_granks.alloc(n + n / 4 + 256));
+            for (int i = 0; i < 2; i++)
+                if (!ev_g[i]) HIPCHK(hipEventCreate(&ev_g[i]));
+            if (rq->ranks) HIPCHK(hipMemcpyAsync(d_granks.p, rq->ranks, n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemsetAsync(d_gctl.p + G_ERROR, 0, sizeof(uint32_t), stream));
+            HIPCHK(hipEventRecord(ev_g[0], stream));
+            const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+            if (rq->ranks)
+                hipLaunchKernelGGL(k_g_generate<true>, grid, block, 0, stream, (uint32_t)n, (uint32_t)len, 0ull, (const unsigned long long *)d_granks.p,
+                                   n_states, (const double *)d_gw.p, (const uint32_t *)d_goff.p, (const uint32_t *)d_gdst.p, (const uint32_t *)d_geid.p,
+                                   (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_gobs.p, gen_n_obs, (const uint8_t *)d_pfinal.p, d_gout.p,
+                                   d_gfin.p, d_gctl.p);
+            else
+                hipLaunchKernelGGL(k_g_generate<false>, grid, block, 0, stream, (uint32_t)n, (uint32_t)len, (unsigned long long)rq->seed,
+                                   (const unsigned long long *)nullptr, n_states, (const double *)d_gw.p, (const uint32_t *)d_goff.p,
+                                   (const uint32_t *)d_gdst.p, (const uint32_t *)d_geid.p, (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_gobs.p,
+                                   gen_n_obs, (const uint8_t *)d_pfinal.p, d_gout.p, d_gfin.p, d_gctl.p);
+            HIPCHK(hipEventRecord(ev_g[1], stream));
+            HIPCHK(hipGetLastError());
+            uint32_t bad = 0;
+            if (cells) HIPCHK(hipMemcpyAsync(g_values.data(), d_gout.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(g_fin.data(), d_gfin.p, n, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(&bad, d_gctl.p + G_ERROR, sizeof bad, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            float ms_k = 0;
+            HIPCHK(hipEventElapsedTime(&ms_k, ev_g[0], ev_g[1]));
+            out->seconds_kernel = ms_k * 1e-3;
+            if (bad) return fail(STCSP_E_INTERNAL, "generate: a state without an edge of non-zero weight");
+        }
+        out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return STCSP_OK;
+    }
+
     // unsharded export: ok-fixpoint + compaction on the device, result arrays land in pinned memory
     int export_device(stcsp_result *res, stcsp_counters &ctr, size_t &E_out) {
         const int N = ctx.N;
@@ -2655,6 +2834,7 @@ struct stcsp_engine {
         exp_on_device = true;
         post_done = false;
         mon_built = false;
+        gen_built = false;
         return STCSP_OK;
     }
 
@@ -2885,6 +3065,16 @@ int stcsp_engine_monitor_build(stcsp_engine *e, const stcsp_monitor_options *opt
 int stcsp_engine_monitor_check(stcsp_engine *e, const stcsp_monitor_streams *streams, stcsp_monitor_result *result) {
     if (!e || !streams || !result) return STCSP_E_INVALID;
     return e->monitor_check(streams, result);
+}
+
+int stcsp_engine_generator_build(stcsp_engine *e, const stcsp_generator_options *options, stcsp_generator_info *info) {
+    if (!e || !info) return STCSP_E_INVALID;
+    return e->generator_build(options, info);
+}
+
+int stcsp_engine_generate(stcsp_engine *e, const stcsp_generate_request *request, stcsp_generate_result *result) {
+    if (!e || !request || !result) return STCSP_E_INVALID;
+    return e->generate(request, result);
 }
 
 void stcsp_engine_destroy(stcsp_engine *e) { delete e; }

@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "generate_host.hpp"
 #include "monitor_host.hpp"
 #include "okfix.hpp"
 #include "stcsp_host.h"
@@ -1041,6 +1042,47 @@ int stcsp_automaton_check_streams(const stcsp_automaton *a, const uint8_t *obser
         for (int64_t i = 0; i < n_streams; i++)
             largest = std::max(largest, mon.check_one(values + offsets[i] * mon.n_obs, offsets[i + 1] - offsets[i], &accepted_len[i], &n_end[i], &end_final[i]));
         if (max_set_size) *max_set_size = largest;
+    } catch (const std::bad_alloc &) {
+        return STCSP_E_NOMEM;
+    }
+    return STCSP_OK;
+}
+static stcsp::MonitorView generator_view(const Automaton &g) {
+    stcsp::MonitorView v;
+    v.n_vars = g.n_vars;
+    v.n_states = g.n_states;
+    v.n_edges = (int64_t)g.esrc.size();
+    v.src = g.esrc.data();
+    v.dst = g.edst.data();
+    v.values = g.eval.data();
+    v.valid = g.valid.data();
+    v.final_ = g.final_.data();
+    v.alive = g.ealive.data();
+    return v;
+}
+int stcsp_automaton_generate(const stcsp_automaton *a, const uint8_t *observable, int32_t horizon, int32_t flags, int64_t n_streams,
+                             int32_t len, uint64_t seed, const uint64_t *ranks, double *count, int32_t *values, uint8_t *end_final) {
+    if (!a || horizon < 0 || n_streams < 0) return STCSP_E_INVALID;
+    try {
+        stcsp::HostGenerator gen;
+        if (!gen.build(generator_view(a->a), a->a.observable_mask(observable).data(), horizon, flags)) return STCSP_E_UNSUPPORTED;
+        if (count) std::copy(gen.count.begin(), gen.count.end(), count);
+        if (!stcsp::generate_request_ok(gen.count, n_streams, len, ranks)) return STCSP_E_INVALID;
+        if (n_streams > 0 && (!end_final || (!values && len > 0 && gen.n_obs > 0))) return STCSP_E_INVALID;
+        for (int64_t i = 0; i < n_streams; i++)
+            gen.generate_one(len, seed, (uint64_t)i, ranks ? &ranks[i] : nullptr, values + (size_t)i * (size_t)len * (size_t)gen.n_obs, &end_final[i]);
+    } catch (const std::bad_alloc &) {
+        return STCSP_E_NOMEM;
+    }
+    return STCSP_OK;
+}
+int stcsp_automaton_count_streams(const stcsp_automaton *a, int32_t horizon, int32_t flags, double *count) {
+    if (!a || horizon < 0 || !count) return STCSP_E_INVALID;
+    try {
+        stcsp::HostGenerator gen;
+        std::vector<uint8_t> none((size_t)a->a.n_vars, 0);
+        if (!gen.build(generator_view(a->a), none.data(), horizon, flags)) return STCSP_E_UNSUPPORTED;
+        std::copy(gen.count.begin(), gen.count.end(), count);
     } catch (const std::bad_alloc &) {
         return STCSP_E_NOMEM;
     }

@@ -2,7 +2,8 @@
 // (src/stcsp.y:180-219 main, src/solver.cpp:195-359 solve): same flags, same stdout contract,
 // same solutions.dot. The search itself runs on the MI355X engine behind the C-ABI.
 //
-//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--check=<file>] input.csp
+//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--check=<file>]
+//         [--sample=<N>:<L>[:<seed>] [--sample-final] [--sample-mask=all]] [--count=<L>] input.csp
 //
 // --binary=<file> (not in the reference) additionally writes the printed automaton in the compact
 // binary form of include/stcsp_host.h.
@@ -27,6 +28,14 @@
 // and the reference's statistics line (and "adver1: ..." of -a / -z) goes to stderr. The streams are checked on the device, or
 // by the host twin where the flags live on the host (--shards=N, host adversarial passes); with -a / -z the flags are the ones
 // those passes left. Combined with --quotient the streams are checked against the automaton before it is folded.
+//
+// --sample=<N>:<L>[:<seed>] (not in the reference) prints N sampled solution prefixes of L steps (include/stcsp_engine.h,
+// stcsp_engine_generate; seed 0 when left out) in exactly the format --check= reads: the line "# name name ..." names the
+// observable variables -- the default mask, or every variable with --sample-mask=all -- then one step per line, and a blank line
+// ends each stream, so the output can be fed straight back into --check=. --count=<L> prints "t count[t]" for t = 0 .. L instead:
+// the number of solution prefixes of every length. With --sample-final both take only the prefixes that end in a final state.
+// As with --check, stdout then holds these lines only, and the work is done on the device, or by the host twin where the flags
+// live on the host (--shards=N, host adversarial passes). --check, --sample and --count exclude each other.
 //
 // Options must be glued to their value (-k3, not -k 3): like the reference, the first argument
 // that does not start with '-' is the input file (stcsp.y:199-206).
@@ -62,6 +71,10 @@ struct Flags {
     const char *file = nullptr;
     const char *binary = nullptr;
     const char *check = nullptr;
+    bool sample = false, sample_final = false, sample_all = false;
+    long long sample_n = 0, sample_seed = 0;
+    int sample_len = 0, count_len = -1;
+    bool quiet() const { return check || sample || count_len >= 0; }  // stdout holds the answers only
 };
 
 // --check=<file>: the streams of the file, columns reordered to variable order
@@ -170,6 +183,77 @@ static int check_on_host(const Streams &st, const stcsp_automaton *a) {
     return 0;
 }
 
+// --sample / --count: the mask, and the lines on stdout
+static std::vector<uint8_t> sample_mask(const Flags &f, const stcsp_problem *p) {
+    std::vector<uint8_t> mask((size_t)p->n_vars, 1);
+    for (int v = 0; v < p->n_vars; v++)
+        if (!f.sample_all && p->var_names && p->var_names[v] && strncmp(p->var_names[v], "_V", 2) == 0) mask[(size_t)v] = 0;
+    return mask;
+}
+
+static void print_counts(const double *count, int horizon) {
+    for (int t = 0; t <= horizon; t++) printf("%d %.0f\n", t, count[t]);
+    fflush(stdout);
+}
+
+static void print_samples(const stcsp_problem *p, const std::vector<uint8_t> &mask, long long n, int len, const int32_t *values) {
+    int n_obs = 0;
+    printf("#");
+    for (int v = 0; v < p->n_vars; v++)
+        if (mask[(size_t)v]) {
+            printf(" %s", p->var_names[v]);
+            n_obs++;
+        }
+    printf("\n");
+    for (long long i = 0; i < n; i++) {
+        for (int t = 0; t < len; t++) {
+            const int32_t *row = values + ((size_t)i * (size_t)len + (size_t)t) * (size_t)n_obs;
+            for (int k = 0; k < n_obs; k++) printf(k ? " %d" : "%d", row[k]);
+            printf("\n");
+        }
+        printf("\n");
+    }
+    fflush(stdout);
+}
+
+// --sample / --count on the host twin: the automaton's current flags
+static int generate_on_host(const Flags &f, const stcsp_problem *p, const stcsp_automaton *a) {
+    const int flags = f.sample_final ? STCSP_GEN_END_FINAL : 0;
+    if (f.count_len >= 0) {
+        std::vector<double> count((size_t)f.count_len + 1);
+        if (stcsp_automaton_count_streams(a, f.count_len, flags, count.data()) != STCSP_OK) return 1;
+        print_counts(count.data(), f.count_len);
+        return 0;
+    }
+    const std::vector<uint8_t> mask = sample_mask(f, p);
+    size_t n_obs = 0;
+    for (uint8_t m : mask) n_obs += m;
+    std::vector<int32_t> values((size_t)f.sample_n * (size_t)f.sample_len * n_obs + 1);
+    std::vector<uint8_t> fin((size_t)f.sample_n + 1);
+    if (stcsp_automaton_generate(a, mask.data(), f.sample_len, flags, f.sample_n, f.sample_len, (uint64_t)f.sample_seed, nullptr, nullptr,
+                                 values.data(), fin.data()) != STCSP_OK)
+        return 1;
+    print_samples(p, mask, f.sample_n, f.sample_len, values.data());
+    return 0;
+}
+
+// ... and on the device, over the flags postprocess() has just left
+static int generate_on_device(const Flags &f, const stcsp_problem *p, stcsp_engine *eng) {
+    const std::vector<uint8_t> mask = sample_mask(f, p);
+    stcsp_generator_options go = {mask.data(), f.count_len >= 0 ? f.count_len : f.sample_len, f.sample_final ? STCSP_GEN_END_FINAL : 0, {0, 0}};
+    stcsp_generator_info gi;
+    if (stcsp_engine_generator_build(eng, &go, &gi) != STCSP_OK) return 1;
+    if (f.count_len >= 0) {
+        print_counts(gi.count, f.count_len);
+        return 0;
+    }
+    stcsp_generate_request rq = {f.sample_n, nullptr, (uint64_t)f.sample_seed, f.sample_len, 0};
+    stcsp_generate_result gr;
+    if (stcsp_engine_generate(eng, &rq, &gr) != STCSP_OK) return 1;
+    print_samples(p, mask, f.sample_n, f.sample_len, gr.values);
+    return 0;
+}
+
 // --quotient: replace *a by its quotient under `state_class` (from the device pass), or under the host twin's partition when
 // state_class is NULL
 static int fold(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, const int32_t *state_class, int64_t n_live, int64_t n_classes) {
@@ -210,7 +294,7 @@ static int run_once(const Flags &f, bool print_line, double *total) {
     const stcsp_problem *p = stcsp_model_problem(model);
     Streams streams;
     if (f.check && read_streams(f.check, p, streams)) return 1;
-    FILE *info = f.check ? stderr : stdout;  // --check: stdout holds the answers only
+    FILE *info = f.quiet() ? stderr : stdout;  // --check, --sample, --count: stdout holds the answers only
     double init_time = cpu_time() - t_init;
     stcsp_options opt;
     memset(&opt, 0, sizeof opt);
@@ -248,6 +332,10 @@ static int run_once(const Flags &f, bool print_line, double *total) {
             fprintf(stderr, "the streams could not be checked\n");
             return 1;
         }
+        if ((f.sample || f.count_len >= 0) && generate_on_host(f, p, a)) {
+            fprintf(stderr, "the streams could not be generated: no solution prefix of that length, or their number overflows a double\n");
+            return 1;
+        }
         if (f.quotient && fold(f, p, &a, nullptr, 0, 0)) {
             fprintf(stderr, "the quotient could not be built\n");
             return 1;
@@ -269,6 +357,10 @@ static int run_once(const Flags &f, bool print_line, double *total) {
                 return 1;
             }
             print_streams(streams, mr.accepted_len, mr.n_end, mr.end_final);
+        }
+        if ((f.sample || f.count_len >= 0) && generate_on_device(f, p, eng)) {
+            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
+            return 1;
         }
         if (f.quotient) {
             std::vector<uint8_t> all((size_t)p->n_vars, 1);
@@ -317,7 +409,7 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
     const stcsp_problem *p = stcsp_model_problem(model);
     Streams streams;
     if (f.check && read_streams(f.check, p, streams)) return 1;
-    FILE *info = f.check ? stderr : stdout;  // --check: stdout holds the answers only
+    FILE *info = f.quiet() ? stderr : stdout;  // --check, --sample, --count: stdout holds the answers only
     double init_time = cpu_time() - t_init;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
@@ -381,6 +473,10 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
         fprintf(stderr, "the streams could not be checked\n");
         return 1;
     }
+    if ((f.sample || f.count_len >= 0) && generate_on_host(f, p, a)) {  // (host twin likewise)
+        fprintf(stderr, "the streams could not be generated: no solution prefix of that length, or their number overflows a double\n");
+        return 1;
+    }
     if (f.quotient && fold(f, p, &a, nullptr, 0, 0)) {  // (host twin: the merged automaton lives on the host)
         fprintf(stderr, "the quotient could not be built\n");
         return 1;
@@ -428,6 +524,46 @@ int main(int argc, char **argv) {
             f.check = a + 8;
             continue;
         }
+        if (strncmp(a, "--sample=", 9) == 0) {
+            char *end = nullptr;
+            f.sample_n = strtoll(a + 9, &end, 10);
+            bool ok = end != a + 9 && *end == ':' && f.sample_n >= 0 && f.sample_n <= 100000000;
+            if (ok) {
+                const char *q = end + 1;
+                const long len = strtol(q, &end, 10);
+                ok = end != q && (*end == 0 || *end == ':') && len >= 0 && len <= 1000000;
+                f.sample_len = (int)len;
+                if (ok && *end == ':') {
+                    q = end + 1;
+                    f.sample_seed = strtoll(q, &end, 10);
+                    ok = end != q && *end == 0 && f.sample_seed >= 0;
+                }
+            }
+            if (!ok) {
+                fprintf(stderr, "Invalid argument: %s\n", a);
+                return 1;
+            }
+            f.sample = true;
+            continue;
+        }
+        if (strncmp(a, "--count=", 8) == 0) {
+            char *end = nullptr;
+            const long len = strtol(a + 8, &end, 10);
+            if (end == a + 8 || *end || len < 0 || len > 1000000) {
+                fprintf(stderr, "Invalid argument: %s\n", a);
+                return 1;
+            }
+            f.count_len = (int)len;
+            continue;
+        }
+        if (strcmp(a, "--sample-final") == 0) {
+            f.sample_final = true;
+            continue;
+        }
+        if (strcmp(a, "--sample-mask=all") == 0) {
+            f.sample_all = true;
+            continue;
+        }
         if (strcmp(a, "--intervals") == 0) {
             f.intervals = true;
             continue;
@@ -467,6 +603,10 @@ int main(int argc, char **argv) {
                 default: fprintf(stderr, "Unknown argument: %c\n", o); return 1;
             }
         }
+    }
+    if ((f.check != nullptr) + f.sample + (f.count_len >= 0) > 1) {
+        fprintf(stderr, "--check, --sample and --count exclude each other\n");
+        return 1;
     }
     if (!f.file) {
         printf("No constraints!\n");
