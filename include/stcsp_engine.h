@@ -405,6 +405,81 @@ typedef struct stcsp_generate_result {
 int stcsp_engine_generator_build(stcsp_engine *engine, const stcsp_generator_options *options, stcsp_generator_info *info);
 int stcsp_engine_generate(stcsp_engine *engine, const stcsp_generate_request *request, stcsp_generate_result *result);
 
+/* ---- repairing observed streams: the nearest solution prefix, on the device (no reference counterpart) ---------
+ * The monitor says where a stream stops being a prefix of a solution; this says which prefix of a solution is the
+ * closest one and how far away it is. Live automaton, projected label, default mask and the canonical order of a
+ * state's live out-edges (full value row, ties by edge index) are exactly those of stcsp_engine_generate().
+ *
+ * Input. Streams in the monitor's format (n_streams, offsets in steps, values), weights[n_observable] (int32, each
+ * >= 0; NULL = all 1) and flags. A value STCSP_REPAIR_MISSING in a row means "not observed".
+ *
+ * Step cost. For an edge e with projected row p_e and the observed row x_t:
+ *   c_t(e) = the sum over the observable variables v of weights[v] * [x_t[v] != STCSP_REPAIR_MISSING and p_e[v] != x_t[v]].
+ *
+ * Cost to go, for a stream of len steps. G_0(s) = 0 for every live state (with STCSP_REPAIR_END_FINAL: 0 if final[s],
+ * else infinity). G_{r+1}(s) = the minimum over the live out-edges e of s of c_{len-r-1}(e) + G_r(dst(e)); infinity for a
+ * state without a live out-edge or when every term is infinite. Infinity is 0xffffffff, finite values are uint32. A
+ * request with (the sum of the weights) * (the longest len) > 2^31 - 2 is STCSP_E_INVALID, so no finite value reaches
+ * infinity.
+ *
+ * Answer per stream i.
+ *   distance[i]   G_len(root) as int32; -1 if it is infinite or the root is not live. That is no error: the other
+ *                 outputs of that stream are then 0.
+ *   values        the repaired stream, len rows in the place of the input's. Start at s = root; at step t, with
+ *                 r = len - t, take the FIRST live out-edge of s in canonical order with c_t(e) + G_{r-1}(dst) == G_r(s),
+ *                 emit its projected row, s = dst. That is the path whose sequence of full rows is lexicographically
+ *                 least among the paths of minimum cost: it depends on no state number, edge number or scheduling.
+ *   end_final[i]  final[the last s].
+ *   n_changed[i]  the (step, variable) positions that were observed (not MISSING) and whose emitted value differs.
+ * Everything is integer arithmetic: the device, the host twin (stcsp_automaton_repair_streams() of stcsp_host.h) and any
+ * implementation of this text agree exactly.
+ *
+ * Consequences. With every weight > 0, no MISSING entry and without END_FINAL, distance == 0 exactly when the monitor
+ * reports accepted_len == len, and the repaired stream is then the input. Every repaired stream is accepted whole by
+ * the monitor under the same mask. A stream of L rows of MISSING repairs to the generator's prefix of rank 0 and length L.
+ *
+ * repair() needs a valid stcsp_engine_generator_build() on the engine and uses its mask, live set and canonical order;
+ * the generator's horizon does not limit len and its STCSP_GEN_END_FINAL is not inherited. Without one: STCSP_E_STATE;
+ * STCSP_E_STATE and STCSP_E_UNSUPPORTED otherwise as for stcsp_engine_generate(). Malformed offsets, a negative weight
+ * and the bound above: STCSP_E_INVALID. On the first repair after a generator_build() the exact ids of the projected
+ * labels are built in HBM (n_labels of them); per step and label the cost is then computed once, and a level of the
+ * table reads 4-byte ids, not rows. The request is cut, in its order, into consecutive batches of streams: for each
+ * batch the tables [stream][len + 1][n_states] of uint32 and the costs [step][n_labels] of uint32 fit a byte budget,
+ * by default half of the free device memory; the environment variable STCSP_REPAIR_BYTES sets it (tests use it to
+ * force several batches). STCSP_E_NOMEM only when the table and costs of a SINGLE stream do not fit the budget.
+ * STCSP_REPAIR_WAVE_SEGMENT (default 128) sets the out-degree above which a state is relaxed by a whole wavefront
+ * instead of one lane (measurements). Results are owned by the engine until the next call on it. The call invalidates
+ * neither the generator's nor the monitor's structures. */
+#define STCSP_REPAIR_END_FINAL 1           /* the repaired stream must end in a final state */
+#define STCSP_REPAIR_MISSING (-2147483647 - 1) /* INT32_MIN in a row: this variable was not observed at this step */
+
+typedef struct stcsp_repair_request {
+    int64_t n_streams;
+    const int64_t *offsets; /* [n_streams + 1] in steps: offsets[0] == 0, not decreasing, every stream < 2^31 steps */
+    const int32_t *values;  /* [offsets[n_streams] * n_observable]                                                  */
+    const int32_t *weights; /* [n_observable], each >= 0; NULL = all 1                                              */
+    int32_t flags;          /* STCSP_REPAIR_*                                                                       */
+    int32_t reserved;
+} stcsp_repair_request;
+
+typedef struct stcsp_repair_result {
+    int64_t n_streams;
+    const int32_t *distance;  /* [n_streams] owned by the engine, valid until the next call on it               */
+    const int32_t *values;    /* [offsets[n_streams] * n_observable] the repaired rows, at the input's offsets  */
+    const uint8_t *end_final; /* [n_streams]                                                                    */
+    const int32_t *n_changed; /* [n_streams]                                                                    */
+    int64_t n_labels;         /* distinct projected labels of the live automaton                                */
+    int64_t table_bytes;      /* HBM of the largest batch: tables and costs                                     */
+    int32_t n_batches;
+    int32_t n_observable;
+    double seconds;           /* wall time from the host input to the host output                               */
+    double seconds_relax;     /* HIP-event time of the level-0 and relax kernels, all batches                   */
+    double seconds_walk;      /* HIP-event time of the walk kernel, all batches                                 */
+    double seconds_cost;      /* HIP-event time of the cost kernel, all batches                                 */
+} stcsp_repair_result;
+
+int stcsp_engine_repair(stcsp_engine *engine, const stcsp_repair_request *request, stcsp_repair_result *result);
+
 void stcsp_engine_destroy(stcsp_engine *engine);
 
 /* Message of the last error on this engine (or of the last failed create when engine==NULL). */

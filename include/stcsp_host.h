@@ -136,6 +136,17 @@ int stcsp_automaton_generate(const stcsp_automaton *a, const uint8_t *observable
 /* count[t], t = 0 .. horizon, alone. */
 int stcsp_automaton_count_streams(const stcsp_automaton *a, int32_t horizon, int32_t flags, double *count);
 
+/* ---- repairing observed streams: the nearest solution prefix (definition: stcsp_engine.h, stcsp_engine_repair) ----
+ * The same contract written plainly, on the automaton's current flags: the checker of the device pass in the tests, and
+ * the path for automata whose flags live on the host (sharded runs, host adversarial passes, read_binary). observable:
+ * as in stcsp_automaton_bisimulation(); flags: STCSP_REPAIR_*; weights: [number of observable variables] or NULL;
+ * offsets / values: the streams, as for stcsp_automaton_check_streams() (STCSP_REPAIR_MISSING = not observed).
+ * distance, end_final, n_changed: [n_streams]; out_values: the repaired rows at the input's offsets, 0 for a stream of
+ * distance -1. STCSP_E_INVALID as there. */
+int stcsp_automaton_repair_streams(const stcsp_automaton *a, const uint8_t *observable, int32_t flags, const int32_t *weights, int64_t n_streams,
+                                   const int64_t *offsets, const int32_t *values, int32_t *distance, int32_t *out_values, uint8_t *end_final,
+                                   int32_t *n_changed);
+
 /* Merge the per-shard results of a sharded run (global state ids, see stcsp_engine.h) into
  * one result with dense ids; runs the ok-fixpoint over the union. The merged result is owned
  * by the returned handle. */

@@ -145,6 +145,39 @@ class GenerateResult(C.Structure):
 
 GEN_END_FINAL = 1  # generator(end_final=True): only the prefixes that end in a final state
 
+
+class RepairRequest(C.Structure):
+    _fields_ = [("n_streams", C.c_int64), ("offsets", C.POINTER(C.c_int64)), ("values", C.POINTER(C.c_int32)),
+                ("weights", C.POINTER(C.c_int32)), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RepairResult(C.Structure):
+    _fields_ = [("n_streams", C.c_int64), ("distance", C.POINTER(C.c_int32)), ("values", C.POINTER(C.c_int32)),
+                ("end_final", C.POINTER(C.c_uint8)), ("n_changed", C.POINTER(C.c_int32)), ("n_labels", C.c_int64), ("table_bytes", C.c_int64),
+                ("n_batches", C.c_int32), ("n_observable", C.c_int32), ("seconds", C.c_double), ("seconds_relax", C.c_double),
+                ("seconds_walk", C.c_double), ("seconds_cost", C.c_double)]
+
+
+REPAIR_END_FINAL = 1          # repair_streams(end_final=True): the repaired stream must end in a final state
+REPAIR_MISSING = -2 ** 31     # a value of a row that was not observed
+
+
+def _repair_weights(weights, n_obs):
+    """None or one non-negative int32 per observable variable -> contiguous int32 array or None."""
+    import numpy as np
+    if weights is None:
+        return None
+    w = np.asarray(weights, dtype=np.int64)
+    if w.shape != (n_obs,):
+        raise ValueError(f"weights must have one entry per observable variable ({n_obs})")
+    if (np.abs(w) >= 2 ** 31).any():
+        raise StcspError(-1, "a weight does not fit an int32")
+    return np.ascontiguousarray(w, dtype=np.int32) if n_obs else np.zeros(1, np.int32)
+
+
+def _repair_unpack(values, offsets, n_obs):
+    return [values[int(offsets[i]) * n_obs:int(offsets[i + 1]) * n_obs].reshape(-1, n_obs) for i in range(len(offsets) - 1)]
+
 F_KEEP_RAW_EDGES = 1
 F_NO_EXPORT = 2
 F_PROFILE = 4
@@ -160,6 +193,7 @@ ENGINE_SYMBOLS = [
     "stcsp_engine_propagate", "stcsp_engine_set_expand_budget", "stcsp_engine_node_bytes", "stcsp_engine_donate",
     "stcsp_engine_adopt", "stcsp_engine_expand_variant", "stcsp_engine_quotient",
     "stcsp_engine_monitor_build", "stcsp_engine_monitor_check", "stcsp_engine_generator_build", "stcsp_engine_generate",
+    "stcsp_engine_repair",
 ]
 # include/stcsp_sharded.h: the superstep loop + in-process transport (libstcsp_hip.so), the RCCL transport (libstcsp_rccl.so)
 SHARDED_SYMBOLS_HIP = ["stcsp_engine_solve_sharded", "stcsp_local_group_create", "stcsp_local_group_transport", "stcsp_local_group_destroy"]
@@ -175,6 +209,7 @@ HOST_SYMBOLS = [
     "stcsp_merge_shards", "stcsp_merged_result", "stcsp_merged_free", "stcsp_host_free",
     "stcsp_automaton_bisimulation", "stcsp_automaton_set_observable", "stcsp_automaton_quotient",
     "stcsp_automaton_check_streams", "stcsp_automaton_num_observable", "stcsp_automaton_generate", "stcsp_automaton_count_streams",
+    "stcsp_automaton_repair_streams",
 ]
 
 
@@ -252,6 +287,8 @@ def host_lib() -> C.CDLL:
         lib.stcsp_automaton_generate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_uint64, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
         lib.stcsp_automaton_count_streams.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        lib.stcsp_automaton_repair_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.stcsp_merge_shards.argtypes = [C.POINTER(C.POINTER(Result)), C.c_int, C.POINTER(C.c_void_p)]
         lib.stcsp_merged_result.argtypes = [C.c_void_p]
         lib.stcsp_merged_result.restype = C.POINTER(Result)
@@ -303,6 +340,8 @@ def bind_engine_api(lib: C.CDLL, prefix: str = "stcsp_engine") -> None:
     if hasattr(lib, f"{prefix}_generator_build"):
         g("generator_build").argtypes = [C.c_void_p, C.POINTER(GeneratorOptions), C.POINTER(GeneratorInfo)]
         g("generate").argtypes = [C.c_void_p, C.POINTER(GenerateRequest), C.POINTER(GenerateResult)]
+    if hasattr(lib, f"{prefix}_repair"):
+        g("repair").argtypes = [C.c_void_p, C.POINTER(RepairRequest), C.POINTER(RepairResult)]
     if hasattr(lib, f"{prefix}_propagate"):
         g("propagate").argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64)]
@@ -561,6 +600,29 @@ class Automaton:
             raise StcspError(rc, "generate failed: a length without a prefix or beyond the horizon, a rank that is not below count[length] < 2^53, "
                                  "or a count that overflows a double")
         return values, fin[:n], count
+
+    def repair_streams(self, streams, observable=None, weights=None, end_final=False):
+        """The nearest solution prefix of every observed stream by the host twin of Engine.repair_streams() (contract:
+        include/stcsp_engine.h, stcsp_engine_repair), on the automaton's current flags. `streams` as in pack_streams(), a
+        value REPAIR_MISSING = not observed; `observable` as in bisimulation(); `weights`: one non-negative int per observable
+        variable (None: all 1). Returns (distance int32, list of repaired streams int32 [len, n_observable], end_final uint8,
+        n_changed int32); distance -1 = no solution prefix of that length (its repaired stream is all 0)."""
+        import numpy as np
+        lib = host_lib()
+        m = self._mask(observable)
+        mp = m.ctypes.data if m is not None else None
+        n_obs = lib.stcsp_automaton_num_observable(self._h, mp)
+        values, offsets = pack_streams(streams, n_obs)
+        w = _repair_weights(weights, n_obs)
+        n = len(offsets) - 1
+        dist, nchg, fin = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
+        out = np.zeros(max(values.size, 1), np.int32)
+        rc = lib.stcsp_automaton_repair_streams(self._h, mp, REPAIR_END_FINAL if end_final else 0, w.ctypes.data if w is not None else None, n,
+                                                offsets.ctypes.data, values.ctypes.data if values.size else None, dist.ctypes.data,
+                                                out.ctypes.data, fin.ctypes.data, nchg.ctypes.data)
+        if rc != 0:
+            raise StcspError(rc, "repair_streams failed: malformed offsets, a negative weight, or (sum of the weights) x (longest stream) above 2^31 - 2")
+        return dist[:n], _repair_unpack(out[:values.size], offsets, n_obs), fin[:n], nchg[:n]
 
     def count_streams(self, horizon, end_final=False):
         """count[t], t = 0 .. horizon: the number of solution prefixes of length t (float64; exact below 2^53)."""
@@ -827,6 +889,30 @@ class EngineBase:
         values = np.ctypeslib.as_array(out.values, shape=(cells,)).copy() if cells else np.zeros(0, np.int32)
         fin = np.ctypeslib.as_array(out.end_final, shape=(n,)).copy() if n else np.zeros(0, np.uint8)
         return values.reshape(n, length, n_obs), fin
+
+    def repair_streams(self, streams, weights=None, end_final=False):
+        """The nearest solution prefix of every observed stream, on the device, after generator() (its mask; its horizon does
+        not limit the streams). `streams` as for check_streams(), a value REPAIR_MISSING = not observed; `weights`: one
+        non-negative int per observable variable (None: all 1). Returns (distance int32, list of repaired streams int32
+        [len, n_observable], end_final uint8, n_changed int32); distance -1 = no solution prefix of that length. The whole
+        RepairResult of the call is kept in self.repair_result. Contract: include/stcsp_engine.h, stcsp_engine_repair."""
+        import numpy as np
+        if getattr(self, "generator_info", None) is None:
+            raise StcspError(-6, "repair_streams() needs generator() first")
+        n_obs = self.generator_info.n_observable
+        values, offsets = pack_streams(streams, n_obs)
+        w = _repair_weights(weights, n_obs)
+        n = len(offsets) - 1
+        rq = RepairRequest(n, offsets.ctypes.data_as(C.POINTER(C.c_int64)), values.ctypes.data_as(C.POINTER(C.c_int32)) if values.size else None,
+                           w.ctypes.data_as(C.POINTER(C.c_int32)) if w is not None else None, REPAIR_END_FINAL if end_final else 0, 0)
+        out = RepairResult()
+        self._check(self._f("repair")(self._h, C.byref(rq), C.byref(out)))
+        self.repair_result = out
+        if n == 0:
+            return np.zeros(0, np.int32), [], np.zeros(0, np.uint8), np.zeros(0, np.int32)
+        rows = np.ctypeslib.as_array(out.values, shape=(values.size,)).copy() if values.size else np.zeros(0, np.int32)
+        return (np.ctypeslib.as_array(out.distance, shape=(n,)).copy(), _repair_unpack(rows, offsets, n_obs),
+                np.ctypeslib.as_array(out.end_final, shape=(n,)).copy(), np.ctypeslib.as_array(out.n_changed, shape=(n,)).copy())
 
     def automaton(self, result: Result | None = None) -> Automaton:
         return Automaton(self._model, result if result is not None else self.result)

@@ -59,6 +59,8 @@ using namespace stcsp;
 #include "monitor_host.hpp"
 #include "dev_generate.hpp"
 #include "generate_host.hpp"
+#include "dev_repair.hpp"
+#include "repair_host.hpp"
 
 using namespace stcsp::dev;
 
@@ -234,6 +236,16 @@ struct stcsp_engine {
     hipEvent_t ev_g[2] = {nullptr, nullptr};
     std::vector<int32_t> g_values;
     std::vector<uint8_t> g_fin;
+    // stream repair (dev_repair.hpp): label ids per position of the generator's CSR, valid while gen_built && rep_built
+    bool rep_built = false;
+    uint32_t rep_n_labels = 0, rep_n_long = 0, rep_total = 0, rep_wave_segment = 0;
+    DevBuf<uint32_t> d_rtab, d_rlid, d_rrep, d_rlong, d_rctl, d_rG, d_rcost;
+    DevBuf<RepStream> d_rstreams;
+    DevBuf<int32_t> d_rweights, d_rrows, d_rout, d_rdist, d_rnchg;
+    DevBuf<uint8_t> d_rfin;
+    hipEvent_t ev_r[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::vector<int32_t> r_dist, r_values, r_nchg;
+    std::vector<uint8_t> r_fin;
 
     ~stcsp_engine() {
         // the device writes several of the pinned buffers freed below (progress mirror, streamed result arrays) from
@@ -271,6 +283,8 @@ struct stcsp_engine {
             if (ev_m[i]) (void)hipEventDestroy(ev_m[i]);
         for (int i = 0; i < 2; i++)
             if (ev_g[i]) (void)hipEventDestroy(ev_g[i]);
+        for (int i = 0; i < 4; i++)
+            if (ev_r[i]) (void)hipEventDestroy(ev_r[i]);
         if (stream) (void)hipStreamDestroy(stream);
     }
 
@@ -1112,6 +1126,7 @@ struct stcsp_engine {
         post_done = false;
         mon_built = false;
         gen_built = false;
+        rep_built = false;
         ev_used = 0;
         seconds_expand_kernel = 0;
         expand_launches = 0;
@@ -2091,6 +2106,7 @@ struct stcsp_engine {
         post_done = false;
         mon_built = false;
         gen_built = false;
+        rep_built = false;
         const size_t E = exp_edges;
         const uint32_t S = n_states;
         auto width = [&](int v) { return (long long)mgr.ub[v] - (long long)mgr.lb[v] + 1; };
@@ -2539,6 +2555,7 @@ struct stcsp_engine {
         if (!go || go->horizon < 0) return fail(STCSP_E_INVALID, "generator_build: the horizon must not be negative");
         auto t0 = std::chrono::steady_clock::now();
         gen_built = false;
+        rep_built = false;
         const int N = ctx.N, H = go->horizon;
         const uint32_t E = (uint32_t)exp_edges, S = n_states;
         if ((size_t)exp_edges > 0x7fffffffull) return fail(STCSP_E_NOMEM, "edge list too large for the device generator");
@@ -2690,6 +2707,191 @@ struct stcsp_engine {
         return STCSP_OK;
     }
 
+    // Stream repair, the label ids of the generator's CSR (dev_repair.hpp): built on the first repair() after a generator_build().
+    int repair_labels() {
+        const uint32_t S = n_states;
+        uint32_t total = 0;
+        HIPCHK(hipMemcpyAsync(&total, d_goff.p + S, sizeof total, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        uint32_t slots = 64;
+        while (slots < 2 * (size_t)total && slots < 0x80000000u) slots <<= 1;
+        if (d_rtab.n < slots) HIPCHK(d_rtab.alloc(slots));
+        if (d_rlid.n < total) {
+            const size_t c = (size_t)total + total / 4 + 256;
+            HIPCHK(d_rlid.alloc(c));
+            HIPCHK(d_rrep.alloc(c));
+        }
+        if (d_rlong.n < S) HIPCHK(d_rlong.alloc((size_t)S + S / 4 + 256));
+        if (!d_rctl.p) HIPCHK(d_rctl.alloc(R_WORDS));
+        rep_wave_segment = kRepWaveSegment;
+        if (const char *v = getenv("STCSP_REPAIR_WAVE_SEGMENT")) rep_wave_segment = (uint32_t)std::max(1ll, std::min(atoll(v), 0x7fffffffll));
+        uint32_t ctl[R_WORDS] = {0};
+        HIPCHK(hipMemsetAsync(d_rctl.p, 0, sizeof ctl, stream));
+        HIPCHK(hipMemsetAsync(d_rtab.p, 0xff, (size_t)slots * sizeof(uint32_t), stream));
+        if (total) {
+            const unsigned kb = (total + 255) / 256;
+            hipLaunchKernelGGL(k_r_labels, dim3(kb), dim3(256), 0, stream, total, (const uint32_t *)d_geid.p, (const int32_t *)d_oval.p, ctx.N,
+                               (const int32_t *)d_gobs.p, gen_n_obs, d_rtab.p, slots - 1, d_rlid.p, d_rctl.p);
+            hipLaunchKernelGGL(k_r_number, dim3((slots + 255) / 256), dim3(256), 0, stream, slots, d_rtab.p, d_rrep.p, d_rctl.p);
+            hipLaunchKernelGGL(k_r_remap, dim3(kb), dim3(256), 0, stream, total, (const uint32_t *)d_rtab.p, d_rlid.p);
+        }
+        hipLaunchKernelGGL(k_r_long, dim3((S + 255) / 256), dim3(256), 0, stream, S, (const uint32_t *)d_goff.p, rep_wave_segment, d_rlong.p, d_rctl.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ctl, d_rctl.p, sizeof ctl, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (ctl[R_ERROR]) return fail(STCSP_E_INTERNAL, "repair: the label table overflowed");
+        rep_total = total;
+        rep_n_labels = ctl[R_LABELS];
+        rep_n_long = ctl[R_LONG];
+        rep_built = true;
+        return STCSP_OK;
+    }
+
+    // Stream repair: the nearest solution prefix of every stream (contract: stcsp_engine.h).
+    int repair(const stcsp_repair_request *rq, stcsp_repair_result *out) {
+        if (sharded) return fail(STCSP_E_UNSUPPORTED, "the device repair is for unsharded engines (stcsp_automaton_repair_streams on the merged automaton)");
+        if (!exp_on_device || !post_done || truncated || !gen_built)
+            return fail(STCSP_E_STATE, "repair needs generator_build() after the last postprocess()");
+        if (!stcsp::repair_request_ok(rq->n_streams, rq->offsets, rq->weights, gen_n_obs))
+            return fail(STCSP_E_INVALID, "repair: malformed stream offsets, a negative weight, or (sum of the weights) x (longest stream) above 2^31 - 2");
+        auto t0 = std::chrono::steady_clock::now();
+        const size_t n = (size_t)rq->n_streams, n_obs = (size_t)gen_n_obs;
+        const size_t steps = n ? (size_t)rq->offsets[n] : 0;
+        if (steps && n_obs && !rq->values) return fail(STCSP_E_INVALID, "repair: no step values");
+        r_dist.assign(n, -1);
+        r_values.assign(steps * n_obs, 0);
+        r_fin.assign(n, 0);
+        r_nchg.assign(n, 0);
+        memset(out, 0, sizeof *out);
+        out->n_streams = rq->n_streams;
+        out->distance = r_dist.data();
+        out->values = r_values.data();
+        out->end_final = r_fin.data();
+        out->n_changed = r_nchg.data();
+        out->n_observable = gen_n_obs;
+        if (n && gen_root_live) {
+            if (!rep_built) {
+                const int rc = repair_labels();
+                if (rc != STCSP_OK) return rc;
+            }
+            const uint32_t S = n_states, nL = rep_n_labels;
+            const int end_final = (rq->flags & STCSP_REPAIR_END_FINAL) ? 1 : 0;
+            size_t budget = 0;
+            if (const char *v = getenv("STCSP_REPAIR_BYTES")) budget = (size_t)std::max(0ll, atoll(v));
+            if (!budget) {
+                size_t free_b = 0, total_b = 0;
+                HIPCHK(hipMemGetInfo(&free_b, &total_b));
+                budget = std::max<size_t>(free_b / 2, (size_t)1 << 20);
+            }
+            auto need = [&](size_t len) { return ((len + 1) * (size_t)S + len * (size_t)nL) * sizeof(uint32_t); };
+            std::vector<int32_t> w(n_obs, 1);
+            if (rq->weights) w.assign(rq->weights, rq->weights + n_obs);
+            if (d_rweights.n < n_obs) HIPCHK(d_rweights.alloc(n_obs + 16));
+            if (n_obs) HIPCHK(hipMemcpyAsync(d_rweights.p, w.data(), n_obs * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+            for (int i = 0; i < 4; i++)
+                if (!ev_r[i]) HIPCHK(hipEventCreate(&ev_r[i]));
+            std::vector<RepStream> meta;
+            const unsigned sb = (S + 255) / 256;
+            for (size_t b0 = 0; b0 < n;) {
+                // the next batch: consecutive streams while their tables and costs fit the budget
+                size_t b1 = b0, bytes = 0, words_G = 0, steps_b = 0, longest = 0;
+                meta.clear();
+                while (b1 < n && b1 - b0 < 65535) {
+                    const size_t len = (size_t)(rq->offsets[b1 + 1] - rq->offsets[b1]);
+                    if (need(len) > budget)
+                        return fail(STCSP_E_NOMEM, "repair: stream %zu of %zu steps needs %zu bytes of tables, the budget is %zu", b1, len, need(len), budget);
+                    if (b1 > b0 && bytes + need(len) > budget) break;
+                    RepStream st;
+                    st.table = words_G;
+                    st.step = steps_b;
+                    st.len = (uint32_t)len;
+                    st.pad = 0;
+                    meta.push_back(st);
+                    bytes += need(len);
+                    words_G += (len + 1) * (size_t)S;
+                    steps_b += len;
+                    longest = std::max(longest, len);
+                    b1++;
+                }
+                const size_t nb = b1 - b0, cells = steps_b * n_obs, words_c = steps_b * (size_t)nL;
+                const size_t first = (size_t)rq->offsets[b0] * n_obs;
+                if (d_rG.n < words_G && d_rG.alloc(words_G) != hipSuccess) {
+                    (void)hipGetLastError();
+                    d_rG.release();
+                    return fail(STCSP_E_NOMEM, "repair: no room for %zu bytes of tables", words_G * sizeof(uint32_t));
+                }
+                if (d_rcost.n < words_c && d_rcost.alloc(words_c) != hipSuccess) {
+                    (void)hipGetLastError();
+                    d_rcost.release();
+                    return fail(STCSP_E_NOMEM, "repair: no room for %zu bytes of step costs", words_c * sizeof(uint32_t));
+                }
+                if (d_rstreams.n < nb) {
+                    const size_t c = nb + nb / 4 + 256;
+                    HIPCHK(d_rstreams.alloc(c));
+                    HIPCHK(d_rdist.alloc(c));
+                    HIPCHK(d_rnchg.alloc(c));
+                    HIPCHK(d_rfin.alloc(c));
+                }
+                if (d_rrows.n < cells) {
+                    const size_t c = cells + cells / 4 + 256;
+                    HIPCHK(d_rrows.alloc(c));
+                    HIPCHK(d_rout.alloc(c));
+                }
+                HIPCHK(hipMemcpyAsync(d_rstreams.p, meta.data(), nb * sizeof(RepStream), hipMemcpyHostToDevice, stream));
+                if (cells) {
+                    HIPCHK(hipMemcpyAsync(d_rrows.p, rq->values + first, cells * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+                    HIPCHK(hipMemsetAsync(d_rout.p, 0, cells * sizeof(int32_t), stream));
+                }
+                HIPCHK(hipMemsetAsync(d_rctl.p + R_ERROR, 0, sizeof(uint32_t), stream));
+                HIPCHK(hipEventRecord(ev_r[0], stream));
+                if (words_c)
+                    hipLaunchKernelGGL(k_r_cost, dim3((nL + 255) / 256, (unsigned)std::min<size_t>(steps_b, 65535)), dim3(256), 0, stream, nL,
+                                       (uint32_t)steps_b, (const uint32_t *)d_rrep.p, (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_gobs.p, gen_n_obs,
+                                       (const int32_t *)d_rweights.p, (const int32_t *)d_rrows.p, d_rcost.p);
+                HIPCHK(hipEventRecord(ev_r[1], stream));
+                hipLaunchKernelGGL(k_r_level0, dim3(sb, (unsigned)nb), dim3(256), 0, stream, S, (const RepStream *)d_rstreams.p, (const uint8_t *)d_glive.p,
+                                   (const uint8_t *)d_pfinal.p, end_final, d_rG.p);
+                for (uint32_t r = 1; r <= (uint32_t)longest; r++) {
+                    hipLaunchKernelGGL(k_r_relax, dim3(sb, (unsigned)nb), dim3(256), 0, stream, S, r, (const RepStream *)d_rstreams.p,
+                                       (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint32_t *)d_rcost.p,
+                                       rep_wave_segment, d_rG.p);
+                    if (rep_n_long)
+                        hipLaunchKernelGGL(k_r_relax_long, dim3((rep_n_long + 3) / 4, (unsigned)nb), dim3(256), 0, stream, rep_n_long,
+                                           (const uint32_t *)d_rlong.p, S, r, (const RepStream *)d_rstreams.p, (const uint32_t *)d_goff.p,
+                                           (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint32_t *)d_rcost.p, d_rG.p);
+                }
+                HIPCHK(hipEventRecord(ev_r[2], stream));
+                hipLaunchKernelGGL(k_r_walk, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, stream, (uint32_t)nb, (const RepStream *)d_rstreams.p, S,
+                                   (const uint32_t *)d_rG.p, (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p,
+                                   (const uint32_t *)d_geid.p, nL, (const uint32_t *)d_rcost.p, (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_gobs.p,
+                                   gen_n_obs, (const uint8_t *)d_pfinal.p, (const int32_t *)d_rrows.p, d_rout.p, d_rdist.p, d_rfin.p, d_rnchg.p, d_rctl.p);
+                HIPCHK(hipEventRecord(ev_r[3], stream));
+                HIPCHK(hipGetLastError());
+                uint32_t bad = 0;
+                if (cells) HIPCHK(hipMemcpyAsync(r_values.data() + first, d_rout.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipMemcpyAsync(r_dist.data() + b0, d_rdist.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipMemcpyAsync(r_nchg.data() + b0, d_rnchg.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipMemcpyAsync(r_fin.data() + b0, d_rfin.p, nb, hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipMemcpyAsync(&bad, d_rctl.p + R_ERROR, sizeof bad, hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipStreamSynchronize(stream));
+                float ms_c = 0, ms_r = 0, ms_w = 0;
+                HIPCHK(hipEventElapsedTime(&ms_c, ev_r[0], ev_r[1]));
+                HIPCHK(hipEventElapsedTime(&ms_r, ev_r[1], ev_r[2]));
+                HIPCHK(hipEventElapsedTime(&ms_w, ev_r[2], ev_r[3]));
+                out->seconds_cost += ms_c * 1e-3;
+                out->seconds_relax += ms_r * 1e-3;
+                out->seconds_walk += ms_w * 1e-3;
+                out->n_batches++;
+                out->table_bytes = std::max<int64_t>(out->table_bytes, (int64_t)bytes);
+                if (bad) return fail(STCSP_E_INTERNAL, "repair: a state with a finite cost to go and no edge that attains it");
+                b0 = b1;
+            }
+            out->n_labels = nL;
+        }
+        out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return STCSP_OK;
+    }
+
     // unsharded export: ok-fixpoint + compaction on the device, result arrays land in pinned memory
     int export_device(stcsp_result *res, stcsp_counters &ctr, size_t &E_out) {
         const int N = ctx.N;
@@ -2835,6 +3037,7 @@ struct stcsp_engine {
         post_done = false;
         mon_built = false;
         gen_built = false;
+        rep_built = false;
         return STCSP_OK;
     }
 
@@ -3075,6 +3278,11 @@ int stcsp_engine_generator_build(stcsp_engine *e, const stcsp_generator_options 
 int stcsp_engine_generate(stcsp_engine *e, const stcsp_generate_request *request, stcsp_generate_result *result) {
     if (!e || !request || !result) return STCSP_E_INVALID;
     return e->generate(request, result);
+}
+
+int stcsp_engine_repair(stcsp_engine *e, const stcsp_repair_request *request, stcsp_repair_result *result) {
+    if (!e || !request || !result) return STCSP_E_INVALID;
+    return e->repair(request, result);
 }
 
 void stcsp_engine_destroy(stcsp_engine *e) { delete e; }

@@ -23,6 +23,7 @@
 
 #include "generate_host.hpp"
 #include "monitor_host.hpp"
+#include "repair_host.hpp"
 #include "okfix.hpp"
 #include "stcsp_host.h"
 
@@ -1083,6 +1084,29 @@ int stcsp_automaton_count_streams(const stcsp_automaton *a, int32_t horizon, int
         std::vector<uint8_t> none((size_t)a->a.n_vars, 0);
         if (!gen.build(generator_view(a->a), none.data(), horizon, flags)) return STCSP_E_UNSUPPORTED;
         std::copy(gen.count.begin(), gen.count.end(), count);
+    } catch (const std::bad_alloc &) {
+        return STCSP_E_NOMEM;
+    }
+    return STCSP_OK;
+}
+int stcsp_automaton_repair_streams(const stcsp_automaton *a, const uint8_t *observable, int32_t flags, const int32_t *weights, int64_t n_streams,
+                                   const int64_t *offsets, const int32_t *values, int32_t *distance, int32_t *out_values, uint8_t *end_final,
+                                   int32_t *n_changed) {
+    if (!a) return STCSP_E_INVALID;
+    try {
+        stcsp::HostRepair rep;
+        const std::vector<uint8_t> mask = a->a.observable_mask(observable);
+        int n_obs = 0;
+        for (uint8_t m : mask) n_obs += m != 0;
+        if (!stcsp::repair_request_ok(n_streams, offsets, weights, n_obs)) return STCSP_E_INVALID;
+        if (n_streams > 0 && (!distance || !end_final || !n_changed)) return STCSP_E_INVALID;
+        const int64_t cells = n_streams > 0 ? offsets[n_streams] * n_obs : 0;
+        if (cells > 0 && (!values || !out_values)) return STCSP_E_INVALID;
+        rep.build(generator_view(a->a), mask.data(), weights);
+        std::fill(out_values, out_values + cells, 0);
+        for (int64_t i = 0; i < n_streams; i++)
+            rep.repair_one(values + offsets[i] * n_obs, offsets[i + 1] - offsets[i], flags, &distance[i], out_values + offsets[i] * n_obs, &end_final[i],
+                           &n_changed[i]);
     } catch (const std::bad_alloc &) {
         return STCSP_E_NOMEM;
     }

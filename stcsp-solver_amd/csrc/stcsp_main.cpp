@@ -3,7 +3,8 @@
 // same solutions.dot. The search itself runs on the MI355X engine behind the C-ABI.
 //
 //   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--check=<file>]
-//         [--sample=<N>:<L>[:<seed>] [--sample-final] [--sample-mask=all]] [--count=<L>] input.csp
+//         [--sample=<N>:<L>[:<seed>] [--sample-final] [--sample-mask=all]] [--count=<L>]
+//         [--repair=<file> [--repair-final]] input.csp
 //
 // --binary=<file> (not in the reference) additionally writes the printed automaton in the compact
 // binary form of include/stcsp_host.h.
@@ -36,6 +37,16 @@
 // the number of solution prefixes of every length. With --sample-final both take only the prefixes that end in a final state.
 // As with --check, stdout then holds these lines only, and the work is done on the device, or by the host twin where the flags
 // live on the host (--shards=N, host adversarial passes). --check, --sample and --count exclude each other.
+//
+// --repair=<file> (not in the reference) repairs observed streams: for each stream of the file, which has the format of --check=
+// and sets the mask by its first line, the nearest prefix of a solution and its distance (include/stcsp_engine.h,
+// stcsp_engine_repair; every weight 1). A token "?" is a value that was not observed. stdout holds the repaired streams in
+// exactly the format --check= reads, each one preceded by the comment line
+//     # index distance <d> len <len> n_changed <k> end_final <f>
+// (--check= skips lines that start with '#' after the first, so the output can be fed straight back into it); a stream without
+// a solution prefix of its length has distance -1 and prints that line and a blank line only. --repair-final asks for prefixes
+// that end in a final state. The work is done on the device, or by the host twin where the flags live on the host (--shards=N,
+// host adversarial passes). --repair excludes --check, --sample and --count.
 //
 // Options must be glued to their value (-k3, not -k 3): like the reference, the first argument
 // that does not start with '-' is the input file (stcsp.y:199-206).
@@ -71,20 +82,22 @@ struct Flags {
     const char *file = nullptr;
     const char *binary = nullptr;
     const char *check = nullptr;
+    const char *repair = nullptr;
+    bool repair_final = false;
     bool sample = false, sample_final = false, sample_all = false;
     long long sample_n = 0, sample_seed = 0;
     int sample_len = 0, count_len = -1;
-    bool quiet() const { return check || sample || count_len >= 0; }  // stdout holds the answers only
+    bool quiet() const { return check || repair || sample || count_len >= 0; }  // stdout holds the answers only
 };
 
-// --check=<file>: the streams of the file, columns reordered to variable order
+// --check=<file>, --repair=<file>: the streams of the file, columns reordered to variable order
 struct Streams {
     std::vector<uint8_t> mask;
     std::vector<int64_t> offsets{0};
     std::vector<int32_t> values;
 };
 
-static int read_streams(const char *path, const stcsp_problem *p, Streams &out) {
+static int read_streams(const char *path, const stcsp_problem *p, Streams &out, bool missing_ok = false) {
     FILE *fp = fopen(path, "r");
     if (!fp) {
         fprintf(stderr, "cannot read %s\n", path);
@@ -134,6 +147,7 @@ static int read_streams(const char *path, const stcsp_problem *p, Streams &out) 
             header = true;
             continue;
         }
+        if (!tok.empty() && tok[0][0] == '#') continue;  // a comment (--repair writes one per stream)
         if (tok.empty()) {  // a blank line ends the stream
             out.offsets.push_back(steps);
             continue;
@@ -146,6 +160,10 @@ static int read_streams(const char *path, const stcsp_problem *p, Streams &out) 
         const size_t base = out.values.size();
         out.values.resize(base + col_var.size());
         for (size_t k = 0; k < tok.size(); k++) {
+            if (missing_ok && tok[k] == "?") {
+                out.values[base + (size_t)col_pos[k]] = STCSP_REPAIR_MISSING;
+                continue;
+            }
             char *end = nullptr;
             const long long x = strtoll(tok[k].c_str(), &end, 10);
             if (end == tok[k].c_str() || *end || x < INT32_MIN || x > INT32_MAX) {
@@ -180,6 +198,53 @@ static int check_on_host(const Streams &st, const stcsp_automaton *a) {
     if (stcsp_automaton_check_streams(a, st.mask.data(), (int64_t)n, st.offsets.data(), st.values.data(), acc.data(), n_end.data(), fin.data(), nullptr) != STCSP_OK)
         return 1;
     print_streams(st, acc.data(), n_end.data(), fin.data());
+    return 0;
+}
+
+// --repair: the lines on stdout
+static void print_repairs(const stcsp_problem *p, const Streams &st, const int32_t *distance, const int32_t *values, const uint8_t *fin,
+                          const int32_t *n_changed) {
+    size_t n_obs = 0;
+    printf("#");
+    for (int v = 0; v < p->n_vars; v++)
+        if (st.mask[(size_t)v]) {
+            printf(" %s", p->var_names[v]);
+            n_obs++;
+        }
+    printf("\n");
+    for (size_t i = 0; i + 1 < st.offsets.size(); i++) {
+        printf("# %zu distance %d len %lld n_changed %d end_final %d\n", i, distance[i], (long long)(st.offsets[i + 1] - st.offsets[i]), n_changed[i],
+               (int)fin[i]);
+        for (int64_t t = st.offsets[i]; distance[i] >= 0 && t < st.offsets[i + 1]; t++) {
+            for (size_t k = 0; k < n_obs; k++) printf(k ? " %d" : "%d", values[(size_t)t * n_obs + k]);
+            printf("\n");
+        }
+        printf("\n");
+    }
+    fflush(stdout);
+}
+
+// --repair on the host twin: the automaton's current flags
+static int repair_on_host(const Flags &f, const stcsp_problem *p, const Streams &st, const stcsp_automaton *a) {
+    const size_t n = st.offsets.size() - 1;
+    std::vector<int32_t> distance(n + 1), n_changed(n + 1), values(st.values.size() + 1);
+    std::vector<uint8_t> fin(n + 1);
+    if (stcsp_automaton_repair_streams(a, st.mask.data(), f.repair_final ? STCSP_REPAIR_END_FINAL : 0, nullptr, (int64_t)n, st.offsets.data(),
+                                       st.values.data(), distance.data(), values.data(), fin.data(), n_changed.data()) != STCSP_OK)
+        return 1;
+    print_repairs(p, st, distance.data(), values.data(), fin.data(), n_changed.data());
+    return 0;
+}
+
+// ... and on the device, over the flags postprocess() has just left
+static int repair_on_device(const Flags &f, const stcsp_problem *p, const Streams &st, stcsp_engine *eng) {
+    stcsp_generator_options go = {st.mask.data(), 0, 0, {0, 0}};
+    stcsp_generator_info gi;
+    if (stcsp_engine_generator_build(eng, &go, &gi) != STCSP_OK) return 1;
+    stcsp_repair_request rq = {(int64_t)st.offsets.size() - 1, st.offsets.data(), st.values.data(), nullptr, f.repair_final ? STCSP_REPAIR_END_FINAL : 0, 0};
+    stcsp_repair_result rr;
+    if (stcsp_engine_repair(eng, &rq, &rr) != STCSP_OK) return 1;
+    print_repairs(p, st, rr.distance, rr.values, rr.end_final, rr.n_changed);
     return 0;
 }
 
@@ -294,6 +359,7 @@ static int run_once(const Flags &f, bool print_line, double *total) {
     const stcsp_problem *p = stcsp_model_problem(model);
     Streams streams;
     if (f.check && read_streams(f.check, p, streams)) return 1;
+    if (f.repair && read_streams(f.repair, p, streams, true)) return 1;
     FILE *info = f.quiet() ? stderr : stdout;  // --check, --sample, --count: stdout holds the answers only
     double init_time = cpu_time() - t_init;
     stcsp_options opt;
@@ -336,6 +402,10 @@ static int run_once(const Flags &f, bool print_line, double *total) {
             fprintf(stderr, "the streams could not be generated: no solution prefix of that length, or their number overflows a double\n");
             return 1;
         }
+        if (f.repair && repair_on_host(f, p, streams, a)) {
+            fprintf(stderr, "the streams could not be repaired\n");
+            return 1;
+        }
         if (f.quotient && fold(f, p, &a, nullptr, 0, 0)) {
             fprintf(stderr, "the quotient could not be built\n");
             return 1;
@@ -359,6 +429,10 @@ static int run_once(const Flags &f, bool print_line, double *total) {
             print_streams(streams, mr.accepted_len, mr.n_end, mr.end_final);
         }
         if ((f.sample || f.count_len >= 0) && generate_on_device(f, p, eng)) {
+            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
+            return 1;
+        }
+        if (f.repair && repair_on_device(f, p, streams, eng)) {
             fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
             return 1;
         }
@@ -409,6 +483,7 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
     const stcsp_problem *p = stcsp_model_problem(model);
     Streams streams;
     if (f.check && read_streams(f.check, p, streams)) return 1;
+    if (f.repair && read_streams(f.repair, p, streams, true)) return 1;
     FILE *info = f.quiet() ? stderr : stdout;  // --check, --sample, --count: stdout holds the answers only
     double init_time = cpu_time() - t_init;
     int ndev = 0;
@@ -477,6 +552,10 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
         fprintf(stderr, "the streams could not be generated: no solution prefix of that length, or their number overflows a double\n");
         return 1;
     }
+    if (f.repair && repair_on_host(f, p, streams, a)) {  // (host twin likewise)
+        fprintf(stderr, "the streams could not be repaired\n");
+        return 1;
+    }
     if (f.quotient && fold(f, p, &a, nullptr, 0, 0)) {  // (host twin: the merged automaton lives on the host)
         fprintf(stderr, "the quotient could not be built\n");
         return 1;
@@ -522,6 +601,14 @@ int main(int argc, char **argv) {
         }
         if (strncmp(a, "--check=", 8) == 0) {
             f.check = a + 8;
+            continue;
+        }
+        if (strncmp(a, "--repair=", 9) == 0) {
+            f.repair = a + 9;
+            continue;
+        }
+        if (strcmp(a, "--repair-final") == 0) {
+            f.repair_final = true;
             continue;
         }
         if (strncmp(a, "--sample=", 9) == 0) {
@@ -604,8 +691,8 @@ int main(int argc, char **argv) {
             }
         }
     }
-    if ((f.check != nullptr) + f.sample + (f.count_len >= 0) > 1) {
-        fprintf(stderr, "--check, --sample and --count exclude each other\n");
+    if ((f.check != nullptr) + (f.repair != nullptr) + f.sample + (f.count_len >= 0) > 1) {
+        fprintf(stderr, "--check, --repair, --sample and --count exclude each other\n");
         return 1;
     }
     if (!f.file) {
