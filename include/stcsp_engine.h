@@ -480,6 +480,113 @@ typedef struct stcsp_repair_result {
 
 int stcsp_engine_repair(stcsp_engine *engine, const stcsp_repair_request *request, stcsp_repair_result *result);
 
+/* ---- inferring the unobserved entries of a stream: supports, counts, draws, on the device (no reference counterpart) ----
+ * The monitor says whether a stream is a prefix of a solution, the generator gives some solution, the repair the nearest
+ * one. This says, for a PARTIALLY observed stream, what the entries that were not seen can be and how many solutions
+ * are still consistent with what was seen: the forward-backward pass over (time x automaton). Live automaton,
+ * projected label p_e, default mask and the canonical order of a state's live out-edges (full value row, ties by edge
+ * index) are exactly those of stcsp_engine_generate() / stcsp_engine_repair().
+ *
+ * Input. Streams in the repair's format (n_streams, offsets in steps, values), a value STCSP_INFER_MISSING (the same
+ * value as STCSP_REPAIR_MISSING) meaning "not observed"; flags; draws >= 0, the number of completions returned per
+ * stream; ranks[n_streams * draws] to unrank, NULL to sample with `seed`.
+ *
+ * Match. Edge e matches the row x_t iff for every observable variable v: x_t[v] == MISSING or p_e[v] == x_t[v].
+ *
+ * Weight to go, for a stream of len steps. B_0(s) = 1 on the live states (with STCSP_INFER_END_FINAL: final[s]).
+ * B_{r+1}(s) = the sum of B_r(dst(e)) over the live out-edges e of s that match step len-r-1, in canonical order:
+ * IEEE doubles, added one after the other starting from 0, no fused multiply-add, no reassociation.
+ * count[i] = B_len(root), 0 without a live root. Below 2^53 it is the exact number of live paths of len edges from the
+ * root whose every edge matches its step (and that end in a final state with END_FINAL). A count may be +inf; all
+ * terms are non-negative, so no NaN arises and "> 0" below is exact.
+ *
+ * Feasible edges. F_0 = {root} if count[i] > 0, else empty. Edge e is feasible at step t iff src(e) is in F_t, e matches
+ * x_t and B_{len-t-1}(dst(e)) > 0; F_{t+1} = the destinations of the edges feasible at t. So an edge is feasible at t
+ * exactly when some consistent path uses it there.
+ *
+ * Answer per stream i.
+ *   count[i], feasible[i] = count[i] > 0.
+ *   support       for every (step t, observable variable v) of the request, in the input's row order: the sorted, distinct
+ *                 values p_e[v] over the edges feasible at t, as CSR: support_off[total_steps * n_observable + 1] (int64)
+ *                 and support_val[] (int32). An infeasible stream has empty sets; an observed entry of a feasible stream
+ *                 has the one-element set of its value.
+ *   n_states      |F_t| for t = 0 .. len, at n_states[offsets[i] + i + t]: the number of automaton states the system can
+ *                 be in. It does not depend on the state numbering.
+ *   values        `draws` completions, draw j of stream i at index q = i * draws + j: len rows at row
+ *                 offsets[i] * draws + j * len; end_final[q]. Start at s = root. For t = 0 .. len-1, with r = len - t and
+ *                 a target tau: go over the live out-edges of s that match x_t, in canonical order, with a running sum
+ *                 that starts at 0 and adds B_{r-1}(dst) per edge; take the first edge after whose addition the sum
+ *                 exceeds tau (if rounding lets none exceed it, the last matching edge of non-zero weight); emit its
+ *                 projected row; s = dst.
+ *                   sample (ranks == NULL): tau = u * B_r(s), u and z = mix(mix(mix(seed + 0x9e3779b97f4a7c15) + q) + t)
+ *                     exactly as in stcsp_engine_generate(). Every consistent path is drawn with probability
+ *                     1 / count[i] while count[i] < 2^53.
+ *                   unrank: tau = (double)ranks[q] at t = 0; after each step tau -= the running sum before the chosen
+ *                     edge. Needs count[i] < 2^53 and ranks[q] < count[i], else STCSP_E_INVALID; the ranks of an
+ *                     infeasible stream are ignored. The answer is the ranks[q]-th consistent path in lexicographic
+ *                     order of its sequence of full rows.
+ *                 The draws of an infeasible stream are rows of MISSING with end_final 0. draws > 0 with a feasible
+ *                 stream whose count is not finite: STCSP_E_UNSUPPORTED (with draws == 0 everything else is answered).
+ * Integers, sets, and doubles added in a fixed order: the device, the host twin (stcsp_automaton_infer_streams() of
+ * stcsp_host.h) and any IEEE implementation of this text agree exactly, the doubles bit for bit.
+ *
+ * Consequences. count > 0 <=> the repair's distance is 0 under all-1 weights and the same END_FINAL. Without a MISSING
+ * entry and with every variable observable, count is 0 or 1, and 1 <=> the monitor accepts the stream whole. L rows of
+ * MISSING give the generator's count[L] under the same END_FINAL. Every draw agrees with the stream on every observed
+ * entry and is accepted whole by the monitor. The draw of rank 0 is the repair's repaired stream at distance 0.
+ * Replacing a MISSING entry by a value of its support keeps count > 0, any other value makes it 0, and the counts of the
+ * streams so specialised sum to count[i], exactly below 2^53.
+ *
+ * infer() needs a valid stcsp_engine_generator_build() on the engine and uses its mask, live set and CSR; the generator's
+ * horizon does not limit len and its STCSP_GEN_END_FINAL is not inherited. Without one, before postprocess() or after a
+ * truncated solve: STCSP_E_STATE; on sharded and stepped engines STCSP_E_UNSUPPORTED; malformed offsets or draws < 0:
+ * STCSP_E_INVALID. The exact label ids of stcsp_engine_repair() are built on the first infer or repair after a
+ * generator_build() and serve both calls; the first infer adds, per observable variable, the sorted dictionary of the
+ * values the labels carry. The request is cut, in its order, into consecutive batches of at most 65,535 streams whose
+ * structures fit a byte budget: [stream][len + 1][n_states] doubles (B) and bytes (F), [step][n_labels] bytes twice
+ * (match, feasible) and the support bitmaps; by default half of the free device memory, the environment variable
+ * STCSP_INFER_BYTES sets it. STCSP_E_NOMEM only when a SINGLE stream does not fit. STCSP_REPAIR_WAVE_SEGMENT applies to
+ * the forward sweep as it does to the repair's relaxation. Results are owned by the engine until the next call on it.
+ * The call invalidates none of the generator's, monitor's or repair's structures; its own are invalidated wherever the
+ * generator's are. */
+#define STCSP_INFER_END_FINAL 1            /* count only the completions that end in a final state */
+#define STCSP_INFER_MISSING (-2147483647 - 1) /* == STCSP_REPAIR_MISSING */
+
+typedef struct stcsp_infer_request {
+    int64_t n_streams;
+    const int64_t *offsets; /* [n_streams + 1] in steps: offsets[0] == 0, not decreasing, every stream < 2^31 steps */
+    const int32_t *values;  /* [offsets[n_streams] * n_observable]                                                  */
+    const uint64_t *ranks;  /* [n_streams * draws] unrank these; NULL = sample                                      */
+    uint64_t seed;          /* sample only                                                                          */
+    int32_t flags;          /* STCSP_INFER_*                                                                        */
+    int32_t draws;          /* >= 0 completions per stream                                                          */
+} stcsp_infer_request;
+
+typedef struct stcsp_infer_result {
+    int64_t n_streams;
+    const double *count;        /* [n_streams] owned by the engine, valid until the next call on it             */
+    const uint8_t *feasible;    /* [n_streams]                                                                  */
+    const int64_t *support_off; /* [offsets[n_streams] * n_observable + 1]                                      */
+    const int32_t *support_val; /* [support_off[last]]                                                          */
+    const int32_t *n_states;    /* [offsets[n_streams] + n_streams]: |F_t| at offsets[i] + i + t                */
+    const int32_t *values;      /* [offsets[n_streams] * draws * n_observable] the draws                        */
+    const uint8_t *end_final;   /* [n_streams * draws]                                                          */
+    int64_t n_labels;           /* distinct projected labels of the live automaton                              */
+    int64_t table_bytes;        /* HBM of the largest batch: B, F, match, feasible, support bitmaps             */
+    int32_t n_batches;          /* 0 without streams or without a live root: nothing runs on the device         */
+    int32_t n_observable;
+    int32_t draws;
+    int32_t reserved;
+    double seconds;             /* wall time from the host input to the host output                             */
+    double seconds_match;       /* HIP-event times, all batches: the match kernel                               */
+    double seconds_backward;    /* level 0, the backward levels and the counts                                  */
+    double seconds_forward;     /* the forward levels and |F_t|                                                 */
+    double seconds_support;     /* the support bitmaps                                                          */
+    double seconds_walk;        /* the draws                                                                    */
+} stcsp_infer_result;
+
+int stcsp_engine_infer(stcsp_engine *engine, const stcsp_infer_request *request, stcsp_infer_result *result);
+
 void stcsp_engine_destroy(stcsp_engine *engine);
 
 /* Message of the last error on this engine (or of the last failed create when engine==NULL). */

@@ -147,6 +147,19 @@ int stcsp_automaton_repair_streams(const stcsp_automaton *a, const uint8_t *obse
                                    const int64_t *offsets, const int32_t *values, int32_t *distance, int32_t *out_values, uint8_t *end_final,
                                    int32_t *n_changed);
 
+/* ---- inferring the unobserved entries of a stream (definition: stcsp_engine.h, stcsp_engine_infer) ----
+ * The same contract written plainly, on the automaton's current flags: the checker of the device pass in the tests, and
+ * the path for automata whose flags live on the host (sharded runs, host adversarial passes, read_binary). observable:
+ * as in stcsp_automaton_bisimulation(); flags: STCSP_INFER_*; offsets / values: the streams (STCSP_INFER_MISSING = not
+ * observed); draws >= 0; ranks: [n_streams * draws] to unrank, NULL to sample with `seed`. count: [n_streams];
+ * support_off: [offsets[n_streams] * (number of observable variables) + 1]; *support_val receives the support values in
+ * one block the caller releases with stcsp_host_free(); n_states: [offsets[n_streams] + n_streams]; draw_values:
+ * [offsets[n_streams] * draws * (number of observable variables)]; end_final: [n_streams * draws]. STCSP_E_INVALID and
+ * STCSP_E_UNSUPPORTED as there; the outputs of the streams before the refused one are then filled. */
+int stcsp_automaton_infer_streams(const stcsp_automaton *a, const uint8_t *observable, int32_t flags, int64_t n_streams, const int64_t *offsets,
+                                  const int32_t *values, int32_t draws, const uint64_t *ranks, uint64_t seed, double *count, int64_t *support_off,
+                                  int32_t **support_val, int32_t *n_states, int32_t *draw_values, uint8_t *end_final);
+
 /* Merge the per-shard results of a sharded run (global state ids, see stcsp_engine.h) into
  * one result with dense ids; runs the ok-fixpoint over the union. The merged result is owned
  * by the returned handle. */

@@ -178,6 +178,52 @@ def _repair_weights(weights, n_obs):
 def _repair_unpack(values, offsets, n_obs):
     return [values[int(offsets[i]) * n_obs:int(offsets[i + 1]) * n_obs].reshape(-1, n_obs) for i in range(len(offsets) - 1)]
 
+
+
+class InferRequest(C.Structure):
+    _fields_ = [("n_streams", C.c_int64), ("offsets", C.POINTER(C.c_int64)), ("values", C.POINTER(C.c_int32)),
+                ("ranks", C.POINTER(C.c_uint64)), ("seed", C.c_uint64), ("flags", C.c_int32), ("draws", C.c_int32)]
+
+
+class InferResult(C.Structure):
+    _fields_ = [("n_streams", C.c_int64), ("count", C.POINTER(C.c_double)), ("feasible", C.POINTER(C.c_uint8)),
+                ("support_off", C.POINTER(C.c_int64)), ("support_val", C.POINTER(C.c_int32)), ("n_states", C.POINTER(C.c_int32)),
+                ("values", C.POINTER(C.c_int32)), ("end_final", C.POINTER(C.c_uint8)), ("n_labels", C.c_int64), ("table_bytes", C.c_int64),
+                ("n_batches", C.c_int32), ("n_observable", C.c_int32), ("draws", C.c_int32), ("reserved", C.c_int32),
+                ("seconds", C.c_double), ("seconds_match", C.c_double), ("seconds_backward", C.c_double), ("seconds_forward", C.c_double),
+                ("seconds_support", C.c_double), ("seconds_walk", C.c_double)]
+
+
+INFER_END_FINAL = 1           # infer_streams(end_final=True): only the completions that end in a final state
+INFER_MISSING = -2 ** 31      # a value of a row that was not observed (== REPAIR_MISSING)
+
+
+def _infer_ranks(ranks, n, draws):
+    """None or [n][draws] ranks -> contiguous uint64 array or None."""
+    import numpy as np
+    if ranks is None:
+        return None
+    rk = np.ascontiguousarray(ranks, dtype=np.uint64).reshape(-1)
+    if rk.size != n * draws:
+        raise ValueError("ranks must have `draws` entries per stream")
+    return rk if rk.size else np.zeros(1, np.uint64)
+
+
+def _infer_unpack(count, soff, sval, nst, dvals, dfin, offsets, n_obs, draws):
+    """The flat outputs of an infer call -> (count float64 [n], supports, n_states, draws, end_final): per stream a
+    [len][n_obs] list of lists of ints, an int32 array [len + 1], an int32 array [draws, len, n_obs], a uint8 array [draws]."""
+    n = len(offsets) - 1
+    soff = soff.tolist()
+    sval = sval.tolist()
+    supports, n_states, out, fin = [], [], [], []
+    for i in range(n):
+        a, b = int(offsets[i]), int(offsets[i + 1])
+        supports.append([[sval[soff[t * n_obs + v]:soff[t * n_obs + v + 1]] for v in range(n_obs)] for t in range(a, b)])
+        n_states.append(nst[a + i:b + i + 1].copy())
+        out.append(dvals[a * draws * n_obs:b * draws * n_obs].reshape(draws, b - a, n_obs).copy())
+        fin.append(dfin[i * draws:(i + 1) * draws].copy())
+    return count, supports, n_states, out, fin
+
 F_KEEP_RAW_EDGES = 1
 F_NO_EXPORT = 2
 F_PROFILE = 4
@@ -193,7 +239,7 @@ ENGINE_SYMBOLS = [
     "stcsp_engine_propagate", "stcsp_engine_set_expand_budget", "stcsp_engine_node_bytes", "stcsp_engine_donate",
     "stcsp_engine_adopt", "stcsp_engine_expand_variant", "stcsp_engine_quotient",
     "stcsp_engine_monitor_build", "stcsp_engine_monitor_check", "stcsp_engine_generator_build", "stcsp_engine_generate",
-    "stcsp_engine_repair",
+    "stcsp_engine_repair", "stcsp_engine_infer",
 ]
 # include/stcsp_sharded.h: the superstep loop + in-process transport (libstcsp_hip.so), the RCCL transport (libstcsp_rccl.so)
 SHARDED_SYMBOLS_HIP = ["stcsp_engine_solve_sharded", "stcsp_local_group_create", "stcsp_local_group_transport", "stcsp_local_group_destroy"]
@@ -209,7 +255,7 @@ HOST_SYMBOLS = [
     "stcsp_merge_shards", "stcsp_merged_result", "stcsp_merged_free", "stcsp_host_free",
     "stcsp_automaton_bisimulation", "stcsp_automaton_set_observable", "stcsp_automaton_quotient",
     "stcsp_automaton_check_streams", "stcsp_automaton_num_observable", "stcsp_automaton_generate", "stcsp_automaton_count_streams",
-    "stcsp_automaton_repair_streams",
+    "stcsp_automaton_repair_streams", "stcsp_automaton_infer_streams",
 ]
 
 
@@ -289,6 +335,8 @@ def host_lib() -> C.CDLL:
         lib.stcsp_automaton_count_streams.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         lib.stcsp_automaton_repair_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.stcsp_automaton_infer_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                      C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]
         lib.stcsp_merge_shards.argtypes = [C.POINTER(C.POINTER(Result)), C.c_int, C.POINTER(C.c_void_p)]
         lib.stcsp_merged_result.argtypes = [C.c_void_p]
         lib.stcsp_merged_result.restype = C.POINTER(Result)
@@ -342,6 +390,8 @@ def bind_engine_api(lib: C.CDLL, prefix: str = "stcsp_engine") -> None:
         g("generate").argtypes = [C.c_void_p, C.POINTER(GenerateRequest), C.POINTER(GenerateResult)]
     if hasattr(lib, f"{prefix}_repair"):
         g("repair").argtypes = [C.c_void_p, C.POINTER(RepairRequest), C.POINTER(RepairResult)]
+    if hasattr(lib, f"{prefix}_infer"):
+        g("infer").argtypes = [C.c_void_p, C.POINTER(InferRequest), C.POINTER(InferResult)]
     if hasattr(lib, f"{prefix}_propagate"):
         g("propagate").argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64)]
@@ -623,6 +673,40 @@ class Automaton:
         if rc != 0:
             raise StcspError(rc, "repair_streams failed: malformed offsets, a negative weight, or (sum of the weights) x (longest stream) above 2^31 - 2")
         return dist[:n], _repair_unpack(out[:values.size], offsets, n_obs), fin[:n], nchg[:n]
+
+    def infer_streams(self, streams, observable=None, end_final=False, draws=0, seed=0, ranks=None):
+        """What the unobserved entries of partially observed streams can be, by the host twin of Engine.infer_streams()
+        (contract: include/stcsp_engine.h, stcsp_engine_infer), on the automaton's current flags. `streams` as in
+        pack_streams(), a value INFER_MISSING = not observed; `observable` as in bisimulation(); `draws` completions per
+        stream, sampled with `seed` or, with `ranks` ([n][draws]), unranked. Returns (count float64 [n], supports, n_states,
+        draws, end_final): per stream the supports as a [len][n_observable] list of sorted lists of ints, |F_t| as int32
+        [len + 1], the draws as int32 [draws, len, n_observable] and their end_final as uint8 [draws]."""
+        import numpy as np
+        lib = host_lib()
+        m = self._mask(observable)
+        mp = m.ctypes.data if m is not None else None
+        n_obs = lib.stcsp_automaton_num_observable(self._h, mp)
+        values, offsets = pack_streams(streams, n_obs)
+        n = len(offsets) - 1
+        steps = max(int(offsets[n]), 0) if n else 0
+        rk = _infer_ranks(ranks, n, draws)
+        count = np.zeros(max(n, 1), np.float64)
+        soff = np.zeros(steps * n_obs + 1, np.int64)
+        nst = np.zeros(steps + n + 1, np.int32)
+        dvals = np.zeros(max(steps * max(draws, 0) * n_obs, 1), np.int32)
+        dfin = np.zeros(max(n * max(draws, 0), 1), np.uint8)
+        sval = C.c_void_p()
+        rc = lib.stcsp_automaton_infer_streams(self._h, mp, INFER_END_FINAL if end_final else 0, n, offsets.ctypes.data,
+                                               values.ctypes.data if values.size else None, draws, rk.ctypes.data if rk is not None else None,
+                                               seed, count.ctypes.data, soff.ctypes.data, C.byref(sval), nst.ctypes.data, dvals.ctypes.data,
+                                               dfin.ctypes.data)
+        if rc != 0:
+            raise StcspError(rc, "infer_streams failed: malformed offsets, a negative number of draws, a rank that is not below its stream's "
+                                 "count < 2^53, or draws from a count that overflows a double")
+        total = int(soff[-1])
+        vals = np.ctypeslib.as_array(C.cast(sval, C.POINTER(C.c_int32)), shape=(max(total, 1),))[:total].copy()
+        lib.stcsp_host_free(sval)
+        return _infer_unpack(count[:n], soff, vals, nst, dvals, dfin, offsets, n_obs, max(draws, 0))
 
     def count_streams(self, horizon, end_final=False):
         """count[t], t = 0 .. horizon: the number of solution prefixes of length t (float64; exact below 2^53)."""
@@ -913,6 +997,33 @@ class EngineBase:
         rows = np.ctypeslib.as_array(out.values, shape=(values.size,)).copy() if values.size else np.zeros(0, np.int32)
         return (np.ctypeslib.as_array(out.distance, shape=(n,)).copy(), _repair_unpack(rows, offsets, n_obs),
                 np.ctypeslib.as_array(out.end_final, shape=(n,)).copy(), np.ctypeslib.as_array(out.n_changed, shape=(n,)).copy())
+
+    def infer_streams(self, streams, end_final=False, draws=0, seed=0, ranks=None):
+        """What the unobserved entries of partially observed streams can be, on the device, after generator() (its mask; its
+        horizon does not limit the streams). `streams` as for check_streams(), a value INFER_MISSING = not observed; `draws`
+        completions per stream, sampled with `seed` or, with `ranks` ([n][draws]), unranked. Returns (count float64 [n],
+        supports, n_states, draws, end_final) as Automaton.infer_streams() does; the whole InferResult of the call is kept in
+        self.infer_result. Contract: include/stcsp_engine.h, stcsp_engine_infer."""
+        import numpy as np
+        if getattr(self, "generator_info", None) is None:
+            raise StcspError(-6, "infer_streams() needs generator() first")
+        n_obs = self.generator_info.n_observable
+        values, offsets = pack_streams(streams, n_obs)
+        n = len(offsets) - 1
+        steps = max(int(offsets[n]), 0) if n else 0
+        rk = _infer_ranks(ranks, n, draws)
+        rq = InferRequest(n, offsets.ctypes.data_as(C.POINTER(C.c_int64)), values.ctypes.data_as(C.POINTER(C.c_int32)) if values.size else None,
+                          rk.ctypes.data_as(C.POINTER(C.c_uint64)) if rk is not None else None, seed, INFER_END_FINAL if end_final else 0, draws)
+        out = InferResult()
+        self._check(self._f("infer")(self._h, C.byref(rq), C.byref(out)))
+        self.infer_result = out
+
+        def arr(ptr, size, dtype):
+            return np.ctypeslib.as_array(ptr, shape=(size,)).copy() if size else np.zeros(0, dtype)
+
+        soff = arr(out.support_off, steps * n_obs + 1, np.int64)
+        return _infer_unpack(arr(out.count, n, np.float64), soff, arr(out.support_val, int(soff[-1]), np.int32), arr(out.n_states, steps + n, np.int32),
+                             arr(out.values, steps * draws * n_obs, np.int32), arr(out.end_final, n * draws, np.uint8), offsets, n_obs, draws)
 
     def automaton(self, result: Result | None = None) -> Automaton:
         return Automaton(self._model, result if result is not None else self.result)

@@ -60,7 +60,9 @@ using namespace stcsp;
 #include "dev_generate.hpp"
 #include "generate_host.hpp"
 #include "dev_repair.hpp"
+#include "dev_infer.hpp"
 #include "repair_host.hpp"
+#include "infer_host.hpp"
 
 using namespace stcsp::dev;
 
@@ -246,6 +248,23 @@ struct stcsp_engine {
     hipEvent_t ev_r[4] = {nullptr, nullptr, nullptr, nullptr};
     std::vector<int32_t> r_dist, r_values, r_nchg;
     std::vector<uint8_t> r_fin;
+    // stream inference (dev_infer.hpp): the value dictionaries of the labels, valid while gen_built && rep_built && inf_built
+    bool inf_built = false;
+    uint32_t inf_words = 0;                      // bitmap words per step: the sum over the variables
+    std::vector<std::vector<int32_t>> inf_dict;  // [n_obs] the sorted distinct values the labels carry
+    std::vector<uint32_t> inf_word_off;          // [n_obs] first bitmap word of a variable
+    DevBuf<uint32_t> d_ividx, d_iwoff, d_ibits, d_ictl;
+    DevBuf<InfStream> d_istreams;
+    DevBuf<double> d_iB, d_icount;
+    DevBuf<uint8_t> d_iF, d_imatch, d_ifeas, d_ifin;
+    DevBuf<int32_t> d_irows, d_iout, d_instates, d_ilabrows;
+    DevBuf<unsigned long long> d_iranks;
+    hipEvent_t ev_i[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    std::vector<double> i_count;
+    std::vector<uint8_t> i_feas, i_fin;
+    std::vector<int64_t> i_soff;
+    std::vector<int32_t> i_sval, i_nstates, i_values;
+    std::vector<uint32_t> i_bits;
 
     ~stcsp_engine() {
         // the device writes several of the pinned buffers freed below (progress mirror, streamed result arrays) from
@@ -285,6 +304,8 @@ struct stcsp_engine {
             if (ev_g[i]) (void)hipEventDestroy(ev_g[i]);
         for (int i = 0; i < 4; i++)
             if (ev_r[i]) (void)hipEventDestroy(ev_r[i]);
+        for (int i = 0; i < 7; i++)
+            if (ev_i[i]) (void)hipEventDestroy(ev_i[i]);
         if (stream) (void)hipStreamDestroy(stream);
     }
 
@@ -1127,6 +1148,7 @@ struct stcsp_engine {
         mon_built = false;
         gen_built = false;
         rep_built = false;
+        inf_built = false;
         ev_used = 0;
         seconds_expand_kernel = 0;
         expand_launches = 0;
@@ -2107,6 +2129,7 @@ struct stcsp_engine {
         mon_built = false;
         gen_built = false;
         rep_built = false;
+        inf_built = false;
         const size_t E = exp_edges;
         const uint32_t S = n_states;
         auto width = [&](int v) { return (long long)mgr.ub[v] - (long long)mgr.lb[v] + 1; };
@@ -2556,6 +2579,7 @@ struct stcsp_engine {
         auto t0 = std::chrono::steady_clock::now();
         gen_built = false;
         rep_built = false;
+        inf_built = false;
         const int N = ctx.N, H = go->horizon;
         const uint32_t E = (uint32_t)exp_edges, S = n_states;
         if ((size_t)exp_edges > 0x7fffffffull) return fail(STCSP_E_NOMEM, "edge list too large for the device generator");
@@ -2892,6 +2916,256 @@ struct stcsp_engine {
         return STCSP_OK;
     }
 
+    // Stream inference, the value dictionaries (dev_infer.hpp): built on the first infer() after a generator_build(), over
+    // the label representatives of repair_labels(). Sized by what the labels carry, not by the variables' bounds.
+    int infer_dictionaries() {
+        const size_t nL = rep_n_labels, n_obs = (size_t)gen_n_obs, cells = nL * n_obs;
+        std::vector<int32_t> rows(cells);
+        if (cells) {
+            if (d_ilabrows.n < cells) HIPCHK(d_ilabrows.alloc(cells + cells / 4 + 256));
+            hipLaunchKernelGGL(k_i_rows, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, (uint32_t)nL, (const uint32_t *)d_rrep.p,
+                               (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_gobs.p, gen_n_obs, d_ilabrows.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(rows.data(), d_ilabrows.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+        }
+        inf_dict.assign(n_obs, std::vector<int32_t>());
+        inf_word_off.assign(n_obs, 0);
+        std::vector<uint32_t> vidx(cells);
+        size_t words = 0;
+        for (size_t v = 0; v < n_obs; v++) {
+            std::vector<int32_t> &d = inf_dict[v];
+            d.resize(nL);
+            for (size_t l = 0; l < nL; l++) d[l] = rows[l * n_obs + v];
+            std::sort(d.begin(), d.end());
+            d.erase(std::unique(d.begin(), d.end()), d.end());
+            for (size_t l = 0; l < nL; l++) vidx[l * n_obs + v] = (uint32_t)(std::lower_bound(d.begin(), d.end(), rows[l * n_obs + v]) - d.begin());
+            inf_word_off[v] = (uint32_t)words;
+            words += (d.size() + 31) / 32;
+        }
+        if (words > 0x7fffffffull) return fail(STCSP_E_NOMEM, "infer: the support bitmaps of one step are too large");
+        inf_words = (uint32_t)words;
+        if (d_ividx.n < cells) HIPCHK(d_ividx.alloc(cells + cells / 4 + 256));
+        if (d_iwoff.n < n_obs) HIPCHK(d_iwoff.alloc(n_obs + 16));
+        if (cells) HIPCHK(hipMemcpyAsync(d_ividx.p, vidx.data(), cells * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        if (n_obs) HIPCHK(hipMemcpyAsync(d_iwoff.p, inf_word_off.data(), n_obs * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));  // (vidx is a local)
+        inf_built = true;
+        return STCSP_OK;
+    }
+
+    // Stream inference: supports, counts and draws of partially observed streams (contract: stcsp_engine.h).
+    int infer(const stcsp_infer_request *rq, stcsp_infer_result *out) {
+        if (sharded) return fail(STCSP_E_UNSUPPORTED, "the device inference is for unsharded engines (stcsp_automaton_infer_streams on the merged automaton)");
+        if (!exp_on_device || !post_done || truncated || !gen_built)
+            return fail(STCSP_E_STATE, "infer needs generator_build() after the last postprocess()");
+        if (!stcsp::infer_request_ok(rq->n_streams, rq->offsets, rq->draws)) return fail(STCSP_E_INVALID, "infer: malformed stream offsets or a negative number of draws");
+        auto t0 = std::chrono::steady_clock::now();
+        const size_t n = (size_t)rq->n_streams, n_obs = (size_t)gen_n_obs, draws = (size_t)rq->draws;
+        const size_t steps = n ? (size_t)rq->offsets[n] : 0;
+        if (steps && n_obs && !rq->values) return fail(STCSP_E_INVALID, "infer: no step values");
+        i_count.assign(n, 0.0);
+        i_feas.assign(n, 0);
+        i_soff.assign(steps * n_obs + 1, 0);
+        i_sval.clear();
+        i_nstates.assign(steps + n, 0);
+        i_values.assign(steps * draws * n_obs, STCSP_INFER_MISSING);
+        i_fin.assign(n * draws, 0);
+        memset(out, 0, sizeof *out);
+        out->n_streams = rq->n_streams;
+        out->n_observable = gen_n_obs;
+        out->draws = rq->draws;
+        auto publish = [&]() {  // (the vectors may have grown)
+            out->count = i_count.data();
+            out->feasible = i_feas.data();
+            out->support_off = i_soff.data();
+            out->support_val = i_sval.data();
+            out->n_states = i_nstates.data();
+            out->values = i_values.data();
+            out->end_final = i_fin.data();
+        };
+        publish();
+        if (n && gen_root_live) {
+            if (!rep_built) {
+                const int rc = repair_labels();
+                if (rc != STCSP_OK) return rc;
+            }
+            if (!inf_built) {
+                const int rc = infer_dictionaries();
+                if (rc != STCSP_OK) return rc;
+            }
+            const uint32_t S = n_states, nL = rep_n_labels, W = inf_words;
+            const int end_final = (rq->flags & STCSP_INFER_END_FINAL) ? 1 : 0;
+            size_t budget = 0;
+            if (const char *v = getenv("STCSP_INFER_BYTES")) budget = (size_t)std::max(0ll, atoll(v));
+            if (!budget) {
+                size_t free_b = 0, total_b = 0;
+                HIPCHK(hipMemGetInfo(&free_b, &total_b));
+                budget = std::max<size_t>(free_b / 2, (size_t)1 << 20);
+            }
+            auto need = [&](size_t len) { return (len + 1) * (size_t)S * (sizeof(double) + 1) + len * ((size_t)nL * 2 + (size_t)W * sizeof(uint32_t)); };
+            if (!d_ictl.p) HIPCHK(d_ictl.alloc(I_WORDS));
+            for (int i = 0; i < 7; i++)
+                if (!ev_i[i]) HIPCHK(hipEventCreate(&ev_i[i]));
+            std::vector<InfStream> meta;
+            const unsigned sb = (S + 255) / 256;
+            for (size_t b0 = 0; b0 < n;) {
+                // the next batch: consecutive streams while their structures fit the budget
+                size_t b1 = b0, bytes = 0, entries = 0, steps_b = 0, longest = 0;
+                meta.clear();
+                while (b1 < n && b1 - b0 < 65535) {
+                    const size_t len = (size_t)(rq->offsets[b1 + 1] - rq->offsets[b1]);
+                    if (need(len) > budget)
+                        return fail(STCSP_E_NOMEM, "infer: stream %zu of %zu steps needs %zu bytes of tables, the budget is %zu", b1, len, need(len), budget);
+                    if (b1 > b0 && bytes + need(len) > budget) break;
+                    InfStream st;
+                    st.table = entries;
+                    st.step = steps_b;
+                    st.len = (uint32_t)len;
+                    st.index = (uint32_t)(b1 - b0);
+                    meta.push_back(st);
+                    bytes += need(len);
+                    entries += (len + 1) * (size_t)S;
+                    steps_b += len;
+                    longest = std::max(longest, len);
+                    b1++;
+                }
+                const size_t nb = b1 - b0, cells = steps_b * n_obs, marks = steps_b * (size_t)nL, words = steps_b * (size_t)W;
+                const size_t n_q = nb * draws, out_cells = cells * draws;
+                const size_t first_step = (size_t)rq->offsets[b0], first = first_step * n_obs;
+                if (n_q >= 0x7fffffffull) return fail(STCSP_E_NOMEM, "infer: too many draws for one batch");
+                if ((d_iB.n < entries && d_iB.alloc(entries) != hipSuccess) || (d_iF.n < entries && d_iF.alloc(entries) != hipSuccess) ||
+                    (d_imatch.n < marks && d_imatch.alloc(marks) != hipSuccess) || (d_ifeas.n < marks && d_ifeas.alloc(marks) != hipSuccess) ||
+                    (d_ibits.n < words && d_ibits.alloc(words) != hipSuccess)) {
+                    (void)hipGetLastError();
+                    d_iB.release();
+                    d_iF.release();
+                    d_imatch.release();
+                    d_ifeas.release();
+                    d_ibits.release();
+                    return fail(STCSP_E_NOMEM, "infer: no room for %zu bytes of tables", bytes);
+                }
+                if (d_istreams.n < nb) {
+                    const size_t c = nb + nb / 4 + 256;
+                    HIPCHK(d_istreams.alloc(c));
+                    HIPCHK(d_icount.alloc(c));
+                }
+                if (d_irows.n < cells) HIPCHK(d_irows.alloc(cells + cells / 4 + 256));
+                if (d_instates.n < steps_b + nb) HIPCHK(d_instates.alloc(steps_b + nb + (steps_b + nb) / 4 + 256));
+                if (n_q) {
+                    if (d_ifin.n < n_q) HIPCHK(d_ifin.alloc(n_q + n_q / 4 + 256));
+                    if (rq->ranks && d_iranks.n < n_q) HIPCHK(d_iranks.alloc(n_q + n_q / 4 + 256));
+                    if (d_iout.n < out_cells) HIPCHK(d_iout.alloc(out_cells + out_cells / 4 + 256));
+                }
+                HIPCHK(hipMemcpyAsync(d_istreams.p, meta.data(), nb * sizeof(InfStream), hipMemcpyHostToDevice, stream));
+                if (cells) HIPCHK(hipMemcpyAsync(d_irows.p, rq->values + first, cells * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+                HIPCHK(hipMemsetAsync(d_iF.p, 0, entries, stream));
+                if (marks) HIPCHK(hipMemsetAsync(d_ifeas.p, 0, marks, stream));
+                if (words) HIPCHK(hipMemsetAsync(d_ibits.p, 0, words * sizeof(uint32_t), stream));
+                HIPCHK(hipMemsetAsync(d_instates.p, 0, (steps_b + nb) * sizeof(int32_t), stream));
+                HIPCHK(hipMemsetAsync(d_ictl.p, 0, I_WORDS * sizeof(uint32_t), stream));
+                const unsigned step_rows = (unsigned)std::min<size_t>(std::max<size_t>(steps_b, 1), 65535);
+                HIPCHK(hipEventRecord(ev_i[0], stream));
+                if (marks)
+                    hipLaunchKernelGGL(k_i_match, dim3((nL + 255) / 256, step_rows), dim3(256), 0, stream, nL, (uint32_t)steps_b, (const uint32_t *)d_rrep.p,
+                                       (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_gobs.p, gen_n_obs, (const int32_t *)d_irows.p, d_imatch.p);
+                HIPCHK(hipEventRecord(ev_i[1], stream));
+                hipLaunchKernelGGL(k_i_level0, dim3(sb, (unsigned)nb), dim3(256), 0, stream, S, (const InfStream *)d_istreams.p, (const uint8_t *)d_glive.p,
+                                   (const uint8_t *)d_pfinal.p, end_final, d_iB.p);
+                for (uint32_t r = 1; r <= (uint32_t)longest; r++)
+                    hipLaunchKernelGGL(k_i_backward, dim3(sb, (unsigned)nb), dim3(256), 0, stream, S, r, (const InfStream *)d_istreams.p,
+                                       (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_imatch.p,
+                                       d_iB.p);
+                hipLaunchKernelGGL(k_i_root, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, stream, (uint32_t)nb, (const InfStream *)d_istreams.p, S,
+                                   (const double *)d_iB.p, d_iF.p, d_icount.p);
+                HIPCHK(hipEventRecord(ev_i[2], stream));
+                for (uint32_t t = 0; t < (uint32_t)longest; t++) {
+                    hipLaunchKernelGGL(k_i_forward, dim3(sb, (unsigned)nb), dim3(256), 0, stream, S, t, (const InfStream *)d_istreams.p,
+                                       (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_imatch.p,
+                                       (const double *)d_iB.p, rep_wave_segment, d_iF.p, d_ifeas.p);
+                    if (rep_n_long)
+                        hipLaunchKernelGGL(k_i_forward_long, dim3((rep_n_long + 3) / 4, (unsigned)nb), dim3(256), 0, stream, rep_n_long,
+                                           (const uint32_t *)d_rlong.p, S, t, (const InfStream *)d_istreams.p, (const uint32_t *)d_goff.p,
+                                           (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_imatch.p, (const double *)d_iB.p,
+                                           d_iF.p, d_ifeas.p);
+                }
+                hipLaunchKernelGGL(k_i_count, dim3(sb, (unsigned)nb), dim3(256), 0, stream, S, (const InfStream *)d_istreams.p, (const uint8_t *)d_iF.p,
+                                   d_instates.p);
+                HIPCHK(hipEventRecord(ev_i[3], stream));
+                if (marks && W)
+                    hipLaunchKernelGGL(k_i_support, dim3((nL + 255) / 256, step_rows), dim3(256), 0, stream, nL, (uint32_t)steps_b, (const uint8_t *)d_ifeas.p,
+                                       (const uint32_t *)d_ividx.p, (const uint32_t *)d_iwoff.p, gen_n_obs, W, d_ibits.p);
+                HIPCHK(hipEventRecord(ev_i[4], stream));
+                HIPCHK(hipGetLastError());
+                i_bits.resize(words);
+                HIPCHK(hipMemcpyAsync(i_count.data() + b0, d_icount.p, nb * sizeof(double), hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipMemcpyAsync(i_nstates.data() + first_step + b0, d_instates.p, (steps_b + nb) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+                if (words) HIPCHK(hipMemcpyAsync(i_bits.data(), d_ibits.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipStreamSynchronize(stream));
+                // the bitmaps -> sorted lists: bit order is value order
+                for (size_t step = 0; step < steps_b; step++)
+                    for (size_t v = 0; v < n_obs; v++) {
+                        const uint32_t *w = i_bits.data() + step * W + inf_word_off[v];
+                        const std::vector<int32_t> &d = inf_dict[v];
+                        for (size_t k = 0; k < d.size(); k++)
+                            if (w[k >> 5] >> (k & 31) & 1u) i_sval.push_back(d[k]);
+                        i_soff[(first_step + step) * n_obs + v + 1] = (int64_t)i_sval.size();
+                    }
+                for (size_t i = b0; i < b1; i++) i_feas[i] = i_count[i] > 0.0;
+                publish();
+                float ms[5] = {0, 0, 0, 0, 0};
+                if (n_q) {
+                    // the draws: the counts decide whether they can be asked for
+                    for (size_t i = b0; i < b1; i++) {
+                        const int bad = stcsp::infer_draws_ok(i_count[i], rq->draws, rq->ranks ? rq->ranks + i * draws : nullptr);
+                        if (bad == 1) return fail(STCSP_E_UNSUPPORTED, "infer: draws from stream %zu, whose count overflows a double", i);
+                        if (bad) return fail(STCSP_E_INVALID, "infer: stream %zu: a rank that is not below its count < 2^53", i);
+                    }
+                    if (rq->ranks) HIPCHK(hipMemcpyAsync(d_iranks.p, rq->ranks + b0 * draws, n_q * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+                    if (out_cells) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d_iout.p, STCSP_INFER_MISSING, out_cells, stream));
+                    HIPCHK(hipMemsetAsync(d_ifin.p, 0, n_q, stream));
+                    const dim3 grid((unsigned)((n_q + 255) / 256)), block(256);
+                    HIPCHK(hipEventRecord(ev_i[5], stream));
+                    if (rq->ranks)
+                        hipLaunchKernelGGL(k_i_walk<true>, grid, block, 0, stream, (uint32_t)n_q, (uint32_t)draws, (unsigned long long)(b0 * draws), 0ull,
+                                           (const unsigned long long *)d_iranks.p, (const InfStream *)d_istreams.p, S, (const double *)d_iB.p,
+                                           (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, (const uint32_t *)d_geid.p, nL,
+                                           (const uint8_t *)d_imatch.p, (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_gobs.p, gen_n_obs,
+                                           (const uint8_t *)d_pfinal.p, d_iout.p, d_ifin.p, d_ictl.p);
+                    else
+                        hipLaunchKernelGGL(k_i_walk<false>, grid, block, 0, stream, (uint32_t)n_q, (uint32_t)draws, (unsigned long long)(b0 * draws),
+                                           (unsigned long long)rq->seed, (const unsigned long long *)nullptr, (const InfStream *)d_istreams.p, S,
+                                           (const double *)d_iB.p, (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p,
+                                           (const uint32_t *)d_geid.p, nL, (const uint8_t *)d_imatch.p, (const int32_t *)d_oval.p, ctx.N,
+                                           (const int32_t *)d_gobs.p, gen_n_obs, (const uint8_t *)d_pfinal.p, d_iout.p, d_ifin.p, d_ictl.p);
+                    HIPCHK(hipEventRecord(ev_i[6], stream));
+                    HIPCHK(hipGetLastError());
+                    uint32_t bad = 0;
+                    if (out_cells) HIPCHK(hipMemcpyAsync(i_values.data() + first * draws, d_iout.p, out_cells * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+                    HIPCHK(hipMemcpyAsync(i_fin.data() + b0 * draws, d_ifin.p, n_q, hipMemcpyDeviceToHost, stream));
+                    HIPCHK(hipMemcpyAsync(&bad, d_ictl.p + I_ERROR, sizeof bad, hipMemcpyDeviceToHost, stream));
+                    HIPCHK(hipStreamSynchronize(stream));
+                    HIPCHK(hipEventElapsedTime(&ms[4], ev_i[5], ev_i[6]));
+                    if (bad) return fail(STCSP_E_INTERNAL, "infer: a state with weight to go and no matching edge of non-zero weight");
+                }
+                for (int k = 0; k < 4; k++) HIPCHK(hipEventElapsedTime(&ms[k], ev_i[k], ev_i[k + 1]));
+                out->seconds_match += ms[0] * 1e-3;
+                out->seconds_backward += ms[1] * 1e-3;
+                out->seconds_forward += ms[2] * 1e-3;
+                out->seconds_support += ms[3] * 1e-3;
+                out->seconds_walk += ms[4] * 1e-3;
+                out->n_batches++;
+                out->table_bytes = std::max<int64_t>(out->table_bytes, (int64_t)bytes);
+                b0 = b1;
+            }
+            out->n_labels = nL;
+        }
+        if (i_sval.empty()) i_sval.reserve(1);
+        publish();
+        out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return STCSP_OK;
+    }
+
     // unsharded export: ok-fixpoint + compaction on the device, result arrays land in pinned memory
     int export_device(stcsp_result *res, stcsp_counters &ctr, size_t &E_out) {
         const int N = ctx.N;
@@ -3038,6 +3312,7 @@ struct stcsp_engine {
         mon_built = false;
         gen_built = false;
         rep_built = false;
+        inf_built = false;
         return STCSP_OK;
     }
 
@@ -3283,6 +3558,10 @@ int stcsp_engine_generate(stcsp_engine *e, const stcsp_generate_request *request
 int stcsp_engine_repair(stcsp_engine *e, const stcsp_repair_request *request, stcsp_repair_result *result) {
     if (!e || !request || !result) return STCSP_E_INVALID;
     return e->repair(request, result);
+}
+int stcsp_engine_infer(stcsp_engine *e, const stcsp_infer_request *request, stcsp_infer_result *result) {
+    if (!e || !request || !result) return STCSP_E_INVALID;
+    return e->infer(request, result);
 }
 
 void stcsp_engine_destroy(stcsp_engine *e) { delete e; }

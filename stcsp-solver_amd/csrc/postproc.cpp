@@ -24,6 +24,7 @@
 #include "generate_host.hpp"
 #include "monitor_host.hpp"
 #include "repair_host.hpp"
+#include "infer_host.hpp"
 #include "okfix.hpp"
 #include "stcsp_host.h"
 
@@ -1107,6 +1108,57 @@ int stcsp_automaton_repair_streams(const stcsp_automaton *a, const uint8_t *obse
         for (int64_t i = 0; i < n_streams; i++)
             rep.repair_one(values + offsets[i] * n_obs, offsets[i + 1] - offsets[i], flags, &distance[i], out_values + offsets[i] * n_obs, &end_final[i],
                            &n_changed[i]);
+    } catch (const std::bad_alloc &) {
+        return STCSP_E_NOMEM;
+    }
+    return STCSP_OK;
+}
+int stcsp_automaton_infer_streams(const stcsp_automaton *a, const uint8_t *observable, int32_t flags, int64_t n_streams, const int64_t *offsets,
+                                  const int32_t *values, int32_t draws, const uint64_t *ranks, uint64_t seed, double *count, int64_t *support_off,
+                                  int32_t **support_val, int32_t *n_states, int32_t *draw_values, uint8_t *end_final) {
+    if (!a || !support_val) return STCSP_E_INVALID;
+    *support_val = nullptr;
+    try {
+        stcsp::HostInfer inf;
+        const std::vector<uint8_t> mask = a->a.observable_mask(observable);
+        int n_obs = 0;
+        for (uint8_t m : mask) n_obs += m != 0;
+        if (!stcsp::infer_request_ok(n_streams, offsets, draws) || !support_off) return STCSP_E_INVALID;
+        if (n_streams > 0 && (!count || !n_states || (draws > 0 && !end_final))) return STCSP_E_INVALID;
+        const int64_t steps = n_streams > 0 ? offsets[n_streams] : 0;
+        if (steps * n_obs > 0 && (!values || (draws > 0 && !draw_values))) return STCSP_E_INVALID;
+        inf.build(generator_view(a->a), mask.data());
+        std::vector<int32_t> all;
+        std::vector<std::vector<double>> B;
+        std::vector<std::vector<int32_t>> support;
+        support_off[0] = 0;
+        for (int64_t i = 0; i < n_streams; i++) {
+            const int64_t len = offsets[i + 1] - offsets[i];
+            const int32_t *rows = values + offsets[i] * n_obs;
+            count[i] = inf.backward(rows, len, flags, B);
+            inf.forward(rows, len, B, count[i], support, n_states + offsets[i] + i);
+            for (size_t c = 0; c < support.size(); c++) {
+                all.insert(all.end(), support[c].begin(), support[c].end());
+                support_off[(size_t)offsets[i] * n_obs + c + 1] = (int64_t)all.size();
+            }
+            const uint64_t *rk = ranks ? ranks + i * draws : nullptr;
+            const int bad = stcsp::infer_draws_ok(count[i], draws, rk);
+            if (bad) return bad == 1 ? STCSP_E_UNSUPPORTED : STCSP_E_INVALID;
+            for (int64_t j = 0; j < draws; j++) {
+                const int64_t q = i * draws + j;
+                int32_t *out = draw_values + (offsets[i] * draws + j * len) * n_obs;
+                end_final[q] = 0;
+                if (count[i] > 0.0) {
+                    if (!inf.walk(rows, len, B, seed, (uint64_t)q, rk ? &rk[j] : nullptr, out, &end_final[q])) return STCSP_E_INTERNAL;
+                } else {
+                    std::fill(out, out + len * n_obs, stcsp::kInferMissing);
+                }
+            }
+        }
+        int32_t *vals = (int32_t *)malloc(std::max<size_t>(all.size(), 1) * sizeof(int32_t));
+        if (!vals) return STCSP_E_NOMEM;
+        std::copy(all.begin(), all.end(), vals);
+        *support_val = vals;
     } catch (const std::bad_alloc &) {
         return STCSP_E_NOMEM;
     }

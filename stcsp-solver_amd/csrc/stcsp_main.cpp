@@ -4,7 +4,7 @@
 //
 //   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--check=<file>]
 //         [--sample=<N>:<L>[:<seed>] [--sample-final] [--sample-mask=all]] [--count=<L>]
-//         [--repair=<file> [--repair-final]] input.csp
+//         [--repair=<file> [--repair-final]] [--infer=<file> [--infer-final] [--infer-draws=<D>[:<seed>]]] input.csp
 //
 // --binary=<file> (not in the reference) additionally writes the printed automaton in the compact
 // binary form of include/stcsp_host.h.
@@ -48,6 +48,17 @@
 // that end in a final state. The work is done on the device, or by the host twin where the flags live on the host (--shards=N,
 // host adversarial passes). --repair excludes --check, --sample and --count.
 //
+// --infer=<file> (not in the reference) infers what the entries of partially observed streams that were not seen can be
+// (include/stcsp_engine.h, stcsp_engine_infer). The file has the format of --repair=: "?" is a value that was not observed. For
+// each stream stdout holds the comment line
+//     # index count <c> len <len> feasible <f>
+// where c is the number of solution prefixes consistent with the stream, then one comment line per step, "# {a,b,...} {...} ...":
+// for every observable variable the sorted values it can take at that step. --infer-final counts only the prefixes that end in a
+// final state. --infer-draws=<D>[:<seed>] prints, after the supports of a feasible stream, D sampled completions of it (seed 0 when
+// left out), each followed by a blank line: every line that is no stream starts with '#', so the output can be fed straight into
+// --check=. The work is done on the device for an unsharded solve, by the host twin otherwise (--shards=N, host adversarial
+// passes). --infer excludes --check, --repair, --sample and --count.
+//
 // Options must be glued to their value (-k3, not -k 3): like the reference, the first argument
 // that does not start with '-' is the input file (stcsp.y:199-206).
 #include <sys/times.h>
@@ -84,10 +95,14 @@ struct Flags {
     const char *check = nullptr;
     const char *repair = nullptr;
     bool repair_final = false;
+    const char *infer = nullptr;
+    bool infer_final = false;
+    int infer_draws = 0;
+    long long infer_seed = 0;
     bool sample = false, sample_final = false, sample_all = false;
     long long sample_n = 0, sample_seed = 0;
     int sample_len = 0, count_len = -1;
-    bool quiet() const { return check || repair || sample || count_len >= 0; }  // stdout holds the answers only
+    bool quiet() const { return check || repair || infer || sample || count_len >= 0; }  // stdout holds the answers only
 };
 
 // --check=<file>, --repair=<file>: the streams of the file, columns reordered to variable order
@@ -248,6 +263,74 @@ static int repair_on_device(const Flags &f, const stcsp_problem *p, const Stream
     return 0;
 }
 
+// --infer: the lines on stdout
+static void print_inferences(const stcsp_problem *p, const Streams &st, int draws, const double *count, const int64_t *support_off,
+                             const int32_t *support_val, const int32_t *values) {
+    size_t n_obs = 0;
+    printf("#");
+    for (int v = 0; v < p->n_vars; v++)
+        if (st.mask[(size_t)v]) {
+            printf(" %s", p->var_names[v]);
+            n_obs++;
+        }
+    printf("\n");
+    for (size_t i = 0; i + 1 < st.offsets.size(); i++) {
+        const int64_t len = st.offsets[i + 1] - st.offsets[i];
+        printf("# %zu count %.0f len %lld feasible %d\n", i, count[i], (long long)len, count[i] > 0.0 ? 1 : 0);
+        for (int64_t t = st.offsets[i]; t < st.offsets[i + 1]; t++) {
+            printf("#");
+            for (size_t k = 0; k < n_obs; k++) {
+                const int64_t b = support_off[(size_t)t * n_obs + k], e = support_off[(size_t)t * n_obs + k + 1];
+                printf(" {");
+                for (int64_t j = b; j < e; j++) printf(j > b ? ",%d" : "%d", support_val[j]);
+                printf("}");
+            }
+            printf("\n");
+        }
+        for (int j = 0; j < draws && count[i] > 0.0; j++) {
+            const int32_t *rows = values + ((size_t)st.offsets[i] * (size_t)draws + (size_t)j * (size_t)len) * n_obs;
+            for (int64_t t = 0; t < len; t++) {
+                for (size_t k = 0; k < n_obs; k++) printf(k ? " %d" : "%d", rows[(size_t)t * n_obs + k]);
+                printf("\n");
+            }
+            printf("\n");
+        }
+    }
+    fflush(stdout);
+}
+
+// --infer on the host twin: the automaton's current flags
+static int infer_on_host(const Flags &f, const stcsp_problem *p, const Streams &st, const stcsp_automaton *a) {
+    const size_t n = st.offsets.size() - 1, steps = (size_t)st.offsets[n], draws = (size_t)f.infer_draws;
+    size_t n_obs = 0;
+    for (uint8_t m : st.mask) n_obs += m != 0;
+    std::vector<double> count(n + 1);
+    std::vector<int64_t> support_off(steps * n_obs + 1);
+    std::vector<int32_t> n_states(steps + n + 1), values(steps * draws * n_obs + 1);
+    std::vector<uint8_t> fin(n * draws + 1);
+    int32_t *support_val = nullptr;
+    if (stcsp_automaton_infer_streams(a, st.mask.data(), f.infer_final ? STCSP_INFER_END_FINAL : 0, (int64_t)n, st.offsets.data(), st.values.data(),
+                                      f.infer_draws, nullptr, (uint64_t)f.infer_seed, count.data(), support_off.data(), &support_val, n_states.data(),
+                                      values.data(), fin.data()) != STCSP_OK)
+        return 1;
+    print_inferences(p, st, f.infer_draws, count.data(), support_off.data(), support_val, values.data());
+    stcsp_host_free(support_val);
+    return 0;
+}
+
+// ... and on the device, over the flags postprocess() has just left
+static int infer_on_device(const Flags &f, const stcsp_problem *p, const Streams &st, stcsp_engine *eng) {
+    stcsp_generator_options go = {st.mask.data(), 0, 0, {0, 0}};
+    stcsp_generator_info gi;
+    if (stcsp_engine_generator_build(eng, &go, &gi) != STCSP_OK) return 1;
+    stcsp_infer_request rq = {(int64_t)st.offsets.size() - 1, st.offsets.data(), st.values.data(), nullptr, (uint64_t)f.infer_seed,
+                              f.infer_final ? STCSP_INFER_END_FINAL : 0, f.infer_draws};
+    stcsp_infer_result ir;
+    if (stcsp_engine_infer(eng, &rq, &ir) != STCSP_OK) return 1;
+    print_inferences(p, st, f.infer_draws, ir.count, ir.support_off, ir.support_val, ir.values);
+    return 0;
+}
+
 // --sample / --count: the mask, and the lines on stdout
 static std::vector<uint8_t> sample_mask(const Flags &f, const stcsp_problem *p) {
     std::vector<uint8_t> mask((size_t)p->n_vars, 1);
@@ -360,6 +443,7 @@ static int run_once(const Flags &f, bool print_line, double *total) {
     Streams streams;
     if (f.check && read_streams(f.check, p, streams)) return 1;
     if (f.repair && read_streams(f.repair, p, streams, true)) return 1;
+    if (f.infer && read_streams(f.infer, p, streams, true)) return 1;
     FILE *info = f.quiet() ? stderr : stdout;  // --check, --sample, --count: stdout holds the answers only
     double init_time = cpu_time() - t_init;
     stcsp_options opt;
@@ -406,6 +490,10 @@ static int run_once(const Flags &f, bool print_line, double *total) {
             fprintf(stderr, "the streams could not be repaired\n");
             return 1;
         }
+        if (f.infer && infer_on_host(f, p, streams, a)) {
+            fprintf(stderr, "the streams could not be inferred: draws from a count that overflows a double\n");
+            return 1;
+        }
         if (f.quotient && fold(f, p, &a, nullptr, 0, 0)) {
             fprintf(stderr, "the quotient could not be built\n");
             return 1;
@@ -433,6 +521,10 @@ static int run_once(const Flags &f, bool print_line, double *total) {
             return 1;
         }
         if (f.repair && repair_on_device(f, p, streams, eng)) {
+            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
+            return 1;
+        }
+        if (f.infer && infer_on_device(f, p, streams, eng)) {
             fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
             return 1;
         }
@@ -484,6 +576,7 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
     Streams streams;
     if (f.check && read_streams(f.check, p, streams)) return 1;
     if (f.repair && read_streams(f.repair, p, streams, true)) return 1;
+    if (f.infer && read_streams(f.infer, p, streams, true)) return 1;
     FILE *info = f.quiet() ? stderr : stdout;  // --check, --sample, --count: stdout holds the answers only
     double init_time = cpu_time() - t_init;
     int ndev = 0;
@@ -556,6 +649,10 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
         fprintf(stderr, "the streams could not be repaired\n");
         return 1;
     }
+    if (f.infer && infer_on_host(f, p, streams, a)) {  // (host twin likewise)
+        fprintf(stderr, "the streams could not be inferred: draws from a count that overflows a double\n");
+        return 1;
+    }
     if (f.quotient && fold(f, p, &a, nullptr, 0, 0)) {  // (host twin: the merged automaton lives on the host)
         fprintf(stderr, "the quotient could not be built\n");
         return 1;
@@ -609,6 +706,30 @@ int main(int argc, char **argv) {
         }
         if (strcmp(a, "--repair-final") == 0) {
             f.repair_final = true;
+            continue;
+        }
+        if (strncmp(a, "--infer=", 8) == 0) {
+            f.infer = a + 8;
+            continue;
+        }
+        if (strcmp(a, "--infer-final") == 0) {
+            f.infer_final = true;
+            continue;
+        }
+        if (strncmp(a, "--infer-draws=", 14) == 0) {
+            char *end = nullptr;
+            const long d = strtol(a + 14, &end, 10);
+            bool ok = end != a + 14 && (*end == 0 || *end == ':') && d >= 0 && d <= 1000000;
+            if (ok && *end == ':') {
+                const char *q = end + 1;
+                f.infer_seed = strtoll(q, &end, 10);
+                ok = end != q && *end == 0 && f.infer_seed >= 0;
+            }
+            if (!ok) {
+                fprintf(stderr, "Invalid argument: %s\n", a);
+                return 1;
+            }
+            f.infer_draws = (int)d;
             continue;
         }
         if (strncmp(a, "--sample=", 9) == 0) {
@@ -691,8 +812,8 @@ int main(int argc, char **argv) {
             }
         }
     }
-    if ((f.check != nullptr) + (f.repair != nullptr) + f.sample + (f.count_len >= 0) > 1) {
-        fprintf(stderr, "--check, --repair, --sample and --count exclude each other\n");
+    if ((f.check != nullptr) + (f.repair != nullptr) + (f.infer != nullptr) + f.sample + (f.count_len >= 0) > 1) {
+        fprintf(stderr, "--check, --repair, --infer, --sample and --count exclude each other\n");
         return 1;
     }
     if (!f.file) {
