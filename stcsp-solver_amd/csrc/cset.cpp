@@ -718,10 +718,12 @@ void SetManager::build_entry(const HostCon &c, TableEntry &e) {
     e.words.assign((size_t)((product + 31) / 32), 0u);
     if (product > kBitmapMaxBits) {  // the device fills it in (engine.hip: k_tabulate), then store_tabulated()
         // k_tabulate's interpreter keeps its operand stack in 32 registers per thread: an expression that nests deeper
-        // stays interpreted by the wavefront revision (whose stack spills to LDS) instead of being tabulated wrongly
+        // stays interpreted by the wavefront revision (whose stack spills to LDS) instead of being tabulated wrongly. So does a
+        // constraint over more variables than k_tabulate decodes: 23 to 28 two-valued variables have a product in this band.
         std::vector<int32_t> scratch;
         int depth = 0, max_depth = 0, mask_depth = 0;
-        if (compile_expr(c.root, c.scope, tree_has_arr(c.root), scratch, depth, max_depth, mask_depth) != STCSP_OK || max_depth > kTabulateMaxStack) {
+        if (s > kTabulateMaxScope || compile_expr(c.root, c.scope, tree_has_arr(c.root), scratch, depth, max_depth, mask_depth) != STCSP_OK ||
+            max_depth > kTabulateMaxStack) {
             e = TableEntry();
             return;
         }
@@ -816,6 +818,7 @@ void SetManager::store_tabulated(const std::vector<int32_t> &key, const uint32_t
     TableEntry &e = it->second;
     std::copy(words, words + n, e.words.begin());
     e.pending = false;
+    e.from_device = true;
     long long allowed = 0;  // (bits beyond the product in the last word are zero: k_tabulate masks them)
     for (uint32_t wd : e.words) allowed += __builtin_popcount(wd);
     e.n_forbidden = product - allowed <= kFewForbidden ? (int32_t)(product - allowed) : -1;
@@ -1047,6 +1050,9 @@ int SetManager::compile(FlatProgram &out) {
                 cd.bitmap_off = -1;
                 cd.stride_off = 0;
                 cd.n_forbidden = -1;
+                if (te.bitmap && (te.pending || te.from_device)) out.n_device_tabulated++;
+                else if (te.is_small || te.bitmap) out.n_host_tabulated++;
+                else out.n_interpreted++;
                 if (te.is_small || te.bitmap) {
                     auto pl = placed.find(key);
                     if (pl == placed.end()) {

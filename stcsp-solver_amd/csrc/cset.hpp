@@ -48,6 +48,7 @@ struct TableEntry {
     ItemDesc small{};
     bool bitmap = false;          // one bit per tuple of the full initial product
     bool pending = false;         // bitmap still to be tabulated -- on the device (engine.hip k_tabulate)
+    bool from_device = false;     // ... and one the device has filled in (store_tabulated)
     std::vector<uint32_t> words;
     std::vector<int32_t> strides;
     int32_t n_forbidden = -1;
@@ -90,6 +91,9 @@ struct FlatProgram {
     int max_nsmall = 0;
     bool any_until_item = false;
     int max_scope = 0;  // the widest constraint's scope (more than kLaneScope: engine.hip runs the big-scope kernels)
+    // point constraints (with a scope, counted once per set they are in) by the evaluator that decides their tuples: eval_tree on the
+    // host (row tables and bitmaps), k_tabulate (bitmaps the device fills in), the wavefront interpreter (no table at all)
+    int n_host_tabulated = 0, n_device_tabulated = 0, n_interpreted = 0;
 };
 
 class SetManager {

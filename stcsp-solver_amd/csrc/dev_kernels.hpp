@@ -1155,16 +1155,17 @@ struct TabArgs {
     const int *arr_data;
     long long product;
     int scope_len, uses_valid;
-    int size[kMaxScope > 16 ? 16 : kMaxScope];  // (constraints over more than 16 variables are never tabulated: 2^16 < product)
-    int lb[16];
+    int size[kTabulateMaxScope];  // (cset.cpp build_entry leaves a constraint over more variables to the wavefront interpreter: a
+    int lb[kTabulateMaxScope];    // product in the device's band needs no more than 23 two-valued variables)
 };
+static_assert((kTabulateMaxScope & (kTabulateMaxScope - 1)) == 0, "k_tabulate masks scope positions with kTabulateMaxScope - 1");
 __global__ __launch_bounds__(256) void k_tabulate(TabArgs a, uint32_t *bitmap) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    int vals[16];
+    int vals[kTabulateMaxScope];
     {
         uint32_t rem = t < a.product ? (uint32_t)t : 0u;  // product <= kBitmapMaxBitsDevice = 2^28
 #pragma unroll
-        for (int j = 0; j < 16; j++)
+        for (int j = 0; j < kTabulateMaxScope; j++)
             if (j < a.scope_len) {
                 const uint32_t q = rem / (uint32_t)a.size[j];
                 vals[j] = a.lb[j] + (int)(rem - q * (uint32_t)a.size[j]);
@@ -1181,7 +1182,7 @@ __global__ __launch_bounds__(256) void k_tabulate(TabArgs a, uint32_t *bitmap) {
         if (op == OP_END) break;
         switch (op) {
             case OP_CONST: stk[sp++ & 31] = tos; tos = a.code[pc++]; break;
-            case OP_VAR: stk[sp++ & 31] = tos; tos = vals[arg & 15]; break;
+            case OP_VAR: stk[sp++ & 31] = tos; tos = vals[arg & (kTabulateMaxScope - 1)]; break;
             case OP_ARR: {
                 const int off = a.arr_off[arg], size = a.arr_off[arg + 1] - off;
                 const bool inr = (unsigned)tos < (unsigned)size;

@@ -48,6 +48,7 @@ constexpr long long kDirectTransTotalMax = 1ll << 26;  // ... and of all the tab
 constexpr long long kWideConditional = 1ll << 20;  // a conditional constraint over more tuples than this marks a program whose search is shallow and bushy (engine.hip: chain policy)
 constexpr int kBatchArity = 16;             // scope variables of an item revise_batch can take (one row of 16 lanes scans a scope)
 constexpr int kTabulateMaxStack = 32;        // operand-stack entries of k_tabulate's per-thread interpreter (deeper programs are not tabulated on the device)
+constexpr int kTabulateMaxScope = 16;        // scope variables k_tabulate decodes per tuple (TabArgs): wider constraints are not tabulated on the device
 constexpr long long kBitmapMaxBitsDevice = 1ll << 28;  // ... and the largest one at all: bigger ones up to here are tabulated on the device
 
 enum ConType : int32_t { CT_NEXT = 0, CT_POINT = 1, CT_UNTIL = 2, CT_AT = 3 };

@@ -491,7 +491,7 @@ struct stcsp_engine {
         // bitmaps too big for the host to tabulate: the device fills them in (k_tabulate), once -- the result goes
         // back into the SetManager's table cache, so later compiles place the finished words
         for (const TabulateTodo &td : prog.todo) {
-            if (td.scope.size() > 16) return fail(STCSP_E_INTERNAL, "device tabulation of a %zu-ary constraint", td.scope.size());
+            if (td.scope.size() > (size_t)kTabulateMaxScope) return fail(STCSP_E_INTERNAL, "device tabulation of a %zu-ary constraint", td.scope.size());
             TabArgs ta{};
             ta.code = d_code.p + td.code_off;
             ta.product = td.product;
@@ -623,6 +623,9 @@ struct stcsp_engine {
                 for (int cut : hot_end) fprintf(stderr, " %d", cut);
                 fprintf(stderr, "\n");
             }
+            if (getenv("STCSP_DEBUG"))
+                fprintf(stderr, "[engine] point constraints: %d host-tabulated, %d device-tabulated, %d interpreted\n", prog.n_host_tabulated,
+                        prog.n_device_tabulated, prog.n_interpreted);
             if (getenv("STCSP_DEBUG"))
                 fprintf(stderr, "[engine] %s kernel, image %d words (%s: %d words staged), per-wavefront LDS scratch %zu B (stack slots %d), LDS/workgroup %zu B, %d workgroups/CU -> grid %d\n",
                         big ? "LITE big-workgroup" : shape1 ? "LITE one-register shape" : lite ? "LITE" : prefix_complete ? "general (descriptors in LDS, tables global)" : "general", o.words, img_in_lds || big ? "in LDS" : "global", ctx.stage_words, scratch / 4, ctx.stack_slots, lds_bytes, per_cu, max_blocks);
