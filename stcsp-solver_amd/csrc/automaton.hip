@@ -1,0 +1,948 @@
+// automaton.hip -- the host side of the services on the exported automaton: post-processing, bisimulation quotient, stream monitor,
+// generator, repair and inference, with the kernels they launch. No kernel is shared with the search (engine.hip).
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "automaton.hpp"
+#include "dev_postproc.hpp"
+#include "dev_quotient.hpp"
+#include "dev_monitor.hpp"
+#include "monitor_host.hpp"
+#include "dev_generate.hpp"
+#include "generate_host.hpp"
+#include "dev_repair.hpp"
+#include "dev_infer.hpp"
+#include "repair_host.hpp"
+#include "infer_host.hpp"
+
+namespace stcsp {
+using namespace dev;
+
+// widest adversarial variable the device post-processing passes take (cover sets of kPostMaxWidth / 32 words per state)
+static constexpr long long kPostMaxWidth = 4096;
+// the columns of a label row a 0/1 mask over the variables selects
+static std::vector<int32_t> observed_columns(const uint8_t *mask, int N) {
+    std::vector<int32_t> obs;
+    for (int x = 0; x < N; x++)
+        if (mask[x]) obs.push_back(x);
+    return obs;
+}
+
+AutomatonServices::AutomatonServices() = default;
+AutomatonServices::~AutomatonServices() = default;
+
+int AutomatonServices::fail(int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    *v.err = buf;
+    return code;
+}
+
+void AutomatonServices::invalidate() {
+    post_done = live_done = mon_built = gen_built = rep_built = inf_built = false;
+    mon_host.reset();
+}
+
+// Every entry point starts here: takes the view and checks what `who` needs. host_twin: what to use on a sharded solve's merged automaton.
+int AutomatonServices::enter(const AutomatonView &view, const char *who, Need need, const char *host_twin) {
+    v = view;
+    if (v.sharded)
+        return host_twin ? fail(STCSP_E_UNSUPPORTED, "%s: the device services are for unsharded engines (%s on the merged automaton)", who, host_twin)
+                         : fail(STCSP_E_STATE, "%s: device post-processing is for unsharded engines (merge shards on the host)", who);
+    if (!v.exp_on_device) return fail(STCSP_E_STATE, "%s needs the device export of a finished solve (export first)", who);
+    if (need == NEED_EXPORT) return STCSP_OK;
+    if (!post_done) return fail(STCSP_E_STATE, "%s needs the flags of postprocess() on the last solve", who);
+    if (v.truncated) return fail(STCSP_E_STATE, "%s after a truncated solve: the open states of a partial automaton have no known language", who);
+    if (need == NEED_MONITOR && !mon_built) return fail(STCSP_E_STATE, "%s needs monitor_build() after the last postprocess()", who);
+    if (need == NEED_GENERATOR && !gen_built) return fail(STCSP_E_STATE, "%s needs generator_build() after the last postprocess()", who);
+    return STCSP_OK;
+}
+
+// The live automaton: forward reachability from a valid root over alive edges (what write_dot walks), on first need after a postprocess()
+int AutomatonServices::live_set() {
+    if (live_done) return STCSP_OK;
+    const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
+    HIPCHK(d_live.reserve(S));
+    HIPCHK(d_lctl.reserve_exact(Q_WORDS));
+    uint32_t ctl[Q_WORDS] = {0, 0, 0, 0};
+    HIPCHK(hipMemsetAsync(d_lctl.p, 0, sizeof ctl, v.stream));
+    HIPCHK(hipMemsetAsync(d_live.p, 0, S, v.stream));
+    HIPCHK(hipMemcpyAsync(d_live.p, d_pvalid.p, 1, hipMemcpyDeviceToDevice, v.stream));
+    for (int sweeps = 0; E; sweeps++) {
+        HIPCHK(hipMemsetAsync(d_lctl.p + Q_CHANGED, 0, sizeof(uint32_t), v.stream));
+        hipLaunchKernelGGL(k_q_reach, dim3((E + 255) / 256), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)d_palive.p,
+                           (const uint8_t *)d_pvalid.p, d_live.p, d_lctl.p);
+        HIPCHK(hipMemcpyAsync(ctl, d_lctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        if (!ctl[Q_CHANGED]) break;
+        if (sweeps > (int)S + 8) return fail(STCSP_E_INTERNAL, "live set: reachability did not converge");
+    }
+    live.resize(S);
+    HIPCHK(hipMemcpyAsync(live.data(), d_live.p, S, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    n_live = std::count(live.begin(), live.end(), 1);
+    root_live = S > 0 && live[0];
+    live_done = true;
+    return STCSP_OK;
+}
+
+// The bytes the tables of one batch of streams may take: the environment's, else half of the free memory, 1 MiB at least
+int AutomatonServices::table_budget(const char *env_name, size_t &budget) {
+    budget = 0;
+    if (const char *e = getenv(env_name)) budget = (size_t)std::max(0ll, atoll(e));
+    if (!budget) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        budget = std::max<size_t>(free_b / 2, (size_t)1 << 20);
+    }
+    return STCSP_OK;
+}
+
+// The next batch of a repair() or infer(): the streams from b0 on whose tables, need(len) bytes each, fit the budget together, 65535 at most
+template <typename Rec, typename NeedFn>
+int AutomatonServices::plan_batch(const char *who, const int64_t *offsets, size_t n, size_t b0, size_t budget, NeedFn need, std::vector<Rec> &meta, Batch &b) {
+    b = Batch{b0};
+    meta.clear();
+    while (b.b1 < n && b.b1 - b0 < 65535) {
+        const size_t len = (size_t)(offsets[b.b1 + 1] - offsets[b.b1]);
+        if (need(len) > budget)
+            return fail(STCSP_E_NOMEM, "%s: stream %zu of %zu steps needs %zu bytes of tables, the budget is %zu", who, b.b1, len, need(len), budget);
+        if (b.b1 > b0 && b.bytes + need(len) > budget) break;
+        meta.push_back(Rec{(unsigned long long)b.entries, (unsigned long long)b.steps, (uint32_t)len, (uint32_t)(b.b1 - b0)});
+        b.bytes += need(len);
+        b.entries += (len + 1) * (size_t)v.n_states;
+        b.steps += len;
+        b.longest = std::max(b.longest, len);
+        b.b1++;
+    }
+    return STCSP_OK;
+}
+
+// graphTraverse / adversarialTraverse / adversarialTraverse2 on the device (dev_postproc.hpp)
+int AutomatonServices::postprocess(const AutomatonView &view, const stcsp_post_options *po, stcsp_post_result *out) {
+    if (int rc = enter(view, "postprocess", NEED_EXPORT, nullptr)) return rc;
+    const int N = v.N;
+    const int a1 = po ? po->adversarial_var : -1, op = po ? po->adversarial2_op : -1, ava = po ? po->adversarial2_ava : -1;
+    if (a1 >= N || op >= N || ava >= N || a1 < -1 || op < -1 || (op >= 0 && ava < 0))
+        return fail(STCSP_E_INVALID, "postprocess: variable index out of range");
+    auto t0 = std::chrono::steady_clock::now();
+    invalidate();
+    const size_t E = v.exp_edges;
+    const uint32_t S = v.n_states;
+    auto width = [&](int x) { return (long long)v.ub[x] - (long long)v.lb[x] + 1; };
+    // cover sets of CW = ceil(width / 32) words (dev_postproc.hpp); without interval domains widths are at most 128 (create()
+    // refuses wider), with them the adversarial variables may have at most kPostMaxWidth values
+    for (int x : {a1, op, op >= 0 ? ava : -1})
+        if (x >= 0 && width(x) > kPostMaxWidth)
+            return fail(STCSP_E_UNSUPPORTED, "postprocess: variable %d has %lld values; the device adversarial passes take at most %lld (%lld cover words per state)",
+                        x, width(x), kPostMaxWidth, kPostMaxWidth / 32);
+    auto cover_w = [&](int x) { return (int)((width(x) + 31) / 32); };
+    auto last_full = [&](int x) { return width(x) % 32 == 0 ? 0xffffffffu : ((1u << (width(x) % 32)) - 1u); };
+    const int wa = op >= 0 ? (int)width(ava) : 0;
+    const int cw1 = a1 >= 0 ? cover_w(a1) : 1, cw2 = op >= 0 ? cover_w(op) : 1;
+    HIPCHK(reserve_all(S, 0, d_pvalid, d_pfinal, d_pnodeok));
+    const size_t cover_words = (size_t)S * std::max(cw1, std::max(1, wa) * cw2);
+    HIPCHK(d_pcover.reserve(cover_words));
+    HIPCHK(d_palive.reserve(E, 1));
+    HIPCHK(d_pctl.reserve_exact(4));
+    const unsigned eb = (unsigned)((E + 255) / 256), sb = (S + 255) / 256;
+    const long long *src = v.d_osrc, *dst = v.d_odst;
+    const int32_t *val = v.d_oval;
+    uint32_t *changed = d_pctl.p;
+    // one round = the kernels `body` enqueues; returns the number of rounds until nothing changed
+    auto fixpoint = [&](int &rounds, auto body) -> int {  // HIPCHK returns the error code from the enclosing lambda
+        for (rounds = 0;; rounds++) {
+            HIPCHK(hipMemsetAsync(changed, 0, sizeof(uint32_t), v.stream));
+            const int rb = body();
+            if (rb != STCSP_OK) return rb;
+            uint32_t ch = 0;
+            HIPCHK(hipMemcpyAsync(&ch, changed, sizeof ch, hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipStreamSynchronize(v.stream));
+            if (!ch) return STCSP_OK;
+            if (rounds > (int)S + 8) return fail(STCSP_E_INTERNAL, "post-processing fixpoint did not converge");
+        }
+    };
+    int rounds[3] = {0, 0, 0};
+    HIPCHK(hipMemsetAsync(d_palive.p, 1, E + 1, v.stream));
+    // graphTraverse (src/graph.cpp:357-418); the loop bound numSignVar + numUntil is the reference's
+    hipLaunchKernelGGL(k_trav_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)v.d_state_keys, v.KL, v.n_sig,
+                       v.n_sig + v.n_until, (int)(v.n_until_cons == 0), d_pvalid.p, d_pfinal.p);
+    if (E) {
+        if (int rc = fixpoint(rounds[0], [&] {
+            hipLaunchKernelGGL(k_trav_back, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, (const uint8_t *)d_palive.p, d_pvalid.p, changed);
+            return (int)STCSP_OK;
+        })) return rc;
+        hipLaunchKernelGGL(k_kill_into_invalid, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, d_palive.p, (const uint8_t *)d_pvalid.p, 1);
+    }
+    int adver1 = -1, adver2 = -1;
+    uint8_t root_valid = 0;
+    if (a1 >= 0) {  // adversarialTraverse (src/graph.cpp:304-355)
+        const uint32_t full = last_full(a1);
+        if (int rc = fixpoint(rounds[1], [&] {
+            HIPCHK(hipMemsetAsync(d_pcover.p, 0, (size_t)S * cw1 * sizeof(uint32_t), v.stream));
+            if (E)
+                hipLaunchKernelGGL(k_adv_cover, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, val, N, a1, v.lb[a1], cw1,
+                                   (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_pcover.p);
+            hipLaunchKernelGGL(k_adv_check, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)d_pcover.p, cw1, full, d_pvalid.p, changed);
+            return (int)STCSP_OK;
+        })) return rc;
+        if (E) hipLaunchKernelGGL(k_kill_into_invalid, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, d_palive.p, (const uint8_t *)d_pvalid.p, 0);
+        HIPCHK(hipMemcpyAsync(&root_valid, d_pvalid.p, 1, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        adver1 = root_valid;
+    }
+    if (op >= 0) {  // adversarialTraverse2 (src/graph.cpp:247-302)
+        const uint32_t full = last_full(op);
+        if (int rc = fixpoint(rounds[2], [&] {
+            HIPCHK(hipMemsetAsync(d_pcover.p, 0, (size_t)S * wa * cw2 * sizeof(uint32_t), v.stream));
+            if (E)
+                hipLaunchKernelGGL(k_adv2_cover, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, val, N, op, ava, v.lb[op], v.lb[ava],
+                                   wa, cw2, (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_pcover.p);
+            hipLaunchKernelGGL(k_adv2_check, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)d_pcover.p, wa, cw2, full, d_pvalid.p, d_pnodeok.p,
+                               changed);
+            if (E)
+                hipLaunchKernelGGL(k_adv2_kill, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, val, N, ava, v.lb[ava], wa, cw2, full, d_palive.p,
+                                   (const uint8_t *)d_pvalid.p, (const uint8_t *)d_pnodeok.p, (const uint32_t *)d_pcover.p);
+            return (int)STCSP_OK;
+        })) return rc;
+        HIPCHK(hipMemcpyAsync(&root_valid, d_pvalid.p, 1, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        adver2 = root_valid;
+        // the reference drops the edges into invalid states only when the root survived (graph.cpp:288-301)
+        if (root_valid && E)
+            hipLaunchKernelGGL(k_kill_into_invalid, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, d_palive.p, (const uint8_t *)d_pvalid.p, 0);
+    }
+    HIPCHK(hipGetLastError());
+    p_valid.resize(S);
+    p_final.resize(S);
+    p_alive.resize(E + 1);
+    HIPCHK(hipMemcpyAsync(p_valid.data(), d_pvalid.p, S, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(p_final.data(), d_pfinal.p, S, hipMemcpyDeviceToHost, v.stream));
+    if (E) HIPCHK(hipMemcpyAsync(p_alive.data(), d_palive.p, E, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    memset(out, 0, sizeof *out);
+    out->n_states = S;
+    out->n_edges = (int64_t)E;
+    out->state_valid = p_valid.data();
+    out->state_final = p_final.data();
+    out->edge_alive = p_alive.data();
+    out->adver1 = adver1;
+    out->adver2 = adver2;
+    for (int i = 0; i < 3; i++) out->rounds[i] = rounds[i];
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    post_done = true;
+    return STCSP_OK;
+}
+
+// Bisimulation quotient of the live automaton on the device (dev_quotient.hpp): classes of the
+// states that are valid and reachable from the root over alive edges, under the labels projected on `observable`.
+int AutomatonServices::quotient(const AutomatonView &view, const stcsp_quotient_options *qo, stcsp_quotient_result *out) {
+    if (int rc = enter(view, "quotient", NEED_FLAGS, "stcsp_automaton_bisimulation")) return rc;
+    auto t0 = std::chrono::steady_clock::now();
+    const int N = v.N;
+    const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
+    const std::vector<int32_t> obs = observed_columns(qo && qo->observable ? qo->observable : v.default_observable, N);
+    auto pow2 = [](size_t n) {
+        size_t c = 1024;
+        while (c < 2 * n) c <<= 1;
+        return c;
+    };
+    const size_t cap_e = pow2(E), cap_s = pow2(S);
+    if (cap_e > 0x80000000ull) return fail(STCSP_E_NOMEM, "edge list too large for the device quotient");
+    if (int rc = live_set()) return rc;
+    HIPCHK(reserve_all(S, 0, d_qcls[0], d_qcls[1], d_qacc[0], d_qacc[1], d_qcnt));
+    HIPCHK(reserve_all(E, 1, d_qsrc, d_qdst, d_qlid));
+    HIPCHK(d_qtab_e.reserve_exact(cap_e));
+    HIPCHK(d_qtab_s.reserve_exact(cap_s));
+    HIPCHK(d_qobs.reserve_exact((size_t)N));
+    HIPCHK(d_qctl.reserve_exact(Q_WORDS));
+    const unsigned eb = (E + 255) / 256, sb = (S + 255) / 256;
+    const uint32_t mask_e = (uint32_t)(cap_e - 1), mask_s = (uint32_t)(cap_s - 1);
+    uint32_t ctl[Q_WORDS] = {0, 0, 0, 0};
+    auto check = [&]() -> int {
+        HIPCHK(hipMemcpyAsync(ctl, d_qctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        if (ctl[Q_ERROR] & Q_ERR_TABLE_FULL) return fail(STCSP_E_INTERNAL, "quotient: a device table overflowed");
+        if (ctl[Q_ERROR]) return fail(STCSP_E_INTERNAL, "quotient: a state differs from its class representative (signature collision, flags %u)", ctl[Q_ERROR]);
+        return STCSP_OK;
+    };
+    if (!obs.empty()) HIPCHK(hipMemcpyAsync(d_qobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+    HIPCHK(hipMemsetAsync(d_qctl.p, 0, sizeof ctl, v.stream));
+    // label ids (the one sweep over the label rows) and the 12-byte edge records of the rounds
+    if (E) {
+        HIPCHK(hipMemsetAsync(d_qtab_e.p, 0xff, cap_e * sizeof(uint32_t), v.stream));
+        hipLaunchKernelGGL(k_q_labels, dim3(eb), dim3(256), 0, v.stream, E, (const long long *)v.d_osrc, (const long long *)v.d_odst,
+                           (const int32_t *)v.d_oval, N, (const int32_t *)d_qobs.p, (int)obs.size(), (const uint8_t *)d_palive.p,
+                           (const uint8_t *)d_live.p, d_qtab_e.p, mask_e, d_qsrc.p, d_qdst.p, d_qlid.p, d_qctl.p);
+    }
+    // every live state starts in class 0; a round splits the classes by (final, set of (label id, class of destination))
+    HIPCHK(hipMemsetAsync(d_qcls[0].p, 0, (size_t)S * sizeof(uint32_t), v.stream));
+    int cur = 0, rounds = 0;
+    bool dedup = true;  // until round 1 has shown that no state has two edges with one projected label
+    auto edge_sweep = [&](bool dd) -> int {
+        hipLaunchKernelGGL(k_q_state_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_pfinal.p, d_qacc[0].p, d_qacc[1].p, d_qcnt.p);
+        if (!E) return STCSP_OK;
+        if (dd) HIPCHK(hipMemsetAsync(d_qtab_e.p, 0xff, cap_e * sizeof(uint32_t), v.stream));
+        hipLaunchKernelGGL(k_q_edges, dim3(eb), dim3(256), 0, v.stream, E, (const uint32_t *)d_qsrc.p, (const uint32_t *)d_qdst.p,
+                           (const uint32_t *)d_qlid.p, (const uint32_t *)d_qcls[cur].p, (int)dd, d_qtab_e.p, mask_e, d_qacc[0].p, d_qacc[1].p,
+                           d_qcnt.p, d_qctl.p);
+        return STCSP_OK;
+    };
+    for (uint32_t prev = 0;;) {
+        rounds++;
+        HIPCHK(hipMemsetAsync(d_qctl.p, 0, 2 * sizeof(uint32_t), v.stream));  // Q_CLASSES, Q_DUPS
+        if (int rc = edge_sweep(dedup)) return rc;
+        HIPCHK(hipMemsetAsync(d_qtab_s.p, 0xff, cap_s * sizeof(uint32_t), v.stream));
+        hipLaunchKernelGGL(k_q_number, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint32_t *)d_qcls[cur].p,
+                           (const unsigned long long *)d_qacc[0].p, (const unsigned long long *)d_qacc[1].p, d_qtab_s.p, mask_s,
+                           d_qcls[1 - cur].p, d_qctl.p);
+        if (int rc = check()) return rc;
+        cur = 1 - cur;
+        if (rounds == 1 && ctl[Q_DUPS] == 0) dedup = false;
+        if (ctl[Q_CLASSES] == prev) break;
+        prev = ctl[Q_CLASSES];
+        if ((uint32_t)rounds > S + 1) return fail(STCSP_E_INTERNAL, "quotient: refinement did not converge");
+    }
+    // exact verification against the class representatives; leaves the distinct pairs per state in d_qcnt
+    if (int rc = edge_sweep(true)) return rc;
+    if (E)
+        hipLaunchKernelGGL(k_q_verify_edges, dim3(eb), dim3(256), 0, v.stream, E, (const uint32_t *)d_qsrc.p, (const uint32_t *)d_qdst.p,
+                           (const uint32_t *)d_qlid.p, (const uint32_t *)d_qcls[cur].p, (const uint32_t *)d_qtab_e.p, mask_e, d_qctl.p);
+    hipLaunchKernelGGL(k_q_verify_states, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint8_t *)d_pfinal.p,
+                       (const uint32_t *)d_qcls[cur].p, (const uint32_t *)d_qcnt.p, d_qctl.p);
+    HIPCHK(hipGetLastError());
+    q_raw.resize(S);
+    q_cnt.resize(S);
+    HIPCHK(hipMemcpyAsync(q_raw.data(), d_qcls[cur].p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(q_cnt.data(), d_qcnt.p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+    if (int rc = check()) return rc;
+    // canonical class numbers: by least member (the first state, in index order, that shows the class)
+    q_class.assign(S, -1);
+    std::vector<int32_t> number(S, -1);
+    int64_t n_classes = 0, n_class_edges = 0;
+    for (uint32_t s = 0; s < S; s++) {
+        const uint32_t r = q_raw[s];
+        if (r == kQEmpty) continue;  // (not live)
+        if (number[r] < 0) {
+            number[r] = (int32_t)n_classes++;
+            n_class_edges += q_cnt[r];
+        }
+        q_class[s] = number[r];
+    }
+    memset(out, 0, sizeof *out);
+    out->n_states = n_live;
+    out->n_classes = n_classes;
+    out->n_class_edges = n_class_edges;
+    out->state_class = q_class.data();
+    out->rounds = rounds;
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return STCSP_OK;
+}
+
+// Stream monitor, build (dev_monitor.hpp): label ids and the (state, label id) -> destinations
+// multimap of the live automaton under one mask, from the flags the last postprocess() left in HBM.
+int AutomatonServices::monitor_build(const AutomatonView &view, const stcsp_monitor_options *mo, stcsp_monitor_info *info) {
+    if (int rc = enter(view, "monitor_build", NEED_FLAGS, "stcsp_automaton_check_streams")) return rc;
+    auto t0 = std::chrono::steady_clock::now();
+    mon_built = false;
+    mon_host.reset();
+    const int N = v.N;
+    const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
+    const uint8_t *mask = mo && mo->observable ? mo->observable : v.default_observable;
+    const std::vector<int32_t> obs = observed_columns(mask, N);
+    mon_observable.assign(mask, mask + N);
+    size_t cap = 1024;
+    while (cap < 2 * (size_t)E) cap <<= 1;
+    if (cap > 0x80000000ull) return fail(STCSP_E_NOMEM, "edge list too large for the device monitor");
+    if (int rc = live_set()) return rc;
+    HIPCHK(reserve_all(E, 1, d_mdst, d_mnext));
+    HIPCHK(d_mltab.reserve_exact(cap));
+    HIPCHK(d_mhead.reserve_exact(cap));
+    HIPCHK(d_mdst0.reserve_exact(cap));
+    HIPCHK(d_mkeys.reserve_exact(cap));
+    HIPCHK(d_mobs.reserve_exact((size_t)N));
+    HIPCHK(d_mctl.reserve_exact(M_WORDS));
+    const unsigned eb = (E + 255) / 256;
+    uint32_t ctl[M_WORDS] = {0};
+    if (!obs.empty()) HIPCHK(hipMemcpyAsync(d_mobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+    HIPCHK(hipMemsetAsync(d_mctl.p, 0, sizeof ctl, v.stream));
+    if (E) {
+        HIPCHK(hipMemsetAsync(d_mltab.p, 0xff, cap * sizeof(uint32_t), v.stream));
+        HIPCHK(hipMemsetAsync(d_mhead.p, 0xff, cap * sizeof(uint32_t), v.stream));
+        HIPCHK(hipMemsetAsync(d_mkeys.p, 0xff, cap * sizeof(unsigned long long), v.stream));
+        hipLaunchKernelGGL(k_m_build, dim3(eb), dim3(256), 0, v.stream, E, (const long long *)v.d_osrc, (const long long *)v.d_odst,
+                           (const int32_t *)v.d_oval, N, (const int32_t *)d_mobs.p, (int)obs.size(), (const uint8_t *)d_palive.p,
+                           (const uint8_t *)d_live.p, d_mltab.p, d_mkeys.p, d_mhead.p, (uint32_t)(cap - 1), d_mdst.p, d_mnext.p, d_mctl.p);
+        hipLaunchKernelGGL(k_m_finish, dim3((unsigned)(cap / 256)), dim3(256), 0, v.stream, (uint32_t)cap, (const unsigned long long *)d_mkeys.p,
+                           (const uint32_t *)d_mhead.p, d_mnext.p, (const uint32_t *)d_mdst.p, d_mdst0.p, d_mctl.p);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(ctl, d_mctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    if (ctl[M_ERROR]) return fail(STCSP_E_INTERNAL, "monitor: a device table overflowed");
+    mon_n_obs = (int)obs.size();
+    mon_max_dst = (int)std::max(ctl[M_MAXDST], ctl[M_PAIRS] ? 1u : 0u);
+    mon_mask = (uint32_t)(cap - 1);
+    mon_built = true;
+    memset(info, 0, sizeof *info);
+    info->n_states = n_live;
+    info->n_edges = ctl[M_EDGES];
+    info->n_labels = ctl[M_LABELS];
+    info->n_pairs = ctl[M_PAIRS];
+    info->table_bytes = (int64_t)(E ? cap * (3 * sizeof(uint32_t) + sizeof(unsigned long long)) + 2 * (size_t)E * sizeof(uint32_t) : 0) + S;
+    info->n_observable = mon_n_obs;
+    info->max_destinations = mon_max_dst;
+    info->set_capacity = kMonSetCap;
+    info->root_live = root_live;
+    info->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return STCSP_OK;
+}
+
+// Stream monitor, check: every stream's accepted_len / n_end / end_final (contract: stcsp_engine.h). Exact always: the
+// streams the state-set kernel marks as over its capacity are finished by the host twin (monitor_host.hpp).
+int AutomatonServices::monitor_check(const AutomatonView &view, const stcsp_monitor_streams *ms, stcsp_monitor_result *out) {
+    if (int rc = enter(view, "monitor_check", NEED_MONITOR, "stcsp_automaton_check_streams")) return rc;
+    if (!monitor_offsets_ok(ms->n_streams, ms->offsets)) return fail(STCSP_E_INVALID, "monitor_check: malformed stream offsets");
+    auto t0 = std::chrono::steady_clock::now();
+    const size_t n = (size_t)ms->n_streams;
+    const size_t steps = n ? (size_t)ms->offsets[n] : 0;
+    if (steps && mon_n_obs && !ms->values) return fail(STCSP_E_INVALID, "monitor_check: no step values");
+    if (n >= 0x7fffffffull || steps >= 0x7fffffffull) return fail(STCSP_E_NOMEM, "monitor_check: too many streams or steps for one call");
+    m_acc.assign(n, 0);
+    m_nend.assign(n, 0);
+    m_fin.assign(n, 0);
+    memset(out, 0, sizeof *out);
+    out->n_streams = ms->n_streams;
+    out->accepted_len = m_acc.data();
+    out->n_end = m_nend.data();
+    out->end_final = m_fin.data();
+    if (n && root_live) {
+        const bool sets = mon_max_dst > 1 || (ms->flags & STCSP_MON_FORCE_SETS);
+        const uint32_t E = (uint32_t)v.exp_edges;
+        HIPCHK(d_moff.reserve(n, 1));
+        HIPCHK(reserve_all(n, 0, d_macc, d_mnend, d_mfin));
+        HIPCHK(d_mlid.reserve(steps));
+        HIPCHK(d_mrows.reserve(steps * mon_n_obs));
+        HIPCHK(ev.ready(3));
+        HIPCHK(hipMemcpyAsync(d_moff.p, ms->offsets, (n + 1) * sizeof(long long), hipMemcpyHostToDevice, v.stream));
+        if (steps * mon_n_obs) HIPCHK(hipMemcpyAsync(d_mrows.p, ms->values, steps * mon_n_obs * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+        HIPCHK(hipMemsetAsync(d_mctl.p + M_OVERFLOW, 0, sizeof(uint32_t), v.stream));
+        HIPCHK(hipEventRecord(ev[0], v.stream));
+        if (steps) {
+            if (E)
+                hipLaunchKernelGGL(k_m_steps, dim3((unsigned)((steps + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)steps, (const int32_t *)d_mrows.p,
+                                   mon_n_obs, (const int32_t *)v.d_oval, v.N, (const int32_t *)d_mobs.p, (const uint32_t *)d_mltab.p, mon_mask,
+                                   d_mlid.p);
+            else  // no edge, no label: every step is a rejection
+                HIPCHK(hipMemsetAsync(d_mlid.p, 0xff, steps * sizeof(uint32_t), v.stream));
+        }
+        HIPCHK(hipEventRecord(ev[1], v.stream));
+        if (sets)
+            hipLaunchKernelGGL(k_m_walk_sets, dim3((unsigned)n), dim3(64), 0, v.stream, (uint32_t)n, (const long long *)d_moff.p,
+                               (const uint32_t *)d_mlid.p, (const unsigned long long *)d_mkeys.p, (const uint32_t *)d_mhead.p,
+                               (const uint32_t *)d_mnext.p, (const uint32_t *)d_mdst.p, mon_mask, (const uint8_t *)d_pfinal.p, d_macc.p, d_mnend.p,
+                               d_mfin.p, d_mctl.p);
+        else
+            hipLaunchKernelGGL(k_m_walk_det, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)n, (const long long *)d_moff.p,
+                               (const uint32_t *)d_mlid.p, (const unsigned long long *)d_mkeys.p, (const uint32_t *)d_mdst0.p, mon_mask,
+                               (const uint8_t *)d_pfinal.p, d_macc.p, d_mnend.p, d_mfin.p);
+        HIPCHK(hipEventRecord(ev[2], v.stream));
+        HIPCHK(hipGetLastError());
+        uint32_t over = 0;
+        HIPCHK(hipMemcpyAsync(m_acc.data(), d_macc.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(m_nend.data(), d_mnend.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(m_fin.data(), d_mfin.p, n, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(&over, d_mctl.p + M_OVERFLOW, sizeof over, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        float ms_l = 0, ms_w = 0;
+        HIPCHK(hipEventElapsedTime(&ms_l, ev[0], ev[1]));
+        HIPCHK(hipEventElapsedTime(&ms_w, ev[1], ev[2]));
+        out->seconds_labels = ms_l * 1e-3;
+        out->seconds_walk = ms_w * 1e-3;
+        out->walk_kernel = sets ? 2 : 1;
+        if (over) {
+            if (!mon_host) {
+                const MonitorView mv{v.N, v.n_states, (int64_t)v.exp_edges, (const int64_t *)v.h_osrc, (const int64_t *)v.h_odst, v.h_oval,
+                                     p_valid.data(), p_final.data(), p_alive.data()};
+                mon_host.reset(new HostMonitor());
+                mon_host->build(mv, mon_observable.data());
+            }
+            for (size_t i = 0; i < n; i++)
+                if (m_acc[i] < 0) {
+                    mon_host->check_one(ms->values + ms->offsets[i] * mon_n_obs, ms->offsets[i + 1] - ms->offsets[i], &m_acc[i], &m_nend[i], &m_fin[i]);
+                    out->n_host_fallback++;
+                }
+        }
+    }
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return STCSP_OK;
+}
+
+// Stream generator, build (dev_generate.hpp): the live edges by source in canonical order and the
+// weights W_0 .. W_horizon of every state, from the flags the last postprocess() left in HBM.
+int AutomatonServices::generator_build(const AutomatonView &view, const stcsp_generator_options *go, stcsp_generator_info *info) {
+    if (int rc = enter(view, "generator_build", NEED_FLAGS, "stcsp_automaton_generate")) return rc;
+    if (!go || go->horizon < 0) return fail(STCSP_E_INVALID, "generator_build: the horizon must not be negative");
+    auto t0 = std::chrono::steady_clock::now();
+    gen_built = false;
+    rep_built = false;
+    inf_built = false;
+    const int N = v.N, H = go->horizon;
+    const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
+    if ((size_t)v.exp_edges > 0x7fffffffull) return fail(STCSP_E_NOMEM, "edge list too large for the device generator");
+    const std::vector<int32_t> obs = observed_columns(go->observable ? go->observable : v.default_observable, N);
+    const uint32_t n_tiles = (S + kGenScanTile - 1) / kGenScanTile;
+    if (int rc = live_set()) return rc;
+    HIPCHK(d_gtile.reserve_exact(grown(S) / kGenScanTile + 2));
+    HIPCHK(d_goff.reserve(S, 1));
+    HIPCHK(d_gcur.reserve(S));
+    HIPCHK(reserve_all(E, 0, d_gseg, d_geid, d_gdst));
+    const size_t table = ((size_t)H + 1) * S;
+    if (!d_gw.reserve_or_release(table)) return fail(STCSP_E_NOMEM, "generator_build: no room for the %d x %u table of weights", H + 1, S);
+    HIPCHK(d_gcount.reserve_exact((size_t)H + 1));
+    HIPCHK(d_gobs.reserve_exact((size_t)N));
+    HIPCHK(d_gctl.reserve_exact(G_WORDS));
+    const unsigned eb = (E + 255) / 256, sb = (S + 255) / 256;
+    uint32_t ctl[G_WORDS] = {0}, total = 0;
+    if (!obs.empty()) HIPCHK(hipMemcpyAsync(d_gobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+    HIPCHK(hipMemsetAsync(d_gctl.p, 0, sizeof ctl, v.stream));
+    // live edges by source: histogram, exclusive scan over the states, fill through a cursor, canonical order
+    HIPCHK(hipMemsetAsync(d_gcur.p, 0, (size_t)S * sizeof(uint32_t), v.stream));
+    if (E)
+        hipLaunchKernelGGL(k_g_degree, dim3(eb), dim3(256), 0, v.stream, E, (const long long *)v.d_osrc, (const long long *)v.d_odst,
+                           (const uint8_t *)d_palive.p, (const uint8_t *)d_live.p, d_gcur.p);
+    hipLaunchKernelGGL(k_g_scan_tiles, dim3(n_tiles), dim3(256), 0, v.stream, S, (const uint32_t *)d_gcur.p, d_gtile.p);
+    hipLaunchKernelGGL(k_g_scan_sums, dim3(1), dim3(256), 0, v.stream, n_tiles, d_gtile.p);
+    hipLaunchKernelGGL(k_g_scan_write, dim3(n_tiles), dim3(256), 0, v.stream, S, (const uint32_t *)d_gcur.p, (const uint32_t *)d_gtile.p, n_tiles,
+                       d_goff.p, d_gcur.p);
+    if (E) {
+        hipLaunchKernelGGL(k_g_fill, dim3(eb), dim3(256), 0, v.stream, E, (const long long *)v.d_osrc, (const long long *)v.d_odst,
+                           (const uint8_t *)d_palive.p, (const uint8_t *)d_live.p, d_gcur.p, d_gseg.p);
+        hipLaunchKernelGGL(k_g_order, dim3((S + 3) / 4), dim3(256), 0, v.stream, S, (const uint32_t *)d_goff.p, d_gseg.p, (const long long *)v.d_odst,
+                           (const int32_t *)v.d_oval, N, d_geid.p, d_gdst.p, d_gctl.p);
+    }
+    // the weights, one launch per level
+    hipLaunchKernelGGL(k_g_level0, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint8_t *)d_pfinal.p,
+                       (go->flags & STCSP_GEN_END_FINAL) ? 1 : 0, d_gw.p, d_gcount.p);
+    for (int t = 0; t < H; t++)
+        hipLaunchKernelGGL(k_g_weights, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)d_goff.p, (const uint32_t *)d_gdst.p,
+                           (const double *)(d_gw.p + (size_t)t * S), d_gw.p + (size_t)(t + 1) * S, d_gcount.p + t + 1);
+    HIPCHK(hipGetLastError());
+    gen_count.assign((size_t)H + 1, 0.0);
+    HIPCHK(hipMemcpyAsync(gen_count.data(), d_gcount.p, ((size_t)H + 1) * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(&total, d_goff.p + S, sizeof total, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(ctl, d_gctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    for (double c : gen_count)
+        if (!std::isfinite(c)) return fail(STCSP_E_UNSUPPORTED, "generator_build: the number of prefixes of length %d overflows a double", H);
+    gen_n_obs = (int)obs.size();
+    gen_horizon = H;
+    gen_built = true;
+    memset(info, 0, sizeof *info);
+    info->n_states = n_live;
+    info->n_edges = total;
+    info->table_bytes = (int64_t)(table * sizeof(double) + 3 * (size_t)E * sizeof(uint32_t) + (2 * (size_t)S + 1) * sizeof(uint32_t) + S);
+    info->count = gen_count.data();
+    info->n_observable = gen_n_obs;
+    info->horizon = H;
+    info->max_out_degree = (int32_t)ctl[G_MAXDEG];
+    info->root_live = root_live;
+    info->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return STCSP_OK;
+}
+
+// Stream generator, generate: n_streams prefixes of one length, sampled or unranked (contract: stcsp_engine.h).
+int AutomatonServices::generate(const AutomatonView &view, const stcsp_generate_request *rq, stcsp_generate_result *out) {
+    if (int rc = enter(view, "generate", NEED_GENERATOR, "stcsp_automaton_generate")) return rc;
+    if (!generate_request_ok(gen_count, rq->n_streams, rq->len, rq->n_streams > 0 ? rq->ranks : nullptr))
+        return fail(STCSP_E_INVALID, "generate: a length outside 0 .. horizon or without a prefix, or a rank that is not below count[len] < 2^53");
+    auto t0 = std::chrono::steady_clock::now();
+    const size_t n = (size_t)rq->n_streams, len = (size_t)rq->len;
+    const size_t cells = n * len * (size_t)gen_n_obs;
+    if (n >= 0x7fffffffull) return fail(STCSP_E_NOMEM, "generate: too many streams for one call");
+    g_values.assign(cells, 0);
+    g_fin.assign(n, 0);
+    memset(out, 0, sizeof *out);
+    out->n_streams = rq->n_streams;
+    out->values = g_values.data();
+    out->end_final = g_fin.data();
+    out->len = rq->len;
+    out->n_observable = gen_n_obs;
+    if (n) {  // (count[len] > 0: the root is live)
+        HIPCHK(d_gfin.reserve(n));
+        HIPCHK(d_gout.reserve(cells));
+        if (rq->ranks) HIPCHK(d_granks.reserve(n));
+        HIPCHK(ev.ready(2));
+        if (rq->ranks) HIPCHK(hipMemcpyAsync(d_granks.p, rq->ranks, n * sizeof(uint64_t), hipMemcpyHostToDevice, v.stream));
+        HIPCHK(hipMemsetAsync(d_gctl.p + G_ERROR, 0, sizeof(uint32_t), v.stream));
+        HIPCHK(hipEventRecord(ev[0], v.stream));
+        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+        hipLaunchKernelGGL(rq->ranks ? k_g_generate<true> : k_g_generate<false>, grid, block, 0, v.stream, (uint32_t)n, (uint32_t)len,
+                           rq->ranks ? 0ull : (unsigned long long)rq->seed, rq->ranks ? (const unsigned long long *)d_granks.p : nullptr, v.n_states,
+                           (const double *)d_gw.p, (const uint32_t *)d_goff.p, (const uint32_t *)d_gdst.p, (const uint32_t *)d_geid.p,
+                           (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p, gen_n_obs, (const uint8_t *)d_pfinal.p, d_gout.p, d_gfin.p, d_gctl.p);
+        HIPCHK(hipEventRecord(ev[1], v.stream));
+        HIPCHK(hipGetLastError());
+        uint32_t bad = 0;
+        if (cells) HIPCHK(hipMemcpyAsync(g_values.data(), d_gout.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(g_fin.data(), d_gfin.p, n, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(&bad, d_gctl.p + G_ERROR, sizeof bad, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        float ms_k = 0;
+        HIPCHK(hipEventElapsedTime(&ms_k, ev[0], ev[1]));
+        out->seconds_kernel = ms_k * 1e-3;
+        if (bad) return fail(STCSP_E_INTERNAL, "generate: a state without an edge of non-zero weight");
+    }
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return STCSP_OK;
+}
+
+// Stream repair, the label ids of the generator's CSR (dev_repair.hpp): built on the first repair() after a generator_build().
+int AutomatonServices::repair_labels() {
+    const uint32_t S = v.n_states;
+    uint32_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, d_goff.p + S, sizeof total, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    uint32_t slots = 64;
+    while (slots < 2 * (size_t)total && slots < 0x80000000u) slots <<= 1;
+    HIPCHK(d_rtab.reserve_exact(slots));
+    HIPCHK(reserve_all(total, 0, d_rlid, d_rrep));
+    HIPCHK(d_rlong.reserve(S));
+    HIPCHK(d_rctl.reserve_exact(R_WORDS));
+    rep_wave_segment = kRepWaveSegment;
+    if (const char *e = getenv("STCSP_REPAIR_WAVE_SEGMENT")) rep_wave_segment = (uint32_t)std::max(1ll, std::min(atoll(e), 0x7fffffffll));
+    uint32_t ctl[R_WORDS] = {0};
+    HIPCHK(hipMemsetAsync(d_rctl.p, 0, sizeof ctl, v.stream));
+    HIPCHK(hipMemsetAsync(d_rtab.p, 0xff, (size_t)slots * sizeof(uint32_t), v.stream));
+    if (total) {
+        const unsigned kb = (total + 255) / 256;
+        hipLaunchKernelGGL(k_r_labels, dim3(kb), dim3(256), 0, v.stream, total, (const uint32_t *)d_geid.p, (const int32_t *)v.d_oval, v.N,
+                           (const int32_t *)d_gobs.p, gen_n_obs, d_rtab.p, slots - 1, d_rlid.p, d_rctl.p);
+        hipLaunchKernelGGL(k_r_number, dim3((slots + 255) / 256), dim3(256), 0, v.stream, slots, d_rtab.p, d_rrep.p, d_rctl.p);
+        hipLaunchKernelGGL(k_r_remap, dim3(kb), dim3(256), 0, v.stream, total, (const uint32_t *)d_rtab.p, d_rlid.p);
+    }
+    hipLaunchKernelGGL(k_r_long, dim3((S + 255) / 256), dim3(256), 0, v.stream, S, (const uint32_t *)d_goff.p, rep_wave_segment, d_rlong.p, d_rctl.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ctl, d_rctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    if (ctl[R_ERROR]) return fail(STCSP_E_INTERNAL, "repair: the label table overflowed");
+    rep_total = total;
+    rep_n_labels = ctl[R_LABELS];
+    rep_n_long = ctl[R_LONG];
+    rep_built = true;
+    return STCSP_OK;
+}
+
+// Stream repair: the nearest solution prefix of every stream (contract: stcsp_engine.h).
+int AutomatonServices::repair(const AutomatonView &view, const stcsp_repair_request *rq, stcsp_repair_result *out) {
+    if (int rc = enter(view, "repair", NEED_GENERATOR, "stcsp_automaton_repair_streams")) return rc;
+    if (!repair_request_ok(rq->n_streams, rq->offsets, rq->weights, gen_n_obs))
+        return fail(STCSP_E_INVALID, "repair: malformed stream offsets, a negative weight, or (sum of the weights) x (longest stream) above 2^31 - 2");
+    auto t0 = std::chrono::steady_clock::now();
+    const size_t n = (size_t)rq->n_streams, n_obs = (size_t)gen_n_obs;
+    const size_t steps = n ? (size_t)rq->offsets[n] : 0;
+    if (steps && n_obs && !rq->values) return fail(STCSP_E_INVALID, "repair: no step values");
+    r_dist.assign(n, -1);
+    r_values.assign(steps * n_obs, 0);
+    r_fin.assign(n, 0);
+    r_nchg.assign(n, 0);
+    memset(out, 0, sizeof *out);
+    out->n_streams = rq->n_streams;
+    out->distance = r_dist.data();
+    out->values = r_values.data();
+    out->end_final = r_fin.data();
+    out->n_changed = r_nchg.data();
+    out->n_observable = gen_n_obs;
+    if (n && root_live) {
+        if (int rc = rep_built ? STCSP_OK : repair_labels()) return rc;
+        const uint32_t S = v.n_states, nL = rep_n_labels;
+        const int end_final = (rq->flags & STCSP_REPAIR_END_FINAL) ? 1 : 0;
+        size_t budget = 0;
+        if (int rc = table_budget("STCSP_REPAIR_BYTES", budget)) return rc;
+        auto need = [&](size_t len) { return ((len + 1) * (size_t)S + len * (size_t)nL) * sizeof(uint32_t); };
+        std::vector<int32_t> w(n_obs, 1);
+        if (rq->weights) w.assign(rq->weights, rq->weights + n_obs);
+        if (d_rweights.n < n_obs) HIPCHK(d_rweights.alloc(n_obs + 16));
+        if (n_obs) HIPCHK(hipMemcpyAsync(d_rweights.p, w.data(), n_obs * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+        HIPCHK(ev.ready(4));
+        std::vector<RepStream> meta;
+        const unsigned sb = (S + 255) / 256;
+        for (size_t b0 = 0; b0 < n;) {
+            Batch b;  // consecutive streams while their tables and costs fit the budget
+            if (int rc = plan_batch("repair", rq->offsets, n, b0, budget, need, meta, b)) return rc;
+            const size_t nb = b.b1 - b0, cells = b.steps * n_obs, words_c = b.steps * (size_t)nL;
+            const size_t first = (size_t)rq->offsets[b0] * n_obs;
+            if (!d_rG.reserve_or_release(b.entries)) return fail(STCSP_E_NOMEM, "repair: no room for %zu bytes of tables", b.entries * sizeof(uint32_t));
+            if (!d_rcost.reserve_or_release(words_c)) return fail(STCSP_E_NOMEM, "repair: no room for %zu bytes of step costs", words_c * sizeof(uint32_t));
+            HIPCHK(reserve_all(nb, 0, d_rstreams, d_rdist, d_rnchg, d_rfin));
+            HIPCHK(reserve_all(cells, 0, d_rrows, d_rout));
+            HIPCHK(hipMemcpyAsync(d_rstreams.p, meta.data(), nb * sizeof(RepStream), hipMemcpyHostToDevice, v.stream));
+            if (cells) {
+                HIPCHK(hipMemcpyAsync(d_rrows.p, rq->values + first, cells * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+                HIPCHK(hipMemsetAsync(d_rout.p, 0, cells * sizeof(int32_t), v.stream));
+            }
+            HIPCHK(hipMemsetAsync(d_rctl.p + R_ERROR, 0, sizeof(uint32_t), v.stream));
+            HIPCHK(hipEventRecord(ev[0], v.stream));
+            if (words_c)
+                hipLaunchKernelGGL(k_r_cost, dim3((nL + 255) / 256, (unsigned)std::min<size_t>(b.steps, 65535)), dim3(256), 0, v.stream, nL,
+                                   (uint32_t)b.steps, (const uint32_t *)d_rrep.p, (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p, gen_n_obs,
+                                   (const int32_t *)d_rweights.p, (const int32_t *)d_rrows.p, d_rcost.p);
+            HIPCHK(hipEventRecord(ev[1], v.stream));
+            hipLaunchKernelGGL(k_r_level0, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, (const RepStream *)d_rstreams.p, (const uint8_t *)d_live.p,
+                               (const uint8_t *)d_pfinal.p, end_final, d_rG.p);
+            for (uint32_t r = 1; r <= (uint32_t)b.longest; r++) {
+                hipLaunchKernelGGL(k_r_relax, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, r, (const RepStream *)d_rstreams.p,
+                                   (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint32_t *)d_rcost.p,
+                                   rep_wave_segment, d_rG.p);
+                if (rep_n_long)
+                    hipLaunchKernelGGL(k_r_relax_long, dim3((rep_n_long + 3) / 4, (unsigned)nb), dim3(256), 0, v.stream, rep_n_long,
+                                       (const uint32_t *)d_rlong.p, S, r, (const RepStream *)d_rstreams.p, (const uint32_t *)d_goff.p,
+                                       (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint32_t *)d_rcost.p, d_rG.p);
+            }
+            HIPCHK(hipEventRecord(ev[2], v.stream));
+            hipLaunchKernelGGL(k_r_walk, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)nb, (const RepStream *)d_rstreams.p, S,
+                               (const uint32_t *)d_rG.p, (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p,
+                               (const uint32_t *)d_geid.p, nL, (const uint32_t *)d_rcost.p, (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p,
+                               gen_n_obs, (const uint8_t *)d_pfinal.p, (const int32_t *)d_rrows.p, d_rout.p, d_rdist.p, d_rfin.p, d_rnchg.p, d_rctl.p);
+            HIPCHK(hipEventRecord(ev[3], v.stream));
+            HIPCHK(hipGetLastError());
+            uint32_t bad = 0;
+            if (cells) HIPCHK(hipMemcpyAsync(r_values.data() + first, d_rout.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(r_dist.data() + b0, d_rdist.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(r_nchg.data() + b0, d_rnchg.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(r_fin.data() + b0, d_rfin.p, nb, hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(&bad, d_rctl.p + R_ERROR, sizeof bad, hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipStreamSynchronize(v.stream));
+            float ms_c = 0, ms_r = 0, ms_w = 0;
+            HIPCHK(hipEventElapsedTime(&ms_c, ev[0], ev[1]));
+            HIPCHK(hipEventElapsedTime(&ms_r, ev[1], ev[2]));
+            HIPCHK(hipEventElapsedTime(&ms_w, ev[2], ev[3]));
+            out->seconds_cost += ms_c * 1e-3;
+            out->seconds_relax += ms_r * 1e-3;
+            out->seconds_walk += ms_w * 1e-3;
+            out->n_batches++;
+            out->table_bytes = std::max<int64_t>(out->table_bytes, (int64_t)b.bytes);
+            if (bad) return fail(STCSP_E_INTERNAL, "repair: a state with a finite cost to go and no edge that attains it");
+            b0 = b.b1;
+        }
+        out->n_labels = nL;
+    }
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return STCSP_OK;
+}
+
+// Stream inference, the value dictionaries (dev_infer.hpp): built on the first infer() after a generator_build(), over
+// the label representatives of repair_labels(). Sized by what the labels carry, not by the variables' bounds.
+int AutomatonServices::infer_dictionaries() {
+    const size_t nL = rep_n_labels, n_obs = (size_t)gen_n_obs, cells = nL * n_obs;
+    std::vector<int32_t> rows(cells);
+    if (cells) {
+        HIPCHK(d_ilabrows.reserve(cells));
+        hipLaunchKernelGGL(k_i_rows, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)nL, (const uint32_t *)d_rrep.p,
+                           (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p, gen_n_obs, d_ilabrows.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rows.data(), d_ilabrows.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+    }
+    inf_dict.assign(n_obs, std::vector<int32_t>());
+    inf_word_off.assign(n_obs, 0);
+    std::vector<uint32_t> vidx(cells);
+    size_t words = 0;
+    for (size_t x = 0; x < n_obs; x++) {
+        std::vector<int32_t> &d = inf_dict[x];
+        d.resize(nL);
+        for (size_t l = 0; l < nL; l++) d[l] = rows[l * n_obs + x];
+        std::sort(d.begin(), d.end());
+        d.erase(std::unique(d.begin(), d.end()), d.end());
+        for (size_t l = 0; l < nL; l++) vidx[l * n_obs + x] = (uint32_t)(std::lower_bound(d.begin(), d.end(), rows[l * n_obs + x]) - d.begin());
+        inf_word_off[x] = (uint32_t)words;
+        words += (d.size() + 31) / 32;
+    }
+    if (words > 0x7fffffffull) return fail(STCSP_E_NOMEM, "infer: the support bitmaps of one step are too large");
+    inf_words = (uint32_t)words;
+    HIPCHK(d_ividx.reserve(cells));
+    if (d_iwoff.n < n_obs) HIPCHK(d_iwoff.alloc(n_obs + 16));
+    if (cells) HIPCHK(hipMemcpyAsync(d_ividx.p, vidx.data(), cells * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+    if (n_obs) HIPCHK(hipMemcpyAsync(d_iwoff.p, inf_word_off.data(), n_obs * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+    HIPCHK(hipStreamSynchronize(v.stream));  // (vidx is a local)
+    inf_built = true;
+    return STCSP_OK;
+}
+
+// Stream inference: supports, counts and draws of partially observed streams (contract: stcsp_engine.h).
+int AutomatonServices::infer(const AutomatonView &view, const stcsp_infer_request *rq, stcsp_infer_result *out) {
+    if (int rc = enter(view, "infer", NEED_GENERATOR, "stcsp_automaton_infer_streams")) return rc;
+    if (!infer_request_ok(rq->n_streams, rq->offsets, rq->draws)) return fail(STCSP_E_INVALID, "infer: malformed stream offsets or a negative number of draws");
+    auto t0 = std::chrono::steady_clock::now();
+    const size_t n = (size_t)rq->n_streams, n_obs = (size_t)gen_n_obs, draws = (size_t)rq->draws;
+    const size_t steps = n ? (size_t)rq->offsets[n] : 0;
+    if (steps && n_obs && !rq->values) return fail(STCSP_E_INVALID, "infer: no step values");
+    i_count.assign(n, 0.0);
+    i_feas.assign(n, 0);
+    i_soff.assign(steps * n_obs + 1, 0);
+    i_sval.clear();
+    i_nstates.assign(steps + n, 0);
+    i_values.assign(steps * draws * n_obs, STCSP_INFER_MISSING);
+    i_fin.assign(n * draws, 0);
+    memset(out, 0, sizeof *out);
+    out->n_streams = rq->n_streams;
+    out->n_observable = gen_n_obs;
+    out->draws = rq->draws;
+    auto publish = [&]() {  // (the vectors may have grown)
+        out->count = i_count.data();
+        out->feasible = i_feas.data();
+        out->support_off = i_soff.data();
+        out->support_val = i_sval.data();
+        out->n_states = i_nstates.data();
+        out->values = i_values.data();
+        out->end_final = i_fin.data();
+    };
+    publish();
+    if (n && root_live) {
+        if (int rc = rep_built ? STCSP_OK : repair_labels()) return rc;
+        if (int rc = inf_built ? STCSP_OK : infer_dictionaries()) return rc;
+        const uint32_t S = v.n_states, nL = rep_n_labels, W = inf_words;
+        const int end_final = (rq->flags & STCSP_INFER_END_FINAL) ? 1 : 0;
+        size_t budget = 0;
+        if (int rc = table_budget("STCSP_INFER_BYTES", budget)) return rc;
+        auto need = [&](size_t len) { return (len + 1) * (size_t)S * (sizeof(double) + 1) + len * ((size_t)nL * 2 + (size_t)W * sizeof(uint32_t)); };
+        HIPCHK(d_ictl.reserve_exact(I_WORDS));
+        HIPCHK(ev.ready(7));
+        std::vector<InfStream> meta;
+        const unsigned sb = (S + 255) / 256;
+        for (size_t b0 = 0; b0 < n;) {
+            Batch b;  // consecutive streams while their structures fit the budget
+            if (int rc = plan_batch("infer", rq->offsets, n, b0, budget, need, meta, b)) return rc;
+            const size_t nb = b.b1 - b0, cells = b.steps * n_obs, marks = b.steps * (size_t)nL, words = b.steps * (size_t)W;
+            const size_t n_q = nb * draws, out_cells = cells * draws;
+            const size_t first_step = (size_t)rq->offsets[b0], first = first_step * n_obs;
+            if (n_q >= 0x7fffffffull) return fail(STCSP_E_NOMEM, "infer: too many draws for one batch");
+            if (!(d_iB.reserve_or_release(b.entries) && d_iF.reserve_or_release(b.entries) && d_imatch.reserve_or_release(marks) &&
+                  d_ifeas.reserve_or_release(marks) && d_ibits.reserve_or_release(words))) {
+                d_iB.release();
+                d_iF.release();
+                d_imatch.release();
+                d_ifeas.release();
+                d_ibits.release();
+                return fail(STCSP_E_NOMEM, "infer: no room for %zu bytes of tables", b.bytes);
+            }
+            HIPCHK(reserve_all(nb, 0, d_istreams, d_icount));
+            HIPCHK(d_irows.reserve(cells));
+            HIPCHK(d_instates.reserve(b.steps + nb));
+            if (n_q) {
+                HIPCHK(d_ifin.reserve(n_q));
+                if (rq->ranks) HIPCHK(d_iranks.reserve(n_q));
+                HIPCHK(d_iout.reserve(out_cells));
+            }
+            HIPCHK(hipMemcpyAsync(d_istreams.p, meta.data(), nb * sizeof(InfStream), hipMemcpyHostToDevice, v.stream));
+            if (cells) HIPCHK(hipMemcpyAsync(d_irows.p, rq->values + first, cells * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+            HIPCHK(hipMemsetAsync(d_iF.p, 0, b.entries, v.stream));
+            if (marks) HIPCHK(hipMemsetAsync(d_ifeas.p, 0, marks, v.stream));
+            if (words) HIPCHK(hipMemsetAsync(d_ibits.p, 0, words * sizeof(uint32_t), v.stream));
+            HIPCHK(hipMemsetAsync(d_instates.p, 0, (b.steps + nb) * sizeof(int32_t), v.stream));
+            HIPCHK(hipMemsetAsync(d_ictl.p, 0, I_WORDS * sizeof(uint32_t), v.stream));
+            const unsigned step_rows = (unsigned)std::min<size_t>(std::max<size_t>(b.steps, 1), 65535);
+            HIPCHK(hipEventRecord(ev[0], v.stream));
+            if (marks)
+                hipLaunchKernelGGL(k_i_match, dim3((nL + 255) / 256, step_rows), dim3(256), 0, v.stream, nL, (uint32_t)b.steps, (const uint32_t *)d_rrep.p,
+                                   (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p, gen_n_obs, (const int32_t *)d_irows.p, d_imatch.p);
+            HIPCHK(hipEventRecord(ev[1], v.stream));
+            hipLaunchKernelGGL(k_i_level0, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, (const InfStream *)d_istreams.p, (const uint8_t *)d_live.p,
+                               (const uint8_t *)d_pfinal.p, end_final, d_iB.p);
+            for (uint32_t r = 1; r <= (uint32_t)b.longest; r++)
+                hipLaunchKernelGGL(k_i_backward, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, r, (const InfStream *)d_istreams.p,
+                                   (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_imatch.p,
+                                   d_iB.p);
+            hipLaunchKernelGGL(k_i_root, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)nb, (const InfStream *)d_istreams.p, S,
+                               (const double *)d_iB.p, d_iF.p, d_icount.p);
+            HIPCHK(hipEventRecord(ev[2], v.stream));
+            for (uint32_t t = 0; t < (uint32_t)b.longest; t++) {
+                hipLaunchKernelGGL(k_i_forward, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, t, (const InfStream *)d_istreams.p,
+                                   (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_imatch.p,
+                                   (const double *)d_iB.p, rep_wave_segment, d_iF.p, d_ifeas.p);
+                if (rep_n_long)
+                    hipLaunchKernelGGL(k_i_forward_long, dim3((rep_n_long + 3) / 4, (unsigned)nb), dim3(256), 0, v.stream, rep_n_long,
+                                       (const uint32_t *)d_rlong.p, S, t, (const InfStream *)d_istreams.p, (const uint32_t *)d_goff.p,
+                                       (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_imatch.p, (const double *)d_iB.p,
+                                       d_iF.p, d_ifeas.p);
+            }
+            hipLaunchKernelGGL(k_i_count, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, (const InfStream *)d_istreams.p, (const uint8_t *)d_iF.p,
+                               d_instates.p);
+            HIPCHK(hipEventRecord(ev[3], v.stream));
+            if (marks && W)
+                hipLaunchKernelGGL(k_i_support, dim3((nL + 255) / 256, step_rows), dim3(256), 0, v.stream, nL, (uint32_t)b.steps, (const uint8_t *)d_ifeas.p,
+                                   (const uint32_t *)d_ividx.p, (const uint32_t *)d_iwoff.p, gen_n_obs, W, d_ibits.p);
+            HIPCHK(hipEventRecord(ev[4], v.stream));
+            HIPCHK(hipGetLastError());
+            i_bits.resize(words);
+            HIPCHK(hipMemcpyAsync(i_count.data() + b0, d_icount.p, nb * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(i_nstates.data() + first_step + b0, d_instates.p, (b.steps + nb) * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+            if (words) HIPCHK(hipMemcpyAsync(i_bits.data(), d_ibits.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipStreamSynchronize(v.stream));
+            // the bitmaps -> sorted lists: bit order is value order
+            for (size_t step = 0; step < b.steps; step++)
+                for (size_t x = 0; x < n_obs; x++) {
+                    const uint32_t *w = i_bits.data() + step * W + inf_word_off[x];
+                    const std::vector<int32_t> &d = inf_dict[x];
+                    for (size_t k = 0; k < d.size(); k++)
+                        if (w[k >> 5] >> (k & 31) & 1u) i_sval.push_back(d[k]);
+                    i_soff[(first_step + step) * n_obs + x + 1] = (int64_t)i_sval.size();
+                }
+            for (size_t i = b0; i < b.b1; i++) i_feas[i] = i_count[i] > 0.0;
+            publish();
+            float ms[5] = {0, 0, 0, 0, 0};
+            if (n_q) {
+                // the draws: the counts decide whether they can be asked for
+                for (size_t i = b0; i < b.b1; i++) {
+                    const int bad = infer_draws_ok(i_count[i], rq->draws, rq->ranks ? rq->ranks + i * draws : nullptr);
+                    if (bad == 1) return fail(STCSP_E_UNSUPPORTED, "infer: draws from stream %zu, whose count overflows a double", i);
+                    if (bad) return fail(STCSP_E_INVALID, "infer: stream %zu: a rank that is not below its count < 2^53", i);
+                }
+                if (rq->ranks) HIPCHK(hipMemcpyAsync(d_iranks.p, rq->ranks + b0 * draws, n_q * sizeof(uint64_t), hipMemcpyHostToDevice, v.stream));
+                if (out_cells) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d_iout.p, STCSP_INFER_MISSING, out_cells, v.stream));
+                HIPCHK(hipMemsetAsync(d_ifin.p, 0, n_q, v.stream));
+                const dim3 grid((unsigned)((n_q + 255) / 256)), block(256);
+                HIPCHK(hipEventRecord(ev[5], v.stream));
+                hipLaunchKernelGGL(rq->ranks ? k_i_walk<true> : k_i_walk<false>, grid, block, 0, v.stream, (uint32_t)n_q, (uint32_t)draws,
+                                   (unsigned long long)(b0 * draws), rq->ranks ? 0ull : (unsigned long long)rq->seed,
+                                   rq->ranks ? (const unsigned long long *)d_iranks.p : nullptr, (const InfStream *)d_istreams.p, S, (const double *)d_iB.p,
+                                   (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, (const uint32_t *)d_geid.p, nL,
+                                   (const uint8_t *)d_imatch.p, (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p, gen_n_obs,
+                                   (const uint8_t *)d_pfinal.p, d_iout.p, d_ifin.p, d_ictl.p);
+                HIPCHK(hipEventRecord(ev[6], v.stream));
+                HIPCHK(hipGetLastError());
+                uint32_t bad = 0;
+                if (out_cells) HIPCHK(hipMemcpyAsync(i_values.data() + first * draws, d_iout.p, out_cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+                HIPCHK(hipMemcpyAsync(i_fin.data() + b0 * draws, d_ifin.p, n_q, hipMemcpyDeviceToHost, v.stream));
+                HIPCHK(hipMemcpyAsync(&bad, d_ictl.p + I_ERROR, sizeof bad, hipMemcpyDeviceToHost, v.stream));
+                HIPCHK(hipStreamSynchronize(v.stream));
+                HIPCHK(hipEventElapsedTime(&ms[4], ev[5], ev[6]));
+                if (bad) return fail(STCSP_E_INTERNAL, "infer: a state with weight to go and no matching edge of non-zero weight");
+            }
+            for (int k = 0; k < 4; k++) HIPCHK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+            out->seconds_match += ms[0] * 1e-3;
+            out->seconds_backward += ms[1] * 1e-3;
+            out->seconds_forward += ms[2] * 1e-3;
+            out->seconds_support += ms[3] * 1e-3;
+            out->seconds_walk += ms[4] * 1e-3;
+            out->n_batches++;
+            out->table_bytes = std::max<int64_t>(out->table_bytes, (int64_t)b.bytes);
+            b0 = b.b1;
+        }
+        out->n_labels = nL;
+    }
+    if (i_sval.empty()) i_sval.reserve(1);
+    publish();
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return STCSP_OK;
+}
+
+}  // namespace stcsp

@@ -1,0 +1,123 @@
+// automaton.hpp -- what engine.hip sees of the services on the exported automaton (automaton.hip)
+#pragma once
+#include <cstdint>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "hip_host.hpp"
+
+namespace stcsp {
+
+namespace dev { struct RepStream; struct InfStream; }
+struct HostMonitor;
+
+// what the engine hands a service call: the last export and the facts of model and solve the services read. Valid for the call only.
+struct AutomatonView {
+    hipStream_t stream;  // the engine's: a service is ordered after the export
+    int N, KL;
+    uint32_t n_states;
+    size_t exp_edges;
+    const long long *d_osrc, *d_odst;  // [exp_edges]
+    const int32_t *d_oval;             // [exp_edges][N]
+    const uint32_t *d_state_keys;      // [n_states][KL]
+    const long long *h_osrc, *h_odst;  // the pinned host copies
+    const int32_t *h_oval;
+    const int *lb, *ub;  // [N] the variables' bounds
+    int n_sig, n_until, n_until_cons;
+    const uint8_t *default_observable;  // [N]
+    bool sharded, truncated, exp_on_device;
+    std::string *err;  // where a failing call leaves its message
+};
+
+struct AutomatonServices {
+    AutomatonServices();  // (both out of line: HostMonitor is incomplete here)
+    ~AutomatonServices();
+    void invalidate();     // a new solve, a new export or new flags: everything derived from the old ones is dropped
+    int postprocess(const AutomatonView &view, const stcsp_post_options *po, stcsp_post_result *out);
+    int quotient(const AutomatonView &view, const stcsp_quotient_options *qo, stcsp_quotient_result *out);
+    int monitor_build(const AutomatonView &view, const stcsp_monitor_options *mo, stcsp_monitor_info *info);
+    int monitor_check(const AutomatonView &view, const stcsp_monitor_streams *ms, stcsp_monitor_result *out);
+    int generator_build(const AutomatonView &view, const stcsp_generator_options *go, stcsp_generator_info *info);
+    int generate(const AutomatonView &view, const stcsp_generate_request *rq, stcsp_generate_result *out);
+    int repair(const AutomatonView &view, const stcsp_repair_request *rq, stcsp_repair_result *out);
+    int infer(const AutomatonView &view, const stcsp_infer_request *rq, stcsp_infer_result *out);
+
+private:
+    enum Need { NEED_EXPORT, NEED_FLAGS, NEED_MONITOR, NEED_GENERATOR };
+    struct Batch { size_t b1 = 0, bytes = 0, entries = 0, steps = 0, longest = 0; };  // of plan_batch()
+    int fail(int code, const char *fmt, ...);
+    int enter(const AutomatonView &view, const char *who, Need need, const char *host_twin);
+    int live_set();
+    int table_budget(const char *env_name, size_t &budget);
+    template <typename Rec, typename NeedFn>
+    int plan_batch(const char *who, const int64_t *offsets, size_t n, size_t b0, size_t budget, NeedFn need, std::vector<Rec> &meta, Batch &b);
+    int repair_labels();
+    int infer_dictionaries();
+
+    AutomatonView v{};  // of the call that is running: its pointers are the engine's, not to be used after it
+    DevEvents ev;     // (every call waits for its own work: one set serves them all)
+    // post-processing (dev_postproc.hpp): the flags of the last postprocess(), valid while post_done; and the live set (the valid
+    // states reachable from the root over alive edges), computed on first need after a postprocess(), valid while live_done
+    bool post_done = false, live_done = false, root_live = false;
+    int64_t n_live = 0;
+    DevBuf<uint8_t> d_pvalid, d_pfinal, d_palive, d_pnodeok, d_live;
+    DevBuf<uint32_t> d_pcover, d_pctl, d_lctl;
+    std::vector<uint8_t> p_valid, p_final, p_alive, live;
+    // bisimulation quotient (dev_quotient.hpp)
+    DevBuf<int32_t> d_qobs;
+    DevBuf<uint32_t> d_qsrc, d_qdst, d_qlid, d_qcls[2], d_qcnt, d_qtab_e, d_qtab_s, d_qctl;
+    DevBuf<unsigned long long> d_qacc[2];
+    std::vector<int32_t> q_class;
+    std::vector<uint32_t> q_raw, q_cnt;
+    // stream monitor (dev_monitor.hpp): the look-up structures of the last monitor_build(), valid while mon_built
+    bool mon_built = false;
+    int mon_n_obs = 0, mon_max_dst = 0;
+    uint32_t mon_mask = 0;
+    std::vector<uint8_t> mon_observable, m_fin;
+    std::unique_ptr<HostMonitor> mon_host;  // built when the first stream falls back to the host twin
+    DevBuf<uint8_t> d_mfin;
+    DevBuf<int32_t> d_mobs, d_mrows, d_macc, d_mnend;
+    DevBuf<uint32_t> d_mltab, d_mhead, d_mdst0, d_mdst, d_mnext, d_mctl, d_mlid;
+    DevBuf<unsigned long long> d_mkeys;
+    DevBuf<long long> d_moff;
+    std::vector<int32_t> m_acc, m_nend;
+    // stream generator (dev_generate.hpp): the structures of the last generator_build(), valid while gen_built
+    bool gen_built = false;
+    int gen_n_obs = 0, gen_horizon = 0;
+    std::vector<double> gen_count;
+    DevBuf<uint8_t> d_gfin;
+    DevBuf<int32_t> d_gobs, d_gout;
+    DevBuf<uint32_t> d_goff, d_gcur, d_gseg, d_geid, d_gdst, d_gtile, d_gctl;
+    DevBuf<double> d_gw, d_gcount;
+    DevBuf<unsigned long long> d_granks;
+    std::vector<int32_t> g_values;
+    std::vector<uint8_t> g_fin;
+    // stream repair (dev_repair.hpp): label ids per position of the generator's CSR, valid while gen_built && rep_built
+    bool rep_built = false;
+    uint32_t rep_n_labels = 0, rep_n_long = 0, rep_total = 0, rep_wave_segment = 0;
+    DevBuf<uint32_t> d_rtab, d_rlid, d_rrep, d_rlong, d_rctl, d_rG, d_rcost;
+    DevBuf<dev::RepStream> d_rstreams;
+    DevBuf<int32_t> d_rweights, d_rrows, d_rout, d_rdist, d_rnchg;
+    DevBuf<uint8_t> d_rfin;
+    std::vector<int32_t> r_dist, r_values, r_nchg;
+    std::vector<uint8_t> r_fin;
+    // stream inference (dev_infer.hpp): the value dictionaries of the labels, valid while gen_built && rep_built && inf_built
+    bool inf_built = false;
+    uint32_t inf_words = 0;                      // bitmap words per step: the sum over the variables
+    std::vector<std::vector<int32_t>> inf_dict;  // [n_obs] the sorted distinct values the labels carry
+    std::vector<uint32_t> inf_word_off;          // [n_obs] first bitmap word of a variable
+    DevBuf<uint32_t> d_ividx, d_iwoff, d_ibits, d_ictl;
+    DevBuf<dev::InfStream> d_istreams;
+    DevBuf<double> d_iB, d_icount;
+    DevBuf<uint8_t> d_iF, d_imatch, d_ifeas, d_ifin;
+    DevBuf<int32_t> d_irows, d_iout, d_instates, d_ilabrows;
+    DevBuf<unsigned long long> d_iranks;
+    std::vector<double> i_count;
+    std::vector<uint8_t> i_feas, i_fin;
+    std::vector<int64_t> i_soff;
+    std::vector<int32_t> i_sval, i_nstates, i_values;
+    std::vector<uint32_t> i_bits;
+};
+
+}  // namespace stcsp

@@ -39,8 +39,8 @@ namespace dev {
 constexpr uint32_t kGenWaveSegment = 4096;  // longest segment k_g_order ranks by counting; longer ones are sorted by one lane
 constexpr int kGenScanItems = 4;            // states per lane in the scan
 constexpr int kGenScanTile = 256 * kGenScanItems;
-// the words the host reads; G_ERROR and G_CHANGED sit where k_q_reach expects them
-enum { G_MAXDEG = 0, G_ERROR = Q_ERROR, G_CHANGED = Q_CHANGED, G_WORDS = 4 };
+// the words the host reads
+enum { G_MAXDEG = 0, G_ERROR = Q_ERROR, G_WORDS = 4 };
 enum { G_ERR_NO_EDGE = 8 };
 
 __device__ inline bool g_edge_live(uint32_t e, const long long *src, const long long *dst, const uint8_t *alive, const uint8_t *live) {

@@ -38,8 +38,8 @@ namespace dev {
 constexpr unsigned long long kMEmptyKey = ~0ull;
 constexpr int kMonSetCap = 256;    // states a stream's set may hold on the device
 constexpr int kMonSetSlots = 512;  // LDS words per set (load factor <= 1/2)
-// the words the host reads; M_ERROR and M_CHANGED sit where k_q_reach and the quotient's tables expect them
-enum { M_LABELS = 0, M_PAIRS = 1, M_ERROR = Q_ERROR, M_CHANGED = Q_CHANGED, M_MAXDST = 4, M_EDGES = 5, M_OVERFLOW = 6, M_WORDS = 8 };
+// the words the host reads; M_ERROR sits where the quotient's tables expect it (word 3 is free)
+enum { M_LABELS = 0, M_PAIRS = 1, M_ERROR = Q_ERROR, M_MAXDST = 4, M_EDGES = 5, M_OVERFLOW = 6, M_WORDS = 8 };
 
 __device__ inline unsigned long long m_row_hash(const int32_t *row, int n_obs) {
     unsigned long long h = 0x9e3779b97f4a7c15ull;

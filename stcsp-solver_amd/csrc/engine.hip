@@ -52,46 +52,12 @@
 
 using namespace stcsp;
 
+#include "automaton.hpp"
 #include "dev_kernels.hpp"
-#include "dev_postproc.hpp"
-#include "dev_quotient.hpp"
-#include "dev_monitor.hpp"
-#include "monitor_host.hpp"
-#include "dev_generate.hpp"
-#include "generate_host.hpp"
-#include "dev_repair.hpp"
-#include "dev_infer.hpp"
-#include "repair_host.hpp"
-#include "infer_host.hpp"
 
 using namespace stcsp::dev;
 
 namespace {
-// widest adversarial variable the device post-processing passes take (cover sets of kPostMaxWidth / 32 words per state)
-constexpr long long kPostMaxWidth = 4096;
-// ------------------------------------------------------------------ host side
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    hipError_t alloc(size_t count) {
-        release();
-        n = count;
-        return hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
-    }
-    hipError_t upload(const std::vector<T> &v) {
-        hipError_t e = alloc(v.size());
-        if (e != hipSuccess) return e;
-        if (!v.empty()) e = hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-        return e;
-    }
-};
 
 thread_local std::string g_create_error;
 
@@ -196,75 +162,15 @@ struct stcsp_engine {
     int32_t *h_oval = nullptr;
     uint8_t *h_fail = nullptr;
     size_t h_edge_cap = 0, h_state_cap = 0;
-    // device post-processing (dev_postproc.hpp) over the compacted export
+    // the services on the exported automaton (automaton.hip): post-processing, quotient, monitor, generator, repair, inference
     bool exp_on_device = false;  // d_osrc/d_odst/d_oval/d_state_keys describe the last exported automaton
     size_t exp_edges = 0;
-    DevBuf<uint8_t> d_pvalid, d_pfinal, d_palive, d_pnodeok;
-    DevBuf<uint32_t> d_pcover;
-    std::vector<uint8_t> p_valid, p_final, p_alive;
-    // bisimulation quotient (dev_quotient.hpp) over the flags the last postprocess() left in d_pvalid / d_pfinal / d_palive
-    bool post_done = false;
     std::vector<uint8_t> default_observable;  // [N] every variable whose name does not start with "_V"
-    DevBuf<uint8_t> d_qlive;
-    DevBuf<int32_t> d_qobs;
-    DevBuf<uint32_t> d_qsrc, d_qdst, d_qlid, d_qcls[2], d_qcnt, d_qtab_e, d_qtab_s, d_qctl;
-    DevBuf<unsigned long long> d_qacc[2];
-    std::vector<int32_t> q_class;
-    std::vector<uint32_t> q_raw, q_cnt;
-    // stream monitor (dev_monitor.hpp): the look-up structures of the last monitor_build(), valid while mon_built
-    bool mon_built = false, mon_root_live = false, mon_host_built = false;
-    int mon_n_obs = 0, mon_max_dst = 0;
-    uint32_t mon_mask = 0;
-    std::vector<uint8_t> mon_observable, mon_live;
-    stcsp::HostMonitor mon_host;  // built when the first stream falls back to the host twin
-    DevBuf<uint8_t> d_mlive, d_mfin;
-    DevBuf<int32_t> d_mobs, d_mrows, d_macc, d_mnend;
-    DevBuf<uint32_t> d_mltab, d_mhead, d_mdst0, d_mdst, d_mnext, d_mctl, d_mlid;
-    DevBuf<unsigned long long> d_mkeys;
-    DevBuf<long long> d_moff;
-    hipEvent_t ev_m[3] = {nullptr, nullptr, nullptr};
-    std::vector<int32_t> m_acc, m_nend;
-    std::vector<uint8_t> m_fin;
-    // stream generator (dev_generate.hpp): the structures of the last generator_build(), valid while gen_built
-    bool gen_built = false, gen_root_live = false;
-    int gen_n_obs = 0, gen_horizon = 0;
-    std::vector<double> gen_count;
-    std::vector<uint8_t> gen_live;
-    DevBuf<uint8_t> d_glive, d_gfin;
-    DevBuf<int32_t> d_gobs, d_gout;
-    DevBuf<uint32_t> d_goff, d_gcur, d_gseg, d_geid, d_gdst, d_gtile, d_gctl;
-    DevBuf<double> d_gw, d_gcount;
-    DevBuf<unsigned long long> d_granks;
-    hipEvent_t ev_g[2] = {nullptr, nullptr};
-    std::vector<int32_t> g_values;
-    std::vector<uint8_t> g_fin;
-    // stream repair (dev_repair.hpp): label ids per position of the generator's CSR, valid while gen_built && rep_built
-    bool rep_built = false;
-    uint32_t rep_n_labels = 0, rep_n_long = 0, rep_total = 0, rep_wave_segment = 0;
-    DevBuf<uint32_t> d_rtab, d_rlid, d_rrep, d_rlong, d_rctl, d_rG, d_rcost;
-    DevBuf<RepStream> d_rstreams;
-    DevBuf<int32_t> d_rweights, d_rrows, d_rout, d_rdist, d_rnchg;
-    DevBuf<uint8_t> d_rfin;
-    hipEvent_t ev_r[4] = {nullptr, nullptr, nullptr, nullptr};
-    std::vector<int32_t> r_dist, r_values, r_nchg;
-    std::vector<uint8_t> r_fin;
-    // stream inference (dev_infer.hpp): the value dictionaries of the labels, valid while gen_built && rep_built && inf_built
-    bool inf_built = false;
-    uint32_t inf_words = 0;                      // bitmap words per step: the sum over the variables
-    std::vector<std::vector<int32_t>> inf_dict;  // [n_obs] the sorted distinct values the labels carry
-    std::vector<uint32_t> inf_word_off;          // [n_obs] first bitmap word of a variable
-    DevBuf<uint32_t> d_ividx, d_iwoff, d_ibits, d_ictl;
-    DevBuf<InfStream> d_istreams;
-    DevBuf<double> d_iB, d_icount;
-    DevBuf<uint8_t> d_iF, d_imatch, d_ifeas, d_ifin;
-    DevBuf<int32_t> d_irows, d_iout, d_instates, d_ilabrows;
-    DevBuf<unsigned long long> d_iranks;
-    hipEvent_t ev_i[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    std::vector<double> i_count;
-    std::vector<uint8_t> i_feas, i_fin;
-    std::vector<int64_t> i_soff;
-    std::vector<int32_t> i_sval, i_nstates, i_values;
-    std::vector<uint32_t> i_bits;
+    AutomatonServices services;
+    AutomatonView view() {
+        return {stream, ctx.N, ctx.KL, n_states, exp_edges, d_osrc.p, d_odst.p, d_oval.p, d_state_keys.p, h_osrc, h_odst, h_oval, mgr.lb.data(), mgr.ub.data(),
+                mgr.n_sig, mgr.n_until, mgr.n_until_cons, default_observable.data(), sharded, truncated, exp_on_device, &err};
+    }
 
     ~stcsp_engine() {
         // the device writes several of the pinned buffers freed below (progress mirror, streamed result arrays) from
@@ -298,14 +204,6 @@ struct stcsp_engine {
         for (int i = 0; i < 2; i++)
             if (ev_c[i]) (void)hipEventDestroy(ev_c[i]);
         if (ev_k) (void)hipEventDestroy(ev_k);
-        for (int i = 0; i < 3; i++)
-            if (ev_m[i]) (void)hipEventDestroy(ev_m[i]);
-        for (int i = 0; i < 2; i++)
-            if (ev_g[i]) (void)hipEventDestroy(ev_g[i]);
-        for (int i = 0; i < 4; i++)
-            if (ev_r[i]) (void)hipEventDestroy(ev_r[i]);
-        for (int i = 0; i < 7; i++)
-            if (ev_i[i]) (void)hipEventDestroy(ev_i[i]);
         if (stream) (void)hipStreamDestroy(stream);
     }
 
@@ -318,11 +216,6 @@ struct stcsp_engine {
         err = buf;
         return code;
     }
-#define HIPCHK(call)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (call);                                                                             \
-        if (e_ != hipSuccess) return fail(STCSP_E_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
 
     // chunk c (values lb + 32 c ...) of variable v's initial domain [lb, ub]; interval domains: chunk 0 = lb, chunk 1 = ub
     uint32_t init_chunk(int v, int c) const {
@@ -1147,11 +1040,7 @@ struct stcsp_engine {
         translation_stops = 0;
         finished = false;
         exp_on_device = false;
-        post_done = false;
-        mon_built = false;
-        gen_built = false;
-        rep_built = false;
-        inf_built = false;
+        services.invalidate();
         ev_used = 0;
         seconds_expand_kernel = 0;
         expand_launches = 0;
@@ -1548,7 +1437,7 @@ struct stcsp_engine {
     int ensure_export_capacity(size_t E) {
         const int N = ctx.N;
         if (d_osrc.n < E) {
-            const size_t cap = std::max(E + E / 4 + 256, d_osrc.n * 2);
+            const size_t cap = std::max(grown(E), d_osrc.n * 2);
             DevBuf<long long> ns, nd;
             DevBuf<int32_t> nv;
             HIPCHK(ns.alloc(cap));
@@ -1568,7 +1457,7 @@ struct stcsp_engine {
             std::swap(d_oval.n, nv.n);
         }
         if (h_edge_cap < E) {
-            const size_t cap = std::max(E + E / 4 + 256, h_edge_cap * 2);
+            const size_t cap = std::max(grown(E), h_edge_cap * 2);
             long long *ns = nullptr, *nd = nullptr;
             int32_t *nv = nullptr;
             HIPCHK(hipHostMalloc((void **)&ns, cap * sizeof(long long)));
@@ -1658,7 +1547,7 @@ struct stcsp_engine {
         if (upto <= streamed_states) return STCSP_OK;
         const int sl = std::max(ctx.sig_len, 0);
         if (h_key_cap < upto) {
-            const size_t cap = std::max<size_t>((size_t)upto + upto / 4 + 256, h_key_cap * 2);
+            const size_t cap = std::max(grown(upto), h_key_cap * 2);
             int32_t *nc = nullptr, *nsg = nullptr;
             HIPCHK(hipHostMalloc((void **)&nc, cap * sizeof(int32_t)));
             HIPCHK(hipHostMalloc((void **)&nsg, std::max<size_t>(cap * sl, 1) * sizeof(int32_t)));
@@ -2119,1056 +2008,6 @@ struct stcsp_engine {
         return STCSP_OK;  // not waited for (like commit): `records` must stay valid until the next expand_local / finish
     }
 
-    // graphTraverse / adversarialTraverse / adversarialTraverse2 on the device (dev_postproc.hpp)
-    int postprocess(const stcsp_post_options *po, stcsp_post_result *out) {
-        if (sharded) return fail(STCSP_E_STATE, "device post-processing is for unsharded engines (merge shards on the host)");
-        if (!exp_on_device) return fail(STCSP_E_STATE, "postprocess needs the device export of a finished solve (export first)");
-        const int N = ctx.N;
-        const int a1 = po ? po->adversarial_var : -1, op = po ? po->adversarial2_op : -1, ava = po ? po->adversarial2_ava : -1;
-        if (a1 >= N || op >= N || ava >= N || a1 < -1 || op < -1 || (op >= 0 && ava < 0))
-            return fail(STCSP_E_INVALID, "postprocess: variable index out of range");
-        auto t0 = std::chrono::steady_clock::now();
-        post_done = false;
-        mon_built = false;
-        gen_built = false;
-        rep_built = false;
-        inf_built = false;
-        const size_t E = exp_edges;
-        const uint32_t S = n_states;
-        auto width = [&](int v) { return (long long)mgr.ub[v] - (long long)mgr.lb[v] + 1; };
-        // cover sets of CW = ceil(width / 32) words (dev_postproc.hpp); without interval domains widths are at most 128 (create()
-        // refuses wider), with them the adversarial variables may have at most kPostMaxWidth values
-        for (int v : {a1, op, op >= 0 ? ava : -1})
-            if (v >= 0 && width(v) > kPostMaxWidth)
-                return fail(STCSP_E_UNSUPPORTED, "postprocess: variable %d has %lld values; the device adversarial passes take at most %lld (%lld cover words per state)",
-                            v, width(v), kPostMaxWidth, kPostMaxWidth / 32);
-        auto cover_w = [&](int v) { return (int)((width(v) + 31) / 32); };
-        auto last_full = [&](int v) { return width(v) % 32 == 0 ? 0xffffffffu : ((1u << (width(v) % 32)) - 1u); };
-        const int wa = op >= 0 ? (int)width(ava) : 0;
-        const int cw1 = a1 >= 0 ? cover_w(a1) : 1, cw2 = op >= 0 ? cover_w(op) : 1;
-        if (d_pvalid.n < S) {
-            const size_t cap = (size_t)S + S / 4 + 256;
-            HIPCHK(d_pvalid.alloc(cap));
-            HIPCHK(d_pfinal.alloc(cap));
-            HIPCHK(d_pnodeok.alloc(cap));
-        }
-        const size_t cover_words = (size_t)S * std::max(cw1, std::max(1, wa) * cw2);
-        if (d_pcover.n < cover_words) HIPCHK(d_pcover.alloc(cover_words + cover_words / 4 + 256));
-        if (d_palive.n < E + 1) HIPCHK(d_palive.alloc(E + E / 4 + 256));
-        if (!d_post.p) HIPCHK(d_post.alloc(4));
-        const unsigned eb = (unsigned)((E + 255) / 256), sb = (S + 255) / 256;
-        const long long *src = d_osrc.p, *dst = d_odst.p;
-        const int32_t *val = d_oval.p;
-        uint32_t *changed = d_post.p;
-        // one round = the kernels `body` enqueues; returns the number of rounds until nothing changed
-        auto fixpoint = [&](int &rounds, auto body) -> int {  // HIPCHK returns the error code from the enclosing lambda
-            for (rounds = 0;; rounds++) {
-                HIPCHK(hipMemsetAsync(changed, 0, sizeof(uint32_t), stream));
-                const int rb = body();
-                if (rb != STCSP_OK) return rb;
-                uint32_t ch = 0;
-                HIPCHK(hipMemcpyAsync(&ch, changed, sizeof ch, hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                if (!ch) return STCSP_OK;
-                if (rounds > (int)S + 8) return fail(STCSP_E_INTERNAL, "post-processing fixpoint did not converge");
-            }
-        };
-        int rounds[3] = {0, 0, 0};
-        HIPCHK(hipMemsetAsync(d_palive.p, 1, E + 1, stream));
-        // graphTraverse (src/graph.cpp:357-418); the loop bound numSignVar + numUntil is the reference's
-        hipLaunchKernelGGL(k_trav_init, dim3(sb), dim3(256), 0, stream, S, (const uint32_t *)d_state_keys.p, ctx.KL, mgr.n_sig,
-                           mgr.n_sig + mgr.n_until, (int)(mgr.n_until_cons == 0), d_pvalid.p, d_pfinal.p);
-        if (E) {
-            int rc = fixpoint(rounds[0], [&] {
-                hipLaunchKernelGGL(k_trav_back, dim3(eb), dim3(256), 0, stream, (uint32_t)E, src, dst, (const uint8_t *)d_palive.p, d_pvalid.p, changed);
-                return (int)STCSP_OK;
-            });
-            if (rc != STCSP_OK) return rc;
-            hipLaunchKernelGGL(k_kill_into_invalid, dim3(eb), dim3(256), 0, stream, (uint32_t)E, src, dst, d_palive.p, (const uint8_t *)d_pvalid.p, 1);
-        }
-        int adver1 = -1, adver2 = -1;
-        uint8_t root_valid = 0;
-        if (a1 >= 0) {  // adversarialTraverse (src/graph.cpp:304-355)
-            const uint32_t full = last_full(a1);
-            int rc = fixpoint(rounds[1], [&] {
-                HIPCHK(hipMemsetAsync(d_pcover.p, 0, (size_t)S * cw1 * sizeof(uint32_t), stream));
-                if (E)
-                    hipLaunchKernelGGL(k_adv_cover, dim3(eb), dim3(256), 0, stream, (uint32_t)E, src, dst, val, N, a1, mgr.lb[a1], cw1,
-                                       (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_pcover.p);
-                hipLaunchKernelGGL(k_adv_check, dim3(sb), dim3(256), 0, stream, S, (const uint32_t *)d_pcover.p, cw1, full, d_pvalid.p, changed);
-                return (int)STCSP_OK;
-            });
-            if (rc != STCSP_OK) return rc;
-            if (E) hipLaunchKernelGGL(k_kill_into_invalid, dim3(eb), dim3(256), 0, stream, (uint32_t)E, src, dst, d_palive.p, (const uint8_t *)d_pvalid.p, 0);
-            HIPCHK(hipMemcpyAsync(&root_valid, d_pvalid.p, 1, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            adver1 = root_valid;
-        }
-        if (op >= 0) {  // adversarialTraverse2 (src/graph.cpp:247-302)
-            const uint32_t full = last_full(op);
-            int rc = fixpoint(rounds[2], [&] {
-                HIPCHK(hipMemsetAsync(d_pcover.p, 0, (size_t)S * wa * cw2 * sizeof(uint32_t), stream));
-                if (E)
-                    hipLaunchKernelGGL(k_adv2_cover, dim3(eb), dim3(256), 0, stream, (uint32_t)E, src, dst, val, N, op, ava, mgr.lb[op], mgr.lb[ava],
-                                       wa, cw2, (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_pcover.p);
-                hipLaunchKernelGGL(k_adv2_check, dim3(sb), dim3(256), 0, stream, S, (const uint32_t *)d_pcover.p, wa, cw2, full, d_pvalid.p, d_pnodeok.p,
-                                   changed);
-                if (E)
-                    hipLaunchKernelGGL(k_adv2_kill, dim3(eb), dim3(256), 0, stream, (uint32_t)E, src, dst, val, N, ava, mgr.lb[ava], wa, cw2, full, d_palive.p,
-                                       (const uint8_t *)d_pvalid.p, (const uint8_t *)d_pnodeok.p, (const uint32_t *)d_pcover.p);
-                return (int)STCSP_OK;
-            });
-            if (rc != STCSP_OK) return rc;
-            HIPCHK(hipMemcpyAsync(&root_valid, d_pvalid.p, 1, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            adver2 = root_valid;
-            // the reference drops the edges into invalid states only when the root survived (graph.cpp:288-301)
-            if (root_valid && E)
-                hipLaunchKernelGGL(k_kill_into_invalid, dim3(eb), dim3(256), 0, stream, (uint32_t)E, src, dst, d_palive.p, (const uint8_t *)d_pvalid.p, 0);
-        }
-        HIPCHK(hipGetLastError());
-        p_valid.resize(S);
-        p_final.resize(S);
-        p_alive.resize(E + 1);
-        HIPCHK(hipMemcpyAsync(p_valid.data(), d_pvalid.p, S, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipMemcpyAsync(p_final.data(), d_pfinal.p, S, hipMemcpyDeviceToHost, stream));
-        if (E) HIPCHK(hipMemcpyAsync(p_alive.data(), d_palive.p, E, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        memset(out, 0, sizeof *out);
-        out->n_states = S;
-        out->n_edges = (int64_t)E;
-        out->state_valid = p_valid.data();
-        out->state_final = p_final.data();
-        out->edge_alive = p_alive.data();
-        out->adver1 = adver1;
-        out->adver2 = adver2;
-        for (int i = 0; i < 3; i++) out->rounds[i] = rounds[i];
-        out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        post_done = true;
-        return STCSP_OK;
-    }
-
-    // Bisimulation quotient of the live automaton on the device (dev_quotient.hpp): classes of the
-    // states that are valid and reachable from the root over alive edges, under the labels projected on `observable`.
-    int quotient(const stcsp_quotient_options *qo, stcsp_quotient_result *out) {
-        if (sharded) return fail(STCSP_E_UNSUPPORTED, "the device quotient is for unsharded engines (stcsp_automaton_bisimulation on the merged automaton)");
-        if (!exp_on_device || !post_done) return fail(STCSP_E_STATE, "quotient needs the flags of postprocess() on the last solve");
-        if (truncated) return fail(STCSP_E_STATE, "quotient after a truncated solve: the open states of a partial automaton have no known language");
-        auto t0 = std::chrono::steady_clock::now();
-        const int N = ctx.N;
-        const uint32_t E = (uint32_t)exp_edges, S = n_states;
-        const uint8_t *mask = qo && qo->observable ? qo->observable : default_observable.data();
-        std::vector<int32_t> obs;
-        for (int v = 0; v < N; v++)
-            if (mask[v]) obs.push_back(v);
-        auto pow2 = [](size_t n) {
-            size_t c = 1024;
-            while (c < 2 * n) c <<= 1;
-            return c;
-        };
-        const size_t cap_e = pow2(E), cap_s = pow2(S);
-        if (cap_e > 0x80000000ull) return fail(STCSP_E_NOMEM, "edge list too large for the device quotient");
-        if (d_qlive.n < S) {
-            const size_t cap = (size_t)S + S / 4 + 256;
-            HIPCHK(d_qlive.alloc(cap));
-            HIPCHK(d_qcls[0].alloc(cap));
-            HIPCHK(d_qcls[1].alloc(cap));
-            HIPCHK(d_qcnt.alloc(cap));
-            HIPCHK(d_qacc[0].alloc(cap));
-            HIPCHK(d_qacc[1].alloc(cap));
-        }
-        if (d_qsrc.n < (size_t)E + 1) {
-            const size_t cap = (size_t)E + E / 4 + 256;
-            HIPCHK(d_qsrc.alloc(cap));
-            HIPCHK(d_qdst.alloc(cap));
-            HIPCHK(d_qlid.alloc(cap));
-        }
-        if (d_qtab_e.n < cap_e) HIPCHK(d_qtab_e.alloc(cap_e));
-        if (d_qtab_s.n < cap_s) HIPCHK(d_qtab_s.alloc(cap_s));
-        if (d_qobs.n < (size_t)N) HIPCHK(d_qobs.alloc((size_t)N));
-        if (!d_qctl.p) HIPCHK(d_qctl.alloc(Q_WORDS));
-        const unsigned eb = (E + 255) / 256, sb = (S + 255) / 256;
-        const uint32_t mask_e = (uint32_t)(cap_e - 1), mask_s = (uint32_t)(cap_s - 1);
-        uint32_t ctl[Q_WORDS] = {0, 0, 0, 0};
-        auto read_ctl = [&]() -> int {
-            HIPCHK(hipMemcpyAsync(ctl, d_qctl.p, sizeof ctl, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            return STCSP_OK;
-        };
-        auto check = [&]() -> int {
-            int rc = read_ctl();
-            if (rc != STCSP_OK) return rc;
-            if (ctl[Q_ERROR] & Q_ERR_TABLE_FULL) return fail(STCSP_E_INTERNAL, "quotient: a device table overflowed");
-            if (ctl[Q_ERROR]) return fail(STCSP_E_INTERNAL, "quotient: a state differs from its class representative (signature collision, flags %u)", ctl[Q_ERROR]);
-            return STCSP_OK;
-        };
-        int rc;
-        if (!obs.empty()) HIPCHK(hipMemcpyAsync(d_qobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemsetAsync(d_qctl.p, 0, sizeof ctl, stream));
-        // the live automaton: forward reachability from a valid root (what write_dot walks)
-        HIPCHK(hipMemsetAsync(d_qlive.p, 0, S, stream));
-        HIPCHK(hipMemcpyAsync(d_qlive.p, d_pvalid.p, 1, hipMemcpyDeviceToDevice, stream));
-        for (int sweeps = 0; E; sweeps++) {
-            HIPCHK(hipMemsetAsync(d_qctl.p + Q_CHANGED, 0, sizeof(uint32_t), stream));
-            hipLaunchKernelGGL(k_q_reach, dim3(eb), dim3(256), 0, stream, E, (const long long *)d_osrc.p, (const long long *)d_odst.p,
-                               (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_qlive.p, d_qctl.p);
-            if ((rc = read_ctl()) != STCSP_OK) return rc;
-            if (!ctl[Q_CHANGED]) break;
-            if (sweeps > (int)S + 8) return fail(STCSP_E_INTERNAL, "quotient: reachability did not converge");
-        }
-        // label ids (the one sweep over the label rows) and the 12-byte edge records of the rounds
-        if (E) {
-            HIPCHK(hipMemsetAsync(d_qtab_e.p, 0xff, cap_e * sizeof(uint32_t), stream));
-            hipLaunchKernelGGL(k_q_labels, dim3(eb), dim3(256), 0, stream, E, (const long long *)d_osrc.p, (const long long *)d_odst.p,
-                               (const int32_t *)d_oval.p, N, (const int32_t *)d_qobs.p, (int)obs.size(), (const uint8_t *)d_palive.p,
-                               (const uint8_t *)d_qlive.p, d_qtab_e.p, mask_e, d_qsrc.p, d_qdst.p, d_qlid.p, d_qctl.p);
-        }
-        // every live state starts in class 0; a round splits the classes by (final, set of (label id, class of destination))
-        HIPCHK(hipMemsetAsync(d_qcls[0].p, 0, (size_t)S * sizeof(uint32_t), stream));
-        int cur = 0, rounds = 0;
-        bool dedup = true;  // until round 1 has shown that no state has two edges with one projected label
-        auto edge_sweep = [&](bool dd) -> int {
-            hipLaunchKernelGGL(k_q_state_init, dim3(sb), dim3(256), 0, stream, S, (const uint8_t *)d_pfinal.p, d_qacc[0].p, d_qacc[1].p, d_qcnt.p);
-            if (!E) return STCSP_OK;
-            if (dd) HIPCHK(hipMemsetAsync(d_qtab_e.p, 0xff, cap_e * sizeof(uint32_t), stream));
-            hipLaunchKernelGGL(k_q_edges, dim3(eb), dim3(256), 0, stream, E, (const uint32_t *)d_qsrc.p, (const uint32_t *)d_qdst.p,
-                               (const uint32_t *)d_qlid.p, (const uint32_t *)d_qcls[cur].p, (int)dd, d_qtab_e.p, mask_e, d_qacc[0].p, d_qacc[1].p,
-                               d_qcnt.p, d_qctl.p);
-            return STCSP_OK;
-        };
-        for (uint32_t prev = 0;;) {
-            rounds++;
-            HIPCHK(hipMemsetAsync(d_qctl.p, 0, 2 * sizeof(uint32_t), stream));  // Q_CLASSES, Q_DUPS
-            if ((rc = edge_sweep(dedup)) != STCSP_OK) return rc;
-            HIPCHK(hipMemsetAsync(d_qtab_s.p, 0xff, cap_s * sizeof(uint32_t), stream));
-            hipLaunchKernelGGL(k_q_number, dim3(sb), dim3(256), 0, stream, S, (const uint8_t *)d_qlive.p, (const uint32_t *)d_qcls[cur].p,
-                               (const unsigned long long *)d_qacc[0].p, (const unsigned long long *)d_qacc[1].p, d_qtab_s.p, mask_s,
-                               d_qcls[1 - cur].p, d_qctl.p);
-            if ((rc = check()) != STCSP_OK) return rc;
-            cur = 1 - cur;
-            if (rounds == 1 && ctl[Q_DUPS] == 0) dedup = false;
-            if (ctl[Q_CLASSES] == prev) break;
-            prev = ctl[Q_CLASSES];
-            if ((uint32_t)rounds > S + 1) return fail(STCSP_E_INTERNAL, "quotient: refinement did not converge");
-        }
-        // exact verification against the class representatives; leaves the distinct pairs per state in d_qcnt
-        if ((rc = edge_sweep(true)) != STCSP_OK) return rc;
-        if (E)
-            hipLaunchKernelGGL(k_q_verify_edges, dim3(eb), dim3(256), 0, stream, E, (const uint32_t *)d_qsrc.p, (const uint32_t *)d_qdst.p,
-                               (const uint32_t *)d_qlid.p, (const uint32_t *)d_qcls[cur].p, (const uint32_t *)d_qtab_e.p, mask_e, d_qctl.p);
-        hipLaunchKernelGGL(k_q_verify_states, dim3(sb), dim3(256), 0, stream, S, (const uint8_t *)d_qlive.p, (const uint8_t *)d_pfinal.p,
-                           (const uint32_t *)d_qcls[cur].p, (const uint32_t *)d_qcnt.p, d_qctl.p);
-        HIPCHK(hipGetLastError());
-        q_raw.resize(S);
-        q_cnt.resize(S);
-        HIPCHK(hipMemcpyAsync(q_raw.data(), d_qcls[cur].p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipMemcpyAsync(q_cnt.data(), d_qcnt.p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        if ((rc = check()) != STCSP_OK) return rc;
-        // canonical class numbers: by least member (the first state, in index order, that shows the class)
-        q_class.assign(S, -1);
-        std::vector<int32_t> number(S, -1);
-        int64_t n_live = 0, n_classes = 0, n_class_edges = 0;
-        for (uint32_t s = 0; s < S; s++) {
-            const uint32_t r = q_raw[s];
-            if (r == kQEmpty) continue;
-            n_live++;
-            if (number[r] < 0) {
-                number[r] = (int32_t)n_classes++;
-                n_class_edges += q_cnt[r];
-            }
-            q_class[s] = number[r];
-        }
-        memset(out, 0, sizeof *out);
-        out->n_states = n_live;
-        out->n_classes = n_classes;
-        out->n_class_edges = n_class_edges;
-        out->state_class = q_class.data();
-        out->rounds = rounds;
-        out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return STCSP_OK;
-    }
-
-    // Stream monitor, build (dev_monitor.hpp): label ids and the (state, label id) -> destinations
-    // multimap of the live automaton under one mask, from the flags the last postprocess() left in HBM.
-    int monitor_build(const stcsp_monitor_options *mo, stcsp_monitor_info *info) {
-        if (sharded) return fail(STCSP_E_UNSUPPORTED, "the device monitor is for unsharded engines (stcsp_automaton_check_streams on the merged automaton)");
-        if (!exp_on_device || !post_done) return fail(STCSP_E_STATE, "monitor_build needs the flags of postprocess() on the last solve");
-        if (truncated) return fail(STCSP_E_STATE, "monitor_build after a truncated solve: the open states of a partial automaton have no known language");
-        auto t0 = std::chrono::steady_clock::now();
-        mon_built = mon_host_built = false;
-        const int N = ctx.N;
-        const uint32_t E = (uint32_t)exp_edges, S = n_states;
-        const uint8_t *mask = mo && mo->observable ? mo->observable : default_observable.data();
-        mon_observable.assign((size_t)N, 0);
-        std::vector<int32_t> obs;
-        for (int v = 0; v < N; v++)
-            if (mask[v]) {
-                obs.push_back(v);
-                mon_observable[(size_t)v] = 1;
-            }
-        size_t cap = 1024;
-        while (cap < 2 * (size_t)E) cap <<= 1;
-        if (cap > 0x80000000ull) return fail(STCSP_E_NOMEM, "edge list too large for the device monitor");
-        if (d_mlive.n < S) HIPCHK(d_mlive.alloc((size_t)S + S / 4 + 256));
-        if (d_mdst.n < (size_t)E + 1) {
-            const size_t c = (size_t)E + E / 4 + 256;
-            HIPCHK(d_mdst.alloc(c));
-            HIPCHK(d_mnext.alloc(c));
-        }
-        if (d_mltab.n < cap) {
-            HIPCHK(d_mltab.alloc(cap));
-            HIPCHK(d_mhead.alloc(cap));
-            HIPCHK(d_mdst0.alloc(cap));
-            HIPCHK(d_mkeys.alloc(cap));
-        }
-        if (d_mobs.n < (size_t)N) HIPCHK(d_mobs.alloc((size_t)N));
-        if (!d_mctl.p) HIPCHK(d_mctl.alloc(M_WORDS));
-        const unsigned eb = (E + 255) / 256;
-        uint32_t ctl[M_WORDS] = {0};
-        if (!obs.empty()) HIPCHK(hipMemcpyAsync(d_mobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemsetAsync(d_mctl.p, 0, sizeof ctl, stream));
-        // the live automaton: forward reachability from a valid root, as the quotient does it
-        HIPCHK(hipMemsetAsync(d_mlive.p, 0, S, stream));
-        HIPCHK(hipMemcpyAsync(d_mlive.p, d_pvalid.p, 1, hipMemcpyDeviceToDevice, stream));
-        for (int sweeps = 0; E; sweeps++) {
-            HIPCHK(hipMemsetAsync(d_mctl.p + M_CHANGED, 0, sizeof(uint32_t), stream));
-            hipLaunchKernelGGL(k_q_reach, dim3(eb), dim3(256), 0, stream, E, (const long long *)d_osrc.p, (const long long *)d_odst.p,
-                               (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_mlive.p, d_mctl.p);
-            HIPCHK(hipMemcpyAsync(ctl, d_mctl.p, sizeof ctl, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            if (!ctl[M_CHANGED]) break;
-            if (sweeps > (int)S + 8) return fail(STCSP_E_INTERNAL, "monitor: reachability did not converge");
-        }
-        if (E) {
-            HIPCHK(hipMemsetAsync(d_mltab.p, 0xff, cap * sizeof(uint32_t), stream));
-            HIPCHK(hipMemsetAsync(d_mhead.p, 0xff, cap * sizeof(uint32_t), stream));
-            HIPCHK(hipMemsetAsync(d_mkeys.p, 0xff, cap * sizeof(unsigned long long), stream));
-            hipLaunchKernelGGL(k_m_build, dim3(eb), dim3(256), 0, stream, E, (const long long *)d_osrc.p, (const long long *)d_odst.p,
-                               (const int32_t *)d_oval.p, N, (const int32_t *)d_mobs.p, (int)obs.size(), (const uint8_t *)d_palive.p,
-                               (const uint8_t *)d_mlive.p, d_mltab.p, d_mkeys.p, d_mhead.p, (uint32_t)(cap - 1), d_mdst.p, d_mnext.p, d_mctl.p);
-            hipLaunchKernelGGL(k_m_finish, dim3((unsigned)(cap / 256)), dim3(256), 0, stream, (uint32_t)cap, (const unsigned long long *)d_mkeys.p,
-                               (const uint32_t *)d_mhead.p, d_mnext.p, (const uint32_t *)d_mdst.p, d_mdst0.p, d_mctl.p);
-            HIPCHK(hipGetLastError());
-        }
-        mon_live.resize(S);
-        HIPCHK(hipMemcpyAsync(mon_live.data(), d_mlive.p, S, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipMemcpyAsync(ctl, d_mctl.p, sizeof ctl, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        if (ctl[M_ERROR]) return fail(STCSP_E_INTERNAL, "monitor: a device table overflowed");
-        int64_t n_live = 0;
-        for (uint32_t s = 0; s < S; s++) n_live += mon_live[s];
-        mon_root_live = S > 0 && mon_live[0];
-        mon_n_obs = (int)obs.size();
-        mon_max_dst = (int)std::max(ctl[M_MAXDST], ctl[M_PAIRS] ? 1u : 0u);
-        mon_mask = (uint32_t)(cap - 1);
-        mon_built = true;
-        memset(info, 0, sizeof *info);
-        info->n_states = n_live;
-        info->n_edges = ctl[M_EDGES];
-        info->n_labels = ctl[M_LABELS];
-        info->n_pairs = ctl[M_PAIRS];
-        info->table_bytes = (int64_t)(E ? cap * (3 * sizeof(uint32_t) + sizeof(unsigned long long)) + 2 * (size_t)E * sizeof(uint32_t) : 0) + S;
-        info->n_observable = mon_n_obs;
-        info->max_destinations = mon_max_dst;
-        info->set_capacity = kMonSetCap;
-        info->root_live = mon_root_live;
-        info->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return STCSP_OK;
-    }
-
-    // Stream monitor, check: every stream's accepted_len / n_end / end_final (contract: stcsp_engine.h). Exact always: the
-    // streams the state-set kernel marks as over its capacity are finished by the host twin (monitor_host.hpp).
-    int monitor_check(const stcsp_monitor_streams *ms, stcsp_monitor_result *out) {
-        if (sharded) return fail(STCSP_E_UNSUPPORTED, "the device monitor is for unsharded engines (stcsp_automaton_check_streams on the merged automaton)");
-        if (!exp_on_device || !post_done || truncated || !mon_built)
-            return fail(STCSP_E_STATE, "monitor_check needs monitor_build() after the last postprocess()");
-        if (!stcsp::monitor_offsets_ok(ms->n_streams, ms->offsets)) return fail(STCSP_E_INVALID, "monitor_check: malformed stream offsets");
-        auto t0 = std::chrono::steady_clock::now();
-        const size_t n = (size_t)ms->n_streams;
-        const size_t steps = n ? (size_t)ms->offsets[n] : 0;
-        if (steps && mon_n_obs && !ms->values) return fail(STCSP_E_INVALID, "monitor_check: no step values");
-        if (n >= 0x7fffffffull || steps >= 0x7fffffffull) return fail(STCSP_E_NOMEM, "monitor_check: too many streams or steps for one call");
-        m_acc.assign(n, 0);
-        m_nend.assign(n, 0);
-        m_fin.assign(n, 0);
-        memset(out, 0, sizeof *out);
-        out->n_streams = ms->n_streams;
-        out->accepted_len = m_acc.data();
-        out->n_end = m_nend.data();
-        out->end_final = m_fin.data();
-        if (n && mon_root_live) {
-            const bool sets = mon_max_dst > 1 || (ms->flags & STCSP_MON_FORCE_SETS);
-            const uint32_t E = (uint32_t)exp_edges;
-            if (d_moff.n < n + 1) {
-                const size_t c = n + n / 4 + 256;
-                HIPCHK(d_moff.alloc(c + 1));
-                HIPCHK(d_macc.alloc(c));
-                HIPCHK(d_mnend.alloc(c));
-                HIPCHK(d_mfin.alloc(c));
-            }
-            if (d_mlid.n < steps) HIPCHK(d_mlid.alloc(steps + steps / 4 + 256));
-            if (d_mrows.n < steps * mon_n_obs) HIPCHK(d_mrows.alloc(steps * mon_n_obs + steps * mon_n_obs / 4 + 256));
-            for (int i = 0; i < 3; i++)
-                if (!ev_m[i]) HIPCHK(hipEventCreate(&ev_m[i]));
-            HIPCHK(hipMemcpyAsync(d_moff.p, ms->offsets, (n + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
-            if (steps * mon_n_obs) HIPCHK(hipMemcpyAsync(d_mrows.p, ms->values, steps * mon_n_obs * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipMemsetAsync(d_mctl.p + M_OVERFLOW, 0, sizeof(uint32_t), stream));
-            HIPCHK(hipEventRecord(ev_m[0], stream));
-            if (steps) {
-                if (E)
-                    hipLaunchKernelGGL(k_m_steps, dim3((unsigned)((steps + 255) / 256)), dim3(256), 0, stream, (uint32_t)steps, (const int32_t *)d_mrows.p,
-                                       mon_n_obs, (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_mobs.p, (const uint32_t *)d_mltab.p, mon_mask,
-                                       d_mlid.p);
-                else  // no edge, no label: every step is a rejection
-                    HIPCHK(hipMemsetAsync(d_mlid.p, 0xff, steps * sizeof(uint32_t), stream));
-            }
-            HIPCHK(hipEventRecord(ev_m[1], stream));
-            if (sets)
-                hipLaunchKernelGGL(k_m_walk_sets, dim3((unsigned)n), dim3(64), 0, stream, (uint32_t)n, (const long long *)d_moff.p,
-                                   (const uint32_t *)d_mlid.p, (const unsigned long long *)d_mkeys.p, (const uint32_t *)d_mhead.p,
-                                   (const uint32_t *)d_mnext.p, (const uint32_t *)d_mdst.p, mon_mask, (const uint8_t *)d_pfinal.p, d_macc.p, d_mnend.p,
-                                   d_mfin.p, d_mctl.p);
-            else
-                hipLaunchKernelGGL(k_m_walk_det, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (uint32_t)n, (const long long *)d_moff.p,
-                                   (const uint32_t *)d_mlid.p, (const unsigned long long *)d_mkeys.p, (const uint32_t *)d_mdst0.p, mon_mask,
-                                   (const uint8_t *)d_pfinal.p, d_macc.p, d_mnend.p, d_mfin.p);
-            HIPCHK(hipEventRecord(ev_m[2], stream));
-            HIPCHK(hipGetLastError());
-            uint32_t over = 0;
-            HIPCHK(hipMemcpyAsync(m_acc.data(), d_macc.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(m_nend.data(), d_mnend.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(m_fin.data(), d_mfin.p, n, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(&over, d_mctl.p + M_OVERFLOW, sizeof over, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            float ms_l = 0, ms_w = 0;
-            HIPCHK(hipEventElapsedTime(&ms_l, ev_m[0], ev_m[1]));
-            HIPCHK(hipEventElapsedTime(&ms_w, ev_m[1], ev_m[2]));
-            out->seconds_labels = ms_l * 1e-3;
-            out->seconds_walk = ms_w * 1e-3;
-            out->walk_kernel = sets ? 2 : 1;
-            if (over) {
-                if (!mon_host_built) {
-                    stcsp::MonitorView v;
-                    v.n_vars = ctx.N;
-                    v.n_states = n_states;
-                    v.n_edges = (int64_t)exp_edges;
-                    v.src = (const int64_t *)h_osrc;
-                    v.dst = (const int64_t *)h_odst;
-                    v.values = h_oval;
-                    v.valid = p_valid.data();
-                    v.final_ = p_final.data();
-                    v.alive = p_alive.data();
-                    mon_host.build(v, mon_observable.data());
-                    mon_host_built = true;
-                }
-                for (size_t i = 0; i < n; i++)
-                    if (m_acc[i] < 0) {
-                        mon_host.check_one(ms->values + ms->offsets[i] * mon_n_obs, ms->offsets[i + 1] - ms->offsets[i], &m_acc[i], &m_nend[i], &m_fin[i]);
-                        out->n_host_fallback++;
-                    }
-            }
-        }
-        out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return STCSP_OK;
-    }
-
-    // Stream generator, build (dev_generate.hpp): the live edges by source in canonical order and the
-    // weights W_0 .. W_horizon of every state, from the flags the last postprocess() left in HBM.
-    int generator_build(const stcsp_generator_options *go, stcsp_generator_info *info) {
-        if (sharded) return fail(STCSP_E_UNSUPPORTED, "the device generator is for unsharded engines (stcsp_automaton_generate on the merged automaton)");
-        if (!exp_on_device || !post_done) return fail(STCSP_E_STATE, "generator_build needs the flags of postprocess() on the last solve");
-        if (truncated) return fail(STCSP_E_STATE, "generator_build after a truncated solve: the open states of a partial automaton have no known language");
-        if (!go || go->horizon < 0) return fail(STCSP_E_INVALID, "generator_build: the horizon must not be negative");
-        auto t0 = std::chrono::steady_clock::now();
-        gen_built = false;
-        rep_built = false;
-        inf_built = false;
-        const int N = ctx.N, H = go->horizon;
-        const uint32_t E = (uint32_t)exp_edges, S = n_states;
-        if ((size_t)exp_edges > 0x7fffffffull) return fail(STCSP_E_NOMEM, "edge list too large for the device generator");
-        const uint8_t *mask = go->observable ? go->observable : default_observable.data();
-        std::vector<int32_t> obs;
-        for (int v = 0; v < N; v++)
-            if (mask[v]) obs.push_back(v);
-        const uint32_t n_tiles = (S + kGenScanTile - 1) / kGenScanTile;
-        if (d_glive.n < S) {
-            const size_t c = (size_t)S + S / 4 + 256;
-            HIPCHK(d_glive.alloc(c));
-            HIPCHK(d_goff.alloc(c + 1));
-            HIPCHK(d_gcur.alloc(c));
-            HIPCHK(d_gtile.alloc(c / kGenScanTile + 2));
-        }
-        if (d_gseg.n < E) {
-            const size_t c = (size_t)E + E / 4 + 256;
-            HIPCHK(d_gseg.alloc(c));
-            HIPCHK(d_geid.alloc(c));
-            HIPCHK(d_gdst.alloc(c));
-        }
-        const size_t table = ((size_t)H + 1) * S;
-        if (d_gw.n < table && d_gw.alloc(table) != hipSuccess) {
-            (void)hipGetLastError();
-            d_gw.release();
-            return fail(STCSP_E_NOMEM, "generator_build: no room for the %d x %u table of weights", H + 1, S);
-        }
-        if (d_gcount.n < (size_t)H + 1) HIPCHK(d_gcount.alloc((size_t)H + 1));
-        if (d_gobs.n < (size_t)N) HIPCHK(d_gobs.alloc((size_t)N));
-        if (!d_gctl.p) HIPCHK(d_gctl.alloc(G_WORDS));
-        const unsigned eb = (E + 255) / 256, sb = (S + 255) / 256;
-        uint32_t ctl[G_WORDS] = {0}, total = 0;
-        if (!obs.empty()) HIPCHK(hipMemcpyAsync(d_gobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemsetAsync(d_gctl.p, 0, sizeof ctl, stream));
-        // the live automaton: forward reachability from a valid root, as the quotient does it
-        HIPCHK(hipMemsetAsync(d_glive.p, 0, S, stream));
-        HIPCHK(hipMemcpyAsync(d_glive.p, d_pvalid.p, 1, hipMemcpyDeviceToDevice, stream));
-        for (int sweeps = 0; E; sweeps++) {
-            HIPCHK(hipMemsetAsync(d_gctl.p + G_CHANGED, 0, sizeof(uint32_t), stream));
-            hipLaunchKernelGGL(k_q_reach, dim3(eb), dim3(256), 0, stream, E, (const long long *)d_osrc.p, (const long long *)d_odst.p,
-                               (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_glive.p, d_gctl.p);
-            HIPCHK(hipMemcpyAsync(ctl, d_gctl.p, sizeof ctl, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            if (!ctl[G_CHANGED]) break;
-            if (sweeps > (int)S + 8) return fail(STCSP_E_INTERNAL, "generator: reachability did not converge");
-        }
-        // live edges by source: histogram, exclusive scan over the states, fill through a cursor, canonical order
-        HIPCHK(hipMemsetAsync(d_gcur.p, 0, (size_t)S * sizeof(uint32_t), stream));
-        if (E)
-            hipLaunchKernelGGL(k_g_degree, dim3(eb), dim3(256), 0, stream, E, (const long long *)d_osrc.p, (const long long *)d_odst.p,
-                               (const uint8_t *)d_palive.p, (const uint8_t *)d_glive.p, d_gcur.p);
-        hipLaunchKernelGGL(k_g_scan_tiles, dim3(n_tiles), dim3(256), 0, stream, S, (const uint32_t *)d_gcur.p, d_gtile.p);
-        hipLaunchKernelGGL(k_g_scan_sums, dim3(1), dim3(256), 0, stream, n_tiles, d_gtile.p);
-        hipLaunchKernelGGL(k_g_scan_write, dim3(n_tiles), dim3(256), 0, stream, S, (const uint32_t *)d_gcur.p, (const uint32_t *)d_gtile.p, n_tiles,
-                           d_goff.p, d_gcur.p);
-        if (E) {
-            hipLaunchKernelGGL(k_g_fill, dim3(eb), dim3(256), 0, stream, E, (const long long *)d_osrc.p, (const long long *)d_odst.p,
-                               (const uint8_t *)d_palive.p, (const uint8_t *)d_glive.p, d_gcur.p, d_gseg.p);
-            hipLaunchKernelGGL(k_g_order, dim3((S + 3) / 4), dim3(256), 0, stream, S, (const uint32_t *)d_goff.p, d_gseg.p, (const long long *)d_odst.p,
-                               (const int32_t *)d_oval.p, N, d_geid.p, d_gdst.p, d_gctl.p);
-        }
-        // the weights, one launch per level
-        hipLaunchKernelGGL(k_g_level0, dim3(sb), dim3(256), 0, stream, S, (const uint8_t *)d_glive.p, (const uint8_t *)d_pfinal.p,
-                           (go->flags & STCSP_GEN_END_FINAL) ? 1 : 0, d_gw.p, d_gcount.p);
-        for (int t = 0; t < H; t++)
-            hipLaunchKernelGGL(k_g_weights, dim3(sb), dim3(256), 0, stream, S, (const uint32_t *)d_goff.p, (const uint32_t *)d_gdst.p,
-                               (const double *)(d_gw.p + (size_t)t * S), d_gw.p + (size_t)(t + 1) * S, d_gcount.p + t + 1);
-        HIPCHK(hipGetLastError());
-        gen_live.resize(S);
-        gen_count.assign((size_t)H + 1, 0.0);
-        HIPCHK(hipMemcpyAsync(gen_live.data(), d_glive.p, S, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipMemcpyAsync(gen_count.data(), d_gcount.p, ((size_t)H + 1) * sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipMemcpyAsync(&total, d_goff.p + S, sizeof total, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipMemcpyAsync(ctl, d_gctl.p, sizeof ctl, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        int64_t n_live = 0;
-        for (uint32_t s = 0; s < S; s++) n_live += gen_live[s];
-        gen_root_live = S > 0 && gen_live[0];
-        for (double c : gen_count)
-            if (!std::isfinite(c)) return fail(STCSP_E_UNSUPPORTED, "generator_build: the number of prefixes of length %d overflows a double", H);
-        gen_n_obs = (int)obs.size();
-        gen_horizon = H;
-        gen_built = true;
-        memset(info, 0, sizeof *info);
-        info->n_states = n_live;
-        info->n_edges = total;
-        info->table_bytes = (int64_t)(table * sizeof(double) + 3 * (size_t)E * sizeof(uint32_t) + (2 * (size_t)S + 1) * sizeof(uint32_t) + S);
-        info->count = gen_count.data();
-        info->n_observable = gen_n_obs;
-        info->horizon = H;
-        info->max_out_degree = (int32_t)ctl[G_MAXDEG];
-        info->root_live = gen_root_live;
-        info->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return STCSP_OK;
-    }
-
-    // Stream generator, generate: n_streams prefixes of one length, sampled or unranked (contract: stcsp_engine.h).
-    int generate(const stcsp_generate_request *rq, stcsp_generate_result *out) {
-        if (sharded) return fail(STCSP_E_UNSUPPORTED, "the device generator is for unsharded engines (stcsp_automaton_generate on the merged automaton)");
-        if (!exp_on_device || !post_done || truncated || !gen_built)
-            return fail(STCSP_E_STATE, "generate needs generator_build() after the last postprocess()");
-        if (!stcsp::generate_request_ok(gen_count, rq->n_streams, rq->len, rq->n_streams > 0 ? rq->ranks : nullptr))
-            return fail(STCSP_E_INVALID, "generate: a length outside 0 .. horizon or without a prefix, or a rank that is not below count[len] < 2^53");
-        auto t0 = std::chrono::steady_clock::now();
-        const size_t n = (size_t)rq->n_streams, len = (size_t)rq->len;
-        const size_t cells = n * len * (size_t)gen_n_obs;
-        if (n >= 0x7fffffffull) return fail(STCSP_E_NOMEM, "generate: too many streams for one call");
-        g_values.assign(cells, 0);
-        g_fin.assign(n, 0);
-        memset(out, 0, sizeof *out);
-        out->n_streams = rq->n_streams;
-        out->values = g_values.data();
-        out->end_final = g_fin.data();
-        out->len = rq->len;
-        out->n_observable = gen_n_obs;
-        if (n) {  // (count[len] > 0: the root is live)
-            if (d_gfin.n < n) HIPCHK(d_gfin.alloc(n + n / 4 + 256));
-            if (d_gout.n < cells) HIPCHK(d_gout.alloc(cells + cells / 4 + 256));
-            if (rq->ranks && d_granks.n < n) HIPCHK(d_granks.alloc(n + n / 4 + 256));
-            for (int i = 0; i < 2; i++)
-                if (!ev_g[i]) HIPCHK(hipEventCreate(&ev_g[i]));
-            if (rq->ranks) HIPCHK(hipMemcpyAsync(d_granks.p, rq->ranks, n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipMemsetAsync(d_gctl.p + G_ERROR, 0, sizeof(uint32_t), stream));
-            HIPCHK(hipEventRecord(ev_g[0], stream));
-            const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-            if (rq->ranks)
-                hipLaunchKernelGGL(k_g_generate<true>, grid, block, 0, stream, (uint32_t)n, (uint32_t)len, 0ull, (const unsigned long long *)d_granks.p,
-                                   n_states, (const double *)d_gw.p, (const uint32_t *)d_goff.p, (const uint32_t *)d_gdst.p, (const uint32_t *)d_geid.p,
-                                   (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_gobs.p, gen_n_obs, (const uint8_t *)d_pfinal.p, d_gout.p,
-                                   d_gfin.p, d_gctl.p);
-            else
-                hipLaunchKernelGGL(k_g_generate<false>, grid, block, 0, stream, (uint32_t)n, (uint32_t)len, (unsigned long long)rq->seed,
-                                   (const unsigned long long *)nullptr, n_states, (const double *)d_gw.p, (const uint32_t *)d_goff.p,
-                                   (const uint32_t *)d_gdst.p, (const uint32_t *)d_geid.p, (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_gobs.p,
-                                   gen_n_obs, (const uint8_t *)d_pfinal.p, d_gout.p, d_gfin.p, d_gctl.p);
-            HIPCHK(hipEventRecord(ev_g[1], stream));
-            HIPCHK(hipGetLastError());
-            uint32_t bad = 0;
-            if (cells) HIPCHK(hipMemcpyAsync(g_values.data(), d_gout.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(g_fin.data(), d_gfin.p, n, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(&bad, d_gctl.p + G_ERROR, sizeof bad, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            float ms_k = 0;
-            HIPCHK(hipEventElapsedTime(&ms_k, ev_g[0], ev_g[1]));
-            out->seconds_kernel = ms_k * 1e-3;
-            if (bad) return fail(STCSP_E_INTERNAL, "generate: a state without an edge of non-zero weight");
-        }
-        out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return STCSP_OK;
-    }
-
-    // Stream repair, the label ids of the generator's CSR (dev_repair.hpp): built on the first repair() after a generator_build().
-    int repair_labels() {
-        const uint32_t S = n_states;
-        uint32_t total = 0;
-        HIPCHK(hipMemcpyAsync(&total, d_goff.p + S, sizeof total, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        uint32_t slots = 64;
-        while (slots < 2 * (size_t)total && slots < 0x80000000u) slots <<= 1;
-        if (d_rtab.n < slots) HIPCHK(d_rtab.alloc(slots));
-        if (d_rlid.n < total) {
-            const size_t c = (size_t)total + total / 4 + 256;
-            HIPCHK(d_rlid.alloc(c));
-            HIPCHK(d_rrep.alloc(c));
-        }
-        if (d_rlong.n < S) HIPCHK(d_rlong.alloc((size_t)S + S / 4 + 256));
-        if (!d_rctl.p) HIPCHK(d_rctl.alloc(R_WORDS));
-        rep_wave_segment = kRepWaveSegment;
-        if (const char *v = getenv("STCSP_REPAIR_WAVE_SEGMENT")) rep_wave_segment = (uint32_t)std::max(1ll, std::min(atoll(v), 0x7fffffffll));
-        uint32_t ctl[R_WORDS] = {0};
-        HIPCHK(hipMemsetAsync(d_rctl.p, 0, sizeof ctl, stream));
-        HIPCHK(hipMemsetAsync(d_rtab.p, 0xff, (size_t)slots * sizeof(uint32_t), stream));
-        if (total) {
-            const unsigned kb = (total + 255) / 256;
-            hipLaunchKernelGGL(k_r_labels, dim3(kb), dim3(256), 0, stream, total, (const uint32_t *)d_geid.p, (const int32_t *)d_oval.p, ctx.N,
-                               (const int32_t *)d_gobs.p, gen_n_obs, d_rtab.p, slots - 1, d_rlid.p, d_rctl.p);
-            hipLaunchKernelGGL(k_r_number, dim3((slots + 255) / 256), dim3(256), 0, stream, slots, d_rtab.p, d_rrep.p, d_rctl.p);
-            hipLaunchKernelGGL(k_r_remap, dim3(kb), dim3(256), 0, stream, total, (const uint32_t *)d_rtab.p, d_rlid.p);
-        }
-        hipLaunchKernelGGL(k_r_long, dim3((S + 255) / 256), dim3(256), 0, stream, S, (const uint32_t *)d_goff.p, rep_wave_segment, d_rlong.p, d_rctl.p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(ctl, d_rctl.p, sizeof ctl, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        if (ctl[R_ERROR]) return fail(STCSP_E_INTERNAL, "repair: the label table overflowed");
-        rep_total = total;
-        rep_n_labels = ctl[R_LABELS];
-        rep_n_long = ctl[R_LONG];
-        rep_built = true;
-        return STCSP_OK;
-    }
-
-    // Stream repair: the nearest solution prefix of every stream (contract: stcsp_engine.h).
-    int repair(const stcsp_repair_request *rq, stcsp_repair_result *out) {
-        if (sharded) return fail(STCSP_E_UNSUPPORTED, "the device repair is for unsharded engines (stcsp_automaton_repair_streams on the merged automaton)");
-        if (!exp_on_device || !post_done || truncated || !gen_built)
-            return fail(STCSP_E_STATE, "repair needs generator_build() after the last postprocess()");
-        if (!stcsp::repair_request_ok(rq->n_streams, rq->offsets, rq->weights, gen_n_obs))
-            return fail(STCSP_E_INVALID, "repair: malformed stream offsets, a negative weight, or (sum of the weights) x (longest stream) above 2^31 - 2");
-        auto t0 = std::chrono::steady_clock::now();
-        const size_t n = (size_t)rq->n_streams, n_obs = (size_t)gen_n_obs;
-        const size_t steps = n ? (size_t)rq->offsets[n] : 0;
-        if (steps && n_obs && !rq->values) return fail(STCSP_E_INVALID, "repair: no step values");
-        r_dist.assign(n, -1);
-        r_values.assign(steps * n_obs, 0);
-        r_fin.assign(n, 0);
-        r_nchg.assign(n, 0);
-        memset(out, 0, sizeof *out);
-        out->n_streams = rq->n_streams;
-        out->distance = r_dist.data();
-        out->values = r_values.data();
-        out->end_final = r_fin.data();
-        out->n_changed = r_nchg.data();
-        out->n_observable = gen_n_obs;
-        if (n && gen_root_live) {
-            if (!rep_built) {
-                const int rc = repair_labels();
-                if (rc != STCSP_OK) return rc;
-            }
-            const uint32_t S = n_states, nL = rep_n_labels;
-            const int end_final = (rq->flags & STCSP_REPAIR_END_FINAL) ? 1 : 0;
-            size_t budget = 0;
-            if (const char *v = getenv("STCSP_REPAIR_BYTES")) budget = (size_t)std::max(0ll, atoll(v));
-            if (!budget) {
-                size_t free_b = 0, total_b = 0;
-                HIPCHK(hipMemGetInfo(&free_b, &total_b));
-                budget = std::max<size_t>(free_b / 2, (size_t)1 << 20);
-            }
-            auto need = [&](size_t len) { return ((len + 1) * (size_t)S + len * (size_t)nL) * sizeof(uint32_t); };
-            std::vector<int32_t> w(n_obs, 1);
-            if (rq->weights) w.assign(rq->weights, rq->weights + n_obs);
-            if (d_rweights.n < n_obs) HIPCHK(d_rweights.alloc(n_obs + 16));
-            if (n_obs) HIPCHK(hipMemcpyAsync(d_rweights.p, w.data(), n_obs * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-            for (int i = 0; i < 4; i++)
-                if (!ev_r[i]) HIPCHK(hipEventCreate(&ev_r[i]));
-            std::vector<RepStream> meta;
-            const unsigned sb = (S + 255) / 256;
-            for (size_t b0 = 0; b0 < n;) {
-                // the next batch: consecutive streams while their tables and costs fit the budget
-                size_t b1 = b0, bytes = 0, words_G = 0, steps_b = 0, longest = 0;
-                meta.clear();
-                while (b1 < n && b1 - b0 < 65535) {
-                    const size_t len = (size_t)(rq->offsets[b1 + 1] - rq->offsets[b1]);
-                    if (need(len) > budget)
-                        return fail(STCSP_E_NOMEM, "repair: stream %zu of %zu steps needs %zu bytes of tables, the budget is %zu", b1, len, need(len), budget);
-                    if (b1 > b0 && bytes + need(len) > budget) break;
-                    RepStream st;
-                    st.table = words_G;
-                    st.step = steps_b;
-                    st.len = (uint32_t)len;
-                    st.pad = 0;
-                    meta.push_back(st);
-                    bytes += need(len);
-                    words_G += (len + 1) * (size_t)S;
-                    steps_b += len;
-                    longest = std::max(longest, len);
-                    b1++;
-                }
-                const size_t nb = b1 - b0, cells = steps_b * n_obs, words_c = steps_b * (size_t)nL;
-                const size_t first = (size_t)rq->offsets[b0] * n_obs;
-                if (d_rG.n < words_G && d_rG.alloc(words_G) != hipSuccess) {
-                    (void)hipGetLastError();
-                    d_rG.release();
-                    return fail(STCSP_E_NOMEM, "repair: no room for %zu bytes of tables", words_G * sizeof(uint32_t));
-                }
-                if (d_rcost.n < words_c && d_rcost.alloc(words_c) != hipSuccess) {
-                    (void)hipGetLastError();
-                    d_rcost.release();
-                    return fail(STCSP_E_NOMEM, "repair: no room for %zu bytes of step costs", words_c * sizeof(uint32_t));
-                }
-                if (d_rstreams.n < nb) {
-                    const size_t c = nb + nb / 4 + 256;
-                    HIPCHK(d_rstreams.alloc(c));
-                    HIPCHK(d_rdist.alloc(c));
-                    HIPCHK(d_rnchg.alloc(c));
-                    HIPCHK(d_rfin.alloc(c));
-                }
-                if (d_rrows.n < cells) {
-                    const size_t c = cells + cells / 4 + 256;
-                    HIPCHK(d_rrows.alloc(c));
-                    HIPCHK(d_rout.alloc(c));
-                }
-                HIPCHK(hipMemcpyAsync(d_rstreams.p, meta.data(), nb * sizeof(RepStream), hipMemcpyHostToDevice, stream));
-                if (cells) {
-                    HIPCHK(hipMemcpyAsync(d_rrows.p, rq->values + first, cells * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-                    HIPCHK(hipMemsetAsync(d_rout.p, 0, cells * sizeof(int32_t), stream));
-                }
-                HIPCHK(hipMemsetAsync(d_rctl.p + R_ERROR, 0, sizeof(uint32_t), stream));
-                HIPCHK(hipEventRecord(ev_r[0], stream));
-                if (words_c)
-                    hipLaunchKernelGGL(k_r_cost, dim3((nL + 255) / 256, (unsigned)std::min<size_t>(steps_b, 65535)), dim3(256), 0, stream, nL,
-                                       (uint32_t)steps_b, (const uint32_t *)d_rrep.p, (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_gobs.p, gen_n_obs,
-                                       (const int32_t *)d_rweights.p, (const int32_t *)d_rrows.p, d_rcost.p);
-                HIPCHK(hipEventRecord(ev_r[1], stream));
-                hipLaunchKernelGGL(k_r_level0, dim3(sb, (unsigned)nb), dim3(256), 0, stream, S, (const RepStream *)d_rstreams.p, (const uint8_t *)d_glive.p,
-                                   (const uint8_t *)d_pfinal.p, end_final, d_rG.p);
-                for (uint32_t r = 1; r <= (uint32_t)longest; r++) {
-                    hipLaunchKernelGGL(k_r_relax, dim3(sb, (unsigned)nb), dim3(256), 0, stream, S, r, (const RepStream *)d_rstreams.p,
-                                       (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint32_t *)d_rcost.p,
-                                       rep_wave_segment, d_rG.p);
-                    if (rep_n_long)
-                        hipLaunchKernelGGL(k_r_relax_long, dim3((rep_n_long + 3) / 4, (unsigned)nb), dim3(256), 0, stream, rep_n_long,
-                                           (const uint32_t *)d_rlong.p, S, r, (const RepStream *)d_rstreams.p, (const uint32_t *)d_goff.p,
-                                           (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint32_t *)d_rcost.p, d_rG.p);
-                }
-                HIPCHK(hipEventRecord(ev_r[2], stream));
-                hipLaunchKernelGGL(k_r_walk, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, stream, (uint32_t)nb, (const RepStream *)d_rstreams.p, S,
-                                   (const uint32_t *)d_rG.p, (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p,
-                                   (const uint32_t *)d_geid.p, nL, (const uint32_t *)d_rcost.p, (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_gobs.p,
-                                   gen_n_obs, (const uint8_t *)d_pfinal.p, (const int32_t *)d_rrows.p, d_rout.p, d_rdist.p, d_rfin.p, d_rnchg.p, d_rctl.p);
-                HIPCHK(hipEventRecord(ev_r[3], stream));
-                HIPCHK(hipGetLastError());
-                uint32_t bad = 0;
-                if (cells) HIPCHK(hipMemcpyAsync(r_values.data() + first, d_rout.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipMemcpyAsync(r_dist.data() + b0, d_rdist.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipMemcpyAsync(r_nchg.data() + b0, d_rnchg.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipMemcpyAsync(r_fin.data() + b0, d_rfin.p, nb, hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipMemcpyAsync(&bad, d_rctl.p + R_ERROR, sizeof bad, hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                float ms_c = 0, ms_r = 0, ms_w = 0;
-                HIPCHK(hipEventElapsedTime(&ms_c, ev_r[0], ev_r[1]));
-                HIPCHK(hipEventElapsedTime(&ms_r, ev_r[1], ev_r[2]));
-                HIPCHK(hipEventElapsedTime(&ms_w, ev_r[2], ev_r[3]));
-                out->seconds_cost += ms_c * 1e-3;
-                out->seconds_relax += ms_r * 1e-3;
-                out->seconds_walk += ms_w * 1e-3;
-                out->n_batches++;
-                out->table_bytes = std::max<int64_t>(out->table_bytes, (int64_t)bytes);
-                if (bad) return fail(STCSP_E_INTERNAL, "repair: a state with a finite cost to go and no edge that attains it");
-                b0 = b1;
-            }
-            out->n_labels = nL;
-        }
-        out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return STCSP_OK;
-    }
-
-    // Stream inference, the value dictionaries (dev_infer.hpp): built on the first infer() after a generator_build(), over
-    // the label representatives of repair_labels(). Sized by what the labels carry, not by the variables' bounds.
-    int infer_dictionaries() {
-        const size_t nL = rep_n_labels, n_obs = (size_t)gen_n_obs, cells = nL * n_obs;
-        std::vector<int32_t> rows(cells);
-        if (cells) {
-            if (d_ilabrows.n < cells) HIPCHK(d_ilabrows.alloc(cells + cells / 4 + 256));
-            hipLaunchKernelGGL(k_i_rows, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, (uint32_t)nL, (const uint32_t *)d_rrep.p,
-                               (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_gobs.p, gen_n_obs, d_ilabrows.p);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(rows.data(), d_ilabrows.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-        }
-        inf_dict.assign(n_obs, std::vector<int32_t>());
-        inf_word_off.assign(n_obs, 0);
-        std::vector<uint32_t> vidx(cells);
-        size_t words = 0;
-        for (size_t v = 0; v < n_obs; v++) {
-            std::vector<int32_t> &d = inf_dict[v];
-            d.resize(nL);
-            for (size_t l = 0; l < nL; l++) d[l] = rows[l * n_obs + v];
-            std::sort(d.begin(), d.end());
-            d.erase(std::unique(d.begin(), d.end()), d.end());
-            for (size_t l = 0; l < nL; l++) vidx[l * n_obs + v] = (uint32_t)(std::lower_bound(d.begin(), d.end(), rows[l * n_obs + v]) - d.begin());
-            inf_word_off[v] = (uint32_t)words;
-            words += (d.size() + 31) / 32;
-        }
-        if (words > 0x7fffffffull) return fail(STCSP_E_NOMEM, "infer: the support bitmaps of one step are too large");
-        inf_words = (uint32_t)words;
-        if (d_ividx.n < cells) HIPCHK(d_ividx.alloc(cells + cells / 4 + 256));
-        if (d_iwoff.n < n_obs) HIPCHK(d_iwoff.alloc(n_obs + 16));
-        if (cells) HIPCHK(hipMemcpyAsync(d_ividx.p, vidx.data(), cells * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-        if (n_obs) HIPCHK(hipMemcpyAsync(d_iwoff.p, inf_word_off.data(), n_obs * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-        HIPCHK(hipStreamSynchronize(stream));  // (vidx is a local)
-        inf_built = true;
-        return STCSP_OK;
-    }
-
-    // Stream inference: supports, counts and draws of partially observed streams (contract: stcsp_engine.h).
-    int infer(const stcsp_infer_request *rq, stcsp_infer_result *out) {
-        if (sharded) return fail(STCSP_E_UNSUPPORTED, "the device inference is for unsharded engines (stcsp_automaton_infer_streams on the merged automaton)");
-        if (!exp_on_device || !post_done || truncated || !gen_built)
-            return fail(STCSP_E_STATE, "infer needs generator_build() after the last postprocess()");
-        if (!stcsp::infer_request_ok(rq->n_streams, rq->offsets, rq->draws)) return fail(STCSP_E_INVALID, "infer: malformed stream offsets or a negative number of draws");
-        auto t0 = std::chrono::steady_clock::now();
-        const size_t n = (size_t)rq->n_streams, n_obs = (size_t)gen_n_obs, draws = (size_t)rq->draws;
-        const size_t steps = n ? (size_t)rq->offsets[n] : 0;
-        if (steps && n_obs && !rq->values) return fail(STCSP_E_INVALID, "infer: no step values");
-        i_count.assign(n, 0.0);
-        i_feas.assign(n, 0);
-        i_soff.assign(steps * n_obs + 1, 0);
-        i_sval.clear();
-        i_nstates.assign(steps + n, 0);
-        i_values.assign(steps * draws * n_obs, STCSP_INFER_MISSING);
-        i_fin.assign(n * draws, 0);
-        memset(out, 0, sizeof *out);
-        out->n_streams = rq->n_streams;
-        out->n_observable = gen_n_obs;
-        out->draws = rq->draws;
-        auto publish = [&]() {  // (the vectors may have grown)
-            out->count = i_count.data();
-            out->feasible = i_feas.data();
-            out->support_off = i_soff.data();
-            out->support_val = i_sval.data();
-            out->n_states = i_nstates.data();
-            out->values = i_values.data();
-            out->end_final = i_fin.data();
-        };
-        publish();
-        if (n && gen_root_live) {
-            if (!rep_built) {
-                const int rc = repair_labels();
-                if (rc != STCSP_OK) return rc;
-            }
-            if (!inf_built) {
-                const int rc = infer_dictionaries();
-                if (rc != STCSP_OK) return rc;
-            }
-            const uint32_t S = n_states, nL = rep_n_labels, W = inf_words;
-            const int end_final = (rq->flags & STCSP_INFER_END_FINAL) ? 1 : 0;
-            size_t budget = 0;
-            if (const char *v = getenv("STCSP_INFER_BYTES")) budget = (size_t)std::max(0ll, atoll(v));
-            if (!budget) {
-                size_t free_b = 0, total_b = 0;
-                HIPCHK(hipMemGetInfo(&free_b, &total_b));
-                budget = std::max<size_t>(free_b / 2, (size_t)1 << 20);
-            }
-            auto need = [&](size_t len) { return (len + 1) * (size_t)S * (sizeof(double) + 1) + len * ((size_t)nL * 2 + (size_t)W * sizeof(uint32_t)); };
-            if (!d_ictl.p) HIPCHK(d_ictl.alloc(I_WORDS));
-            for (int i = 0; i < 7; i++)
-                if (!ev_i[i]) HIPCHK(hipEventCreate(&ev_i[i]));
-            std::vector<InfStream> meta;
-            const unsigned sb = (S + 255) / 256;
-            for (size_t b0 = 0; b0 < n;) {
-                // the next batch: consecutive streams while their structures fit the budget
-                size_t b1 = b0, bytes = 0, entries = 0, steps_b = 0, longest = 0;
-                meta.clear();
-                while (b1 < n && b1 - b0 < 65535) {
-                    const size_t len = (size_t)(rq->offsets[b1 + 1] - rq->offsets[b1]);
-                    if (need(len) > budget)
-                        return fail(STCSP_E_NOMEM, "infer: stream %zu of %zu steps needs %zu bytes of tables, the budget is %zu", b1, len, need(len), budget);
-                    if (b1 > b0 && bytes + need(len) > budget) break;
-                    InfStream st;
-                    st.table = entries;
-                    st.step = steps_b;
-                    st.len = (uint32_t)len;
-                    st.index = (uint32_t)(b1 - b0);
-                    meta.push_back(st);
-                    bytes += need(len);
-                    entries += (len + 1) * (size_t)S;
-                    steps_b += len;
-                    longest = std::max(longest, len);
-                    b1++;
-                }
-                const size_t nb = b1 - b0, cells = steps_b * n_obs, marks = steps_b * (size_t)nL, words = steps_b * (size_t)W;
-                const size_t n_q = nb * draws, out_cells = cells * draws;
-                const size_t first_step = (size_t)rq->offsets[b0], first = first_step * n_obs;
-                if (n_q >= 0x7fffffffull) return fail(STCSP_E_NOMEM, "infer: too many draws for one batch");
-                if ((d_iB.n < entries && d_iB.alloc(entries) != hipSuccess) || (d_iF.n < entries && d_iF.alloc(entries) != hipSuccess) ||
-                    (d_imatch.n < marks && d_imatch.alloc(marks) != hipSuccess) || (d_ifeas.n < marks && d_ifeas.alloc(marks) != hipSuccess) ||
-                    (d_ibits.n < words && d_ibits.alloc(words) != hipSuccess)) {
-                    (void)hipGetLastError();
-                    d_iB.release();
-                    d_iF.release();
-                    d_imatch.release();
-                    d_ifeas.release();
-                    d_ibits.release();
-                    return fail(STCSP_E_NOMEM, "infer: no room for %zu bytes of tables", bytes);
-                }
-                if (d_istreams.n < nb) {
-                    const size_t c = nb + nb / 4 + 256;
-                    HIPCHK(d_istreams.alloc(c));
-                    HIPCHK(d_icount.alloc(c));
-                }
-                if (d_irows.n < cells) HIPCHK(d_irows.alloc(cells + cells / 4 + 256));
-                if (d_instates.n < steps_b + nb) HIPCHK(d_instates.alloc(steps_b + nb + (steps_b + nb) / 4 + 256));
-                if (n_q) {
-                    if (d_ifin.n < n_q) HIPCHK(d_ifin.alloc(n_q + n_q / 4 + 256));
-                    if (rq->ranks && d_iranks.n < n_q) HIPCHK(d_iranks.alloc(n_q + n_q / 4 + 256));
-                    if (d_iout.n < out_cells) HIPCHK(d_iout.alloc(out_cells + out_cells / 4 + 256));
-                }
-                HIPCHK(hipMemcpyAsync(d_istreams.p, meta.data(), nb * sizeof(InfStream), hipMemcpyHostToDevice, stream));
-                if (cells) HIPCHK(hipMemcpyAsync(d_irows.p, rq->values + first, cells * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-                HIPCHK(hipMemsetAsync(d_iF.p, 0, entries, stream));
-                if (marks) HIPCHK(hipMemsetAsync(d_ifeas.p, 0, marks, stream));
-                if (words) HIPCHK(hipMemsetAsync(d_ibits.p, 0, words * sizeof(uint32_t), stream));
-                HIPCHK(hipMemsetAsync(d_instates.p, 0, (steps_b + nb) * sizeof(int32_t), stream));
-                HIPCHK(hipMemsetAsync(d_ictl.p, 0, I_WORDS * sizeof(uint32_t), stream));
-                const unsigned step_rows = (unsigned)std::min<size_t>(std::max<size_t>(steps_b, 1), 65535);
-                HIPCHK(hipEventRecord(ev_i[0], stream));
-                if (marks)
-                    hipLaunchKernelGGL(k_i_match, dim3((nL + 255) / 256, step_rows), dim3(256), 0, stream, nL, (uint32_t)steps_b, (const uint32_t *)d_rrep.p,
-                                       (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_gobs.p, gen_n_obs, (const int32_t *)d_irows.p, d_imatch.p);
-                HIPCHK(hipEventRecord(ev_i[1], stream));
-                hipLaunchKernelGGL(k_i_level0, dim3(sb, (unsigned)nb), dim3(256), 0, stream, S, (const InfStream *)d_istreams.p, (const uint8_t *)d_glive.p,
-                                   (const uint8_t *)d_pfinal.p, end_final, d_iB.p);
-                for (uint32_t r = 1; r <= (uint32_t)longest; r++)
-                    hipLaunchKernelGGL(k_i_backward, dim3(sb, (unsigned)nb), dim3(256), 0, stream, S, r, (const InfStream *)d_istreams.p,
-                                       (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_imatch.p,
-                                       d_iB.p);
-                hipLaunchKernelGGL(k_i_root, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, stream, (uint32_t)nb, (const InfStream *)d_istreams.p, S,
-                                   (const double *)d_iB.p, d_iF.p, d_icount.p);
-                HIPCHK(hipEventRecord(ev_i[2], stream));
-                for (uint32_t t = 0; t < (uint32_t)longest; t++) {
-                    hipLaunchKernelGGL(k_i_forward, dim3(sb, (unsigned)nb), dim3(256), 0, stream, S, t, (const InfStream *)d_istreams.p,
-                                       (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_imatch.p,
-                                       (const double *)d_iB.p, rep_wave_segment, d_iF.p, d_ifeas.p);
-                    if (rep_n_long)
-                        hipLaunchKernelGGL(k_i_forward_long, dim3((rep_n_long + 3) / 4, (unsigned)nb), dim3(256), 0, stream, rep_n_long,
-                                           (const uint32_t *)d_rlong.p, S, t, (const InfStream *)d_istreams.p, (const uint32_t *)d_goff.p,
-                                           (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_imatch.p, (const double *)d_iB.p,
-                                           d_iF.p, d_ifeas.p);
-                }
-                hipLaunchKernelGGL(k_i_count, dim3(sb, (unsigned)nb), dim3(256), 0, stream, S, (const InfStream *)d_istreams.p, (const uint8_t *)d_iF.p,
-                                   d_instates.p);
-                HIPCHK(hipEventRecord(ev_i[3], stream));
-                if (marks && W)
-                    hipLaunchKernelGGL(k_i_support, dim3((nL + 255) / 256, step_rows), dim3(256), 0, stream, nL, (uint32_t)steps_b, (const uint8_t *)d_ifeas.p,
-                                       (const uint32_t *)d_ividx.p, (const uint32_t *)d_iwoff.p, gen_n_obs, W, d_ibits.p);
-                HIPCHK(hipEventRecord(ev_i[4], stream));
-                HIPCHK(hipGetLastError());
-                i_bits.resize(words);
-                HIPCHK(hipMemcpyAsync(i_count.data() + b0, d_icount.p, nb * sizeof(double), hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipMemcpyAsync(i_nstates.data() + first_step + b0, d_instates.p, (steps_b + nb) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-                if (words) HIPCHK(hipMemcpyAsync(i_bits.data(), d_ibits.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                // the bitmaps -> sorted lists: bit order is value order
-                for (size_t step = 0; step < steps_b; step++)
-                    for (size_t v = 0; v < n_obs; v++) {
-                        const uint32_t *w = i_bits.data() + step * W + inf_word_off[v];
-                        const std::vector<int32_t> &d = inf_dict[v];
-                        for (size_t k = 0; k < d.size(); k++)
-                            if (w[k >> 5] >> (k & 31) & 1u) i_sval.push_back(d[k]);
-                        i_soff[(first_step + step) * n_obs + v + 1] = (int64_t)i_sval.size();
-                    }
-                for (size_t i = b0; i < b1; i++) i_feas[i] = i_count[i] > 0.0;
-                publish();
-                float ms[5] = {0, 0, 0, 0, 0};
-                if (n_q) {
-                    // the draws: the counts decide whether they can be asked for
-                    for (size_t i = b0; i < b1; i++) {
-                        const int bad = stcsp::infer_draws_ok(i_count[i], rq->draws, rq->ranks ? rq->ranks + i * draws : nullptr);
-                        if (bad == 1) return fail(STCSP_E_UNSUPPORTED, "infer: draws from stream %zu, whose count overflows a double", i);
-                        if (bad) return fail(STCSP_E_INVALID, "infer: stream %zu: a rank that is not below its count < 2^53", i);
-                    }
-                    if (rq->ranks) HIPCHK(hipMemcpyAsync(d_iranks.p, rq->ranks + b0 * draws, n_q * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-                    if (out_cells) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d_iout.p, STCSP_INFER_MISSING, out_cells, stream));
-                    HIPCHK(hipMemsetAsync(d_ifin.p, 0, n_q, stream));
-                    const dim3 grid((unsigned)((n_q + 255) / 256)), block(256);
-                    HIPCHK(hipEventRecord(ev_i[5], stream));
-                    if (rq->ranks)
-                        hipLaunchKernelGGL(k_i_walk<true>, grid, block, 0, stream, (uint32_t)n_q, (uint32_t)draws, (unsigned long long)(b0 * draws), 0ull,
-                                           (const unsigned long long *)d_iranks.p, (const InfStream *)d_istreams.p, S, (const double *)d_iB.p,
-                                           (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, (const uint32_t *)d_geid.p, nL,
-                                           (const uint8_t *)d_imatch.p, (const int32_t *)d_oval.p, ctx.N, (const int32_t *)d_gobs.p, gen_n_obs,
-                                           (const uint8_t *)d_pfinal.p, d_iout.p, d_ifin.p, d_ictl.p);
-                    else
-                        hipLaunchKernelGGL(k_i_walk<false>, grid, block, 0, stream, (uint32_t)n_q, (uint32_t)draws, (unsigned long long)(b0 * draws),
-                                           (unsigned long long)rq->seed, (const unsigned long long *)nullptr, (const InfStream *)d_istreams.p, S,
-                                           (const double *)d_iB.p, (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p,
-                                           (const uint32_t *)d_geid.p, nL, (const uint8_t *)d_imatch.p, (const int32_t *)d_oval.p, ctx.N,
-                                           (const int32_t *)d_gobs.p, gen_n_obs, (const uint8_t *)d_pfinal.p, d_iout.p, d_ifin.p, d_ictl.p);
-                    HIPCHK(hipEventRecord(ev_i[6], stream));
-                    HIPCHK(hipGetLastError());
-                    uint32_t bad = 0;
-                    if (out_cells) HIPCHK(hipMemcpyAsync(i_values.data() + first * draws, d_iout.p, out_cells * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-                    HIPCHK(hipMemcpyAsync(i_fin.data() + b0 * draws, d_ifin.p, n_q, hipMemcpyDeviceToHost, stream));
-                    HIPCHK(hipMemcpyAsync(&bad, d_ictl.p + I_ERROR, sizeof bad, hipMemcpyDeviceToHost, stream));
-                    HIPCHK(hipStreamSynchronize(stream));
-                    HIPCHK(hipEventElapsedTime(&ms[4], ev_i[5], ev_i[6]));
-                    if (bad) return fail(STCSP_E_INTERNAL, "infer: a state with weight to go and no matching edge of non-zero weight");
-                }
-                for (int k = 0; k < 4; k++) HIPCHK(hipEventElapsedTime(&ms[k], ev_i[k], ev_i[k + 1]));
-                out->seconds_match += ms[0] * 1e-3;
-                out->seconds_backward += ms[1] * 1e-3;
-                out->seconds_forward += ms[2] * 1e-3;
-                out->seconds_support += ms[3] * 1e-3;
-                out->seconds_walk += ms[4] * 1e-3;
-                out->n_batches++;
-                out->table_bytes = std::max<int64_t>(out->table_bytes, (int64_t)bytes);
-                b0 = b1;
-            }
-            out->n_labels = nL;
-        }
-        if (i_sval.empty()) i_sval.reserve(1);
-        publish();
-        out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return STCSP_OK;
-    }
-
     // unsharded export: ok-fixpoint + compaction on the device, result arrays land in pinned memory
     int export_device(stcsp_result *res, stcsp_counters &ctr, size_t &E_out) {
         const int N = ctx.N;
@@ -3184,7 +2023,7 @@ struct stcsp_engine {
         }
         v.pref[R] = (uint32_t)E;
         if (E > 0xfffffff0ull) return fail(STCSP_E_NOMEM, "edge log too large for the device export");
-        if (d_alive.n < E) HIPCHK(d_alive.alloc(E + E / 4 + 256));
+        HIPCHK(d_alive.reserve(E));
         if (streaming) {  // the rest of the log (the chunks before it left while the search ran)
             if (getenv("STCSP_DEBUG")) {
                 const bool busy = hipStreamQuery(xstream) == hipErrorNotReady || hipStreamQuery(xstream2) == hipErrorNotReady;
@@ -3197,14 +2036,12 @@ struct stcsp_engine {
             int rcs = ensure_export_capacity(E);
             if (rcs != STCSP_OK) return rcs;
         }
-        if (d_fail.n < n_states) {
-            HIPCHK(d_fail.alloc((size_t)n_states + n_states / 4 + 256));
-            HIPCHK(d_outdeg.alloc((size_t)n_states + n_states / 4 + 256));
-        }
-        if (!d_post.p) HIPCHK(d_post.alloc(4));
+        HIPCHK(d_fail.reserve(n_states));
+        HIPCHK(d_outdeg.reserve(n_states));
+        HIPCHK(d_post.reserve_exact(4));
         if (h_state_cap < n_states) {
             if (h_fail) (void)hipHostFree(h_fail);
-            h_state_cap = (size_t)n_states + n_states / 4 + 256;
+            h_state_cap = grown(n_states);
             HIPCHK(hipHostMalloc((void **)&h_fail, h_state_cap));
         }
         {  // the keys of the states the search did not get to ship (all of them when streaming is off)
@@ -3311,11 +2148,7 @@ struct stcsp_engine {
         E_out = live;
         exp_edges = live;
         exp_on_device = true;
-        post_done = false;
-        mon_built = false;
-        gen_built = false;
-        rep_built = false;
-        inf_built = false;
+        services.invalidate();
         return STCSP_OK;
     }
 
@@ -3530,41 +2363,41 @@ int stcsp_engine_export(stcsp_engine *e, stcsp_result *result) {
 
 int stcsp_engine_postprocess(stcsp_engine *e, const stcsp_post_options *options, stcsp_post_result *out) {
     if (!e || !out) return STCSP_E_INVALID;
-    return e->postprocess(options, out);
+    return e->services.postprocess(e->view(), options, out);
 }
 
 int stcsp_engine_quotient(stcsp_engine *e, const stcsp_quotient_options *options, stcsp_quotient_result *out) {
     if (!e || !out) return STCSP_E_INVALID;
-    return e->quotient(options, out);
+    return e->services.quotient(e->view(), options, out);
 }
 
 int stcsp_engine_monitor_build(stcsp_engine *e, const stcsp_monitor_options *options, stcsp_monitor_info *info) {
     if (!e || !info) return STCSP_E_INVALID;
-    return e->monitor_build(options, info);
+    return e->services.monitor_build(e->view(), options, info);
 }
 
 int stcsp_engine_monitor_check(stcsp_engine *e, const stcsp_monitor_streams *streams, stcsp_monitor_result *result) {
     if (!e || !streams || !result) return STCSP_E_INVALID;
-    return e->monitor_check(streams, result);
+    return e->services.monitor_check(e->view(), streams, result);
 }
 
 int stcsp_engine_generator_build(stcsp_engine *e, const stcsp_generator_options *options, stcsp_generator_info *info) {
     if (!e || !info) return STCSP_E_INVALID;
-    return e->generator_build(options, info);
+    return e->services.generator_build(e->view(), options, info);
 }
 
 int stcsp_engine_generate(stcsp_engine *e, const stcsp_generate_request *request, stcsp_generate_result *result) {
     if (!e || !request || !result) return STCSP_E_INVALID;
-    return e->generate(request, result);
+    return e->services.generate(e->view(), request, result);
 }
 
 int stcsp_engine_repair(stcsp_engine *e, const stcsp_repair_request *request, stcsp_repair_result *result) {
     if (!e || !request || !result) return STCSP_E_INVALID;
-    return e->repair(request, result);
+    return e->services.repair(e->view(), request, result);
 }
 int stcsp_engine_infer(stcsp_engine *e, const stcsp_infer_request *request, stcsp_infer_result *result) {
     if (!e || !request || !result) return STCSP_E_INVALID;
-    return e->infer(request, result);
+    return e->services.infer(e->view(), request, result);
 }
 
 void stcsp_engine_destroy(stcsp_engine *e) { delete e; }

@@ -276,6 +276,51 @@ def test_answers_follow_the_flags_of_a_second_postprocess(stcsp, RefOracle):
     assert (after[0] <= before[0]).all()
 
 
+def test_services_share_one_live_set_in_any_order(stcsp):
+    """Monitor, quotient and generator read one live set per postprocess(), whichever of them is called first, and one call drops
+    everything after new flags or a new solve. PRUNED_BY_ADVERSARY by hand: 3 live states before the adversarial pass, 2 after;
+    the root and the state with t == 0 offer the same steps into the same states, so they fold: 2 classes before, 1 after."""
+    m = stcsp.Model(text=PRUNED_BY_ADVERSARY)
+    e = stcsp.Engine(m)
+    r = e.solve()
+    ranks = np.arange(4)
+    streams = list(e.automaton(r).traverse().generate(12, 5, seed=3, observable="all")[0])  # walks of the plain automaton
+
+    def answers(order, host, n_live, n_folded):
+        got = {}
+        for what in order:
+            if what == "monitor":
+                info = e.monitor("all")
+                assert (info.n_states, info.root_live) == (n_live, 1)
+                got[what] = e.check_streams(streams)
+                assert same(got[what], host.check_streams(streams, "all")) and got[what][3] == 0
+            elif what == "quotient":
+                cls, n_classes, _, _ = e.quotient("all")
+                hc, hn, _ = host.bisimulation("all")
+                assert e.quotient_result.n_states == n_live == int((cls >= 0).sum())
+                assert n_classes == hn == n_folded and np.array_equal(cls, hc)
+                got[what] = cls
+            else:
+                info = e.generator("all", 5)
+                assert (info.n_states, info.root_live) == (n_live, 1)
+                got[what] = e.generate(len(ranks), 5, ranks=ranks)
+                hst = host.generate(len(ranks), 5, ranks=ranks, observable="all", horizon=5)
+                assert np.array_equal(got[what][0], hst[0]) and np.array_equal(got[what][1], hst[1])
+        return got
+
+    post = e.postprocess()
+    before = answers(("monitor", "quotient", "generator"), e.automaton(r).import_flags(post), 3, 2)
+    post = e.postprocess(adversarial=5)
+    after = answers(("generator", "quotient", "monitor"), e.automaton(r).import_flags(post), 2, 1)
+    assert not same(before["monitor"], after["monitor"]) and not np.array_equal(before["quotient"], after["quotient"])
+    assert not np.array_equal(before["generator"][0], after["generator"][0])
+    e.solve()  # a new solve: nothing of the old one answers before the next postprocess()
+    for call in (lambda: e.monitor("all"), lambda: e.quotient("all"), lambda: e.generator("all", 5), lambda: e.repair_streams(streams)):
+        with pytest.raises(stcsp.StcspError) as ex:
+            call()
+        assert ex.value.code == -6
+
+
 def write_check_file(path, names, streams):
     lines = ["# " + " ".join(names)]
     for i, s in enumerate(streams):
