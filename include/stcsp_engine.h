@@ -587,6 +587,68 @@ typedef struct stcsp_infer_result {
 
 int stcsp_engine_infer(stcsp_engine *engine, const stcsp_infer_request *request, stcsp_infer_result *result);
 
+/* ---- the observer of the live automaton: subset construction on the device (no reference counterpart) ----------------
+ * Under a mask that hides a variable the live automaton is nondeterministic in its projected labels. The observer is the
+ * deterministic automaton whose states are the sets of automaton states the system can be in after an observed prefix:
+ * the state estimator of the partially observed system. Live automaton, projected label p_e, default mask and label ids
+ * are those of the last stcsp_engine_generator_build() on the engine; its horizon and flags play no part.
+ *
+ * Definition. D_0 = {root}. delta(D, l) = { dst(e) : e a live edge, src(e) in D, p_e = l }, defined when it is not empty.
+ * The observer's states are the sets reachable from D_0, its edges the triples (D, l, delta(D, l)). final(D) = some member
+ * of D is final (the monitor's end_final). Without a live root the observer is empty: n_states == 0, and the call succeeds.
+ *
+ * Canonical numbering. Breadth-first from D_0 = number 0, the out-edges of a state taken in lexicographic order of their
+ * projected rows (the convention of the canonical text and of stcsp_automaton_quotient()). Edges are returned sorted by
+ * (source number, projected row). Nothing in the result depends on state numbers, edge numbers or scheduling, except that
+ * the members of a set are named by their stcsp_result state index (ascending within a set).
+ *
+ * Consequences. Under a mask with every variable observable every set is a singleton and the observer is the live
+ * automaton. A stream the monitor accepts for accepted_len steps with n_end states drives the observer for accepted_len
+ * steps into the one state D with |D| == n_end and final(D) == end_final. Paths of the observer and distinct observable
+ * streams correspond one to one. Folding the observer with the bisimulation quotient under the same mask gives the minimal
+ * deterministic automaton of the observable language.
+ *
+ * Limits. options.max_states bounds the observer's states; 0 selects the default 2^26. The pool of member lists (4 bytes
+ * per member of every set) and the scratch of one level are bounded by a byte budget, by default half of the free device
+ * memory; the environment variable STCSP_OBSERVER_BYTES sets it. A frontier whose work items would not fit is cut into
+ * chunks. Exceeding either limit gives STCSP_E_NOMEM with a message that names the limit and how far the construction
+ * got; there is never a partial result, the engine stays usable, and the generator's, monitor's, repair's and inference's
+ * structures stay valid. Sets of any size up to the number of live states are built on the device: a set lives as a
+ * bitset over the states in LDS (up to 262,144 states) or in a slice of global scratch per workgroup;
+ * STCSP_OBSERVER_GLOBAL_SCRATCH=1 forces the second road (tests).
+ *
+ * Needs a valid stcsp_engine_generator_build(): without one, before stcsp_engine_postprocess() and after a truncated solve
+ * STCSP_E_STATE; on sharded and stepped engines STCSP_E_UNSUPPORTED (run stcsp_automaton_observer() of stcsp_host.h on the
+ * merged automaton). Sets are interned by a 64-bit hash; every set that finds an existing entry is compared with its
+ * member list exactly, and a difference (a collision of the hash) gives STCSP_E_INTERNAL, never a wrong automaton.
+ * Results are owned by the engine until the next call on it. */
+typedef struct stcsp_observer_options {
+    int64_t max_states; /* 0 = the default (2^26) */
+    int32_t reserved[2];
+} stcsp_observer_options;
+
+typedef struct stcsp_observer_result {
+    int64_t n_states, n_edges;
+    const int64_t *member_off;  /* [n_states + 1] into member[]                                                       */
+    const int32_t *member;      /* [member_off[n_states]] stcsp_result state indices, ascending within a set          */
+    const uint8_t *state_final; /* [n_states]                                                                         */
+    const int32_t *edge_src;    /* [n_edges] observer numbers; edges sorted by (source, projected row)                */
+    const int32_t *edge_dst;    /* [n_edges]                                                                          */
+    const int32_t *edge_values; /* [n_edges * n_observable] the projected rows                                        */
+    int64_t n_labels;           /* distinct projected labels of the live automaton                                    */
+    int64_t max_set;            /* the largest set                                                                    */
+    int64_t table_bytes;        /* HBM the construction held at its end: pool, records, tables, edge log, scratch     */
+    int32_t n_observable;
+    int32_t levels;             /* breadth-first levels, the root's included                                          */
+    double seconds;             /* wall time from the generator's structures in HBM to the result on the host         */
+    double seconds_build;       /* HIP-event time of the ordering kernel (first call after a generator_build())       */
+    double seconds_items;       /* HIP-event time of the item kernels, all levels                                     */
+    double seconds_intern;      /* HIP-event time of the intern launches, all levels                                  */
+    double seconds_commit;      /* HIP-event time of the write and verify launches, all levels                        */
+} stcsp_observer_result;
+
+int stcsp_engine_observer(stcsp_engine *engine, const stcsp_observer_options *options, stcsp_observer_result *result);
+
 void stcsp_engine_destroy(stcsp_engine *engine);
 
 /* Message of the last error on this engine (or of the last failed create when engine==NULL). */

@@ -160,6 +160,27 @@ int stcsp_automaton_infer_streams(const stcsp_automaton *a, const uint8_t *obser
                                   const int32_t *values, int32_t draws, const uint64_t *ranks, uint64_t seed, double *count, int64_t *support_off,
                                   int32_t **support_val, int32_t *n_states, int32_t *draw_values, uint8_t *end_final);
 
+/* ---- the observer: subset construction under a mask (definition: stcsp_engine.h, stcsp_engine_observer) ----
+ * The same contract written plainly with ordered containers, on the automaton's current flags: the checker of the device
+ * pass in the tests, and the path for automata whose flags live on the host (sharded runs, host adversarial passes,
+ * read_binary). observable: as in stcsp_automaton_bisimulation(); max_states: 0 = the default of the device pass,
+ * STCSP_E_NOMEM beyond it. The result (stcsp_observer_get(): members named by this automaton's state indices; the time
+ * fields other than `seconds` and table_bytes are 0) lives until stcsp_observer_free(). */
+typedef struct stcsp_observer stcsp_observer;
+int stcsp_automaton_observer(const stcsp_automaton *a, const uint8_t *observable, int64_t max_states, stcsp_observer **out);
+const stcsp_observer_result *stcsp_observer_get(const stcsp_observer *o);
+void stcsp_observer_free(stcsp_observer *o);
+/* The observer as an automaton. `observer` is the result of stcsp_engine_observer() or of stcsp_automaton_observer() for
+ * the automaton `a` (same states, same flags) under `observable`. One state per set, printed with the constraint id and
+ * signature of its member of least canonical number (breadth-first from the root, out-edges in label order); final as
+ * the set; an edge carries the lexicographically least full label among the live edges out of the source set that
+ * project on its row, as stcsp_automaton_quotient() does. An observer without states gives the EMPTY automaton; a result
+ * that does not fit `a` is STCSP_E_INVALID. write_dot, write_binary, canonical, renumber, order_by_label, bisimulation,
+ * quotient, check_streams, count_streams, generate and observer work on the result, whose remembered mask is
+ * `observable`; free it with stcsp_automaton_free(). */
+int stcsp_automaton_from_observer(const stcsp_automaton *a, const uint8_t *observable, const stcsp_observer_result *observer,
+                                  stcsp_automaton **out);
+
 /* Merge the per-shard results of a sharded run (global state ids, see stcsp_engine.h) into
  * one result with dense ids; runs the ok-fixpoint over the union. The merged result is owned
  * by the returned handle. */

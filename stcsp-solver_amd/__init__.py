@@ -224,6 +224,59 @@ def _infer_unpack(count, soff, sval, nst, dvals, dfin, offsets, n_obs, draws):
         fin.append(dfin[i * draws:(i + 1) * draws].copy())
     return count, supports, n_states, out, fin
 
+class ObserverOptions(C.Structure):
+    _fields_ = [("max_states", C.c_int64), ("reserved", C.c_int32 * 2)]
+
+
+class ObserverResult(C.Structure):
+    _fields_ = [("n_states", C.c_int64), ("n_edges", C.c_int64), ("member_off", C.POINTER(C.c_int64)), ("member", C.POINTER(C.c_int32)),
+                ("state_final", C.POINTER(C.c_uint8)), ("edge_src", C.POINTER(C.c_int32)), ("edge_dst", C.POINTER(C.c_int32)),
+                ("edge_values", C.POINTER(C.c_int32)), ("n_labels", C.c_int64), ("max_set", C.c_int64), ("table_bytes", C.c_int64),
+                ("n_observable", C.c_int32), ("levels", C.c_int32), ("seconds", C.c_double), ("seconds_build", C.c_double),
+                ("seconds_items", C.c_double), ("seconds_intern", C.c_double), ("seconds_commit", C.c_double)]
+
+
+OBSERVER_SCALARS = ("n_states", "n_edges", "n_labels", "max_set", "table_bytes", "n_observable", "levels", "seconds", "seconds_build",
+                    "seconds_items", "seconds_intern", "seconds_commit")
+
+
+def _observer_unpack(res):
+    """An ObserverResult -> dict: copies of its arrays as numpy arrays (member_off int64 [n_states + 1], member int32, state_final
+    uint8 [n_states], edge_src / edge_dst int32 [n_edges], edge_values int32 [n_edges, n_observable]) and its scalars."""
+    import numpy as np
+    ns, ne, no = res.n_states, res.n_edges, res.n_observable
+
+    def arr(ptr, n, dtype):
+        return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dtype)
+    d = {k: getattr(res, k) for k in OBSERVER_SCALARS}
+    d["member_off"] = arr(res.member_off, ns + 1, np.int64)
+    d["member"] = arr(res.member, int(d["member_off"][-1]), np.int32)
+    d["state_final"] = arr(res.state_final, ns, np.uint8)
+    d["edge_src"] = arr(res.edge_src, ne, np.int32)
+    d["edge_dst"] = arr(res.edge_dst, ne, np.int32)
+    d["edge_values"] = arr(res.edge_values, ne * no, np.int32).reshape(ne, no)
+    return d
+
+
+def _observer_pack(obs):
+    """The dict of _observer_unpack() -> (ObserverResult, the arrays it points into)."""
+    import numpy as np
+    keep = {k: np.ascontiguousarray(obs[k], dtype=t) for k, t in (("member_off", np.int64), ("member", np.int32), ("state_final", np.uint8),
+                                                                     ("edge_src", np.int32), ("edge_dst", np.int32), ("edge_values", np.int32))}
+    for k in list(keep):
+        if keep[k].size == 0:
+            keep[k] = np.zeros(1, keep[k].dtype)
+    res = ObserverResult()
+    res.n_states, res.n_edges, res.n_observable = int(obs["n_states"]), int(obs["n_edges"]), int(obs["n_observable"])
+    res.member_off = keep["member_off"].ctypes.data_as(C.POINTER(C.c_int64))
+    res.member = keep["member"].ctypes.data_as(C.POINTER(C.c_int32))
+    res.state_final = keep["state_final"].ctypes.data_as(C.POINTER(C.c_uint8))
+    res.edge_src = keep["edge_src"].ctypes.data_as(C.POINTER(C.c_int32))
+    res.edge_dst = keep["edge_dst"].ctypes.data_as(C.POINTER(C.c_int32))
+    res.edge_values = keep["edge_values"].ctypes.data_as(C.POINTER(C.c_int32))
+    return res, keep
+
+
 F_KEEP_RAW_EDGES = 1
 F_NO_EXPORT = 2
 F_PROFILE = 4
@@ -239,7 +292,7 @@ ENGINE_SYMBOLS = [
     "stcsp_engine_propagate", "stcsp_engine_set_expand_budget", "stcsp_engine_node_bytes", "stcsp_engine_donate",
     "stcsp_engine_adopt", "stcsp_engine_expand_variant", "stcsp_engine_quotient",
     "stcsp_engine_monitor_build", "stcsp_engine_monitor_check", "stcsp_engine_generator_build", "stcsp_engine_generate",
-    "stcsp_engine_repair", "stcsp_engine_infer",
+    "stcsp_engine_repair", "stcsp_engine_infer", "stcsp_engine_observer",
 ]
 # include/stcsp_sharded.h: the superstep loop + in-process transport (libstcsp_hip.so), the RCCL transport (libstcsp_rccl.so)
 SHARDED_SYMBOLS_HIP = ["stcsp_engine_solve_sharded", "stcsp_local_group_create", "stcsp_local_group_transport", "stcsp_local_group_destroy"]
@@ -256,6 +309,7 @@ HOST_SYMBOLS = [
     "stcsp_automaton_bisimulation", "stcsp_automaton_set_observable", "stcsp_automaton_quotient",
     "stcsp_automaton_check_streams", "stcsp_automaton_num_observable", "stcsp_automaton_generate", "stcsp_automaton_count_streams",
     "stcsp_automaton_repair_streams", "stcsp_automaton_infer_streams",
+    "stcsp_automaton_observer", "stcsp_observer_get", "stcsp_observer_free", "stcsp_automaton_from_observer",
 ]
 
 
@@ -337,6 +391,11 @@ def host_lib() -> C.CDLL:
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.stcsp_automaton_infer_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                                       C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.stcsp_automaton_observer.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+        lib.stcsp_observer_get.argtypes = [C.c_void_p]
+        lib.stcsp_observer_get.restype = C.POINTER(ObserverResult)
+        lib.stcsp_observer_free.argtypes = [C.c_void_p]
+        lib.stcsp_automaton_from_observer.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ObserverResult), C.POINTER(C.c_void_p)]
         lib.stcsp_merge_shards.argtypes = [C.POINTER(C.POINTER(Result)), C.c_int, C.POINTER(C.c_void_p)]
         lib.stcsp_merged_result.argtypes = [C.c_void_p]
         lib.stcsp_merged_result.restype = C.POINTER(Result)
@@ -392,6 +451,8 @@ def bind_engine_api(lib: C.CDLL, prefix: str = "stcsp_engine") -> None:
         g("repair").argtypes = [C.c_void_p, C.POINTER(RepairRequest), C.POINTER(RepairResult)]
     if hasattr(lib, f"{prefix}_infer"):
         g("infer").argtypes = [C.c_void_p, C.POINTER(InferRequest), C.POINTER(InferResult)]
+    if hasattr(lib, f"{prefix}_observer"):
+        g("observer").argtypes = [C.c_void_p, C.POINTER(ObserverOptions), C.POINTER(ObserverResult)]
     if hasattr(lib, f"{prefix}_propagate"):
         g("propagate").argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64)]
@@ -707,6 +768,36 @@ class Automaton:
         vals = np.ctypeslib.as_array(C.cast(sval, C.POINTER(C.c_int32)), shape=(max(total, 1),))[:total].copy()
         lib.stcsp_host_free(sval)
         return _infer_unpack(count[:n], soff, vals, nst, dvals, dfin, offsets, n_obs, max(draws, 0))
+
+    def observer(self, observable=None, max_states=0):
+        """The observer (subset construction) of the live automaton under `observable` (as in bisimulation()) by the host twin
+        of Engine.observer() (contract: include/stcsp_engine.h, stcsp_engine_observer), on the automaton's current flags.
+        Returns a dict of numpy arrays and scalars (see _observer_unpack()); StcspError -4 beyond max_states (0: the default)."""
+        lib = host_lib()
+        m = self._mask(observable)
+        h = C.c_void_p()
+        rc = lib.stcsp_automaton_observer(self._h, m.ctypes.data if m is not None else None, max_states, C.byref(h))
+        if rc != 0:
+            raise StcspError(rc, "observer failed: more sets than max_states" if rc == -4 else "observer failed")
+        try:
+            return _observer_unpack(lib.stcsp_observer_get(h).contents)
+        finally:
+            lib.stcsp_observer_free(h)
+
+    def from_observer(self, obs, observable=None) -> "Automaton":
+        """The observer `obs` (the dict of Engine.observer() or observer() for this automaton under `observable`) as an
+        Automaton: one state per set, one edge per (set, projected row), carrying the least full label that projects on it."""
+        lib = host_lib()
+        m = self._mask(observable)
+        res, keep = _observer_pack(obs)
+        h = C.c_void_p()
+        rc = lib.stcsp_automaton_from_observer(self._h, m.ctypes.data if m is not None else None, C.byref(res), C.byref(h))
+        del keep
+        if rc != 0:
+            raise StcspError(rc, "from_observer failed: the observer does not belong to this automaton and mask")
+        q = Automaton.__new__(Automaton)
+        q._h, q._model, q._n_edges = h, self._model, 0
+        return q
 
     def count_streams(self, horizon, end_final=False):
         """count[t], t = 0 .. horizon: the number of solution prefixes of length t (float64; exact below 2^53)."""
@@ -1024,6 +1115,18 @@ class EngineBase:
         soff = arr(out.support_off, steps * n_obs + 1, np.int64)
         return _infer_unpack(arr(out.count, n, np.float64), soff, arr(out.support_val, int(soff[-1]), np.int32), arr(out.n_states, steps + n, np.int32),
                              arr(out.values, steps * draws * n_obs, np.int32), arr(out.end_final, n * draws, np.uint8), offsets, n_obs, draws)
+
+    def observer(self, max_states=0):
+        """The observer (subset construction) of the live automaton on the device, after generator() (its mask; its horizon plays
+        no part): the deterministic automaton over the sets of states the system can be in after an observed prefix. Returns a
+        dict of numpy arrays and scalars (see _observer_unpack()); members are state indices of the last Result. StcspError -4
+        beyond max_states (0: the default) or the byte budget. Contract: include/stcsp_engine.h, stcsp_engine_observer."""
+        if getattr(self, "generator_info", None) is None:
+            raise StcspError(-6, "observer() needs generator() first")
+        oo = ObserverOptions(max_states)
+        out = ObserverResult()
+        self._check(self._f("observer")(self._h, C.byref(oo), C.byref(out)))
+        return _observer_unpack(out)
 
     def automaton(self, result: Result | None = None) -> Automaton:
         return Automaton(self._model, result if result is not None else self.result)

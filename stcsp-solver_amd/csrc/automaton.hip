@@ -1,5 +1,5 @@
 // automaton.hip -- the host side of the services on the exported automaton: post-processing, bisimulation quotient, stream monitor,
-// generator, repair and inference, with the kernels they launch. No kernel is shared with the search (engine.hip).
+// generator, repair, inference and observer, with the kernels they launch. No kernel is shared with the search (engine.hip).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -17,6 +17,7 @@
 #include "generate_host.hpp"
 #include "dev_repair.hpp"
 #include "dev_infer.hpp"
+#include "dev_observer.hpp"
 #include "repair_host.hpp"
 #include "infer_host.hpp"
 
@@ -47,7 +48,7 @@ int AutomatonServices::fail(int code, const char *fmt, ...) {
 }
 
 void AutomatonServices::invalidate() {
-    post_done = live_done = mon_built = gen_built = rep_built = inf_built = false;
+    post_done = live_done = mon_built = gen_built = rep_built = inf_built = obs_built = false;
     mon_host.reset();
 }
 
@@ -495,6 +496,7 @@ int AutomatonServices::generator_build(const AutomatonView &view, const stcsp_ge
     gen_built = false;
     rep_built = false;
     inf_built = false;
+    obs_built = false;
     const int N = v.N, H = go->horizon;
     const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
     if ((size_t)v.exp_edges > 0x7fffffffull) return fail(STCSP_E_NOMEM, "edge list too large for the device generator");
@@ -942,6 +944,334 @@ int AutomatonServices::infer(const AutomatonView &view, const stcsp_infer_reques
     if (i_sval.empty()) i_sval.reserve(1);
     publish();
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return STCSP_OK;
+}
+
+// A buffer that has to grow in the middle of a construction: the first `keep` elements move to the larger one.
+template <typename T>
+int AutomatonServices::grow_keeping(DevBuf<T> &buf, size_t keep, size_t count) {
+    if (buf.n >= count) return STCSP_OK;
+    DevBuf<T> bigger;
+    const size_t room = std::max(grown(count), 2 * buf.n);
+    if (bigger.alloc(room) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(STCSP_E_NOMEM, "observer: no room for %zu bytes on the device", room * sizeof(T));
+    }
+    if (keep) HIPCHK(hipMemcpyAsync(bigger.p, buf.p, keep * sizeof(T), hipMemcpyDeviceToDevice, v.stream));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    std::swap(buf.p, bigger.p);
+    std::swap(buf.n, bigger.n);
+    return STCSP_OK;
+}
+
+// Observer, the ordered out-edges (dev_observer.hpp): built on the first observer() after a generator_build(), over the label
+// ids of repair_labels(). The host sorts the n_labels projected rows; their ranks are the labels of the construction.
+int AutomatonServices::observer_order(double &seconds) {
+    const uint32_t S = v.n_states, nL = rep_n_labels;
+    const size_t n_obs = (size_t)gen_n_obs, cells = (size_t)nL * n_obs;
+    std::vector<int32_t> rows(cells);
+    if (cells) {
+        HIPCHK(d_ilabrows.reserve(cells));
+        hipLaunchKernelGGL(k_i_rows, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, v.stream, nL, (const uint32_t *)d_rrep.p,
+                           (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p, gen_n_obs, d_ilabrows.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rows.data(), d_ilabrows.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+    }
+    std::vector<uint32_t> order(nL), lrank(nL);
+    for (uint32_t l = 0; l < nL; l++) order[l] = l;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        return std::lexicographical_compare(rows.begin() + a * n_obs, rows.begin() + (a + 1) * n_obs, rows.begin() + b * n_obs, rows.begin() + (b + 1) * n_obs);
+    });
+    obs_rows.resize(cells);
+    for (uint32_t r = 0; r < nL; r++) {
+        lrank[order[r]] = r;
+        std::copy(rows.begin() + order[r] * n_obs, rows.begin() + (order[r] + 1) * n_obs, obs_rows.begin() + r * n_obs);
+    }
+    HIPCHK(d_olrank.reserve(nL));
+    HIPCHK(d_okey.reserve(rep_total));
+    HIPCHK(d_octl.reserve_exact(O_WORDS));
+    HIPCHK(ev.ready(2));
+    uint32_t ctl[O_WORDS] = {0};
+    HIPCHK(hipMemsetAsync(d_octl.p, 0, sizeof ctl, v.stream));
+    if (nL) HIPCHK(hipMemcpyAsync(d_olrank.p, lrank.data(), nL * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+    HIPCHK(hipEventRecord(ev[0], v.stream));
+    if (rep_total)
+        hipLaunchKernelGGL(k_o_order, dim3((S + 3) / 4), dim3(256), 0, v.stream, S, (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p,
+                           (const uint32_t *)d_gdst.p, (const uint32_t *)d_olrank.p, d_okey.p, d_octl.p);
+    HIPCHK(hipEventRecord(ev[1], v.stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ctl, d_octl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipStreamSynchronize(v.stream));  // (lrank is a local)
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    seconds = ms * 1e-3;
+    obs_max_deg = ctl[O_MAXDEG];
+    obs_built = true;
+    return STCSP_OK;
+}
+
+// Observer: the subset construction of the live automaton under the generator's mask (contract: stcsp_engine.h).
+int AutomatonServices::observer(const AutomatonView &view, const stcsp_observer_options *oo, stcsp_observer_result *out) {
+    if (int rc = enter(view, "observer", NEED_GENERATOR, "stcsp_automaton_observer")) return rc;
+    if (oo && oo->max_states < 0) return fail(STCSP_E_INVALID, "observer: max_states must not be negative");
+    auto t0 = std::chrono::steady_clock::now();
+    const unsigned long long max_states = std::min<unsigned long long>(oo && oo->max_states ? (unsigned long long)oo->max_states : 1ull << 26, 0x7ffffffeull);
+    const size_t n_obs = (size_t)gen_n_obs;
+    o_moff.assign(1, 0);
+    o_member.clear();
+    o_final.clear();
+    o_esrc.clear();
+    o_edst.clear();
+    o_evalues.clear();
+    memset(out, 0, sizeof *out);
+    out->n_observable = gen_n_obs;
+    auto publish = [&]() {  // (empty vectors still give valid pointers)
+        o_member.reserve(1);
+        o_final.reserve(1);
+        o_esrc.reserve(1);
+        o_edst.reserve(1);
+        o_evalues.reserve(1);
+        out->member_off = o_moff.data();
+        out->member = o_member.data();
+        out->state_final = o_final.data();
+        out->edge_src = o_esrc.data();
+        out->edge_dst = o_edst.data();
+        out->edge_values = o_evalues.data();
+        out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    };
+    if (!root_live) {
+        publish();
+        return STCSP_OK;
+    }
+    if (int rc = rep_built ? STCSP_OK : repair_labels()) return rc;
+    if (int rc = obs_built ? STCSP_OK : observer_order(out->seconds_build)) return rc;
+    size_t budget = 0;
+    if (int rc = table_budget("STCSP_OBSERVER_BYTES", budget)) return rc;
+    const char *force = getenv("STCSP_OBSERVER_GLOBAL_SCRATCH");
+    const uint32_t S = v.n_states, W = (S + 31) / 32, nL = rep_n_labels;
+    const bool global_bits = W > kObsLdsWords || (force && atoi(force) != 0);
+    auto pow2 = [](unsigned long long n) {
+        unsigned long long c = 1024;
+        while (c < n) c <<= 1;
+        return c;
+    };
+    HIPCHK(ev.ready(6));
+    // the root's set
+    unsigned long long cap_s = 1024, pool_top = 1, scratch_peak = 0;
+    uint32_t n_states = 1, e_total = 0;
+    HIPCHK(d_ostab.reserve_exact(cap_s));
+    HIPCHK(d_ossid.reserve_exact(cap_s));
+    HIPCHK(d_orec.reserve(1));
+    HIPCHK(d_opool.reserve(1));
+    uint32_t ctl[O_WORDS] = {0};
+    HIPCHK(hipMemsetAsync(d_octl.p, 0, sizeof ctl, v.stream));
+    HIPCHK(hipMemsetAsync(d_ostab.p, 0xff, cap_s * sizeof(unsigned long long), v.stream));
+    hipLaunchKernelGGL(k_o_init, dim3(1), dim3(64), 0, v.stream, (const uint8_t *)d_pfinal.p, d_orec.p, d_opool.p, d_ostab.p, d_ossid.p, (uint32_t)(cap_s - 1),
+                       d_octl.p);
+    auto read_ctl = [&]() -> int {
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ctl, d_octl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        if (ctl[O_ERROR] & (O_ERR_TABLE_FULL | O_ERR_ITEMS_FULL)) return fail(STCSP_E_INTERNAL, "observer: a device table overflowed (flags %u)", ctl[O_ERROR]);
+        if (ctl[O_ERROR]) return fail(STCSP_E_INTERNAL, "observer: two distinct sets of states share a hash (collision)");
+        return STCSP_OK;
+    };
+    bool commit_pending = false;
+    auto take_commit_time = [&]() -> int {
+        float ms = 0;
+        if (commit_pending) HIPCHK(hipEventElapsedTime(&ms, ev[4], ev[5]));
+        out->seconds_commit += ms * 1e-3;
+        commit_pending = false;
+        return STCSP_OK;
+    };
+    auto succ = [&](int mode, uint32_t n_items, uint32_t c0, uint32_t grid, uint32_t e_base) {
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, v.stream, n_items, c0, (const unsigned long long *)d_oitems.p, d_orec.p, d_opool.p,
+                               (const uint32_t *)d_goff.p, (const unsigned long long *)d_okey.p, (const uint8_t *)d_pfinal.p, W, d_oscratch.p, d_ostab.p,
+                               d_ossid.p, (uint32_t)(cap_s - 1), d_oslot.p, e_base, d_oesrc.p, d_oelab.p, d_oedst.p, d_octl.p);
+        };
+        if (global_bits)
+            mode == O_INTERN ? go(k_o_succ<true, O_INTERN>) : mode == O_WRITE ? go(k_o_succ<true, O_WRITE>) : go(k_o_succ<true, O_VERIFY>);
+        else
+            mode == O_INTERN ? go(k_o_succ<false, O_INTERN>) : mode == O_WRITE ? go(k_o_succ<false, O_WRITE>) : go(k_o_succ<false, O_VERIFY>);
+    };
+    struct Level { uint32_t e0, e1, s0, s1; };  // the edges logged at a level, the states new there
+    std::vector<Level> levels;
+    unsigned long long level_members = 1;
+    for (uint32_t f0 = 0, f1 = 1; f0 < f1;) {
+        const uint32_t e_begin = e_total;
+        const unsigned long long pool_begin = pool_top;
+        const int level = (int)levels.size();
+        for (uint32_t c0 = f0; c0 < f1;) {
+            // the chunk: as many frontier sets as their possible items (a set has at most n_labels, a member at most max_deg) leave in the budget
+            auto bound_of = [&](unsigned long long sets) {
+                return std::max<unsigned long long>(1, std::min<unsigned long long>(sets * nL, level_members * obs_max_deg));
+            };
+            auto bytes_of = [&](unsigned long long items) { return pow2(2 * items) * sizeof(unsigned long long) + items * (sizeof(unsigned long long) + sizeof(uint32_t)); };
+            unsigned long long chunk = f1 - c0;
+            while (chunk > 1 && (bytes_of(bound_of(chunk)) > budget || bound_of(chunk) > 0x3fffffffull)) chunk = (chunk + 1) / 2;
+            const unsigned long long bound = bound_of(chunk);
+            if (bytes_of(bound) > budget || bound > 0x3fffffffull)
+                return fail(STCSP_E_NOMEM, "observer: the %llu possible work items of one set need %llu bytes, the budget (STCSP_OBSERVER_BYTES) is %zu; the construction got to level %d with %u states and %u edges",
+                            bound, bytes_of(bound), budget, level, n_states, e_total);
+            const uint32_t c1 = c0 + (uint32_t)chunk;
+            const unsigned long long cap_i = pow2(2 * bound);
+            scratch_peak = std::max(scratch_peak, bytes_of(bound));
+            if (!d_oitab.reserve_or_release(cap_i) || !d_oitems.reserve_or_release(bound))
+                return fail(STCSP_E_NOMEM, "observer: no room for %llu bytes of work items at level %d (%u states so far)", bytes_of(bound), level, n_states);
+            HIPCHK(hipMemsetAsync(d_oitab.p, 0xff, cap_i * sizeof(unsigned long long), v.stream));
+            HIPCHK(hipMemsetAsync(d_octl.p + O_ITEMS, 0, sizeof(uint32_t), v.stream));
+            HIPCHK(hipEventRecord(ev[0], v.stream));
+            hipLaunchKernelGGL(k_o_items, dim3((unsigned)std::min<unsigned long long>(chunk, 4096)), dim3(256), 0, v.stream, c0, c1, (const ObsRec *)d_orec.p,
+                               (const uint32_t *)d_opool.p, (const uint32_t *)d_goff.p, (const unsigned long long *)d_okey.p, d_oitab.p, (uint32_t)(cap_i - 1),
+                               d_oitems.p, (uint32_t)bound, d_octl.p);
+            HIPCHK(hipEventRecord(ev[1], v.stream));
+            if (int rc = read_ctl()) return rc;
+            if (int rc = take_commit_time()) return rc;
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            out->seconds_items += ms * 1e-3;
+            const uint32_t n_items = ctl[O_ITEMS];
+            c0 = c1;
+            if (!n_items) continue;
+            if ((unsigned long long)e_total + n_items > 0x7fffffffull)
+                return fail(STCSP_E_NOMEM, "observer: more than 2^31 - 1 edges (level %d, %u states so far)", level, n_states);
+            // room for what the items may add: slots, records, edges
+            if (cap_s < 2ull * ((unsigned long long)n_states + n_items)) {
+                const unsigned long long old = cap_s;
+                cap_s = pow2(2ull * ((unsigned long long)n_states + n_items));
+                if (cap_s > 0x80000000ull || !d_ostab2.reserve_or_release(cap_s) || !d_ossid2.reserve_or_release(cap_s))
+                    return fail(STCSP_E_NOMEM, "observer: no room for a table of %llu slots at level %d (%u states so far)", cap_s, level, n_states);
+                HIPCHK(hipMemsetAsync(d_ostab2.p, 0xff, cap_s * sizeof(unsigned long long), v.stream));
+                hipLaunchKernelGGL(k_o_rehash, dim3((unsigned)(old / 256)), dim3(256), 0, v.stream, (uint32_t)old, (const unsigned long long *)d_ostab.p,
+                                   (const uint32_t *)d_ossid.p, d_ostab2.p, d_ossid2.p, (uint32_t)(cap_s - 1), d_octl.p);
+                HIPCHK(hipStreamSynchronize(v.stream));
+                std::swap(d_ostab.p, d_ostab2.p);
+                std::swap(d_ostab.n, d_ostab2.n);
+                std::swap(d_ossid.p, d_ossid2.p);
+                std::swap(d_ossid.n, d_ossid2.n);
+            }
+            if (int rc = grow_keeping(d_orec, n_states, (size_t)n_states + n_items)) return rc;
+            if (int rc = grow_keeping(d_oesrc, e_total, (size_t)e_total + n_items)) return rc;
+            if (int rc = grow_keeping(d_oelab, e_total, (size_t)e_total + n_items)) return rc;
+            if (int rc = grow_keeping(d_oedst, e_total, (size_t)e_total + n_items)) return rc;
+            HIPCHK(d_oslot.reserve(n_items));
+            uint32_t grid = std::min<uint32_t>(n_items, 2048);
+            if (global_bits) {  // a slice of W words per workgroup
+                grid = (uint32_t)std::max<unsigned long long>(1, std::min<unsigned long long>(std::min<uint32_t>(n_items, 1024), budget / ((size_t)W * sizeof(uint32_t))));
+                scratch_peak = std::max(scratch_peak, bytes_of(bound) + (unsigned long long)grid * W * sizeof(uint32_t));
+                if (!d_oscratch.reserve_or_release((size_t)grid * W))
+                    return fail(STCSP_E_NOMEM, "observer: no room for %zu bytes of bitsets at level %d (%u states so far)", (size_t)grid * W * sizeof(uint32_t), level, n_states);
+            }
+            HIPCHK(hipEventRecord(ev[2], v.stream));
+            succ(O_INTERN, n_items, c1 - (uint32_t)chunk, grid, e_total);
+            HIPCHK(hipEventRecord(ev[3], v.stream));
+            if (int rc = read_ctl()) return rc;
+            HIPCHK(hipEventElapsedTime(&ms, ev[2], ev[3]));
+            out->seconds_intern += ms * 1e-3;
+            const unsigned long long pool_now = (unsigned long long)ctl[O_POOL] | ((unsigned long long)ctl[O_POOL + 1] << 32);
+            // both limits are checked here, before a list is written
+            if (ctl[O_STATES] > max_states)
+                return fail(STCSP_E_NOMEM, "observer: more than max_states = %llu states; the construction got to level %d with %u states and %u edges", max_states,
+                            level, n_states, e_total);
+            if (pool_now * sizeof(uint32_t) > budget)
+                return fail(STCSP_E_NOMEM, "observer: the member lists need more than the budget of %zu bytes (STCSP_OBSERVER_BYTES); the construction got to level %d with %u states, %llu members and %u edges",
+                            budget, level, n_states, pool_top, e_total);
+            if (int rc = grow_keeping(d_opool, (size_t)pool_top, (size_t)pool_now)) return rc;
+            HIPCHK(hipEventRecord(ev[4], v.stream));
+            succ(O_WRITE, n_items, c1 - (uint32_t)chunk, grid, e_total);
+            succ(O_VERIFY, n_items, c1 - (uint32_t)chunk, grid, e_total);
+            HIPCHK(hipEventRecord(ev[5], v.stream));
+            commit_pending = true;
+            n_states = ctl[O_STATES];
+            pool_top = pool_now;
+            e_total += n_items;
+        }
+        levels.push_back(Level{e_begin, e_total, f1, n_states});
+        level_members = pool_top - pool_begin;
+        f0 = f1;
+        f1 = n_states;
+    }
+    if (int rc = read_ctl()) return rc;  // (the last verify)
+    if (int rc = take_commit_time()) return rc;
+    // canonical numbers, level by level: a new state's key is the least (number of a parent, label rank) over the edges of the level
+    std::vector<uint32_t> canon(n_states, 0), idx;
+    std::vector<unsigned long long> keys;
+    HIPCHK(d_ocanon.reserve(n_states));
+    HIPCHK(d_okeys.reserve(n_states));
+    HIPCHK(hipMemsetAsync(d_okeys.p, 0xff, (size_t)n_states * sizeof(unsigned long long), v.stream));
+    HIPCHK(hipMemsetAsync(d_ocanon.p, 0, sizeof(uint32_t), v.stream));
+    uint32_t next = 1;
+    for (const Level &lv : levels) {
+        const uint32_t n_new = lv.s1 - lv.s0;
+        if (!n_new) continue;
+        hipLaunchKernelGGL(k_o_keys, dim3((lv.e1 - lv.e0 + 255) / 256), dim3(256), 0, v.stream, lv.e0, lv.e1, (const uint32_t *)d_oesrc.p,
+                           (const uint32_t *)d_oelab.p, (const uint32_t *)d_oedst.p, lv.s0, (const uint32_t *)d_ocanon.p, d_okeys.p);
+        HIPCHK(hipGetLastError());
+        keys.resize(n_new);
+        HIPCHK(hipMemcpyAsync(keys.data(), d_okeys.p + lv.s0, (size_t)n_new * sizeof(unsigned long long), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        idx.resize(n_new);
+        for (uint32_t i = 0; i < n_new; i++) idx[i] = i;
+        std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
+        for (uint32_t i = 0; i < n_new; i++) canon[lv.s0 + idx[i]] = next++;
+        HIPCHK(hipMemcpyAsync(d_ocanon.p + lv.s0, canon.data() + lv.s0, (size_t)n_new * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+    }
+    // the result: records, members in canonical order, edges sorted by (source number, label rank)
+    std::vector<ObsRec> rec(n_states);
+    std::vector<unsigned long long> where(n_states);
+    HIPCHK(hipMemcpyAsync(rec.data(), d_orec.p, (size_t)n_states * sizeof(ObsRec), hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    o_moff.assign((size_t)n_states + 1, 0);
+    o_final.assign(n_states, 0);
+    int64_t max_set = 0;
+    for (uint32_t s = 0; s < n_states; s++) {
+        o_moff[canon[s] + 1] = rec[s].n;
+        o_final[canon[s]] = (uint8_t)rec[s].fin;
+        max_set = std::max<int64_t>(max_set, rec[s].n);
+    }
+    for (uint32_t c = 0; c < n_states; c++) o_moff[c + 1] += o_moff[c];
+    for (uint32_t s = 0; s < n_states; s++) where[s] = (unsigned long long)o_moff[canon[s]];
+    if ((unsigned long long)o_moff[n_states] != pool_top) return fail(STCSP_E_INTERNAL, "observer: the records name %lld members, the pool holds %llu", (long long)o_moff[n_states], pool_top);
+    HIPCHK(d_owhere.reserve(n_states));
+    HIPCHK(d_omember.reserve((size_t)pool_top));
+    HIPCHK(hipMemcpyAsync(d_owhere.p, where.data(), (size_t)n_states * sizeof(unsigned long long), hipMemcpyHostToDevice, v.stream));
+    hipLaunchKernelGGL(k_o_gather, dim3(std::min<uint32_t>(n_states, 4096)), dim3(256), 0, v.stream, n_states, (const ObsRec *)d_orec.p,
+                       (const unsigned long long *)d_owhere.p, (const uint32_t *)d_opool.p, d_omember.p);
+    if (e_total)
+        hipLaunchKernelGGL(k_o_renumber, dim3((e_total + 255) / 256), dim3(256), 0, v.stream, e_total, d_oesrc.p, d_oedst.p, (const uint32_t *)d_ocanon.p);
+    HIPCHK(hipGetLastError());
+    o_member.resize((size_t)pool_top);
+    std::vector<uint32_t> esrc(e_total), elab(e_total), edst(e_total);
+    HIPCHK(hipMemcpyAsync(o_member.data(), d_omember.p, (size_t)pool_top * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+    if (e_total) {
+        HIPCHK(hipMemcpyAsync(esrc.data(), d_oesrc.p, (size_t)e_total * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(elab.data(), d_oelab.p, (size_t)e_total * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(edst.data(), d_oedst.p, (size_t)e_total * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+    }
+    HIPCHK(hipStreamSynchronize(v.stream));
+    idx.resize(e_total);
+    for (uint32_t e = 0; e < e_total; e++) idx[e] = e;
+    std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return esrc[a] != esrc[b] ? esrc[a] < esrc[b] : elab[a] < elab[b]; });
+    o_esrc.resize(e_total);
+    o_edst.resize(e_total);
+    o_evalues.resize((size_t)e_total * n_obs);
+    for (uint32_t i = 0; i < e_total; i++) {
+        const uint32_t e = idx[i];
+        o_esrc[i] = (int32_t)esrc[e];
+        o_edst[i] = (int32_t)edst[e];
+        std::copy(obs_rows.begin() + elab[e] * n_obs, obs_rows.begin() + (elab[e] + 1) * n_obs, o_evalues.begin() + i * n_obs);
+    }
+    out->n_states = n_states;
+    out->n_edges = e_total;
+    out->n_labels = nL;
+    out->max_set = max_set;
+    out->levels = (int32_t)levels.size();
+    out->table_bytes = (int64_t)(pool_top * sizeof(uint32_t) + (size_t)n_states * sizeof(ObsRec) + cap_s * (sizeof(unsigned long long) + sizeof(uint32_t)) +
+                                 (size_t)e_total * 3 * sizeof(uint32_t) + scratch_peak + (size_t)rep_total * sizeof(unsigned long long));
+    publish();
     return STCSP_OK;
 }
 

@@ -9,7 +9,7 @@
 
 namespace stcsp {
 
-namespace dev { struct RepStream; struct InfStream; }
+namespace dev { struct RepStream; struct InfStream; struct ObsRec; }
 struct HostMonitor;
 
 // what the engine hands a service call: the last export and the facts of model and solve the services read. Valid for the call only.
@@ -42,6 +42,7 @@ struct AutomatonServices {
     int generate(const AutomatonView &view, const stcsp_generate_request *rq, stcsp_generate_result *out);
     int repair(const AutomatonView &view, const stcsp_repair_request *rq, stcsp_repair_result *out);
     int infer(const AutomatonView &view, const stcsp_infer_request *rq, stcsp_infer_result *out);
+    int observer(const AutomatonView &view, const stcsp_observer_options *oo, stcsp_observer_result *out);
 
 private:
     enum Need { NEED_EXPORT, NEED_FLAGS, NEED_MONITOR, NEED_GENERATOR };
@@ -54,6 +55,9 @@ private:
     int plan_batch(const char *who, const int64_t *offsets, size_t n, size_t b0, size_t budget, NeedFn need, std::vector<Rec> &meta, Batch &b);
     int repair_labels();
     int infer_dictionaries();
+    int observer_order(double &seconds);
+    template <typename T>
+    int grow_keeping(DevBuf<T> &buf, size_t keep, size_t count);
 
     AutomatonView v{};  // of the call that is running: its pointers are the engine's, not to be used after it
     DevEvents ev;     // (every call waits for its own work: one set serves them all)
@@ -118,6 +122,18 @@ private:
     std::vector<int64_t> i_soff;
     std::vector<int32_t> i_sval, i_nstates, i_values;
     std::vector<uint32_t> i_bits;
+    // observer (dev_observer.hpp): the out-edges ordered by (label rank, destination) and the label rows in rank order, valid
+    // while gen_built && rep_built && obs_built; everything else lives for one call
+    bool obs_built = false;
+    uint32_t obs_max_deg = 0;
+    std::vector<int32_t> obs_rows;  // [n_labels][n_obs], sorted
+    DevBuf<unsigned long long> d_okey, d_oitab, d_oitems, d_ostab, d_ostab2, d_okeys, d_owhere;
+    DevBuf<uint32_t> d_olrank, d_octl, d_opool, d_ossid, d_ossid2, d_oslot, d_oesrc, d_oelab, d_oedst, d_ocanon, d_oscratch;
+    DevBuf<dev::ObsRec> d_orec;
+    DevBuf<int32_t> d_omember;
+    std::vector<int64_t> o_moff;
+    std::vector<int32_t> o_member, o_esrc, o_edst, o_evalues;
+    std::vector<uint8_t> o_final;
 };
 
 }  // namespace stcsp

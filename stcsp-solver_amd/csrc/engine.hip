@@ -2399,6 +2399,10 @@ int stcsp_engine_infer(stcsp_engine *e, const stcsp_infer_request *request, stcs
     if (!e || !request || !result) return STCSP_E_INVALID;
     return e->services.infer(e->view(), request, result);
 }
+int stcsp_engine_observer(stcsp_engine *e, const stcsp_observer_options *options, stcsp_observer_result *result) {
+    if (!e || !result) return STCSP_E_INVALID;
+    return e->services.observer(e->view(), options, result);
+}
 
 void stcsp_engine_destroy(stcsp_engine *e) { delete e; }
 

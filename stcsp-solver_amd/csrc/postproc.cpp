@@ -23,7 +23,9 @@
 
 #include "generate_host.hpp"
 #include "monitor_host.hpp"
+#include <chrono>
 #include "repair_host.hpp"
+#include "observer_host.hpp"
 #include "infer_host.hpp"
 #include "okfix.hpp"
 #include "stcsp_host.h"
@@ -896,6 +898,83 @@ struct Automaton {
         q.build_csr();
         return STCSP_OK;
     }
+    // The observer as an automaton (o: stcsp_engine_observer() or stcsp_automaton_observer() of this automaton under `obs`): one state
+    // per set, printed with the constraint id and signature of its member of least canonical number; an edge carries the
+    // lexicographically least full label among the live edges between members of its two sets that project on its row.
+    int from_observer(const uint8_t *obs, const stcsp_observer_result &o, Automaton &q) const {
+        const std::vector<uint8_t> mask = observable_mask(obs);
+        int n_obs = 0;
+        for (uint8_t m : mask) n_obs += m != 0;
+        if (o.n_states < 0 || o.n_edges < 0 || o.n_observable != n_obs || (o.n_states == 0 && o.n_edges != 0)) return STCSP_E_INVALID;
+        q.n_vars = n_vars;
+        q.sig_len = sig_len;
+        q.n_sig_vars = n_sig_vars;
+        q.n_until = n_until;
+        q.names = names;
+        q.is_sig = is_sig;
+        q.var_lb = var_lb;
+        q.var_ub = var_ub;
+        q.observable = mask;
+        const bool empty = o.n_states == 0;  // no live root: the EMPTY automaton
+        q.n_states = empty ? 1 : o.n_states;
+        q.cid.assign((size_t)q.n_states, 0);
+        q.sig.assign((size_t)q.n_states * sig_len, 0);
+        q.fail.assign((size_t)q.n_states, 0);
+        q.valid.assign((size_t)q.n_states, empty ? 0 : 1);
+        q.final_.assign((size_t)q.n_states, 0);
+        q.id.resize((size_t)q.n_states);
+        for (int64_t c = 0; c < q.n_states; c++) q.id[(size_t)c] = c;
+        if (!empty) {
+            const std::vector<int64_t> num = canonical_numbers();
+            if (o.member_off[0] != 0) return STCSP_E_INVALID;
+            for (int64_t c = 0; c < o.n_states; c++) {
+                int64_t rep = -1;
+                if (o.member_off[c + 1] <= o.member_off[c]) return STCSP_E_INVALID;  // (a set is never empty)
+                for (int64_t k = o.member_off[c]; k < o.member_off[c + 1]; k++) {
+                    const int64_t s = o.member[k];
+                    if (s < 0 || s >= n_states || num[(size_t)s] < 0) return STCSP_E_INVALID;  // not a live state
+                    if (rep < 0 || num[(size_t)s] < num[(size_t)rep]) rep = s;
+                }
+                q.cid[(size_t)c] = cid[(size_t)rep];
+                q.final_[(size_t)c] = o.state_final[c] ? 1 : 0;
+                std::copy(sig.begin() + rep * sig_len, sig.begin() + (rep + 1) * sig_len, q.sig.begin() + c * sig_len);
+            }
+            std::map<std::vector<int32_t>, int64_t> least;  // of the source set in hand: projected row -> edge with the least full label
+            int64_t in_hand = -1;
+            std::vector<int32_t> row;
+            for (int64_t i = 0; i < o.n_edges; i++) {
+                const int64_t c = o.edge_src[i], d = o.edge_dst[i];
+                if (c < 0 || c >= o.n_states || d < 0 || d >= o.n_states) return STCSP_E_INVALID;
+                if (c != in_hand) {
+                    least.clear();
+                    in_hand = c;
+                    for (int64_t k = o.member_off[c]; k < o.member_off[c + 1]; k++) {
+                        const int64_t s = o.member[k];
+                        for (int64_t j = out_off[s]; j < out_off[s + 1]; j++) {
+                            const int64_t e = out_edge[j];
+                            if (!ealive[e] || num[(size_t)edst[e]] < 0) continue;
+                            row.clear();
+                            for (int v = 0; v < n_vars; v++)
+                                if (mask[(size_t)v]) row.push_back(eval[e * n_vars + v]);
+                            auto it = least.emplace(row, e);
+                            if (!it.second && std::lexicographical_compare(eval.begin() + e * n_vars, eval.begin() + (e + 1) * n_vars,
+                                                                           eval.begin() + it.first->second * n_vars, eval.begin() + (it.first->second + 1) * n_vars))
+                                it.first->second = e;
+                        }
+                    }
+                }
+                row.assign(o.edge_values + i * n_obs, o.edge_values + (i + 1) * n_obs);
+                const auto it = least.find(row);
+                if (it == least.end()) return STCSP_E_INVALID;  // no live edge of the set projects on this row
+                q.esrc.push_back(c);
+                q.edst.push_back(d);
+                q.eval.insert(q.eval.end(), eval.begin() + it->second * n_vars, eval.begin() + (it->second + 1) * n_vars);
+            }
+        }
+        q.ealive.assign(q.esrc.size(), 1);
+        q.build_csr();
+        return STCSP_OK;
+    }
 };
 
 struct Merged {
@@ -915,6 +994,10 @@ struct stcsp_automaton {
 };
 struct stcsp_merged {
     stcsp::Merged m;
+};
+struct stcsp_observer {
+    stcsp::HostObserver o;
+    stcsp_observer_result res;
 };
 
 extern "C" {
@@ -1181,6 +1264,64 @@ int stcsp_automaton_quotient(const stcsp_automaton *a, const int32_t *state_clas
     try {
         h = new stcsp_automaton();
         const int rc = a->a.quotient(state_class, n_classes, h->a);
+        if (rc != STCSP_OK) {
+            delete h;
+            return rc;
+        }
+        h->root_final = h->a.final_[0];
+    } catch (const std::bad_alloc &) {
+        delete h;
+        return STCSP_E_NOMEM;
+    }
+    *out = h;
+    return STCSP_OK;
+}
+
+int stcsp_automaton_observer(const stcsp_automaton *a, const uint8_t *observable, int64_t max_states, stcsp_observer **out) {
+    if (!a || !out || max_states < 0) return STCSP_E_INVALID;
+    stcsp_observer *h = nullptr;
+    try {
+        h = new stcsp_observer();
+        const auto t0 = std::chrono::steady_clock::now();
+        if (!h->o.build(generator_view(a->a), a->a.observable_mask(observable).data(), max_states ? max_states : (int64_t)1 << 26)) {
+            delete h;
+            return STCSP_E_NOMEM;
+        }
+        stcsp::HostObserver &o = h->o;
+        o.member.reserve(1);  // (empty vectors still give valid pointers)
+        o.state_final.reserve(1);
+        o.edge_src.reserve(1);
+        o.edge_dst.reserve(1);
+        o.edge_values.reserve(1);
+        memset(&h->res, 0, sizeof h->res);
+        h->res.n_states = o.n_states();
+        h->res.n_edges = o.n_edges();
+        h->res.member_off = o.member_off.data();
+        h->res.member = o.member.data();
+        h->res.state_final = o.state_final.data();
+        h->res.edge_src = o.edge_src.data();
+        h->res.edge_dst = o.edge_dst.data();
+        h->res.edge_values = o.edge_values.data();
+        h->res.n_labels = o.n_labels;
+        h->res.max_set = o.max_set;
+        h->res.n_observable = o.n_obs;
+        h->res.levels = o.levels;
+        h->res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    } catch (const std::bad_alloc &) {
+        delete h;
+        return STCSP_E_NOMEM;
+    }
+    *out = h;
+    return STCSP_OK;
+}
+const stcsp_observer_result *stcsp_observer_get(const stcsp_observer *o) { return o ? &o->res : nullptr; }
+void stcsp_observer_free(stcsp_observer *o) { delete o; }
+int stcsp_automaton_from_observer(const stcsp_automaton *a, const uint8_t *observable, const stcsp_observer_result *observer, stcsp_automaton **out) {
+    if (!a || !observer || !out) return STCSP_E_INVALID;
+    stcsp_automaton *h = nullptr;
+    try {
+        h = new stcsp_automaton();
+        const int rc = a->a.from_observer(observable, *observer, h->a);
         if (rc != STCSP_OK) {
             delete h;
             return rc;

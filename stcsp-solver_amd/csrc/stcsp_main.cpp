@@ -2,10 +2,18 @@
 // (src/stcsp.y:180-219 main, src/solver.cpp:195-359 solve): same flags, same stdout contract,
 // same solutions.dot. The search itself runs on the MI355X engine behind the C-ABI.
 //
-//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--check=<file>]
+//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--observer[=all|NAME[,NAME...]]] [--check=<file>]
 //         [--sample=<N>:<L>[:<seed>] [--sample-final] [--sample-mask=all]] [--count=<L>]
 //         [--repair=<file> [--repair-final]] [--infer=<file> [--infer-final] [--infer-draws=<D>[:<seed>]]] input.csp
 //
+// --observer (not in the reference) writes the observer of the automaton instead of the automaton itself, to solutions.dot and
+// --binary=: the deterministic automaton whose states are the sets of states the system can be in after an observed prefix
+// (include/stcsp_engine.h, stcsp_engine_observer). Observable are the variables whose name does not start with "_V";
+// --observer=all makes every variable observable, --observer=NAME[,NAME...] the named ones only. The stdout line is unchanged;
+// "observer: <live states> -> <states> states, <edges> edges" goes to stderr. The construction runs on the device for an unsharded
+// solve and by the host twin otherwise (--shards=N, host adversarial passes). With --quotient the observer is then folded by the
+// host bisimulation under the same mask (--quotient=all is not taken with it): the minimal deterministic automaton of the observable language, which
+// --quotient alone cannot promise.
 // --binary=<file> (not in the reference) additionally writes the printed automaton in the compact
 // binary form of include/stcsp_host.h.
 // --shards=<N> (not in the reference, which is single-threaded) shards the open search frontier and the state table over N
@@ -64,6 +72,7 @@
 #include <sys/times.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cctype>
 #include <climits>
 #include <cmath>
@@ -89,6 +98,8 @@ static double cpu_time() {  // cpuTime (util.cpp:149-155)
 struct Flags {
     bool print_solution = false, testing = false, adv1 = false, adv2 = false, intervals = false;
     bool quotient = false, quotient_all = false;
+    bool observer = false;
+    const char *observer_mask = "";  // "" (the default mask), "all" or NAME[,NAME...]
     int prefix_k = 2, time_limit = 0, shards = 1;
     const char *file = nullptr;
     const char *binary = nullptr;
@@ -425,6 +436,62 @@ static int fold(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, con
     return 0;
 }
 
+// --observer: replace *a by its observer, built on the device (eng: a finished postprocess()) or by the host twin (eng NULL);
+// with --quotient, folded by the host bisimulation under the same mask
+static int observe(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, stcsp_engine *eng) {
+    std::vector<uint8_t> named((size_t)p->n_vars, strcmp(f.observer_mask, "all") == 0 ? 1 : 0);
+    const uint8_t *mask = f.observer_mask[0] ? named.data() : nullptr;
+    if (f.observer_mask[0] && strcmp(f.observer_mask, "all") != 0) {
+        std::string list = f.observer_mask;
+        for (size_t at = 0; at <= list.size();) {
+            const size_t comma = std::min(list.find(',', at), list.size());
+            const std::string name = list.substr(at, comma - at);
+            int v = 0;
+            while (v < p->n_vars && name != p->var_names[v]) v++;
+            if (v == p->n_vars) {
+                fprintf(stderr, "--observer: no variable named '%s'\n", name.c_str());
+                return 1;
+            }
+            named[(size_t)v] = 1;
+            at = comma + 1;
+        }
+    }
+    const long long n_live = (long long)stcsp_automaton_num_live_states(*a);
+    stcsp_observer *twin = nullptr;
+    stcsp_observer_result dev;
+    const stcsp_observer_result *res = &dev;
+    if (eng) {
+        stcsp_generator_options go = {mask, 0, 0, {0, 0}};
+        stcsp_generator_info gi;
+        stcsp_observer_options oo = {0, {0, 0}};
+        if (stcsp_engine_generator_build(eng, &go, &gi) != STCSP_OK || stcsp_engine_observer(eng, &oo, &dev) != STCSP_OK) {
+            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
+            return 1;
+        }
+    } else {
+        if (stcsp_automaton_observer(*a, mask, 0, &twin) != STCSP_OK) return 1;
+        res = stcsp_observer_get(twin);
+    }
+    stcsp_automaton *q = nullptr;
+    const int rc = stcsp_automaton_from_observer(*a, mask, res, &q);
+    fprintf(stderr, "observer: %lld -> %lld states, %lld edges\n", n_live, (long long)res->n_states, (long long)res->n_edges);
+    stcsp_observer_free(twin);
+    if (rc != STCSP_OK) return 1;
+    stcsp_automaton_free(*a);
+    *a = q;
+    if (f.quotient) {
+        std::vector<int32_t> cls((size_t)stcsp_automaton_num_states(*a) + 1, -1);
+        int64_t n_classes = 0, n_states = 0;
+        if (stcsp_automaton_bisimulation(*a, mask, cls.data(), &n_classes) < 0) return 1;
+        for (int32_t c : cls) n_states += c >= 0;
+        if (stcsp_automaton_quotient(*a, cls.data(), n_classes, &q) != STCSP_OK) return 1;
+        stcsp_automaton_free(*a);
+        *a = q;
+        fprintf(stderr, "quotient: %lld -> %lld\n", (long long)n_states, (long long)n_classes);
+    }
+    return 0;
+}
+
 static int run_once(const Flags &f, bool print_line, double *total) {
     double t_init = cpu_time();
     stcsp_model *model = nullptr;
@@ -494,7 +561,11 @@ static int run_once(const Flags &f, bool print_line, double *total) {
             fprintf(stderr, "the streams could not be inferred: draws from a count that overflows a double\n");
             return 1;
         }
-        if (f.quotient && fold(f, p, &a, nullptr, 0, 0)) {
+        if (f.observer && observe(f, p, &a, nullptr)) {
+            fprintf(stderr, "the observer could not be built\n");
+            return 1;
+        }
+        if (f.quotient && !f.observer && fold(f, p, &a, nullptr, 0, 0)) {
             fprintf(stderr, "the quotient could not be built\n");
             return 1;
         }
@@ -528,7 +599,11 @@ static int run_once(const Flags &f, bool print_line, double *total) {
             fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
             return 1;
         }
-        if (f.quotient) {
+        if (f.observer && observe(f, p, &a, eng)) {
+            fprintf(stderr, "the observer could not be built\n");
+            return 1;
+        }
+        if (f.quotient && !f.observer) {
             std::vector<uint8_t> all((size_t)p->n_vars, 1);
             stcsp_quotient_options qo = {f.quotient_all ? all.data() : nullptr, {0, 0}};
             stcsp_quotient_result qr;
@@ -653,7 +728,11 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
         fprintf(stderr, "the streams could not be inferred: draws from a count that overflows a double\n");
         return 1;
     }
-    if (f.quotient && fold(f, p, &a, nullptr, 0, 0)) {  // (host twin: the merged automaton lives on the host)
+    if (f.observer && observe(f, p, &a, nullptr)) {  // (host twin likewise)
+        fprintf(stderr, "the observer could not be built\n");
+        return 1;
+    }
+    if (f.quotient && !f.observer && fold(f, p, &a, nullptr, 0, 0)) {  // (host twin: the merged automaton lives on the host)
         fprintf(stderr, "the quotient could not be built\n");
         return 1;
     }
@@ -689,6 +768,11 @@ int main(int argc, char **argv) {
         }
         if (strncmp(a, "--binary=", 9) == 0) {
             f.binary = a + 9;
+            continue;
+        }
+        if (strcmp(a, "--observer") == 0 || strncmp(a, "--observer=", 11) == 0) {
+            f.observer = true;
+            f.observer_mask = a[10] == '=' ? a + 11 : "";
             continue;
         }
         if (strcmp(a, "--quotient") == 0 || strcmp(a, "--quotient=all") == 0) {
