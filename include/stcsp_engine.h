@@ -649,6 +649,69 @@ typedef struct stcsp_observer_result {
 
 int stcsp_engine_observer(stcsp_engine *engine, const stcsp_observer_options *options, stcsp_observer_result *result);
 
+/* ---- comparing two observable languages: inclusion and shortest witnesses on the device (no reference counterpart) ----
+ * Do two models show the same streams, and if not, which is the shortest stream one admits and the other does not? The
+ * call builds the synchronous product of two deterministic automata and reads four inclusions off it.
+ *
+ * Operands. The left operand L is the observer that the last successful stcsp_engine_observer() built on this engine,
+ * under that call's mask. The engine keeps what it needs of it; stcsp_engine_compare() does not disturb it, so several
+ * right operands can be compared against one observer. A new solve, new flags, a new stcsp_engine_generator_build() and
+ * a failed stcsp_engine_observer() end its validity. The right operand R is a deterministic labelled automaton in the
+ * layout of stcsp_observer_result, of which only n_states, n_edges, state_final, edge_src, edge_dst, edge_values and
+ * n_observable are read: state 0 is the root, n_states == 0 is an automaton without states, and its rows are in the
+ * column order of this engine's observable variables (the caller's job). STCSP_E_INVALID when n_observable differs from
+ * the left's, an index is out of range, the edges are not sorted by (source, row), or two edges share (source, row).
+ *
+ * Languages. For a deterministic automaton X, P(X) is the set of row sequences that have a run from the root (it holds
+ * the empty sequence iff X has a state), and F(X) the subset whose run ends in a final state.
+ *
+ * Product. Each operand is completed with a sink _|_ that is not final and that every missing (state, row) leads to. The
+ * product's states are the pairs (l, r) != (_|_, _|_) reachable from (root of L or _|_, root of R or _|_); a pair has one
+ * edge per row that at least one of its components has. Pairs are numbered breadth-first from the root pair, the
+ * out-edges of a pair taken in lexicographic order of their rows (the observer's convention). So the least-numbered pair
+ * that satisfies a predicate is reached by the shortest row sequence that reaches such a pair, and by the
+ * lexicographically least among those. Nothing in the result depends on scheduling.
+ *
+ * Verdicts. Verdict k is the least-numbered pair that satisfies predicate k, or none:
+ *   0  refutes P(L) in P(R):  l != _|_ and r == _|_
+ *   1  refutes P(R) in P(L):  r != _|_ and l == _|_
+ *   2  refutes F(L) in F(R):  l != _|_, final(l), and (r == _|_ or not final(r))
+ *   3  refutes F(R) in F(L):  r != _|_, final(r), and (l == _|_ or not final(l))
+ * witness_len[k] == -1 means the inclusion holds. Otherwise the witness is the pair's access sequence: witness_len[k]
+ * rows of n_observable values at witness_values + witness_off[k] * n_observable (witness_off counts rows), and
+ * witness_left[k] / witness_right[k] are the pair's components, -1 for _|_. The whole product is always explored.
+ *
+ * Limits. request.max_pairs bounds the pairs; 0 selects the default 2^26. The table, the records of the pairs and the
+ * scratch of a level are bounded by a byte budget, by default half of the free device memory; the environment variable
+ * STCSP_COMPARE_BYTES sets it. Exceeding either limit gives STCSP_E_NOMEM with a message that names the limit, the level
+ * and the pairs so far; there is never a partial result, and the engine, the observer and the generator's, monitor's,
+ * repair's and inference's structures stay valid. STCSP_COMPARE_SLOTS sets the initial slot count of the table (tests:
+ * the table grows by rehashing between launches). STCSP_E_STATE without a valid observer; STCSP_E_UNSUPPORTED on sharded
+ * and stepped engines (run stcsp_compare_observers() of stcsp_host.h on two observers). Results are owned by the engine
+ * until the next call on it. */
+typedef struct stcsp_compare_request {
+    const stcsp_observer_result *right;
+    int64_t max_pairs; /* 0 = the default (2^26) */
+    int32_t reserved[2];
+} stcsp_compare_request;
+
+typedef struct stcsp_compare_result {
+    int64_t n_pairs, n_pair_edges;
+    int64_t witness_off[5];        /* in rows: witness k is rows [witness_off[k], witness_off[k + 1])                    */
+    const int32_t *witness_values; /* [witness_off[4] * n_observable]                                                   */
+    int32_t witness_len[4];        /* -1: the inclusion holds                                                           */
+    int32_t witness_left[4];       /* the witness pair's state of L, -1 for the sink                                    */
+    int32_t witness_right[4];      /* ... and of R                                                                      */
+    int64_t table_bytes;           /* HBM the comparison held at its end: operands, table, records, scratch of a level  */
+    int32_t n_observable;
+    int32_t levels;                /* breadth-first levels, the root pair's included                                    */
+    double seconds;                /* wall time from the request to the result on the host                              */
+    double seconds_expand;         /* HIP-event time of the expansion launches, all levels                              */
+    double seconds_number;         /* HIP-event time of the collect and number launches, all levels                     */
+} stcsp_compare_result;
+
+int stcsp_engine_compare(stcsp_engine *engine, const stcsp_compare_request *request, stcsp_compare_result *result);
+
 void stcsp_engine_destroy(stcsp_engine *engine);
 
 /* Message of the last error on this engine (or of the last failed create when engine==NULL). */

@@ -88,6 +88,10 @@ char *stcsp_automaton_canonical(const stcsp_automaton *a, size_t *len);
 int64_t stcsp_automaton_num_states(const stcsp_automaton *a);      /* table size (incl. failed) */
 int64_t stcsp_automaton_num_live_states(const stcsp_automaton *a); /* reachable + printed        */
 int64_t stcsp_automaton_num_live_edges(const stcsp_automaton *a);
+/* The variables of the automaton (a binary file carries their names): how many, and the name of one, owned by the
+ * automaton; NULL for an index out of range. */
+int stcsp_automaton_num_vars(const stcsp_automaton *a);
+const char *stcsp_automaton_var_name(const stcsp_automaton *a, int index);
 
 /* ---- bisimulation quotient (definition: stcsp_engine.h, stcsp_engine_quotient) ----
  * The exact CPU twin of the device pass, written as plain partition refinement with ordered containers: the
@@ -180,6 +184,18 @@ void stcsp_observer_free(stcsp_observer *o);
  * `observable`; free it with stcsp_automaton_free(). */
 int stcsp_automaton_from_observer(const stcsp_automaton *a, const uint8_t *observable, const stcsp_observer_result *observer,
                                   stcsp_automaton **out);
+
+/* ---- comparing two observable languages (definition: stcsp_engine.h, stcsp_engine_compare) ----
+ * The same contract written plainly with ordered containers over two observers (results of stcsp_engine_observer() or
+ * stcsp_automaton_observer(), or any deterministic automata in that layout; `right` has its rows in the column order of
+ * `left`): the checker of the device pass in the tests, and the road for sharded runs, host adversarial passes and
+ * automata read from binary files. max_pairs: 0 = the default of the device pass, STCSP_E_NOMEM beyond it;
+ * STCSP_E_INVALID for a malformed operand, either one. The result (stcsp_comparison_get(): the time fields other than
+ * `seconds` and table_bytes are 0) lives until stcsp_comparison_free(). */
+typedef struct stcsp_comparison stcsp_comparison;
+int stcsp_compare_observers(const stcsp_observer_result *left, const stcsp_observer_result *right, int64_t max_pairs, stcsp_comparison **out);
+const stcsp_compare_result *stcsp_comparison_get(const stcsp_comparison *c);
+void stcsp_comparison_free(stcsp_comparison *c);
 
 /* Merge the per-shard results of a sharded run (global state ids, see stcsp_engine.h) into
  * one result with dense ids; runs the ok-fixpoint over the union. The merged result is owned

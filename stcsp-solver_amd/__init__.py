@@ -277,6 +277,53 @@ def _observer_pack(obs):
     return res, keep
 
 
+class CompareRequest(C.Structure):
+    _fields_ = [("right", C.POINTER(ObserverResult)), ("max_pairs", C.c_int64), ("reserved", C.c_int32 * 2)]
+
+
+class CompareResult(C.Structure):
+    _fields_ = [("n_pairs", C.c_int64), ("n_pair_edges", C.c_int64), ("witness_off", C.c_int64 * 5), ("witness_values", C.POINTER(C.c_int32)),
+                ("witness_len", C.c_int32 * 4), ("witness_left", C.c_int32 * 4), ("witness_right", C.c_int32 * 4), ("table_bytes", C.c_int64),
+                ("n_observable", C.c_int32), ("levels", C.c_int32), ("seconds", C.c_double), ("seconds_expand", C.c_double),
+                ("seconds_number", C.c_double)]
+
+
+COMPARE_SCALARS = ("n_pairs", "n_pair_edges", "table_bytes", "n_observable", "levels", "seconds", "seconds_expand", "seconds_number")
+
+
+def _compare_unpack(res):
+    """A CompareResult -> dict: its scalars, witness_off int64 [5] (in rows), witness_len / witness_left / witness_right int32 [4]
+    and witness_values int32 [witness_off[4], n_observable], all copies."""
+    import numpy as np
+    d = {k: getattr(res, k) for k in COMPARE_SCALARS}
+    d["witness_off"] = np.array(res.witness_off[:], np.int64)
+    for k in ("witness_len", "witness_left", "witness_right"):
+        d[k] = np.array(getattr(res, k)[:], np.int32)
+    rows, no = int(d["witness_off"][4]), res.n_observable
+    d["witness_values"] = (np.ctypeslib.as_array(res.witness_values, shape=(rows * no,)).copy() if rows * no else np.zeros(0, np.int32)).reshape(rows, no)
+    return d
+
+
+def compare_observers(left, right, max_pairs=0):
+    """The comparison of two observers (the dicts of Engine.observer() / Automaton.observer(), or any deterministic automata in that
+    form; `right` with its columns in the order of `left`) by the host twin of Engine.compare(): the product of the two, the four
+    inclusions P(L) in P(R), P(R) in P(L), F(L) in F(R), F(R) in F(L) and their shortest witnesses. Returns the dict of
+    _compare_unpack(); StcspError -1 for a malformed operand, -4 beyond max_pairs (0: the default). Contract: include/stcsp_engine.h,
+    stcsp_engine_compare."""
+    lib = host_lib()
+    lres, lkeep = _observer_pack(left)
+    rres, rkeep = _observer_pack(right)
+    h = C.c_void_p()
+    rc = lib.stcsp_compare_observers(C.byref(lres), C.byref(rres), max_pairs, C.byref(h))
+    del lkeep, rkeep
+    if rc != 0:
+        raise StcspError(rc, "compare_observers failed: more pairs than max_pairs" if rc == -4 else "compare_observers failed: a malformed operand")
+    try:
+        return _compare_unpack(lib.stcsp_comparison_get(h).contents)
+    finally:
+        lib.stcsp_comparison_free(h)
+
+
 F_KEEP_RAW_EDGES = 1
 F_NO_EXPORT = 2
 F_PROFILE = 4
@@ -292,7 +339,7 @@ ENGINE_SYMBOLS = [
     "stcsp_engine_propagate", "stcsp_engine_set_expand_budget", "stcsp_engine_node_bytes", "stcsp_engine_donate",
     "stcsp_engine_adopt", "stcsp_engine_expand_variant", "stcsp_engine_quotient",
     "stcsp_engine_monitor_build", "stcsp_engine_monitor_check", "stcsp_engine_generator_build", "stcsp_engine_generate",
-    "stcsp_engine_repair", "stcsp_engine_infer", "stcsp_engine_observer",
+    "stcsp_engine_repair", "stcsp_engine_infer", "stcsp_engine_observer", "stcsp_engine_compare",
 ]
 # include/stcsp_sharded.h: the superstep loop + in-process transport (libstcsp_hip.so), the RCCL transport (libstcsp_rccl.so)
 SHARDED_SYMBOLS_HIP = ["stcsp_engine_solve_sharded", "stcsp_local_group_create", "stcsp_local_group_transport", "stcsp_local_group_destroy"]
@@ -310,6 +357,7 @@ HOST_SYMBOLS = [
     "stcsp_automaton_check_streams", "stcsp_automaton_num_observable", "stcsp_automaton_generate", "stcsp_automaton_count_streams",
     "stcsp_automaton_repair_streams", "stcsp_automaton_infer_streams",
     "stcsp_automaton_observer", "stcsp_observer_get", "stcsp_observer_free", "stcsp_automaton_from_observer",
+    "stcsp_compare_observers", "stcsp_comparison_get", "stcsp_comparison_free", "stcsp_automaton_num_vars", "stcsp_automaton_var_name",
 ]
 
 
@@ -396,6 +444,13 @@ def host_lib() -> C.CDLL:
         lib.stcsp_observer_get.restype = C.POINTER(ObserverResult)
         lib.stcsp_observer_free.argtypes = [C.c_void_p]
         lib.stcsp_automaton_from_observer.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ObserverResult), C.POINTER(C.c_void_p)]
+        lib.stcsp_compare_observers.argtypes = [C.POINTER(ObserverResult), C.POINTER(ObserverResult), C.c_int64, C.POINTER(C.c_void_p)]
+        lib.stcsp_comparison_get.argtypes = [C.c_void_p]
+        lib.stcsp_comparison_get.restype = C.POINTER(CompareResult)
+        lib.stcsp_comparison_free.argtypes = [C.c_void_p]
+        lib.stcsp_automaton_num_vars.argtypes = [C.c_void_p]
+        lib.stcsp_automaton_var_name.argtypes = [C.c_void_p, C.c_int]
+        lib.stcsp_automaton_var_name.restype = C.c_char_p
         lib.stcsp_merge_shards.argtypes = [C.POINTER(C.POINTER(Result)), C.c_int, C.POINTER(C.c_void_p)]
         lib.stcsp_merged_result.argtypes = [C.c_void_p]
         lib.stcsp_merged_result.restype = C.POINTER(Result)
@@ -453,6 +508,8 @@ def bind_engine_api(lib: C.CDLL, prefix: str = "stcsp_engine") -> None:
         g("infer").argtypes = [C.c_void_p, C.POINTER(InferRequest), C.POINTER(InferResult)]
     if hasattr(lib, f"{prefix}_observer"):
         g("observer").argtypes = [C.c_void_p, C.POINTER(ObserverOptions), C.POINTER(ObserverResult)]
+    if hasattr(lib, f"{prefix}_compare"):
+        g("compare").argtypes = [C.c_void_p, C.POINTER(CompareRequest), C.POINTER(CompareResult)]
     if hasattr(lib, f"{prefix}_propagate"):
         g("propagate").argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64)]
@@ -1127,6 +1184,21 @@ class EngineBase:
         out = ObserverResult()
         self._check(self._f("observer")(self._h, C.byref(oo), C.byref(out)))
         return _observer_unpack(out)
+
+    def compare(self, right, max_pairs=0):
+        """The comparison of the observer that the last observer() built on this engine (left) with `right`, an observer dict (of
+        another engine's observer(), of Automaton.observer(), or any deterministic automaton in that form, its columns in the order
+        of this engine's observable variables), on the device: the product of the two, the four inclusions P(L) in P(R), P(R) in
+        P(L), F(L) in F(R), F(R) in F(L) and their shortest witnesses. Returns the dict of _compare_unpack(). StcspError -6 without
+        a valid observer, -1 for a malformed operand, -4 beyond max_pairs (0: the default) or the byte budget. Contract:
+        include/stcsp_engine.h, stcsp_engine_compare."""
+        res, keep = _observer_pack(right)
+        rq = CompareRequest(C.pointer(res), max_pairs)
+        out = CompareResult()
+        rc = self._f("compare")(self._h, C.byref(rq), C.byref(out))
+        del keep
+        self._check(rc)
+        return _compare_unpack(out)
 
     def automaton(self, result: Result | None = None) -> Automaton:
         return Automaton(self._model, result if result is not None else self.result)

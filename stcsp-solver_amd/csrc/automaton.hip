@@ -1,5 +1,5 @@
 // automaton.hip -- the host side of the services on the exported automaton: post-processing, bisimulation quotient, stream monitor,
-// generator, repair, inference and observer, with the kernels they launch. No kernel is shared with the search (engine.hip).
+// generator, repair, inference, observer and comparison, with the kernels they launch. No kernel is shared with the search (engine.hip).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -18,6 +18,7 @@
 #include "dev_repair.hpp"
 #include "dev_infer.hpp"
 #include "dev_observer.hpp"
+#include "dev_compare.hpp"
 #include "repair_host.hpp"
 #include "infer_host.hpp"
 
@@ -48,7 +49,7 @@ int AutomatonServices::fail(int code, const char *fmt, ...) {
 }
 
 void AutomatonServices::invalidate() {
-    post_done = live_done = mon_built = gen_built = rep_built = inf_built = obs_built = false;
+    post_done = live_done = mon_built = gen_built = rep_built = inf_built = obs_built = cmp_valid = false;
     mon_host.reset();
 }
 
@@ -497,6 +498,7 @@ int AutomatonServices::generator_build(const AutomatonView &view, const stcsp_ge
     rep_built = false;
     inf_built = false;
     obs_built = false;
+    cmp_valid = false;
     const int N = v.N, H = go->horizon;
     const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
     if ((size_t)v.exp_edges > 0x7fffffffull) return fail(STCSP_E_NOMEM, "edge list too large for the device generator");
@@ -949,13 +951,13 @@ int AutomatonServices::infer(const AutomatonView &view, const stcsp_infer_reques
 
 // A buffer that has to grow in the middle of a construction: the first `keep` elements move to the larger one.
 template <typename T>
-int AutomatonServices::grow_keeping(DevBuf<T> &buf, size_t keep, size_t count) {
+int AutomatonServices::grow_keeping(DevBuf<T> &buf, size_t keep, size_t count, const char *who) {
     if (buf.n >= count) return STCSP_OK;
     DevBuf<T> bigger;
     const size_t room = std::max(grown(count), 2 * buf.n);
     if (bigger.alloc(room) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(STCSP_E_NOMEM, "observer: no room for %zu bytes on the device", room * sizeof(T));
+        return fail(STCSP_E_NOMEM, "%s: no room for %zu bytes on the device", who, room * sizeof(T));
     }
     if (keep) HIPCHK(hipMemcpyAsync(bigger.p, buf.p, keep * sizeof(T), hipMemcpyDeviceToDevice, v.stream));
     HIPCHK(hipStreamSynchronize(v.stream));
@@ -1014,6 +1016,7 @@ int AutomatonServices::observer_order(double &seconds) {
 // Observer: the subset construction of the live automaton under the generator's mask (contract: stcsp_engine.h).
 int AutomatonServices::observer(const AutomatonView &view, const stcsp_observer_options *oo, stcsp_observer_result *out) {
     if (int rc = enter(view, "observer", NEED_GENERATOR, "stcsp_automaton_observer")) return rc;
+    cmp_valid = false;  // (the left operand of compare() is the observer of the last call that succeeded)
     if (oo && oo->max_states < 0) return fail(STCSP_E_INVALID, "observer: max_states must not be negative");
     auto t0 = std::chrono::steady_clock::now();
     const unsigned long long max_states = std::min<unsigned long long>(oo && oo->max_states ? (unsigned long long)oo->max_states : 1ull << 26, 0x7ffffffeull);
@@ -1041,6 +1044,10 @@ int AutomatonServices::observer(const AutomatonView &view, const stcsp_observer_
         out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     };
     if (!root_live) {
+        cmp_left.clear();
+        cmp_left.n_obs = gen_n_obs;
+        cmp_valid = true;
+        cmp_left_on_device = false;
         publish();
         return STCSP_OK;
     }
@@ -1264,6 +1271,12 @@ int AutomatonServices::observer(const AutomatonView &view, const stcsp_observer_
         o_edst[i] = (int32_t)edst[e];
         std::copy(obs_rows.begin() + elab[e] * n_obs, obs_rows.begin() + (elab[e] + 1) * n_obs, o_evalues.begin() + i * n_obs);
     }
+    cmp_left.set_graph(gen_n_obs, n_states, o_final.data(), e_total, [&](size_t i) { return o_esrc[i]; }, [&](size_t i) { return elab[idx[i]]; },
+                       [&](size_t i) { return o_edst[i]; });
+    cmp_left.rows = obs_rows;
+    cmp_left.n_rows = nL;
+    cmp_valid = true;
+    cmp_left_on_device = false;
     out->n_states = n_states;
     out->n_edges = e_total;
     out->n_labels = nL;
@@ -1272,6 +1285,224 @@ int AutomatonServices::observer(const AutomatonView &view, const stcsp_observer_
     out->table_bytes = (int64_t)(pool_top * sizeof(uint32_t) + (size_t)n_states * sizeof(ObsRec) + cap_s * (sizeof(unsigned long long) + sizeof(uint32_t)) +
                                  (size_t)e_total * 3 * sizeof(uint32_t) + scratch_peak + (size_t)rep_total * sizeof(unsigned long long));
     publish();
+    return STCSP_OK;
+}
+
+// Comparison: the synchronous product of the last observer (left) and the request's automaton (right), its four inclusions and their
+// witnesses (contract: stcsp_engine.h; dev_compare.hpp).
+int AutomatonServices::compare(const AutomatonView &view, const stcsp_compare_request *rq, stcsp_compare_result *out) {
+    if (int rc = enter(view, "compare", NEED_GENERATOR, "stcsp_compare_observers")) return rc;
+    if (!cmp_valid) return fail(STCSP_E_STATE, "compare needs a successful observer() after the last generator_build()");
+    if (!rq->right || rq->max_pairs < 0) return fail(STCSP_E_INVALID, "compare: no right operand, or a negative max_pairs");
+    if (const char *fault = compare_operand_fault(*rq->right)) return fail(STCSP_E_INVALID, "compare: the right operand %s", fault);
+    if (rq->right->n_observable != cmp_left.n_obs)
+        return fail(STCSP_E_INVALID, "compare: the right operand has %d observable variables, the observer has %d", rq->right->n_observable, cmp_left.n_obs);
+    auto t0 = std::chrono::steady_clock::now();
+    const unsigned long long max_pairs = std::min<unsigned long long>(rq->max_pairs ? (unsigned long long)rq->max_pairs : 1ull << 26, 0x7ffffffeull);
+    const size_t n_obs = (size_t)cmp_left.n_obs;
+    c_witness.clear();
+    c_witness.reserve(1);  // (an empty vector still gives a valid pointer)
+    memset(out, 0, sizeof *out);
+    out->n_observable = cmp_left.n_obs;
+    out->witness_values = c_witness.data();
+    for (int k = 0; k < 4; k++) out->witness_len[k] = out->witness_left[k] = out->witness_right[k] = -1;
+    const CompareOperand &left = cmp_left;
+    CompareOperand right;
+    right.load(*rq->right);
+    if (!left.n_states && !right.n_states) {  // two automata without states: no pair
+        out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return STCSP_OK;
+    }
+    // common label ranks: the rows of both operands in one order
+    std::vector<int32_t> rows;
+    std::vector<uint32_t> map_l, map_r, lab_l(left.lab.size()), lab_r(right.lab.size());
+    const uint32_t n_rows = merge_rows(n_obs, left.rows, left.n_rows, right.rows, right.n_rows, rows, map_l, map_r);
+    for (size_t e = 0; e < lab_l.size(); e++) lab_l[e] = map_l[left.lab[e]];
+    for (size_t e = 0; e < lab_r.size(); e++) lab_r[e] = map_r[right.lab[e]];
+    size_t budget = 0;
+    if (int rc = table_budget("STCSP_COMPARE_BYTES", budget)) return rc;
+    const size_t operand_bytes = (left.off.size() + right.off.size() + 2 * (lab_l.size() + lab_r.size())) * sizeof(uint32_t) + left.fin.size() + right.fin.size();
+    if (operand_bytes > budget)
+        return fail(STCSP_E_NOMEM, "compare: the operands need %zu bytes, the budget (STCSP_COMPARE_BYTES) is %zu; the product got to level 0 with 0 pairs", operand_bytes, budget);
+    auto upload = [&](auto &buf, const auto &vec) -> int {
+        HIPCHK(buf.reserve(vec.size()));
+        if (!vec.empty()) HIPCHK(hipMemcpyAsync(buf.p, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice, v.stream));
+        return STCSP_OK;
+    };
+    if (!cmp_left_on_device) {
+        if (int rc = upload(d_cloff, left.off)) return rc;
+        if (int rc = upload(d_cldst, left.dst)) return rc;
+        if (int rc = upload(d_clfin, left.fin)) return rc;
+    }
+    if (int rc = upload(d_cllab, lab_l)) return rc;
+    if (int rc = upload(d_croff, right.off)) return rc;
+    if (int rc = upload(d_crlab, lab_r)) return rc;
+    if (int rc = upload(d_crdst, right.dst)) return rc;
+    if (int rc = upload(d_crfin, right.fin)) return rc;
+    HIPCHK(hipStreamSynchronize(v.stream));  // (the vectors of this call are locals)
+    cmp_left_on_device = true;
+    const CmpSide L{d_cloff.p, d_cllab.p, d_cldst.p, d_clfin.p, left.n_states}, R{d_croff.p, d_crlab.p, d_crdst.p, d_crfin.p, right.n_states};
+    auto pow2 = [](unsigned long long n) {
+        unsigned long long c = 64;
+        while (c < n) c <<= 1;
+        return c;
+    };
+    unsigned long long slots = 1024;
+    if (const char *e = getenv("STCSP_COMPARE_SLOTS")) slots = pow2((unsigned long long)std::max(1ll, std::min(atoll(e), 1ll << 30)));
+    unsigned long long cap_new = 1, n_pairs = 0, edges = 0, peak = 0;
+    int levels = 0;
+    auto bytes_of = [&](unsigned long long s, unsigned long long fresh, unsigned long long pairs) {
+        return operand_bytes + s * 2 * sizeof(unsigned long long) + fresh * (sizeof(unsigned long long) + 2 * sizeof(uint32_t)) +
+               pairs * (sizeof(unsigned long long) + 2 * sizeof(uint32_t));
+    };
+    auto over_budget = [&](unsigned long long need) {
+        return fail(STCSP_E_NOMEM, "compare: level %d needs %llu bytes of table, records and scratch, the budget (STCSP_COMPARE_BYTES) is %zu; the product got to level %d with %llu pairs and %llu edges",
+                    levels, need, budget, levels, n_pairs, edges);
+    };
+    if (bytes_of(slots, cap_new, 1) > budget) return over_budget(bytes_of(slots, cap_new, 1));
+    if (!d_ctab.reserve_or_release(slots) || !d_cmin.reserve_or_release(slots)) return fail(STCSP_E_NOMEM, "compare: no room for a table of %llu slots", slots);
+    HIPCHK(d_cnew.reserve(1));
+    HIPCHK(d_cctl.reserve_exact(C_WORDS));
+    HIPCHK(ev.ready(6));
+    uint32_t ctl[C_WORDS] = {0};
+    for (int k = 0; k < 4; k++) ctl[C_VERDICT + k] = kCmpNone;
+    HIPCHK(hipMemcpyAsync(d_cctl.p, ctl, sizeof ctl, hipMemcpyHostToDevice, v.stream));
+    HIPCHK(hipMemsetAsync(d_ctab.p, 0xff, slots * sizeof(unsigned long long), v.stream));
+    HIPCHK(hipMemsetAsync(d_cmin.p, 0xff, slots * sizeof(unsigned long long), v.stream));
+    // the root pair: an operand without states starts in its sink (index 0 == n_states)
+    hipLaunchKernelGGL(k_c_init, dim3(1), dim3(64), 0, v.stream, 0ull, d_ctab.p, d_cmin.p, (uint32_t)(slots - 1), d_cnew.p, d_cctl.p);
+    auto read_ctl = [&]() -> int {
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ctl, d_cctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        if (ctl[C_ERROR]) return fail(STCSP_E_INTERNAL, "compare: a device table overflowed (flags %u)", ctl[C_ERROR]);
+        return STCSP_OK;
+    };
+    bool number_pending = false;
+    auto take_number_time = [&]() -> int {
+        float ms = 0;
+        if (number_pending) HIPCHK(hipEventElapsedTime(&ms, ev[4], ev[5]));
+        out->seconds_number += ms * 1e-3;
+        number_pending = false;
+        return STCSP_OK;
+    };
+    std::vector<unsigned long long> keys;
+    std::vector<uint32_t> idx;
+    std::vector<uint32_t> &rank = c_rank;  // (a member: its upload may still be queued when a level fails)
+    for (unsigned long long n_new = 1; n_new;) {
+        // the n_new pairs of this level: their numbers, their records, their verdicts
+        if (n_pairs + n_new > max_pairs)
+            return fail(STCSP_E_NOMEM, "compare: more than max_pairs = %llu pairs; the product got to level %d with %llu pairs and %llu edges", max_pairs, levels,
+                        n_pairs, edges);
+        if (bytes_of(slots, cap_new, n_pairs + n_new) > budget) return over_budget(bytes_of(slots, cap_new, n_pairs + n_new));
+        if (int rc = grow_keeping(d_cpkey, (size_t)n_pairs, (size_t)(n_pairs + n_new), "compare")) return rc;
+        if (int rc = grow_keeping(d_cparent, (size_t)n_pairs, (size_t)(n_pairs + n_new), "compare")) return rc;
+        if (int rc = grow_keeping(d_cplabel, (size_t)n_pairs, (size_t)(n_pairs + n_new), "compare")) return rc;
+        HIPCHK(d_ckeys.reserve((size_t)n_new));
+        HIPCHK(d_crank.reserve((size_t)n_new));
+        const unsigned nb = (unsigned)((n_new + 255) / 256);
+        HIPCHK(hipMemsetAsync(d_cctl.p + C_DEG, 0, 2 * sizeof(uint32_t), v.stream));
+        HIPCHK(hipEventRecord(ev[2], v.stream));
+        hipLaunchKernelGGL(k_c_collect, dim3(nb), dim3(256), 0, v.stream, (uint32_t)n_new, (const uint32_t *)d_cnew.p, (const unsigned long long *)d_ctab.p,
+                           (const unsigned long long *)d_cmin.p, L.off, R.off, d_ckeys.p, d_cctl.p);
+        HIPCHK(hipEventRecord(ev[3], v.stream));
+        keys.resize((size_t)n_new);
+        HIPCHK(hipMemcpyAsync(keys.data(), d_ckeys.p, (size_t)n_new * sizeof(unsigned long long), hipMemcpyDeviceToHost, v.stream));
+        if (int rc = read_ctl()) return rc;
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, ev[2], ev[3]));
+        out->seconds_number += ms * 1e-3;
+        idx.resize((size_t)n_new);
+        rank.resize((size_t)n_new);
+        for (uint32_t i = 0; i < n_new; i++) idx[i] = i;
+        std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
+        for (uint32_t i = 0; i < n_new; i++) rank[idx[i]] = i;
+        HIPCHK(hipMemcpyAsync(d_crank.p, rank.data(), (size_t)n_new * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+        HIPCHK(hipEventRecord(ev[4], v.stream));
+        hipLaunchKernelGGL(k_c_number, dim3(nb), dim3(256), 0, v.stream, (uint32_t)n_new, (uint32_t)n_pairs, (const uint32_t *)d_cnew.p, (const uint32_t *)d_crank.p,
+                           (const unsigned long long *)d_ctab.p, (const unsigned long long *)d_ckeys.p, L.fin, R.fin, L.n, R.n, d_cpkey.p, d_cparent.p, d_cplabel.p,
+                           d_cctl.p);
+        HIPCHK(hipEventRecord(ev[5], v.stream));
+        number_pending = true;
+        const uint32_t f0 = (uint32_t)n_pairs, f1 = (uint32_t)(n_pairs + n_new);
+        n_pairs += n_new;
+        levels++;
+        peak = std::max(peak, bytes_of(slots, cap_new, n_pairs));
+        // the next level: the out-degrees of the frontier's components bound its new pairs
+        const unsigned long long bound = (unsigned long long)ctl[C_DEG] | ((unsigned long long)ctl[C_DEG + 1] << 32);
+        if (!bound) break;
+        if (n_pairs + bound > 0x3fffffffull)
+            return fail(STCSP_E_NOMEM, "compare: a table for %llu pairs has more than 2^31 slots; the product got to level %d with %llu pairs and %llu edges",
+                        n_pairs + bound, levels, n_pairs, edges);
+        const unsigned long long want = std::max(slots, pow2(2 * (n_pairs + bound)));
+        if (bytes_of(want, bound, n_pairs) > budget) return over_budget(bytes_of(want, bound, n_pairs));
+        if (want > slots) {
+            if (!d_ctab2.reserve_or_release(want) || !d_cmin.reserve_or_release(want))
+                return fail(STCSP_E_NOMEM, "compare: no room for a table of %llu slots at level %d (%llu pairs so far)", want, levels, n_pairs);
+            HIPCHK(hipMemsetAsync(d_ctab2.p, 0xff, want * sizeof(unsigned long long), v.stream));
+            HIPCHK(hipMemsetAsync(d_cmin.p, 0xff, want * sizeof(unsigned long long), v.stream));
+            hipLaunchKernelGGL(k_c_rehash, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)slots, (const unsigned long long *)d_ctab.p, d_ctab2.p,
+                               (uint32_t)(want - 1), d_cctl.p);
+            std::swap(d_ctab.p, d_ctab2.p);
+            std::swap(d_ctab.n, d_ctab2.n);
+            slots = want;
+        }
+        cap_new = std::min<unsigned long long>(bound, 0xffffffffull);
+        if (!d_cnew.reserve_or_release((size_t)cap_new)) return fail(STCSP_E_NOMEM, "compare: no room for %llu new pairs at level %d (%llu pairs so far)", cap_new, levels, n_pairs);
+        peak = std::max(peak, bytes_of(slots, cap_new, n_pairs));
+        // lanes per pair by the mean out-degree of the frontier: 8 for the common few edges per pair, a wavefront for wide pairs
+        const bool wide = bound > 16ull * (f1 - f0);
+        const unsigned groups = wide ? 4 : 32;
+        const unsigned grid = (unsigned)std::min<unsigned long long>(((unsigned long long)(f1 - f0) + groups - 1) / groups, 8192);
+        HIPCHK(hipMemsetAsync(d_cctl.p + C_NEW, 0, sizeof(uint32_t), v.stream));
+        HIPCHK(hipEventRecord(ev[0], v.stream));
+        hipLaunchKernelGGL(wide ? k_c_expand<64> : k_c_expand<8>, dim3(grid), dim3(256), 0, v.stream, f0, f1, (const unsigned long long *)d_cpkey.p, L, R, d_ctab.p,
+                           d_cmin.p, (uint32_t)(slots - 1), d_cnew.p, (uint32_t)cap_new, d_cctl.p);
+        HIPCHK(hipEventRecord(ev[1], v.stream));
+        if (int rc = read_ctl()) return rc;
+        if (int rc = take_number_time()) return rc;
+        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        out->seconds_expand += ms * 1e-3;
+        n_new = ctl[C_NEW];
+        edges = (unsigned long long)ctl[C_EDGES] | ((unsigned long long)ctl[C_EDGES + 1] << 32);
+    }
+    if (int rc = read_ctl()) return rc;  // (the last number launch)
+    if (int rc = take_number_time()) return rc;
+    // the witnesses: the access sequence of each verdict's pair, from the (parent, label) records
+    std::vector<uint32_t> parent((size_t)n_pairs), plabel((size_t)n_pairs);
+    HIPCHK(hipMemcpyAsync(parent.data(), d_cparent.p, (size_t)n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(plabel.data(), d_cplabel.p, (size_t)n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+    unsigned long long wkey[4] = {0, 0, 0, 0};
+    for (int k = 0; k < 4; k++)
+        if (ctl[C_VERDICT + k] != kCmpNone) {
+            if (ctl[C_VERDICT + k] >= n_pairs) return fail(STCSP_E_INTERNAL, "compare: verdict %d names pair %u of %llu", k, ctl[C_VERDICT + k], n_pairs);
+            HIPCHK(hipMemcpyAsync(&wkey[k], d_cpkey.p + ctl[C_VERDICT + k], sizeof(unsigned long long), hipMemcpyDeviceToHost, v.stream));
+        }
+    HIPCHK(hipStreamSynchronize(v.stream));
+    std::vector<uint32_t> path;
+    for (int k = 0; k < 4; k++) {
+        out->witness_off[k + 1] = out->witness_off[k];
+        if (ctl[C_VERDICT + k] == kCmpNone) continue;
+        path.clear();
+        for (uint32_t q = ctl[C_VERDICT + k]; q; q = parent[q]) {
+            if (parent[q] >= q || plabel[q] >= n_rows)
+                return fail(STCSP_E_INTERNAL, "compare: the record of pair %u does not lead to the root", q);
+            path.push_back(plabel[q]);
+        }
+        for (size_t i = path.size(); i-- > 0;) c_witness.insert(c_witness.end(), rows.begin() + path[i] * n_obs, rows.begin() + (path[i] + 1) * n_obs);
+        const uint32_t l = (uint32_t)(wkey[k] >> 32), r = (uint32_t)wkey[k];
+        out->witness_len[k] = (int32_t)path.size();
+        out->witness_left[k] = l == left.n_states ? -1 : (int32_t)l;
+        out->witness_right[k] = r == right.n_states ? -1 : (int32_t)r;
+        out->witness_off[k + 1] += (int64_t)path.size();
+    }
+    c_witness.reserve(1);
+    out->witness_values = c_witness.data();
+    out->n_pairs = (int64_t)n_pairs;
+    out->n_pair_edges = (int64_t)edges;
+    out->levels = levels;
+    out->table_bytes = (int64_t)peak;
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;
 }
 

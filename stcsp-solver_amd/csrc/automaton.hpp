@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 
+#include "compare_host.hpp"
 #include "hip_host.hpp"
 
 namespace stcsp {
@@ -43,6 +44,7 @@ struct AutomatonServices {
     int repair(const AutomatonView &view, const stcsp_repair_request *rq, stcsp_repair_result *out);
     int infer(const AutomatonView &view, const stcsp_infer_request *rq, stcsp_infer_result *out);
     int observer(const AutomatonView &view, const stcsp_observer_options *oo, stcsp_observer_result *out);
+    int compare(const AutomatonView &view, const stcsp_compare_request *rq, stcsp_compare_result *out);
 
 private:
     enum Need { NEED_EXPORT, NEED_FLAGS, NEED_MONITOR, NEED_GENERATOR };
@@ -57,7 +59,7 @@ private:
     int infer_dictionaries();
     int observer_order(double &seconds);
     template <typename T>
-    int grow_keeping(DevBuf<T> &buf, size_t keep, size_t count);
+    int grow_keeping(DevBuf<T> &buf, size_t keep, size_t count, const char *who = "observer");
 
     AutomatonView v{};  // of the call that is running: its pointers are the engine's, not to be used after it
     DevEvents ev;     // (every call waits for its own work: one set serves them all)
@@ -134,6 +136,15 @@ private:
     std::vector<int64_t> o_moff;
     std::vector<int32_t> o_member, o_esrc, o_edst, o_evalues;
     std::vector<uint8_t> o_final;
+    // comparison (dev_compare.hpp): the left operand is the observer of the last successful observer(), kept on the host while
+    // cmp_valid and, from the first compare() on, as CSR in HBM while cmp_left_on_device; everything else lives for one call
+    bool cmp_valid = false, cmp_left_on_device = false;
+    CompareOperand cmp_left;
+    DevBuf<uint32_t> d_cloff, d_cllab, d_cldst, d_croff, d_crlab, d_crdst, d_cnew, d_crank, d_cparent, d_cplabel, d_cctl;
+    DevBuf<uint8_t> d_clfin, d_crfin;
+    DevBuf<unsigned long long> d_ctab, d_ctab2, d_cmin, d_ckeys, d_cpkey;
+    std::vector<int32_t> c_witness;
+    std::vector<uint32_t> c_rank;
 };
 
 }  // namespace stcsp

@@ -2403,6 +2403,10 @@ int stcsp_engine_observer(stcsp_engine *e, const stcsp_observer_options *options
     if (!e || !result) return STCSP_E_INVALID;
     return e->services.observer(e->view(), options, result);
 }
+int stcsp_engine_compare(stcsp_engine *e, const stcsp_compare_request *request, stcsp_compare_result *result) {
+    if (!e || !request || !result) return STCSP_E_INVALID;
+    return e->services.compare(e->view(), request, result);
+}
 
 void stcsp_engine_destroy(stcsp_engine *e) { delete e; }
 

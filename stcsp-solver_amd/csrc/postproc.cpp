@@ -26,6 +26,7 @@
 #include <chrono>
 #include "repair_host.hpp"
 #include "observer_host.hpp"
+#include "compare_host.hpp"
 #include "infer_host.hpp"
 #include "okfix.hpp"
 #include "stcsp_host.h"
@@ -999,6 +1000,10 @@ struct stcsp_observer {
     stcsp::HostObserver o;
     stcsp_observer_result res;
 };
+struct stcsp_comparison {
+    stcsp::HostComparison c;
+    stcsp_compare_result res;
+};
 
 extern "C" {
 
@@ -1334,6 +1339,47 @@ int stcsp_automaton_from_observer(const stcsp_automaton *a, const uint8_t *obser
     *out = h;
     return STCSP_OK;
 }
+
+int stcsp_automaton_num_vars(const stcsp_automaton *a) { return a ? a->a.n_vars : STCSP_E_INVALID; }
+const char *stcsp_automaton_var_name(const stcsp_automaton *a, int index) {
+    return a && index >= 0 && index < a->a.n_vars && (size_t)index < a->a.names.size() ? a->a.names[(size_t)index].c_str() : nullptr;
+}
+
+int stcsp_compare_observers(const stcsp_observer_result *left, const stcsp_observer_result *right, int64_t max_pairs, stcsp_comparison **out) {
+    if (!left || !right || !out || max_pairs < 0) return STCSP_E_INVALID;
+    stcsp_comparison *h = nullptr;
+    try {
+        h = new stcsp_comparison();
+        const auto t0 = std::chrono::steady_clock::now();
+        const int rc = h->c.run(*left, *right, max_pairs ? max_pairs : (int64_t)1 << 26);
+        if (rc != STCSP_OK) {
+            delete h;
+            return rc;
+        }
+        stcsp::HostComparison &c = h->c;
+        c.witness_values.reserve(1);  // (an empty vector still gives a valid pointer)
+        memset(&h->res, 0, sizeof h->res);
+        h->res.n_pairs = c.n_pairs;
+        h->res.n_pair_edges = c.n_pair_edges;
+        h->res.witness_values = c.witness_values.data();
+        for (int k = 0; k < 4; k++) {
+            h->res.witness_len[k] = c.witness_len[k];
+            h->res.witness_left[k] = c.witness_left[k];
+            h->res.witness_right[k] = c.witness_right[k];
+        }
+        std::copy(c.witness_off, c.witness_off + 5, h->res.witness_off);
+        h->res.n_observable = c.n_obs;
+        h->res.levels = c.levels;
+        h->res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    } catch (const std::bad_alloc &) {
+        delete h;
+        return STCSP_E_NOMEM;
+    }
+    *out = h;
+    return STCSP_OK;
+}
+const stcsp_compare_result *stcsp_comparison_get(const stcsp_comparison *c) { return c ? &c->res : nullptr; }
+void stcsp_comparison_free(stcsp_comparison *c) { delete c; }
 
 char *stcsp_automaton_canonical(const stcsp_automaton *a, size_t *len) {
     if (!a) return nullptr;

@@ -2,7 +2,7 @@
 // (src/stcsp.y:180-219 main, src/solver.cpp:195-359 solve): same flags, same stdout contract,
 // same solutions.dot. The search itself runs on the MI355X engine behind the C-ABI.
 //
-//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--observer[=all|NAME[,NAME...]]] [--check=<file>]
+//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--observer[=all|NAME[,NAME...]] [--compare=<file>]] [--check=<file>]
 //         [--sample=<N>:<L>[:<seed>] [--sample-final] [--sample-mask=all]] [--count=<L>]
 //         [--repair=<file> [--repair-final]] [--infer=<file> [--infer-final] [--infer-draws=<D>[:<seed>]]] input.csp
 //
@@ -14,6 +14,15 @@
 // solve and by the host twin otherwise (--shards=N, host adversarial passes). With --quotient the observer is then folded by the
 // host bisimulation under the same mask (--quotient=all is not taken with it): the minimal deterministic automaton of the observable language, which
 // --quotient alone cannot promise.
+// --compare=<file> (not in the reference; only together with --observer) compares what this model shows with what another one
+// shows (include/stcsp_engine.h, stcsp_engine_compare). The file is a binary automaton written by --binary= of any run: it
+// carries its variable names, the observable variables are matched by name (a name the file lacks is an error that says so),
+// its observer under those variables is built by the host twin and its columns are put in this model's order. This model's
+// observer is the left operand, the file's the right one. The comparison runs on the device for an unsharded solve and by the
+// host twin otherwise. Five lines go to stderr, "compare: <pairs> pairs, <edges> edges, <levels> levels" and one per inclusion,
+// "compare: <P|F>(<left|right>) in <P|F>(<right|left>): yes" or "...: no, <len> steps: v v ..; v v .." with the shortest stream
+// that refutes it (P: the streams with a run, F: those whose run ends in a final state). stdout and the written automaton are
+// unchanged.
 // --binary=<file> (not in the reference) additionally writes the printed automaton in the compact
 // binary form of include/stcsp_host.h.
 // --shards=<N> (not in the reference, which is single-threaded) shards the open search frontier and the state table over N
@@ -100,6 +109,7 @@ struct Flags {
     bool quotient = false, quotient_all = false;
     bool observer = false;
     const char *observer_mask = "";  // "" (the default mask), "all" or NAME[,NAME...]
+    const char *compare = nullptr;
     int prefix_k = 2, time_limit = 0, shards = 1;
     const char *file = nullptr;
     const char *binary = nullptr;
@@ -436,6 +446,98 @@ static int fold(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, con
     return 0;
 }
 
+// --compare=FILE: the observer `mine` of this model under `mask` (left) against the observer of FILE's automaton under the same
+// variables, matched by name (right); on the device (eng: its last observer() built `mine`) or by the host twin (eng NULL)
+static int compare_with_file(const Flags &f, const stcsp_problem *p, const uint8_t *mask, const stcsp_observer_result *mine, stcsp_engine *eng) {
+    stcsp_automaton *other = nullptr;
+    if (stcsp_automaton_read_binary(f.compare, &other) != STCSP_OK) {
+        fprintf(stderr, "--compare: cannot read the automaton of '%s'\n", f.compare);
+        return 1;
+    }
+    const int n_other = stcsp_automaton_num_vars(other);
+    std::vector<uint8_t> other_mask((size_t)n_other, 0);
+    std::vector<int> index_there;  // per observable variable of this model, in its order: the variable's index in FILE
+    for (int v = 0; v < p->n_vars; v++) {
+        if (!(mask ? mask[v] != 0 : strncmp(p->var_names[v], "_V", 2) != 0)) continue;
+        int u = 0;
+        while (u < n_other && strcmp(stcsp_automaton_var_name(other, u), p->var_names[v]) != 0) u++;
+        if (u == n_other) {
+            fprintf(stderr, "--compare: '%s' has no variable named '%s'\n", f.compare, p->var_names[v]);
+            stcsp_automaton_free(other);
+            return 1;
+        }
+        other_mask[(size_t)u] = 1;
+        index_there.push_back(u);
+    }
+    stcsp_observer *theirs = nullptr;
+    if (stcsp_automaton_observer(other, other_mask.data(), 0, &theirs) != STCSP_OK) {
+        fprintf(stderr, "--compare: the observer of '%s' could not be built\n", f.compare);
+        stcsp_automaton_free(other);
+        return 1;
+    }
+    // FILE's rows have its own column order: into this model's, and the edges of every state into the order of the new rows
+    stcsp_observer_result right = *stcsp_observer_get(theirs);
+    const size_t w = index_there.size(), E = (size_t)right.n_edges;
+    std::vector<size_t> column(w), order(E);
+    for (size_t c = 0; c < w; c++) column[c] = (size_t)std::count(other_mask.begin(), other_mask.begin() + index_there[c], 1);
+    std::vector<int32_t> rows(E * w), src(E), dst(E), values(E * w);
+    for (size_t e = 0; e < E; e++) {
+        order[e] = e;
+        for (size_t c = 0; c < w; c++) rows[e * w + c] = right.edge_values[e * w + column[c]];
+    }
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+        if (right.edge_src[a] != right.edge_src[b]) return right.edge_src[a] < right.edge_src[b];
+        return std::lexicographical_compare(rows.begin() + a * w, rows.begin() + (a + 1) * w, rows.begin() + b * w, rows.begin() + (b + 1) * w);
+    });
+    for (size_t i = 0; i < E; i++) {
+        src[i] = right.edge_src[order[i]];
+        dst[i] = right.edge_dst[order[i]];
+        std::copy(rows.begin() + order[i] * w, rows.begin() + (order[i] + 1) * w, values.begin() + i * w);
+    }
+    src.reserve(1);
+    dst.reserve(1);
+    values.reserve(1);
+    right.edge_src = src.data();
+    right.edge_dst = dst.data();
+    right.edge_values = values.data();
+    stcsp_comparison *twin = nullptr;
+    stcsp_compare_result dev;
+    const stcsp_compare_result *res = &dev;
+    int rc = 0;
+    if (eng) {
+        stcsp_compare_request rq = {&right, 0, {0, 0}};
+        if (stcsp_engine_compare(eng, &rq, &dev) != STCSP_OK) {
+            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
+            rc = 1;
+        }
+    } else if (stcsp_compare_observers(mine, &right, 0, &twin) != STCSP_OK) {
+        fprintf(stderr, "--compare: the comparison failed\n");
+        rc = 1;
+    } else {
+        res = stcsp_comparison_get(twin);
+    }
+    if (!rc) {
+        static const char *const claim[4] = {"P(left) in P(right)", "P(right) in P(left)", "F(left) in F(right)", "F(right) in F(left)"};
+        fprintf(stderr, "compare: %lld pairs, %lld edges, %d levels\n", (long long)res->n_pairs, (long long)res->n_pair_edges, res->levels);
+        for (int k = 0; k < 4; k++) {
+            if (res->witness_len[k] < 0) {
+                fprintf(stderr, "compare: %s: yes\n", claim[k]);
+                continue;
+            }
+            fprintf(stderr, "compare: %s: no, %d steps:", claim[k], res->witness_len[k]);
+            for (int t = 0; t < res->witness_len[k]; t++) {
+                if (t) fprintf(stderr, ";");
+                for (size_t c = 0; c < w; c++) fprintf(stderr, " %d", res->witness_values[((size_t)res->witness_off[k] + (size_t)t) * w + c]);
+            }
+            fprintf(stderr, "\n");
+        }
+    }
+    stcsp_comparison_free(twin);
+    stcsp_observer_free(theirs);
+    stcsp_automaton_free(other);
+    return rc;
+}
+
 // --observer: replace *a by its observer, built on the device (eng: a finished postprocess()) or by the host twin (eng NULL);
 // with --quotient, folded by the host bisimulation under the same mask
 static int observe(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, stcsp_engine *eng) {
@@ -475,6 +577,11 @@ static int observe(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, 
     stcsp_automaton *q = nullptr;
     const int rc = stcsp_automaton_from_observer(*a, mask, res, &q);
     fprintf(stderr, "observer: %lld -> %lld states, %lld edges\n", n_live, (long long)res->n_states, (long long)res->n_edges);
+    if (rc == STCSP_OK && f.compare && compare_with_file(f, p, mask, res, eng)) {
+        stcsp_observer_free(twin);
+        stcsp_automaton_free(q);
+        return 1;
+    }
     stcsp_observer_free(twin);
     if (rc != STCSP_OK) return 1;
     stcsp_automaton_free(*a);
@@ -775,6 +882,10 @@ int main(int argc, char **argv) {
             f.observer_mask = a[10] == '=' ? a + 11 : "";
             continue;
         }
+        if (strncmp(a, "--compare=", 10) == 0) {
+            f.compare = a + 10;
+            continue;
+        }
         if (strcmp(a, "--quotient") == 0 || strcmp(a, "--quotient=all") == 0) {
             f.quotient = true;
             f.quotient_all = a[10] == '=';
@@ -898,6 +1009,10 @@ int main(int argc, char **argv) {
     }
     if ((f.check != nullptr) + (f.repair != nullptr) + (f.infer != nullptr) + f.sample + (f.count_len >= 0) > 1) {
         fprintf(stderr, "--check, --repair, --infer, --sample and --count exclude each other\n");
+        return 1;
+    }
+    if (f.compare && !f.observer) {
+        fprintf(stderr, "--compare needs --observer: the observers of the two models are compared\n");
         return 1;
     }
     if (!f.file) {
