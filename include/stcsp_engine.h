@@ -712,6 +712,81 @@ typedef struct stcsp_compare_result {
 
 int stcsp_engine_compare(stcsp_engine *engine, const stcsp_compare_request *request, stcsp_compare_result *result);
 
+/* ---- strongly connected components and lasso solutions on the device (no reference counterpart) ----------------------
+ * Every other service speaks about finite prefixes; a solution of a stream CSP is an infinite stream. This call answers the
+ * questions about it: is there an infinite solution, which long-run regimes (components) exist, which states are only
+ * passed through, and what does one ultimately periodic solution stem . loop^omega look like.
+ *
+ * Live automaton, flags and validity are those of stcsp_engine_quotient(): the flags the last stcsp_engine_postprocess()
+ * wrote, adversarial passes included; STCSP_E_STATE before it and after a truncated solve; STCSP_E_UNSUPPORTED on sharded
+ * engines (run stcsp_automaton_components() of stcsp_host.h on the merged automaton). The call touches no other service's
+ * state: the monitor's, generator's, repair's and inference's structures, the observer and the compare operand stay valid.
+ *
+ * Components. state_component[s] is the strongly connected component of the live state s over the live edges, -1 outside
+ * the live automaton. Components are numbered by their least member's state index (the quotient's rule), so the numbers
+ * follow this solve's state numbering while the partition does not. Per component: comp_size, comp_depth (the least number
+ * of steps from the root to a member) and comp_flags:
+ *   STCSP_SCC_CYCLIC     more than one state, or a live self-loop
+ *   STCSP_SCC_FINAL      holds a final state
+ *   STCSP_SCC_BOTTOM     no live edge leaves it
+ *   STCSP_SCC_ACCEPTING  CYCLIC and FINAL
+ * state_omega[s] == 1 when s reaches an accepting component: Buechi acceptance on `final`, the state starts an infinite run
+ * that is final infinitely often. root_omega == 1 is "the model has an infinite solution".
+ *
+ * Lassos. options.max_lassos asks for them: 0 none, -1 all, n > 0 the first n. STCSP_SCC_LASSO_BOTTOM keeps only the
+ * accepting components that are bottom. The candidates are the accepting components (the root reaches every live
+ * component), taken in order of (comp_depth, component number); so which components of equal depth survive a truncating
+ * max_lassos follows this solve's state numbering. For a component c,
+ *   stem  is the shortest sequence of full label rows (all n_vars variables, in variable order) from the root to a final
+ *         state of c, and among the shortest the lexicographically least (length 0 when the root is such a state); its
+ *         end state is the anchor;
+ *   loop  is the shortest sequence, of at least one row, from the anchor back to the anchor over edges inside c, and among
+ *         the shortest the lexicographically least.
+ * The live automaton is deterministic under full labels, so both are unique and depend on neither scheduling nor state
+ * numbering; two live out-edges of one state with the same full row, met on a walk, give STCSP_E_INTERNAL. Lasso i belongs
+ * to component lasso_component[i] and is the rows [lasso_off[i], lasso_off[i + 1]) of lasso_values: lasso_stem_len[i] rows
+ * of stem, then the loop.
+ *
+ * STCSP_SCC_NO_TRIM (tests, measurements) lets the colouring rounds find every component, the trivial ones included; the
+ * result is the same. A pass that has not converged after n_states + 8 rounds gives STCSP_E_INTERNAL. Results are owned by
+ * the engine until the next call on it. */
+#define STCSP_SCC_LASSO_BOTTOM 1 /* options.flags: lassos of bottom accepting components only                        */
+#define STCSP_SCC_NO_TRIM 2      /* options.flags: no trimming, colouring alone                                        */
+#define STCSP_SCC_CYCLIC 1       /* comp_flags                                                                         */
+#define STCSP_SCC_FINAL 2
+#define STCSP_SCC_BOTTOM 4
+#define STCSP_SCC_ACCEPTING 8
+
+typedef struct stcsp_components_options {
+    int64_t max_lassos; /* 0 = none, -1 = all */
+    int32_t flags;      /* STCSP_SCC_LASSO_BOTTOM | STCSP_SCC_NO_TRIM */
+    int32_t reserved;
+} stcsp_components_options;
+
+typedef struct stcsp_components_result {
+    int64_t n_states; /* live states */
+    int64_t n_components, n_cyclic, n_accepting, n_bottom;
+    int64_t n_omega;                /* live states with state_omega set                                                  */
+    const int32_t *state_component; /* [stcsp_result::n_states], -1 outside the live automaton                           */
+    const uint8_t *state_omega;     /* [stcsp_result::n_states]                                                          */
+    const int32_t *comp_size;       /* [n_components]                                                                    */
+    const int32_t *comp_depth;      /* [n_components]                                                                    */
+    const int32_t *comp_flags;      /* [n_components] STCSP_SCC_CYCLIC | FINAL | BOTTOM | ACCEPTING                      */
+    int64_t n_lassos;
+    const int32_t *lasso_component; /* [n_lassos]                                                                        */
+    const int64_t *lasso_off;       /* [n_lassos + 1] in rows                                                            */
+    const int32_t *lasso_stem_len;  /* [n_lassos]                                                                        */
+    const int32_t *lasso_values;    /* [lasso_off[n_lassos] * n_vars]                                                    */
+    int32_t n_vars;
+    int32_t root_omega;
+    int32_t rounds[3];      /* trim rounds, colouring rounds, launches of sweep kernels in all (0 on the host twin)      */
+    int32_t reserved;
+    double seconds;         /* wall time from the flags in HBM to the result on the host                                 */
+    double seconds_kernels; /* HIP-event time of the launches, all phases (0 on the host twin)                           */
+} stcsp_components_result;
+
+int stcsp_engine_components(stcsp_engine *engine, const stcsp_components_options *options, stcsp_components_result *result);
+
 void stcsp_engine_destroy(stcsp_engine *engine);
 
 /* Message of the last error on this engine (or of the last failed create when engine==NULL). */

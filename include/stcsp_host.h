@@ -197,6 +197,18 @@ int stcsp_compare_observers(const stcsp_observer_result *left, const stcsp_obser
 const stcsp_compare_result *stcsp_comparison_get(const stcsp_comparison *c);
 void stcsp_comparison_free(stcsp_comparison *c);
 
+/* ---- strongly connected components and lasso solutions (definition: stcsp_engine.h, stcsp_engine_components) ----
+ * The same contract written plainly, on the automaton's current flags: an iterative Tarjan, breadth-first searches and the
+ * same greedy walks. The checker of the device pass in the tests, and the path for automata whose flags live on the host
+ * (merged sharded runs, host adversarial passes, read_binary, import_flags). max_lassos and flags as in
+ * stcsp_components_options (STCSP_SCC_NO_TRIM has no meaning here); STCSP_E_INTERNAL when a walk meets two live out-edges
+ * of one state with the same full row. The result (stcsp_components_get(): rounds and seconds_kernels are 0) lives until
+ * stcsp_components_free(). */
+typedef struct stcsp_components stcsp_components;
+int stcsp_automaton_components(const stcsp_automaton *a, int64_t max_lassos, int32_t flags, stcsp_components **out);
+const stcsp_components_result *stcsp_components_get(const stcsp_components *c);
+void stcsp_components_free(stcsp_components *c);
+
 /* Merge the per-shard results of a sharded run (global state ids, see stcsp_engine.h) into
  * one result with dense ids; runs the ok-fixpoint over the union. The merged result is owned
  * by the returned handle. */

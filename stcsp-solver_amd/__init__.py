@@ -324,6 +324,55 @@ def compare_observers(left, right, max_pairs=0):
         lib.stcsp_comparison_free(h)
 
 
+class ComponentsOptions(C.Structure):
+    _fields_ = [("max_lassos", C.c_int64), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ComponentsResult(C.Structure):
+    _fields_ = [("n_states", C.c_int64), ("n_components", C.c_int64), ("n_cyclic", C.c_int64), ("n_accepting", C.c_int64),
+                ("n_bottom", C.c_int64), ("n_omega", C.c_int64), ("state_component", C.POINTER(C.c_int32)),
+                ("state_omega", C.POINTER(C.c_uint8)), ("comp_size", C.POINTER(C.c_int32)), ("comp_depth", C.POINTER(C.c_int32)),
+                ("comp_flags", C.POINTER(C.c_int32)), ("n_lassos", C.c_int64), ("lasso_component", C.POINTER(C.c_int32)),
+                ("lasso_off", C.POINTER(C.c_int64)), ("lasso_stem_len", C.POINTER(C.c_int32)), ("lasso_values", C.POINTER(C.c_int32)),
+                ("n_vars", C.c_int32), ("root_omega", C.c_int32), ("rounds", C.c_int32 * 3), ("reserved", C.c_int32),
+                ("seconds", C.c_double), ("seconds_kernels", C.c_double)]
+
+
+SCC_LASSO_BOTTOM, SCC_NO_TRIM = 1, 2                       # ComponentsOptions.flags
+SCC_CYCLIC, SCC_FINAL, SCC_BOTTOM, SCC_ACCEPTING = 1, 2, 4, 8  # comp_flags
+COMPONENTS_SCALARS = ("n_states", "n_components", "n_cyclic", "n_accepting", "n_bottom", "n_omega", "n_lassos", "n_vars", "root_omega",
+                      "seconds", "seconds_kernels")
+
+
+def _components_options(lassos, no_trim):
+    """lassos: 0 (none), "all", "bottom" (all of the bottom accepting components) or a positive count."""
+    if lassos not in ("all", "bottom") and (not isinstance(lassos, int) or lassos < 0):
+        raise ValueError('lassos is 0, "bottom", "all" or a positive count')
+    return ComponentsOptions(-1 if lassos in ("all", "bottom") else lassos, (SCC_LASSO_BOTTOM if lassos == "bottom" else 0) | (SCC_NO_TRIM if no_trim else 0))
+
+
+def _components_unpack(res, n_states):
+    """A ComponentsResult -> dict: its scalars, rounds int32 [3], copies of state_component int32 / state_omega uint8 [n_states of the
+    Result], comp_size / comp_depth / comp_flags int32 [n_components], and "lassos": a list of (component, stem, loop), stem and loop
+    int32 arrays of full label rows [steps, n_vars]."""
+    import numpy as np
+
+    def arr(ptr, n, dtype):
+        return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dtype)
+    d = {k: getattr(res, k) for k in COMPONENTS_SCALARS}
+    d["rounds"] = np.array(res.rounds[:], np.int32)
+    d["state_component"] = arr(res.state_component, n_states, np.int32)
+    d["state_omega"] = arr(res.state_omega, n_states, np.uint8)
+    for k in ("comp_size", "comp_depth", "comp_flags"):
+        d[k] = arr(getattr(res, k), res.n_components, np.int32)
+    nl, nv = res.n_lassos, res.n_vars
+    off = arr(res.lasso_off, nl + 1, np.int64) if nl else np.zeros(1, np.int64)
+    comp, stem = arr(res.lasso_component, nl, np.int32), arr(res.lasso_stem_len, nl, np.int32)
+    values = arr(res.lasso_values, int(off[-1]) * nv, np.int32).reshape(int(off[-1]), nv)
+    d["lassos"] = [(int(comp[i]), values[off[i]:off[i] + stem[i]].copy(), values[off[i] + stem[i]:off[i + 1]].copy()) for i in range(nl)]
+    return d
+
+
 F_KEEP_RAW_EDGES = 1
 F_NO_EXPORT = 2
 F_PROFILE = 4
@@ -340,6 +389,7 @@ ENGINE_SYMBOLS = [
     "stcsp_engine_adopt", "stcsp_engine_expand_variant", "stcsp_engine_quotient",
     "stcsp_engine_monitor_build", "stcsp_engine_monitor_check", "stcsp_engine_generator_build", "stcsp_engine_generate",
     "stcsp_engine_repair", "stcsp_engine_infer", "stcsp_engine_observer", "stcsp_engine_compare",
+    "stcsp_engine_components",
 ]
 # include/stcsp_sharded.h: the superstep loop + in-process transport (libstcsp_hip.so), the RCCL transport (libstcsp_rccl.so)
 SHARDED_SYMBOLS_HIP = ["stcsp_engine_solve_sharded", "stcsp_local_group_create", "stcsp_local_group_transport", "stcsp_local_group_destroy"]
@@ -358,6 +408,7 @@ HOST_SYMBOLS = [
     "stcsp_automaton_repair_streams", "stcsp_automaton_infer_streams",
     "stcsp_automaton_observer", "stcsp_observer_get", "stcsp_observer_free", "stcsp_automaton_from_observer",
     "stcsp_compare_observers", "stcsp_comparison_get", "stcsp_comparison_free", "stcsp_automaton_num_vars", "stcsp_automaton_var_name",
+    "stcsp_automaton_components", "stcsp_components_get", "stcsp_components_free",
 ]
 
 
@@ -448,6 +499,10 @@ def host_lib() -> C.CDLL:
         lib.stcsp_comparison_get.argtypes = [C.c_void_p]
         lib.stcsp_comparison_get.restype = C.POINTER(CompareResult)
         lib.stcsp_comparison_free.argtypes = [C.c_void_p]
+        lib.stcsp_automaton_components.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
+        lib.stcsp_components_get.argtypes = [C.c_void_p]
+        lib.stcsp_components_get.restype = C.POINTER(ComponentsResult)
+        lib.stcsp_components_free.argtypes = [C.c_void_p]
         lib.stcsp_automaton_num_vars.argtypes = [C.c_void_p]
         lib.stcsp_automaton_var_name.argtypes = [C.c_void_p, C.c_int]
         lib.stcsp_automaton_var_name.restype = C.c_char_p
@@ -510,6 +565,8 @@ def bind_engine_api(lib: C.CDLL, prefix: str = "stcsp_engine") -> None:
         g("observer").argtypes = [C.c_void_p, C.POINTER(ObserverOptions), C.POINTER(ObserverResult)]
     if hasattr(lib, f"{prefix}_compare"):
         g("compare").argtypes = [C.c_void_p, C.POINTER(CompareRequest), C.POINTER(CompareResult)]
+    if hasattr(lib, f"{prefix}_components"):
+        g("components").argtypes = [C.c_void_p, C.POINTER(ComponentsOptions), C.POINTER(ComponentsResult)]
     if hasattr(lib, f"{prefix}_propagate"):
         g("propagate").argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64)]
@@ -840,6 +897,21 @@ class Automaton:
             return _observer_unpack(lib.stcsp_observer_get(h).contents)
         finally:
             lib.stcsp_observer_free(h)
+
+    def components(self, lassos=0, no_trim=False):
+        """The strongly connected components, omega-liveness and lasso solutions of the live automaton by the host twin of
+        Engine.components() (contract: include/stcsp_engine.h, stcsp_engine_components), on the automaton's current flags.
+        lassos as there; no_trim is accepted and means nothing here. Returns the dict of _components_unpack()."""
+        lib = host_lib()
+        co = _components_options(lassos, no_trim)
+        h = C.c_void_p()
+        rc = lib.stcsp_automaton_components(self._h, co.max_lassos, co.flags, C.byref(h))
+        if rc != 0:
+            raise StcspError(rc, "components failed: two live out-edges of one state carry the same full row" if rc == -5 else "components failed")
+        try:
+            return _components_unpack(lib.stcsp_components_get(h).contents, int(lib.stcsp_automaton_num_states(self._h)))
+        finally:
+            lib.stcsp_components_free(h)
 
     def from_observer(self, obs, observable=None) -> "Automaton":
         """The observer `obs` (the dict of Engine.observer() or observer() for this automaton under `observable`) as an
@@ -1199,6 +1271,18 @@ class EngineBase:
         del keep
         self._check(rc)
         return _compare_unpack(out)
+
+    def components(self, lassos=0, no_trim=False):
+        """The strongly connected components of the live automaton on the device, after postprocess(): which states belong
+        together in the long run, which components are cyclic, final, bottom and accepting, which states start an infinite
+        solution (state_omega, root_omega), and lasso solutions stem . loop^omega. lassos: 0 (none), "all", "bottom" (the bottom
+        accepting components only) or a count; no_trim (tests, measurements) lets the colouring rounds find every component.
+        Returns the dict of _components_unpack(); it touches no other service's state. Contract: include/stcsp_engine.h,
+        stcsp_engine_components."""
+        co = _components_options(lassos, no_trim)
+        out = ComponentsResult()
+        self._check(self._f("components")(self._h, C.byref(co), C.byref(out)))
+        return _components_unpack(out, self.result.n_states)
 
     def automaton(self, result: Result | None = None) -> Automaton:
         return Automaton(self._model, result if result is not None else self.result)

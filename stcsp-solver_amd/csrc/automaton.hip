@@ -19,6 +19,7 @@
 #include "dev_infer.hpp"
 #include "dev_observer.hpp"
 #include "dev_compare.hpp"
+#include "dev_components.hpp"
 #include "repair_host.hpp"
 #include "infer_host.hpp"
 
@@ -1502,6 +1503,293 @@ int AutomatonServices::compare(const AutomatonView &view, const stcsp_compare_re
     out->n_pair_edges = (int64_t)edges;
     out->levels = levels;
     out->table_bytes = (int64_t)peak;
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return STCSP_OK;
+}
+
+// Strongly connected components of the live automaton, omega-liveness and lasso solutions (contract: stcsp_engine.h;
+// dev_components.hpp). Every device buffer lives for the call; no other service's state is touched.
+int AutomatonServices::components(const AutomatonView &view, const stcsp_components_options *co, stcsp_components_result *out) {
+    if (int rc = enter(view, "components", NEED_FLAGS, "stcsp_automaton_components")) return rc;
+    auto t0 = std::chrono::steady_clock::now();
+    const int N = v.N;
+    const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
+    const int64_t max_lassos = co ? co->max_lassos : 0;
+    const int32_t flags = co ? co->flags : 0;
+    if (max_lassos < -1) return fail(STCSP_E_INVALID, "components: max_lassos is 0 (none), -1 (all) or a positive count");
+    if (v.exp_edges > 0x7fffffffull || S > 0x3fffffffu) return fail(STCSP_E_NOMEM, "automaton too large for the device component pass");
+    if (int rc = live_set()) return rc;
+    HIPCHK(reserve_all(S, 1, d_scomp, d_scolour, d_sin, d_sout, d_sdepth, d_soff));
+    HIPCHK(d_sinfo.reserve(4 * (size_t)S));
+    HIPCHK(d_somega.reserve(S));
+    HIPCHK(d_sctl.reserve_exact(S_WORDS));
+    HIPCHK(d_ssel.reserve_exact(64));
+    HIPCHK(ev.ready(2));
+    const unsigned sb = (S + 255) / 256, eb = (E + 255) / 256;
+    const size_t sw = (size_t)S * sizeof(uint32_t);
+    uint32_t ctl[S_WORDS] = {0, 0, 0, 0};
+    double ms_kernels = 0;
+    bool open = false;  // between the event before a batch of launches and the one after it
+    int32_t sweeps = 0, trim_rounds = 0, colour_rounds = 0;
+    auto begin = [&]() -> int {
+        if (!open) HIPCHK(hipEventRecord(ev[0], v.stream));
+        open = true;
+        return STCSP_OK;
+    };
+    auto flush = [&]() -> int {  // ends a batch: the control words, and the batch's time on the device
+        if (int rc = begin()) return rc;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev[1], v.stream));
+        HIPCHK(hipMemcpyAsync(ctl, d_sctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        ms_kernels += ms;
+        open = false;
+        return STCSP_OK;
+    };
+    // the live edges as CSR by source
+    uint32_t L = 0;
+    if (int rc = begin()) return rc;
+    HIPCHK(hipMemsetAsync(d_sctl.p, 0, sizeof ctl, v.stream));
+    HIPCHK(hipMemsetAsync(d_sin.p, 0, sw, v.stream));
+    if (E)
+        hipLaunchKernelGGL(k_s_count, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)d_palive.p, (const uint8_t *)d_live.p,
+                           d_sin.p);
+    hipLaunchKernelGGL(k_s_scan, dim3(1), dim3(256), 0, v.stream, S, (S + 255) / 256, (const uint32_t *)d_sin.p, d_soff.p, d_sout.p);
+    HIPCHK(hipMemcpyAsync(&L, d_soff.p + S, sizeof L, hipMemcpyDeviceToHost, v.stream));
+    if (int rc = flush()) return rc;
+    if (L > E) return fail(STCSP_E_INTERNAL, "components: %u live edges of %u", L, E);
+    HIPCHK(reserve_all(L, 1, d_ssrc, d_sdst, d_seid));
+    const unsigned lb = (L + 255) / 256;
+    const uint32_t *csrc = d_ssrc.p, *cdst = d_sdst.p;
+    if (L)
+        hipLaunchKernelGGL(k_s_fill, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)d_palive.p, (const uint8_t *)d_live.p,
+                           d_sout.p, L, d_ssrc.p, d_sdst.p, d_seid.p);
+    // step(i) launches sweep i; a batch of sweeps, then one look at the changed word; past the fixpoint a sweep changes nothing
+    const int kBatch = 4;
+    auto fixpoint = [&](const char *what, auto &&step) -> int {
+        for (uint32_t done = 0;;) {
+            if (int rc = begin()) return rc;
+            HIPCHK(hipMemsetAsync(d_sctl.p + S_CHANGED, 0, sizeof(uint32_t), v.stream));
+            for (int b = 0; b < kBatch; b++, sweeps++)
+                if (int rc = step(done++)) return rc;
+            if (int rc = flush()) return rc;
+            if (!ctl[S_CHANGED]) return STCSP_OK;
+            if (done > S + 8) return fail(STCSP_E_INTERNAL, "components: %s did not converge", what);
+        }
+    };
+    // trim and colour until every live state has a component
+    HIPCHK(hipMemsetAsync(d_scomp.p, 0xff, sw, v.stream));
+    while ((int64_t)ctl[S_ASSIGNED] < n_live) {
+        if (!(flags & STCSP_SCC_NO_TRIM)) {
+            const int rc = fixpoint("trimming", [&](uint32_t) -> int {
+                HIPCHK(hipMemsetAsync(d_sin.p, 0, sw, v.stream));
+                HIPCHK(hipMemsetAsync(d_sout.p, 0, sw, v.stream));
+                if (L) hipLaunchKernelGGL(k_s_deg, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, (const uint32_t *)d_scomp.p, d_sin.p, d_sout.p);
+                hipLaunchKernelGGL(k_s_trim, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint32_t *)d_sin.p,
+                                   (const uint32_t *)d_sout.p, d_scomp.p, d_sctl.p);
+                trim_rounds++;
+                return STCSP_OK;
+            });
+            if (rc) return rc;
+            if ((int64_t)ctl[S_ASSIGNED] >= n_live) break;
+        }
+        if ((uint32_t)colour_rounds++ > S + 8) return fail(STCSP_E_INTERNAL, "components: the colouring rounds did not converge");
+        if (int rc = begin()) return rc;
+        hipLaunchKernelGGL(k_s_colour_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint32_t *)d_scomp.p, d_scolour.p);
+        int rc = fixpoint("colouring", [&](uint32_t) -> int {
+            if (L) hipLaunchKernelGGL(k_s_colour_fwd, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, d_scolour.p, d_sctl.p);
+            return STCSP_OK;
+        });
+        if (rc) return rc;
+        if (int rc2 = begin()) return rc2;
+        hipLaunchKernelGGL(k_s_roots, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)d_scolour.p, d_scomp.p, d_sctl.p);
+        rc = fixpoint("collecting", [&](uint32_t) -> int {
+            if (L) hipLaunchKernelGGL(k_s_colour_back, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, (const uint32_t *)d_scolour.p, d_scomp.p, d_sctl.p);
+            return STCSP_OK;
+        });
+        if (rc) return rc;
+    }
+    if ((int64_t)ctl[S_ASSIGNED] != n_live) return fail(STCSP_E_INTERNAL, "components: %u of %lld live states have a component", ctl[S_ASSIGNED], (long long)n_live);
+    // depths, the facts of every component, omega
+    if (int rc = begin()) return rc;
+    HIPCHK(hipMemsetAsync(d_sdepth.p, 0xff, sw, v.stream));
+    if (root_live) HIPCHK(hipMemsetAsync(d_sdepth.p, 0, sizeof(uint32_t), v.stream));
+    if (int rc = fixpoint("the depths", [&](uint32_t level) -> int {
+            if (L) hipLaunchKernelGGL(k_s_bfs, dim3(lb), dim3(256), 0, v.stream, L, level, csrc, cdst, d_sdepth.p, d_sctl.p);
+            return STCSP_OK;
+        }))
+        return rc;
+    if (int rc = begin()) return rc;
+    HIPCHK(hipMemsetAsync(d_sinfo.p, 0, 2 * sw, v.stream));
+    HIPCHK(hipMemsetAsync(d_sinfo.p + 2 * (size_t)S, 0xff, 2 * sw, v.stream));
+    hipLaunchKernelGGL(k_s_state_info, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint8_t *)d_pfinal.p,
+                       (const uint32_t *)d_scomp.p, (const uint32_t *)d_sdepth.p, d_sinfo.p);
+    if (L) hipLaunchKernelGGL(k_s_edge_info, dim3(lb), dim3(256), 0, v.stream, L, S, csrc, cdst, (const uint32_t *)d_scomp.p, d_sinfo.p);
+    hipLaunchKernelGGL(k_s_omega_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint32_t *)d_scomp.p,
+                       (const uint32_t *)d_sinfo.p, d_somega.p);
+    if (int rc = fixpoint("omega", [&](uint32_t) -> int {
+            if (L) hipLaunchKernelGGL(k_s_omega_back, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, d_somega.p, d_sctl.p);
+            return STCSP_OK;
+        }))
+        return rc;
+    std::vector<uint32_t> raw(S), info(4 * (size_t)S);
+    s_omega.assign(S, 0);
+    HIPCHK(hipMemcpyAsync(raw.data(), d_scomp.p, sw, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(info.data(), d_sinfo.p, 4 * sw, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(s_omega.data(), d_somega.p, S, hipMemcpyDeviceToHost, v.stream));
+    if (int rc = flush()) return rc;
+    // component numbers by least member: a component's raw name is its least member, so the first state that shows it is that member
+    s_component.assign(S, -1);
+    s_size.clear();
+    s_depth.clear();
+    s_flags.clear();
+    std::vector<int32_t> number(S, -1);
+    std::vector<uint32_t> least;
+    memset(out, 0, sizeof *out);
+    for (uint32_t s = 0; s < S; s++) {
+        if (!live[s]) continue;
+        const uint32_t r = raw[s];
+        if (r >= S || (number[r] < 0 && r != s)) return fail(STCSP_E_INTERNAL, "components: state %u is named after %u, not its component's least member", s, r);
+        if (number[r] < 0) {
+            number[r] = (int32_t)least.size();
+            least.push_back(r);
+            const uint32_t f = info[(size_t)S + r];
+            int32_t cf = (f & S_INFO_CYCLIC ? STCSP_SCC_CYCLIC : 0) | (f & S_INFO_FINAL ? STCSP_SCC_FINAL : 0) | (f & S_INFO_LEAVES ? 0 : STCSP_SCC_BOTTOM);
+            if ((f & S_INFO_CYCLIC) && (f & S_INFO_FINAL)) cf |= STCSP_SCC_ACCEPTING;
+            s_size.push_back((int32_t)info[r]);
+            s_depth.push_back((int32_t)info[2 * (size_t)S + r]);
+            s_flags.push_back(cf);
+            out->n_cyclic += (cf & STCSP_SCC_CYCLIC) != 0;
+            out->n_accepting += (cf & STCSP_SCC_ACCEPTING) != 0;
+            out->n_bottom += (cf & STCSP_SCC_BOTTOM) != 0;
+        }
+        s_component[s] = number[r];
+        out->n_omega += s_omega[s];
+    }
+    // lassos: the accepting components by (depth, number), 64 stems per pass, then every loop at once
+    s_lcomp.clear();
+    s_lstem.clear();
+    s_lvalues.clear();
+    s_loff.assign(1, 0);
+    std::vector<int32_t> wanted;
+    if (max_lassos != 0)
+        for (int32_t c = 0; c < (int32_t)s_flags.size(); c++)
+            if ((s_flags[c] & STCSP_SCC_ACCEPTING) && (!(flags & STCSP_SCC_LASSO_BOTTOM) || (s_flags[c] & STCSP_SCC_BOTTOM))) wanted.push_back(c);
+    std::stable_sort(wanted.begin(), wanted.end(), [&](int32_t a, int32_t b) { return s_depth[a] < s_depth[b]; });
+    if (max_lassos > 0 && (int64_t)wanted.size() > max_lassos) wanted.resize((size_t)max_lassos);
+    if (!wanted.empty()) {
+        std::vector<uint32_t> depth(S), off((size_t)S + 1), heid(L), dist(S), anchors(wanted.size());
+        auto hdst = [&](uint32_t k) { return (uint32_t)v.h_odst[heid[k]]; };  // (the destinations are in the pinned export already)
+        std::vector<unsigned long long> mark(S);
+        std::vector<std::vector<int32_t>> stems(wanted.size());
+        HIPCHK(d_smark.reserve(S));
+        HIPCHK(d_sdist.reserve(S));
+        HIPCHK(hipMemcpyAsync(depth.data(), d_sdepth.p, sw, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(off.data(), d_soff.p, sw + sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(heid.data(), d_seid.p, (size_t)L * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+        bool twice = false;
+        // the position of the live out-edge of u with the least full row among those whose destination `ok` admits; L when there is none
+        auto least_edge = [&](uint32_t u, auto &&ok) {
+            uint32_t best = L;
+            for (uint32_t k = off[u]; k < off[u + 1]; k++) {
+                if (!ok(hdst(k))) continue;
+                if (best == L) {
+                    best = k;
+                    continue;
+                }
+                const int32_t *x = v.h_oval + (size_t)heid[k] * N, *y = v.h_oval + (size_t)heid[best] * N;
+                if (std::equal(x, x + N, y)) twice = true;
+                if (std::lexicographical_compare(x, x + N, y, y + N)) best = k;
+            }
+            return best;
+        };
+        for (size_t p0 = 0; p0 < wanted.size(); p0 += 64) {
+            const int n_sel = (int)std::min<size_t>(64, wanted.size() - p0);
+            uint32_t sel[64], deepest = 0;
+            for (int j = 0; j < n_sel; j++) {
+                sel[j] = least[(size_t)wanted[p0 + j]];
+                deepest = std::max(deepest, info[3 * (size_t)S + sel[j]]);
+            }
+            if (deepest > S) return fail(STCSP_E_INTERNAL, "components: an accepting component without a final state");
+            if (int rc = begin()) return rc;
+            HIPCHK(hipMemcpyAsync(d_ssel.p, sel, (size_t)n_sel * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+            hipLaunchKernelGGL(k_s_stem_init, dim3(sb), dim3(256), 0, v.stream, S, n_sel, (const uint32_t *)d_ssel.p, (const uint8_t *)d_live.p,
+                               (const uint8_t *)d_pfinal.p, (const uint32_t *)d_scomp.p, (const uint32_t *)d_sdepth.p, (const uint32_t *)d_sinfo.p,
+                               d_smark.p);
+            for (uint32_t level = deepest; level-- > 0; sweeps++)
+                hipLaunchKernelGGL(k_s_stem_back, dim3(lb), dim3(256), 0, v.stream, L, level, csrc, cdst, (const uint32_t *)d_sdepth.p, d_smark.p);
+            HIPCHK(hipMemcpyAsync(mark.data(), d_smark.p, (size_t)S * sizeof(unsigned long long), hipMemcpyDeviceToHost, v.stream));
+            if (int rc = flush()) return rc;
+            for (int j = 0; j < n_sel; j++) {
+                const uint32_t len = info[3 * (size_t)S + sel[j]];
+                uint32_t u = 0;
+                for (uint32_t t = 0; t < len; t++) {
+                    const uint32_t k = least_edge(u, [&](uint32_t w) { return depth[w] == t + 1 && ((mark[w] >> j) & 1); });
+                    if (twice) return fail(STCSP_E_INTERNAL, "components: two live out-edges of state %u carry the same full row", u);
+                    if (k == L) return fail(STCSP_E_INTERNAL, "components: the stem of component %d stops at state %u", wanted[p0 + j], u);
+                    stems[p0 + j].insert(stems[p0 + j].end(), v.h_oval + (size_t)heid[k] * N, v.h_oval + ((size_t)heid[k] + 1) * N);
+                    u = hdst(k);
+                }
+                if (raw[u] != sel[j] || !((mark[u] >> j) & 1)) return fail(STCSP_E_INTERNAL, "components: the stem of component %d ends in state %u", wanted[p0 + j], u);
+                anchors[p0 + j] = u;
+            }
+        }
+        // the anchors' buffer: the colours are no longer needed (as many anchors as components at the most)
+        if (int rc = begin()) return rc;
+        HIPCHK(hipMemcpyAsync(d_scolour.p, anchors.data(), anchors.size() * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+        HIPCHK(hipMemsetAsync(d_sdist.p, 0xff, sw, v.stream));
+        hipLaunchKernelGGL(k_s_loop_init, dim3(((unsigned)anchors.size() + 255) / 256), dim3(256), 0, v.stream, (uint32_t)anchors.size(), S,
+                           (const uint32_t *)d_scolour.p, d_sdist.p);
+        if (int rc = fixpoint("the loop distances", [&](uint32_t level) -> int {
+                if (L) hipLaunchKernelGGL(k_s_loop_back, dim3(lb), dim3(256), 0, v.stream, L, level, csrc, cdst, (const uint32_t *)d_scomp.p, d_sdist.p, d_sctl.p);
+                return STCSP_OK;
+            }))
+            return rc;
+        HIPCHK(hipMemcpyAsync(dist.data(), d_sdist.p, sw, hipMemcpyDeviceToHost, v.stream));
+        if (int rc = flush()) return rc;
+        for (size_t i = 0; i < wanted.size(); i++) {
+            const uint32_t a = anchors[i], r = raw[a];
+            uint32_t loop_len = kSNone;
+            for (uint32_t k = off[a]; k < off[a + 1]; k++)
+                if (raw[hdst(k)] == r && dist[hdst(k)] != kSNone) loop_len = std::min(loop_len, dist[hdst(k)] + 1);
+            if (loop_len == kSNone) return fail(STCSP_E_INTERNAL, "components: no loop through state %u of component %d", a, wanted[i]);
+            s_lvalues.insert(s_lvalues.end(), stems[i].begin(), stems[i].end());
+            uint32_t u = a;
+            for (uint32_t rem = loop_len; rem > 0; rem--) {
+                const uint32_t k = least_edge(u, [&](uint32_t w) { return raw[w] == r && dist[w] == rem - 1; });
+                if (twice) return fail(STCSP_E_INTERNAL, "components: two live out-edges of state %u carry the same full row", u);
+                if (k == L) return fail(STCSP_E_INTERNAL, "components: the loop of component %d stops at state %u", wanted[i], u);
+                s_lvalues.insert(s_lvalues.end(), v.h_oval + (size_t)heid[k] * N, v.h_oval + ((size_t)heid[k] + 1) * N);
+                u = hdst(k);
+            }
+            if (u != a) return fail(STCSP_E_INTERNAL, "components: the loop of component %d ends in state %u, not in %u", wanted[i], u, a);
+            s_lcomp.push_back(wanted[i]);
+            s_lstem.push_back((int32_t)(stems[i].size() / (size_t)std::max(N, 1)));
+            s_loff.push_back(s_loff.back() + (int64_t)(stems[i].size() / (size_t)std::max(N, 1)) + loop_len);
+        }
+    }
+    for (auto *vec : {&s_component, &s_size, &s_depth, &s_flags, &s_lcomp, &s_lstem, &s_lvalues}) vec->reserve(1);
+    s_omega.reserve(1);
+    out->n_states = n_live;
+    out->n_components = (int64_t)s_size.size();
+    out->state_component = s_component.data();
+    out->state_omega = s_omega.data();
+    out->comp_size = s_size.data();
+    out->comp_depth = s_depth.data();
+    out->comp_flags = s_flags.data();
+    out->n_lassos = (int64_t)s_lcomp.size();
+    out->lasso_component = s_lcomp.data();
+    out->lasso_off = s_loff.data();
+    out->lasso_stem_len = s_lstem.data();
+    out->lasso_values = s_lvalues.data();
+    out->n_vars = N;
+    out->root_omega = root_live && s_omega[0];
+    out->rounds[0] = trim_rounds;
+    out->rounds[1] = colour_rounds;
+    out->rounds[2] = sweeps;
+    out->seconds_kernels = ms_kernels * 1e-3;
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;
 }

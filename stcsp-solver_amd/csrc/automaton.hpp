@@ -45,6 +45,7 @@ struct AutomatonServices {
     int infer(const AutomatonView &view, const stcsp_infer_request *rq, stcsp_infer_result *out);
     int observer(const AutomatonView &view, const stcsp_observer_options *oo, stcsp_observer_result *out);
     int compare(const AutomatonView &view, const stcsp_compare_request *rq, stcsp_compare_result *out);
+    int components(const AutomatonView &view, const stcsp_components_options *co, stcsp_components_result *out);
 
 private:
     enum Need { NEED_EXPORT, NEED_FLAGS, NEED_MONITOR, NEED_GENERATOR };
@@ -145,6 +146,13 @@ private:
     DevBuf<unsigned long long> d_ctab, d_ctab2, d_cmin, d_ckeys, d_cpkey;
     std::vector<int32_t> c_witness;
     std::vector<uint32_t> c_rank;
+    // components (dev_components.hpp): everything lives for one call; the vectors back the result until the next call
+    DevBuf<uint32_t> d_scomp, d_scolour, d_sin, d_sout, d_sdepth, d_sdist, d_soff, d_sinfo, d_ssrc, d_sdst, d_seid, d_ssel, d_sctl;
+    DevBuf<uint8_t> d_somega;
+    DevBuf<unsigned long long> d_smark;
+    std::vector<int32_t> s_component, s_size, s_depth, s_flags, s_lcomp, s_lstem, s_lvalues;
+    std::vector<uint8_t> s_omega;
+    std::vector<int64_t> s_loff;
 };
 
 }  // namespace stcsp

@@ -2407,6 +2407,10 @@ int stcsp_engine_compare(stcsp_engine *e, const stcsp_compare_request *request, 
     if (!e || !request || !result) return STCSP_E_INVALID;
     return e->services.compare(e->view(), request, result);
 }
+int stcsp_engine_components(stcsp_engine *e, const stcsp_components_options *options, stcsp_components_result *result) {
+    if (!e || !result) return STCSP_E_INVALID;
+    return e->services.components(e->view(), options, result);
+}
 
 void stcsp_engine_destroy(stcsp_engine *e) { delete e; }
 

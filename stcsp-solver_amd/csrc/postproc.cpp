@@ -26,6 +26,7 @@
 #include <chrono>
 #include "repair_host.hpp"
 #include "observer_host.hpp"
+#include "components_host.hpp"
 #include "compare_host.hpp"
 #include "infer_host.hpp"
 #include "okfix.hpp"
@@ -1004,6 +1005,10 @@ struct stcsp_comparison {
     stcsp::HostComparison c;
     stcsp_compare_result res;
 };
+struct stcsp_components {
+    stcsp::HostComponents c;
+    stcsp_components_result res;
+};
 
 extern "C" {
 
@@ -1380,6 +1385,50 @@ int stcsp_compare_observers(const stcsp_observer_result *left, const stcsp_obser
 }
 const stcsp_compare_result *stcsp_comparison_get(const stcsp_comparison *c) { return c ? &c->res : nullptr; }
 void stcsp_comparison_free(stcsp_comparison *c) { delete c; }
+
+int stcsp_automaton_components(const stcsp_automaton *a, int64_t max_lassos, int32_t flags, stcsp_components **out) {
+    if (!a || !out || max_lassos < -1) return STCSP_E_INVALID;
+    stcsp_components *h = nullptr;
+    try {
+        h = new stcsp_components();
+        const auto t0 = std::chrono::steady_clock::now();
+        if (!h->c.run(generator_view(a->a), max_lassos, flags)) {
+            delete h;
+            return STCSP_E_INTERNAL;
+        }
+        stcsp::HostComponents &c = h->c;
+        for (auto *v : {&c.state_component, &c.comp_size, &c.comp_depth, &c.comp_flags, &c.lasso_component, &c.lasso_stem_len, &c.lasso_values})
+            v->reserve(1);  // (empty vectors still give valid pointers)
+        c.state_omega.reserve(1);
+        memset(&h->res, 0, sizeof h->res);
+        h->res.n_states = c.n_live;
+        h->res.n_components = (int64_t)c.comp_size.size();
+        h->res.n_cyclic = c.n_cyclic;
+        h->res.n_accepting = c.n_accepting;
+        h->res.n_bottom = c.n_bottom;
+        h->res.n_omega = c.n_omega;
+        h->res.state_component = c.state_component.data();
+        h->res.state_omega = c.state_omega.data();
+        h->res.comp_size = c.comp_size.data();
+        h->res.comp_depth = c.comp_depth.data();
+        h->res.comp_flags = c.comp_flags.data();
+        h->res.n_lassos = (int64_t)c.lasso_component.size();
+        h->res.lasso_component = c.lasso_component.data();
+        h->res.lasso_off = c.lasso_off.data();
+        h->res.lasso_stem_len = c.lasso_stem_len.data();
+        h->res.lasso_values = c.lasso_values.data();
+        h->res.n_vars = c.n_vars;
+        h->res.root_omega = c.root_omega;
+        h->res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    } catch (const std::bad_alloc &) {
+        delete h;
+        return STCSP_E_NOMEM;
+    }
+    *out = h;
+    return STCSP_OK;
+}
+const stcsp_components_result *stcsp_components_get(const stcsp_components *c) { return c ? &c->res : nullptr; }
+void stcsp_components_free(stcsp_components *c) { delete c; }
 
 char *stcsp_automaton_canonical(const stcsp_automaton *a, size_t *len) {
     if (!a) return nullptr;

@@ -2,7 +2,7 @@
 // (src/stcsp.y:180-219 main, src/solver.cpp:195-359 solve): same flags, same stdout contract,
 // same solutions.dot. The search itself runs on the MI355X engine behind the C-ABI.
 //
-//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--observer[=all|NAME[,NAME...]] [--compare=<file>]] [--check=<file>]
+//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--observer[=all|NAME[,NAME...]] [--compare=<file>]] [--components[=bottom|all|<N>]] [--check=<file>]
 //         [--sample=<N>:<L>[:<seed>] [--sample-final] [--sample-mask=all]] [--count=<L>]
 //         [--repair=<file> [--repair-final]] [--infer=<file> [--infer-final] [--infer-draws=<D>[:<seed>]]] input.csp
 //
@@ -14,6 +14,13 @@
 // solve and by the host twin otherwise (--shards=N, host adversarial passes). With --quotient the observer is then folded by the
 // host bisimulation under the same mask (--quotient=all is not taken with it): the minimal deterministic automaton of the observable language, which
 // --quotient alone cannot promise.
+// --components[=bottom|all|<N>] (not in the reference) prints to stderr what the automaton says about INFINITE solutions
+// (include/stcsp_engine.h, stcsp_engine_components): a line of counts that ends in "infinite solution: yes|no", one line per strongly
+// connected component (number, size, depth, flags: C cyclic, F final, B bottom, A accepting) and, asked for with =all, =bottom (the
+// bottom accepting components only) or =<N> (the first N), lasso solutions stem . loop^omega: a line "# name name ..." of the
+// variables of the default mask, then per lasso the lines "stem:" and "loop:", the rows in the format --check= reads, separated by
+// ';'. stdout and the written files are unchanged. On the device for an unsharded solve, by the host twin otherwise.
+//
 // --compare=<file> (not in the reference; only together with --observer) compares what this model shows with what another one
 // shows (include/stcsp_engine.h, stcsp_engine_compare). The file is a binary automaton written by --binary= of any run: it
 // carries its variable names, the observable variables are matched by name (a name the file lacks is an error that says so),
@@ -110,6 +117,9 @@ struct Flags {
     bool observer = false;
     const char *observer_mask = "";  // "" (the default mask), "all" or NAME[,NAME...]
     const char *compare = nullptr;
+    bool components = false;
+    long long components_lassos = 0;  // 0 none, -1 all, n the first n
+    bool components_bottom = false;
     int prefix_k = 2, time_limit = 0, shards = 1;
     const char *file = nullptr;
     const char *binary = nullptr;
@@ -538,6 +548,54 @@ static int compare_with_file(const Flags &f, const stcsp_problem *p, const uint8
     return rc;
 }
 
+// --components[=bottom|all|N]: the strongly connected components of the live automaton, which states start an infinite solution,
+// and lasso solutions; on the device (eng: a finished postprocess()) or by the host twin on `a`'s current flags (eng NULL). stderr.
+static int report_components(const Flags &f, const stcsp_problem *p, const stcsp_automaton *a, stcsp_engine *eng) {
+    stcsp_components_options co = {f.components_lassos, f.components_bottom ? STCSP_SCC_LASSO_BOTTOM : 0, 0};
+    stcsp_components_result dev;
+    stcsp_components *twin = nullptr;
+    const stcsp_components_result *r = &dev;
+    if (eng) {
+        if (stcsp_engine_components(eng, &co, &dev) != STCSP_OK) {
+            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
+            return 1;
+        }
+    } else {
+        if (stcsp_automaton_components(a, co.max_lassos, co.flags, &twin) != STCSP_OK) return 1;
+        r = stcsp_components_get(twin);
+    }
+    fprintf(stderr, "components: %lld states, %lld components, %lld cyclic, %lld accepting, %lld bottom, %lld omega-live, infinite solution: %s\n",
+            (long long)r->n_states, (long long)r->n_components, (long long)r->n_cyclic, (long long)r->n_accepting, (long long)r->n_bottom,
+            (long long)r->n_omega, r->root_omega ? "yes" : "no");
+    for (int64_t c = 0; c < r->n_components; c++) {
+        const int32_t cf = r->comp_flags[c];
+        fprintf(stderr, "components: component %lld: size %d, depth %d, flags %s%s%s%s%s\n", (long long)c, r->comp_size[c], r->comp_depth[c],
+                cf & STCSP_SCC_CYCLIC ? "C" : "", cf & STCSP_SCC_FINAL ? "F" : "", cf & STCSP_SCC_BOTTOM ? "B" : "", cf & STCSP_SCC_ACCEPTING ? "A" : "",
+                cf ? "" : "-");
+    }
+    if (r->n_lassos) {
+        fprintf(stderr, "components: #");
+        for (int v = 0; v < p->n_vars; v++)
+            if (!(p->var_names && p->var_names[v] && strncmp(p->var_names[v], "_V", 2) == 0)) fprintf(stderr, " %s", p->var_names[v]);
+        fprintf(stderr, "\n");
+    }
+    for (int64_t i = 0; i < r->n_lassos; i++) {
+        const int64_t b = r->lasso_off[i], m = b + r->lasso_stem_len[i], e = r->lasso_off[i + 1];
+        fprintf(stderr, "components: lasso of component %d: %lld + %lld steps\n", r->lasso_component[i], (long long)(m - b), (long long)(e - m));
+        for (int part = 0; part < 2; part++) {
+            fprintf(stderr, part ? "components: loop:" : "components: stem:");
+            for (int64_t t = part ? m : b; t < (part ? e : m); t++) {
+                if (t > (part ? m : b)) fprintf(stderr, ";");
+                for (int v = 0; v < p->n_vars; v++)
+                    if (!(p->var_names && p->var_names[v] && strncmp(p->var_names[v], "_V", 2) == 0)) fprintf(stderr, " %d", r->lasso_values[t * r->n_vars + v]);
+            }
+            fprintf(stderr, "\n");
+        }
+    }
+    stcsp_components_free(twin);
+    return 0;
+}
+
 // --observer: replace *a by its observer, built on the device (eng: a finished postprocess()) or by the host twin (eng NULL);
 // with --quotient, folded by the host bisimulation under the same mask
 static int observe(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, stcsp_engine *eng) {
@@ -668,6 +726,10 @@ static int run_once(const Flags &f, bool print_line, double *total) {
             fprintf(stderr, "the streams could not be inferred: draws from a count that overflows a double\n");
             return 1;
         }
+        if (f.components && report_components(f, p, a, nullptr)) {
+            fprintf(stderr, "the components could not be computed\n");
+            return 1;
+        }
         if (f.observer && observe(f, p, &a, nullptr)) {
             fprintf(stderr, "the observer could not be built\n");
             return 1;
@@ -706,6 +768,7 @@ static int run_once(const Flags &f, bool print_line, double *total) {
             fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
             return 1;
         }
+        if (f.components && report_components(f, p, a, eng)) return 1;
         if (f.observer && observe(f, p, &a, eng)) {
             fprintf(stderr, "the observer could not be built\n");
             return 1;
@@ -835,6 +898,10 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
         fprintf(stderr, "the streams could not be inferred: draws from a count that overflows a double\n");
         return 1;
     }
+    if (f.components && report_components(f, p, a, nullptr)) {  // (host twin likewise)
+        fprintf(stderr, "the components could not be computed\n");
+        return 1;
+    }
     if (f.observer && observe(f, p, &a, nullptr)) {  // (host twin likewise)
         fprintf(stderr, "the observer could not be built\n");
         return 1;
@@ -880,6 +947,18 @@ int main(int argc, char **argv) {
         if (strcmp(a, "--observer") == 0 || strncmp(a, "--observer=", 11) == 0) {
             f.observer = true;
             f.observer_mask = a[10] == '=' ? a + 11 : "";
+            continue;
+        }
+        if (strcmp(a, "--components") == 0 || strncmp(a, "--components=", 13) == 0) {
+            const char *arg = a[12] == '=' ? a + 13 : "";
+            f.components = true;
+            f.components_bottom = strcmp(arg, "bottom") == 0;
+            f.components_lassos = !*arg ? 0 : (f.components_bottom || strcmp(arg, "all") == 0) ? -1 : atoll(arg);
+            if (*arg && f.components_lassos == 0) f.components_lassos = -2;
+            if (f.components_lassos < -1) {
+                fprintf(stderr, "--components takes nothing, bottom, all or a positive count\n");
+                return 1;
+            }
             continue;
         }
         if (strncmp(a, "--compare=", 10) == 0) {
