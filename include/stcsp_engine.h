@@ -787,6 +787,90 @@ typedef struct stcsp_components_result {
 
 int stcsp_engine_components(stcsp_engine *engine, const stcsp_components_options *options, stcsp_components_result *result);
 
+/* ---- optimal solution streams on the device: least cost per length, least mean (no reference counterpart) -----------
+ * Which solution is BEST under an objective: a linear integer cost over the values on an edge,
+ *   c(e) = sum over the variables v of weights[v] * edge_values[e][v]        (int64),
+ * minimised exactly in two ways over the live automaton.
+ *
+ * Live automaton, flags and validity are those of stcsp_engine_quotient() and stcsp_engine_components(): the flags of the
+ * last stcsp_engine_postprocess(); STCSP_E_STATE before it and after a truncated solve; STCSP_E_UNSUPPORTED on sharded
+ * engines (run stcsp_automaton_optimise() of stcsp_host.h on the merged automaton). The call keeps its own buffers and
+ * leaves the monitor, generator, repair, inference, observer and compare operand valid. With STCSP_OPT_MEAN it runs the
+ * component pass of stcsp_engine_components() itself (no lassos): the result pointers of an earlier
+ * stcsp_engine_components() call are then no longer valid. It invalidates nothing else. Results are owned by the engine
+ * until the next call on it.
+ *
+ * Request. weights[n_vars]: one int32 per variable of the full label row (callers give the auxiliary variables 0; the
+ * engine does not care). horizon >= 0. lengths[n_lengths]: the lengths for which a witness is wanted, each in 0 .. horizon.
+ * STCSP_OPT_MAXIMISE is done on the host: the weights are negated, the kernels minimise, and every reported cost and
+ * numerator is negated again. With cmax = sum of |weights[v]| * max(|lb[v]|, |ub[v]|): cmax * max(horizon, 1) > 2^62 is
+ * STCSP_E_INVALID, as are horizon < 0, a length outside 0 .. horizon, n_lengths < 0 and a null weights.
+ *
+ * Finite horizon. best[L], L = 0 .. horizon: the least sum of c(e) over the paths of L live edges from the root; with
+ * STCSP_OPT_END_FINAL over those that end in a final state. STCSP_OPT_NONE (INT64_MAX, also under MAXIMISE) where there
+ * is no such path; best[0] is 0, or NONE under END_FINAL with a root that is not final. No live root: NONE everywhere, no
+ * error. With STCSP_OPT_STATE_BEST, state_best[s] is the same quantity for L = horizon from every live state s, NONE
+ * outside the live automaton (NULL without the flag).
+ * Witness i belongs to lengths[i] and is the rows [witness_off[i], witness_off[i + 1]) of witness_values (full label rows,
+ * n_vars values each); witness_states holds, row by row, the state the step enters (every walk starts at the root, state
+ * 0). It is empty when best[lengths[i]] is NONE. The walk: with k steps left in state s (V_k = the least cost of k steps
+ * from a state), take the live out-edge with the least full row among those with c(e) + V_{k-1}[dst] == V_k[s]. The live
+ * automaton is deterministic under full rows, so the witness is the lexicographically least prefix that attains
+ * best[L]; two equal rows among the candidates of one step give STCSP_E_INTERNAL.
+ *
+ * Long run (STCSP_OPT_MEAN). n_components and state_component exactly as stcsp_engine_components() numbers them.
+ * comp_mean_num[c] / comp_mean_den[c]: the minimum cycle mean (Karp) of component c over the live edges with both ends in
+ * c, a reduced fraction with den > 0; num == den == 0 for a component that is not STCSP_SCC_CYCLIC. omega_mean_num /
+ * omega_mean_den and omega_component: the least mean over the STCSP_SCC_ACCEPTING components, ties to the least component
+ * number; den == 0 and component -1 when the model has no infinite solution. This is the INFIMUM of the long-run mean
+ * cost over the infinite solutions: a lasso attains it only if a least-mean cycle passes a final state, which is always
+ * so in a model without `until` constraints (every state is final there). The rational comparisons cross-multiply in
+ * int64: with nmax the size of the largest cyclic component, nmax^2 * cmax > 2^62 is STCSP_E_UNSUPPORTED with a message
+ * that names both numbers. Without the flag n_components is 0 and the omega fields are 0, 0, -1.
+ *
+ * Memory: two rows of n_states int64 without witnesses, horizon + 1 with them, besides the live edges (20 B each) and,
+ * with MEAN, 44 B per state. All of it is counted against a byte budget (the environment's STCSP_OPTIMISE_BYTES, else half
+ * of the free device memory): beyond it STCSP_E_NOMEM with a message that names the limit and the need, never a partial
+ * result. */
+#define STCSP_OPT_MAXIMISE 1
+#define STCSP_OPT_END_FINAL 2
+#define STCSP_OPT_MEAN 4
+#define STCSP_OPT_STATE_BEST 8
+#define STCSP_OPT_NONE INT64_MAX
+
+typedef struct stcsp_optimise_request {
+    const int32_t *weights; /* [n_vars]                                 */
+    const int32_t *lengths; /* [n_lengths], each in 0 .. horizon        */
+    int32_t horizon;
+    int32_t n_lengths;
+    int32_t flags; /* STCSP_OPT_*                                       */
+    int32_t reserved;
+} stcsp_optimise_request;
+
+typedef struct stcsp_optimise_result {
+    int64_t n_states;              /* live states                                                                       */
+    const int64_t *best;           /* [horizon + 1]                                                                     */
+    const int64_t *state_best;     /* [stcsp_result::n_states] with STCSP_OPT_STATE_BEST, else NULL                     */
+    int64_t n_witnesses;           /* == n_lengths                                                                      */
+    const int64_t *witness_off;    /* [n_witnesses + 1] in rows                                                         */
+    const int32_t *witness_values; /* [witness_off[n_witnesses] * n_vars]                                               */
+    const int32_t *witness_states; /* [witness_off[n_witnesses]] the state every step enters                            */
+    int64_t n_components;          /* with STCSP_OPT_MEAN, else 0                                                       */
+    const int32_t *state_component; /* [stcsp_result::n_states] with STCSP_OPT_MEAN, else NULL                          */
+    const int64_t *comp_mean_num;  /* [n_components]                                                                    */
+    const int64_t *comp_mean_den;  /* [n_components]                                                                    */
+    int64_t omega_mean_num, omega_mean_den;
+    int32_t omega_component;
+    int32_t n_vars;
+    int32_t horizon;
+    int32_t largest_cyclic; /* nmax: the size of the largest cyclic component (0 without STCSP_OPT_MEAN)                */
+    int32_t rounds[2];      /* launches of the finite-horizon kernels, of the Karp kernels (0 on the host twin)         */
+    double seconds;         /* wall time from the flags in HBM to the result on the host                                */
+    double seconds_kernels; /* HIP-event time of the launches (0 on the host twin)                                      */
+} stcsp_optimise_result;
+
+int stcsp_engine_optimise(stcsp_engine *engine, const stcsp_optimise_request *request, stcsp_optimise_result *result);
+
 void stcsp_engine_destroy(stcsp_engine *engine);
 
 /* Message of the last error on this engine (or of the last failed create when engine==NULL). */

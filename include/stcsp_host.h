@@ -209,6 +209,18 @@ int stcsp_automaton_components(const stcsp_automaton *a, int64_t max_lassos, int
 const stcsp_components_result *stcsp_components_get(const stcsp_components *c);
 void stcsp_components_free(stcsp_components *c);
 
+/* ---- optimal solution streams: least cost per length, least mean (definition: stcsp_engine.h, stcsp_engine_optimise) ----
+ * The same contract written plainly, on the automaton's current flags: the same dynamic programme, the same greedy walk,
+ * and a textbook Karp per component with the full table of (size + 1) * size int64 (STCSP_E_NOMEM when that cannot be
+ * allocated). The checker of the device pass in the tests, and the path for automata whose flags live on the host (merged
+ * sharded runs, host adversarial passes, read_binary, import_flags). The variables' bounds are the automaton's. Errors as
+ * there, without a message. The result (stcsp_optimise_get(): rounds and seconds_kernels are 0) lives until
+ * stcsp_optimise_free(). */
+typedef struct stcsp_optimise stcsp_optimise;
+int stcsp_automaton_optimise(const stcsp_automaton *a, const stcsp_optimise_request *request, stcsp_optimise **out);
+const stcsp_optimise_result *stcsp_optimise_get(const stcsp_optimise *o);
+void stcsp_optimise_free(stcsp_optimise *o);
+
 /* Merge the per-shard results of a sharded run (global state ids, see stcsp_engine.h) into
  * one result with dense ids; runs the ok-fixpoint over the union. The merged result is owned
  * by the returned handle. */

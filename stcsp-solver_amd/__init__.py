@@ -373,6 +373,68 @@ def _components_unpack(res, n_states):
     return d
 
 
+class OptimiseRequest(C.Structure):
+    _fields_ = [("weights", C.POINTER(C.c_int32)), ("lengths", C.POINTER(C.c_int32)), ("horizon", C.c_int32), ("n_lengths", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OptimiseResult(C.Structure):
+    _fields_ = [("n_states", C.c_int64), ("best", C.POINTER(C.c_int64)), ("state_best", C.POINTER(C.c_int64)), ("n_witnesses", C.c_int64),
+                ("witness_off", C.POINTER(C.c_int64)), ("witness_values", C.POINTER(C.c_int32)), ("witness_states", C.POINTER(C.c_int32)),
+                ("n_components", C.c_int64), ("state_component", C.POINTER(C.c_int32)), ("comp_mean_num", C.POINTER(C.c_int64)),
+                ("comp_mean_den", C.POINTER(C.c_int64)), ("omega_mean_num", C.c_int64), ("omega_mean_den", C.c_int64),
+                ("omega_component", C.c_int32), ("n_vars", C.c_int32), ("horizon", C.c_int32), ("largest_cyclic", C.c_int32),
+                ("rounds", C.c_int32 * 2), ("seconds", C.c_double), ("seconds_kernels", C.c_double)]
+
+
+OPT_MAXIMISE, OPT_END_FINAL, OPT_MEAN, OPT_STATE_BEST = 1, 2, 4, 8  # OptimiseRequest.flags
+OPT_NONE = 2**63 - 1                                                # best / state_best: no such path
+
+
+def _optimise_request(weights, names, horizon, lengths, maximise, end_final, mean, state_best):
+    """(OptimiseRequest, the arrays it points into). weights: a dict name -> int (the other variables 0) or one int per variable."""
+    import numpy as np
+    if isinstance(weights, dict):
+        unknown = sorted(set(weights) - set(names))
+        if unknown:
+            raise ValueError(f"no variable named {unknown[0]!r}")
+        weights = [weights.get(n, 0) for n in names]
+    w = np.ascontiguousarray(weights, dtype=np.int32)
+    if w.shape != (len(names),):
+        raise ValueError(f"weights must have one entry per variable ({len(names)})")
+    ln = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+    rq = OptimiseRequest(w.ctypes.data_as(C.POINTER(C.c_int32)), ln.ctypes.data_as(C.POINTER(C.c_int32)) if ln.size else None, horizon, ln.size,
+                         (OPT_MAXIMISE if maximise else 0) | (OPT_END_FINAL if end_final else 0) | (OPT_MEAN if mean else 0) |
+                         (OPT_STATE_BEST if state_best else 0), 0)
+    return rq, (w, ln)
+
+
+def _optimise_unpack(res, lengths, n_states):
+    """An OptimiseResult -> dict: n_states, n_components, n_vars, horizon, largest_cyclic, seconds, seconds_kernels; rounds int32 [2];
+    best int64 [horizon + 1] (OPT_NONE = no such prefix); state_best int64 [n_states of the Result] or None; "witnesses": a list of
+    (length, rows int32 [steps, n_vars], states int32 [steps]: the state every step enters), empty arrays where best[length] is
+    OPT_NONE; with mean: state_component int32 [n_states of the Result], "comp_mean": a list of (num, den) per component ((0, 0) when it
+    is not cyclic), "omega_mean": (num, den) ((0, 0): no infinite solution) and omega_component; else None, [], (0, 0) and -1."""
+    import numpy as np
+
+    def arr(ptr, n, dtype):
+        return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dtype)
+    d = {k: getattr(res, k) for k in ("n_states", "n_components", "n_vars", "horizon", "largest_cyclic", "omega_component", "seconds", "seconds_kernels")}
+    d["rounds"] = np.array(res.rounds[:], np.int32)
+    d["best"] = arr(res.best, res.horizon + 1, np.int64)
+    d["state_best"] = arr(res.state_best, n_states, np.int64) if res.state_best else None
+    nw, nv = res.n_witnesses, res.n_vars
+    off = arr(res.witness_off, nw + 1, np.int64) if nw else np.zeros(1, np.int64)
+    values = arr(res.witness_values, int(off[-1]) * nv, np.int32).reshape(int(off[-1]), nv)
+    states = arr(res.witness_states, int(off[-1]), np.int32)
+    d["witnesses"] = [(int(lengths[i]), values[off[i]:off[i + 1]].copy(), states[off[i]:off[i + 1]].copy()) for i in range(nw)]
+    d["state_component"] = arr(res.state_component, n_states, np.int32) if res.state_component else None
+    num, den = arr(res.comp_mean_num, res.n_components, np.int64), arr(res.comp_mean_den, res.n_components, np.int64)
+    d["comp_mean"] = [(int(p), int(q)) for p, q in zip(num, den)]
+    d["omega_mean"] = (int(res.omega_mean_num), int(res.omega_mean_den))
+    return d
+
+
 F_KEEP_RAW_EDGES = 1
 F_NO_EXPORT = 2
 F_PROFILE = 4
@@ -389,7 +451,7 @@ ENGINE_SYMBOLS = [
     "stcsp_engine_adopt", "stcsp_engine_expand_variant", "stcsp_engine_quotient",
     "stcsp_engine_monitor_build", "stcsp_engine_monitor_check", "stcsp_engine_generator_build", "stcsp_engine_generate",
     "stcsp_engine_repair", "stcsp_engine_infer", "stcsp_engine_observer", "stcsp_engine_compare",
-    "stcsp_engine_components",
+    "stcsp_engine_components", "stcsp_engine_optimise",
 ]
 # include/stcsp_sharded.h: the superstep loop + in-process transport (libstcsp_hip.so), the RCCL transport (libstcsp_rccl.so)
 SHARDED_SYMBOLS_HIP = ["stcsp_engine_solve_sharded", "stcsp_local_group_create", "stcsp_local_group_transport", "stcsp_local_group_destroy"]
@@ -409,6 +471,7 @@ HOST_SYMBOLS = [
     "stcsp_automaton_observer", "stcsp_observer_get", "stcsp_observer_free", "stcsp_automaton_from_observer",
     "stcsp_compare_observers", "stcsp_comparison_get", "stcsp_comparison_free", "stcsp_automaton_num_vars", "stcsp_automaton_var_name",
     "stcsp_automaton_components", "stcsp_components_get", "stcsp_components_free",
+    "stcsp_automaton_optimise", "stcsp_optimise_get", "stcsp_optimise_free",
 ]
 
 
@@ -503,6 +566,10 @@ def host_lib() -> C.CDLL:
         lib.stcsp_components_get.argtypes = [C.c_void_p]
         lib.stcsp_components_get.restype = C.POINTER(ComponentsResult)
         lib.stcsp_components_free.argtypes = [C.c_void_p]
+        lib.stcsp_automaton_optimise.argtypes = [C.c_void_p, C.POINTER(OptimiseRequest), C.POINTER(C.c_void_p)]
+        lib.stcsp_optimise_get.argtypes = [C.c_void_p]
+        lib.stcsp_optimise_get.restype = C.POINTER(OptimiseResult)
+        lib.stcsp_optimise_free.argtypes = [C.c_void_p]
         lib.stcsp_automaton_num_vars.argtypes = [C.c_void_p]
         lib.stcsp_automaton_var_name.argtypes = [C.c_void_p, C.c_int]
         lib.stcsp_automaton_var_name.restype = C.c_char_p
@@ -567,6 +634,8 @@ def bind_engine_api(lib: C.CDLL, prefix: str = "stcsp_engine") -> None:
         g("compare").argtypes = [C.c_void_p, C.POINTER(CompareRequest), C.POINTER(CompareResult)]
     if hasattr(lib, f"{prefix}_components"):
         g("components").argtypes = [C.c_void_p, C.POINTER(ComponentsOptions), C.POINTER(ComponentsResult)]
+    if hasattr(lib, f"{prefix}_optimise"):
+        g("optimise").argtypes = [C.c_void_p, C.POINTER(OptimiseRequest), C.POINTER(OptimiseResult)]
     if hasattr(lib, f"{prefix}_propagate"):
         g("propagate").argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64)]
@@ -912,6 +981,25 @@ class Automaton:
             return _components_unpack(lib.stcsp_components_get(h).contents, int(lib.stcsp_automaton_num_states(self._h)))
         finally:
             lib.stcsp_components_free(h)
+
+    def optimise(self, weights, horizon=0, lengths=(), maximise=False, end_final=False, mean=False, state_best=False):
+        """The best solution prefixes and the least long-run mean cost under a linear objective by the host twin of Engine.optimise()
+        (contract: include/stcsp_engine.h, stcsp_engine_optimise), on the automaton's current flags. Arguments as there. Returns the
+        dict of _optimise_unpack()."""
+        lib = host_lib()
+        names = [lib.stcsp_automaton_var_name(self._h, i).decode() for i in range(lib.stcsp_automaton_num_vars(self._h))]
+        rq, keep = _optimise_request(weights, names, horizon, lengths, maximise, end_final, mean, state_best)
+        h = C.c_void_p()
+        rc = lib.stcsp_automaton_optimise(self._h, C.byref(rq), C.byref(h))
+        if rc != 0:
+            raise StcspError(rc, {-1: "optimise failed: a negative horizon, a length outside 0 .. horizon, or costs beyond 2^62",
+                                  -2: "optimise failed: nmax^2 * cmax exceeds 2^62 (the largest cyclic component, the largest edge cost)",
+                                  -4: "optimise failed: no memory for the tables",
+                                  -5: "optimise failed: two live out-edges of one state carry the same full row"}.get(rc, "optimise failed"))
+        try:
+            return _optimise_unpack(lib.stcsp_optimise_get(h).contents, keep[1], int(lib.stcsp_automaton_num_states(self._h)))
+        finally:
+            lib.stcsp_optimise_free(h)
 
     def from_observer(self, obs, observable=None) -> "Automaton":
         """The observer `obs` (the dict of Engine.observer() or observer() for this automaton under `observable`) as an
@@ -1283,6 +1371,20 @@ class EngineBase:
         out = ComponentsResult()
         self._check(self._f("components")(self._h, C.byref(co), C.byref(out)))
         return _components_unpack(out, self.result.n_states)
+
+    def optimise(self, weights, horizon=0, lengths=(), maximise=False, end_final=False, mean=False, state_best=False):
+        """Which solution is best, on the device, after postprocess(). The cost of a step is sum_v weights[v] * value of v on the edge;
+        weights is a dict name -> int (the other variables 0) or one int per variable. Finite horizon: best[L], L = 0 .. horizon, the
+        least (maximise: the greatest) total cost of a solution prefix of L steps (end_final: that ends in a final state), OPT_NONE
+        where there is none; for every L in `lengths` the lexicographically least prefix that attains it; state_best: the same for
+        L = horizon from every live state. mean: per strongly connected component (numbered as components() numbers them) the least
+        mean cost per step of a cycle in it, as an exact fraction, and the least over the accepting components, which is the infimum
+        of the long-run mean cost of an infinite solution. Returns the dict of _optimise_unpack(); it touches no other service's state
+        but, with mean, the result of an earlier components(). Contract: include/stcsp_engine.h, stcsp_engine_optimise."""
+        rq, keep = _optimise_request(weights, self._model.var_names, horizon, lengths, maximise, end_final, mean, state_best)
+        out = OptimiseResult()
+        self._check(self._f("optimise")(self._h, C.byref(rq), C.byref(out)))
+        return _optimise_unpack(out, keep[1], self.result.n_states)
 
     def automaton(self, result: Result | None = None) -> Automaton:
         return Automaton(self._model, result if result is not None else self.result)

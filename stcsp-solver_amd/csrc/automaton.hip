@@ -20,6 +20,7 @@
 #include "dev_observer.hpp"
 #include "dev_compare.hpp"
 #include "dev_components.hpp"
+#include "dev_optimise.hpp"
 #include "repair_host.hpp"
 #include "infer_host.hpp"
 
@@ -1789,6 +1790,289 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
     out->rounds[0] = trim_rounds;
     out->rounds[1] = colour_rounds;
     out->rounds[2] = sweeps;
+    out->seconds_kernels = ms_kernels * 1e-3;
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return STCSP_OK;
+}
+
+// Optimal solution streams: the least cost of a solution prefix per length with its lexicographically least witness, and the
+// minimum cycle mean of every cyclic component (contract: stcsp_engine.h; dev_optimise.hpp). Every
+// device buffer is this call's own; with STCSP_OPT_MEAN the component pass above runs first and its result is replaced.
+int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_request *rq, stcsp_optimise_result *out) {
+    if (int rc = enter(view, "optimise", NEED_FLAGS, "stcsp_automaton_optimise")) return rc;
+    auto t0 = std::chrono::steady_clock::now();
+    const int N = v.N;
+    const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
+    const int32_t horizon = rq->horizon, n_len = rq->n_lengths, flags = rq->flags;
+    if (!rq->weights) return fail(STCSP_E_INVALID, "optimise: weights is null");
+    if (horizon < 0) return fail(STCSP_E_INVALID, "optimise: horizon %d is negative", horizon);
+    if (n_len < 0 || (n_len > 0 && !rq->lengths)) return fail(STCSP_E_INVALID, "optimise: n_lengths = %d without that many lengths", n_len);
+    for (int32_t i = 0; i < n_len; i++)
+        if (rq->lengths[i] < 0 || rq->lengths[i] > horizon)
+            return fail(STCSP_E_INVALID, "optimise: lengths[%d] = %d is outside 0 .. horizon = %d", i, rq->lengths[i], horizon);
+    const __int128 kLimit = (__int128)1 << 62;
+    __int128 cmax = 0;
+    for (int x = 0; x < N; x++)
+        cmax += (__int128)std::llabs((long long)rq->weights[x]) * std::max(std::llabs((long long)v.lb[x]), std::llabs((long long)v.ub[x]));
+    if (cmax * std::max(horizon, 1) > kLimit)
+        return fail(STCSP_E_INVALID, "optimise: the largest edge cost %.0f times the horizon %d exceeds 2^62", (double)cmax, horizon);
+    if (v.exp_edges > 0x7fffffffull || S > 0x3fffffffu) return fail(STCSP_E_NOMEM, "automaton too large for the device optimisation pass");
+    if (int rc = live_set()) return rc;
+    const bool maximise = flags & STCSP_OPT_MAXIMISE, mean = flags & STCSP_OPT_MEAN, witnesses = n_len > 0;
+    const int end_final = (flags & STCSP_OPT_END_FINAL) ? 1 : 0;
+    // the components first: their call takes the view again
+    uint32_t nmax = 0, n_comp = 0;
+    std::vector<uint32_t> n_of, comp_of, least;
+    if (mean) {
+        const stcsp_components_options co = {0, 0, 0};
+        stcsp_components_result cres;
+        if (int rc = components(view, &co, &cres)) return rc;
+        n_comp = (uint32_t)s_size.size();
+        n_of.assign(S, 0);
+        comp_of.assign(S, kOptIdxNone);
+        least.assign(n_comp, kOptIdxNone);
+        for (uint32_t s = 0; s < S; s++) {
+            const int32_t c = s_component[s];
+            if (c < 0) continue;
+            comp_of[s] = (uint32_t)c;
+            if (least[c] == kOptIdxNone) least[c] = s;
+            if (s_flags[c] & STCSP_SCC_CYCLIC) {
+                n_of[s] = (uint32_t)s_size[c];
+                nmax = std::max(nmax, n_of[s]);
+            }
+        }
+        if ((__int128)nmax * nmax * cmax > kLimit)
+            return fail(STCSP_E_UNSUPPORTED, "optimise: the largest cyclic component has nmax = %u states and the largest edge cost is cmax = %.0f; nmax^2 * cmax exceeds 2^62, the range of the exact comparisons",
+                        nmax, (double)cmax);
+    }
+    size_t budget = 0;
+    if (int rc = table_budget("STCSP_OPTIMISE_BYTES", budget)) return rc;
+    const size_t n_rows = witnesses ? (size_t)horizon + 1 : 2;
+    const size_t row_bytes = n_rows * (size_t)S * sizeof(long long);
+    if (row_bytes > budget)
+        return fail(STCSP_E_NOMEM, "optimise: %zu value rows of %u states need %zu bytes, the budget (STCSP_OPTIMISE_BYTES) is %zu", n_rows, S, row_bytes, budget);
+    opt_best.assign((size_t)horizon + 1, kOptNone);
+    opt_state_best.clear();
+    opt_woff.assign((size_t)n_len + 1, 0);
+    opt_wvalues.clear();
+    opt_wstates.clear();
+    opt_component.clear();
+    opt_num.assign(n_comp, 0);
+    opt_den.assign(n_comp, 0);
+    HIPCHK(reserve_all(S, 1, d_opt_deg, d_opt_off, d_opt_cur));
+    HIPCHK(d_opt_ctl.reserve_exact(OPT_WORDS));
+    HIPCHK(d_opt_w.reserve_exact((size_t)std::max(N, 1)));
+    HIPCHK(d_opt_best.reserve((size_t)horizon + 1));
+    HIPCHK(ev.ready(2));
+    const unsigned sb = (S + 255) / 256, eb = (E + 255) / 256;
+    uint32_t ctl[OPT_WORDS] = {0, 0, 0, 0};
+    double ms_kernels = 0;
+    bool open = false;
+    int32_t launches_dp = 0, launches_karp = 0;
+    auto begin = [&]() -> int {
+        if (!open) HIPCHK(hipEventRecord(ev[0], v.stream));
+        open = true;
+        return STCSP_OK;
+    };
+    auto flush = [&]() -> int {  // ends a batch of launches: the error words, and the batch's time on the device
+        if (int rc = begin()) return rc;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev[1], v.stream));
+        HIPCHK(hipMemcpyAsync(ctl, d_opt_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        ms_kernels += ms;
+        open = false;
+        return STCSP_OK;
+    };
+    std::vector<int32_t> w(rq->weights, rq->weights + N);
+    for (int x = 0; x < N && maximise; x++) {
+        if (w[x] == INT32_MIN) return fail(STCSP_E_INVALID, "optimise: weights[%d] = INT32_MIN cannot be negated to maximise", x);
+        w[x] = -w[x];
+    }
+    // the live edges as CSR by source, in this call's buffers
+    uint32_t L = 0;
+    if (S) {
+        if (int rc = begin()) return rc;
+        HIPCHK(hipMemsetAsync(d_opt_ctl.p, 0, sizeof ctl, v.stream));
+        HIPCHK(hipMemsetAsync(d_opt_deg.p, 0, (size_t)S * sizeof(uint32_t), v.stream));
+        if (N) HIPCHK(hipMemcpyAsync(d_opt_w.p, w.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+        if (E)
+            hipLaunchKernelGGL(k_s_count, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)d_palive.p, (const uint8_t *)d_live.p,
+                               d_opt_deg.p);
+        hipLaunchKernelGGL(k_s_scan, dim3(1), dim3(256), 0, v.stream, S, (S + 255) / 256, (const uint32_t *)d_opt_deg.p, d_opt_off.p, d_opt_cur.p);
+        HIPCHK(hipMemcpyAsync(&L, d_opt_off.p + S, sizeof L, hipMemcpyDeviceToHost, v.stream));
+        if (int rc = flush()) return rc;
+        if (L > E) return fail(STCSP_E_INTERNAL, "optimise: %u live edges of %u", L, E);
+    }
+    const size_t need = row_bytes + 3 * ((size_t)S + 1) * sizeof(uint32_t) + (size_t)L * (3 * sizeof(uint32_t) + sizeof(long long)) +
+                        ((size_t)horizon + 1) * sizeof(long long) +
+                        (mean ? (size_t)S * (3 * sizeof(uint32_t) + 4 * sizeof(long long)) + 2 * (size_t)n_comp * sizeof(uint32_t) : 0);
+    if (need > budget)
+        return fail(STCSP_E_NOMEM, "optimise: %zu value rows of %u states, %u live edges%s need %zu bytes, the budget (STCSP_OPTIMISE_BYTES) is %zu", n_rows, S, L,
+                    mean ? " and the cycle-mean tables" : "", need, budget);
+    if (!d_opt_rows.reserve_or_release(n_rows * (size_t)S)) return fail(STCSP_E_NOMEM, "optimise: no room for %zu bytes of value rows", row_bytes);
+    HIPCHK(reserve_all(L, 1, d_opt_src, d_opt_dst, d_opt_eid));
+    HIPCHK(d_opt_cost.reserve(L, 1));
+    const unsigned lb = (L + 255) / 256;
+    const uint32_t *csrc = d_opt_src.p, *cdst = d_opt_dst.p;
+    if (S) {
+        // finite horizon: V_0, then a relaxation and a clearing launch per level
+        auto row = [&](int32_t k) { return d_opt_rows.p + (size_t)(witnesses ? k : k % 2) * S; };
+        auto next_row = [&](int32_t k) { return k + 1 <= horizon ? row(k + 1) : (long long *)nullptr; };
+        if (int rc = begin()) return rc;
+        if (L) {
+            hipLaunchKernelGGL(k_s_fill, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)d_palive.p, (const uint8_t *)d_live.p,
+                               d_opt_cur.p, L, d_opt_src.p, d_opt_dst.p, d_opt_eid.p);
+            hipLaunchKernelGGL(k_opt_cost, dim3(lb), dim3(256), 0, v.stream, L, N, (const uint32_t *)d_opt_eid.p, v.d_oval, (const int32_t *)d_opt_w.p, d_opt_cost.p);
+        }
+        hipLaunchKernelGGL(k_opt_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint8_t *)d_pfinal.p, end_final, row(0));
+        hipLaunchKernelGGL(k_opt_clear, dim3(sb), dim3(256), 0, v.stream, S, next_row(0), (const long long *)row(0), d_opt_best.p);
+        launches_dp += 2;
+        for (int32_t k = 1; k <= horizon; k++, launches_dp += 2) {
+            if (L)
+                hipLaunchKernelGGL(k_opt_relax_back, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, (const long long *)d_opt_cost.p,
+                                   (const long long *)row(k - 1), row(k));
+            hipLaunchKernelGGL(k_opt_clear, dim3(sb), dim3(256), 0, v.stream, S, next_row(k), (const long long *)row(k), d_opt_best.p + k);
+        }
+        HIPCHK(hipMemcpyAsync(opt_best.data(), d_opt_best.p, ((size_t)horizon + 1) * sizeof(long long), hipMemcpyDeviceToHost, v.stream));
+        if (flags & STCSP_OPT_STATE_BEST) {
+            opt_state_best.resize(S);
+            HIPCHK(hipMemcpyAsync(opt_state_best.data(), row(horizon), (size_t)S * sizeof(long long), hipMemcpyDeviceToHost, v.stream));
+        }
+        if (int rc = flush()) return rc;
+        // witnesses: one wavefront per requested length walks the rows; the host gathers the label rows from the pinned export
+        for (int32_t i = 0; i < n_len; i++) opt_woff[(size_t)i + 1] = opt_woff[i] + (opt_best[rq->lengths[i]] == kOptNone ? 0 : rq->lengths[i]);
+        const size_t T = (size_t)opt_woff[n_len];
+        if (T) {
+            std::vector<uint32_t> weid(T);
+            opt_wstates.resize(T);
+            HIPCHK(d_opt_len.reserve((size_t)n_len));
+            HIPCHK(d_opt_woff.reserve((size_t)n_len + 1));
+            HIPCHK(reserve_all(T, 0, d_opt_weid, d_opt_wstate));
+            if (int rc = begin()) return rc;
+            HIPCHK(hipMemcpyAsync(d_opt_len.p, rq->lengths, (size_t)n_len * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+            HIPCHK(hipMemcpyAsync(d_opt_woff.p, opt_woff.data(), ((size_t)n_len + 1) * sizeof(long long), hipMemcpyHostToDevice, v.stream));
+            hipLaunchKernelGGL(k_opt_walk, dim3((unsigned)n_len), dim3(64), 0, v.stream, S, N, (int)n_len, (const int32_t *)d_opt_len.p, (const long long *)d_opt_woff.p,
+                               (const long long *)d_opt_rows.p, (const uint32_t *)d_opt_off.p, cdst, (const uint32_t *)d_opt_eid.p, (const long long *)d_opt_cost.p,
+                               v.d_oval, d_opt_weid.p, d_opt_wstate.p, d_opt_ctl.p);
+            launches_dp++;
+            HIPCHK(hipMemcpyAsync(weid.data(), d_opt_weid.p, T * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(opt_wstates.data(), d_opt_wstate.p, T * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+            if (int rc = flush()) return rc;
+            if (ctl[OPT_DUPLICATE]) return fail(STCSP_E_INTERNAL, "optimise: two live out-edges of state %u carry the same full row", ctl[OPT_DUPLICATE] - 1);
+            if (ctl[OPT_STUCK]) return fail(STCSP_E_INTERNAL, "optimise: the walk stops at state %u", ctl[OPT_STUCK] - 1);
+            opt_wvalues.resize(T * (size_t)N);
+            for (size_t t = 0; t < T; t++) {
+                if (weid[t] >= E) return fail(STCSP_E_INTERNAL, "optimise: the walk names edge %u of %u", weid[t], E);
+                std::copy(v.h_oval + (size_t)weid[t] * N, v.h_oval + ((size_t)weid[t] + 1) * N, opt_wvalues.begin() + t * (size_t)N);
+            }
+        }
+    }
+    // long run: Karp's minimum cycle mean of every cyclic component in two passes over two rows
+    int64_t omega_num = 0, omega_den = 0;
+    int32_t omega_comp = -1;
+    if (mean) {
+        opt_component = s_component;
+        if (nmax) {
+            std::vector<long long> num(S);
+            std::vector<uint32_t> den(S), arg(n_comp);
+            HIPCHK(reserve_all(S, 0, d_opt_nof, d_opt_comp, d_opt_den));
+            HIPCHK(reserve_all(n_comp, 0, d_opt_least, d_opt_arg));
+            HIPCHK(reserve_all(S, 0, d_opt_dn, d_opt_num));
+            HIPCHK(d_opt_d.reserve(2 * (size_t)S));
+            long long *d[2] = {d_opt_d.p, d_opt_d.p + S};
+            if (int rc = begin()) return rc;
+            HIPCHK(hipMemcpyAsync(d_opt_nof.p, n_of.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+            HIPCHK(hipMemcpyAsync(d_opt_comp.p, comp_of.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+            HIPCHK(hipMemcpyAsync(d_opt_least.p, least.data(), (size_t)n_comp * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+            HIPCHK(hipMemsetAsync(d_opt_den.p, 0, (size_t)S * sizeof(uint32_t), v.stream));
+            HIPCHK(hipMemsetAsync(d_opt_num.p, 0, (size_t)S * sizeof(long long), v.stream));
+            HIPCHK(hipMemsetAsync(d_opt_arg.p, 0xff, (size_t)n_comp * sizeof(uint32_t), v.stream));
+            const uint32_t *nof = d_opt_nof.p, *comp = d_opt_comp.p;
+            auto fwd = [&](uint32_t k) {
+                if (L)
+                    hipLaunchKernelGGL(k_opt_karp_fwd, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, comp, (const long long *)d_opt_cost.p,
+                                       (const long long *)d[(k - 1) % 2], d[k % 2]);
+                launches_karp++;
+            };
+            // pass 1: D_n of every state, n the size of its component
+            hipLaunchKernelGGL(k_opt_karp_init, dim3(sb), dim3(256), 0, v.stream, S, nof, comp, (const uint32_t *)d_opt_least.p, d[0], d[1], d_opt_dn.p);
+            for (uint32_t k = 1; k <= nmax; k++, launches_karp++) {
+                fwd(k);
+                hipLaunchKernelGGL(k_opt_karp_keep, dim3(sb), dim3(256), 0, v.stream, S, k, nof, (const long long *)d[k % 2], d[(k - 1) % 2], d_opt_dn.p);
+            }
+            // pass 2: D_k again, level by level, and per state the greatest (D_n - D_k) / (n - k)
+            hipLaunchKernelGGL(k_opt_karp_init, dim3(sb), dim3(256), 0, v.stream, S, nof, comp, (const uint32_t *)d_opt_least.p, d[0], d[1], (long long *)nullptr);
+            for (uint32_t k = 0; k < nmax; k++, launches_karp++) {
+                if (k) fwd(k);
+                hipLaunchKernelGGL(k_opt_karp_ratio, dim3(sb), dim3(256), 0, v.stream, S, k, nof, (const long long *)d[k % 2], d[(k + 1) % 2],
+                                   (const long long *)d_opt_dn.p, d_opt_num.p, d_opt_den.p);
+            }
+            hipLaunchKernelGGL(k_opt_karp_min, dim3(sb), dim3(256), 0, v.stream, S, S, comp, (const long long *)d_opt_num.p, (const uint32_t *)d_opt_den.p,
+                               d_opt_arg.p, d_opt_ctl.p);
+            launches_karp += 3;
+            HIPCHK(hipMemcpyAsync(num.data(), d_opt_num.p, (size_t)S * sizeof(long long), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(den.data(), d_opt_den.p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(arg.data(), d_opt_arg.p, (size_t)n_comp * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+            if (int rc = flush()) return rc;
+            if (ctl[OPT_STUCK]) return fail(STCSP_E_INTERNAL, "optimise: the least mean of the component of state %u did not settle", ctl[OPT_STUCK] - 1);
+            for (uint32_t c = 0; c < n_comp; c++) {
+                if (!(s_flags[c] & STCSP_SCC_CYCLIC)) continue;
+                const uint32_t a = arg[c];
+                if (a >= S || den[a] == 0 || comp_of[a] != c) return fail(STCSP_E_INTERNAL, "optimise: cyclic component %u has no cycle mean", c);
+                long long p = num[a], q = (long long)den[a], x = std::llabs(p), y = q;
+                while (y) {
+                    const long long r = x % y;
+                    x = y;
+                    y = r;
+                }
+                opt_num[c] = p / x;
+                opt_den[c] = q / x;
+            }
+        }
+        for (uint32_t c = 0; c < n_comp; c++) {
+            if (!(s_flags[c] & STCSP_SCC_ACCEPTING)) continue;
+            if (omega_comp < 0 || (__int128)opt_num[c] * omega_den < (__int128)omega_num * opt_den[c]) {
+                omega_num = opt_num[c];
+                omega_den = opt_den[c];
+                omega_comp = (int32_t)c;
+            }
+        }
+    }
+    if (maximise) {
+        for (int64_t &x : opt_best)
+            if (x != kOptNone) x = -x;
+        for (int64_t &x : opt_state_best)
+            if (x != kOptNone) x = -x;
+        for (int64_t &x : opt_num) x = -x;
+        omega_num = -omega_num;
+    }
+    opt_wvalues.reserve(1);
+    opt_wstates.reserve(1);
+    opt_num.reserve(1);
+    opt_den.reserve(1);
+    memset(out, 0, sizeof *out);
+    out->n_states = n_live;
+    out->best = opt_best.data();
+    out->state_best = (flags & STCSP_OPT_STATE_BEST) ? opt_state_best.data() : nullptr;
+    out->n_witnesses = n_len;
+    out->witness_off = opt_woff.data();
+    out->witness_values = opt_wvalues.data();
+    out->witness_states = opt_wstates.data();
+    out->n_components = n_comp;
+    out->state_component = mean ? opt_component.data() : nullptr;
+    out->comp_mean_num = opt_num.data();
+    out->comp_mean_den = opt_den.data();
+    out->omega_mean_num = omega_num;
+    out->omega_mean_den = omega_den;
+    out->omega_component = omega_comp;
+    out->n_vars = N;
+    out->horizon = horizon;
+    out->largest_cyclic = (int32_t)nmax;
+    out->rounds[0] = launches_dp;
+    out->rounds[1] = launches_karp;
     out->seconds_kernels = ms_kernels * 1e-3;
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;

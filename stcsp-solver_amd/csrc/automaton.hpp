@@ -46,6 +46,7 @@ struct AutomatonServices {
     int observer(const AutomatonView &view, const stcsp_observer_options *oo, stcsp_observer_result *out);
     int compare(const AutomatonView &view, const stcsp_compare_request *rq, stcsp_compare_result *out);
     int components(const AutomatonView &view, const stcsp_components_options *co, stcsp_components_result *out);
+    int optimise(const AutomatonView &view, const stcsp_optimise_request *rq, stcsp_optimise_result *out);
 
 private:
     enum Need { NEED_EXPORT, NEED_FLAGS, NEED_MONITOR, NEED_GENERATOR };
@@ -153,6 +154,13 @@ private:
     std::vector<int32_t> s_component, s_size, s_depth, s_flags, s_lcomp, s_lstem, s_lvalues;
     std::vector<uint8_t> s_omega;
     std::vector<int64_t> s_loff;
+    // optimisation (dev_optimise.hpp): everything lives for one call; the vectors back the result until the next call
+    DevBuf<uint32_t> d_opt_deg, d_opt_off, d_opt_cur, d_opt_src, d_opt_dst, d_opt_eid, d_opt_weid, d_opt_wstate, d_opt_ctl;
+    DevBuf<uint32_t> d_opt_nof, d_opt_comp, d_opt_least, d_opt_den, d_opt_arg;
+    DevBuf<int32_t> d_opt_w, d_opt_len;
+    DevBuf<long long> d_opt_cost, d_opt_rows, d_opt_best, d_opt_woff, d_opt_d, d_opt_dn, d_opt_num;
+    std::vector<int64_t> opt_best, opt_state_best, opt_woff, opt_num, opt_den;
+    std::vector<int32_t> opt_wvalues, opt_wstates, opt_component;
 };
 
 }  // namespace stcsp

@@ -2411,6 +2411,10 @@ int stcsp_engine_components(stcsp_engine *e, const stcsp_components_options *opt
     if (!e || !result) return STCSP_E_INVALID;
     return e->services.components(e->view(), options, result);
 }
+int stcsp_engine_optimise(stcsp_engine *e, const stcsp_optimise_request *request, stcsp_optimise_result *result) {
+    if (!e || !request || !result) return STCSP_E_INVALID;
+    return e->services.optimise(e->view(), request, result);
+}
 
 void stcsp_engine_destroy(stcsp_engine *e) { delete e; }
 

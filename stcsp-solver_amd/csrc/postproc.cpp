@@ -27,6 +27,7 @@
 #include "repair_host.hpp"
 #include "observer_host.hpp"
 #include "components_host.hpp"
+#include "optimise_host.hpp"
 #include "compare_host.hpp"
 #include "infer_host.hpp"
 #include "okfix.hpp"
@@ -1009,6 +1010,10 @@ struct stcsp_components {
     stcsp::HostComponents c;
     stcsp_components_result res;
 };
+struct stcsp_optimise {
+    stcsp::HostOptimise o;
+    stcsp_optimise_result res;
+};
 
 extern "C" {
 
@@ -1429,6 +1434,48 @@ int stcsp_automaton_components(const stcsp_automaton *a, int64_t max_lassos, int
 }
 const stcsp_components_result *stcsp_components_get(const stcsp_components *c) { return c ? &c->res : nullptr; }
 void stcsp_components_free(stcsp_components *c) { delete c; }
+
+int stcsp_automaton_optimise(const stcsp_automaton *a, const stcsp_optimise_request *request, stcsp_optimise **out) {
+    if (!a || !request || !out) return STCSP_E_INVALID;
+    stcsp_optimise *h = nullptr;
+    try {
+        h = new stcsp_optimise();
+        const auto t0 = std::chrono::steady_clock::now();
+        if (int rc = h->o.run(generator_view(a->a), a->a.var_lb.data(), a->a.var_ub.data(), *request)) {
+            delete h;
+            return rc;
+        }
+        stcsp::HostOptimise &o = h->o;
+        for (auto *v : {&o.best, &o.state_best, &o.witness_off, &o.comp_num, &o.comp_den}) v->reserve(1);  // (empty vectors still give valid pointers)
+        for (auto *v : {&o.witness_values, &o.witness_states, &o.state_component}) v->reserve(1);
+        memset(&h->res, 0, sizeof h->res);
+        h->res.n_states = o.n_live;
+        h->res.best = o.best.data();
+        h->res.state_best = (request->flags & STCSP_OPT_STATE_BEST) ? o.state_best.data() : nullptr;
+        h->res.n_witnesses = request->n_lengths;
+        h->res.witness_off = o.witness_off.data();
+        h->res.witness_values = o.witness_values.data();
+        h->res.witness_states = o.witness_states.data();
+        h->res.n_components = (int64_t)o.comp_num.size();
+        h->res.state_component = (request->flags & STCSP_OPT_MEAN) ? o.state_component.data() : nullptr;
+        h->res.comp_mean_num = o.comp_num.data();
+        h->res.comp_mean_den = o.comp_den.data();
+        h->res.omega_mean_num = o.omega_num;
+        h->res.omega_mean_den = o.omega_den;
+        h->res.omega_component = o.omega_component;
+        h->res.n_vars = o.n_vars;
+        h->res.horizon = request->horizon;
+        h->res.largest_cyclic = o.largest_cyclic;
+        h->res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    } catch (const std::bad_alloc &) {
+        delete h;
+        return STCSP_E_NOMEM;
+    }
+    *out = h;
+    return STCSP_OK;
+}
+const stcsp_optimise_result *stcsp_optimise_get(const stcsp_optimise *o) { return o ? &o->res : nullptr; }
+void stcsp_optimise_free(stcsp_optimise *o) { delete o; }
 
 char *stcsp_automaton_canonical(const stcsp_automaton *a, size_t *len) {
     if (!a) return nullptr;

@@ -2,7 +2,7 @@
 // (src/stcsp.y:180-219 main, src/solver.cpp:195-359 solve): same flags, same stdout contract,
 // same solutions.dot. The search itself runs on the MI355X engine behind the C-ABI.
 //
-//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--observer[=all|NAME[,NAME...]] [--compare=<file>]] [--components[=bottom|all|<N>]] [--check=<file>]
+//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--observer[=all|NAME[,NAME...]] [--compare=<file>]] [--components[=bottom|all|<N>]] [--optimise=<spec>] [--check=<file>]
 //         [--sample=<N>:<L>[:<seed>] [--sample-final] [--sample-mask=all]] [--count=<L>]
 //         [--repair=<file> [--repair-final]] [--infer=<file> [--infer-final] [--infer-draws=<D>[:<seed>]]] input.csp
 //
@@ -20,6 +20,15 @@
 // bottom accepting components only) or =<N> (the first N), lasso solutions stem . loop^omega: a line "# name name ..." of the
 // variables of the default mask, then per lasso the lines "stem:" and "loop:", the rows in the format --check= reads, separated by
 // ';'. stdout and the written files are unchanged. On the device for an unsharded solve, by the host twin otherwise.
+//
+// --optimise=min|max:NAME=W[,NAME=W...][:HORIZON][:mean] (not in the reference) says which solution is best under the cost
+// sum of W * NAME per step (include/stcsp_engine.h, stcsp_engine_optimise; the variables not named weigh 0; HORIZON 0 when left
+// out). To stderr: a line "optimise: best[L] = <cost>" (or "none") for L = 0 .. HORIZON; when there is a prefix of HORIZON steps, a
+// line "optimise: # name name ..." of the variables of the default mask and a line "optimise: witness:" with the lexicographically
+// least best prefix, the rows in the format --check= reads, separated by ';'; with mean a line "optimise: component <c>: mean
+// <num>/<den>" per cyclic component and "optimise: omega: mean <num>/<den> in component <c>" (or "optimise: omega: none"), the
+// infimum of the long-run mean cost over the infinite solutions. stdout and the written files are unchanged. On the device for an
+// unsharded solve, by the host twin otherwise.
 //
 // --compare=<file> (not in the reference; only together with --observer) compares what this model shows with what another one
 // shows (include/stcsp_engine.h, stcsp_engine_compare). The file is a binary automaton written by --binary= of any run: it
@@ -120,6 +129,7 @@ struct Flags {
     bool components = false;
     long long components_lassos = 0;  // 0 none, -1 all, n the first n
     bool components_bottom = false;
+    const char *optimise = nullptr;  // the text after --optimise=
     int prefix_k = 2, time_limit = 0, shards = 1;
     const char *file = nullptr;
     const char *binary = nullptr;
@@ -596,6 +606,97 @@ static int report_components(const Flags &f, const stcsp_problem *p, const stcsp
     return 0;
 }
 
+// --optimise=min|max:NAME=W[,NAME=W...][:HORIZON][:mean]: the best prefixes and the least long-run mean; on the device (eng: a finished
+// postprocess()) or by the host twin on `a`'s current flags (eng NULL). stderr.
+static int report_optimum(const Flags &f, const stcsp_problem *p, const stcsp_automaton *a, stcsp_engine *eng) {
+    std::vector<int32_t> w((size_t)p->n_vars, 0);
+    std::string spec = f.optimise;
+    std::vector<std::string> parts;
+    for (size_t at = 0;;) {
+        const size_t colon = spec.find(':', at);
+        parts.push_back(spec.substr(at, colon == std::string::npos ? colon : colon - at));
+        if (colon == std::string::npos) break;
+        at = colon + 1;
+    }
+    const char *usage = "--optimise takes min|max:NAME=W[,NAME=W...][:HORIZON][:mean]";
+    if (parts.size() < 2 || (parts[0] != "min" && parts[0] != "max")) {
+        fprintf(stderr, "%s\n", usage);
+        return 1;
+    }
+    int32_t flags = parts[0] == "max" ? STCSP_OPT_MAXIMISE : 0, horizon = 0;
+    for (size_t at = 0; at <= parts[1].size();) {
+        const size_t comma = std::min(parts[1].find(',', at), parts[1].size());
+        const std::string item = parts[1].substr(at, comma - at);
+        const size_t eq = item.find('=');
+        int var = -1;
+        for (int v = 0; v < p->n_vars && eq != std::string::npos; v++)
+            if (p->var_names && p->var_names[v] && item.substr(0, eq) == p->var_names[v]) var = v;
+        char *end = nullptr;
+        const long long value = eq == std::string::npos ? 0 : strtoll(item.c_str() + eq + 1, &end, 10);
+        if (var < 0 || !end || *end || end == item.c_str() + eq + 1 || value < -2147483647ll || value > 2147483647ll) {
+            fprintf(stderr, "--optimise: '%s' is not NAME=W with a variable of the model and an integer\n", item.c_str());
+            return 1;
+        }
+        w[(size_t)var] = (int32_t)value;
+        at = comma + 1;
+    }
+    for (size_t i = 2; i < parts.size(); i++) {
+        char *end = nullptr;
+        const long long h = strtoll(parts[i].c_str(), &end, 10);
+        if (parts[i] == "mean" && i + 1 == parts.size())
+            flags |= STCSP_OPT_MEAN;
+        else if (i == 2 && !parts[i].empty() && !*end && h >= 0 && h <= 0x7fffffffll)
+            horizon = (int32_t)h;
+        else {
+            fprintf(stderr, "%s\n", usage);
+            return 1;
+        }
+    }
+    const stcsp_optimise_request rq = {w.data(), &horizon, horizon, 1, flags, 0};
+    stcsp_optimise_result dev;
+    stcsp_optimise *twin = nullptr;
+    const stcsp_optimise_result *r = &dev;
+    if (eng) {
+        if (stcsp_engine_optimise(eng, &rq, &dev) != STCSP_OK) {
+            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
+            return 1;
+        }
+    } else {
+        if (stcsp_automaton_optimise(a, &rq, &twin) != STCSP_OK) return 1;
+        r = stcsp_optimise_get(twin);
+    }
+    for (int32_t L = 0; L <= horizon; L++) {
+        if (r->best[L] == STCSP_OPT_NONE)
+            fprintf(stderr, "optimise: best[%d] = none\n", L);
+        else
+            fprintf(stderr, "optimise: best[%d] = %lld\n", L, (long long)r->best[L]);
+    }
+    if (r->best[horizon] != STCSP_OPT_NONE) {
+        auto shown = [&](int v) { return !(p->var_names && p->var_names[v] && strncmp(p->var_names[v], "_V", 2) == 0); };
+        fprintf(stderr, "optimise: #");
+        for (int v = 0; v < p->n_vars; v++)
+            if (shown(v)) fprintf(stderr, " %s", p->var_names[v]);
+        fprintf(stderr, "\noptimise: witness:");
+        for (int64_t t = r->witness_off[0]; t < r->witness_off[1]; t++) {
+            if (t > r->witness_off[0]) fprintf(stderr, ";");
+            for (int v = 0; v < p->n_vars; v++)
+                if (shown(v)) fprintf(stderr, " %d", r->witness_values[t * r->n_vars + v]);
+        }
+        fprintf(stderr, "\n");
+    }
+    if (flags & STCSP_OPT_MEAN) {
+        for (int64_t c = 0; c < r->n_components; c++)
+            if (r->comp_mean_den[c])
+                fprintf(stderr, "optimise: component %lld: mean %lld/%lld\n", (long long)c, (long long)r->comp_mean_num[c], (long long)r->comp_mean_den[c]);
+        if (r->omega_mean_den)
+            fprintf(stderr, "optimise: omega: mean %lld/%lld in component %d\n", (long long)r->omega_mean_num, (long long)r->omega_mean_den, r->omega_component);
+        else
+            fprintf(stderr, "optimise: omega: none\n");
+    }
+    stcsp_optimise_free(twin);
+    return 0;
+}
+
 // --observer: replace *a by its observer, built on the device (eng: a finished postprocess()) or by the host twin (eng NULL);
 // with --quotient, folded by the host bisimulation under the same mask
 static int observe(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, stcsp_engine *eng) {
@@ -730,6 +831,10 @@ static int run_once(const Flags &f, bool print_line, double *total) {
             fprintf(stderr, "the components could not be computed\n");
             return 1;
         }
+        if (f.optimise && report_optimum(f, p, a, nullptr)) {
+            fprintf(stderr, "the optimum could not be computed\n");
+            return 1;
+        }
         if (f.observer && observe(f, p, &a, nullptr)) {
             fprintf(stderr, "the observer could not be built\n");
             return 1;
@@ -769,6 +874,7 @@ static int run_once(const Flags &f, bool print_line, double *total) {
             return 1;
         }
         if (f.components && report_components(f, p, a, eng)) return 1;
+        if (f.optimise && report_optimum(f, p, a, eng)) return 1;
         if (f.observer && observe(f, p, &a, eng)) {
             fprintf(stderr, "the observer could not be built\n");
             return 1;
@@ -902,6 +1008,10 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
         fprintf(stderr, "the components could not be computed\n");
         return 1;
     }
+    if (f.optimise && report_optimum(f, p, a, nullptr)) {  // (host twin likewise)
+        fprintf(stderr, "the optimum could not be computed\n");
+        return 1;
+    }
     if (f.observer && observe(f, p, &a, nullptr)) {  // (host twin likewise)
         fprintf(stderr, "the observer could not be built\n");
         return 1;
@@ -959,6 +1069,10 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "--components takes nothing, bottom, all or a positive count\n");
                 return 1;
             }
+            continue;
+        }
+        if (strncmp(a, "--optimise=", 11) == 0) {
+            f.optimise = a + 11;
             continue;
         }
         if (strncmp(a, "--compare=", 10) == 0) {
