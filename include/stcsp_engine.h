@@ -930,6 +930,36 @@ int stcsp_engine_counters(stcsp_engine *engine, stcsp_counters *out);
 /* The expansion kernel the engine runs for its current program (tests, diagnostics): bit 0 a LITE kernel, bit 1 the
  * one-register LITE shape kernel, bit 2 the image staged in LDS. */
 int stcsp_engine_expand_variant(const stcsp_engine *engine);
+/* The three kernels the engine runs for its current program, by the template arguments they were instantiated with (tests,
+ * diagnostics; read-only). Written by the statements that choose the kernels (select_kernels() in engine.hip). */
+enum { /* family: the expansion kernel's row in the table at select_kernels() */
+    STCSP_KF_VARIANT = 0,      /* k_expand<DR, L, CS, LITE> with its big-workgroup and one-register refinements */
+    STCSP_KF_PREFIX = 1,       /* k_expand<DR, 2, false, false> */
+    STCSP_KF_WIDE_DOMAINS = 2, /* k_expand<DR, false, false, false, false, W> */
+    STCSP_KF_LONG_KEY = 3,     /* k_expand<4, false, CS, false, false, W, 2> */
+    STCSP_KF_LARGE_BLOCK = 4,  /* k_expand<8, false, CS, false, false, W, KR> */
+    STCSP_KF_UNTIL_HEAVY = 5,  /* k_expand_until<DR, CS, W, KR, ..> */
+    STCSP_KF_BIG_SCOPE = 6     /* k_expand_big<DR, CS, W, KR> */
+};
+enum { STCSP_KP_PROBE = 0, STCSP_KP_PROBE_BIG = 1 };    /* probe_family: k_probe, k_probe_big */
+enum { STCSP_KC_COMMIT = 0, STCSP_KC_COMMIT_UNTIL = 1 }; /* commit_family: k_commit, k_commit_until */
+typedef struct stcsp_kernel_choice {
+    int32_t family;             /* STCSP_KF_* */
+    int32_t dom_regs;           /* DR: 1, 2, 4 or 8 block registers per lane */
+    int32_t domain_form;        /* W: 1, 2 or 4 bitset words per domain; 0: interval domains */
+    int32_t key_regs;           /* KR: 1, or 2 for a key of more than 64 words */
+    int32_t image_in_lds;       /* the expansion kernel's own L (whole image, or the prefix family's staged prefix) ... */
+    int32_t compact_sweeps;     /* ... CS ... */
+    int32_t lite;               /* ... LITE ... */
+    int32_t big_workgroup;      /* ... BIG ... */
+    int32_t one_register_shape; /* ... and SHP */
+    int32_t expand_threads;     /* its workgroup size */
+    int32_t probe_family;       /* STCSP_KP_* */
+    int32_t probe_image_in_lds, probe_compact_sweeps, probe_lite; /* k_probe's L, CS, LITE (k_probe_big: 0, CS, 0) */
+    int32_t commit_family;      /* STCSP_KC_* */
+    int32_t commit_key_regs;    /* the commit kernel's KR */
+} stcsp_kernel_choice;
+int stcsp_engine_kernel_choice(const stcsp_engine *engine, stcsp_kernel_choice *out);
 /* Constraint-set registry exchange: every shard must know a set before it can open a state that
  * uses it. sets_blob returns this shard's registry serialised as int32 words (valid until the
  * next call); sets_import registers the sets of another shard's blob (idempotent). */

@@ -58,6 +58,23 @@ class Counters(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class KernelChoice(C.Structure):
+    """stcsp_kernel_choice (include/stcsp_engine.h): the expansion, probe and commit kernel by their template arguments."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "family", "dom_regs", "domain_form", "key_regs", "image_in_lds", "compact_sweeps", "lite", "big_workgroup",
+        "one_register_shape", "expand_threads", "probe_family", "probe_image_in_lds", "probe_compact_sweeps", "probe_lite",
+        "commit_family", "commit_key_regs")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# KernelChoice.family / .probe_family / .commit_family (STCSP_KF_* / STCSP_KP_* / STCSP_KC_*)
+KF_VARIANT, KF_PREFIX, KF_WIDE_DOMAINS, KF_LONG_KEY, KF_LARGE_BLOCK, KF_UNTIL_HEAVY, KF_BIG_SCOPE = range(7)
+KP_PROBE, KP_PROBE_BIG = 0, 1
+KC_COMMIT, KC_COMMIT_UNTIL = 0, 1
+
+
 class Result(C.Structure):
     _fields_ = [("n_states", C.c_int64), ("sig_len", C.c_int32), ("n_sig_vars", C.c_int32),
                 ("n_until", C.c_int32), ("n_until_cons", C.c_int32),
@@ -448,7 +465,7 @@ ENGINE_SYMBOLS = [
     "stcsp_engine_candidate_bytes", "stcsp_engine_outbox", "stcsp_engine_commit", "stcsp_engine_finish",
     "stcsp_engine_counters", "stcsp_engine_sets_blob", "stcsp_engine_sets_import", "stcsp_engine_postprocess",
     "stcsp_engine_propagate", "stcsp_engine_set_expand_budget", "stcsp_engine_node_bytes", "stcsp_engine_donate",
-    "stcsp_engine_adopt", "stcsp_engine_expand_variant", "stcsp_engine_quotient",
+    "stcsp_engine_adopt", "stcsp_engine_expand_variant", "stcsp_engine_kernel_choice", "stcsp_engine_quotient",
     "stcsp_engine_monitor_build", "stcsp_engine_monitor_check", "stcsp_engine_generator_build", "stcsp_engine_generate",
     "stcsp_engine_repair", "stcsp_engine_infer", "stcsp_engine_observer", "stcsp_engine_compare",
     "stcsp_engine_components", "stcsp_engine_optimise",
@@ -612,6 +629,7 @@ def bind_engine_api(lib: C.CDLL, prefix: str = "stcsp_engine") -> None:
         g("counters").argtypes = [C.c_void_p, C.POINTER(Counters)]
     if hasattr(lib, f"{prefix}_expand_variant"):
         g("expand_variant").argtypes = [C.c_void_p]
+        g("kernel_choice").argtypes = [C.c_void_p, C.POINTER(KernelChoice)]
         g("sets_blob").argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int64)]
         g("sets_import").argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int64]
     if hasattr(lib, f"{prefix}_postprocess"):
@@ -1155,6 +1173,12 @@ class EngineBase:
         v = self._f("expand_variant")(self._h)
         self._check(min(v, 0))
         return v
+
+    def kernel_choice(self) -> dict:
+        """The expansion, probe and commit kernel of the current program, by their template arguments (KernelChoice's fields)."""
+        k = KernelChoice()
+        self._check(self._f("kernel_choice")(self._h, C.byref(k)))
+        return k.as_dict()
 
     def sets_blob(self):
         """This shard's constraint-set registry as a list of int32 words."""

@@ -1185,11 +1185,80 @@ struct stcsp_engine {
     using ExpandFn = void (*)(const Ctx *, const Plan *, unsigned, uint32_t);
     using ProbeFn = void (*)(const Ctx *, uint32_t *, int, int, uint32_t, int *);
     using CommitFn = void (*)(Ctx, CommitArgs);
+    // A kernel with the template arguments it was instantiated with, as stcsp_engine_kernel_choice reports them: the factories
+    // below are the only places that name an instantiation, so the pointer and its description come from one argument list.
+    struct Expand {
+        ExpandFn fn = nullptr;
+        int family = STCSP_KF_VARIANT, dr = 0, form = 1, kr = 1, in_lds = 0, cs = 0, lite = 0, big = 0, shape = 0, threads = 256;
+    };
+    struct Probe {
+        ProbeFn fn = nullptr;
+        int family = STCSP_KP_PROBE, in_lds = 0, cs = 0, lite = 0;
+    };
+    struct Commit {
+        CommitFn fn = nullptr;
+        int family = STCSP_KC_COMMIT, kr = 1;
+    };
+    template <int DRT, int LV, bool CS, bool LITE, bool BIG = false, int W = 1, int KR = 1, bool SHP = false>
+    static Expand plain(int family) {
+        return {k_expand<DRT, LV, CS, LITE, BIG, W, KR, SHP>, family, DRT, W, KR, LV != 0, CS, LITE, BIG, SHP, BIG ? STCSP_BIG_WAVES * 64 : 256};
+    }
+    template <int DRT, bool CS, int W, int KR>
+    static Expand until_heavy() {
+        return {k_expand_until<DRT, CS, W, KR, kMaxExpireWords>, STCSP_KF_UNTIL_HEAVY, DRT, W, KR, 0, CS, 0, 0, 0, 256};
+    }
+    template <int DRT, bool CS, int W, int KR>
+    static Expand big_scoped() {
+        return {k_expand_big<DRT, CS, W, KR>, STCSP_KF_BIG_SCOPE, DRT, W, KR, 0, CS, 0, 0, 0, 256};
+    }
+    template <int DRT, int LV, bool CS, bool LITE>
+    static Probe probe_plain() {
+        return {k_probe<DRT, LV, CS, LITE>, STCSP_KP_PROBE, LV != 0, CS, LITE};
+    }
+    template <int DRT, bool CS>
+    static Probe probe_big() {
+        return {k_probe_big<DRT, CS>, STCSP_KP_PROBE_BIG, 0, CS, 0};
+    }
+    template <int DRT, int KR>
+    static Commit commit_plain() {
+        return {k_commit<DRT, KR>, STCSP_KC_COMMIT, KR};
+    }
+    template <int DRT, int KR>
+    static Commit commit_until() {
+        return {k_commit_until<DRT, KR, kMaxExpireWords>, STCSP_KC_COMMIT_UNTIL, KR};
+    }
     struct Kernels {
         ExpandFn expand = nullptr;
         ProbeFn probe = nullptr;
         CommitFn commit = nullptr;
         unsigned expand_threads = 256;  // workgroup size of `expand`
+        stcsp_kernel_choice what{};     // the three kernels as stcsp_engine_kernel_choice reports them
+        void set(const Expand &x) {
+            expand = x.fn;
+            expand_threads = (unsigned)x.threads;
+            what.family = x.family;
+            what.dom_regs = x.dr;
+            what.domain_form = x.form;  // (kWIntervals is 0)
+            what.key_regs = x.kr;
+            what.image_in_lds = x.in_lds;
+            what.compact_sweeps = x.cs;
+            what.lite = x.lite;
+            what.big_workgroup = x.big;
+            what.one_register_shape = x.shape;
+            what.expand_threads = x.threads;
+        }
+        void set(const Probe &x) {
+            probe = x.fn;
+            what.probe_family = x.family;
+            what.probe_image_in_lds = x.in_lds;
+            what.probe_compact_sweeps = x.cs;
+            what.probe_lite = x.lite;
+        }
+        void set(const Commit &x) {
+            commit = x.fn;
+            what.commit_family = x.family;
+            what.commit_key_regs = x.kr;
+        }
     };
     Kernels kernels;
 
@@ -1212,71 +1281,67 @@ struct stcsp_engine {
     template <int DRT, int V>
     void select_variant(Kernels &k) const {
         constexpr bool L = (V & 4) != 0, CS = (V & 2) != 0, LITE = (V & 1) != 0;
-        k.probe = k_probe<DRT, L, CS, LITE>;
+        k.set(probe_plain<DRT, L, CS, LITE>());
         if constexpr (DRT <= 4) {
-            k.expand = k_expand<DRT, L, CS, LITE>;
+            k.set(plain<DRT, L, CS, LITE>(STCSP_KF_VARIANT));
             if constexpr (L && LITE)
-                if (big) {
-                    k.expand = k_expand<DRT, true, CS, true, true>;
-                    k.expand_threads = STCSP_BIG_WAVES * 64;
-                }
+                if (big) k.set(plain<DRT, true, CS, true, true>(STCSP_KF_VARIANT));
             if constexpr (DRT == 1 && V == 5)
-                if (shape1) k.expand = k_expand<1, true, false, true, false, 1, 1, true>;
+                if (shape1) k.set(plain<1, true, false, true, false, 1, 1, true>(STCSP_KF_VARIANT));
         }
     }
-    // one family's general, partly-staged kernels by domain form (nullptr: the family has no such kernel)
-    ExpandFn by_domain(ExpandFn plain, ExpandFn compact, ExpandFn w2, ExpandFn w4, ExpandFn intervals) const {
+    // one family's general, partly-staged kernels by domain form (no fn: the family has no such kernel)
+    Expand by_domain(const Expand &plain_w1, const Expand &compact, const Expand &w2, const Expand &w4, const Expand &intervals) const {
         if (mgr.intervals) return intervals;
         if (mgr.W == 2) return w2;
         if (mgr.W > 2) return w4;
-        return compact_sweeps ? compact : plain;
+        return compact_sweeps ? compact : plain_w1;
     }
     template <int DRT, int KR>
-    ExpandFn expand_general() const {
-        ExpandFn iv = nullptr;  // (create refuses interval blocks of more than 256 words)
-        if constexpr (DRT <= 4) iv = k_expand<DRT, false, false, false, false, kWIntervals, KR>;
-        return by_domain(k_expand<DRT, false, false, false, false, 1, KR>, k_expand<DRT, false, true, false, false, 1, KR>,
-                         k_expand<DRT, false, false, false, false, 2, KR>, k_expand<DRT, false, false, false, false, 4, KR>, iv);
+    Expand expand_general(int family) const {
+        Expand iv;  // (create refuses interval blocks of more than 256 words)
+        if constexpr (DRT <= 4) iv = plain<DRT, false, false, false, false, kWIntervals, KR>(family);
+        return by_domain(plain<DRT, false, false, false, false, 1, KR>(family), plain<DRT, false, true, false, false, 1, KR>(family),
+                         plain<DRT, false, false, false, false, 2, KR>(family), plain<DRT, false, false, false, false, 4, KR>(family), iv);
     }
     template <int DRT, int KR>
-    ExpandFn expand_keyed() const {  // the families with one or two key registers (DRT >= 4)
-        constexpr int UW = kMaxExpireWords;
+    Expand expand_keyed() const {  // the families with one or two key registers (DRT >= 4)
         if (big_scope())  // (create refuses interval domains beside a big scope)
-            return by_domain(k_expand_big<DRT, false, 1, KR>, k_expand_big<DRT, true, 1, KR>, k_expand_big<DRT, false, 2, KR>, k_expand_big<DRT, false, 4, KR>, nullptr);
+            return by_domain(big_scoped<DRT, false, 1, KR>(), big_scoped<DRT, true, 1, KR>(), big_scoped<DRT, false, 2, KR>(), big_scoped<DRT, false, 4, KR>(), Expand{});
         if (many_until()) {
-            ExpandFn iv = nullptr;
-            if constexpr (DRT == 4) iv = k_expand_until<4, false, kWIntervals, KR, UW>;
-            return by_domain(k_expand_until<DRT, false, 1, KR, UW>, k_expand_until<DRT, true, 1, KR, UW>, k_expand_until<DRT, false, 2, KR, UW>,
-                             k_expand_until<DRT, false, 4, KR, UW>, iv);
+            Expand iv;
+            if constexpr (DRT == 4) iv = until_heavy<4, false, kWIntervals, KR>();
+            return by_domain(until_heavy<DRT, false, 1, KR>(), until_heavy<DRT, true, 1, KR>(), until_heavy<DRT, false, 2, KR>(),
+                             until_heavy<DRT, false, 4, KR>(), iv);
         }
-        return expand_general<DRT, KR>();
+        return expand_general<DRT, KR>(DRT == 8 ? STCSP_KF_LARGE_BLOCK : STCSP_KF_LONG_KEY);
     }
     // the families that come before the (L, CS, LITE) variant. false: none applies
     template <int DRT>
-    bool select_family(ExpandFn &fn) const {
+    bool select_family(Expand &x) const {
         if constexpr (DRT >= 4)
             if (big_scope() || many_until() || DRT == 8 || long_key()) {
-                fn = long_key() ? expand_keyed<DRT, 2>() : expand_keyed<DRT, 1>();
+                x = long_key() ? expand_keyed<DRT, 2>() : expand_keyed<DRT, 1>();
                 return true;
             }
         if (mgr.W > 1) {
-            fn = expand_general<DRT, 1>();  // (its two W = 1 kernels are variants 0 and 2 below)
+            x = expand_general<DRT, 1>(STCSP_KF_WIDE_DOMAINS);  // (its two W = 1 kernels are variants 0 and 2 below)
             return true;
         }
         if constexpr (staged_general_exists(DRT))
             if (prefix_complete) {
-                fn = k_expand<DRT, 2, false, false>;
+                x = plain<DRT, 2, false, false>(STCSP_KF_PREFIX);
                 return true;
             }
         return false;
     }
     template <int DRT>
-    CommitFn select_commit() const {
+    Commit select_commit() const {
         if constexpr (DRT >= 4) {
-            if (many_until()) return long_key() ? k_commit_until<DRT, 2, kMaxExpireWords> : k_commit_until<DRT, 1, kMaxExpireWords>;
-            if (long_key()) return k_commit<DRT, 2>;
+            if (many_until()) return long_key() ? commit_until<DRT, 2>() : commit_until<DRT, 1>();
+            if (long_key()) return commit_plain<DRT, 2>();
         }
-        return many_until() ? nullptr : k_commit<DRT, 1>;
+        return many_until() ? Commit{} : commit_plain<DRT, 1>();
     }
     template <int DRT>
     Kernels select_for() const {
@@ -1292,14 +1357,11 @@ struct stcsp_engine {
             case 6: select_variant<DRT, kept_variant<DRT>(6)>(k); break;
             default: select_variant<DRT, kept_variant<DRT>(7)>(k); break;
         }
-        ExpandFn family = nullptr;
-        if (select_family<DRT>(family)) {
-            k.expand = family;
-            k.expand_threads = 256;
-        }
+        Expand family;
+        if (select_family<DRT>(family)) k.set(family);
         if constexpr (DRT >= 4)
-            if (big_scope()) k.probe = compact_sweeps ? k_probe_big<DRT, true> : k_probe_big<DRT, false>;
-        k.commit = select_commit<DRT>();
+            if (big_scope()) k.set(compact_sweeps ? probe_big<DRT, true>() : probe_big<DRT, false>());
+        k.set(select_commit<DRT>());
         return k;
     }
     int select_kernels() {
@@ -2443,6 +2505,11 @@ int stcsp_engine_donate(stcsp_engine *e, int64_t want, void **ptr, int64_t *coun
 int stcsp_engine_adopt(stcsp_engine *e, const void *records, int64_t count) { return e ? e->adopt(records, count) : STCSP_E_INVALID; }
 int stcsp_engine_expand_variant(const stcsp_engine *e) {
     return e ? (e->lite ? 1 : 0) | (e->shape1 ? 2 : 0) | (e->img_in_lds || e->big ? 4 : 0) | (e->big_scope() ? 8 : 0) : STCSP_E_INVALID;
+}
+int stcsp_engine_kernel_choice(const stcsp_engine *e, stcsp_kernel_choice *out) {
+    if (!e || !out) return STCSP_E_INVALID;
+    *out = e->kernels.what;
+    return STCSP_OK;
 }
 int stcsp_engine_counters(stcsp_engine *e, stcsp_counters *out) {
     if (!e || !out) return STCSP_E_INVALID;

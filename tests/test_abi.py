@@ -64,6 +64,20 @@ def test_abi_struct_sizes(stcsp):
     assert C.sizeof(stcsp.Counters) == 8 * 8 + 2 * 8 + 8 + 8 + 24 + 8  # + translation_stops
     assert C.sizeof(stcsp.PostOptions) == 16
     assert C.sizeof(stcsp.PostResult) == 72
+    assert C.sizeof(stcsp.KernelChoice) == 16 * 4  # stcsp_kernel_choice: int32 fields only
+
+
+def test_kernel_choice_is_declared_and_mirrored(stcsp):
+    """stcsp_engine_kernel_choice: the header's struct and the ctypes mirror name the same fields in the same order, and the
+    family constants agree."""
+    text = (REPO / "include" / "stcsp_engine.h").read_text()
+    assert "stcsp_engine_kernel_choice" in declared("stcsp_engine.h") and "stcsp_engine_kernel_choice" in stcsp.ENGINE_SYMBOLS
+    body = re.search(r"typedef struct stcsp_kernel_choice \{(.*?)\} stcsp_kernel_choice;", text, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = [f.strip() for decl in body.split(";") if decl.strip() for f in decl.replace("int32_t", "").split(",")]
+    assert fields == [n for n, _ in stcsp.KernelChoice._fields_]
+    for name, value in re.findall(r"STCSP_(K[FPC]_[A-Z_]+) = (\d+)", text):
+        assert getattr(stcsp, name) == int(value), name
 
 
 def test_automaton_flags_roundtrip(stcsp, RefOracle):

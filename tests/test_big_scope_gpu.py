@@ -148,6 +148,8 @@ def test_big_scope_node_seam_equals_gac_fixpoint(stcsp, oracle_lib, FrontierMode
     blocks = seam_blocks(m, scope, 2, np.random.default_rng(20261016), 64)
     e = stcsp.Engine(m)
     assert e.expand_variant() & 8
+    k = e.kernel_choice()  # k_expand_big<4, true, 1, 1> and k_probe_big<4, true> (79 links at two time points: CS)
+    assert (k["family"], k["dom_regs"], k["compact_sweeps"], k["probe_family"], k["probe_compact_sweeps"]) == (stcsp.KF_BIG_SCOPE, 4, 1, stcsp.KP_PROBE_BIG, 1)
     got, outcome, skipped = e.propagate(blocks, 0, 0)
     want, ok = fmodel_propagate(oracle_lib, FrontierModel, m, blocks)
     assert skipped == 0

@@ -42,6 +42,7 @@ def compare(stcsp, RefOracle, text, prefix_k=2, **opts):
     assert not ro.truncated
     ao, _ = finish(o, ro)
     e = iv(stcsp, m, time_limit_s=120.0, **opts)
+    assert e.kernel_choice()["domain_form"] == 0  # an interval kernel: k_expand<DR, .., kWIntervals, KR> or k_expand_until<4, false, kWIntervals, ..>
     r = e.solve()
     assert not r.truncated
     a, _ = finish(e, r)

@@ -94,6 +94,8 @@ def test_large_block_same_engine_twice(stcsp, RefOracle):
         o = RefOracle(m)
         ao, _ = finish(o, o.solve())
         e = stcsp.Engine(m)
+        k = e.kernel_choice()  # k_expand<8, false, true, false, false, 1, KR> (more than 128 lane-revised items: CS), KR = 2 for the ring's key
+        assert (k["family"], k["dom_regs"], k["compact_sweeps"], k["key_regs"], k["commit_key_regs"]) == (stcsp.KF_LARGE_BLOCK, 8, 1, 1 + (name == "ring100"), 1 + (name == "ring100"))
         for _ in range(2):
             a, _ = finish(e, e.solve())
             assert a.canonical() == ao.canonical()

@@ -23,6 +23,8 @@ def test_partialorder_runs_the_shape_kernel_and_matches_golden(stcsp, golden, n)
     name = f"partialorder_{n}"
     e = stcsp.Engine(stcsp.Model.from_name(name))
     assert e.expand_variant() == LITE | SHAPE | IN_LDS
+    k = e.kernel_choice()  # k_expand<1, true, false, true, false, 1, 1, true>
+    assert (k["family"], k["dom_regs"], k["image_in_lds"], k["compact_sweeps"], k["lite"], k["big_workgroup"], k["one_register_shape"]) == (stcsp.KF_VARIANT, 1, 1, 0, 1, 0, 1)
     r = e.solve()
     a, _ = finish(e, r)
     g = golden[name]

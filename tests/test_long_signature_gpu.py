@@ -98,6 +98,8 @@ def test_long_signature_same_engine_twice_and_small_pools(stcsp, RefOracle, monk
     o = RefOracle(m)
     ao, _ = finish(o, o.solve())
     e = stcsp.Engine(m)
+    k = e.kernel_choice()  # k_expand<4, false, false, false, false, 1, 2> and k_commit<4, 2>
+    assert (k["family"], k["dom_regs"], k["domain_form"], k["key_regs"], k["compact_sweeps"], k["commit_key_regs"]) == (stcsp.KF_LONG_KEY, 4, 1, 2, 0, 2)
     for _ in range(2):
         a, _ = finish(e, e.solve())
         assert a.canonical() == ao.canonical()

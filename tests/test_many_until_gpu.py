@@ -47,6 +47,9 @@ def test_many_until_small_pools_and_same_engine_twice(stcsp, RefOracle, monkeypa
     o = RefOracle(m)
     ao, _ = finish(o, o.solve())
     e = stcsp.Engine(m)
+    k = e.kernel_choice()  # k_expand_until<4, true, 1, 2, ..> (100 until items and the y_b at two time points: CS) and k_commit_until<4, 2, ..>
+    assert (k["family"], k["dom_regs"], k["domain_form"], k["key_regs"], k["compact_sweeps"], k["commit_family"], k["commit_key_regs"]) == \
+           (stcsp.KF_UNTIL_HEAVY, 4, 1, 2, 1, stcsp.KC_COMMIT_UNTIL, 2)
     for _ in range(2):
         a, _ = finish(e, e.solve())
         assert a.canonical() == ao.canonical()

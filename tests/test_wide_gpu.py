@@ -79,6 +79,7 @@ def test_fuzz_wide_domains(stcsp, RefOracle, block):
         ao, _ = finish(o, ro)
         try:
             e = stcsp.Engine(m)
+            assert e.kernel_choice()["domain_form"] in (2, 4)  # a W = 2 or W = 4 kernel: k_expand<DR, false, false, false, false, W, KR>
         except stcsp.StcspError as ex:
             assert ex.code == -2, f"seed {seed}: {ex}\n{text}"  # hull bounds of an aux variable beyond 128 values
             continue
