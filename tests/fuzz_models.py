@@ -154,3 +154,56 @@ class WideGen(Gen):
 
 def random_wide_model(seed: int) -> str:
     return WideGen(seed).model()
+
+
+# WideGen seeds that no node cap cuts short: seed 142 has no solution, but the oracle's support search over three
+# occurrences of 87-value variables in one constraint takes minutes before the first search node. Fuzzes that must check
+# the same models on every machine (a max_search_nodes cap, no wall-clock limit) leave these out by name.
+WIDE_SLOW_SEEDS = (142,)
+
+
+class UntilGen(Gen):
+    """Gen's model with one more `until` constraint over two of its variables, so that most automata carry until flags
+    and the backward traverse has something to decide."""
+
+    def model(self):
+        text = super().model()
+        a = self.var()
+        b = self.var()
+        return text + f"{a} until {b};\n"
+
+
+def random_until_model(seed: int) -> str:
+    return UntilGen(seed).model()
+
+
+def game_model(W: int, alo: int, shift: int = 0) -> str:
+    """A game over an opponent variable o of W values (var 0) and an avatar a (var 1): o's low half adds a to the
+    counter s, its high half takes one off; the top value of o is forbidden once s reaches 3. Eight states whatever W
+    is. The top value of o is missing exactly in the states the adversarial passes invalidate, so the answer changes
+    with a wrong last cover word. `shift` moves o's domain and the two constants that mention it."""
+    lo, top, mid = shift, W - 1 + shift, W // 2 + shift
+    return (f"var o:[{lo},{top}]; var a:[{alo},2]; var s:[0,6]; first s == 0;\n"
+            f"next s == (if (o lt {_const(mid)}) then (s + a) else (if (s gt 0) then (s - 1) else 0));\n"
+            f"((s lt 3) or (o ne {_const(top)})) == 1;\n")
+
+
+def _const(c: int) -> str:
+    return str(c) if c >= 0 else f"(0 - {-c})"
+
+
+def adv_chain(L: int) -> str:
+    """A chain of L + 1 states whose last one lacks o == 1: adversarial(o) invalidates one state per sweep, back to
+    the root."""
+    return (f"var o:[0,1]; var s:[0,{L}]; first s == 0;\n"
+            f"next s == (if (s lt {L}) then (s + 1) else s);\n"
+            f"((s lt {L}) or (o ne 1)) == 1;\n")
+
+
+def until_chain(L: int) -> str:
+    """An until flag that only the end of a chain of L steps fulfils: validity travels backwards over L edges."""
+    return (f"var x:[0,{L}]; var y:[0,1]; var g:[0,1]; first x == 0; next x == if (x lt {L}) then x + 1 else x; "
+            f"y == (x eq {L}); g until y;")
+
+
+NO_SOLUTION = "var x:[0,1]; x == 0; x == 1;\n"
