@@ -207,3 +207,84 @@ def until_chain(L: int) -> str:
 
 
 NO_SOLUTION = "var x:[0,1]; x == 0; x == 1;\n"
+
+
+def table_automaton(seed, digits, letters, keep_pct, goal_pct, rooted=True, colours=2):
+    """A random automaton of a chosen size through the ordinary front end: the model's arrays are its transition table. The
+    state is one variable s of S values, or two digits s1, s0 of bases `digits` (S their product: several hundred states with
+    every domain at most 32 values); the letter x picks the successor T[s * A + x], OK keeps `keep_pct` of the S * A entries,
+    G makes `goal_pct` of the states goals of `w until g`, and the colour c == CC[s * A + x] is a random function of state and
+    letter: observed alone it hides both. rooted=False drops the `first` of the low digit: one edge of the root per start state."""
+    digits = tuple(digits)
+    assert len(digits) in (1, 2) and all(b >= 1 for b in digits) and letters >= 1 and colours >= 1
+    A, B0 = letters, digits[-1]
+    S = digits[0] * B0 if len(digits) == 2 else B0
+    r = _inst.SplitMix64(0x7AB1E000 + seed)
+    T = [r.below(S) for _ in range(S * A)]
+    OK = [int(r.below(100) < keep_pct) for _ in range(S * A)]
+    G = [int(r.below(100) < goal_pct) for _ in range(S)]
+    CC = [r.below(colours) for _ in range(S * A)]
+    # what the front end needs: every array as long as its index range, every index inside it, every entry inside its variable's domain
+    assert len(T) == len(OK) == len(CC) == S * A and len(G) == S
+    assert (S - 1) * A + (A - 1) < len(T) and S - 1 < len(G)  # the largest indices the model forms
+    assert all(0 <= t < S for t in T) and all(0 <= c < colours for c in CC)
+
+    def arr(name, xs):
+        return f"arr {name} : {{{', '.join(map(str, xs))}}};"
+    if len(digits) == 1:
+        out = [f"var s:[0,{S - 1}];", arr("T", T)]
+        state, index = "s", f"s * {A} + x"
+        rules = (["first s == 0;"] if rooted else []) + [f"next s == T[{index}];"]
+    else:
+        out = [f"var s1:[0,{digits[0] - 1}]; var s0:[0,{B0 - 1}];", arr("T1", [t // B0 for t in T]), arr("T0", [t % B0 for t in T])]
+        state = f"s1 * {B0} + s0"
+        index = f"({state}) * {A} + x"
+        rules = ["first s1 == 0;"] + (["first s0 == 0;"] if rooted else []) + [f"next s1 == T1[{index}];", f"next s0 == T0[{index}];"]
+    out.insert(1, f"var x:[0,{A - 1}]; var g:[0,1]; var w:[0,1]; var c:[0,{colours - 1}];")
+    out += [arr("OK", OK), arr("G", G), arr("CC", CC)]
+    out += rules + [f"OK[{index}] == 1;", f"c == CC[{index}];", f"g == G[{state}];", "w until g;"]
+    return "\n".join(out) + "\n"
+
+
+def _table_reach(T, OK, A, starts):
+    """The table's states that a start state reaches over kept entries (the until flag aside), in breadth-first order."""
+    seen, order = set(starts), list(starts)
+    for s in order:
+        for x in range(A):
+            t = T[s * A + x]
+            if OK[s * A + x] and t not in seen:
+                seen.add(t)
+                order.append(t)
+    return order
+
+
+def table_mutant(text, seed):
+    """The table automaton `text` with one more constraint that forbids one state its table reaches (no start state where
+    another is reached): every solution prefix of the mutant is one of the original. The arrays are read back from the text."""
+    arrays = {}
+    for line in text.splitlines():
+        if line.startswith("arr "):
+            name, body = line[4:].split(":", 1)
+            arrays[name.strip()] = [int(v) for v in body.strip(" {};").split(",")]
+    two = "T1" in arrays
+    B0 = int(text.split("var s0:[0,")[1].split("]")[0]) + 1 if two else len(arrays["G"])
+    T = [hi * B0 + lo for hi, lo in zip(arrays["T1"], arrays["T0"])] if two else arrays["T"]
+    S = len(arrays["G"])
+    A = len(T) // S
+    assert len(T) == S * A == len(arrays["OK"])
+    rooted = ("first s0 == 0;" if two else "first s == 0;") in text
+    order = _table_reach(T, arrays["OK"], A, [0] if rooted else list(range(B0)))
+    later = order[1 if rooted else B0:] or order
+    k = later[_inst.SplitMix64(0x7AB1E000 + seed).below(len(later))]
+    if two:
+        return text + f"((s1 ne {k // B0}) or (s0 ne {k % B0})) == 1;\n"
+    return text + f"(s ne {k}) == 1;\n"
+
+
+def table_by_name(name):
+    """`table:<seed>:<digits>:<letters>:<keep>:<goal>[:unrooted][:<colours>]`, digits as `20` or `32x33`: its model text."""
+    kind, seed, digits, letters, keep, goal, *rest = name.split(":")
+    assert kind == "table" and all(x == "unrooted" or x.isdigit() for x in rest)
+    colours = [int(x) for x in rest if x.isdigit()]
+    return table_automaton(int(seed), tuple(int(b) for b in digits.split("x")), int(letters), int(keep), int(goal),
+                           rooted="unrooted" not in rest, colours=colours[0] if colours else 2)

@@ -67,6 +67,12 @@ def check_device(stcsp, RefOracle, m, what, horizon=32, oracle=True, masks=("def
         e.monitor(arg)  # the two sets of structures live apart: building the monitor's leaves the generator's valid
         exact = [t for t in range(horizon + 1) if 0 < info.count[t] < 2.0 ** 53]
         for length, seed in ((horizon, 0), (horizon, 7), (1, 0), (horizon // 3, 7)):
+            if info.count[length] == 0:  # no prefix of that length: both refuse
+                for run in (lambda: e.generate(n, length, seed), lambda: host.generate(n, length, seed, observable=arg, horizon=horizon)):
+                    with pytest.raises(stcsp.StcspError) as ex:
+                        run()
+                    assert ex.value.code == -1, f"{what} [{name}] len {length}"
+                continue
             dev = e.generate(n, length, seed)
             hst = host.generate(n, length, seed, observable=arg, horizon=horizon)
             assert np.array_equal(dev[0], hst[0]) and np.array_equal(dev[1], hst[1]), f"{what} [{name}] seed {seed} len {length}: device and host twin differ"

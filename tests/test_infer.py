@@ -155,10 +155,10 @@ def check_twin(stcsp, RefOracle, text, what, mask_names=("default", "all", "hidd
             # the consequences
             dist, repaired, rfin, _ = a.repair_streams(streams, arg, end_final=end_final)
             assert np.array_equal(count > 0, dist == 0), f"{tag}: count > 0 exactly when the repair's distance is 0"
-            acc = a.check_streams(streams, arg)[0]
+            acc, nend = a.check_streams(streams, arg)[:2]
             for i, s in enumerate(streams):
-                if name == "all" and not end_final and (s != X).all():
-                    assert count[i] in (0.0, 1.0) and (count[i] == 1.0) == (acc[i] == len(s)), f"{tag}: fully observed, stream {i}"
+                if name == "all" and not end_final and (s != X).all():  # (accepted in a state: without a live root there is none)
+                    assert count[i] in (0.0, 1.0) and (count[i] == 1.0) == (acc[i] == len(s) and nend[i] > 0), f"{tag}: fully observed, stream {i}"
                 if count[i] > 0:
                     for j in range(2):
                         assert ((s == X) | (s == draws[i][j])).all(), f"{tag}: a draw keeps the observed entries"

@@ -113,10 +113,10 @@ def check_twin(stcsp, RefOracle, text, what, mask_names=("default", "all", "hidd
                     assert y.brute(s, **kw) == want, f"{what} [{name}] {kw} stream {s.tolist()}: brute force against the recurrence"
         # the properties, on the plain variant
         dist, values, fin, nchg = a.repair_streams(streams, arg)
-        acc = a.check_streams(streams, arg)[0]
+        acc, nend = a.check_streams(streams, arg)[:2]
         for i, s in enumerate(streams):
-            if (s != X).all() and n_obs:
-                assert (dist[i] == 0) == (acc[i] == len(s)), f"{what} [{name}]: distance 0 exactly when the monitor accepts"
+            if (s != X).all() and n_obs:  # (accepted in some state: without a live root the monitor "accepts" the empty stream in none)
+                assert (dist[i] == 0) == (acc[i] == len(s) and nend[i] > 0), f"{what} [{name}]: distance 0 exactly when the monitor accepts"
             if dist[i] == 0 and (s != X).all():
                 assert np.array_equal(values[i], s)
             if dist[i] >= 0:

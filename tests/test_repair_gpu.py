@@ -61,7 +61,8 @@ def check_device(stcsp, RefOracle, m, what, masks=("default", "all"), oracle=Tru
         for kw in (dict(), dict(end_final=True), dict(weights=[int(w) for w in rng.randint(0, 5, size=n_obs)]),
                    dict(weights=[int(w) for w in rng.randint(1, 9, size=n_obs)], end_final=True)):
             dev = e.repair_streams(streams, **kw)
-            assert e.repair_result.n_batches == 1 and e.repair_result.n_observable == n_obs
+            # (without a live root nothing runs on the device: no batch, as for the inference)
+            assert e.repair_result.n_batches == (1 if info.root_live else 0) and e.repair_result.n_observable == n_obs
             assert same(dev, host.repair_streams(streams, arg, **kw)), f"{what} [{name}] {kw}: device and host twin differ"
             if oracle:
                 got = R.unpack(dev)
@@ -70,10 +71,10 @@ def check_device(stcsp, RefOracle, m, what, masks=("default", "all"), oracle=Tru
             ok = [v for d, v in zip(dev[0], dev[1]) if d >= 0]
             assert (e.check_streams(ok)[0] == [len(v) for v in ok]).all(), f"{what} [{name}] {kw}: a repaired stream is a prefix of a solution"
             if not kw and n_obs:
-                acc = e.check_streams(streams)[0]
+                acc, nend = e.check_streams(streams)[:2]
                 for i, s in enumerate(streams):
-                    if (s != X).all():
-                        assert (dev[0][i] == 0) == (acc[i] == len(s)), f"{what} [{name}]: distance 0 exactly when the monitor accepts"
+                    if (s != X).all():  # (accepted in some state: without a live root the monitor "accepts" the empty stream in none)
+                        assert (dev[0][i] == 0) == (acc[i] == len(s) and nend[i] > 0), f"{what} [{name}]: distance 0 exactly when the monitor accepts"
         print(f"{what} [{name}]: live {info.n_states} edges {info.n_edges} labels {e.repair_result.n_labels} streams {len(streams)}")
 
 
