@@ -452,6 +452,14 @@ int stcsp_engine_generate(stcsp_engine *engine, const stcsp_generate_request *re
  * neither the generator's nor the monitor's structures. */
 #define STCSP_REPAIR_END_FINAL 1           /* the repaired stream must end in a final state */
 #define STCSP_REPAIR_MISSING (-2147483647 - 1) /* INT32_MIN in a row: this variable was not observed at this step */
+/* INT32_MIN as a label value. A variable whose domain reaches INT32_MIN (interval domains) can carry it on a live edge.
+ *   - In an INPUT row of repair() and infer() INT32_MIN always means "not observed": it matches every value, costs
+ *     nothing and counts as not observed in n_changed; an observed INT32_MIN cannot be expressed there. The monitor has
+ *     no MISSING: in its rows INT32_MIN is the value, matched like any other.
+ *   - OUTPUT rows (generate, repaired values, infer's supports and draws, the optimiser's witnesses, observer and compare
+ *     labels) carry INT32_MIN wherever the chosen edge has it: there it is a value. The only output rows of MISSING are
+ *     the draws of an infeasible stream, which have count == 0.
+ * Device, host twin and yardsticks are pinned to this by tests/test_service_shapes_gpu.py. */
 
 typedef struct stcsp_repair_request {
     int64_t n_streams;
@@ -550,7 +558,7 @@ int stcsp_engine_repair(stcsp_engine *engine, const stcsp_repair_request *reques
  * The call invalidates none of the generator's, monitor's or repair's structures; its own are invalidated wherever the
  * generator's are. */
 #define STCSP_INFER_END_FINAL 1            /* count only the completions that end in a final state */
-#define STCSP_INFER_MISSING (-2147483647 - 1) /* == STCSP_REPAIR_MISSING */
+#define STCSP_INFER_MISSING (-2147483647 - 1) /* == STCSP_REPAIR_MISSING; INT32_MIN as a label value: see there */
 
 typedef struct stcsp_infer_request {
     int64_t n_streams;

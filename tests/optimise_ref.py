@@ -43,10 +43,10 @@ def enumerate_paths(out, final, weights, end_final=False, root_live=True, max_le
                 res[L] = (c, rows)
         if L == max_len:
             break
-        paths = [(rows + (row,), v, c + cost(weights, row)) for rows, s, c in paths for row, v in out.get(s, ())]
-        total += len(paths)
-        if total > MAX_PATHS:
+        total += sum(len(out.get(s, ())) for _, s, _ in paths)
+        if total > MAX_PATHS:  # (counted before the level is built: a level that is too long costs nothing)
             return None
+        paths = [(rows + (row,), v, c + cost(weights, row)) for rows, s, c in paths for row, v in out.get(s, ())]
     return res
 
 

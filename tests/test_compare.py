@@ -52,17 +52,17 @@ def mask_of(model, names):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_observer(stcsp, RefOracle, name, names):
+def oracle_observer(stcsp, RefOracle, name, names, prefix_k=2):
     """(automaton of the CPU oracle, mask, its observer by the host twin) for one model under the named variables."""
-    m = stcsp.Model(text=text_of(stcsp, name))
+    m = stcsp.Model(text=text_of(stcsp, name), prefix_k=prefix_k)
     o = RefOracle(m)
     a = o.automaton(o.solve()).traverse()
     mask = mask_of(m, names)
     return a, mask, a.observer(mask)
 
 
-def twin_against_yardstick(stcsp, RefOracle, left, right, names):
-    (al, ml, ol), (ar, mr, orr) = oracle_observer(stcsp, RefOracle, left, names), oracle_observer(stcsp, RefOracle, right, names)
+def twin_against_yardstick(stcsp, RefOracle, left, right, names, prefix_k=2):
+    (al, ml, ol), (ar, mr, orr) = oracle_observer(stcsp, RefOracle, left, names, prefix_k), oracle_observer(stcsp, RefOracle, right, names, prefix_k)
     twin = stcsp.compare_observers(ol, orr)
     assert R.same(twin, R.product(ol, orr)), f"{left} | {right} [{names}]: twin and yardstick differ"
     return (al, ml, ol), (ar, mr, orr), twin

@@ -59,9 +59,9 @@ def text_of(stcsp, name):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_case(stcsp, RefOracle, name, adversarial=None):
+def oracle_case(stcsp, RefOracle, name, adversarial=None, prefix_k=2):
     """(model, Result, automaton, (valid, final, alive), yardstick with every lasso) of the CPU oracle's automaton; computed once."""
-    m = stcsp.Model(text=text_of(stcsp, name))
+    m = stcsp.Model(text=text_of(stcsp, name), prefix_k=prefix_k)
     o = RefOracle(m)
     r = o.solve()
     a = o.automaton(r).traverse()
@@ -76,9 +76,9 @@ def table_row(ref):
     return tuple(c[k] for k in ("n_states", "n_edges", "n_components", "n_cyclic", "n_accepting", "n_bottom", "largest", "n_omega"))
 
 
-def check_host_twin(stcsp, RefOracle, name, adversarial=None):
+def check_host_twin(stcsp, RefOracle, name, adversarial=None, prefix_k=2):
     """Host twin == yardstick: the partition, the flags, the depths, omega, and every lasso."""
-    m, r, a, (valid, final, alive), ref, _ = oracle_case(stcsp, RefOracle, name, adversarial)
+    m, r, a, (valid, final, alive), ref, _ = oracle_case(stcsp, RefOracle, name, adversarial, prefix_k)
     res = a.components("all")
     R.check_result(r, valid, alive, res, ref)
     assert R.result_lassos(res) == ref["lassos"] and res["n_lassos"] == len(ref["lassos"]) == ref["counts"]["n_accepting"], name

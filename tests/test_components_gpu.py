@@ -27,7 +27,7 @@ def device_case(stcsp, name, interval=False):
     return m, e, r, Q.post_flags(post), e.automaton(r).import_flags(post)
 
 
-def check_device(stcsp, name, lassos="all", no_trim=False, interval=False, RefOracle=None):
+def check_device(stcsp, name, lassos="all", no_trim=False, interval=False, RefOracle=None, prefix_k=2):
     """Device == twin, exactly and array by array; with RefOracle also == the yardstick on the oracle's automaton."""
     m, e, r, (valid, final, alive), a = device_case(stcsp, name, interval)
     dev = e.components(lassos, no_trim)
@@ -36,7 +36,7 @@ def check_device(stcsp, name, lassos="all", no_trim=False, interval=False, RefOr
     assert dev["n_vars"] == m.n_vars and dev["seconds"] > 0
     assert dev["rounds"][1] <= dev["n_components"] and (dev["rounds"][0] == 0 if no_trim else True)  # a colouring round finds a component
     if RefOracle is not None:
-        ref = oracle_case(stcsp, RefOracle, name)[4]
+        ref = oracle_case(stcsp, RefOracle, name, None, prefix_k)[4]
         R.check_result(r, valid, alive, dev, ref, same_numbering=False)
         if lassos == "all":
             assert R.result_lassos(dev) == ref["lassos"], f"{name}: device and yardstick differ"

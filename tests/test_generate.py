@@ -21,22 +21,23 @@ NO_LIVE_ROOT = "var x:[0,1]; var y:[0,1]; x until y; y == 0;"
 _solved = {}
 
 
-def solved(stcsp, RefOracle, text):
-    """(model, oracle, result, automaton) of a model text, solved once per session."""
-    if text not in _solved:
-        m = stcsp.Model(text=text)
-        _solved[text] = (m,) + oracle_automaton(stcsp, RefOracle, m)
-    return _solved[text]
+def solved(stcsp, RefOracle, text, prefix_k=2):
+    """(model, oracle, result, automaton) of a model text, solved once per session (and prefix length, where it is not 2)."""
+    key = text if prefix_k == 2 else (text, prefix_k)
+    if key not in _solved:
+        m = stcsp.Model(text=text, prefix_k=prefix_k)
+        _solved[key] = (m,) + oracle_automaton(stcsp, RefOracle, m)
+    return _solved[key]
 
 
 def text_of(stcsp, name):
     return PROBES[name[6:]]["text"] if name.startswith("probe:") else stcsp.instances.by_name(name)
 
 
-def check_sampling(stcsp, RefOracle, text, what, horizon=64, seeds=(0, 7), n=12, lengths=None, mask_names=("default", "all", "hidden")):
+def check_sampling(stcsp, RefOracle, text, what, horizon=64, seeds=(0, 7), n=12, lengths=None, mask_names=("default", "all", "hidden"), prefix_k=2):
     """Twin == yardstick value for value (count, streams, end_final), and every stream is accepted whole by the monitor's
     host twin under the same mask. Returns the yardstick of the last mask."""
-    m, o, r, a = solved(stcsp, RefOracle, text)
+    m, o, r, a = solved(stcsp, RefOracle, text, prefix_k)
     valid, final, alive = a.flags()
     y = None
     for name, mask in M.masks(m, r).items():

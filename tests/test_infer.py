@@ -119,11 +119,11 @@ def specialisation(a, arg, streams, counts, supports, bounds, keep, what):
     return len(cases)
 
 
-def check_twin(stcsp, RefOracle, text, what, mask_names=("default", "all", "hidden"), length=None, brute=True, seed=1, n=5, most=None):
+def check_twin(stcsp, RefOracle, text, what, mask_names=("default", "all", "hidden"), length=None, brute=True, seed=1, n=5, most=None, prefix_k=2):
     """Twin == the yardstick's recurrences == its brute force on seeded streams at MISSING rates 0, 30 % and 100 %, with and
     without END_FINAL, all five outputs; and the consequences of the contract against the monitor's, the repair's and the
     generator's host twins."""
-    m, o, r, a = solved(stcsp, RefOracle, text)
+    m, o, r, a = solved(stcsp, RefOracle, text, prefix_k)
     valid, final, alive = a.flags()
     bounds = m.var_bounds()
     for name, mask in M.masks(m, r).items():

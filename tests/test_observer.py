@@ -19,13 +19,13 @@ WITNESSES = {"counter": COUNTER, "countdown": COUNTDOWN, "duplicates": DUPLICATE
 SMALL = {**WITNESSES, "crafted3": R.CRAFTED % (3, 3), "juggling_b4_f4": None, "digitinvader1": None}
 
 
-def model_of(stcsp, name):
+def model_of(stcsp, name, prefix_k=2):
     if name.startswith("crafted"):
         k = int(name[7:])
-        return stcsp.Model(text=R.CRAFTED % (k, k))
+        return stcsp.Model(text=R.CRAFTED % (k, k), prefix_k=prefix_k)
     if name in PROBES:
-        return stcsp.Model(text=PROBES[name]["text"])
-    return stcsp.Model(text=SMALL[name]) if SMALL.get(name) else stcsp.Model.from_name(name)
+        return stcsp.Model(text=PROBES[name]["text"], prefix_k=prefix_k)
+    return stcsp.Model(text=SMALL[name], prefix_k=prefix_k) if SMALL.get(name) else stcsp.Model.from_name(name, prefix_k)
 
 
 def masks_of(model, r):
@@ -35,8 +35,8 @@ def masks_of(model, r):
 
 
 @functools.lru_cache(maxsize=4)
-def _oracle(stcsp, RefOracle, name, adversarial):
-    m = model_of(stcsp, name)
+def _oracle(stcsp, RefOracle, name, adversarial, prefix_k=2):
+    m = model_of(stcsp, name, prefix_k)
     o = RefOracle(m)
     r = o.solve()
     a = o.automaton(r).traverse()
@@ -45,9 +45,9 @@ def _oracle(stcsp, RefOracle, name, adversarial):
     return m, o, r, a
 
 
-def twin_against_yardstick(stcsp, RefOracle, name, which, adversarial=None):
+def twin_against_yardstick(stcsp, RefOracle, name, which, adversarial=None, prefix_k=2):
     """Twin == yardstick: member sets by canonical number, final flags, edges (src, row, dst), levels. Returns what a test needs."""
-    m, o, r, a = _oracle(stcsp, RefOracle, name, adversarial)
+    m, o, r, a = _oracle(stcsp, RefOracle, name, adversarial, prefix_k)
     mask = which if isinstance(which, list) else R.resolve_mask(m, which)
     valid, final, alive = a.flags()
     y = M.Yardstick(r, valid, final, alive, mask)

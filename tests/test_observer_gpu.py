@@ -36,8 +36,8 @@ def text_of(stcsp, name):
 
 
 @functools.lru_cache(maxsize=2)
-def oracle_of(stcsp, RefOracle, name):
-    m = stcsp.Model(text=text_of(stcsp, name))
+def oracle_of(stcsp, RefOracle, name, prefix_k=2):
+    m = stcsp.Model(text=text_of(stcsp, name), prefix_k=prefix_k)
     o = RefOracle(m)
     r = o.solve()
     a = o.automaton(r).traverse()
@@ -56,7 +56,7 @@ def same(a, b):
     return all(a[k] == b[k] for k in SCALARS) and all(np.array_equal(a[k], b[k]) for k in ARRAYS)
 
 
-def check_device(stcsp, RefOracle, name, which, max_states=0, oracle=True):
+def check_device(stcsp, RefOracle, name, which, max_states=0, oracle=True, prefix_k=2):
     """Device == twin, exactly and array by array; device == yardstick after mapping the members through the canonical numbers."""
     m, e, r, post, host = solved(stcsp, name)
     mask = which if isinstance(which, list) else R.resolve_mask(m, which)
@@ -66,7 +66,7 @@ def check_device(stcsp, RefOracle, name, which, max_states=0, oracle=True):
     twin = host.observer(mask, max_states)
     assert same(dev, twin), f"{name} [{which}]: device and host twin differ"
     if oracle:
-        mo, o, ro, ao = oracle_of(stcsp, RefOracle, name)
+        mo, o, ro, ao = oracle_of(stcsp, RefOracle, name, prefix_k)
         ovalid, ofinal, oalive = ao.flags()
         expect = R.subset_construction(M.Yardstick(ro, ovalid, ofinal, oalive, mask))
         valid, final, alive = Q.post_flags(post)

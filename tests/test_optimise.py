@@ -91,8 +91,8 @@ def check_mean(a, ref, w, comps=None, res_of=None):
     return res
 
 
-def check_host_twin(stcsp, RefOracle, name, adversarial=None):
-    m, r, a, (valid, final, alive), ref, _ = oracle_case(stcsp, RefOracle, name, adversarial)
+def check_host_twin(stcsp, RefOracle, name, adversarial=None, prefix_k=2):
+    m, r, a, (valid, final, alive), ref, _ = oracle_case(stcsp, RefOracle, name, adversarial, prefix_k)
     for w in (small_weights(m.n_vars), big_weights(m.n_vars)):
         for maximise in (False, True):
             for end_final in (False, True):

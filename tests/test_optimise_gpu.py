@@ -54,7 +54,7 @@ def same(x, y):
         p[0] == q[0] and np.array_equal(p[1], q[1]) and np.array_equal(p[2], q[2]) for p, q in zip(x["witnesses"], y["witnesses"]))
 
 
-def check_device(stcsp, name, w, interval=False, RefOracle=None):
+def check_device(stcsp, name, w, interval=False, RefOracle=None, prefix_k=2):
     """Device == twin for every flag, == the yardstick on the engine's automaton; with RefOracle also == the oracle's automaton."""
     m, e, r, (valid, final, alive), a = device_case(stcsp, name, interval)
     ref = engine_ref(stcsp, name, interval)
@@ -70,7 +70,7 @@ def check_device(stcsp, name, w, interval=False, RefOracle=None):
     dev = check_mean(a, ref, w, comps=comps, res_of=lambda **k: e.optimise(w, **k))
     assert CR.same(e.components("all"), comps)
     if RefOracle is not None:
-        mo, ro, ao, (_, final_o, _), ref_o, _ = oracle_case(stcsp, RefOracle, name)
+        mo, ro, ao, (_, final_o, _), ref_o, _ = oracle_case(stcsp, RefOracle, name, None, prefix_k)
         for maximise in (False, True):
             kw = dict(horizon=9, lengths=[0, 1, 6, 9], maximise=maximise, mean=True)
             d, o = e.optimise(w, **kw), ao.optimise(w, **kw)

@@ -87,10 +87,10 @@ def longest_enumerable(y, limit=5000, cap=7):
     return max([t for t in range(1, cap + 1) if 0 < y.n_paths(t) <= limit], default=0)
 
 
-def check_twin(stcsp, RefOracle, text, what, mask_names=("default", "all", "hidden"), length=None, brute=True, seed=1, first=0, most=100):
+def check_twin(stcsp, RefOracle, text, what, mask_names=("default", "all", "hidden"), length=None, brute=True, seed=1, first=0, most=100, prefix_k=2):
     """Twin == the yardstick's recurrence == its brute force on seeded streams, all four outputs; and the properties of the
     contract against the monitor's and the generator's host twins."""
-    m, o, r, a = solved(stcsp, RefOracle, text)
+    m, o, r, a = solved(stcsp, RefOracle, text, prefix_k)
     valid, final, alive = a.flags()
     for name, mask in M.masks(m, r).items():
         if name not in mask_names:
