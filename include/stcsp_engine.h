@@ -595,6 +595,108 @@ typedef struct stcsp_infer_result {
 
 int stcsp_engine_infer(stcsp_engine *engine, const stcsp_infer_request *request, stcsp_infer_result *result);
 
+/* ---- posterior marginals of the unobserved entries of a stream, under value weights, on the device (no reference counterpart) ----
+ * stcsp_engine_infer() says which values an entry that was not seen can take and how many solution prefixes fit the
+ * stream. This says how many of them give each value: the per-edge products A * B of the forward-backward pass, with a
+ * weight on every edge. Live automaton, projected label p_e, default mask, the canonical order of a state's live
+ * out-edges, the match of an edge and a row, the label ids, the per-variable sorted value dictionaries and
+ * vidx[label][v] are exactly those of stcsp_engine_infer().
+ *
+ * Input. Streams in the repair's / infer's format (n_streams, offsets in steps, values), STCSP_POSTERIOR_MISSING ==
+ * STCSP_INFER_MISSING meaning "not observed"; flags; optional value weights as CSR over the observable variables, in
+ * mask order: weight_off[n_observable + 1] (int64, weight_off[0] == 0, not decreasing), weight_val[] (int32, strictly
+ * increasing inside a variable), weight_w[] (int32, each >= 0). A value that is not listed weighs 1. All three NULL:
+ * every value weighs 1. Values out of order or listed twice, a negative weight, malformed offsets or one of the three
+ * arrays missing where it is needed: STCSP_E_INVALID.
+ *
+ * Label weight. w(l) = the product over the observable variables v, in variable order, of the weight of p_l[v]: doubles,
+ * starting from 1.0, one multiplication at a time. It may be +inf. The weight of an edge is that of its label.
+ *
+ * Weight to go, for a stream of len steps. B_0(s) = 1 on the live states (with STCSP_POSTERIOR_END_FINAL: final[s]).
+ * B_{r+1}(s) = the sum over the live out-edges e of s, in canonical order, of w(e) * B_r(dst(e)), over the edges that
+ * match step len-r-1 and have w(e) > 0 and B_r(dst(e)) > 0. A term that fails one of the three is skipped, not
+ * multiplied: 0 * inf never arises, and no NaN. Each term is one multiplication, then one addition to the running sum
+ * that starts at 0: IEEE doubles, no fused multiply-add, no reassociation. mass[i] = B_len(root), 0 without a live root.
+ * With all weights 1, mass[i] is stcsp_engine_infer()'s count[i], bit for bit.
+ *
+ * Exactness. exact[i] = mass[i] < 2^53. Every partial result is a non-negative double and rounding is monotone, so a
+ * computed root mass below 2^53 means every term under it was below 2^53, hence an exact integer; and on every state s
+ * reachable at level t over matching edges of positive weight with weight to go, A_t(s) * B_{len-t}(s) <= mass. For an
+ * exact stream every quantity below is therefore an integer below 2^53; the forward pass runs in uint64_t, the order of
+ * its additions does not matter, and no floating-point atomic is used anywhere. A stream that is not exact still gets
+ * its mass (the double the fixed order gives, possibly +inf), exact = 0, final_mass = 0 and empty marginals: no error,
+ * and the other streams of the call are answered in full.
+ *
+ * Forward, exact streams only. A_0(root) = 1 if mass > 0, 0 elsewhere. Edge e is feasible at t iff A_t(src(e)) > 0, e
+ * matches x_t, w(e) > 0 and B_{len-t-1}(dst(e)) > 0. A_{t+1}(d) = the sum over the edges feasible at t into d of
+ * A_t(src) * w. With all weights positive this is stcsp_engine_infer()'s feasibility.
+ *
+ * Answer per stream i.
+ *   mass[i], exact[i], feasible[i] = mass[i] > 0.
+ *   final_mass[i]  the sum of A_len(s) over the final states s. With END_FINAL it equals mass[i].
+ *   marginals      for every (step t, observable variable v) of the request, in the input's row order, as CSR:
+ *                  marg_off[total_steps * n_observable + 1] (int64), marg_val[] (int32, sorted, distinct), marg_mass[]
+ *                  (uint64): the values a with m(t, v, a) > 0, where m(t, v, a) = the sum over the edges e feasible at
+ *                  t with p_e[v] == a of A_t(src) * w(e) * B_{len-t-1}(dst).
+ * Integers, and doubles multiplied and added in a fixed order: the device, the host twin
+ * (stcsp_automaton_posterior_streams() of stcsp_host.h) and any IEEE implementation of this text agree exactly.
+ *
+ * Consequences (tests/test_posterior.py checks each).
+ *   (a) For every (t, v) of an exact feasible stream the marginal masses sum to mass.
+ *   (b) With all weights positive the values of a marginal are exactly stcsp_engine_infer()'s support of that entry.
+ *   (c) An observed entry of an exact feasible stream has the one-element marginal {value: mass}.
+ *   (d) Replacing a MISSING entry by a value a gives a stream whose mass is m(t, v, a); a value outside the marginal
+ *       gives 0.
+ *   (e) A weight of 0 on a value gives what deleting every edge that carries it would give.
+ *   (f) Multiplying every weight of one variable by c multiplies mass and every marginal by c^len, while exact.
+ *   (g) L rows of MISSING with all weights 1 give the generator's count[L] under the same END_FINAL.
+ *
+ * posterior() needs a valid stcsp_engine_generator_build() and builds or reuses the repair's label ids and the infer's
+ * dictionaries. STCSP_E_STATE, STCSP_E_UNSUPPORTED and STCSP_E_INVALID as for stcsp_engine_infer(). The label weights
+ * are computed once per call in one launch over the labels. The request is cut, in its order, into consecutive batches
+ * of at most 65,535 streams whose structures fit a byte budget: [stream][len + 1][n_states] doubles (B), two rolling
+ * rows [stream][2][n_states] of uint64 (A: the marginals of step t need A_t only), [step][n_labels] bytes (match) and
+ * uint64 (the per-label masses) and [step][bins] uint64, one bin per (variable, dictionary value); by default half of
+ * the free device memory, the environment variable STCSP_POSTERIOR_BYTES sets it. STCSP_E_NOMEM only when a SINGLE
+ * stream does not fit. STCSP_REPAIR_WAVE_SEGMENT applies to the forward sweep as in infer. Results are owned by the
+ * engine until the next call on it. The call invalidates nothing of the generator, monitor, repair or infer; its own
+ * structures fall wherever the generator's do. */
+#define STCSP_POSTERIOR_END_FINAL 1             /* only the completions that end in a final state */
+#define STCSP_POSTERIOR_MISSING (-2147483647 - 1) /* == STCSP_INFER_MISSING */
+
+typedef struct stcsp_posterior_request {
+    int64_t n_streams;
+    const int64_t *offsets;    /* [n_streams + 1] in steps: offsets[0] == 0, not decreasing, every stream < 2^31 steps */
+    const int32_t *values;     /* [offsets[n_streams] * n_observable]                                                  */
+    const int64_t *weight_off; /* [n_observable + 1]; NULL with the two below = every value weighs 1                   */
+    const int32_t *weight_val; /* [weight_off[n_observable]] strictly increasing inside a variable                     */
+    const int32_t *weight_w;   /* [weight_off[n_observable]] each >= 0                                                 */
+    int32_t flags;             /* STCSP_POSTERIOR_*                                                                    */
+    int32_t reserved;
+} stcsp_posterior_request;
+
+typedef struct stcsp_posterior_result {
+    int64_t n_streams;
+    const double *mass;         /* [n_streams] owned by the engine, valid until the next call on it             */
+    const uint8_t *exact;       /* [n_streams] mass < 2^53                                                      */
+    const uint8_t *feasible;    /* [n_streams] mass > 0                                                         */
+    const uint64_t *final_mass; /* [n_streams]                                                                  */
+    const int64_t *marg_off;    /* [offsets[n_streams] * n_observable + 1]                                      */
+    const int32_t *marg_val;    /* [marg_off[last]]                                                             */
+    const uint64_t *marg_mass;  /* [marg_off[last]]                                                             */
+    int64_t n_labels;           /* distinct projected labels of the live automaton                              */
+    int64_t table_bytes;        /* HBM of the largest batch: B, A, match, per-label masses, bins                */
+    int32_t n_batches;          /* 0 without streams or without a live root: nothing runs on the device         */
+    int32_t n_observable;
+    double seconds;             /* wall time from the host input to the host output                             */
+    double seconds_weights;     /* HIP-event times, all batches: the label weights and the match kernel         */
+    double seconds_backward;    /* level 0, the backward levels and the masses                                  */
+    double seconds_forward;     /* the forward levels and final_mass                                            */
+    double seconds_bins;        /* the bins                                                                     */
+} stcsp_posterior_result;
+
+int stcsp_engine_posterior(stcsp_engine *engine, const stcsp_posterior_request *request, stcsp_posterior_result *result);
+
 /* ---- the observer of the live automaton: subset construction on the device (no reference counterpart) ----------------
  * Under a mask that hides a variable the live automaton is nondeterministic in its projected labels. The observer is the
  * deterministic automaton whose states are the sets of automaton states the system can be in after an observed prefix:

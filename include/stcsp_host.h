@@ -164,6 +164,18 @@ int stcsp_automaton_infer_streams(const stcsp_automaton *a, const uint8_t *obser
                                   const int32_t *values, int32_t draws, const uint64_t *ranks, uint64_t seed, double *count, int64_t *support_off,
                                   int32_t **support_val, int32_t *n_states, int32_t *draw_values, uint8_t *end_final);
 
+/* ---- posterior marginals of the unobserved entries of a stream (definition: stcsp_engine.h, stcsp_engine_posterior) ----
+ * The same contract written plainly, on the automaton's current flags: the checker of the device pass in the tests, and
+ * the path for automata whose flags live on the host (sharded runs, host adversarial passes, read_binary). observable:
+ * as in stcsp_automaton_bisimulation(); flags: STCSP_POSTERIOR_*; offsets / values: the streams (STCSP_POSTERIOR_MISSING
+ * = not observed); weight_off / weight_val / weight_w: the value weights as there, all NULL = every value weighs 1.
+ * mass, exact, final_mass: [n_streams]; marg_off: [offsets[n_streams] * (number of observable variables) + 1];
+ * *marg_val and *marg_mass receive the marginals in two blocks the caller releases with stcsp_host_free().
+ * STCSP_E_INVALID as there. */
+int stcsp_automaton_posterior_streams(const stcsp_automaton *a, const uint8_t *observable, int32_t flags, int64_t n_streams, const int64_t *offsets,
+                                      const int32_t *values, const int64_t *weight_off, const int32_t *weight_val, const int32_t *weight_w,
+                                      double *mass, uint8_t *exact, uint64_t *final_mass, int64_t *marg_off, int32_t **marg_val, uint64_t **marg_mass);
+
 /* ---- the observer: subset construction under a mask (definition: stcsp_engine.h, stcsp_engine_observer) ----
  * The same contract written plainly with ordered containers, on the automaton's current flags: the checker of the device
  * pass in the tests, and the path for automata whose flags live on the host (sharded runs, host adversarial passes,

@@ -241,6 +241,59 @@ def _infer_unpack(count, soff, sval, nst, dvals, dfin, offsets, n_obs, draws):
         fin.append(dfin[i * draws:(i + 1) * draws].copy())
     return count, supports, n_states, out, fin
 
+
+class PosteriorRequest(C.Structure):
+    _fields_ = [("n_streams", C.c_int64), ("offsets", C.POINTER(C.c_int64)), ("values", C.POINTER(C.c_int32)),
+                ("weight_off", C.POINTER(C.c_int64)), ("weight_val", C.POINTER(C.c_int32)), ("weight_w", C.POINTER(C.c_int32)),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PosteriorResult(C.Structure):
+    _fields_ = [("n_streams", C.c_int64), ("mass", C.POINTER(C.c_double)), ("exact", C.POINTER(C.c_uint8)), ("feasible", C.POINTER(C.c_uint8)),
+                ("final_mass", C.POINTER(C.c_uint64)), ("marg_off", C.POINTER(C.c_int64)), ("marg_val", C.POINTER(C.c_int32)),
+                ("marg_mass", C.POINTER(C.c_uint64)), ("n_labels", C.c_int64), ("table_bytes", C.c_int64), ("n_batches", C.c_int32),
+                ("n_observable", C.c_int32), ("seconds", C.c_double), ("seconds_weights", C.c_double), ("seconds_backward", C.c_double),
+                ("seconds_forward", C.c_double), ("seconds_bins", C.c_double)]
+
+
+POSTERIOR_END_FINAL = 1       # posterior_streams(end_final=True): only the completions that end in a final state
+POSTERIOR_MISSING = -2 ** 31  # a value of a row that was not observed (== INFER_MISSING)
+
+
+def _posterior_weights(weights, n_obs):
+    """None, or per observable variable a dict value -> weight or None -> the CSR (weight_off int64 [n_obs + 1], weight_val int32,
+    weight_w int32) of the contract, or (None, None, None). An item list [(value, weight), ...] is taken in its order, so that a
+    request that is out of order can be written down."""
+    import numpy as np
+    if weights is None:
+        return None, None, None
+    if len(weights) != n_obs:
+        raise ValueError(f"weights must have one entry per observable variable ({n_obs})")
+    off, val, w = [0], [], []
+    for d in weights:
+        items = [] if d is None else sorted(d.items()) if isinstance(d, dict) else list(d)
+        for value, weight in items:
+            if not (-2 ** 31 <= int(value) < 2 ** 31 and -2 ** 31 <= int(weight) < 2 ** 31):
+                raise StcspError(-1, "a weighted value or a weight does not fit an int32")
+            val.append(int(value))
+            w.append(int(weight))
+        off.append(len(val))
+    return np.array(off, np.int64), np.array(val + [0], np.int32), np.array(w + [0], np.int32)
+
+
+def _posterior_unpack(mass, exact, fmass, moff, mval, mmass, offsets, n_obs):
+    """The flat outputs of a posterior call -> (mass float64 [n], exact uint8 [n], final_mass list of ints, marginals):
+    marginals[i][t][v] is the list of (value, mass) pairs of Python ints, in value order."""
+    n = len(offsets) - 1
+    moff = moff.tolist()
+    pairs = list(zip(mval.tolist(), mmass.tolist()))
+    marginals = []
+    for i in range(n):
+        a, b = int(offsets[i]), int(offsets[i + 1])
+        marginals.append([[pairs[moff[t * n_obs + v]:moff[t * n_obs + v + 1]] for v in range(n_obs)] for t in range(a, b)])
+    return mass, exact, [int(x) for x in fmass.tolist()], marginals
+
+
 class ObserverOptions(C.Structure):
     _fields_ = [("max_states", C.c_int64), ("reserved", C.c_int32 * 2)]
 
@@ -467,7 +520,7 @@ ENGINE_SYMBOLS = [
     "stcsp_engine_propagate", "stcsp_engine_set_expand_budget", "stcsp_engine_node_bytes", "stcsp_engine_donate",
     "stcsp_engine_adopt", "stcsp_engine_expand_variant", "stcsp_engine_kernel_choice", "stcsp_engine_quotient",
     "stcsp_engine_monitor_build", "stcsp_engine_monitor_check", "stcsp_engine_generator_build", "stcsp_engine_generate",
-    "stcsp_engine_repair", "stcsp_engine_infer", "stcsp_engine_observer", "stcsp_engine_compare",
+    "stcsp_engine_repair", "stcsp_engine_infer", "stcsp_engine_posterior", "stcsp_engine_observer", "stcsp_engine_compare",
     "stcsp_engine_components", "stcsp_engine_optimise",
 ]
 # include/stcsp_sharded.h: the superstep loop + in-process transport (libstcsp_hip.so), the RCCL transport (libstcsp_rccl.so)
@@ -484,7 +537,7 @@ HOST_SYMBOLS = [
     "stcsp_merge_shards", "stcsp_merged_result", "stcsp_merged_free", "stcsp_host_free",
     "stcsp_automaton_bisimulation", "stcsp_automaton_set_observable", "stcsp_automaton_quotient",
     "stcsp_automaton_check_streams", "stcsp_automaton_num_observable", "stcsp_automaton_generate", "stcsp_automaton_count_streams",
-    "stcsp_automaton_repair_streams", "stcsp_automaton_infer_streams",
+    "stcsp_automaton_repair_streams", "stcsp_automaton_infer_streams", "stcsp_automaton_posterior_streams",
     "stcsp_automaton_observer", "stcsp_observer_get", "stcsp_observer_free", "stcsp_automaton_from_observer",
     "stcsp_compare_observers", "stcsp_comparison_get", "stcsp_comparison_free", "stcsp_automaton_num_vars", "stcsp_automaton_var_name",
     "stcsp_automaton_components", "stcsp_components_get", "stcsp_components_free",
@@ -570,6 +623,9 @@ def host_lib() -> C.CDLL:
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.stcsp_automaton_infer_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                                       C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.stcsp_automaton_posterior_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                                          C.POINTER(C.c_void_p)]
         lib.stcsp_automaton_observer.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
         lib.stcsp_observer_get.argtypes = [C.c_void_p]
         lib.stcsp_observer_get.restype = C.POINTER(ObserverResult)
@@ -646,6 +702,8 @@ def bind_engine_api(lib: C.CDLL, prefix: str = "stcsp_engine") -> None:
         g("repair").argtypes = [C.c_void_p, C.POINTER(RepairRequest), C.POINTER(RepairResult)]
     if hasattr(lib, f"{prefix}_infer"):
         g("infer").argtypes = [C.c_void_p, C.POINTER(InferRequest), C.POINTER(InferResult)]
+    if hasattr(lib, f"{prefix}_posterior"):
+        g("posterior").argtypes = [C.c_void_p, C.POINTER(PosteriorRequest), C.POINTER(PosteriorResult)]
     if hasattr(lib, f"{prefix}_observer"):
         g("observer").argtypes = [C.c_void_p, C.POINTER(ObserverOptions), C.POINTER(ObserverResult)]
     if hasattr(lib, f"{prefix}_compare"):
@@ -969,6 +1027,39 @@ class Automaton:
         vals = np.ctypeslib.as_array(C.cast(sval, C.POINTER(C.c_int32)), shape=(max(total, 1),))[:total].copy()
         lib.stcsp_host_free(sval)
         return _infer_unpack(count[:n], soff, vals, nst, dvals, dfin, offsets, n_obs, max(draws, 0))
+
+    def posterior_streams(self, streams, observable=None, end_final=False, weights=None):
+        """How many solution prefixes give each value of the unobserved entries of partially observed streams, by the host twin
+        of Engine.posterior_streams() (contract: include/stcsp_engine.h, stcsp_engine_posterior), on the automaton's current
+        flags. `streams` as in pack_streams(), a value POSTERIOR_MISSING = not observed; `observable` as in bisimulation();
+        `weights`: per observable variable, in mask order, a dict value -> non-negative int weight or None (None: all 1).
+        Returns (mass float64 [n], exact uint8 [n], final_mass list of ints, marginals): marginals[i][t][v] is the list of
+        (value, mass) pairs of Python ints in value order; empty for a stream that is not exact or not feasible."""
+        import numpy as np
+        lib = host_lib()
+        m = self._mask(observable)
+        mp = m.ctypes.data if m is not None else None
+        n_obs = lib.stcsp_automaton_num_observable(self._h, mp)
+        values, offsets = pack_streams(streams, n_obs)
+        n = len(offsets) - 1
+        steps = max(int(offsets[n]), 0) if n else 0
+        woff, wval, ww = _posterior_weights(weights, n_obs)
+        mass, exact, fmass = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint64)
+        moff = np.zeros(steps * n_obs + 1, np.int64)
+        mval, mmass = C.c_void_p(), C.c_void_p()
+        rc = lib.stcsp_automaton_posterior_streams(self._h, mp, POSTERIOR_END_FINAL if end_final else 0, n, offsets.ctypes.data,
+                                                   values.ctypes.data if values.size else None, woff.ctypes.data if woff is not None else None,
+                                                   wval.ctypes.data if woff is not None else None, ww.ctypes.data if woff is not None else None,
+                                                   mass.ctypes.data, exact.ctypes.data, fmass.ctypes.data, moff.ctypes.data, C.byref(mval),
+                                                   C.byref(mmass))
+        if rc != 0:
+            raise StcspError(rc, "posterior_streams failed: malformed offsets, or weights that are not strictly increasing values with weights >= 0")
+        total = int(moff[-1])
+        vals = np.ctypeslib.as_array(C.cast(mval, C.POINTER(C.c_int32)), shape=(max(total, 1),))[:total].copy()
+        masses = np.ctypeslib.as_array(C.cast(mmass, C.POINTER(C.c_uint64)), shape=(max(total, 1),))[:total].copy()
+        lib.stcsp_host_free(mval)
+        lib.stcsp_host_free(mmass)
+        return _posterior_unpack(mass[:n], exact[:n], fmass[:n], moff, vals, masses, offsets, n_obs)
 
     def observer(self, observable=None, max_states=0):
         """The observer (subset construction) of the live automaton under `observable` (as in bisimulation()) by the host twin
@@ -1356,6 +1447,37 @@ class EngineBase:
         soff = arr(out.support_off, steps * n_obs + 1, np.int64)
         return _infer_unpack(arr(out.count, n, np.float64), soff, arr(out.support_val, int(soff[-1]), np.int32), arr(out.n_states, steps + n, np.int32),
                              arr(out.values, steps * draws * n_obs, np.int32), arr(out.end_final, n * draws, np.uint8), offsets, n_obs, draws)
+
+    def posterior_streams(self, streams, end_final=False, weights=None):
+        """How many solution prefixes give each value of the unobserved entries of partially observed streams, on the device,
+        after generator() (its mask; its horizon does not limit the streams). `streams` as for check_streams(), a value
+        POSTERIOR_MISSING = not observed; `weights`: per observable variable, in mask order, a dict value -> non-negative int
+        weight or None (None: all 1). Returns (mass float64 [n], exact, final_mass, marginals) as Automaton.posterior_streams()
+        does; the whole PosteriorResult of the call is kept in self.posterior_result. Contract: include/stcsp_engine.h,
+        stcsp_engine_posterior."""
+        import numpy as np
+        if getattr(self, "generator_info", None) is None:
+            raise StcspError(-6, "posterior_streams() needs generator() first")
+        n_obs = self.generator_info.n_observable
+        values, offsets = pack_streams(streams, n_obs)
+        n = len(offsets) - 1
+        steps = max(int(offsets[n]), 0) if n else 0
+        woff, wval, ww = _posterior_weights(weights, n_obs)
+        rq = PosteriorRequest(n, offsets.ctypes.data_as(C.POINTER(C.c_int64)), values.ctypes.data_as(C.POINTER(C.c_int32)) if values.size else None,
+                              woff.ctypes.data_as(C.POINTER(C.c_int64)) if woff is not None else None,
+                              wval.ctypes.data_as(C.POINTER(C.c_int32)) if woff is not None else None,
+                              ww.ctypes.data_as(C.POINTER(C.c_int32)) if woff is not None else None, POSTERIOR_END_FINAL if end_final else 0, 0)
+        out = PosteriorResult()
+        self._check(self._f("posterior")(self._h, C.byref(rq), C.byref(out)))
+        self.posterior_result = out
+
+        def arr(ptr, size, dtype):
+            return np.ctypeslib.as_array(ptr, shape=(size,)).copy() if size else np.zeros(0, dtype)
+
+        moff = arr(out.marg_off, steps * n_obs + 1, np.int64)
+        total = int(moff[-1])
+        return _posterior_unpack(arr(out.mass, n, np.float64), arr(out.exact, n, np.uint8), arr(out.final_mass, n, np.uint64), moff,
+                                 arr(out.marg_val, total, np.int32), arr(out.marg_mass, total, np.uint64), offsets, n_obs)
 
     def observer(self, max_states=0):
         """The observer (subset construction) of the live automaton on the device, after generator() (its mask; its horizon plays

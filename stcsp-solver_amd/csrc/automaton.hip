@@ -1,5 +1,5 @@
 // automaton.hip -- the host side of the services on the exported automaton: post-processing, bisimulation quotient, stream monitor,
-// generator, repair, inference, observer and comparison, with the kernels they launch. No kernel is shared with the search (engine.hip).
+// generator, repair, inference, posterior marginals, observer and comparison, with the kernels they launch. No kernel is shared with the search (engine.hip).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -17,12 +17,14 @@
 #include "generate_host.hpp"
 #include "dev_repair.hpp"
 #include "dev_infer.hpp"
+#include "dev_posterior.hpp"
 #include "dev_observer.hpp"
 #include "dev_compare.hpp"
 #include "dev_components.hpp"
 #include "dev_optimise.hpp"
 #include "repair_host.hpp"
 #include "infer_host.hpp"
+#include "posterior_host.hpp"
 
 namespace stcsp {
 using namespace dev;
@@ -947,6 +949,162 @@ int AutomatonServices::infer(const AutomatonView &view, const stcsp_infer_reques
     }
     if (i_sval.empty()) i_sval.reserve(1);
     publish();
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return STCSP_OK;
+}
+
+// Posterior marginals of partially observed streams under value weights (contract: stcsp_engine.h).
+int AutomatonServices::posterior(const AutomatonView &view, const stcsp_posterior_request *rq, stcsp_posterior_result *out) {
+    if (int rc = enter(view, "posterior", NEED_GENERATOR, "stcsp_automaton_posterior_streams")) return rc;
+    if (!posterior_request_ok(rq->n_streams, rq->offsets, gen_n_obs, rq->weight_off, rq->weight_val, rq->weight_w))
+        return fail(STCSP_E_INVALID, "posterior: malformed stream offsets, or weights that are not a CSR of strictly increasing values and weights >= 0");
+    auto t0 = std::chrono::steady_clock::now();
+    const size_t n = (size_t)rq->n_streams, n_obs = (size_t)gen_n_obs;
+    const size_t steps = n ? (size_t)rq->offsets[n] : 0;
+    if (steps && n_obs && !rq->values) return fail(STCSP_E_INVALID, "posterior: no step values");
+    y_mass.assign(n, 0.0);
+    y_exact.assign(n, 1);
+    y_feas.assign(n, 0);
+    y_fmass.assign(n, 0);
+    y_moff.assign(steps * n_obs + 1, 0);
+    y_mval.clear();
+    y_mmass.clear();
+    memset(out, 0, sizeof *out);
+    out->n_streams = rq->n_streams;
+    out->n_observable = gen_n_obs;
+    if (n && root_live) {
+        if (int rc = rep_built ? STCSP_OK : repair_labels()) return rc;
+        if (int rc = inf_built ? STCSP_OK : infer_dictionaries()) return rc;
+        const uint32_t S = v.n_states, nL = rep_n_labels;
+        const int end_final = (rq->flags & STCSP_POSTERIOR_END_FINAL) ? 1 : 0;
+        // one bin per (variable, dictionary value), and the weight of each
+        std::vector<uint32_t> bin_off(n_obs, 0);
+        std::vector<double> wbin;
+        for (size_t x = 0; x < n_obs; x++) {
+            bin_off[x] = (uint32_t)wbin.size();
+            for (int32_t value : inf_dict[x]) wbin.push_back(posterior_value_weight((int)x, value, rq->weight_off, rq->weight_val, rq->weight_w));
+            if (wbin.size() > 0x7fffffffull) return fail(STCSP_E_NOMEM, "posterior: the bins of one step are too many");
+        }
+        const uint32_t nB = (uint32_t)wbin.size();
+        size_t budget = 0;
+        if (int rc = table_budget("STCSP_POSTERIOR_BYTES", budget)) return rc;
+        auto need = [&](size_t len) {
+            return (len + 1) * (size_t)S * sizeof(double) + 2 * (size_t)S * sizeof(uint64_t) + len * ((size_t)nL * (1 + sizeof(uint64_t)) + (size_t)nB * sizeof(uint64_t));
+        };
+        HIPCHK(ev.ready(7));
+        HIPCHK(d_yw.reserve(nL));
+        HIPCHK(d_ywbin.reserve(nB));
+        if (d_yboff.n < n_obs) HIPCHK(d_yboff.alloc(n_obs + 16));
+        if (nB) HIPCHK(hipMemcpyAsync(d_ywbin.p, wbin.data(), (size_t)nB * sizeof(double), hipMemcpyHostToDevice, v.stream));
+        if (n_obs) HIPCHK(hipMemcpyAsync(d_yboff.p, bin_off.data(), n_obs * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+        HIPCHK(hipEventRecord(ev[5], v.stream));
+        if (nL)
+            hipLaunchKernelGGL(k_p_label_weight, dim3((nL + 255) / 256), dim3(256), 0, v.stream, nL, (const uint32_t *)d_ividx.p, (const uint32_t *)d_yboff.p,
+                               gen_n_obs, (const double *)d_ywbin.p, d_yw.p);
+        HIPCHK(hipEventRecord(ev[6], v.stream));
+        HIPCHK(hipGetLastError());
+        bool first_batch = true;
+        std::vector<InfStream> meta;
+        const unsigned sb = (S + 255) / 256;
+        for (size_t b0 = 0; b0 < n;) {
+            Batch b;  // consecutive streams while their structures fit the budget
+            if (int rc = plan_batch("posterior", rq->offsets, n, b0, budget, need, meta, b)) return rc;
+            const size_t nb = b.b1 - b0, cells = b.steps * n_obs, marks = b.steps * (size_t)nL, bins = b.steps * (size_t)nB, rows_a = nb * 2 * (size_t)S;
+            const size_t first_step = (size_t)rq->offsets[b0], first = first_step * n_obs;
+            if (!(d_yB.reserve_or_release(b.entries) && d_yA.reserve_or_release(rows_a) && d_ymatch.reserve_or_release(marks) &&
+                  d_ylab.reserve_or_release(marks) && d_ybins.reserve_or_release(bins))) {
+                d_yB.release();
+                d_yA.release();
+                d_ymatch.release();
+                d_ylab.release();
+                d_ybins.release();
+                return fail(STCSP_E_NOMEM, "posterior: no room for %zu bytes of tables", b.bytes);
+            }
+            HIPCHK(reserve_all(nb, 0, d_ystreams, d_ymass, d_yexact, d_yfmass));
+            HIPCHK(d_yrows.reserve(cells));
+            HIPCHK(hipMemcpyAsync(d_ystreams.p, meta.data(), nb * sizeof(InfStream), hipMemcpyHostToDevice, v.stream));
+            if (cells) HIPCHK(hipMemcpyAsync(d_yrows.p, rq->values + first, cells * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+            HIPCHK(hipMemsetAsync(d_yA.p, 0, rows_a * sizeof(uint64_t), v.stream));
+            HIPCHK(hipMemsetAsync(d_yfmass.p, 0, nb * sizeof(uint64_t), v.stream));
+            if (marks) HIPCHK(hipMemsetAsync(d_ylab.p, 0, marks * sizeof(uint64_t), v.stream));
+            if (bins) HIPCHK(hipMemsetAsync(d_ybins.p, 0, bins * sizeof(uint64_t), v.stream));
+            const unsigned step_rows = (unsigned)std::min<size_t>(std::max<size_t>(b.steps, 1), 65535);
+            HIPCHK(hipEventRecord(ev[0], v.stream));
+            if (marks)
+                hipLaunchKernelGGL(k_i_match, dim3((nL + 255) / 256, step_rows), dim3(256), 0, v.stream, nL, (uint32_t)b.steps, (const uint32_t *)d_rrep.p,
+                                   (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p, gen_n_obs, (const int32_t *)d_yrows.p, d_ymatch.p);
+            HIPCHK(hipEventRecord(ev[1], v.stream));
+            hipLaunchKernelGGL(k_p_level0, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, (const InfStream *)d_ystreams.p, (const uint8_t *)d_live.p,
+                               (const uint8_t *)d_pfinal.p, end_final, d_yB.p);
+            for (uint32_t r = 1; r <= (uint32_t)b.longest; r++)
+                hipLaunchKernelGGL(k_p_backward, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, r, (const InfStream *)d_ystreams.p,
+                                   (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_ymatch.p,
+                                   (const double *)d_yw.p, d_yB.p);
+            hipLaunchKernelGGL(k_p_root, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)nb, (const InfStream *)d_ystreams.p, S,
+                               (const double *)d_yB.p, d_yA.p, d_ymass.p, d_yexact.p);
+            HIPCHK(hipEventRecord(ev[2], v.stream));
+            for (uint32_t t = 0; t < (uint32_t)b.longest; t++) {
+                if (rep_n_long)  // before k_p_forward, which clears A_t
+                    hipLaunchKernelGGL(k_p_forward_long, dim3((rep_n_long + 3) / 4, (unsigned)nb), dim3(256), 0, v.stream, rep_n_long,
+                                       (const uint32_t *)d_rlong.p, S, t, (const InfStream *)d_ystreams.p, (const uint32_t *)d_goff.p,
+                                       (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_ymatch.p, (const double *)d_yw.p,
+                                       (const double *)d_yB.p, d_yA.p, d_ylab.p);
+                hipLaunchKernelGGL(k_p_forward, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, t, (const InfStream *)d_ystreams.p,
+                                   (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_ymatch.p,
+                                   (const double *)d_yw.p, (const double *)d_yB.p, rep_wave_segment, d_yA.p, d_ylab.p);
+            }
+            hipLaunchKernelGGL(k_p_final, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, (const InfStream *)d_ystreams.p, (const uint8_t *)d_pfinal.p,
+                               (const unsigned long long *)d_yA.p, d_yfmass.p);
+            HIPCHK(hipEventRecord(ev[3], v.stream));
+            if (marks && nB)
+                hipLaunchKernelGGL(k_p_bins, dim3((nL + 255) / 256, step_rows), dim3(256), 0, v.stream, nL, (uint32_t)b.steps,
+                                   (const unsigned long long *)d_ylab.p, (const uint32_t *)d_ividx.p, (const uint32_t *)d_yboff.p, gen_n_obs, nB, d_ybins.p);
+            HIPCHK(hipEventRecord(ev[4], v.stream));
+            HIPCHK(hipGetLastError());
+            y_bins.resize(bins);
+            HIPCHK(hipMemcpyAsync(y_mass.data() + b0, d_ymass.p, nb * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(y_exact.data() + b0, d_yexact.p, nb, hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(y_fmass.data() + b0, d_yfmass.p, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, v.stream));
+            if (bins) HIPCHK(hipMemcpyAsync(y_bins.data(), d_ybins.p, bins * sizeof(uint64_t), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipStreamSynchronize(v.stream));
+            // the bins -> sorted lists: dictionary order is value order
+            for (size_t step = 0; step < b.steps; step++)
+                for (size_t x = 0; x < n_obs; x++) {
+                    const unsigned long long *row = y_bins.data() + step * nB + bin_off[x];
+                    const std::vector<int32_t> &d = inf_dict[x];
+                    for (size_t k = 0; k < d.size(); k++)
+                        if (row[k]) {
+                            y_mval.push_back(d[k]);
+                            y_mmass.push_back((uint64_t)row[k]);
+                        }
+                    y_moff[(first_step + step) * n_obs + x + 1] = (int64_t)y_mval.size();
+                }
+            float ms[5] = {0, 0, 0, 0, 0};
+            for (int k = 0; k < 4; k++) HIPCHK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+            if (first_batch) HIPCHK(hipEventElapsedTime(&ms[4], ev[5], ev[6]));
+            first_batch = false;
+            out->seconds_weights += (ms[0] + ms[4]) * 1e-3;
+            out->seconds_backward += ms[1] * 1e-3;
+            out->seconds_forward += ms[2] * 1e-3;
+            out->seconds_bins += ms[3] * 1e-3;
+            out->n_batches++;
+            out->table_bytes = std::max<int64_t>(out->table_bytes, (int64_t)b.bytes);
+            b0 = b.b1;
+        }
+        for (size_t i = 0; i < n; i++) y_feas[i] = y_mass[i] > 0.0;
+        out->n_labels = nL;
+    }
+    if (y_mval.empty()) {
+        y_mval.reserve(1);
+        y_mmass.reserve(1);
+    }
+    out->mass = y_mass.data();
+    out->exact = y_exact.data();
+    out->feasible = y_feas.data();
+    out->final_mass = y_fmass.data();
+    out->marg_off = y_moff.data();
+    out->marg_val = y_mval.data();
+    out->marg_mass = y_mmass.data();
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;
 }

@@ -43,6 +43,7 @@ struct AutomatonServices {
     int generate(const AutomatonView &view, const stcsp_generate_request *rq, stcsp_generate_result *out);
     int repair(const AutomatonView &view, const stcsp_repair_request *rq, stcsp_repair_result *out);
     int infer(const AutomatonView &view, const stcsp_infer_request *rq, stcsp_infer_result *out);
+    int posterior(const AutomatonView &view, const stcsp_posterior_request *rq, stcsp_posterior_result *out);
     int observer(const AutomatonView &view, const stcsp_observer_options *oo, stcsp_observer_result *out);
     int compare(const AutomatonView &view, const stcsp_compare_request *rq, stcsp_compare_result *out);
     int components(const AutomatonView &view, const stcsp_components_options *co, stcsp_components_result *out);
@@ -126,6 +127,20 @@ private:
     std::vector<int64_t> i_soff;
     std::vector<int32_t> i_sval, i_nstates, i_values;
     std::vector<uint32_t> i_bits;
+    // posterior marginals (dev_posterior.hpp): everything lives for one call, on the label ids and dictionaries above; the
+    // vectors back the result until the next call
+    DevBuf<double> d_yB, d_yw, d_ywbin, d_ymass;
+    DevBuf<unsigned long long> d_yA, d_ylab, d_ybins, d_yfmass;
+    DevBuf<uint8_t> d_ymatch, d_yexact;
+    DevBuf<uint32_t> d_yboff;
+    DevBuf<int32_t> d_yrows;
+    DevBuf<dev::InfStream> d_ystreams;
+    std::vector<double> y_mass;
+    std::vector<uint8_t> y_exact, y_feas;
+    std::vector<uint64_t> y_fmass, y_mmass;
+    std::vector<unsigned long long> y_bins;
+    std::vector<int64_t> y_moff;
+    std::vector<int32_t> y_mval;
     // observer (dev_observer.hpp): the out-edges ordered by (label rank, destination) and the label rows in rank order, valid
     // while gen_built && rep_built && obs_built; everything else lives for one call
     bool obs_built = false;

@@ -2461,6 +2461,10 @@ int stcsp_engine_infer(stcsp_engine *e, const stcsp_infer_request *request, stcs
     if (!e || !request || !result) return STCSP_E_INVALID;
     return e->services.infer(e->view(), request, result);
 }
+int stcsp_engine_posterior(stcsp_engine *e, const stcsp_posterior_request *request, stcsp_posterior_result *result) {
+    if (!e || !request || !result) return STCSP_E_INVALID;
+    return e->services.posterior(e->view(), request, result);
+}
 int stcsp_engine_observer(stcsp_engine *e, const stcsp_observer_options *options, stcsp_observer_result *result) {
     if (!e || !result) return STCSP_E_INVALID;
     return e->services.observer(e->view(), options, result);

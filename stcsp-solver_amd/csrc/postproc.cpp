@@ -30,6 +30,7 @@
 #include "optimise_host.hpp"
 #include "compare_host.hpp"
 #include "infer_host.hpp"
+#include "posterior_host.hpp"
 #include "okfix.hpp"
 #include "stcsp_host.h"
 
@@ -1257,6 +1258,61 @@ int stcsp_automaton_infer_streams(const stcsp_automaton *a, const uint8_t *obser
         if (!vals) return STCSP_E_NOMEM;
         std::copy(all.begin(), all.end(), vals);
         *support_val = vals;
+    } catch (const std::bad_alloc &) {
+        return STCSP_E_NOMEM;
+    }
+    return STCSP_OK;
+}
+int stcsp_automaton_posterior_streams(const stcsp_automaton *a, const uint8_t *observable, int32_t flags, int64_t n_streams, const int64_t *offsets,
+                                      const int32_t *values, const int64_t *weight_off, const int32_t *weight_val, const int32_t *weight_w,
+                                      double *mass, uint8_t *exact, uint64_t *final_mass, int64_t *marg_off, int32_t **marg_val, uint64_t **marg_mass) {
+    if (!a || !marg_val || !marg_mass) return STCSP_E_INVALID;
+    *marg_val = nullptr;
+    *marg_mass = nullptr;
+    try {
+        stcsp::HostPosterior pos;
+        const std::vector<uint8_t> mask = a->a.observable_mask(observable);
+        int n_obs = 0;
+        for (uint8_t m : mask) n_obs += m != 0;
+        if (!stcsp::posterior_request_ok(n_streams, offsets, n_obs, weight_off, weight_val, weight_w) || !marg_off) return STCSP_E_INVALID;
+        if (n_streams > 0 && (!mass || !exact || !final_mass)) return STCSP_E_INVALID;
+        const int64_t steps = n_streams > 0 ? offsets[n_streams] : 0;
+        if (steps * n_obs > 0 && !values) return STCSP_E_INVALID;
+        pos.build(generator_view(a->a), mask.data(), weight_off, weight_val, weight_w);
+        std::vector<int32_t> all_val;
+        std::vector<uint64_t> all_mass;
+        std::vector<std::vector<double>> B;
+        std::vector<std::vector<std::pair<int32_t, uint64_t>>> marg;
+        marg_off[0] = 0;
+        for (int64_t i = 0; i < n_streams; i++) {
+            const int64_t len = offsets[i + 1] - offsets[i];
+            const int32_t *rows = values + offsets[i] * n_obs;
+            mass[i] = pos.backward(rows, len, flags, B);
+            exact[i] = mass[i] < 0x1.0p53;
+            final_mass[i] = 0;
+            if (exact[i])
+                final_mass[i] = pos.forward(rows, len, B, mass[i], marg);
+            else
+                marg.assign((size_t)len * (size_t)n_obs, std::vector<std::pair<int32_t, uint64_t>>());
+            for (size_t c = 0; c < marg.size(); c++) {
+                for (const auto &vm : marg[c]) {
+                    all_val.push_back(vm.first);
+                    all_mass.push_back(vm.second);
+                }
+                marg_off[(size_t)offsets[i] * n_obs + c + 1] = (int64_t)all_val.size();
+            }
+        }
+        int32_t *vals = (int32_t *)malloc(std::max<size_t>(all_val.size(), 1) * sizeof(int32_t));
+        uint64_t *masses = (uint64_t *)malloc(std::max<size_t>(all_mass.size(), 1) * sizeof(uint64_t));
+        if (!vals || !masses) {
+            free(vals);
+            free(masses);
+            return STCSP_E_NOMEM;
+        }
+        std::copy(all_val.begin(), all_val.end(), vals);
+        std::copy(all_mass.begin(), all_mass.end(), masses);
+        *marg_val = vals;
+        *marg_mass = masses;
     } catch (const std::bad_alloc &) {
         return STCSP_E_NOMEM;
     }

@@ -4,7 +4,8 @@
 //
 //   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--observer[=all|NAME[,NAME...]] [--compare=<file>]] [--components[=bottom|all|<N>]] [--optimise=<spec>] [--check=<file>]
 //         [--sample=<N>:<L>[:<seed>] [--sample-final] [--sample-mask=all]] [--count=<L>]
-//         [--repair=<file> [--repair-final]] [--infer=<file> [--infer-final] [--infer-draws=<D>[:<seed>]]] input.csp
+//         [--repair=<file> [--repair-final]] [--infer=<file> [--infer-final] [--infer-draws=<D>[:<seed>]]]
+//         [--posterior=<file> [--posterior-final] [--posterior-weights=<name>=<value>:<weight>[,...]]] input.csp
 //
 // --observer (not in the reference) writes the observer of the automaton instead of the automaton itself, to solutions.dot and
 // --binary=: the deterministic automaton whose states are the sets of states the system can be in after an observed prefix
@@ -92,6 +93,16 @@
 // --check=. The work is done on the device for an unsharded solve, by the host twin otherwise (--shards=N, host adversarial
 // passes). --infer excludes --check, --repair, --sample and --count.
 //
+// --posterior=<file> (not in the reference) says how many of the solution prefixes consistent with a partially observed stream
+// give each value of an entry that was not seen (include/stcsp_engine.h, stcsp_engine_posterior). The file has the format of
+// --repair=. For each stream stdout holds the comment line
+//     # index mass <m> len <len> exact <e> final_mass <f>
+// then one comment line per step, "# {a:m_a,b:m_b,...} {...} ...": for every observable variable the values it can take at that
+// step, each with the mass of the consistent prefixes that give it. --posterior-final takes only the prefixes that end in a
+// final state. --posterior-weights=x=1:3,y=0:0 weighs the value 1 of x by 3 and the value 0 of y by 0 (non-negative integers;
+// a value that is not listed weighs 1; the variables must be among the file's). The work is done on the device for an unsharded
+// solve, by the host twin otherwise. --posterior excludes --check, --repair, --infer, --sample and --count.
+//
 // Options must be glued to their value (-k3, not -k 3): like the reference, the first argument
 // that does not start with '-' is the input file (stcsp.y:199-206).
 #include <sys/times.h>
@@ -140,10 +151,13 @@ struct Flags {
     bool infer_final = false;
     int infer_draws = 0;
     long long infer_seed = 0;
+    const char *posterior = nullptr;
+    bool posterior_final = false;
+    const char *posterior_weights = nullptr;  // the text after --posterior-weights=
     bool sample = false, sample_final = false, sample_all = false;
     long long sample_n = 0, sample_seed = 0;
     int sample_len = 0, count_len = -1;
-    bool quiet() const { return check || repair || infer || sample || count_len >= 0; }  // stdout holds the answers only
+    bool quiet() const { return check || repair || infer || posterior || sample || count_len >= 0; }  // stdout holds the answers only
 };
 
 // --check=<file>, --repair=<file>: the streams of the file, columns reordered to variable order
@@ -369,6 +383,121 @@ static int infer_on_device(const Flags &f, const stcsp_problem *p, const Streams
     stcsp_infer_result ir;
     if (stcsp_engine_infer(eng, &rq, &ir) != STCSP_OK) return 1;
     print_inferences(p, st, f.infer_draws, ir.count, ir.support_off, ir.support_val, ir.values);
+    return 0;
+}
+
+// --posterior-weights=<name>=<value>:<weight>[,...]: the CSR of the contract over the observable variables of the streams' mask
+struct ValueWeights {
+    std::vector<int64_t> off;
+    std::vector<int32_t> val, w;
+};
+static int parse_value_weights(const char *text, const stcsp_problem *p, const Streams &st, ValueWeights &out) {
+    std::vector<int> column((size_t)p->n_vars, -1);
+    int n_obs = 0;
+    for (int v = 0; v < p->n_vars; v++)
+        if (st.mask[(size_t)v]) column[(size_t)v] = n_obs++;
+    std::vector<std::vector<std::pair<long long, long long>>> per((size_t)n_obs);
+    for (const char *q = text; *q;) {
+        const char *eq = strchr(q, '=');
+        if (!eq) return 1;
+        const std::string name(q, eq);
+        int var = -1;
+        for (int v = 0; v < p->n_vars; v++)
+            if (p->var_names && p->var_names[v] && name == p->var_names[v]) var = v;
+        if (var < 0 || column[(size_t)var] < 0) {
+            fprintf(stderr, "--posterior-weights: %s is not a variable of the streams\n", name.c_str());
+            return 1;
+        }
+        char *end = nullptr;
+        const long long value = strtoll(eq + 1, &end, 10);
+        if (end == eq + 1 || *end != ':' || value < INT_MIN || value > INT_MAX) return 1;
+        const char *ws = end + 1;
+        const long long weight = strtoll(ws, &end, 10);
+        if (end == ws || (*end != 0 && *end != ',') || weight < 0 || weight > INT_MAX) return 1;
+        per[(size_t)column[(size_t)var]].push_back({value, weight});
+        q = *end ? end + 1 : end;
+    }
+    out.off.assign(1, 0);
+    for (auto &list : per) {
+        std::stable_sort(list.begin(), list.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+        for (const auto &vw : list) {
+            out.val.push_back((int32_t)vw.first);
+            out.w.push_back((int32_t)vw.second);
+        }
+        out.off.push_back((int64_t)out.val.size());
+    }
+    out.val.push_back(0);  // (never NULL)
+    out.w.push_back(0);
+    return 0;
+}
+
+// --posterior: the lines on stdout
+static void print_posteriors(const stcsp_problem *p, const Streams &st, const double *mass, const uint8_t *exact, const uint64_t *final_mass,
+                             const int64_t *marg_off, const int32_t *marg_val, const uint64_t *marg_mass) {
+    size_t n_obs = 0;
+    printf("#");
+    for (int v = 0; v < p->n_vars; v++)
+        if (st.mask[(size_t)v]) {
+            printf(" %s", p->var_names[v]);
+            n_obs++;
+        }
+    printf("\n");
+    for (size_t i = 0; i + 1 < st.offsets.size(); i++) {
+        printf("# %zu mass %.0f len %lld exact %d final_mass %llu\n", i, mass[i], (long long)(st.offsets[i + 1] - st.offsets[i]), exact[i] ? 1 : 0,
+               (unsigned long long)final_mass[i]);
+        for (int64_t t = st.offsets[i]; t < st.offsets[i + 1]; t++) {
+            printf("#");
+            for (size_t k = 0; k < n_obs; k++) {
+                const int64_t b = marg_off[(size_t)t * n_obs + k], e = marg_off[(size_t)t * n_obs + k + 1];
+                printf(" {");
+                for (int64_t j = b; j < e; j++) printf(j > b ? ",%d:%llu" : "%d:%llu", marg_val[j], (unsigned long long)marg_mass[j]);
+                printf("}");
+            }
+            printf("\n");
+        }
+    }
+    fflush(stdout);
+}
+
+// --posterior on the host twin: the automaton's current flags
+static int posterior_on_host(const Flags &f, const stcsp_problem *p, const Streams &st, const stcsp_automaton *a) {
+    const size_t n = st.offsets.size() - 1, steps = (size_t)st.offsets[n];
+    size_t n_obs = 0;
+    for (uint8_t m : st.mask) n_obs += m != 0;
+    ValueWeights vw;
+    if (f.posterior_weights && parse_value_weights(f.posterior_weights, p, st, vw)) return 1;
+    std::vector<double> mass(n + 1);
+    std::vector<uint8_t> exact(n + 1);
+    std::vector<uint64_t> final_mass(n + 1);
+    std::vector<int64_t> marg_off(steps * n_obs + 1);
+    int32_t *marg_val = nullptr;
+    uint64_t *marg_mass = nullptr;
+    const bool weighted = f.posterior_weights != nullptr;
+    if (stcsp_automaton_posterior_streams(a, st.mask.data(), f.posterior_final ? STCSP_POSTERIOR_END_FINAL : 0, (int64_t)n, st.offsets.data(),
+                                          st.values.data(), weighted ? vw.off.data() : nullptr, weighted ? vw.val.data() : nullptr,
+                                          weighted ? vw.w.data() : nullptr, mass.data(), exact.data(), final_mass.data(), marg_off.data(), &marg_val,
+                                          &marg_mass) != STCSP_OK)
+        return 1;
+    print_posteriors(p, st, mass.data(), exact.data(), final_mass.data(), marg_off.data(), marg_val, marg_mass);
+    stcsp_host_free(marg_val);
+    stcsp_host_free(marg_mass);
+    return 0;
+}
+
+// ... and on the device, over the flags postprocess() has just left
+static int posterior_on_device(const Flags &f, const stcsp_problem *p, const Streams &st, stcsp_engine *eng) {
+    ValueWeights vw;
+    if (f.posterior_weights && parse_value_weights(f.posterior_weights, p, st, vw)) return 2;
+    stcsp_generator_options go = {st.mask.data(), 0, 0, {0, 0}};
+    stcsp_generator_info gi;
+    if (stcsp_engine_generator_build(eng, &go, &gi) != STCSP_OK) return 1;
+    const bool weighted = f.posterior_weights != nullptr;
+    stcsp_posterior_request rq = {(int64_t)st.offsets.size() - 1, st.offsets.data(), st.values.data(), weighted ? vw.off.data() : nullptr,
+                                  weighted ? vw.val.data() : nullptr, weighted ? vw.w.data() : nullptr,
+                                  f.posterior_final ? STCSP_POSTERIOR_END_FINAL : 0, 0};
+    stcsp_posterior_result pr;
+    if (stcsp_engine_posterior(eng, &rq, &pr) != STCSP_OK) return 1;
+    print_posteriors(p, st, pr.mass, pr.exact, pr.final_mass, pr.marg_off, pr.marg_val, pr.marg_mass);
     return 0;
 }
 
@@ -777,6 +906,7 @@ static int run_once(const Flags &f, bool print_line, double *total) {
     if (f.check && read_streams(f.check, p, streams)) return 1;
     if (f.repair && read_streams(f.repair, p, streams, true)) return 1;
     if (f.infer && read_streams(f.infer, p, streams, true)) return 1;
+    if (f.posterior && read_streams(f.posterior, p, streams, true)) return 1;
     FILE *info = f.quiet() ? stderr : stdout;  // --check, --sample, --count: stdout holds the answers only
     double init_time = cpu_time() - t_init;
     stcsp_options opt;
@@ -827,6 +957,10 @@ static int run_once(const Flags &f, bool print_line, double *total) {
             fprintf(stderr, "the streams could not be inferred: draws from a count that overflows a double\n");
             return 1;
         }
+        if (f.posterior && posterior_on_host(f, p, streams, a)) {
+            fprintf(stderr, "the posterior marginals could not be computed: malformed weights\n");
+            return 1;
+        }
         if (f.components && report_components(f, p, a, nullptr)) {
             fprintf(stderr, "the components could not be computed\n");
             return 1;
@@ -872,6 +1006,13 @@ static int run_once(const Flags &f, bool print_line, double *total) {
         if (f.infer && infer_on_device(f, p, streams, eng)) {
             fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
             return 1;
+        }
+        if (f.posterior) {
+            const int rc = posterior_on_device(f, p, streams, eng);
+            if (rc) {
+                fprintf(stderr, "%s\n", rc == 2 ? "the posterior marginals could not be computed: malformed weights" : stcsp_engine_last_error(eng));
+                return 1;
+            }
         }
         if (f.components && report_components(f, p, a, eng)) return 1;
         if (f.optimise && report_optimum(f, p, a, eng)) return 1;
@@ -928,6 +1069,7 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
     if (f.check && read_streams(f.check, p, streams)) return 1;
     if (f.repair && read_streams(f.repair, p, streams, true)) return 1;
     if (f.infer && read_streams(f.infer, p, streams, true)) return 1;
+    if (f.posterior && read_streams(f.posterior, p, streams, true)) return 1;
     FILE *info = f.quiet() ? stderr : stdout;  // --check, --sample, --count: stdout holds the answers only
     double init_time = cpu_time() - t_init;
     int ndev = 0;
@@ -1002,6 +1144,10 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
     }
     if (f.infer && infer_on_host(f, p, streams, a)) {  // (host twin likewise)
         fprintf(stderr, "the streams could not be inferred: draws from a count that overflows a double\n");
+        return 1;
+    }
+    if (f.posterior && posterior_on_host(f, p, streams, a)) {  // (host twin likewise)
+        fprintf(stderr, "the posterior marginals could not be computed: malformed weights\n");
         return 1;
     }
     if (f.components && report_components(f, p, a, nullptr)) {  // (host twin likewise)
@@ -1120,6 +1266,18 @@ int main(int argc, char **argv) {
             f.infer_draws = (int)d;
             continue;
         }
+        if (strncmp(a, "--posterior=", 12) == 0) {
+            f.posterior = a + 12;
+            continue;
+        }
+        if (strcmp(a, "--posterior-final") == 0) {
+            f.posterior_final = true;
+            continue;
+        }
+        if (strncmp(a, "--posterior-weights=", 20) == 0) {
+            f.posterior_weights = a + 20;
+            continue;
+        }
         if (strncmp(a, "--sample=", 9) == 0) {
             char *end = nullptr;
             f.sample_n = strtoll(a + 9, &end, 10);
@@ -1200,8 +1358,8 @@ int main(int argc, char **argv) {
             }
         }
     }
-    if ((f.check != nullptr) + (f.repair != nullptr) + (f.infer != nullptr) + f.sample + (f.count_len >= 0) > 1) {
-        fprintf(stderr, "--check, --repair, --infer, --sample and --count exclude each other\n");
+    if ((f.check != nullptr) + (f.repair != nullptr) + (f.infer != nullptr) + (f.posterior != nullptr) + f.sample + (f.count_len >= 0) > 1) {
+        fprintf(stderr, "--check, --repair, --infer, --posterior, --sample and --count exclude each other\n");
         return 1;
     }
     if (f.compare && !f.observer) {
