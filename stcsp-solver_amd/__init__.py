@@ -310,14 +310,34 @@ OBSERVER_SCALARS = ("n_states", "n_edges", "n_labels", "max_set", "table_bytes",
                     "seconds_items", "seconds_intern", "seconds_commit")
 
 
+def _copy_array(ptr, n, dtype):
+    """A copy of the n elements at a ctypes pointer as a numpy array; n == 0: an empty one (the pointer is not read)."""
+    import numpy as np
+    return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dtype)
+
+
+def _observable_mask(n_vars, observable):
+    """None (the default mask), "all", or a sequence of n_vars flags -> uint8 array or None."""
+    import numpy as np
+    if observable is None:
+        return None
+    m = np.ones(n_vars, dtype=np.uint8) if isinstance(observable, str) and observable == "all" else np.ascontiguousarray(observable, dtype=np.uint8)
+    if m.shape != (n_vars,):
+        raise ValueError(f"observable must have one flag per variable ({n_vars})")
+    return m
+
+
+def _stream_head(values, offsets):
+    """The (n_streams, offsets, values) head of MonitorStreams, RepairRequest, InferRequest and PosteriorRequest, from pack_streams()."""
+    return len(offsets) - 1, offsets.ctypes.data_as(C.POINTER(C.c_int64)), values.ctypes.data_as(C.POINTER(C.c_int32)) if values.size else None
+
+
 def _observer_unpack(res):
     """An ObserverResult -> dict: copies of its arrays as numpy arrays (member_off int64 [n_states + 1], member int32, state_final
     uint8 [n_states], edge_src / edge_dst int32 [n_edges], edge_values int32 [n_edges, n_observable]) and its scalars."""
     import numpy as np
     ns, ne, no = res.n_states, res.n_edges, res.n_observable
-
-    def arr(ptr, n, dtype):
-        return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dtype)
+    arr = _copy_array
     d = {k: getattr(res, k) for k in OBSERVER_SCALARS}
     d["member_off"] = arr(res.member_off, ns + 1, np.int64)
     d["member"] = arr(res.member, int(d["member_off"][-1]), np.int32)
@@ -426,9 +446,7 @@ def _components_unpack(res, n_states):
     Result], comp_size / comp_depth / comp_flags int32 [n_components], and "lassos": a list of (component, stem, loop), stem and loop
     int32 arrays of full label rows [steps, n_vars]."""
     import numpy as np
-
-    def arr(ptr, n, dtype):
-        return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dtype)
+    arr = _copy_array
     d = {k: getattr(res, k) for k in COMPONENTS_SCALARS}
     d["rounds"] = np.array(res.rounds[:], np.int32)
     d["state_component"] = arr(res.state_component, n_states, np.int32)
@@ -486,9 +504,7 @@ def _optimise_unpack(res, lengths, n_states):
     OPT_NONE; with mean: state_component int32 [n_states of the Result], "comp_mean": a list of (num, den) per component ((0, 0) when it
     is not cyclic), "omega_mean": (num, den) ((0, 0): no infinite solution) and omega_component; else None, [], (0, 0) and -1."""
     import numpy as np
-
-    def arr(ptr, n, dtype):
-        return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dtype)
+    arr = _copy_array
     d = {k: getattr(res, k) for k in ("n_states", "n_components", "n_vars", "horizon", "largest_cyclic", "omega_component", "seconds", "seconds_kernels")}
     d["rounds"] = np.array(res.rounds[:], np.int32)
     d["best"] = arr(res.best, res.horizon + 1, np.int64)
@@ -881,15 +897,10 @@ class Automaton:
         return a
 
     def _mask(self, observable):
-        """None (the default mask), "all", or a sequence of n_vars flags -> ctypes buffer or None."""
-        import numpy as np
+        """None (the default mask), "all", or a sequence of n_vars flags -> uint8 array or None."""
         if observable is None:
             return None
-        nv = len(self._model.var_names) if self._model is not None else len(observable)
-        m = np.ones(nv, dtype=np.uint8) if isinstance(observable, str) and observable == "all" else np.ascontiguousarray(observable, dtype=np.uint8)
-        if m.shape != (nv,):
-            raise ValueError(f"observable must have one flag per variable ({nv})")
-        return m
+        return _observable_mask(len(self._model.var_names) if self._model is not None else len(observable), observable)
 
     def bisimulation(self, observable=None):
         """The largest bisimulation of the live automaton under the labels projected on `observable` (None: every
@@ -1302,13 +1313,9 @@ class EngineBase:
         or one flag per variable). Returns (state_class int32 ndarray with -1 outside the live automaton, n_classes,
         rounds, seconds); the whole QuotientResult of the call is kept in self.quotient_result."""
         import numpy as np
-        nv = self._model.n_vars
         qo = QuotientOptions()
-        m = None
-        if observable is not None:
-            m = np.ones(nv, dtype=np.uint8) if isinstance(observable, str) and observable == "all" else np.ascontiguousarray(observable, dtype=np.uint8)
-            if m.shape != (nv,):
-                raise ValueError(f"observable must have one flag per variable ({nv})")
+        m = _observable_mask(self._model.n_vars, observable)  # (alive until the call returns)
+        if m is not None:
             qo.observable = m.ctypes.data_as(C.POINTER(C.c_uint8))
         out = QuotientResult()
         self._check(self._f("quotient")(self._h, C.byref(qo), C.byref(out)))
@@ -1319,13 +1326,9 @@ class EngineBase:
     def monitor(self, observable=None) -> MonitorInfo:
         """Build the stream monitor's look-up structures on the device for one mask, after postprocess() (`observable`
         as in quotient()). They stay valid until the next solve / postprocess / monitor. Returns the MonitorInfo."""
-        import numpy as np
-        nv = self._model.n_vars
         mo = MonitorOptions()
-        if observable is not None:
-            m = np.ones(nv, dtype=np.uint8) if isinstance(observable, str) and observable == "all" else np.ascontiguousarray(observable, dtype=np.uint8)
-            if m.shape != (nv,):
-                raise ValueError(f"observable must have one flag per variable ({nv})")
+        m = _observable_mask(self._model.n_vars, observable)  # (alive until the call returns)
+        if m is not None:
             mo.observable = m.ctypes.data_as(C.POINTER(C.c_uint8))
         info = MonitorInfo()
         self._check(self._f("monitor_build")(self._h, C.byref(mo), C.byref(info)))
@@ -1342,8 +1345,7 @@ class EngineBase:
             raise StcspError(-6, "check_streams() needs monitor() first")
         values, offsets = pack_streams(streams, self.monitor_info.n_observable)
         n = len(offsets) - 1
-        ms = MonitorStreams(n, offsets.ctypes.data_as(C.POINTER(C.c_int64)),
-                            values.ctypes.data_as(C.POINTER(C.c_int32)) if values.size else None, MON_FORCE_SETS if force_sets else 0, 0)
+        ms = MonitorStreams(*_stream_head(values, offsets), MON_FORCE_SETS if force_sets else 0, 0)
         out = MonitorResult()
         self._check(self._f("monitor_check")(self._h, C.byref(ms), C.byref(out)))
         self.monitor_result = out
@@ -1357,14 +1359,11 @@ class EngineBase:
         as in quotient()). They stay valid until the next solve / postprocess / generator. Returns the GeneratorInfo; its
         .count is a numpy float64 array [horizon + 1]: the number of solution prefixes of every length."""
         import numpy as np
-        nv = self._model.n_vars
         go = GeneratorOptions()
         go.horizon = horizon
         go.flags = GEN_END_FINAL if end_final else 0
-        if observable is not None:
-            m = np.ones(nv, dtype=np.uint8) if isinstance(observable, str) and observable == "all" else np.ascontiguousarray(observable, dtype=np.uint8)
-            if m.shape != (nv,):
-                raise ValueError(f"observable must have one flag per variable ({nv})")
+        m = _observable_mask(self._model.n_vars, observable)  # (alive until the call returns)
+        if m is not None:
             go.observable = m.ctypes.data_as(C.POINTER(C.c_uint8))
         info = GeneratorInfo()
         self.generator_info = None
@@ -1373,13 +1372,16 @@ class EngineBase:
         self.generator_info = info
         return info
 
+    def _needs_generator(self, who):
+        if getattr(self, "generator_info", None) is None:
+            raise StcspError(-6, f"{who}() needs generator() first")
+
     def generate(self, n, length, seed=0, ranks=None):
         """`n` solution prefixes of `length` steps from the device, after generator(): sampled with `seed` (uniform over the
         paths of that length), or the ranks[i]-th in lexicographic order. Returns (values int32 [n, length, n_observable],
         end_final uint8 [n]); the whole GenerateResult of the call is kept in self.generate_result."""
         import numpy as np
-        if getattr(self, "generator_info", None) is None:
-            raise StcspError(-6, "generate() needs generator() first")
+        self._needs_generator("generate")
         rq = GenerateRequest(n, None, seed, length, 0)
         if ranks is not None:
             rk = np.ascontiguousarray(ranks, dtype=np.uint64)
@@ -1404,14 +1406,13 @@ class EngineBase:
         [len, n_observable], end_final uint8, n_changed int32); distance -1 = no solution prefix of that length. The whole
         RepairResult of the call is kept in self.repair_result. Contract: include/stcsp_engine.h, stcsp_engine_repair."""
         import numpy as np
-        if getattr(self, "generator_info", None) is None:
-            raise StcspError(-6, "repair_streams() needs generator() first")
+        self._needs_generator("repair_streams")
         n_obs = self.generator_info.n_observable
         values, offsets = pack_streams(streams, n_obs)
         w = _repair_weights(weights, n_obs)
         n = len(offsets) - 1
-        rq = RepairRequest(n, offsets.ctypes.data_as(C.POINTER(C.c_int64)), values.ctypes.data_as(C.POINTER(C.c_int32)) if values.size else None,
-                           w.ctypes.data_as(C.POINTER(C.c_int32)) if w is not None else None, REPAIR_END_FINAL if end_final else 0, 0)
+        rq = RepairRequest(*_stream_head(values, offsets), w.ctypes.data_as(C.POINTER(C.c_int32)) if w is not None else None,
+                           REPAIR_END_FINAL if end_final else 0, 0)
         out = RepairResult()
         self._check(self._f("repair")(self._h, C.byref(rq), C.byref(out)))
         self.repair_result = out
@@ -1428,22 +1429,18 @@ class EngineBase:
         supports, n_states, draws, end_final) as Automaton.infer_streams() does; the whole InferResult of the call is kept in
         self.infer_result. Contract: include/stcsp_engine.h, stcsp_engine_infer."""
         import numpy as np
-        if getattr(self, "generator_info", None) is None:
-            raise StcspError(-6, "infer_streams() needs generator() first")
+        self._needs_generator("infer_streams")
         n_obs = self.generator_info.n_observable
         values, offsets = pack_streams(streams, n_obs)
         n = len(offsets) - 1
         steps = max(int(offsets[n]), 0) if n else 0
         rk = _infer_ranks(ranks, n, draws)
-        rq = InferRequest(n, offsets.ctypes.data_as(C.POINTER(C.c_int64)), values.ctypes.data_as(C.POINTER(C.c_int32)) if values.size else None,
-                          rk.ctypes.data_as(C.POINTER(C.c_uint64)) if rk is not None else None, seed, INFER_END_FINAL if end_final else 0, draws)
+        rq = InferRequest(*_stream_head(values, offsets), rk.ctypes.data_as(C.POINTER(C.c_uint64)) if rk is not None else None, seed,
+                          INFER_END_FINAL if end_final else 0, draws)
         out = InferResult()
         self._check(self._f("infer")(self._h, C.byref(rq), C.byref(out)))
         self.infer_result = out
-
-        def arr(ptr, size, dtype):
-            return np.ctypeslib.as_array(ptr, shape=(size,)).copy() if size else np.zeros(0, dtype)
-
+        arr = _copy_array
         soff = arr(out.support_off, steps * n_obs + 1, np.int64)
         return _infer_unpack(arr(out.count, n, np.float64), soff, arr(out.support_val, int(soff[-1]), np.int32), arr(out.n_states, steps + n, np.int32),
                              arr(out.values, steps * draws * n_obs, np.int32), arr(out.end_final, n * draws, np.uint8), offsets, n_obs, draws)
@@ -1456,24 +1453,20 @@ class EngineBase:
         does; the whole PosteriorResult of the call is kept in self.posterior_result. Contract: include/stcsp_engine.h,
         stcsp_engine_posterior."""
         import numpy as np
-        if getattr(self, "generator_info", None) is None:
-            raise StcspError(-6, "posterior_streams() needs generator() first")
+        self._needs_generator("posterior_streams")
         n_obs = self.generator_info.n_observable
         values, offsets = pack_streams(streams, n_obs)
         n = len(offsets) - 1
         steps = max(int(offsets[n]), 0) if n else 0
         woff, wval, ww = _posterior_weights(weights, n_obs)
-        rq = PosteriorRequest(n, offsets.ctypes.data_as(C.POINTER(C.c_int64)), values.ctypes.data_as(C.POINTER(C.c_int32)) if values.size else None,
+        rq = PosteriorRequest(*_stream_head(values, offsets),
                               woff.ctypes.data_as(C.POINTER(C.c_int64)) if woff is not None else None,
                               wval.ctypes.data_as(C.POINTER(C.c_int32)) if woff is not None else None,
                               ww.ctypes.data_as(C.POINTER(C.c_int32)) if woff is not None else None, POSTERIOR_END_FINAL if end_final else 0, 0)
         out = PosteriorResult()
         self._check(self._f("posterior")(self._h, C.byref(rq), C.byref(out)))
         self.posterior_result = out
-
-        def arr(ptr, size, dtype):
-            return np.ctypeslib.as_array(ptr, shape=(size,)).copy() if size else np.zeros(0, dtype)
-
+        arr = _copy_array
         moff = arr(out.marg_off, steps * n_obs + 1, np.int64)
         total = int(moff[-1])
         return _posterior_unpack(arr(out.mass, n, np.float64), arr(out.exact, n, np.uint8), arr(out.final_mass, n, np.uint64), moff,
@@ -1484,8 +1477,7 @@ class EngineBase:
         no part): the deterministic automaton over the sets of states the system can be in after an observed prefix. Returns a
         dict of numpy arrays and scalars (see _observer_unpack()); members are state indices of the last Result. StcspError -4
         beyond max_states (0: the default) or the byte budget. Contract: include/stcsp_engine.h, stcsp_engine_observer."""
-        if getattr(self, "generator_info", None) is None:
-            raise StcspError(-6, "observer() needs generator() first")
+        self._needs_generator("observer")
         oo = ObserverOptions(max_states)
         out = ObserverResult()
         self._check(self._f("observer")(self._h, C.byref(oo), C.byref(out)))

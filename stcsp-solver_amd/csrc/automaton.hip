@@ -53,8 +53,9 @@ int AutomatonServices::fail(int code, const char *fmt, ...) {
 }
 
 void AutomatonServices::invalidate() {
-    post_done = live_done = mon_built = gen_built = rep_built = inf_built = obs_built = cmp_valid = false;
-    mon_host.reset();
+    post.done = post.live_done = mon.built = gen.built = false;
+    gen.drop_derived();
+    mon.host.reset();
 }
 
 // Every entry point starts here: takes the view and checks what `who` needs. host_twin: what to use on a sharded solve's merged automaton.
@@ -65,38 +66,38 @@ int AutomatonServices::enter(const AutomatonView &view, const char *who, Need ne
                          : fail(STCSP_E_STATE, "%s: device post-processing is for unsharded engines (merge shards on the host)", who);
     if (!v.exp_on_device) return fail(STCSP_E_STATE, "%s needs the device export of a finished solve (export first)", who);
     if (need == NEED_EXPORT) return STCSP_OK;
-    if (!post_done) return fail(STCSP_E_STATE, "%s needs the flags of postprocess() on the last solve", who);
+    if (!post.done) return fail(STCSP_E_STATE, "%s needs the flags of postprocess() on the last solve", who);
     if (v.truncated) return fail(STCSP_E_STATE, "%s after a truncated solve: the open states of a partial automaton have no known language", who);
-    if (need == NEED_MONITOR && !mon_built) return fail(STCSP_E_STATE, "%s needs monitor_build() after the last postprocess()", who);
-    if (need == NEED_GENERATOR && !gen_built) return fail(STCSP_E_STATE, "%s needs generator_build() after the last postprocess()", who);
+    if (need == NEED_MONITOR && !mon.built) return fail(STCSP_E_STATE, "%s needs monitor_build() after the last postprocess()", who);
+    if (need == NEED_GENERATOR && !gen.built) return fail(STCSP_E_STATE, "%s needs generator_build() after the last postprocess()", who);
     return STCSP_OK;
 }
 
 // The live automaton: forward reachability from a valid root over alive edges (what write_dot walks), on first need after a postprocess()
 int AutomatonServices::live_set() {
-    if (live_done) return STCSP_OK;
+    if (post.live_done) return STCSP_OK;
     const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
-    HIPCHK(d_live.reserve(S));
-    HIPCHK(d_lctl.reserve_exact(Q_WORDS));
+    HIPCHK(post.d_live.reserve(S));
+    HIPCHK(post.d_lctl.reserve_exact(Q_WORDS));
     uint32_t ctl[Q_WORDS] = {0, 0, 0, 0};
-    HIPCHK(hipMemsetAsync(d_lctl.p, 0, sizeof ctl, v.stream));
-    HIPCHK(hipMemsetAsync(d_live.p, 0, S, v.stream));
-    HIPCHK(hipMemcpyAsync(d_live.p, d_pvalid.p, 1, hipMemcpyDeviceToDevice, v.stream));
+    HIPCHK(hipMemsetAsync(post.d_lctl.p, 0, sizeof ctl, v.stream));
+    HIPCHK(hipMemsetAsync(post.d_live.p, 0, S, v.stream));
+    HIPCHK(hipMemcpyAsync(post.d_live.p, post.d_pvalid.p, 1, hipMemcpyDeviceToDevice, v.stream));
     for (int sweeps = 0; E; sweeps++) {
-        HIPCHK(hipMemsetAsync(d_lctl.p + Q_CHANGED, 0, sizeof(uint32_t), v.stream));
-        hipLaunchKernelGGL(k_q_reach, dim3((E + 255) / 256), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)d_palive.p,
-                           (const uint8_t *)d_pvalid.p, d_live.p, d_lctl.p);
-        HIPCHK(hipMemcpyAsync(ctl, d_lctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemsetAsync(post.d_lctl.p + Q_CHANGED, 0, sizeof(uint32_t), v.stream));
+        hipLaunchKernelGGL(k_q_reach, dim3((E + 255) / 256), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p,
+                           (const uint8_t *)post.d_pvalid.p, post.d_live.p, post.d_lctl.p);
+        HIPCHK(hipMemcpyAsync(ctl, post.d_lctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
         HIPCHK(hipStreamSynchronize(v.stream));
         if (!ctl[Q_CHANGED]) break;
         if (sweeps > (int)S + 8) return fail(STCSP_E_INTERNAL, "live set: reachability did not converge");
     }
-    live.resize(S);
-    HIPCHK(hipMemcpyAsync(live.data(), d_live.p, S, hipMemcpyDeviceToHost, v.stream));
+    post.live.resize(S);
+    HIPCHK(hipMemcpyAsync(post.live.data(), post.d_live.p, S, hipMemcpyDeviceToHost, v.stream));
     HIPCHK(hipStreamSynchronize(v.stream));
-    n_live = std::count(live.begin(), live.end(), 1);
-    root_live = S > 0 && live[0];
-    live_done = true;
+    post.n_live = std::count(post.live.begin(), post.live.end(), 1);
+    post.root_live = S > 0 && post.live[0];
+    post.live_done = true;
     return STCSP_OK;
 }
 
@@ -112,17 +113,17 @@ int AutomatonServices::table_budget(const char *env_name, size_t &budget) {
     return STCSP_OK;
 }
 
-// The next batch of a repair() or infer(): the streams from b0 on whose tables, need(len) bytes each, fit the budget together, 65535 at most
-template <typename Rec, typename NeedFn>
-int AutomatonServices::plan_batch(const char *who, const int64_t *offsets, size_t n, size_t b0, size_t budget, NeedFn need, std::vector<Rec> &meta, Batch &b) {
-    b = Batch{b0};
+// The next batch of a repair(), infer() or posterior(): the streams from b0 on whose tables, need(len) bytes each, fit the budget together, 65535 at most
+template <typename NeedFn>
+int AutomatonServices::plan_batch(const char *who, const int64_t *offsets, size_t n, size_t b0, size_t budget, NeedFn need, std::vector<BatchStream> &meta, Batch &b) {
+    b = Batch{b0, b0};
     meta.clear();
     while (b.b1 < n && b.b1 - b0 < 65535) {
         const size_t len = (size_t)(offsets[b.b1 + 1] - offsets[b.b1]);
         if (need(len) > budget)
             return fail(STCSP_E_NOMEM, "%s: stream %zu of %zu steps needs %zu bytes of tables, the budget is %zu", who, b.b1, len, need(len), budget);
         if (b.b1 > b0 && b.bytes + need(len) > budget) break;
-        meta.push_back(Rec{(unsigned long long)b.entries, (unsigned long long)b.steps, (uint32_t)len, (uint32_t)(b.b1 - b0)});
+        meta.push_back(BatchStream{(unsigned long long)b.entries, (unsigned long long)b.steps, (uint32_t)len, (uint32_t)(b.b1 - b0)});
         b.bytes += need(len);
         b.entries += (len + 1) * (size_t)v.n_states;
         b.steps += len;
@@ -130,6 +131,43 @@ int AutomatonServices::plan_batch(const char *who, const int64_t *offsets, size_
         b.b1++;
     }
     return STCSP_OK;
+}
+
+// What repair(), infer() and posterior() share once the request is checked and the result is sized: label ids and, on request,
+// dictionaries on first need, the budget, and per batch of consecutive streams whose tables fit it the upload of the stream
+// records and observed rows, then body(batch, nb, first_step, records, rows): the launches and copies of the service.
+template <typename Result, typename NeedFn, typename Body>
+int AutomatonServices::stream_batches(const char *who, const char *budget_env, int64_t n_streams, const int64_t *offsets, const int32_t *values,
+                                      bool dictionaries, NeedFn need, Result *out, Body body) {
+    const size_t n = (size_t)n_streams, n_obs = (size_t)gen.n_obs;
+    if (!n || !post.root_live) return STCSP_OK;
+    if (int rc = lab.built ? STCSP_OK : repair_labels()) return rc;
+    if (int rc = !dictionaries || dict.built ? STCSP_OK : infer_dictionaries()) return rc;
+    size_t budget = 0;
+    if (int rc = table_budget(budget_env, budget)) return rc;
+    HIPCHK(ev.ready(8));
+    std::vector<BatchStream> meta;
+    for (size_t b0 = 0; b0 < n;) {
+        Batch b;
+        if (int rc = plan_batch(who, offsets, n, b0, budget, need, meta, b)) return rc;
+        const size_t nb = b.b1 - b0, cells = b.steps * n_obs, first_step = (size_t)offsets[b0];
+        HIPCHK(bat.d_streams.reserve(nb));
+        HIPCHK(bat.d_rows.reserve(cells));
+        HIPCHK(hipMemcpyAsync(bat.d_streams.p, meta.data(), nb * sizeof(BatchStream), hipMemcpyHostToDevice, v.stream));
+        if (cells) HIPCHK(hipMemcpyAsync(bat.d_rows.p, values + first_step * n_obs, cells * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+        if (int rc = body(b, nb, first_step, (const BatchStream *)bat.d_streams.p, (const int32_t *)bat.d_rows.p)) return rc;
+        out->n_batches++;
+        out->table_bytes = std::max<int64_t>(out->table_bytes, (int64_t)b.bytes);
+        b0 = b.b1;
+    }
+    out->n_labels = lab.n_labels;
+    return STCSP_OK;
+}
+
+// Every (table, count) of a batch with reserve_or_release(), or none: all released and the service's message
+template <typename... Tables>
+int AutomatonServices::reserve_tables(const char *who, size_t bytes, Tables &&...tables) {
+    return reserve_or_release_all(true, tables...) ? (int)STCSP_OK : fail(STCSP_E_NOMEM, "%s: no room for %zu bytes of tables", who, bytes);
 }
 
 // graphTraverse / adversarialTraverse / adversarialTraverse2 on the device (dev_postproc.hpp)
@@ -154,15 +192,15 @@ int AutomatonServices::postprocess(const AutomatonView &view, const stcsp_post_o
     auto last_full = [&](int x) { return width(x) % 32 == 0 ? 0xffffffffu : ((1u << (width(x) % 32)) - 1u); };
     const int wa = op >= 0 ? (int)width(ava) : 0;
     const int cw1 = a1 >= 0 ? cover_w(a1) : 1, cw2 = op >= 0 ? cover_w(op) : 1;
-    HIPCHK(reserve_all(S, 0, d_pvalid, d_pfinal, d_pnodeok));
+    HIPCHK(reserve_all(S, 0, post.d_pvalid, post.d_pfinal, post.d_pnodeok));
     const size_t cover_words = (size_t)S * std::max(cw1, std::max(1, wa) * cw2);
-    HIPCHK(d_pcover.reserve(cover_words));
-    HIPCHK(d_palive.reserve(E, 1));
-    HIPCHK(d_pctl.reserve_exact(4));
+    HIPCHK(post.d_pcover.reserve(cover_words));
+    HIPCHK(post.d_palive.reserve(E, 1));
+    HIPCHK(post.d_pctl.reserve_exact(4));
     const unsigned eb = (unsigned)((E + 255) / 256), sb = (S + 255) / 256;
     const long long *src = v.d_osrc, *dst = v.d_odst;
     const int32_t *val = v.d_oval;
-    uint32_t *changed = d_pctl.p;
+    uint32_t *changed = post.d_pctl.p;
     // one round = the kernels `body` enqueues; returns the number of rounds until nothing changed
     auto fixpoint = [&](int &rounds, auto body) -> int {  // HIPCHK returns the error code from the enclosing lambda
         for (rounds = 0;; rounds++) {
@@ -177,74 +215,74 @@ int AutomatonServices::postprocess(const AutomatonView &view, const stcsp_post_o
         }
     };
     int rounds[3] = {0, 0, 0};
-    HIPCHK(hipMemsetAsync(d_palive.p, 1, E + 1, v.stream));
+    HIPCHK(hipMemsetAsync(post.d_palive.p, 1, E + 1, v.stream));
     // graphTraverse (src/graph.cpp:357-418); the loop bound numSignVar + numUntil is the reference's
     hipLaunchKernelGGL(k_trav_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)v.d_state_keys, v.KL, v.n_sig,
-                       v.n_sig + v.n_until, (int)(v.n_until_cons == 0), d_pvalid.p, d_pfinal.p);
+                       v.n_sig + v.n_until, (int)(v.n_until_cons == 0), post.d_pvalid.p, post.d_pfinal.p);
     if (E) {
         if (int rc = fixpoint(rounds[0], [&] {
-            hipLaunchKernelGGL(k_trav_back, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, (const uint8_t *)d_palive.p, d_pvalid.p, changed);
+            hipLaunchKernelGGL(k_trav_back, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, (const uint8_t *)post.d_palive.p, post.d_pvalid.p, changed);
             return (int)STCSP_OK;
         })) return rc;
-        hipLaunchKernelGGL(k_kill_into_invalid, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, d_palive.p, (const uint8_t *)d_pvalid.p, 1);
+        hipLaunchKernelGGL(k_kill_into_invalid, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, post.d_palive.p, (const uint8_t *)post.d_pvalid.p, 1);
     }
     int adver1 = -1, adver2 = -1;
     uint8_t root_valid = 0;
     if (a1 >= 0) {  // adversarialTraverse (src/graph.cpp:304-355)
         const uint32_t full = last_full(a1);
         if (int rc = fixpoint(rounds[1], [&] {
-            HIPCHK(hipMemsetAsync(d_pcover.p, 0, (size_t)S * cw1 * sizeof(uint32_t), v.stream));
+            HIPCHK(hipMemsetAsync(post.d_pcover.p, 0, (size_t)S * cw1 * sizeof(uint32_t), v.stream));
             if (E)
                 hipLaunchKernelGGL(k_adv_cover, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, val, N, a1, v.lb[a1], cw1,
-                                   (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_pcover.p);
-            hipLaunchKernelGGL(k_adv_check, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)d_pcover.p, cw1, full, d_pvalid.p, changed);
+                                   (const uint8_t *)post.d_palive.p, (const uint8_t *)post.d_pvalid.p, post.d_pcover.p);
+            hipLaunchKernelGGL(k_adv_check, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)post.d_pcover.p, cw1, full, post.d_pvalid.p, changed);
             return (int)STCSP_OK;
         })) return rc;
-        if (E) hipLaunchKernelGGL(k_kill_into_invalid, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, d_palive.p, (const uint8_t *)d_pvalid.p, 0);
-        HIPCHK(hipMemcpyAsync(&root_valid, d_pvalid.p, 1, hipMemcpyDeviceToHost, v.stream));
+        if (E) hipLaunchKernelGGL(k_kill_into_invalid, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, post.d_palive.p, (const uint8_t *)post.d_pvalid.p, 0);
+        HIPCHK(hipMemcpyAsync(&root_valid, post.d_pvalid.p, 1, hipMemcpyDeviceToHost, v.stream));
         HIPCHK(hipStreamSynchronize(v.stream));
         adver1 = root_valid;
     }
     if (op >= 0) {  // adversarialTraverse2 (src/graph.cpp:247-302)
         const uint32_t full = last_full(op);
         if (int rc = fixpoint(rounds[2], [&] {
-            HIPCHK(hipMemsetAsync(d_pcover.p, 0, (size_t)S * wa * cw2 * sizeof(uint32_t), v.stream));
+            HIPCHK(hipMemsetAsync(post.d_pcover.p, 0, (size_t)S * wa * cw2 * sizeof(uint32_t), v.stream));
             if (E)
                 hipLaunchKernelGGL(k_adv2_cover, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, val, N, op, ava, v.lb[op], v.lb[ava],
-                                   wa, cw2, (const uint8_t *)d_palive.p, (const uint8_t *)d_pvalid.p, d_pcover.p);
-            hipLaunchKernelGGL(k_adv2_check, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)d_pcover.p, wa, cw2, full, d_pvalid.p, d_pnodeok.p,
+                                   wa, cw2, (const uint8_t *)post.d_palive.p, (const uint8_t *)post.d_pvalid.p, post.d_pcover.p);
+            hipLaunchKernelGGL(k_adv2_check, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)post.d_pcover.p, wa, cw2, full, post.d_pvalid.p, post.d_pnodeok.p,
                                changed);
             if (E)
-                hipLaunchKernelGGL(k_adv2_kill, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, val, N, ava, v.lb[ava], wa, cw2, full, d_palive.p,
-                                   (const uint8_t *)d_pvalid.p, (const uint8_t *)d_pnodeok.p, (const uint32_t *)d_pcover.p);
+                hipLaunchKernelGGL(k_adv2_kill, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, val, N, ava, v.lb[ava], wa, cw2, full, post.d_palive.p,
+                                   (const uint8_t *)post.d_pvalid.p, (const uint8_t *)post.d_pnodeok.p, (const uint32_t *)post.d_pcover.p);
             return (int)STCSP_OK;
         })) return rc;
-        HIPCHK(hipMemcpyAsync(&root_valid, d_pvalid.p, 1, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(&root_valid, post.d_pvalid.p, 1, hipMemcpyDeviceToHost, v.stream));
         HIPCHK(hipStreamSynchronize(v.stream));
         adver2 = root_valid;
         // the reference drops the edges into invalid states only when the root survived (graph.cpp:288-301)
         if (root_valid && E)
-            hipLaunchKernelGGL(k_kill_into_invalid, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, d_palive.p, (const uint8_t *)d_pvalid.p, 0);
+            hipLaunchKernelGGL(k_kill_into_invalid, dim3(eb), dim3(256), 0, v.stream, (uint32_t)E, src, dst, post.d_palive.p, (const uint8_t *)post.d_pvalid.p, 0);
     }
     HIPCHK(hipGetLastError());
-    p_valid.resize(S);
-    p_final.resize(S);
-    p_alive.resize(E + 1);
-    HIPCHK(hipMemcpyAsync(p_valid.data(), d_pvalid.p, S, hipMemcpyDeviceToHost, v.stream));
-    HIPCHK(hipMemcpyAsync(p_final.data(), d_pfinal.p, S, hipMemcpyDeviceToHost, v.stream));
-    if (E) HIPCHK(hipMemcpyAsync(p_alive.data(), d_palive.p, E, hipMemcpyDeviceToHost, v.stream));
+    post.p_valid.resize(S);
+    post.p_final.resize(S);
+    post.p_alive.resize(E + 1);
+    HIPCHK(hipMemcpyAsync(post.p_valid.data(), post.d_pvalid.p, S, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(post.p_final.data(), post.d_pfinal.p, S, hipMemcpyDeviceToHost, v.stream));
+    if (E) HIPCHK(hipMemcpyAsync(post.p_alive.data(), post.d_palive.p, E, hipMemcpyDeviceToHost, v.stream));
     HIPCHK(hipStreamSynchronize(v.stream));
     memset(out, 0, sizeof *out);
     out->n_states = S;
     out->n_edges = (int64_t)E;
-    out->state_valid = p_valid.data();
-    out->state_final = p_final.data();
-    out->edge_alive = p_alive.data();
+    out->state_valid = post.p_valid.data();
+    out->state_final = post.p_final.data();
+    out->edge_alive = post.p_alive.data();
     out->adver1 = adver1;
     out->adver2 = adver2;
     for (int i = 0; i < 3; i++) out->rounds[i] = rounds[i];
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    post_done = true;
+    post.done = true;
     return STCSP_OK;
 }
 
@@ -264,52 +302,52 @@ int AutomatonServices::quotient(const AutomatonView &view, const stcsp_quotient_
     const size_t cap_e = pow2(E), cap_s = pow2(S);
     if (cap_e > 0x80000000ull) return fail(STCSP_E_NOMEM, "edge list too large for the device quotient");
     if (int rc = live_set()) return rc;
-    HIPCHK(reserve_all(S, 0, d_qcls[0], d_qcls[1], d_qacc[0], d_qacc[1], d_qcnt));
-    HIPCHK(reserve_all(E, 1, d_qsrc, d_qdst, d_qlid));
-    HIPCHK(d_qtab_e.reserve_exact(cap_e));
-    HIPCHK(d_qtab_s.reserve_exact(cap_s));
-    HIPCHK(d_qobs.reserve_exact((size_t)N));
-    HIPCHK(d_qctl.reserve_exact(Q_WORDS));
+    HIPCHK(reserve_all(S, 0, quo.d_qcls[0], quo.d_qcls[1], quo.d_qacc[0], quo.d_qacc[1], quo.d_qcnt));
+    HIPCHK(reserve_all(E, 1, quo.d_qsrc, quo.d_qdst, quo.d_qlid));
+    HIPCHK(quo.d_qtab_e.reserve_exact(cap_e));
+    HIPCHK(quo.d_qtab_s.reserve_exact(cap_s));
+    HIPCHK(quo.d_qobs.reserve_exact((size_t)N));
+    HIPCHK(quo.d_qctl.reserve_exact(Q_WORDS));
     const unsigned eb = (E + 255) / 256, sb = (S + 255) / 256;
     const uint32_t mask_e = (uint32_t)(cap_e - 1), mask_s = (uint32_t)(cap_s - 1);
     uint32_t ctl[Q_WORDS] = {0, 0, 0, 0};
     auto check = [&]() -> int {
-        HIPCHK(hipMemcpyAsync(ctl, d_qctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(ctl, quo.d_qctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
         HIPCHK(hipStreamSynchronize(v.stream));
         if (ctl[Q_ERROR] & Q_ERR_TABLE_FULL) return fail(STCSP_E_INTERNAL, "quotient: a device table overflowed");
         if (ctl[Q_ERROR]) return fail(STCSP_E_INTERNAL, "quotient: a state differs from its class representative (signature collision, flags %u)", ctl[Q_ERROR]);
         return STCSP_OK;
     };
-    if (!obs.empty()) HIPCHK(hipMemcpyAsync(d_qobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-    HIPCHK(hipMemsetAsync(d_qctl.p, 0, sizeof ctl, v.stream));
+    if (!obs.empty()) HIPCHK(hipMemcpyAsync(quo.d_qobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+    HIPCHK(hipMemsetAsync(quo.d_qctl.p, 0, sizeof ctl, v.stream));
     // label ids (the one sweep over the label rows) and the 12-byte edge records of the rounds
     if (E) {
-        HIPCHK(hipMemsetAsync(d_qtab_e.p, 0xff, cap_e * sizeof(uint32_t), v.stream));
+        HIPCHK(hipMemsetAsync(quo.d_qtab_e.p, 0xff, cap_e * sizeof(uint32_t), v.stream));
         hipLaunchKernelGGL(k_q_labels, dim3(eb), dim3(256), 0, v.stream, E, (const long long *)v.d_osrc, (const long long *)v.d_odst,
-                           (const int32_t *)v.d_oval, N, (const int32_t *)d_qobs.p, (int)obs.size(), (const uint8_t *)d_palive.p,
-                           (const uint8_t *)d_live.p, d_qtab_e.p, mask_e, d_qsrc.p, d_qdst.p, d_qlid.p, d_qctl.p);
+                           (const int32_t *)v.d_oval, N, (const int32_t *)quo.d_qobs.p, (int)obs.size(), (const uint8_t *)post.d_palive.p,
+                           (const uint8_t *)post.d_live.p, quo.d_qtab_e.p, mask_e, quo.d_qsrc.p, quo.d_qdst.p, quo.d_qlid.p, quo.d_qctl.p);
     }
     // every live state starts in class 0; a round splits the classes by (final, set of (label id, class of destination))
-    HIPCHK(hipMemsetAsync(d_qcls[0].p, 0, (size_t)S * sizeof(uint32_t), v.stream));
+    HIPCHK(hipMemsetAsync(quo.d_qcls[0].p, 0, (size_t)S * sizeof(uint32_t), v.stream));
     int cur = 0, rounds = 0;
     bool dedup = true;  // until round 1 has shown that no state has two edges with one projected label
     auto edge_sweep = [&](bool dd) -> int {
-        hipLaunchKernelGGL(k_q_state_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_pfinal.p, d_qacc[0].p, d_qacc[1].p, d_qcnt.p);
+        hipLaunchKernelGGL(k_q_state_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)post.d_pfinal.p, quo.d_qacc[0].p, quo.d_qacc[1].p, quo.d_qcnt.p);
         if (!E) return STCSP_OK;
-        if (dd) HIPCHK(hipMemsetAsync(d_qtab_e.p, 0xff, cap_e * sizeof(uint32_t), v.stream));
-        hipLaunchKernelGGL(k_q_edges, dim3(eb), dim3(256), 0, v.stream, E, (const uint32_t *)d_qsrc.p, (const uint32_t *)d_qdst.p,
-                           (const uint32_t *)d_qlid.p, (const uint32_t *)d_qcls[cur].p, (int)dd, d_qtab_e.p, mask_e, d_qacc[0].p, d_qacc[1].p,
-                           d_qcnt.p, d_qctl.p);
+        if (dd) HIPCHK(hipMemsetAsync(quo.d_qtab_e.p, 0xff, cap_e * sizeof(uint32_t), v.stream));
+        hipLaunchKernelGGL(k_q_edges, dim3(eb), dim3(256), 0, v.stream, E, (const uint32_t *)quo.d_qsrc.p, (const uint32_t *)quo.d_qdst.p,
+                           (const uint32_t *)quo.d_qlid.p, (const uint32_t *)quo.d_qcls[cur].p, (int)dd, quo.d_qtab_e.p, mask_e, quo.d_qacc[0].p, quo.d_qacc[1].p,
+                           quo.d_qcnt.p, quo.d_qctl.p);
         return STCSP_OK;
     };
     for (uint32_t prev = 0;;) {
         rounds++;
-        HIPCHK(hipMemsetAsync(d_qctl.p, 0, 2 * sizeof(uint32_t), v.stream));  // Q_CLASSES, Q_DUPS
+        HIPCHK(hipMemsetAsync(quo.d_qctl.p, 0, 2 * sizeof(uint32_t), v.stream));  // Q_CLASSES, Q_DUPS
         if (int rc = edge_sweep(dedup)) return rc;
-        HIPCHK(hipMemsetAsync(d_qtab_s.p, 0xff, cap_s * sizeof(uint32_t), v.stream));
-        hipLaunchKernelGGL(k_q_number, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint32_t *)d_qcls[cur].p,
-                           (const unsigned long long *)d_qacc[0].p, (const unsigned long long *)d_qacc[1].p, d_qtab_s.p, mask_s,
-                           d_qcls[1 - cur].p, d_qctl.p);
+        HIPCHK(hipMemsetAsync(quo.d_qtab_s.p, 0xff, cap_s * sizeof(uint32_t), v.stream));
+        hipLaunchKernelGGL(k_q_number, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)post.d_live.p, (const uint32_t *)quo.d_qcls[cur].p,
+                           (const unsigned long long *)quo.d_qacc[0].p, (const unsigned long long *)quo.d_qacc[1].p, quo.d_qtab_s.p, mask_s,
+                           quo.d_qcls[1 - cur].p, quo.d_qctl.p);
         if (int rc = check()) return rc;
         cur = 1 - cur;
         if (rounds == 1 && ctl[Q_DUPS] == 0) dedup = false;
@@ -320,34 +358,34 @@ int AutomatonServices::quotient(const AutomatonView &view, const stcsp_quotient_
     // exact verification against the class representatives; leaves the distinct pairs per state in d_qcnt
     if (int rc = edge_sweep(true)) return rc;
     if (E)
-        hipLaunchKernelGGL(k_q_verify_edges, dim3(eb), dim3(256), 0, v.stream, E, (const uint32_t *)d_qsrc.p, (const uint32_t *)d_qdst.p,
-                           (const uint32_t *)d_qlid.p, (const uint32_t *)d_qcls[cur].p, (const uint32_t *)d_qtab_e.p, mask_e, d_qctl.p);
-    hipLaunchKernelGGL(k_q_verify_states, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint8_t *)d_pfinal.p,
-                       (const uint32_t *)d_qcls[cur].p, (const uint32_t *)d_qcnt.p, d_qctl.p);
+        hipLaunchKernelGGL(k_q_verify_edges, dim3(eb), dim3(256), 0, v.stream, E, (const uint32_t *)quo.d_qsrc.p, (const uint32_t *)quo.d_qdst.p,
+                           (const uint32_t *)quo.d_qlid.p, (const uint32_t *)quo.d_qcls[cur].p, (const uint32_t *)quo.d_qtab_e.p, mask_e, quo.d_qctl.p);
+    hipLaunchKernelGGL(k_q_verify_states, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)post.d_live.p, (const uint8_t *)post.d_pfinal.p,
+                       (const uint32_t *)quo.d_qcls[cur].p, (const uint32_t *)quo.d_qcnt.p, quo.d_qctl.p);
     HIPCHK(hipGetLastError());
-    q_raw.resize(S);
-    q_cnt.resize(S);
-    HIPCHK(hipMemcpyAsync(q_raw.data(), d_qcls[cur].p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
-    HIPCHK(hipMemcpyAsync(q_cnt.data(), d_qcnt.p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+    quo.q_raw.resize(S);
+    quo.q_cnt.resize(S);
+    HIPCHK(hipMemcpyAsync(quo.q_raw.data(), quo.d_qcls[cur].p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(quo.q_cnt.data(), quo.d_qcnt.p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
     if (int rc = check()) return rc;
     // canonical class numbers: by least member (the first state, in index order, that shows the class)
-    q_class.assign(S, -1);
+    quo.q_class.assign(S, -1);
     std::vector<int32_t> number(S, -1);
     int64_t n_classes = 0, n_class_edges = 0;
     for (uint32_t s = 0; s < S; s++) {
-        const uint32_t r = q_raw[s];
+        const uint32_t r = quo.q_raw[s];
         if (r == kQEmpty) continue;  // (not live)
         if (number[r] < 0) {
             number[r] = (int32_t)n_classes++;
-            n_class_edges += q_cnt[r];
+            n_class_edges += quo.q_cnt[r];
         }
-        q_class[s] = number[r];
+        quo.q_class[s] = number[r];
     }
     memset(out, 0, sizeof *out);
-    out->n_states = n_live;
+    out->n_states = post.n_live;
     out->n_classes = n_classes;
     out->n_class_edges = n_class_edges;
-    out->state_class = q_class.data();
+    out->state_class = quo.q_class.data();
     out->rounds = rounds;
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;
@@ -358,56 +396,56 @@ int AutomatonServices::quotient(const AutomatonView &view, const stcsp_quotient_
 int AutomatonServices::monitor_build(const AutomatonView &view, const stcsp_monitor_options *mo, stcsp_monitor_info *info) {
     if (int rc = enter(view, "monitor_build", NEED_FLAGS, "stcsp_automaton_check_streams")) return rc;
     auto t0 = std::chrono::steady_clock::now();
-    mon_built = false;
-    mon_host.reset();
+    mon.built = false;
+    mon.host.reset();
     const int N = v.N;
     const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
     const uint8_t *mask = mo && mo->observable ? mo->observable : v.default_observable;
     const std::vector<int32_t> obs = observed_columns(mask, N);
-    mon_observable.assign(mask, mask + N);
+    mon.observable.assign(mask, mask + N);
     size_t cap = 1024;
     while (cap < 2 * (size_t)E) cap <<= 1;
     if (cap > 0x80000000ull) return fail(STCSP_E_NOMEM, "edge list too large for the device monitor");
     if (int rc = live_set()) return rc;
-    HIPCHK(reserve_all(E, 1, d_mdst, d_mnext));
-    HIPCHK(d_mltab.reserve_exact(cap));
-    HIPCHK(d_mhead.reserve_exact(cap));
-    HIPCHK(d_mdst0.reserve_exact(cap));
-    HIPCHK(d_mkeys.reserve_exact(cap));
-    HIPCHK(d_mobs.reserve_exact((size_t)N));
-    HIPCHK(d_mctl.reserve_exact(M_WORDS));
+    HIPCHK(reserve_all(E, 1, mon.d_mdst, mon.d_mnext));
+    HIPCHK(mon.d_mltab.reserve_exact(cap));
+    HIPCHK(mon.d_mhead.reserve_exact(cap));
+    HIPCHK(mon.d_mdst0.reserve_exact(cap));
+    HIPCHK(mon.d_mkeys.reserve_exact(cap));
+    HIPCHK(mon.d_mobs.reserve_exact((size_t)N));
+    HIPCHK(mon.d_mctl.reserve_exact(M_WORDS));
     const unsigned eb = (E + 255) / 256;
     uint32_t ctl[M_WORDS] = {0};
-    if (!obs.empty()) HIPCHK(hipMemcpyAsync(d_mobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-    HIPCHK(hipMemsetAsync(d_mctl.p, 0, sizeof ctl, v.stream));
+    if (!obs.empty()) HIPCHK(hipMemcpyAsync(mon.d_mobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+    HIPCHK(hipMemsetAsync(mon.d_mctl.p, 0, sizeof ctl, v.stream));
     if (E) {
-        HIPCHK(hipMemsetAsync(d_mltab.p, 0xff, cap * sizeof(uint32_t), v.stream));
-        HIPCHK(hipMemsetAsync(d_mhead.p, 0xff, cap * sizeof(uint32_t), v.stream));
-        HIPCHK(hipMemsetAsync(d_mkeys.p, 0xff, cap * sizeof(unsigned long long), v.stream));
+        HIPCHK(hipMemsetAsync(mon.d_mltab.p, 0xff, cap * sizeof(uint32_t), v.stream));
+        HIPCHK(hipMemsetAsync(mon.d_mhead.p, 0xff, cap * sizeof(uint32_t), v.stream));
+        HIPCHK(hipMemsetAsync(mon.d_mkeys.p, 0xff, cap * sizeof(unsigned long long), v.stream));
         hipLaunchKernelGGL(k_m_build, dim3(eb), dim3(256), 0, v.stream, E, (const long long *)v.d_osrc, (const long long *)v.d_odst,
-                           (const int32_t *)v.d_oval, N, (const int32_t *)d_mobs.p, (int)obs.size(), (const uint8_t *)d_palive.p,
-                           (const uint8_t *)d_live.p, d_mltab.p, d_mkeys.p, d_mhead.p, (uint32_t)(cap - 1), d_mdst.p, d_mnext.p, d_mctl.p);
-        hipLaunchKernelGGL(k_m_finish, dim3((unsigned)(cap / 256)), dim3(256), 0, v.stream, (uint32_t)cap, (const unsigned long long *)d_mkeys.p,
-                           (const uint32_t *)d_mhead.p, d_mnext.p, (const uint32_t *)d_mdst.p, d_mdst0.p, d_mctl.p);
+                           (const int32_t *)v.d_oval, N, (const int32_t *)mon.d_mobs.p, (int)obs.size(), (const uint8_t *)post.d_palive.p,
+                           (const uint8_t *)post.d_live.p, mon.d_mltab.p, mon.d_mkeys.p, mon.d_mhead.p, (uint32_t)(cap - 1), mon.d_mdst.p, mon.d_mnext.p, mon.d_mctl.p);
+        hipLaunchKernelGGL(k_m_finish, dim3((unsigned)(cap / 256)), dim3(256), 0, v.stream, (uint32_t)cap, (const unsigned long long *)mon.d_mkeys.p,
+                           (const uint32_t *)mon.d_mhead.p, mon.d_mnext.p, (const uint32_t *)mon.d_mdst.p, mon.d_mdst0.p, mon.d_mctl.p);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipMemcpyAsync(ctl, d_mctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(ctl, mon.d_mctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
     HIPCHK(hipStreamSynchronize(v.stream));
     if (ctl[M_ERROR]) return fail(STCSP_E_INTERNAL, "monitor: a device table overflowed");
-    mon_n_obs = (int)obs.size();
-    mon_max_dst = (int)std::max(ctl[M_MAXDST], ctl[M_PAIRS] ? 1u : 0u);
-    mon_mask = (uint32_t)(cap - 1);
-    mon_built = true;
+    mon.n_obs = (int)obs.size();
+    mon.max_dst = (int)std::max(ctl[M_MAXDST], ctl[M_PAIRS] ? 1u : 0u);
+    mon.mask = (uint32_t)(cap - 1);
+    mon.built = true;
     memset(info, 0, sizeof *info);
-    info->n_states = n_live;
+    info->n_states = post.n_live;
     info->n_edges = ctl[M_EDGES];
     info->n_labels = ctl[M_LABELS];
     info->n_pairs = ctl[M_PAIRS];
     info->table_bytes = (int64_t)(E ? cap * (3 * sizeof(uint32_t) + sizeof(unsigned long long)) + 2 * (size_t)E * sizeof(uint32_t) : 0) + S;
-    info->n_observable = mon_n_obs;
-    info->max_destinations = mon_max_dst;
+    info->n_observable = mon.n_obs;
+    info->max_destinations = mon.max_dst;
     info->set_capacity = kMonSetCap;
-    info->root_live = root_live;
+    info->root_live = post.root_live;
     info->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;
 }
@@ -420,53 +458,53 @@ int AutomatonServices::monitor_check(const AutomatonView &view, const stcsp_moni
     auto t0 = std::chrono::steady_clock::now();
     const size_t n = (size_t)ms->n_streams;
     const size_t steps = n ? (size_t)ms->offsets[n] : 0;
-    if (steps && mon_n_obs && !ms->values) return fail(STCSP_E_INVALID, "monitor_check: no step values");
+    if (steps && mon.n_obs && !ms->values) return fail(STCSP_E_INVALID, "monitor_check: no step values");
     if (n >= 0x7fffffffull || steps >= 0x7fffffffull) return fail(STCSP_E_NOMEM, "monitor_check: too many streams or steps for one call");
-    m_acc.assign(n, 0);
-    m_nend.assign(n, 0);
-    m_fin.assign(n, 0);
+    mon.m_acc.assign(n, 0);
+    mon.m_nend.assign(n, 0);
+    mon.m_fin.assign(n, 0);
     memset(out, 0, sizeof *out);
     out->n_streams = ms->n_streams;
-    out->accepted_len = m_acc.data();
-    out->n_end = m_nend.data();
-    out->end_final = m_fin.data();
-    if (n && root_live) {
-        const bool sets = mon_max_dst > 1 || (ms->flags & STCSP_MON_FORCE_SETS);
+    out->accepted_len = mon.m_acc.data();
+    out->n_end = mon.m_nend.data();
+    out->end_final = mon.m_fin.data();
+    if (n && post.root_live) {
+        const bool sets = mon.max_dst > 1 || (ms->flags & STCSP_MON_FORCE_SETS);
         const uint32_t E = (uint32_t)v.exp_edges;
-        HIPCHK(d_moff.reserve(n, 1));
-        HIPCHK(reserve_all(n, 0, d_macc, d_mnend, d_mfin));
-        HIPCHK(d_mlid.reserve(steps));
-        HIPCHK(d_mrows.reserve(steps * mon_n_obs));
+        HIPCHK(mon.d_moff.reserve(n, 1));
+        HIPCHK(reserve_all(n, 0, mon.d_macc, mon.d_mnend, mon.d_mfin));
+        HIPCHK(mon.d_mlid.reserve(steps));
+        HIPCHK(mon.d_mrows.reserve(steps * mon.n_obs));
         HIPCHK(ev.ready(3));
-        HIPCHK(hipMemcpyAsync(d_moff.p, ms->offsets, (n + 1) * sizeof(long long), hipMemcpyHostToDevice, v.stream));
-        if (steps * mon_n_obs) HIPCHK(hipMemcpyAsync(d_mrows.p, ms->values, steps * mon_n_obs * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-        HIPCHK(hipMemsetAsync(d_mctl.p + M_OVERFLOW, 0, sizeof(uint32_t), v.stream));
+        HIPCHK(hipMemcpyAsync(mon.d_moff.p, ms->offsets, (n + 1) * sizeof(long long), hipMemcpyHostToDevice, v.stream));
+        if (steps * mon.n_obs) HIPCHK(hipMemcpyAsync(mon.d_mrows.p, ms->values, steps * mon.n_obs * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+        HIPCHK(hipMemsetAsync(mon.d_mctl.p + M_OVERFLOW, 0, sizeof(uint32_t), v.stream));
         HIPCHK(hipEventRecord(ev[0], v.stream));
         if (steps) {
             if (E)
-                hipLaunchKernelGGL(k_m_steps, dim3((unsigned)((steps + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)steps, (const int32_t *)d_mrows.p,
-                                   mon_n_obs, (const int32_t *)v.d_oval, v.N, (const int32_t *)d_mobs.p, (const uint32_t *)d_mltab.p, mon_mask,
-                                   d_mlid.p);
+                hipLaunchKernelGGL(k_m_steps, dim3((unsigned)((steps + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)steps, (const int32_t *)mon.d_mrows.p,
+                                   mon.n_obs, (const int32_t *)v.d_oval, v.N, (const int32_t *)mon.d_mobs.p, (const uint32_t *)mon.d_mltab.p, mon.mask,
+                                   mon.d_mlid.p);
             else  // no edge, no label: every step is a rejection
-                HIPCHK(hipMemsetAsync(d_mlid.p, 0xff, steps * sizeof(uint32_t), v.stream));
+                HIPCHK(hipMemsetAsync(mon.d_mlid.p, 0xff, steps * sizeof(uint32_t), v.stream));
         }
         HIPCHK(hipEventRecord(ev[1], v.stream));
         if (sets)
-            hipLaunchKernelGGL(k_m_walk_sets, dim3((unsigned)n), dim3(64), 0, v.stream, (uint32_t)n, (const long long *)d_moff.p,
-                               (const uint32_t *)d_mlid.p, (const unsigned long long *)d_mkeys.p, (const uint32_t *)d_mhead.p,
-                               (const uint32_t *)d_mnext.p, (const uint32_t *)d_mdst.p, mon_mask, (const uint8_t *)d_pfinal.p, d_macc.p, d_mnend.p,
-                               d_mfin.p, d_mctl.p);
+            hipLaunchKernelGGL(k_m_walk_sets, dim3((unsigned)n), dim3(64), 0, v.stream, (uint32_t)n, (const long long *)mon.d_moff.p,
+                               (const uint32_t *)mon.d_mlid.p, (const unsigned long long *)mon.d_mkeys.p, (const uint32_t *)mon.d_mhead.p,
+                               (const uint32_t *)mon.d_mnext.p, (const uint32_t *)mon.d_mdst.p, mon.mask, (const uint8_t *)post.d_pfinal.p, mon.d_macc.p, mon.d_mnend.p,
+                               mon.d_mfin.p, mon.d_mctl.p);
         else
-            hipLaunchKernelGGL(k_m_walk_det, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)n, (const long long *)d_moff.p,
-                               (const uint32_t *)d_mlid.p, (const unsigned long long *)d_mkeys.p, (const uint32_t *)d_mdst0.p, mon_mask,
-                               (const uint8_t *)d_pfinal.p, d_macc.p, d_mnend.p, d_mfin.p);
+            hipLaunchKernelGGL(k_m_walk_det, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)n, (const long long *)mon.d_moff.p,
+                               (const uint32_t *)mon.d_mlid.p, (const unsigned long long *)mon.d_mkeys.p, (const uint32_t *)mon.d_mdst0.p, mon.mask,
+                               (const uint8_t *)post.d_pfinal.p, mon.d_macc.p, mon.d_mnend.p, mon.d_mfin.p);
         HIPCHK(hipEventRecord(ev[2], v.stream));
         HIPCHK(hipGetLastError());
         uint32_t over = 0;
-        HIPCHK(hipMemcpyAsync(m_acc.data(), d_macc.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(hipMemcpyAsync(m_nend.data(), d_mnend.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(hipMemcpyAsync(m_fin.data(), d_mfin.p, n, hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(hipMemcpyAsync(&over, d_mctl.p + M_OVERFLOW, sizeof over, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(mon.m_acc.data(), mon.d_macc.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(mon.m_nend.data(), mon.d_mnend.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(mon.m_fin.data(), mon.d_mfin.p, n, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(&over, mon.d_mctl.p + M_OVERFLOW, sizeof over, hipMemcpyDeviceToHost, v.stream));
         HIPCHK(hipStreamSynchronize(v.stream));
         float ms_l = 0, ms_w = 0;
         HIPCHK(hipEventElapsedTime(&ms_l, ev[0], ev[1]));
@@ -475,15 +513,15 @@ int AutomatonServices::monitor_check(const AutomatonView &view, const stcsp_moni
         out->seconds_walk = ms_w * 1e-3;
         out->walk_kernel = sets ? 2 : 1;
         if (over) {
-            if (!mon_host) {
+            if (!mon.host) {
                 const MonitorView mv{v.N, v.n_states, (int64_t)v.exp_edges, (const int64_t *)v.h_osrc, (const int64_t *)v.h_odst, v.h_oval,
-                                     p_valid.data(), p_final.data(), p_alive.data()};
-                mon_host.reset(new HostMonitor());
-                mon_host->build(mv, mon_observable.data());
+                                     post.p_valid.data(), post.p_final.data(), post.p_alive.data()};
+                mon.host.reset(new HostMonitor());
+                mon.host->build(mv, mon.observable.data());
             }
             for (size_t i = 0; i < n; i++)
-                if (m_acc[i] < 0) {
-                    mon_host->check_one(ms->values + ms->offsets[i] * mon_n_obs, ms->offsets[i + 1] - ms->offsets[i], &m_acc[i], &m_nend[i], &m_fin[i]);
+                if (mon.m_acc[i] < 0) {
+                    mon.host->check_one(ms->values + ms->offsets[i] * mon.n_obs, ms->offsets[i + 1] - ms->offsets[i], &mon.m_acc[i], &mon.m_nend[i], &mon.m_fin[i]);
                     out->n_host_fallback++;
                 }
         }
@@ -498,71 +536,68 @@ int AutomatonServices::generator_build(const AutomatonView &view, const stcsp_ge
     if (int rc = enter(view, "generator_build", NEED_FLAGS, "stcsp_automaton_generate")) return rc;
     if (!go || go->horizon < 0) return fail(STCSP_E_INVALID, "generator_build: the horizon must not be negative");
     auto t0 = std::chrono::steady_clock::now();
-    gen_built = false;
-    rep_built = false;
-    inf_built = false;
-    obs_built = false;
-    cmp_valid = false;
+    gen.built = false;
+    gen.drop_derived();
     const int N = v.N, H = go->horizon;
     const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
     if ((size_t)v.exp_edges > 0x7fffffffull) return fail(STCSP_E_NOMEM, "edge list too large for the device generator");
     const std::vector<int32_t> obs = observed_columns(go->observable ? go->observable : v.default_observable, N);
     const uint32_t n_tiles = (S + kGenScanTile - 1) / kGenScanTile;
     if (int rc = live_set()) return rc;
-    HIPCHK(d_gtile.reserve_exact(grown(S) / kGenScanTile + 2));
-    HIPCHK(d_goff.reserve(S, 1));
-    HIPCHK(d_gcur.reserve(S));
-    HIPCHK(reserve_all(E, 0, d_gseg, d_geid, d_gdst));
+    HIPCHK(gen.d_gtile.reserve_exact(grown(S) / kGenScanTile + 2));
+    HIPCHK(gen.d_goff.reserve(S, 1));
+    HIPCHK(gen.d_gcur.reserve(S));
+    HIPCHK(reserve_all(E, 0, gen.d_gseg, gen.d_geid, gen.d_gdst));
     const size_t table = ((size_t)H + 1) * S;
-    if (!d_gw.reserve_or_release(table)) return fail(STCSP_E_NOMEM, "generator_build: no room for the %d x %u table of weights", H + 1, S);
-    HIPCHK(d_gcount.reserve_exact((size_t)H + 1));
-    HIPCHK(d_gobs.reserve_exact((size_t)N));
-    HIPCHK(d_gctl.reserve_exact(G_WORDS));
+    if (!gen.d_gw.reserve_or_release(table)) return fail(STCSP_E_NOMEM, "generator_build: no room for the %d x %u table of weights", H + 1, S);
+    HIPCHK(gen.d_gcount.reserve_exact((size_t)H + 1));
+    HIPCHK(gen.d_gobs.reserve_exact((size_t)N));
+    HIPCHK(gen.d_gctl.reserve_exact(G_WORDS));
     const unsigned eb = (E + 255) / 256, sb = (S + 255) / 256;
     uint32_t ctl[G_WORDS] = {0}, total = 0;
-    if (!obs.empty()) HIPCHK(hipMemcpyAsync(d_gobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-    HIPCHK(hipMemsetAsync(d_gctl.p, 0, sizeof ctl, v.stream));
+    if (!obs.empty()) HIPCHK(hipMemcpyAsync(gen.d_gobs.p, obs.data(), obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+    HIPCHK(hipMemsetAsync(gen.d_gctl.p, 0, sizeof ctl, v.stream));
     // live edges by source: histogram, exclusive scan over the states, fill through a cursor, canonical order
-    HIPCHK(hipMemsetAsync(d_gcur.p, 0, (size_t)S * sizeof(uint32_t), v.stream));
+    HIPCHK(hipMemsetAsync(gen.d_gcur.p, 0, (size_t)S * sizeof(uint32_t), v.stream));
     if (E)
         hipLaunchKernelGGL(k_g_degree, dim3(eb), dim3(256), 0, v.stream, E, (const long long *)v.d_osrc, (const long long *)v.d_odst,
-                           (const uint8_t *)d_palive.p, (const uint8_t *)d_live.p, d_gcur.p);
-    hipLaunchKernelGGL(k_g_scan_tiles, dim3(n_tiles), dim3(256), 0, v.stream, S, (const uint32_t *)d_gcur.p, d_gtile.p);
-    hipLaunchKernelGGL(k_g_scan_sums, dim3(1), dim3(256), 0, v.stream, n_tiles, d_gtile.p);
-    hipLaunchKernelGGL(k_g_scan_write, dim3(n_tiles), dim3(256), 0, v.stream, S, (const uint32_t *)d_gcur.p, (const uint32_t *)d_gtile.p, n_tiles,
-                       d_goff.p, d_gcur.p);
+                           (const uint8_t *)post.d_palive.p, (const uint8_t *)post.d_live.p, gen.d_gcur.p);
+    hipLaunchKernelGGL(k_g_scan_tiles, dim3(n_tiles), dim3(256), 0, v.stream, S, (const uint32_t *)gen.d_gcur.p, gen.d_gtile.p);
+    hipLaunchKernelGGL(k_g_scan_sums, dim3(1), dim3(256), 0, v.stream, n_tiles, gen.d_gtile.p);
+    hipLaunchKernelGGL(k_g_scan_write, dim3(n_tiles), dim3(256), 0, v.stream, S, (const uint32_t *)gen.d_gcur.p, (const uint32_t *)gen.d_gtile.p, n_tiles,
+                       gen.d_goff.p, gen.d_gcur.p);
     if (E) {
         hipLaunchKernelGGL(k_g_fill, dim3(eb), dim3(256), 0, v.stream, E, (const long long *)v.d_osrc, (const long long *)v.d_odst,
-                           (const uint8_t *)d_palive.p, (const uint8_t *)d_live.p, d_gcur.p, d_gseg.p);
-        hipLaunchKernelGGL(k_g_order, dim3((S + 3) / 4), dim3(256), 0, v.stream, S, (const uint32_t *)d_goff.p, d_gseg.p, (const long long *)v.d_odst,
-                           (const int32_t *)v.d_oval, N, d_geid.p, d_gdst.p, d_gctl.p);
+                           (const uint8_t *)post.d_palive.p, (const uint8_t *)post.d_live.p, gen.d_gcur.p, gen.d_gseg.p);
+        hipLaunchKernelGGL(k_g_order, dim3((S + 3) / 4), dim3(256), 0, v.stream, S, (const uint32_t *)gen.d_goff.p, gen.d_gseg.p, (const long long *)v.d_odst,
+                           (const int32_t *)v.d_oval, N, gen.d_geid.p, gen.d_gdst.p, gen.d_gctl.p);
     }
     // the weights, one launch per level
-    hipLaunchKernelGGL(k_g_level0, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint8_t *)d_pfinal.p,
-                       (go->flags & STCSP_GEN_END_FINAL) ? 1 : 0, d_gw.p, d_gcount.p);
+    hipLaunchKernelGGL(k_g_level0, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)post.d_live.p, (const uint8_t *)post.d_pfinal.p,
+                       (go->flags & STCSP_GEN_END_FINAL) ? 1 : 0, gen.d_gw.p, gen.d_gcount.p);
     for (int t = 0; t < H; t++)
-        hipLaunchKernelGGL(k_g_weights, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)d_goff.p, (const uint32_t *)d_gdst.p,
-                           (const double *)(d_gw.p + (size_t)t * S), d_gw.p + (size_t)(t + 1) * S, d_gcount.p + t + 1);
+        hipLaunchKernelGGL(k_g_weights, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)gen.d_goff.p, (const uint32_t *)gen.d_gdst.p,
+                           (const double *)(gen.d_gw.p + (size_t)t * S), gen.d_gw.p + (size_t)(t + 1) * S, gen.d_gcount.p + t + 1);
     HIPCHK(hipGetLastError());
-    gen_count.assign((size_t)H + 1, 0.0);
-    HIPCHK(hipMemcpyAsync(gen_count.data(), d_gcount.p, ((size_t)H + 1) * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-    HIPCHK(hipMemcpyAsync(&total, d_goff.p + S, sizeof total, hipMemcpyDeviceToHost, v.stream));
-    HIPCHK(hipMemcpyAsync(ctl, d_gctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+    gen.count.assign((size_t)H + 1, 0.0);
+    HIPCHK(hipMemcpyAsync(gen.count.data(), gen.d_gcount.p, ((size_t)H + 1) * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(&total, gen.d_goff.p + S, sizeof total, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(ctl, gen.d_gctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
     HIPCHK(hipStreamSynchronize(v.stream));
-    for (double c : gen_count)
+    for (double c : gen.count)
         if (!std::isfinite(c)) return fail(STCSP_E_UNSUPPORTED, "generator_build: the number of prefixes of length %d overflows a double", H);
-    gen_n_obs = (int)obs.size();
-    gen_horizon = H;
-    gen_built = true;
+    gen.n_obs = (int)obs.size();
+    gen.horizon = H;
+    gen.built = true;
     memset(info, 0, sizeof *info);
-    info->n_states = n_live;
+    info->n_states = post.n_live;
     info->n_edges = total;
     info->table_bytes = (int64_t)(table * sizeof(double) + 3 * (size_t)E * sizeof(uint32_t) + (2 * (size_t)S + 1) * sizeof(uint32_t) + S);
-    info->count = gen_count.data();
-    info->n_observable = gen_n_obs;
+    info->count = gen.count.data();
+    info->n_observable = gen.n_obs;
     info->horizon = H;
     info->max_out_degree = (int32_t)ctl[G_MAXDEG];
-    info->root_live = root_live;
+    info->root_live = post.root_live;
     info->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;
 }
@@ -570,39 +605,39 @@ int AutomatonServices::generator_build(const AutomatonView &view, const stcsp_ge
 // Stream generator, generate: n_streams prefixes of one length, sampled or unranked (contract: stcsp_engine.h).
 int AutomatonServices::generate(const AutomatonView &view, const stcsp_generate_request *rq, stcsp_generate_result *out) {
     if (int rc = enter(view, "generate", NEED_GENERATOR, "stcsp_automaton_generate")) return rc;
-    if (!generate_request_ok(gen_count, rq->n_streams, rq->len, rq->n_streams > 0 ? rq->ranks : nullptr))
+    if (!generate_request_ok(gen.count, rq->n_streams, rq->len, rq->n_streams > 0 ? rq->ranks : nullptr))
         return fail(STCSP_E_INVALID, "generate: a length outside 0 .. horizon or without a prefix, or a rank that is not below count[len] < 2^53");
     auto t0 = std::chrono::steady_clock::now();
     const size_t n = (size_t)rq->n_streams, len = (size_t)rq->len;
-    const size_t cells = n * len * (size_t)gen_n_obs;
+    const size_t cells = n * len * (size_t)gen.n_obs;
     if (n >= 0x7fffffffull) return fail(STCSP_E_NOMEM, "generate: too many streams for one call");
-    g_values.assign(cells, 0);
-    g_fin.assign(n, 0);
+    gen.g_values.assign(cells, 0);
+    gen.g_fin.assign(n, 0);
     memset(out, 0, sizeof *out);
     out->n_streams = rq->n_streams;
-    out->values = g_values.data();
-    out->end_final = g_fin.data();
+    out->values = gen.g_values.data();
+    out->end_final = gen.g_fin.data();
     out->len = rq->len;
-    out->n_observable = gen_n_obs;
+    out->n_observable = gen.n_obs;
     if (n) {  // (count[len] > 0: the root is live)
-        HIPCHK(d_gfin.reserve(n));
-        HIPCHK(d_gout.reserve(cells));
-        if (rq->ranks) HIPCHK(d_granks.reserve(n));
+        HIPCHK(gen.d_gfin.reserve(n));
+        HIPCHK(gen.d_gout.reserve(cells));
+        if (rq->ranks) HIPCHK(gen.d_granks.reserve(n));
         HIPCHK(ev.ready(2));
-        if (rq->ranks) HIPCHK(hipMemcpyAsync(d_granks.p, rq->ranks, n * sizeof(uint64_t), hipMemcpyHostToDevice, v.stream));
-        HIPCHK(hipMemsetAsync(d_gctl.p + G_ERROR, 0, sizeof(uint32_t), v.stream));
+        if (rq->ranks) HIPCHK(hipMemcpyAsync(gen.d_granks.p, rq->ranks, n * sizeof(uint64_t), hipMemcpyHostToDevice, v.stream));
+        HIPCHK(hipMemsetAsync(gen.d_gctl.p + G_ERROR, 0, sizeof(uint32_t), v.stream));
         HIPCHK(hipEventRecord(ev[0], v.stream));
         const dim3 grid((unsigned)((n + 255) / 256)), block(256);
         hipLaunchKernelGGL(rq->ranks ? k_g_generate<true> : k_g_generate<false>, grid, block, 0, v.stream, (uint32_t)n, (uint32_t)len,
-                           rq->ranks ? 0ull : (unsigned long long)rq->seed, rq->ranks ? (const unsigned long long *)d_granks.p : nullptr, v.n_states,
-                           (const double *)d_gw.p, (const uint32_t *)d_goff.p, (const uint32_t *)d_gdst.p, (const uint32_t *)d_geid.p,
-                           (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p, gen_n_obs, (const uint8_t *)d_pfinal.p, d_gout.p, d_gfin.p, d_gctl.p);
+                           rq->ranks ? 0ull : (unsigned long long)rq->seed, rq->ranks ? (const unsigned long long *)gen.d_granks.p : nullptr, v.n_states,
+                           (const double *)gen.d_gw.p, (const uint32_t *)gen.d_goff.p, (const uint32_t *)gen.d_gdst.p, (const uint32_t *)gen.d_geid.p,
+                           (const int32_t *)v.d_oval, v.N, (const int32_t *)gen.d_gobs.p, gen.n_obs, (const uint8_t *)post.d_pfinal.p, gen.d_gout.p, gen.d_gfin.p, gen.d_gctl.p);
         HIPCHK(hipEventRecord(ev[1], v.stream));
         HIPCHK(hipGetLastError());
         uint32_t bad = 0;
-        if (cells) HIPCHK(hipMemcpyAsync(g_values.data(), d_gout.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(hipMemcpyAsync(g_fin.data(), d_gfin.p, n, hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(hipMemcpyAsync(&bad, d_gctl.p + G_ERROR, sizeof bad, hipMemcpyDeviceToHost, v.stream));
+        if (cells) HIPCHK(hipMemcpyAsync(gen.g_values.data(), gen.d_gout.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(gen.g_fin.data(), gen.d_gfin.p, n, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(&bad, gen.d_gctl.p + G_ERROR, sizeof bad, hipMemcpyDeviceToHost, v.stream));
         HIPCHK(hipStreamSynchronize(v.stream));
         float ms_k = 0;
         HIPCHK(hipEventElapsedTime(&ms_k, ev[0], ev[1]));
@@ -617,132 +652,111 @@ int AutomatonServices::generate(const AutomatonView &view, const stcsp_generate_
 int AutomatonServices::repair_labels() {
     const uint32_t S = v.n_states;
     uint32_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, d_goff.p + S, sizeof total, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(&total, gen.d_goff.p + S, sizeof total, hipMemcpyDeviceToHost, v.stream));
     HIPCHK(hipStreamSynchronize(v.stream));
     uint32_t slots = 64;
     while (slots < 2 * (size_t)total && slots < 0x80000000u) slots <<= 1;
-    HIPCHK(d_rtab.reserve_exact(slots));
-    HIPCHK(reserve_all(total, 0, d_rlid, d_rrep));
-    HIPCHK(d_rlong.reserve(S));
-    HIPCHK(d_rctl.reserve_exact(R_WORDS));
-    rep_wave_segment = kRepWaveSegment;
-    if (const char *e = getenv("STCSP_REPAIR_WAVE_SEGMENT")) rep_wave_segment = (uint32_t)std::max(1ll, std::min(atoll(e), 0x7fffffffll));
+    HIPCHK(lab.d_rtab.reserve_exact(slots));
+    HIPCHK(reserve_all(total, 0, lab.d_rlid, lab.d_rrep));
+    HIPCHK(lab.d_rlong.reserve(S));
+    HIPCHK(lab.d_rctl.reserve_exact(R_WORDS));
+    lab.wave_segment = kRepWaveSegment;
+    if (const char *e = getenv("STCSP_REPAIR_WAVE_SEGMENT")) lab.wave_segment = (uint32_t)std::max(1ll, std::min(atoll(e), 0x7fffffffll));
     uint32_t ctl[R_WORDS] = {0};
-    HIPCHK(hipMemsetAsync(d_rctl.p, 0, sizeof ctl, v.stream));
-    HIPCHK(hipMemsetAsync(d_rtab.p, 0xff, (size_t)slots * sizeof(uint32_t), v.stream));
+    HIPCHK(hipMemsetAsync(lab.d_rctl.p, 0, sizeof ctl, v.stream));
+    HIPCHK(hipMemsetAsync(lab.d_rtab.p, 0xff, (size_t)slots * sizeof(uint32_t), v.stream));
     if (total) {
         const unsigned kb = (total + 255) / 256;
-        hipLaunchKernelGGL(k_r_labels, dim3(kb), dim3(256), 0, v.stream, total, (const uint32_t *)d_geid.p, (const int32_t *)v.d_oval, v.N,
-                           (const int32_t *)d_gobs.p, gen_n_obs, d_rtab.p, slots - 1, d_rlid.p, d_rctl.p);
-        hipLaunchKernelGGL(k_r_number, dim3((slots + 255) / 256), dim3(256), 0, v.stream, slots, d_rtab.p, d_rrep.p, d_rctl.p);
-        hipLaunchKernelGGL(k_r_remap, dim3(kb), dim3(256), 0, v.stream, total, (const uint32_t *)d_rtab.p, d_rlid.p);
+        hipLaunchKernelGGL(k_r_labels, dim3(kb), dim3(256), 0, v.stream, total, (const uint32_t *)gen.d_geid.p, (const int32_t *)v.d_oval, v.N,
+                           (const int32_t *)gen.d_gobs.p, gen.n_obs, lab.d_rtab.p, slots - 1, lab.d_rlid.p, lab.d_rctl.p);
+        hipLaunchKernelGGL(k_r_number, dim3((slots + 255) / 256), dim3(256), 0, v.stream, slots, lab.d_rtab.p, lab.d_rrep.p, lab.d_rctl.p);
+        hipLaunchKernelGGL(k_r_remap, dim3(kb), dim3(256), 0, v.stream, total, (const uint32_t *)lab.d_rtab.p, lab.d_rlid.p);
     }
-    hipLaunchKernelGGL(k_r_long, dim3((S + 255) / 256), dim3(256), 0, v.stream, S, (const uint32_t *)d_goff.p, rep_wave_segment, d_rlong.p, d_rctl.p);
+    hipLaunchKernelGGL(k_r_long, dim3((S + 255) / 256), dim3(256), 0, v.stream, S, (const uint32_t *)gen.d_goff.p, lab.wave_segment, lab.d_rlong.p, lab.d_rctl.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(ctl, d_rctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(ctl, lab.d_rctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
     HIPCHK(hipStreamSynchronize(v.stream));
     if (ctl[R_ERROR]) return fail(STCSP_E_INTERNAL, "repair: the label table overflowed");
-    rep_total = total;
-    rep_n_labels = ctl[R_LABELS];
-    rep_n_long = ctl[R_LONG];
-    rep_built = true;
+    lab.total = total;
+    lab.n_labels = ctl[R_LABELS];
+    lab.n_long = ctl[R_LONG];
+    lab.built = true;
     return STCSP_OK;
 }
 
 // Stream repair: the nearest solution prefix of every stream (contract: stcsp_engine.h).
 int AutomatonServices::repair(const AutomatonView &view, const stcsp_repair_request *rq, stcsp_repair_result *out) {
     if (int rc = enter(view, "repair", NEED_GENERATOR, "stcsp_automaton_repair_streams")) return rc;
-    if (!repair_request_ok(rq->n_streams, rq->offsets, rq->weights, gen_n_obs))
+    if (!repair_request_ok(rq->n_streams, rq->offsets, rq->weights, gen.n_obs))
         return fail(STCSP_E_INVALID, "repair: malformed stream offsets, a negative weight, or (sum of the weights) x (longest stream) above 2^31 - 2");
     auto t0 = std::chrono::steady_clock::now();
-    const size_t n = (size_t)rq->n_streams, n_obs = (size_t)gen_n_obs;
+    const size_t n = (size_t)rq->n_streams, n_obs = (size_t)gen.n_obs;
     const size_t steps = n ? (size_t)rq->offsets[n] : 0;
     if (steps && n_obs && !rq->values) return fail(STCSP_E_INVALID, "repair: no step values");
-    r_dist.assign(n, -1);
-    r_values.assign(steps * n_obs, 0);
-    r_fin.assign(n, 0);
-    r_nchg.assign(n, 0);
+    rep.r_dist.assign(n, -1);
+    rep.r_values.assign(steps * n_obs, 0);
+    rep.r_fin.assign(n, 0);
+    rep.r_nchg.assign(n, 0);
     memset(out, 0, sizeof *out);
     out->n_streams = rq->n_streams;
-    out->distance = r_dist.data();
-    out->values = r_values.data();
-    out->end_final = r_fin.data();
-    out->n_changed = r_nchg.data();
-    out->n_observable = gen_n_obs;
-    if (n && root_live) {
-        if (int rc = rep_built ? STCSP_OK : repair_labels()) return rc;
-        const uint32_t S = v.n_states, nL = rep_n_labels;
-        const int end_final = (rq->flags & STCSP_REPAIR_END_FINAL) ? 1 : 0;
-        size_t budget = 0;
-        if (int rc = table_budget("STCSP_REPAIR_BYTES", budget)) return rc;
-        auto need = [&](size_t len) { return ((len + 1) * (size_t)S + len * (size_t)nL) * sizeof(uint32_t); };
-        std::vector<int32_t> w(n_obs, 1);
-        if (rq->weights) w.assign(rq->weights, rq->weights + n_obs);
-        if (d_rweights.n < n_obs) HIPCHK(d_rweights.alloc(n_obs + 16));
-        if (n_obs) HIPCHK(hipMemcpyAsync(d_rweights.p, w.data(), n_obs * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-        HIPCHK(ev.ready(4));
-        std::vector<RepStream> meta;
-        const unsigned sb = (S + 255) / 256;
-        for (size_t b0 = 0; b0 < n;) {
-            Batch b;  // consecutive streams while their tables and costs fit the budget
-            if (int rc = plan_batch("repair", rq->offsets, n, b0, budget, need, meta, b)) return rc;
-            const size_t nb = b.b1 - b0, cells = b.steps * n_obs, words_c = b.steps * (size_t)nL;
-            const size_t first = (size_t)rq->offsets[b0] * n_obs;
-            if (!d_rG.reserve_or_release(b.entries)) return fail(STCSP_E_NOMEM, "repair: no room for %zu bytes of tables", b.entries * sizeof(uint32_t));
-            if (!d_rcost.reserve_or_release(words_c)) return fail(STCSP_E_NOMEM, "repair: no room for %zu bytes of step costs", words_c * sizeof(uint32_t));
-            HIPCHK(reserve_all(nb, 0, d_rstreams, d_rdist, d_rnchg, d_rfin));
-            HIPCHK(reserve_all(cells, 0, d_rrows, d_rout));
-            HIPCHK(hipMemcpyAsync(d_rstreams.p, meta.data(), nb * sizeof(RepStream), hipMemcpyHostToDevice, v.stream));
-            if (cells) {
-                HIPCHK(hipMemcpyAsync(d_rrows.p, rq->values + first, cells * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-                HIPCHK(hipMemsetAsync(d_rout.p, 0, cells * sizeof(int32_t), v.stream));
-            }
-            HIPCHK(hipMemsetAsync(d_rctl.p + R_ERROR, 0, sizeof(uint32_t), v.stream));
-            HIPCHK(hipEventRecord(ev[0], v.stream));
-            if (words_c)
-                hipLaunchKernelGGL(k_r_cost, dim3((nL + 255) / 256, (unsigned)std::min<size_t>(b.steps, 65535)), dim3(256), 0, v.stream, nL,
-                                   (uint32_t)b.steps, (const uint32_t *)d_rrep.p, (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p, gen_n_obs,
-                                   (const int32_t *)d_rweights.p, (const int32_t *)d_rrows.p, d_rcost.p);
-            HIPCHK(hipEventRecord(ev[1], v.stream));
-            hipLaunchKernelGGL(k_r_level0, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, (const RepStream *)d_rstreams.p, (const uint8_t *)d_live.p,
-                               (const uint8_t *)d_pfinal.p, end_final, d_rG.p);
-            for (uint32_t r = 1; r <= (uint32_t)b.longest; r++) {
-                hipLaunchKernelGGL(k_r_relax, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, r, (const RepStream *)d_rstreams.p,
-                                   (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint32_t *)d_rcost.p,
-                                   rep_wave_segment, d_rG.p);
-                if (rep_n_long)
-                    hipLaunchKernelGGL(k_r_relax_long, dim3((rep_n_long + 3) / 4, (unsigned)nb), dim3(256), 0, v.stream, rep_n_long,
-                                       (const uint32_t *)d_rlong.p, S, r, (const RepStream *)d_rstreams.p, (const uint32_t *)d_goff.p,
-                                       (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint32_t *)d_rcost.p, d_rG.p);
-            }
-            HIPCHK(hipEventRecord(ev[2], v.stream));
-            hipLaunchKernelGGL(k_r_walk, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)nb, (const RepStream *)d_rstreams.p, S,
-                               (const uint32_t *)d_rG.p, (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p,
-                               (const uint32_t *)d_geid.p, nL, (const uint32_t *)d_rcost.p, (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p,
-                               gen_n_obs, (const uint8_t *)d_pfinal.p, (const int32_t *)d_rrows.p, d_rout.p, d_rdist.p, d_rfin.p, d_rnchg.p, d_rctl.p);
-            HIPCHK(hipEventRecord(ev[3], v.stream));
-            HIPCHK(hipGetLastError());
-            uint32_t bad = 0;
-            if (cells) HIPCHK(hipMemcpyAsync(r_values.data() + first, d_rout.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
-            HIPCHK(hipMemcpyAsync(r_dist.data() + b0, d_rdist.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
-            HIPCHK(hipMemcpyAsync(r_nchg.data() + b0, d_rnchg.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
-            HIPCHK(hipMemcpyAsync(r_fin.data() + b0, d_rfin.p, nb, hipMemcpyDeviceToHost, v.stream));
-            HIPCHK(hipMemcpyAsync(&bad, d_rctl.p + R_ERROR, sizeof bad, hipMemcpyDeviceToHost, v.stream));
-            HIPCHK(hipStreamSynchronize(v.stream));
-            float ms_c = 0, ms_r = 0, ms_w = 0;
-            HIPCHK(hipEventElapsedTime(&ms_c, ev[0], ev[1]));
-            HIPCHK(hipEventElapsedTime(&ms_r, ev[1], ev[2]));
-            HIPCHK(hipEventElapsedTime(&ms_w, ev[2], ev[3]));
-            out->seconds_cost += ms_c * 1e-3;
-            out->seconds_relax += ms_r * 1e-3;
-            out->seconds_walk += ms_w * 1e-3;
-            out->n_batches++;
-            out->table_bytes = std::max<int64_t>(out->table_bytes, (int64_t)b.bytes);
-            if (bad) return fail(STCSP_E_INTERNAL, "repair: a state with a finite cost to go and no edge that attains it");
-            b0 = b.b1;
+    out->distance = rep.r_dist.data();
+    out->values = rep.r_values.data();
+    out->end_final = rep.r_fin.data();
+    out->n_changed = rep.r_nchg.data();
+    out->n_observable = gen.n_obs;
+    const uint32_t S = v.n_states;
+    const uint32_t &nL = lab.n_labels;  // a reference: stream_batches() may build the labels, need() and body() read them after that
+    const int end_final = (rq->flags & STCSP_REPAIR_END_FINAL) ? 1 : 0;
+    const unsigned sb = (S + 255) / 256;
+    auto need = [&](size_t len) { return ((len + 1) * (size_t)S + len * (size_t)nL) * sizeof(uint32_t); };
+    std::vector<int32_t> w(n_obs, 1);
+    if (rq->weights) w.assign(rq->weights, rq->weights + n_obs);
+    auto body = [&](const Batch &b, size_t nb, size_t first_step, const BatchStream *streams, const int32_t *rows) -> int {
+        const size_t b0 = b.b0, cells = b.steps * n_obs, words_c = b.steps * (size_t)nL, first = first_step * n_obs;
+        const SweepCsr csr = sweep_csr();
+        const LabelRows L = label_rows();
+        if (int rc = reserve_tables("repair", b.bytes, rep.d_rG, b.entries, rep.d_rcost, words_c)) return rc;
+        HIPCHK(reserve_all(nb, 0, rep.d_rdist, rep.d_rnchg, rep.d_rfin));
+        HIPCHK(rep.d_rout.reserve(cells));
+        if (!b0) {
+            HIPCHK(rep.d_rweights.reserve_exact(n_obs));
+            if (n_obs) HIPCHK(hipMemcpyAsync(rep.d_rweights.p, w.data(), n_obs * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
         }
-        out->n_labels = nL;
-    }
+        if (cells) HIPCHK(hipMemsetAsync(rep.d_rout.p, 0, cells * sizeof(int32_t), v.stream));
+        HIPCHK(hipMemsetAsync(lab.d_rctl.p + R_ERROR, 0, sizeof(uint32_t), v.stream));
+        HIPCHK(ev.mark(0, v.stream));
+        if (words_c)
+            hipLaunchKernelGGL(k_r_cost, dim3((nL + 255) / 256, (unsigned)std::min<size_t>(b.steps, 65535)), dim3(256), 0, v.stream, nL,
+                               (uint32_t)b.steps, L.rep, L.values, L.N, L.obs, L.n_obs, (const int32_t *)rep.d_rweights.p, rows, rep.d_rcost.p);
+        HIPCHK(ev.mark(1, v.stream));
+        hipLaunchKernelGGL(k_r_level0, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, streams, (const uint8_t *)post.d_live.p,
+                           (const uint8_t *)post.d_pfinal.p, end_final, rep.d_rG.p);
+        for (uint32_t r = 1; r <= (uint32_t)b.longest; r++) {
+            hipLaunchKernelGGL(k_r_relax, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, r, streams, csr.off, csr.lid, csr.dstp, nL,
+                               (const uint32_t *)rep.d_rcost.p, lab.wave_segment, rep.d_rG.p);
+            if (lab.n_long)
+                hipLaunchKernelGGL(k_r_relax_long, dim3((lab.n_long + 3) / 4, (unsigned)nb), dim3(256), 0, v.stream, lab.n_long,
+                                   (const uint32_t *)lab.d_rlong.p, S, r, streams, csr.off, csr.lid, csr.dstp, nL, (const uint32_t *)rep.d_rcost.p,
+                                   rep.d_rG.p);
+        }
+        HIPCHK(ev.mark(2, v.stream));
+        hipLaunchKernelGGL(k_r_walk, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)nb, streams, S, (const uint32_t *)rep.d_rG.p,
+                           csr.off, csr.lid, csr.dstp, csr.eid, nL, (const uint32_t *)rep.d_rcost.p, L.values, L.N, L.obs, L.n_obs,
+                           (const uint8_t *)post.d_pfinal.p, rows, rep.d_rout.p, rep.d_rdist.p, rep.d_rfin.p, rep.d_rnchg.p, lab.d_rctl.p);
+        HIPCHK(ev.mark(3, v.stream));
+        HIPCHK(hipGetLastError());
+        uint32_t bad = 0;
+        if (cells) HIPCHK(hipMemcpyAsync(rep.r_values.data() + first, rep.d_rout.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(rep.r_dist.data() + b0, rep.d_rdist.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(rep.r_nchg.data() + b0, rep.d_rnchg.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(rep.r_fin.data() + b0, rep.d_rfin.p, nb, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(&bad, lab.d_rctl.p + R_ERROR, sizeof bad, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        HIPCHK(ev.add_spans(0, {&out->seconds_cost, &out->seconds_relax, &out->seconds_walk}));
+        if (bad) return fail(STCSP_E_INTERNAL, "repair: a state with a finite cost to go and no edge that attains it");
+        return STCSP_OK;
+    };
+    if (int rc = stream_batches("repair", "STCSP_REPAIR_BYTES", rq->n_streams, rq->offsets, rq->values, false, need, out, body)) return rc;
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;
 }
@@ -750,38 +764,43 @@ int AutomatonServices::repair(const AutomatonView &view, const stcsp_repair_requ
 // Stream inference, the value dictionaries (dev_infer.hpp): built on the first infer() after a generator_build(), over
 // the label representatives of repair_labels(). Sized by what the labels carry, not by the variables' bounds.
 int AutomatonServices::infer_dictionaries() {
-    const size_t nL = rep_n_labels, n_obs = (size_t)gen_n_obs, cells = nL * n_obs;
+    const size_t nL = lab.n_labels, n_obs = (size_t)gen.n_obs, cells = nL * n_obs;
     std::vector<int32_t> rows(cells);
     if (cells) {
-        HIPCHK(d_ilabrows.reserve(cells));
-        hipLaunchKernelGGL(k_i_rows, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)nL, (const uint32_t *)d_rrep.p,
-                           (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p, gen_n_obs, d_ilabrows.p);
+        HIPCHK(dict.d_ilabrows.reserve(cells));
+        const LabelRows L = label_rows();
+        hipLaunchKernelGGL(k_i_rows, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)nL, L.rep, L.values, L.N, L.obs, L.n_obs,
+                           dict.d_ilabrows.p);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(rows.data(), d_ilabrows.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(rows.data(), dict.d_ilabrows.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
         HIPCHK(hipStreamSynchronize(v.stream));
     }
-    inf_dict.assign(n_obs, std::vector<int32_t>());
-    inf_word_off.assign(n_obs, 0);
+    dict.values.assign(n_obs, std::vector<int32_t>());
+    dict.word_off.assign(n_obs, 0);
+    dict.bin_off.assign(n_obs, 0);
     std::vector<uint32_t> vidx(cells);
     size_t words = 0;
+    dict.n_values = 0;
     for (size_t x = 0; x < n_obs; x++) {
-        std::vector<int32_t> &d = inf_dict[x];
+        std::vector<int32_t> &d = dict.values[x];
         d.resize(nL);
         for (size_t l = 0; l < nL; l++) d[l] = rows[l * n_obs + x];
         std::sort(d.begin(), d.end());
         d.erase(std::unique(d.begin(), d.end()), d.end());
         for (size_t l = 0; l < nL; l++) vidx[l * n_obs + x] = (uint32_t)(std::lower_bound(d.begin(), d.end(), rows[l * n_obs + x]) - d.begin());
-        inf_word_off[x] = (uint32_t)words;
+        dict.word_off[x] = (uint32_t)words;
         words += (d.size() + 31) / 32;
+        dict.bin_off[x] = (uint32_t)dict.n_values;
+        dict.n_values += d.size();
     }
     if (words > 0x7fffffffull) return fail(STCSP_E_NOMEM, "infer: the support bitmaps of one step are too large");
-    inf_words = (uint32_t)words;
-    HIPCHK(d_ividx.reserve(cells));
-    if (d_iwoff.n < n_obs) HIPCHK(d_iwoff.alloc(n_obs + 16));
-    if (cells) HIPCHK(hipMemcpyAsync(d_ividx.p, vidx.data(), cells * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
-    if (n_obs) HIPCHK(hipMemcpyAsync(d_iwoff.p, inf_word_off.data(), n_obs * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+    dict.words = (uint32_t)words;
+    HIPCHK(dict.d_ividx.reserve(cells));
+    HIPCHK(dict.d_iwoff.reserve_exact(n_obs));
+    if (cells) HIPCHK(hipMemcpyAsync(dict.d_ividx.p, vidx.data(), cells * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+    if (n_obs) HIPCHK(hipMemcpyAsync(dict.d_iwoff.p, dict.word_off.data(), n_obs * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
     HIPCHK(hipStreamSynchronize(v.stream));  // (vidx is a local)
-    inf_built = true;
+    dict.built = true;
     return STCSP_OK;
 }
 
@@ -790,164 +809,131 @@ int AutomatonServices::infer(const AutomatonView &view, const stcsp_infer_reques
     if (int rc = enter(view, "infer", NEED_GENERATOR, "stcsp_automaton_infer_streams")) return rc;
     if (!infer_request_ok(rq->n_streams, rq->offsets, rq->draws)) return fail(STCSP_E_INVALID, "infer: malformed stream offsets or a negative number of draws");
     auto t0 = std::chrono::steady_clock::now();
-    const size_t n = (size_t)rq->n_streams, n_obs = (size_t)gen_n_obs, draws = (size_t)rq->draws;
+    const size_t n = (size_t)rq->n_streams, n_obs = (size_t)gen.n_obs, draws = (size_t)rq->draws;
     const size_t steps = n ? (size_t)rq->offsets[n] : 0;
     if (steps && n_obs && !rq->values) return fail(STCSP_E_INVALID, "infer: no step values");
-    i_count.assign(n, 0.0);
-    i_feas.assign(n, 0);
-    i_soff.assign(steps * n_obs + 1, 0);
-    i_sval.clear();
-    i_nstates.assign(steps + n, 0);
-    i_values.assign(steps * draws * n_obs, STCSP_INFER_MISSING);
-    i_fin.assign(n * draws, 0);
+    inf.i_count.assign(n, 0.0);
+    inf.i_feas.assign(n, 0);
+    inf.i_soff.assign(steps * n_obs + 1, 0);
+    inf.i_sval.clear();
+    inf.i_nstates.assign(steps + n, 0);
+    inf.i_values.assign(steps * draws * n_obs, STCSP_INFER_MISSING);
+    inf.i_fin.assign(n * draws, 0);
     memset(out, 0, sizeof *out);
     out->n_streams = rq->n_streams;
-    out->n_observable = gen_n_obs;
+    out->n_observable = gen.n_obs;
     out->draws = rq->draws;
     auto publish = [&]() {  // (the vectors may have grown)
-        out->count = i_count.data();
-        out->feasible = i_feas.data();
-        out->support_off = i_soff.data();
-        out->support_val = i_sval.data();
-        out->n_states = i_nstates.data();
-        out->values = i_values.data();
-        out->end_final = i_fin.data();
+        out->count = inf.i_count.data();
+        out->feasible = inf.i_feas.data();
+        out->support_off = inf.i_soff.data();
+        out->support_val = inf.i_sval.data();
+        out->n_states = inf.i_nstates.data();
+        out->values = inf.i_values.data();
+        out->end_final = inf.i_fin.data();
     };
     publish();
-    if (n && root_live) {
-        if (int rc = rep_built ? STCSP_OK : repair_labels()) return rc;
-        if (int rc = inf_built ? STCSP_OK : infer_dictionaries()) return rc;
-        const uint32_t S = v.n_states, nL = rep_n_labels, W = inf_words;
-        const int end_final = (rq->flags & STCSP_INFER_END_FINAL) ? 1 : 0;
-        size_t budget = 0;
-        if (int rc = table_budget("STCSP_INFER_BYTES", budget)) return rc;
-        auto need = [&](size_t len) { return (len + 1) * (size_t)S * (sizeof(double) + 1) + len * ((size_t)nL * 2 + (size_t)W * sizeof(uint32_t)); };
-        HIPCHK(d_ictl.reserve_exact(I_WORDS));
-        HIPCHK(ev.ready(7));
-        std::vector<InfStream> meta;
-        const unsigned sb = (S + 255) / 256;
-        for (size_t b0 = 0; b0 < n;) {
-            Batch b;  // consecutive streams while their structures fit the budget
-            if (int rc = plan_batch("infer", rq->offsets, n, b0, budget, need, meta, b)) return rc;
-            const size_t nb = b.b1 - b0, cells = b.steps * n_obs, marks = b.steps * (size_t)nL, words = b.steps * (size_t)W;
-            const size_t n_q = nb * draws, out_cells = cells * draws;
-            const size_t first_step = (size_t)rq->offsets[b0], first = first_step * n_obs;
-            if (n_q >= 0x7fffffffull) return fail(STCSP_E_NOMEM, "infer: too many draws for one batch");
-            if (!(d_iB.reserve_or_release(b.entries) && d_iF.reserve_or_release(b.entries) && d_imatch.reserve_or_release(marks) &&
-                  d_ifeas.reserve_or_release(marks) && d_ibits.reserve_or_release(words))) {
-                d_iB.release();
-                d_iF.release();
-                d_imatch.release();
-                d_ifeas.release();
-                d_ibits.release();
-                return fail(STCSP_E_NOMEM, "infer: no room for %zu bytes of tables", b.bytes);
-            }
-            HIPCHK(reserve_all(nb, 0, d_istreams, d_icount));
-            HIPCHK(d_irows.reserve(cells));
-            HIPCHK(d_instates.reserve(b.steps + nb));
-            if (n_q) {
-                HIPCHK(d_ifin.reserve(n_q));
-                if (rq->ranks) HIPCHK(d_iranks.reserve(n_q));
-                HIPCHK(d_iout.reserve(out_cells));
-            }
-            HIPCHK(hipMemcpyAsync(d_istreams.p, meta.data(), nb * sizeof(InfStream), hipMemcpyHostToDevice, v.stream));
-            if (cells) HIPCHK(hipMemcpyAsync(d_irows.p, rq->values + first, cells * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-            HIPCHK(hipMemsetAsync(d_iF.p, 0, b.entries, v.stream));
-            if (marks) HIPCHK(hipMemsetAsync(d_ifeas.p, 0, marks, v.stream));
-            if (words) HIPCHK(hipMemsetAsync(d_ibits.p, 0, words * sizeof(uint32_t), v.stream));
-            HIPCHK(hipMemsetAsync(d_instates.p, 0, (b.steps + nb) * sizeof(int32_t), v.stream));
-            HIPCHK(hipMemsetAsync(d_ictl.p, 0, I_WORDS * sizeof(uint32_t), v.stream));
-            const unsigned step_rows = (unsigned)std::min<size_t>(std::max<size_t>(b.steps, 1), 65535);
-            HIPCHK(hipEventRecord(ev[0], v.stream));
-            if (marks)
-                hipLaunchKernelGGL(k_i_match, dim3((nL + 255) / 256, step_rows), dim3(256), 0, v.stream, nL, (uint32_t)b.steps, (const uint32_t *)d_rrep.p,
-                                   (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p, gen_n_obs, (const int32_t *)d_irows.p, d_imatch.p);
-            HIPCHK(hipEventRecord(ev[1], v.stream));
-            hipLaunchKernelGGL(k_i_level0, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, (const InfStream *)d_istreams.p, (const uint8_t *)d_live.p,
-                               (const uint8_t *)d_pfinal.p, end_final, d_iB.p);
-            for (uint32_t r = 1; r <= (uint32_t)b.longest; r++)
-                hipLaunchKernelGGL(k_i_backward, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, r, (const InfStream *)d_istreams.p,
-                                   (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_imatch.p,
-                                   d_iB.p);
-            hipLaunchKernelGGL(k_i_root, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)nb, (const InfStream *)d_istreams.p, S,
-                               (const double *)d_iB.p, d_iF.p, d_icount.p);
-            HIPCHK(hipEventRecord(ev[2], v.stream));
-            for (uint32_t t = 0; t < (uint32_t)b.longest; t++) {
-                hipLaunchKernelGGL(k_i_forward, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, t, (const InfStream *)d_istreams.p,
-                                   (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_imatch.p,
-                                   (const double *)d_iB.p, rep_wave_segment, d_iF.p, d_ifeas.p);
-                if (rep_n_long)
-                    hipLaunchKernelGGL(k_i_forward_long, dim3((rep_n_long + 3) / 4, (unsigned)nb), dim3(256), 0, v.stream, rep_n_long,
-                                       (const uint32_t *)d_rlong.p, S, t, (const InfStream *)d_istreams.p, (const uint32_t *)d_goff.p,
-                                       (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_imatch.p, (const double *)d_iB.p,
-                                       d_iF.p, d_ifeas.p);
-            }
-            hipLaunchKernelGGL(k_i_count, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, (const InfStream *)d_istreams.p, (const uint8_t *)d_iF.p,
-                               d_instates.p);
-            HIPCHK(hipEventRecord(ev[3], v.stream));
-            if (marks && W)
-                hipLaunchKernelGGL(k_i_support, dim3((nL + 255) / 256, step_rows), dim3(256), 0, v.stream, nL, (uint32_t)b.steps, (const uint8_t *)d_ifeas.p,
-                                   (const uint32_t *)d_ividx.p, (const uint32_t *)d_iwoff.p, gen_n_obs, W, d_ibits.p);
-            HIPCHK(hipEventRecord(ev[4], v.stream));
-            HIPCHK(hipGetLastError());
-            i_bits.resize(words);
-            HIPCHK(hipMemcpyAsync(i_count.data() + b0, d_icount.p, nb * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-            HIPCHK(hipMemcpyAsync(i_nstates.data() + first_step + b0, d_instates.p, (b.steps + nb) * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
-            if (words) HIPCHK(hipMemcpyAsync(i_bits.data(), d_ibits.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
-            HIPCHK(hipStreamSynchronize(v.stream));
-            // the bitmaps -> sorted lists: bit order is value order
-            for (size_t step = 0; step < b.steps; step++)
-                for (size_t x = 0; x < n_obs; x++) {
-                    const uint32_t *w = i_bits.data() + step * W + inf_word_off[x];
-                    const std::vector<int32_t> &d = inf_dict[x];
-                    for (size_t k = 0; k < d.size(); k++)
-                        if (w[k >> 5] >> (k & 31) & 1u) i_sval.push_back(d[k]);
-                    i_soff[(first_step + step) * n_obs + x + 1] = (int64_t)i_sval.size();
-                }
-            for (size_t i = b0; i < b.b1; i++) i_feas[i] = i_count[i] > 0.0;
-            publish();
-            float ms[5] = {0, 0, 0, 0, 0};
-            if (n_q) {
-                // the draws: the counts decide whether they can be asked for
-                for (size_t i = b0; i < b.b1; i++) {
-                    const int bad = infer_draws_ok(i_count[i], rq->draws, rq->ranks ? rq->ranks + i * draws : nullptr);
-                    if (bad == 1) return fail(STCSP_E_UNSUPPORTED, "infer: draws from stream %zu, whose count overflows a double", i);
-                    if (bad) return fail(STCSP_E_INVALID, "infer: stream %zu: a rank that is not below its count < 2^53", i);
-                }
-                if (rq->ranks) HIPCHK(hipMemcpyAsync(d_iranks.p, rq->ranks + b0 * draws, n_q * sizeof(uint64_t), hipMemcpyHostToDevice, v.stream));
-                if (out_cells) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d_iout.p, STCSP_INFER_MISSING, out_cells, v.stream));
-                HIPCHK(hipMemsetAsync(d_ifin.p, 0, n_q, v.stream));
-                const dim3 grid((unsigned)((n_q + 255) / 256)), block(256);
-                HIPCHK(hipEventRecord(ev[5], v.stream));
-                hipLaunchKernelGGL(rq->ranks ? k_i_walk<true> : k_i_walk<false>, grid, block, 0, v.stream, (uint32_t)n_q, (uint32_t)draws,
-                                   (unsigned long long)(b0 * draws), rq->ranks ? 0ull : (unsigned long long)rq->seed,
-                                   rq->ranks ? (const unsigned long long *)d_iranks.p : nullptr, (const InfStream *)d_istreams.p, S, (const double *)d_iB.p,
-                                   (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, (const uint32_t *)d_geid.p, nL,
-                                   (const uint8_t *)d_imatch.p, (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p, gen_n_obs,
-                                   (const uint8_t *)d_pfinal.p, d_iout.p, d_ifin.p, d_ictl.p);
-                HIPCHK(hipEventRecord(ev[6], v.stream));
-                HIPCHK(hipGetLastError());
-                uint32_t bad = 0;
-                if (out_cells) HIPCHK(hipMemcpyAsync(i_values.data() + first * draws, d_iout.p, out_cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
-                HIPCHK(hipMemcpyAsync(i_fin.data() + b0 * draws, d_ifin.p, n_q, hipMemcpyDeviceToHost, v.stream));
-                HIPCHK(hipMemcpyAsync(&bad, d_ictl.p + I_ERROR, sizeof bad, hipMemcpyDeviceToHost, v.stream));
-                HIPCHK(hipStreamSynchronize(v.stream));
-                HIPCHK(hipEventElapsedTime(&ms[4], ev[5], ev[6]));
-                if (bad) return fail(STCSP_E_INTERNAL, "infer: a state with weight to go and no matching edge of non-zero weight");
-            }
-            for (int k = 0; k < 4; k++) HIPCHK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-            out->seconds_match += ms[0] * 1e-3;
-            out->seconds_backward += ms[1] * 1e-3;
-            out->seconds_forward += ms[2] * 1e-3;
-            out->seconds_support += ms[3] * 1e-3;
-            out->seconds_walk += ms[4] * 1e-3;
-            out->n_batches++;
-            out->table_bytes = std::max<int64_t>(out->table_bytes, (int64_t)b.bytes);
-            b0 = b.b1;
+    const uint32_t S = v.n_states;
+    const uint32_t &nL = lab.n_labels, &W = dict.words;  // references: stream_batches() may build both, need() and body() read them after that
+    const int end_final = (rq->flags & STCSP_INFER_END_FINAL) ? 1 : 0;
+    const unsigned sb = (S + 255) / 256;
+    auto need = [&](size_t len) { return (len + 1) * (size_t)S * (sizeof(double) + 1) + len * ((size_t)nL * 2 + (size_t)W * sizeof(uint32_t)); };
+    auto body = [&](const Batch &b, size_t nb, size_t first_step, const BatchStream *streams, const int32_t *rows) -> int {
+        const size_t b0 = b.b0, cells = b.steps * n_obs, marks = b.steps * (size_t)nL, words = b.steps * (size_t)W;
+        const size_t n_q = nb * draws, out_cells = cells * draws, first = first_step * n_obs;
+        const SweepCsr csr = sweep_csr();
+        const LabelRows L = label_rows();
+        if (n_q >= 0x7fffffffull) return fail(STCSP_E_NOMEM, "infer: too many draws for one batch");
+        if (int rc = reserve_tables("infer", b.bytes, inf.d_iB, b.entries, inf.d_iF, b.entries, inf.d_imatch, marks, inf.d_ifeas, marks, inf.d_ibits, words)) return rc;
+        HIPCHK(inf.d_icount.reserve(nb));
+        HIPCHK(inf.d_instates.reserve(b.steps + nb));
+        HIPCHK(inf.d_ictl.reserve_exact(I_WORDS));
+        if (n_q) {
+            HIPCHK(inf.d_ifin.reserve(n_q));
+            if (rq->ranks) HIPCHK(inf.d_iranks.reserve(n_q));
+            HIPCHK(inf.d_iout.reserve(out_cells));
         }
-        out->n_labels = nL;
-    }
-    if (i_sval.empty()) i_sval.reserve(1);
+        HIPCHK(hipMemsetAsync(inf.d_iF.p, 0, b.entries, v.stream));
+        if (marks) HIPCHK(hipMemsetAsync(inf.d_ifeas.p, 0, marks, v.stream));
+        if (words) HIPCHK(hipMemsetAsync(inf.d_ibits.p, 0, words * sizeof(uint32_t), v.stream));
+        HIPCHK(hipMemsetAsync(inf.d_instates.p, 0, (b.steps + nb) * sizeof(int32_t), v.stream));
+        HIPCHK(hipMemsetAsync(inf.d_ictl.p, 0, I_WORDS * sizeof(uint32_t), v.stream));
+        const unsigned step_rows = (unsigned)std::min<size_t>(std::max<size_t>(b.steps, 1), 65535);
+        HIPCHK(ev.mark(0, v.stream));
+        if (marks)
+            hipLaunchKernelGGL(k_i_match, dim3((nL + 255) / 256, step_rows), dim3(256), 0, v.stream, nL, (uint32_t)b.steps, L.rep, L.values, L.N, L.obs,
+                               L.n_obs, rows, inf.d_imatch.p);
+        HIPCHK(ev.mark(1, v.stream));
+        hipLaunchKernelGGL(k_i_level0, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, streams, (const uint8_t *)post.d_live.p, (const uint8_t *)post.d_pfinal.p,
+                           end_final, inf.d_iB.p);
+        for (uint32_t r = 1; r <= (uint32_t)b.longest; r++)
+            hipLaunchKernelGGL(k_i_backward<false>, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, r, streams, csr.off, csr.lid, csr.dstp, nL,
+                               (const uint8_t *)inf.d_imatch.p, inf.d_iB.p);
+        hipLaunchKernelGGL(k_i_root, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)nb, streams, S, (const double *)inf.d_iB.p, inf.d_iF.p,
+                           inf.d_icount.p);
+        HIPCHK(ev.mark(2, v.stream));
+        for (uint32_t t = 0; t < (uint32_t)b.longest; t++) {
+            hipLaunchKernelGGL(k_i_forward, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, t, streams, csr.off, csr.lid, csr.dstp, nL,
+                               (const uint8_t *)inf.d_imatch.p, (const double *)inf.d_iB.p, lab.wave_segment, inf.d_iF.p, inf.d_ifeas.p);
+            if (lab.n_long)
+                hipLaunchKernelGGL(k_i_forward_long, dim3((lab.n_long + 3) / 4, (unsigned)nb), dim3(256), 0, v.stream, lab.n_long,
+                                   (const uint32_t *)lab.d_rlong.p, S, t, streams, csr.off, csr.lid, csr.dstp, nL, (const uint8_t *)inf.d_imatch.p,
+                                   (const double *)inf.d_iB.p, inf.d_iF.p, inf.d_ifeas.p);
+        }
+        hipLaunchKernelGGL(k_i_count, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, streams, (const uint8_t *)inf.d_iF.p, inf.d_instates.p);
+        HIPCHK(ev.mark(3, v.stream));
+        if (marks && W)
+            hipLaunchKernelGGL(k_i_support, dim3((nL + 255) / 256, step_rows), dim3(256), 0, v.stream, nL, (uint32_t)b.steps, (const uint8_t *)inf.d_ifeas.p,
+                               (const uint32_t *)dict.d_ividx.p, (const uint32_t *)dict.d_iwoff.p, gen.n_obs, W, inf.d_ibits.p);
+        HIPCHK(ev.mark(4, v.stream));
+        HIPCHK(hipGetLastError());
+        inf.i_bits.resize(words);
+        HIPCHK(hipMemcpyAsync(inf.i_count.data() + b0, inf.d_icount.p, nb * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(inf.i_nstates.data() + first_step + b0, inf.d_instates.p, (b.steps + nb) * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        if (words) HIPCHK(hipMemcpyAsync(inf.i_bits.data(), inf.d_ibits.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        HIPCHK(ev.add_spans(0, {&out->seconds_match, &out->seconds_backward, &out->seconds_forward, &out->seconds_support}));
+        // the bitmaps -> sorted lists: bit order is value order
+        for (size_t step = 0; step < b.steps; step++)
+            for (size_t x = 0; x < n_obs; x++) {
+                const uint32_t *w = inf.i_bits.data() + step * W + dict.word_off[x];
+                const std::vector<int32_t> &d = dict.values[x];
+                for (size_t k = 0; k < d.size(); k++)
+                    if (w[k >> 5] >> (k & 31) & 1u) inf.i_sval.push_back(d[k]);
+                inf.i_soff[(first_step + step) * n_obs + x + 1] = (int64_t)inf.i_sval.size();
+            }
+        for (size_t i = b0; i < b.b1; i++) inf.i_feas[i] = inf.i_count[i] > 0.0;
+        publish();
+        if (!n_q) return STCSP_OK;
+        // the draws: the counts decide whether they can be asked for
+        for (size_t i = b0; i < b.b1; i++) {
+            const int bad = infer_draws_ok(inf.i_count[i], rq->draws, rq->ranks ? rq->ranks + i * draws : nullptr);
+            if (bad == 1) return fail(STCSP_E_UNSUPPORTED, "infer: draws from stream %zu, whose count overflows a double", i);
+            if (bad) return fail(STCSP_E_INVALID, "infer: stream %zu: a rank that is not below its count < 2^53", i);
+        }
+        if (rq->ranks) HIPCHK(hipMemcpyAsync(inf.d_iranks.p, rq->ranks + b0 * draws, n_q * sizeof(uint64_t), hipMemcpyHostToDevice, v.stream));
+        if (out_cells) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)inf.d_iout.p, STCSP_INFER_MISSING, out_cells, v.stream));
+        HIPCHK(hipMemsetAsync(inf.d_ifin.p, 0, n_q, v.stream));
+        const dim3 grid((unsigned)((n_q + 255) / 256)), block(256);
+        HIPCHK(ev.mark(5, v.stream));
+        hipLaunchKernelGGL(rq->ranks ? k_i_walk<true> : k_i_walk<false>, grid, block, 0, v.stream, (uint32_t)n_q, (uint32_t)draws,
+                           (unsigned long long)(b0 * draws), rq->ranks ? 0ull : (unsigned long long)rq->seed,
+                           rq->ranks ? (const unsigned long long *)inf.d_iranks.p : nullptr, streams, S, (const double *)inf.d_iB.p, csr.off, csr.lid,
+                           csr.dstp, csr.eid, nL, (const uint8_t *)inf.d_imatch.p, L.values, L.N, L.obs, L.n_obs, (const uint8_t *)post.d_pfinal.p,
+                           inf.d_iout.p, inf.d_ifin.p, inf.d_ictl.p);
+        HIPCHK(ev.mark(6, v.stream));
+        HIPCHK(hipGetLastError());
+        uint32_t bad = 0;
+        if (out_cells) HIPCHK(hipMemcpyAsync(inf.i_values.data() + first * draws, inf.d_iout.p, out_cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(inf.i_fin.data() + b0 * draws, inf.d_ifin.p, n_q, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(&bad, inf.d_ictl.p + I_ERROR, sizeof bad, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        HIPCHK(ev.add_spans(5, {&out->seconds_walk}));
+        if (bad) return fail(STCSP_E_INTERNAL, "infer: a state with weight to go and no matching edge of non-zero weight");
+        return STCSP_OK;
+    };
+    if (int rc = stream_batches("infer", "STCSP_INFER_BYTES", rq->n_streams, rq->offsets, rq->values, true, need, out, body)) return rc;
+    if (inf.i_sval.empty()) inf.i_sval.reserve(1);
     publish();
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;
@@ -956,155 +942,125 @@ int AutomatonServices::infer(const AutomatonView &view, const stcsp_infer_reques
 // Posterior marginals of partially observed streams under value weights (contract: stcsp_engine.h).
 int AutomatonServices::posterior(const AutomatonView &view, const stcsp_posterior_request *rq, stcsp_posterior_result *out) {
     if (int rc = enter(view, "posterior", NEED_GENERATOR, "stcsp_automaton_posterior_streams")) return rc;
-    if (!posterior_request_ok(rq->n_streams, rq->offsets, gen_n_obs, rq->weight_off, rq->weight_val, rq->weight_w))
+    if (!posterior_request_ok(rq->n_streams, rq->offsets, gen.n_obs, rq->weight_off, rq->weight_val, rq->weight_w))
         return fail(STCSP_E_INVALID, "posterior: malformed stream offsets, or weights that are not a CSR of strictly increasing values and weights >= 0");
     auto t0 = std::chrono::steady_clock::now();
-    const size_t n = (size_t)rq->n_streams, n_obs = (size_t)gen_n_obs;
+    const size_t n = (size_t)rq->n_streams, n_obs = (size_t)gen.n_obs;
     const size_t steps = n ? (size_t)rq->offsets[n] : 0;
     if (steps && n_obs && !rq->values) return fail(STCSP_E_INVALID, "posterior: no step values");
-    y_mass.assign(n, 0.0);
-    y_exact.assign(n, 1);
-    y_feas.assign(n, 0);
-    y_fmass.assign(n, 0);
-    y_moff.assign(steps * n_obs + 1, 0);
-    y_mval.clear();
-    y_mmass.clear();
+    pos.y_mass.assign(n, 0.0);
+    pos.y_exact.assign(n, 1);
+    pos.y_feas.assign(n, 0);
+    pos.y_fmass.assign(n, 0);
+    pos.y_moff.assign(steps * n_obs + 1, 0);
+    pos.y_mval.clear();
+    pos.y_mmass.clear();
     memset(out, 0, sizeof *out);
     out->n_streams = rq->n_streams;
-    out->n_observable = gen_n_obs;
-    if (n && root_live) {
-        if (int rc = rep_built ? STCSP_OK : repair_labels()) return rc;
-        if (int rc = inf_built ? STCSP_OK : infer_dictionaries()) return rc;
-        const uint32_t S = v.n_states, nL = rep_n_labels;
-        const int end_final = (rq->flags & STCSP_POSTERIOR_END_FINAL) ? 1 : 0;
-        // one bin per (variable, dictionary value), and the weight of each
-        std::vector<uint32_t> bin_off(n_obs, 0);
-        std::vector<double> wbin;
-        for (size_t x = 0; x < n_obs; x++) {
-            bin_off[x] = (uint32_t)wbin.size();
-            for (int32_t value : inf_dict[x]) wbin.push_back(posterior_value_weight((int)x, value, rq->weight_off, rq->weight_val, rq->weight_w));
-            if (wbin.size() > 0x7fffffffull) return fail(STCSP_E_NOMEM, "posterior: the bins of one step are too many");
-        }
-        const uint32_t nB = (uint32_t)wbin.size();
-        size_t budget = 0;
-        if (int rc = table_budget("STCSP_POSTERIOR_BYTES", budget)) return rc;
-        auto need = [&](size_t len) {
-            return (len + 1) * (size_t)S * sizeof(double) + 2 * (size_t)S * sizeof(uint64_t) + len * ((size_t)nL * (1 + sizeof(uint64_t)) + (size_t)nB * sizeof(uint64_t));
-        };
-        HIPCHK(ev.ready(7));
-        HIPCHK(d_yw.reserve(nL));
-        HIPCHK(d_ywbin.reserve(nB));
-        if (d_yboff.n < n_obs) HIPCHK(d_yboff.alloc(n_obs + 16));
-        if (nB) HIPCHK(hipMemcpyAsync(d_ywbin.p, wbin.data(), (size_t)nB * sizeof(double), hipMemcpyHostToDevice, v.stream));
-        if (n_obs) HIPCHK(hipMemcpyAsync(d_yboff.p, bin_off.data(), n_obs * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
-        HIPCHK(hipEventRecord(ev[5], v.stream));
-        if (nL)
-            hipLaunchKernelGGL(k_p_label_weight, dim3((nL + 255) / 256), dim3(256), 0, v.stream, nL, (const uint32_t *)d_ividx.p, (const uint32_t *)d_yboff.p,
-                               gen_n_obs, (const double *)d_ywbin.p, d_yw.p);
-        HIPCHK(hipEventRecord(ev[6], v.stream));
-        HIPCHK(hipGetLastError());
-        bool first_batch = true;
-        std::vector<InfStream> meta;
-        const unsigned sb = (S + 255) / 256;
-        for (size_t b0 = 0; b0 < n;) {
-            Batch b;  // consecutive streams while their structures fit the budget
-            if (int rc = plan_batch("posterior", rq->offsets, n, b0, budget, need, meta, b)) return rc;
-            const size_t nb = b.b1 - b0, cells = b.steps * n_obs, marks = b.steps * (size_t)nL, bins = b.steps * (size_t)nB, rows_a = nb * 2 * (size_t)S;
-            const size_t first_step = (size_t)rq->offsets[b0], first = first_step * n_obs;
-            if (!(d_yB.reserve_or_release(b.entries) && d_yA.reserve_or_release(rows_a) && d_ymatch.reserve_or_release(marks) &&
-                  d_ylab.reserve_or_release(marks) && d_ybins.reserve_or_release(bins))) {
-                d_yB.release();
-                d_yA.release();
-                d_ymatch.release();
-                d_ylab.release();
-                d_ybins.release();
-                return fail(STCSP_E_NOMEM, "posterior: no room for %zu bytes of tables", b.bytes);
-            }
-            HIPCHK(reserve_all(nb, 0, d_ystreams, d_ymass, d_yexact, d_yfmass));
-            HIPCHK(d_yrows.reserve(cells));
-            HIPCHK(hipMemcpyAsync(d_ystreams.p, meta.data(), nb * sizeof(InfStream), hipMemcpyHostToDevice, v.stream));
-            if (cells) HIPCHK(hipMemcpyAsync(d_yrows.p, rq->values + first, cells * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-            HIPCHK(hipMemsetAsync(d_yA.p, 0, rows_a * sizeof(uint64_t), v.stream));
-            HIPCHK(hipMemsetAsync(d_yfmass.p, 0, nb * sizeof(uint64_t), v.stream));
-            if (marks) HIPCHK(hipMemsetAsync(d_ylab.p, 0, marks * sizeof(uint64_t), v.stream));
-            if (bins) HIPCHK(hipMemsetAsync(d_ybins.p, 0, bins * sizeof(uint64_t), v.stream));
-            const unsigned step_rows = (unsigned)std::min<size_t>(std::max<size_t>(b.steps, 1), 65535);
-            HIPCHK(hipEventRecord(ev[0], v.stream));
-            if (marks)
-                hipLaunchKernelGGL(k_i_match, dim3((nL + 255) / 256, step_rows), dim3(256), 0, v.stream, nL, (uint32_t)b.steps, (const uint32_t *)d_rrep.p,
-                                   (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p, gen_n_obs, (const int32_t *)d_yrows.p, d_ymatch.p);
-            HIPCHK(hipEventRecord(ev[1], v.stream));
-            hipLaunchKernelGGL(k_p_level0, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, (const InfStream *)d_ystreams.p, (const uint8_t *)d_live.p,
-                               (const uint8_t *)d_pfinal.p, end_final, d_yB.p);
-            for (uint32_t r = 1; r <= (uint32_t)b.longest; r++)
-                hipLaunchKernelGGL(k_p_backward, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, r, (const InfStream *)d_ystreams.p,
-                                   (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_ymatch.p,
-                                   (const double *)d_yw.p, d_yB.p);
-            hipLaunchKernelGGL(k_p_root, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)nb, (const InfStream *)d_ystreams.p, S,
-                               (const double *)d_yB.p, d_yA.p, d_ymass.p, d_yexact.p);
-            HIPCHK(hipEventRecord(ev[2], v.stream));
-            for (uint32_t t = 0; t < (uint32_t)b.longest; t++) {
-                if (rep_n_long)  // before k_p_forward, which clears A_t
-                    hipLaunchKernelGGL(k_p_forward_long, dim3((rep_n_long + 3) / 4, (unsigned)nb), dim3(256), 0, v.stream, rep_n_long,
-                                       (const uint32_t *)d_rlong.p, S, t, (const InfStream *)d_ystreams.p, (const uint32_t *)d_goff.p,
-                                       (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_ymatch.p, (const double *)d_yw.p,
-                                       (const double *)d_yB.p, d_yA.p, d_ylab.p);
-                hipLaunchKernelGGL(k_p_forward, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, t, (const InfStream *)d_ystreams.p,
-                                   (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p, (const uint32_t *)d_gdst.p, nL, (const uint8_t *)d_ymatch.p,
-                                   (const double *)d_yw.p, (const double *)d_yB.p, rep_wave_segment, d_yA.p, d_ylab.p);
-            }
-            hipLaunchKernelGGL(k_p_final, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, (const InfStream *)d_ystreams.p, (const uint8_t *)d_pfinal.p,
-                               (const unsigned long long *)d_yA.p, d_yfmass.p);
-            HIPCHK(hipEventRecord(ev[3], v.stream));
-            if (marks && nB)
-                hipLaunchKernelGGL(k_p_bins, dim3((nL + 255) / 256, step_rows), dim3(256), 0, v.stream, nL, (uint32_t)b.steps,
-                                   (const unsigned long long *)d_ylab.p, (const uint32_t *)d_ividx.p, (const uint32_t *)d_yboff.p, gen_n_obs, nB, d_ybins.p);
-            HIPCHK(hipEventRecord(ev[4], v.stream));
+    out->n_observable = gen.n_obs;
+    const uint32_t S = v.n_states;
+    const uint32_t &nL = lab.n_labels;  // references: stream_batches() may build both, need() and body() read them after that
+    const size_t &nB = dict.n_values;   // one bin per (variable, dictionary value)
+    const int end_final = (rq->flags & STCSP_POSTERIOR_END_FINAL) ? 1 : 0;
+    const unsigned sb = (S + 255) / 256;
+    const std::vector<uint32_t> &bin_off = dict.bin_off;
+    std::vector<double> wbin;
+    auto need = [&](size_t len) {
+        return (len + 1) * (size_t)S * sizeof(double) + 2 * (size_t)S * sizeof(uint64_t) + len * ((size_t)nL * (1 + sizeof(uint64_t)) + (size_t)nB * sizeof(uint64_t));
+    };
+    auto body = [&](const Batch &b, size_t nb, size_t first_step, const BatchStream *streams, const int32_t *rows) -> int {
+        const size_t b0 = b.b0, marks = b.steps * (size_t)nL, bins = b.steps * (size_t)nB, rows_a = nb * 2 * (size_t)S;
+        const SweepCsr csr = sweep_csr();
+        const LabelRows L = label_rows();
+        if (!b0) {  // the weight of every bin, and of every label
+            if (nB > 0x7fffffffull) return fail(STCSP_E_NOMEM, "posterior: the bins of one step are too many");
+            for (size_t x = 0; x < n_obs; x++)
+                for (int32_t value : dict.values[x]) wbin.push_back(posterior_value_weight((int)x, value, rq->weight_off, rq->weight_val, rq->weight_w));
+            HIPCHK(pos.d_yw.reserve(nL));
+            HIPCHK(pos.d_ywbin.reserve(nB));
+            HIPCHK(pos.d_yboff.reserve_exact(n_obs));
+            if (nB) HIPCHK(hipMemcpyAsync(pos.d_ywbin.p, wbin.data(), nB * sizeof(double), hipMemcpyHostToDevice, v.stream));
+            if (n_obs) HIPCHK(hipMemcpyAsync(pos.d_yboff.p, bin_off.data(), n_obs * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+            HIPCHK(ev.mark(5, v.stream));
+            if (nL)
+                hipLaunchKernelGGL(k_p_label_weight, dim3((nL + 255) / 256), dim3(256), 0, v.stream, nL, (const uint32_t *)dict.d_ividx.p,
+                                   (const uint32_t *)pos.d_yboff.p, gen.n_obs, (const double *)pos.d_ywbin.p, pos.d_yw.p);
+            HIPCHK(ev.mark(6, v.stream));
             HIPCHK(hipGetLastError());
-            y_bins.resize(bins);
-            HIPCHK(hipMemcpyAsync(y_mass.data() + b0, d_ymass.p, nb * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-            HIPCHK(hipMemcpyAsync(y_exact.data() + b0, d_yexact.p, nb, hipMemcpyDeviceToHost, v.stream));
-            HIPCHK(hipMemcpyAsync(y_fmass.data() + b0, d_yfmass.p, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, v.stream));
-            if (bins) HIPCHK(hipMemcpyAsync(y_bins.data(), d_ybins.p, bins * sizeof(uint64_t), hipMemcpyDeviceToHost, v.stream));
-            HIPCHK(hipStreamSynchronize(v.stream));
-            // the bins -> sorted lists: dictionary order is value order
-            for (size_t step = 0; step < b.steps; step++)
-                for (size_t x = 0; x < n_obs; x++) {
-                    const unsigned long long *row = y_bins.data() + step * nB + bin_off[x];
-                    const std::vector<int32_t> &d = inf_dict[x];
-                    for (size_t k = 0; k < d.size(); k++)
-                        if (row[k]) {
-                            y_mval.push_back(d[k]);
-                            y_mmass.push_back((uint64_t)row[k]);
-                        }
-                    y_moff[(first_step + step) * n_obs + x + 1] = (int64_t)y_mval.size();
-                }
-            float ms[5] = {0, 0, 0, 0, 0};
-            for (int k = 0; k < 4; k++) HIPCHK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-            if (first_batch) HIPCHK(hipEventElapsedTime(&ms[4], ev[5], ev[6]));
-            first_batch = false;
-            out->seconds_weights += (ms[0] + ms[4]) * 1e-3;
-            out->seconds_backward += ms[1] * 1e-3;
-            out->seconds_forward += ms[2] * 1e-3;
-            out->seconds_bins += ms[3] * 1e-3;
-            out->n_batches++;
-            out->table_bytes = std::max<int64_t>(out->table_bytes, (int64_t)b.bytes);
-            b0 = b.b1;
         }
-        for (size_t i = 0; i < n; i++) y_feas[i] = y_mass[i] > 0.0;
-        out->n_labels = nL;
+        if (int rc = reserve_tables("posterior", b.bytes, pos.d_yB, b.entries, pos.d_yA, rows_a, pos.d_ymatch, marks, pos.d_ylab, marks, pos.d_ybins, bins)) return rc;
+        HIPCHK(reserve_all(nb, 0, pos.d_ymass, pos.d_yexact, pos.d_yfmass));
+        HIPCHK(hipMemsetAsync(pos.d_yA.p, 0, rows_a * sizeof(uint64_t), v.stream));
+        HIPCHK(hipMemsetAsync(pos.d_yfmass.p, 0, nb * sizeof(uint64_t), v.stream));
+        if (marks) HIPCHK(hipMemsetAsync(pos.d_ylab.p, 0, marks * sizeof(uint64_t), v.stream));
+        if (bins) HIPCHK(hipMemsetAsync(pos.d_ybins.p, 0, bins * sizeof(uint64_t), v.stream));
+        const unsigned step_rows = (unsigned)std::min<size_t>(std::max<size_t>(b.steps, 1), 65535);
+        HIPCHK(ev.mark(0, v.stream));
+        if (marks)
+            hipLaunchKernelGGL(k_i_match, dim3((nL + 255) / 256, step_rows), dim3(256), 0, v.stream, nL, (uint32_t)b.steps, L.rep, L.values, L.N, L.obs,
+                               L.n_obs, rows, pos.d_ymatch.p);
+        HIPCHK(ev.mark(1, v.stream));
+        hipLaunchKernelGGL(k_i_level0, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, streams, (const uint8_t *)post.d_live.p, (const uint8_t *)post.d_pfinal.p,
+                           end_final, pos.d_yB.p);
+        for (uint32_t r = 1; r <= (uint32_t)b.longest; r++)
+            hipLaunchKernelGGL((k_i_backward<true, const double *>), dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, r, streams, csr.off, csr.lid, csr.dstp, nL,
+                               (const uint8_t *)pos.d_ymatch.p, (const double *)pos.d_yw.p, pos.d_yB.p);
+        hipLaunchKernelGGL(k_p_root, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)nb, streams, S, (const double *)pos.d_yB.p, pos.d_yA.p,
+                           pos.d_ymass.p, pos.d_yexact.p);
+        HIPCHK(ev.mark(2, v.stream));
+        for (uint32_t t = 0; t < (uint32_t)b.longest; t++) {
+            if (lab.n_long)  // before k_p_forward, which clears A_t
+                hipLaunchKernelGGL(k_p_forward_long, dim3((lab.n_long + 3) / 4, (unsigned)nb), dim3(256), 0, v.stream, lab.n_long,
+                                   (const uint32_t *)lab.d_rlong.p, S, t, streams, csr.off, csr.lid, csr.dstp, nL, (const uint8_t *)pos.d_ymatch.p,
+                                   (const double *)pos.d_yw.p, (const double *)pos.d_yB.p, pos.d_yA.p, pos.d_ylab.p);
+            hipLaunchKernelGGL(k_p_forward, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, t, streams, csr.off, csr.lid, csr.dstp, nL,
+                               (const uint8_t *)pos.d_ymatch.p, (const double *)pos.d_yw.p, (const double *)pos.d_yB.p, lab.wave_segment, pos.d_yA.p,
+                               pos.d_ylab.p);
+        }
+        hipLaunchKernelGGL(k_p_final, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, streams, (const uint8_t *)post.d_pfinal.p,
+                           (const unsigned long long *)pos.d_yA.p, pos.d_yfmass.p);
+        HIPCHK(ev.mark(3, v.stream));
+        if (marks && nB)
+            hipLaunchKernelGGL(k_p_bins, dim3((nL + 255) / 256, step_rows), dim3(256), 0, v.stream, nL, (uint32_t)b.steps,
+                               (const unsigned long long *)pos.d_ylab.p, (const uint32_t *)dict.d_ividx.p, (const uint32_t *)pos.d_yboff.p, gen.n_obs, (uint32_t)nB, pos.d_ybins.p);
+        HIPCHK(ev.mark(4, v.stream));
+        HIPCHK(hipGetLastError());
+        pos.y_bins.resize(bins);
+        HIPCHK(hipMemcpyAsync(pos.y_mass.data() + b0, pos.d_ymass.p, nb * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(pos.y_exact.data() + b0, pos.d_yexact.p, nb, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(pos.y_fmass.data() + b0, pos.d_yfmass.p, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, v.stream));
+        if (bins) HIPCHK(hipMemcpyAsync(pos.y_bins.data(), pos.d_ybins.p, bins * sizeof(uint64_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        // seconds_weights = match + label weights, the latter once
+        HIPCHK(ev.add_spans(0, {&out->seconds_weights, &out->seconds_backward, &out->seconds_forward, &out->seconds_bins}));
+        if (!b0) HIPCHK(ev.add_spans(5, {&out->seconds_weights}));
+        // the bins -> sorted lists: dictionary order is value order
+        for (size_t step = 0; step < b.steps; step++)
+            for (size_t x = 0; x < n_obs; x++) {
+                const unsigned long long *row = pos.y_bins.data() + step * nB + bin_off[x];
+                const std::vector<int32_t> &d = dict.values[x];
+                for (size_t k = 0; k < d.size(); k++)
+                    if (row[k]) {
+                        pos.y_mval.push_back(d[k]);
+                        pos.y_mmass.push_back((uint64_t)row[k]);
+                    }
+                pos.y_moff[(first_step + step) * n_obs + x + 1] = (int64_t)pos.y_mval.size();
+            }
+        return STCSP_OK;
+    };
+    if (int rc = stream_batches("posterior", "STCSP_POSTERIOR_BYTES", rq->n_streams, rq->offsets, rq->values, true, need, out, body)) return rc;
+    for (size_t i = 0; i < n; i++) pos.y_feas[i] = pos.y_mass[i] > 0.0;
+    if (pos.y_mval.empty()) {
+        pos.y_mval.reserve(1);
+        pos.y_mmass.reserve(1);
     }
-    if (y_mval.empty()) {
-        y_mval.reserve(1);
-        y_mmass.reserve(1);
-    }
-    out->mass = y_mass.data();
-    out->exact = y_exact.data();
-    out->feasible = y_feas.data();
-    out->final_mass = y_fmass.data();
-    out->marg_off = y_moff.data();
-    out->marg_val = y_mval.data();
-    out->marg_mass = y_mmass.data();
+    out->mass = pos.y_mass.data();
+    out->exact = pos.y_exact.data();
+    out->feasible = pos.y_feas.data();
+    out->final_mass = pos.y_fmass.data();
+    out->marg_off = pos.y_moff.data();
+    out->marg_val = pos.y_mval.data();
+    out->marg_mass = pos.y_mmass.data();
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;
 }
@@ -1129,15 +1085,16 @@ int AutomatonServices::grow_keeping(DevBuf<T> &buf, size_t keep, size_t count, c
 // Observer, the ordered out-edges (dev_observer.hpp): built on the first observer() after a generator_build(), over the label
 // ids of repair_labels(). The host sorts the n_labels projected rows; their ranks are the labels of the construction.
 int AutomatonServices::observer_order(double &seconds) {
-    const uint32_t S = v.n_states, nL = rep_n_labels;
-    const size_t n_obs = (size_t)gen_n_obs, cells = (size_t)nL * n_obs;
+    const uint32_t S = v.n_states, nL = lab.n_labels;
+    const size_t n_obs = (size_t)gen.n_obs, cells = (size_t)nL * n_obs;
     std::vector<int32_t> rows(cells);
     if (cells) {
-        HIPCHK(d_ilabrows.reserve(cells));
-        hipLaunchKernelGGL(k_i_rows, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, v.stream, nL, (const uint32_t *)d_rrep.p,
-                           (const int32_t *)v.d_oval, v.N, (const int32_t *)d_gobs.p, gen_n_obs, d_ilabrows.p);
+        HIPCHK(dict.d_ilabrows.reserve(cells));
+        const LabelRows L = label_rows();
+        hipLaunchKernelGGL(k_i_rows, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, v.stream, nL, L.rep, L.values, L.N, L.obs, L.n_obs,
+                           dict.d_ilabrows.p);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(rows.data(), d_ilabrows.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(rows.data(), dict.d_ilabrows.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
         HIPCHK(hipStreamSynchronize(v.stream));
     }
     std::vector<uint32_t> order(nL), lrank(nL);
@@ -1145,78 +1102,78 @@ int AutomatonServices::observer_order(double &seconds) {
     std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
         return std::lexicographical_compare(rows.begin() + a * n_obs, rows.begin() + (a + 1) * n_obs, rows.begin() + b * n_obs, rows.begin() + (b + 1) * n_obs);
     });
-    obs_rows.resize(cells);
+    obsv.rows.resize(cells);
     for (uint32_t r = 0; r < nL; r++) {
         lrank[order[r]] = r;
-        std::copy(rows.begin() + order[r] * n_obs, rows.begin() + (order[r] + 1) * n_obs, obs_rows.begin() + r * n_obs);
+        std::copy(rows.begin() + order[r] * n_obs, rows.begin() + (order[r] + 1) * n_obs, obsv.rows.begin() + r * n_obs);
     }
-    HIPCHK(d_olrank.reserve(nL));
-    HIPCHK(d_okey.reserve(rep_total));
-    HIPCHK(d_octl.reserve_exact(O_WORDS));
+    HIPCHK(obsv.d_olrank.reserve(nL));
+    HIPCHK(obsv.d_okey.reserve(lab.total));
+    HIPCHK(obsv.d_octl.reserve_exact(O_WORDS));
     HIPCHK(ev.ready(2));
     uint32_t ctl[O_WORDS] = {0};
-    HIPCHK(hipMemsetAsync(d_octl.p, 0, sizeof ctl, v.stream));
-    if (nL) HIPCHK(hipMemcpyAsync(d_olrank.p, lrank.data(), nL * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+    HIPCHK(hipMemsetAsync(obsv.d_octl.p, 0, sizeof ctl, v.stream));
+    if (nL) HIPCHK(hipMemcpyAsync(obsv.d_olrank.p, lrank.data(), nL * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
     HIPCHK(hipEventRecord(ev[0], v.stream));
-    if (rep_total)
-        hipLaunchKernelGGL(k_o_order, dim3((S + 3) / 4), dim3(256), 0, v.stream, S, (const uint32_t *)d_goff.p, (const uint32_t *)d_rlid.p,
-                           (const uint32_t *)d_gdst.p, (const uint32_t *)d_olrank.p, d_okey.p, d_octl.p);
+    if (lab.total)
+        hipLaunchKernelGGL(k_o_order, dim3((S + 3) / 4), dim3(256), 0, v.stream, S, (const uint32_t *)gen.d_goff.p, (const uint32_t *)lab.d_rlid.p,
+                           (const uint32_t *)gen.d_gdst.p, (const uint32_t *)obsv.d_olrank.p, obsv.d_okey.p, obsv.d_octl.p);
     HIPCHK(hipEventRecord(ev[1], v.stream));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(ctl, d_octl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(ctl, obsv.d_octl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
     HIPCHK(hipStreamSynchronize(v.stream));  // (lrank is a local)
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
     seconds = ms * 1e-3;
-    obs_max_deg = ctl[O_MAXDEG];
-    obs_built = true;
+    obsv.max_deg = ctl[O_MAXDEG];
+    obsv.built = true;
     return STCSP_OK;
 }
 
 // Observer: the subset construction of the live automaton under the generator's mask (contract: stcsp_engine.h).
 int AutomatonServices::observer(const AutomatonView &view, const stcsp_observer_options *oo, stcsp_observer_result *out) {
     if (int rc = enter(view, "observer", NEED_GENERATOR, "stcsp_automaton_observer")) return rc;
-    cmp_valid = false;  // (the left operand of compare() is the observer of the last call that succeeded)
+    cmp.valid = false;  // (the left operand of compare() is the observer of the last call that succeeded)
     if (oo && oo->max_states < 0) return fail(STCSP_E_INVALID, "observer: max_states must not be negative");
     auto t0 = std::chrono::steady_clock::now();
     const unsigned long long max_states = std::min<unsigned long long>(oo && oo->max_states ? (unsigned long long)oo->max_states : 1ull << 26, 0x7ffffffeull);
-    const size_t n_obs = (size_t)gen_n_obs;
-    o_moff.assign(1, 0);
-    o_member.clear();
-    o_final.clear();
-    o_esrc.clear();
-    o_edst.clear();
-    o_evalues.clear();
+    const size_t n_obs = (size_t)gen.n_obs;
+    obsv.o_moff.assign(1, 0);
+    obsv.o_member.clear();
+    obsv.o_final.clear();
+    obsv.o_esrc.clear();
+    obsv.o_edst.clear();
+    obsv.o_evalues.clear();
     memset(out, 0, sizeof *out);
-    out->n_observable = gen_n_obs;
+    out->n_observable = gen.n_obs;
     auto publish = [&]() {  // (empty vectors still give valid pointers)
-        o_member.reserve(1);
-        o_final.reserve(1);
-        o_esrc.reserve(1);
-        o_edst.reserve(1);
-        o_evalues.reserve(1);
-        out->member_off = o_moff.data();
-        out->member = o_member.data();
-        out->state_final = o_final.data();
-        out->edge_src = o_esrc.data();
-        out->edge_dst = o_edst.data();
-        out->edge_values = o_evalues.data();
+        obsv.o_member.reserve(1);
+        obsv.o_final.reserve(1);
+        obsv.o_esrc.reserve(1);
+        obsv.o_edst.reserve(1);
+        obsv.o_evalues.reserve(1);
+        out->member_off = obsv.o_moff.data();
+        out->member = obsv.o_member.data();
+        out->state_final = obsv.o_final.data();
+        out->edge_src = obsv.o_esrc.data();
+        out->edge_dst = obsv.o_edst.data();
+        out->edge_values = obsv.o_evalues.data();
         out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     };
-    if (!root_live) {
-        cmp_left.clear();
-        cmp_left.n_obs = gen_n_obs;
-        cmp_valid = true;
-        cmp_left_on_device = false;
+    if (!post.root_live) {
+        cmp.left.clear();
+        cmp.left.n_obs = gen.n_obs;
+        cmp.valid = true;
+        cmp.left_on_device = false;
         publish();
         return STCSP_OK;
     }
-    if (int rc = rep_built ? STCSP_OK : repair_labels()) return rc;
-    if (int rc = obs_built ? STCSP_OK : observer_order(out->seconds_build)) return rc;
+    if (int rc = lab.built ? STCSP_OK : repair_labels()) return rc;
+    if (int rc = obsv.built ? STCSP_OK : observer_order(out->seconds_build)) return rc;
     size_t budget = 0;
     if (int rc = table_budget("STCSP_OBSERVER_BYTES", budget)) return rc;
     const char *force = getenv("STCSP_OBSERVER_GLOBAL_SCRATCH");
-    const uint32_t S = v.n_states, W = (S + 31) / 32, nL = rep_n_labels;
+    const uint32_t S = v.n_states, W = (S + 31) / 32, nL = lab.n_labels;
     const bool global_bits = W > kObsLdsWords || (force && atoi(force) != 0);
     auto pow2 = [](unsigned long long n) {
         unsigned long long c = 1024;
@@ -1227,18 +1184,18 @@ int AutomatonServices::observer(const AutomatonView &view, const stcsp_observer_
     // the root's set
     unsigned long long cap_s = 1024, pool_top = 1, scratch_peak = 0;
     uint32_t n_states = 1, e_total = 0;
-    HIPCHK(d_ostab.reserve_exact(cap_s));
-    HIPCHK(d_ossid.reserve_exact(cap_s));
-    HIPCHK(d_orec.reserve(1));
-    HIPCHK(d_opool.reserve(1));
+    HIPCHK(obsv.d_ostab.reserve_exact(cap_s));
+    HIPCHK(obsv.d_ossid.reserve_exact(cap_s));
+    HIPCHK(obsv.d_orec.reserve(1));
+    HIPCHK(obsv.d_opool.reserve(1));
     uint32_t ctl[O_WORDS] = {0};
-    HIPCHK(hipMemsetAsync(d_octl.p, 0, sizeof ctl, v.stream));
-    HIPCHK(hipMemsetAsync(d_ostab.p, 0xff, cap_s * sizeof(unsigned long long), v.stream));
-    hipLaunchKernelGGL(k_o_init, dim3(1), dim3(64), 0, v.stream, (const uint8_t *)d_pfinal.p, d_orec.p, d_opool.p, d_ostab.p, d_ossid.p, (uint32_t)(cap_s - 1),
-                       d_octl.p);
+    HIPCHK(hipMemsetAsync(obsv.d_octl.p, 0, sizeof ctl, v.stream));
+    HIPCHK(hipMemsetAsync(obsv.d_ostab.p, 0xff, cap_s * sizeof(unsigned long long), v.stream));
+    hipLaunchKernelGGL(k_o_init, dim3(1), dim3(64), 0, v.stream, (const uint8_t *)post.d_pfinal.p, obsv.d_orec.p, obsv.d_opool.p, obsv.d_ostab.p, obsv.d_ossid.p, (uint32_t)(cap_s - 1),
+                       obsv.d_octl.p);
     auto read_ctl = [&]() -> int {
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(ctl, d_octl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(ctl, obsv.d_octl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
         HIPCHK(hipStreamSynchronize(v.stream));
         if (ctl[O_ERROR] & (O_ERR_TABLE_FULL | O_ERR_ITEMS_FULL)) return fail(STCSP_E_INTERNAL, "observer: a device table overflowed (flags %u)", ctl[O_ERROR]);
         if (ctl[O_ERROR]) return fail(STCSP_E_INTERNAL, "observer: two distinct sets of states share a hash (collision)");
@@ -1254,9 +1211,9 @@ int AutomatonServices::observer(const AutomatonView &view, const stcsp_observer_
     };
     auto succ = [&](int mode, uint32_t n_items, uint32_t c0, uint32_t grid, uint32_t e_base) {
         auto go = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, v.stream, n_items, c0, (const unsigned long long *)d_oitems.p, d_orec.p, d_opool.p,
-                               (const uint32_t *)d_goff.p, (const unsigned long long *)d_okey.p, (const uint8_t *)d_pfinal.p, W, d_oscratch.p, d_ostab.p,
-                               d_ossid.p, (uint32_t)(cap_s - 1), d_oslot.p, e_base, d_oesrc.p, d_oelab.p, d_oedst.p, d_octl.p);
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, v.stream, n_items, c0, (const unsigned long long *)obsv.d_oitems.p, obsv.d_orec.p, obsv.d_opool.p,
+                               (const uint32_t *)gen.d_goff.p, (const unsigned long long *)obsv.d_okey.p, (const uint8_t *)post.d_pfinal.p, W, obsv.d_oscratch.p, obsv.d_ostab.p,
+                               obsv.d_ossid.p, (uint32_t)(cap_s - 1), obsv.d_oslot.p, e_base, obsv.d_oesrc.p, obsv.d_oelab.p, obsv.d_oedst.p, obsv.d_octl.p);
         };
         if (global_bits)
             mode == O_INTERN ? go(k_o_succ<true, O_INTERN>) : mode == O_WRITE ? go(k_o_succ<true, O_WRITE>) : go(k_o_succ<true, O_VERIFY>);
@@ -1273,7 +1230,7 @@ int AutomatonServices::observer(const AutomatonView &view, const stcsp_observer_
         for (uint32_t c0 = f0; c0 < f1;) {
             // the chunk: as many frontier sets as their possible items (a set has at most n_labels, a member at most max_deg) leave in the budget
             auto bound_of = [&](unsigned long long sets) {
-                return std::max<unsigned long long>(1, std::min<unsigned long long>(sets * nL, level_members * obs_max_deg));
+                return std::max<unsigned long long>(1, std::min<unsigned long long>(sets * nL, level_members * obsv.max_deg));
             };
             auto bytes_of = [&](unsigned long long items) { return pow2(2 * items) * sizeof(unsigned long long) + items * (sizeof(unsigned long long) + sizeof(uint32_t)); };
             unsigned long long chunk = f1 - c0;
@@ -1285,14 +1242,14 @@ int AutomatonServices::observer(const AutomatonView &view, const stcsp_observer_
             const uint32_t c1 = c0 + (uint32_t)chunk;
             const unsigned long long cap_i = pow2(2 * bound);
             scratch_peak = std::max(scratch_peak, bytes_of(bound));
-            if (!d_oitab.reserve_or_release(cap_i) || !d_oitems.reserve_or_release(bound))
+            if (!obsv.d_oitab.reserve_or_release(cap_i) || !obsv.d_oitems.reserve_or_release(bound))
                 return fail(STCSP_E_NOMEM, "observer: no room for %llu bytes of work items at level %d (%u states so far)", bytes_of(bound), level, n_states);
-            HIPCHK(hipMemsetAsync(d_oitab.p, 0xff, cap_i * sizeof(unsigned long long), v.stream));
-            HIPCHK(hipMemsetAsync(d_octl.p + O_ITEMS, 0, sizeof(uint32_t), v.stream));
+            HIPCHK(hipMemsetAsync(obsv.d_oitab.p, 0xff, cap_i * sizeof(unsigned long long), v.stream));
+            HIPCHK(hipMemsetAsync(obsv.d_octl.p + O_ITEMS, 0, sizeof(uint32_t), v.stream));
             HIPCHK(hipEventRecord(ev[0], v.stream));
-            hipLaunchKernelGGL(k_o_items, dim3((unsigned)std::min<unsigned long long>(chunk, 4096)), dim3(256), 0, v.stream, c0, c1, (const ObsRec *)d_orec.p,
-                               (const uint32_t *)d_opool.p, (const uint32_t *)d_goff.p, (const unsigned long long *)d_okey.p, d_oitab.p, (uint32_t)(cap_i - 1),
-                               d_oitems.p, (uint32_t)bound, d_octl.p);
+            hipLaunchKernelGGL(k_o_items, dim3((unsigned)std::min<unsigned long long>(chunk, 4096)), dim3(256), 0, v.stream, c0, c1, (const ObsRec *)obsv.d_orec.p,
+                               (const uint32_t *)obsv.d_opool.p, (const uint32_t *)gen.d_goff.p, (const unsigned long long *)obsv.d_okey.p, obsv.d_oitab.p, (uint32_t)(cap_i - 1),
+                               obsv.d_oitems.p, (uint32_t)bound, obsv.d_octl.p);
             HIPCHK(hipEventRecord(ev[1], v.stream));
             if (int rc = read_ctl()) return rc;
             if (int rc = take_commit_time()) return rc;
@@ -1308,27 +1265,27 @@ int AutomatonServices::observer(const AutomatonView &view, const stcsp_observer_
             if (cap_s < 2ull * ((unsigned long long)n_states + n_items)) {
                 const unsigned long long old = cap_s;
                 cap_s = pow2(2ull * ((unsigned long long)n_states + n_items));
-                if (cap_s > 0x80000000ull || !d_ostab2.reserve_or_release(cap_s) || !d_ossid2.reserve_or_release(cap_s))
+                if (cap_s > 0x80000000ull || !obsv.d_ostab2.reserve_or_release(cap_s) || !obsv.d_ossid2.reserve_or_release(cap_s))
                     return fail(STCSP_E_NOMEM, "observer: no room for a table of %llu slots at level %d (%u states so far)", cap_s, level, n_states);
-                HIPCHK(hipMemsetAsync(d_ostab2.p, 0xff, cap_s * sizeof(unsigned long long), v.stream));
-                hipLaunchKernelGGL(k_o_rehash, dim3((unsigned)(old / 256)), dim3(256), 0, v.stream, (uint32_t)old, (const unsigned long long *)d_ostab.p,
-                                   (const uint32_t *)d_ossid.p, d_ostab2.p, d_ossid2.p, (uint32_t)(cap_s - 1), d_octl.p);
+                HIPCHK(hipMemsetAsync(obsv.d_ostab2.p, 0xff, cap_s * sizeof(unsigned long long), v.stream));
+                hipLaunchKernelGGL(k_o_rehash, dim3((unsigned)(old / 256)), dim3(256), 0, v.stream, (uint32_t)old, (const unsigned long long *)obsv.d_ostab.p,
+                                   (const uint32_t *)obsv.d_ossid.p, obsv.d_ostab2.p, obsv.d_ossid2.p, (uint32_t)(cap_s - 1), obsv.d_octl.p);
                 HIPCHK(hipStreamSynchronize(v.stream));
-                std::swap(d_ostab.p, d_ostab2.p);
-                std::swap(d_ostab.n, d_ostab2.n);
-                std::swap(d_ossid.p, d_ossid2.p);
-                std::swap(d_ossid.n, d_ossid2.n);
+                std::swap(obsv.d_ostab.p, obsv.d_ostab2.p);
+                std::swap(obsv.d_ostab.n, obsv.d_ostab2.n);
+                std::swap(obsv.d_ossid.p, obsv.d_ossid2.p);
+                std::swap(obsv.d_ossid.n, obsv.d_ossid2.n);
             }
-            if (int rc = grow_keeping(d_orec, n_states, (size_t)n_states + n_items)) return rc;
-            if (int rc = grow_keeping(d_oesrc, e_total, (size_t)e_total + n_items)) return rc;
-            if (int rc = grow_keeping(d_oelab, e_total, (size_t)e_total + n_items)) return rc;
-            if (int rc = grow_keeping(d_oedst, e_total, (size_t)e_total + n_items)) return rc;
-            HIPCHK(d_oslot.reserve(n_items));
+            if (int rc = grow_keeping(obsv.d_orec, n_states, (size_t)n_states + n_items)) return rc;
+            if (int rc = grow_keeping(obsv.d_oesrc, e_total, (size_t)e_total + n_items)) return rc;
+            if (int rc = grow_keeping(obsv.d_oelab, e_total, (size_t)e_total + n_items)) return rc;
+            if (int rc = grow_keeping(obsv.d_oedst, e_total, (size_t)e_total + n_items)) return rc;
+            HIPCHK(obsv.d_oslot.reserve(n_items));
             uint32_t grid = std::min<uint32_t>(n_items, 2048);
             if (global_bits) {  // a slice of W words per workgroup
                 grid = (uint32_t)std::max<unsigned long long>(1, std::min<unsigned long long>(std::min<uint32_t>(n_items, 1024), budget / ((size_t)W * sizeof(uint32_t))));
                 scratch_peak = std::max(scratch_peak, bytes_of(bound) + (unsigned long long)grid * W * sizeof(uint32_t));
-                if (!d_oscratch.reserve_or_release((size_t)grid * W))
+                if (!obsv.d_oscratch.reserve_or_release((size_t)grid * W))
                     return fail(STCSP_E_NOMEM, "observer: no room for %zu bytes of bitsets at level %d (%u states so far)", (size_t)grid * W * sizeof(uint32_t), level, n_states);
             }
             HIPCHK(hipEventRecord(ev[2], v.stream));
@@ -1345,7 +1302,7 @@ int AutomatonServices::observer(const AutomatonView &view, const stcsp_observer_
             if (pool_now * sizeof(uint32_t) > budget)
                 return fail(STCSP_E_NOMEM, "observer: the member lists need more than the budget of %zu bytes (STCSP_OBSERVER_BYTES); the construction got to level %d with %u states, %llu members and %u edges",
                             budget, level, n_states, pool_top, e_total);
-            if (int rc = grow_keeping(d_opool, (size_t)pool_top, (size_t)pool_now)) return rc;
+            if (int rc = grow_keeping(obsv.d_opool, (size_t)pool_top, (size_t)pool_now)) return rc;
             HIPCHK(hipEventRecord(ev[4], v.stream));
             succ(O_WRITE, n_items, c1 - (uint32_t)chunk, grid, e_total);
             succ(O_VERIFY, n_items, c1 - (uint32_t)chunk, grid, e_total);
@@ -1365,85 +1322,85 @@ int AutomatonServices::observer(const AutomatonView &view, const stcsp_observer_
     // canonical numbers, level by level: a new state's key is the least (number of a parent, label rank) over the edges of the level
     std::vector<uint32_t> canon(n_states, 0), idx;
     std::vector<unsigned long long> keys;
-    HIPCHK(d_ocanon.reserve(n_states));
-    HIPCHK(d_okeys.reserve(n_states));
-    HIPCHK(hipMemsetAsync(d_okeys.p, 0xff, (size_t)n_states * sizeof(unsigned long long), v.stream));
-    HIPCHK(hipMemsetAsync(d_ocanon.p, 0, sizeof(uint32_t), v.stream));
+    HIPCHK(obsv.d_ocanon.reserve(n_states));
+    HIPCHK(obsv.d_okeys.reserve(n_states));
+    HIPCHK(hipMemsetAsync(obsv.d_okeys.p, 0xff, (size_t)n_states * sizeof(unsigned long long), v.stream));
+    HIPCHK(hipMemsetAsync(obsv.d_ocanon.p, 0, sizeof(uint32_t), v.stream));
     uint32_t next = 1;
     for (const Level &lv : levels) {
         const uint32_t n_new = lv.s1 - lv.s0;
         if (!n_new) continue;
-        hipLaunchKernelGGL(k_o_keys, dim3((lv.e1 - lv.e0 + 255) / 256), dim3(256), 0, v.stream, lv.e0, lv.e1, (const uint32_t *)d_oesrc.p,
-                           (const uint32_t *)d_oelab.p, (const uint32_t *)d_oedst.p, lv.s0, (const uint32_t *)d_ocanon.p, d_okeys.p);
+        hipLaunchKernelGGL(k_o_keys, dim3((lv.e1 - lv.e0 + 255) / 256), dim3(256), 0, v.stream, lv.e0, lv.e1, (const uint32_t *)obsv.d_oesrc.p,
+                           (const uint32_t *)obsv.d_oelab.p, (const uint32_t *)obsv.d_oedst.p, lv.s0, (const uint32_t *)obsv.d_ocanon.p, obsv.d_okeys.p);
         HIPCHK(hipGetLastError());
         keys.resize(n_new);
-        HIPCHK(hipMemcpyAsync(keys.data(), d_okeys.p + lv.s0, (size_t)n_new * sizeof(unsigned long long), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(keys.data(), obsv.d_okeys.p + lv.s0, (size_t)n_new * sizeof(unsigned long long), hipMemcpyDeviceToHost, v.stream));
         HIPCHK(hipStreamSynchronize(v.stream));
         idx.resize(n_new);
         for (uint32_t i = 0; i < n_new; i++) idx[i] = i;
         std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
         for (uint32_t i = 0; i < n_new; i++) canon[lv.s0 + idx[i]] = next++;
-        HIPCHK(hipMemcpyAsync(d_ocanon.p + lv.s0, canon.data() + lv.s0, (size_t)n_new * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+        HIPCHK(hipMemcpyAsync(obsv.d_ocanon.p + lv.s0, canon.data() + lv.s0, (size_t)n_new * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
         HIPCHK(hipStreamSynchronize(v.stream));
     }
     // the result: records, members in canonical order, edges sorted by (source number, label rank)
     std::vector<ObsRec> rec(n_states);
     std::vector<unsigned long long> where(n_states);
-    HIPCHK(hipMemcpyAsync(rec.data(), d_orec.p, (size_t)n_states * sizeof(ObsRec), hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(rec.data(), obsv.d_orec.p, (size_t)n_states * sizeof(ObsRec), hipMemcpyDeviceToHost, v.stream));
     HIPCHK(hipStreamSynchronize(v.stream));
-    o_moff.assign((size_t)n_states + 1, 0);
-    o_final.assign(n_states, 0);
+    obsv.o_moff.assign((size_t)n_states + 1, 0);
+    obsv.o_final.assign(n_states, 0);
     int64_t max_set = 0;
     for (uint32_t s = 0; s < n_states; s++) {
-        o_moff[canon[s] + 1] = rec[s].n;
-        o_final[canon[s]] = (uint8_t)rec[s].fin;
+        obsv.o_moff[canon[s] + 1] = rec[s].n;
+        obsv.o_final[canon[s]] = (uint8_t)rec[s].fin;
         max_set = std::max<int64_t>(max_set, rec[s].n);
     }
-    for (uint32_t c = 0; c < n_states; c++) o_moff[c + 1] += o_moff[c];
-    for (uint32_t s = 0; s < n_states; s++) where[s] = (unsigned long long)o_moff[canon[s]];
-    if ((unsigned long long)o_moff[n_states] != pool_top) return fail(STCSP_E_INTERNAL, "observer: the records name %lld members, the pool holds %llu", (long long)o_moff[n_states], pool_top);
-    HIPCHK(d_owhere.reserve(n_states));
-    HIPCHK(d_omember.reserve((size_t)pool_top));
-    HIPCHK(hipMemcpyAsync(d_owhere.p, where.data(), (size_t)n_states * sizeof(unsigned long long), hipMemcpyHostToDevice, v.stream));
-    hipLaunchKernelGGL(k_o_gather, dim3(std::min<uint32_t>(n_states, 4096)), dim3(256), 0, v.stream, n_states, (const ObsRec *)d_orec.p,
-                       (const unsigned long long *)d_owhere.p, (const uint32_t *)d_opool.p, d_omember.p);
+    for (uint32_t c = 0; c < n_states; c++) obsv.o_moff[c + 1] += obsv.o_moff[c];
+    for (uint32_t s = 0; s < n_states; s++) where[s] = (unsigned long long)obsv.o_moff[canon[s]];
+    if ((unsigned long long)obsv.o_moff[n_states] != pool_top) return fail(STCSP_E_INTERNAL, "observer: the records name %lld members, the pool holds %llu", (long long)obsv.o_moff[n_states], pool_top);
+    HIPCHK(obsv.d_owhere.reserve(n_states));
+    HIPCHK(obsv.d_omember.reserve((size_t)pool_top));
+    HIPCHK(hipMemcpyAsync(obsv.d_owhere.p, where.data(), (size_t)n_states * sizeof(unsigned long long), hipMemcpyHostToDevice, v.stream));
+    hipLaunchKernelGGL(k_o_gather, dim3(std::min<uint32_t>(n_states, 4096)), dim3(256), 0, v.stream, n_states, (const ObsRec *)obsv.d_orec.p,
+                       (const unsigned long long *)obsv.d_owhere.p, (const uint32_t *)obsv.d_opool.p, obsv.d_omember.p);
     if (e_total)
-        hipLaunchKernelGGL(k_o_renumber, dim3((e_total + 255) / 256), dim3(256), 0, v.stream, e_total, d_oesrc.p, d_oedst.p, (const uint32_t *)d_ocanon.p);
+        hipLaunchKernelGGL(k_o_renumber, dim3((e_total + 255) / 256), dim3(256), 0, v.stream, e_total, obsv.d_oesrc.p, obsv.d_oedst.p, (const uint32_t *)obsv.d_ocanon.p);
     HIPCHK(hipGetLastError());
-    o_member.resize((size_t)pool_top);
+    obsv.o_member.resize((size_t)pool_top);
     std::vector<uint32_t> esrc(e_total), elab(e_total), edst(e_total);
-    HIPCHK(hipMemcpyAsync(o_member.data(), d_omember.p, (size_t)pool_top * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(obsv.o_member.data(), obsv.d_omember.p, (size_t)pool_top * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
     if (e_total) {
-        HIPCHK(hipMemcpyAsync(esrc.data(), d_oesrc.p, (size_t)e_total * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(hipMemcpyAsync(elab.data(), d_oelab.p, (size_t)e_total * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(hipMemcpyAsync(edst.data(), d_oedst.p, (size_t)e_total * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(esrc.data(), obsv.d_oesrc.p, (size_t)e_total * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(elab.data(), obsv.d_oelab.p, (size_t)e_total * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(edst.data(), obsv.d_oedst.p, (size_t)e_total * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
     }
     HIPCHK(hipStreamSynchronize(v.stream));
     idx.resize(e_total);
     for (uint32_t e = 0; e < e_total; e++) idx[e] = e;
     std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return esrc[a] != esrc[b] ? esrc[a] < esrc[b] : elab[a] < elab[b]; });
-    o_esrc.resize(e_total);
-    o_edst.resize(e_total);
-    o_evalues.resize((size_t)e_total * n_obs);
+    obsv.o_esrc.resize(e_total);
+    obsv.o_edst.resize(e_total);
+    obsv.o_evalues.resize((size_t)e_total * n_obs);
     for (uint32_t i = 0; i < e_total; i++) {
         const uint32_t e = idx[i];
-        o_esrc[i] = (int32_t)esrc[e];
-        o_edst[i] = (int32_t)edst[e];
-        std::copy(obs_rows.begin() + elab[e] * n_obs, obs_rows.begin() + (elab[e] + 1) * n_obs, o_evalues.begin() + i * n_obs);
+        obsv.o_esrc[i] = (int32_t)esrc[e];
+        obsv.o_edst[i] = (int32_t)edst[e];
+        std::copy(obsv.rows.begin() + elab[e] * n_obs, obsv.rows.begin() + (elab[e] + 1) * n_obs, obsv.o_evalues.begin() + i * n_obs);
     }
-    cmp_left.set_graph(gen_n_obs, n_states, o_final.data(), e_total, [&](size_t i) { return o_esrc[i]; }, [&](size_t i) { return elab[idx[i]]; },
-                       [&](size_t i) { return o_edst[i]; });
-    cmp_left.rows = obs_rows;
-    cmp_left.n_rows = nL;
-    cmp_valid = true;
-    cmp_left_on_device = false;
+    cmp.left.set_graph(gen.n_obs, n_states, obsv.o_final.data(), e_total, [&](size_t i) { return obsv.o_esrc[i]; }, [&](size_t i) { return elab[idx[i]]; },
+                       [&](size_t i) { return obsv.o_edst[i]; });
+    cmp.left.rows = obsv.rows;
+    cmp.left.n_rows = nL;
+    cmp.valid = true;
+    cmp.left_on_device = false;
     out->n_states = n_states;
     out->n_edges = e_total;
     out->n_labels = nL;
     out->max_set = max_set;
     out->levels = (int32_t)levels.size();
     out->table_bytes = (int64_t)(pool_top * sizeof(uint32_t) + (size_t)n_states * sizeof(ObsRec) + cap_s * (sizeof(unsigned long long) + sizeof(uint32_t)) +
-                                 (size_t)e_total * 3 * sizeof(uint32_t) + scratch_peak + (size_t)rep_total * sizeof(unsigned long long));
+                                 (size_t)e_total * 3 * sizeof(uint32_t) + scratch_peak + (size_t)lab.total * sizeof(unsigned long long));
     publish();
     return STCSP_OK;
 }
@@ -1452,21 +1409,21 @@ int AutomatonServices::observer(const AutomatonView &view, const stcsp_observer_
 // witnesses (contract: stcsp_engine.h; dev_compare.hpp).
 int AutomatonServices::compare(const AutomatonView &view, const stcsp_compare_request *rq, stcsp_compare_result *out) {
     if (int rc = enter(view, "compare", NEED_GENERATOR, "stcsp_compare_observers")) return rc;
-    if (!cmp_valid) return fail(STCSP_E_STATE, "compare needs a successful observer() after the last generator_build()");
+    if (!cmp.valid) return fail(STCSP_E_STATE, "compare needs a successful observer() after the last generator_build()");
     if (!rq->right || rq->max_pairs < 0) return fail(STCSP_E_INVALID, "compare: no right operand, or a negative max_pairs");
     if (const char *fault = compare_operand_fault(*rq->right)) return fail(STCSP_E_INVALID, "compare: the right operand %s", fault);
-    if (rq->right->n_observable != cmp_left.n_obs)
-        return fail(STCSP_E_INVALID, "compare: the right operand has %d observable variables, the observer has %d", rq->right->n_observable, cmp_left.n_obs);
+    if (rq->right->n_observable != cmp.left.n_obs)
+        return fail(STCSP_E_INVALID, "compare: the right operand has %d observable variables, the observer has %d", rq->right->n_observable, cmp.left.n_obs);
     auto t0 = std::chrono::steady_clock::now();
     const unsigned long long max_pairs = std::min<unsigned long long>(rq->max_pairs ? (unsigned long long)rq->max_pairs : 1ull << 26, 0x7ffffffeull);
-    const size_t n_obs = (size_t)cmp_left.n_obs;
-    c_witness.clear();
-    c_witness.reserve(1);  // (an empty vector still gives a valid pointer)
+    const size_t n_obs = (size_t)cmp.left.n_obs;
+    cmp.c_witness.clear();
+    cmp.c_witness.reserve(1);  // (an empty vector still gives a valid pointer)
     memset(out, 0, sizeof *out);
-    out->n_observable = cmp_left.n_obs;
-    out->witness_values = c_witness.data();
+    out->n_observable = cmp.left.n_obs;
+    out->witness_values = cmp.c_witness.data();
     for (int k = 0; k < 4; k++) out->witness_len[k] = out->witness_left[k] = out->witness_right[k] = -1;
-    const CompareOperand &left = cmp_left;
+    const CompareOperand &left = cmp.left;
     CompareOperand right;
     right.load(*rq->right);
     if (!left.n_states && !right.n_states) {  // two automata without states: no pair
@@ -1489,19 +1446,19 @@ int AutomatonServices::compare(const AutomatonView &view, const stcsp_compare_re
         if (!vec.empty()) HIPCHK(hipMemcpyAsync(buf.p, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice, v.stream));
         return STCSP_OK;
     };
-    if (!cmp_left_on_device) {
-        if (int rc = upload(d_cloff, left.off)) return rc;
-        if (int rc = upload(d_cldst, left.dst)) return rc;
-        if (int rc = upload(d_clfin, left.fin)) return rc;
+    if (!cmp.left_on_device) {
+        if (int rc = upload(cmp.d_cloff, left.off)) return rc;
+        if (int rc = upload(cmp.d_cldst, left.dst)) return rc;
+        if (int rc = upload(cmp.d_clfin, left.fin)) return rc;
     }
-    if (int rc = upload(d_cllab, lab_l)) return rc;
-    if (int rc = upload(d_croff, right.off)) return rc;
-    if (int rc = upload(d_crlab, lab_r)) return rc;
-    if (int rc = upload(d_crdst, right.dst)) return rc;
-    if (int rc = upload(d_crfin, right.fin)) return rc;
+    if (int rc = upload(cmp.d_cllab, lab_l)) return rc;
+    if (int rc = upload(cmp.d_croff, right.off)) return rc;
+    if (int rc = upload(cmp.d_crlab, lab_r)) return rc;
+    if (int rc = upload(cmp.d_crdst, right.dst)) return rc;
+    if (int rc = upload(cmp.d_crfin, right.fin)) return rc;
     HIPCHK(hipStreamSynchronize(v.stream));  // (the vectors of this call are locals)
-    cmp_left_on_device = true;
-    const CmpSide L{d_cloff.p, d_cllab.p, d_cldst.p, d_clfin.p, left.n_states}, R{d_croff.p, d_crlab.p, d_crdst.p, d_crfin.p, right.n_states};
+    cmp.left_on_device = true;
+    const CmpSide L{cmp.d_cloff.p, cmp.d_cllab.p, cmp.d_cldst.p, cmp.d_clfin.p, left.n_states}, R{cmp.d_croff.p, cmp.d_crlab.p, cmp.d_crdst.p, cmp.d_crfin.p, right.n_states};
     auto pow2 = [](unsigned long long n) {
         unsigned long long c = 64;
         while (c < n) c <<= 1;
@@ -1520,20 +1477,20 @@ int AutomatonServices::compare(const AutomatonView &view, const stcsp_compare_re
                     levels, need, budget, levels, n_pairs, edges);
     };
     if (bytes_of(slots, cap_new, 1) > budget) return over_budget(bytes_of(slots, cap_new, 1));
-    if (!d_ctab.reserve_or_release(slots) || !d_cmin.reserve_or_release(slots)) return fail(STCSP_E_NOMEM, "compare: no room for a table of %llu slots", slots);
-    HIPCHK(d_cnew.reserve(1));
-    HIPCHK(d_cctl.reserve_exact(C_WORDS));
+    if (!cmp.d_ctab.reserve_or_release(slots) || !cmp.d_cmin.reserve_or_release(slots)) return fail(STCSP_E_NOMEM, "compare: no room for a table of %llu slots", slots);
+    HIPCHK(cmp.d_cnew.reserve(1));
+    HIPCHK(cmp.d_cctl.reserve_exact(C_WORDS));
     HIPCHK(ev.ready(6));
     uint32_t ctl[C_WORDS] = {0};
     for (int k = 0; k < 4; k++) ctl[C_VERDICT + k] = kCmpNone;
-    HIPCHK(hipMemcpyAsync(d_cctl.p, ctl, sizeof ctl, hipMemcpyHostToDevice, v.stream));
-    HIPCHK(hipMemsetAsync(d_ctab.p, 0xff, slots * sizeof(unsigned long long), v.stream));
-    HIPCHK(hipMemsetAsync(d_cmin.p, 0xff, slots * sizeof(unsigned long long), v.stream));
+    HIPCHK(hipMemcpyAsync(cmp.d_cctl.p, ctl, sizeof ctl, hipMemcpyHostToDevice, v.stream));
+    HIPCHK(hipMemsetAsync(cmp.d_ctab.p, 0xff, slots * sizeof(unsigned long long), v.stream));
+    HIPCHK(hipMemsetAsync(cmp.d_cmin.p, 0xff, slots * sizeof(unsigned long long), v.stream));
     // the root pair: an operand without states starts in its sink (index 0 == n_states)
-    hipLaunchKernelGGL(k_c_init, dim3(1), dim3(64), 0, v.stream, 0ull, d_ctab.p, d_cmin.p, (uint32_t)(slots - 1), d_cnew.p, d_cctl.p);
+    hipLaunchKernelGGL(k_c_init, dim3(1), dim3(64), 0, v.stream, 0ull, cmp.d_ctab.p, cmp.d_cmin.p, (uint32_t)(slots - 1), cmp.d_cnew.p, cmp.d_cctl.p);
     auto read_ctl = [&]() -> int {
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(ctl, d_cctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(ctl, cmp.d_cctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
         HIPCHK(hipStreamSynchronize(v.stream));
         if (ctl[C_ERROR]) return fail(STCSP_E_INTERNAL, "compare: a device table overflowed (flags %u)", ctl[C_ERROR]);
         return STCSP_OK;
@@ -1548,26 +1505,26 @@ int AutomatonServices::compare(const AutomatonView &view, const stcsp_compare_re
     };
     std::vector<unsigned long long> keys;
     std::vector<uint32_t> idx;
-    std::vector<uint32_t> &rank = c_rank;  // (a member: its upload may still be queued when a level fails)
+    std::vector<uint32_t> &rank = cmp.c_rank;  // (a member: its upload may still be queued when a level fails)
     for (unsigned long long n_new = 1; n_new;) {
         // the n_new pairs of this level: their numbers, their records, their verdicts
         if (n_pairs + n_new > max_pairs)
             return fail(STCSP_E_NOMEM, "compare: more than max_pairs = %llu pairs; the product got to level %d with %llu pairs and %llu edges", max_pairs, levels,
                         n_pairs, edges);
         if (bytes_of(slots, cap_new, n_pairs + n_new) > budget) return over_budget(bytes_of(slots, cap_new, n_pairs + n_new));
-        if (int rc = grow_keeping(d_cpkey, (size_t)n_pairs, (size_t)(n_pairs + n_new), "compare")) return rc;
-        if (int rc = grow_keeping(d_cparent, (size_t)n_pairs, (size_t)(n_pairs + n_new), "compare")) return rc;
-        if (int rc = grow_keeping(d_cplabel, (size_t)n_pairs, (size_t)(n_pairs + n_new), "compare")) return rc;
-        HIPCHK(d_ckeys.reserve((size_t)n_new));
-        HIPCHK(d_crank.reserve((size_t)n_new));
+        if (int rc = grow_keeping(cmp.d_cpkey, (size_t)n_pairs, (size_t)(n_pairs + n_new), "compare")) return rc;
+        if (int rc = grow_keeping(cmp.d_cparent, (size_t)n_pairs, (size_t)(n_pairs + n_new), "compare")) return rc;
+        if (int rc = grow_keeping(cmp.d_cplabel, (size_t)n_pairs, (size_t)(n_pairs + n_new), "compare")) return rc;
+        HIPCHK(cmp.d_ckeys.reserve((size_t)n_new));
+        HIPCHK(cmp.d_crank.reserve((size_t)n_new));
         const unsigned nb = (unsigned)((n_new + 255) / 256);
-        HIPCHK(hipMemsetAsync(d_cctl.p + C_DEG, 0, 2 * sizeof(uint32_t), v.stream));
+        HIPCHK(hipMemsetAsync(cmp.d_cctl.p + C_DEG, 0, 2 * sizeof(uint32_t), v.stream));
         HIPCHK(hipEventRecord(ev[2], v.stream));
-        hipLaunchKernelGGL(k_c_collect, dim3(nb), dim3(256), 0, v.stream, (uint32_t)n_new, (const uint32_t *)d_cnew.p, (const unsigned long long *)d_ctab.p,
-                           (const unsigned long long *)d_cmin.p, L.off, R.off, d_ckeys.p, d_cctl.p);
+        hipLaunchKernelGGL(k_c_collect, dim3(nb), dim3(256), 0, v.stream, (uint32_t)n_new, (const uint32_t *)cmp.d_cnew.p, (const unsigned long long *)cmp.d_ctab.p,
+                           (const unsigned long long *)cmp.d_cmin.p, L.off, R.off, cmp.d_ckeys.p, cmp.d_cctl.p);
         HIPCHK(hipEventRecord(ev[3], v.stream));
         keys.resize((size_t)n_new);
-        HIPCHK(hipMemcpyAsync(keys.data(), d_ckeys.p, (size_t)n_new * sizeof(unsigned long long), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(keys.data(), cmp.d_ckeys.p, (size_t)n_new * sizeof(unsigned long long), hipMemcpyDeviceToHost, v.stream));
         if (int rc = read_ctl()) return rc;
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, ev[2], ev[3]));
@@ -1577,11 +1534,11 @@ int AutomatonServices::compare(const AutomatonView &view, const stcsp_compare_re
         for (uint32_t i = 0; i < n_new; i++) idx[i] = i;
         std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
         for (uint32_t i = 0; i < n_new; i++) rank[idx[i]] = i;
-        HIPCHK(hipMemcpyAsync(d_crank.p, rank.data(), (size_t)n_new * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+        HIPCHK(hipMemcpyAsync(cmp.d_crank.p, rank.data(), (size_t)n_new * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
         HIPCHK(hipEventRecord(ev[4], v.stream));
-        hipLaunchKernelGGL(k_c_number, dim3(nb), dim3(256), 0, v.stream, (uint32_t)n_new, (uint32_t)n_pairs, (const uint32_t *)d_cnew.p, (const uint32_t *)d_crank.p,
-                           (const unsigned long long *)d_ctab.p, (const unsigned long long *)d_ckeys.p, L.fin, R.fin, L.n, R.n, d_cpkey.p, d_cparent.p, d_cplabel.p,
-                           d_cctl.p);
+        hipLaunchKernelGGL(k_c_number, dim3(nb), dim3(256), 0, v.stream, (uint32_t)n_new, (uint32_t)n_pairs, (const uint32_t *)cmp.d_cnew.p, (const uint32_t *)cmp.d_crank.p,
+                           (const unsigned long long *)cmp.d_ctab.p, (const unsigned long long *)cmp.d_ckeys.p, L.fin, R.fin, L.n, R.n, cmp.d_cpkey.p, cmp.d_cparent.p, cmp.d_cplabel.p,
+                           cmp.d_cctl.p);
         HIPCHK(hipEventRecord(ev[5], v.stream));
         number_pending = true;
         const uint32_t f0 = (uint32_t)n_pairs, f1 = (uint32_t)(n_pairs + n_new);
@@ -1597,27 +1554,27 @@ int AutomatonServices::compare(const AutomatonView &view, const stcsp_compare_re
         const unsigned long long want = std::max(slots, pow2(2 * (n_pairs + bound)));
         if (bytes_of(want, bound, n_pairs) > budget) return over_budget(bytes_of(want, bound, n_pairs));
         if (want > slots) {
-            if (!d_ctab2.reserve_or_release(want) || !d_cmin.reserve_or_release(want))
+            if (!cmp.d_ctab2.reserve_or_release(want) || !cmp.d_cmin.reserve_or_release(want))
                 return fail(STCSP_E_NOMEM, "compare: no room for a table of %llu slots at level %d (%llu pairs so far)", want, levels, n_pairs);
-            HIPCHK(hipMemsetAsync(d_ctab2.p, 0xff, want * sizeof(unsigned long long), v.stream));
-            HIPCHK(hipMemsetAsync(d_cmin.p, 0xff, want * sizeof(unsigned long long), v.stream));
-            hipLaunchKernelGGL(k_c_rehash, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)slots, (const unsigned long long *)d_ctab.p, d_ctab2.p,
-                               (uint32_t)(want - 1), d_cctl.p);
-            std::swap(d_ctab.p, d_ctab2.p);
-            std::swap(d_ctab.n, d_ctab2.n);
+            HIPCHK(hipMemsetAsync(cmp.d_ctab2.p, 0xff, want * sizeof(unsigned long long), v.stream));
+            HIPCHK(hipMemsetAsync(cmp.d_cmin.p, 0xff, want * sizeof(unsigned long long), v.stream));
+            hipLaunchKernelGGL(k_c_rehash, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)slots, (const unsigned long long *)cmp.d_ctab.p, cmp.d_ctab2.p,
+                               (uint32_t)(want - 1), cmp.d_cctl.p);
+            std::swap(cmp.d_ctab.p, cmp.d_ctab2.p);
+            std::swap(cmp.d_ctab.n, cmp.d_ctab2.n);
             slots = want;
         }
         cap_new = std::min<unsigned long long>(bound, 0xffffffffull);
-        if (!d_cnew.reserve_or_release((size_t)cap_new)) return fail(STCSP_E_NOMEM, "compare: no room for %llu new pairs at level %d (%llu pairs so far)", cap_new, levels, n_pairs);
+        if (!cmp.d_cnew.reserve_or_release((size_t)cap_new)) return fail(STCSP_E_NOMEM, "compare: no room for %llu new pairs at level %d (%llu pairs so far)", cap_new, levels, n_pairs);
         peak = std::max(peak, bytes_of(slots, cap_new, n_pairs));
         // lanes per pair by the mean out-degree of the frontier: 8 for the common few edges per pair, a wavefront for wide pairs
         const bool wide = bound > 16ull * (f1 - f0);
         const unsigned groups = wide ? 4 : 32;
         const unsigned grid = (unsigned)std::min<unsigned long long>(((unsigned long long)(f1 - f0) + groups - 1) / groups, 8192);
-        HIPCHK(hipMemsetAsync(d_cctl.p + C_NEW, 0, sizeof(uint32_t), v.stream));
+        HIPCHK(hipMemsetAsync(cmp.d_cctl.p + C_NEW, 0, sizeof(uint32_t), v.stream));
         HIPCHK(hipEventRecord(ev[0], v.stream));
-        hipLaunchKernelGGL(wide ? k_c_expand<64> : k_c_expand<8>, dim3(grid), dim3(256), 0, v.stream, f0, f1, (const unsigned long long *)d_cpkey.p, L, R, d_ctab.p,
-                           d_cmin.p, (uint32_t)(slots - 1), d_cnew.p, (uint32_t)cap_new, d_cctl.p);
+        hipLaunchKernelGGL(wide ? k_c_expand<64> : k_c_expand<8>, dim3(grid), dim3(256), 0, v.stream, f0, f1, (const unsigned long long *)cmp.d_cpkey.p, L, R, cmp.d_ctab.p,
+                           cmp.d_cmin.p, (uint32_t)(slots - 1), cmp.d_cnew.p, (uint32_t)cap_new, cmp.d_cctl.p);
         HIPCHK(hipEventRecord(ev[1], v.stream));
         if (int rc = read_ctl()) return rc;
         if (int rc = take_number_time()) return rc;
@@ -1630,13 +1587,13 @@ int AutomatonServices::compare(const AutomatonView &view, const stcsp_compare_re
     if (int rc = take_number_time()) return rc;
     // the witnesses: the access sequence of each verdict's pair, from the (parent, label) records
     std::vector<uint32_t> parent((size_t)n_pairs), plabel((size_t)n_pairs);
-    HIPCHK(hipMemcpyAsync(parent.data(), d_cparent.p, (size_t)n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
-    HIPCHK(hipMemcpyAsync(plabel.data(), d_cplabel.p, (size_t)n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(parent.data(), cmp.d_cparent.p, (size_t)n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(plabel.data(), cmp.d_cplabel.p, (size_t)n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
     unsigned long long wkey[4] = {0, 0, 0, 0};
     for (int k = 0; k < 4; k++)
         if (ctl[C_VERDICT + k] != kCmpNone) {
             if (ctl[C_VERDICT + k] >= n_pairs) return fail(STCSP_E_INTERNAL, "compare: verdict %d names pair %u of %llu", k, ctl[C_VERDICT + k], n_pairs);
-            HIPCHK(hipMemcpyAsync(&wkey[k], d_cpkey.p + ctl[C_VERDICT + k], sizeof(unsigned long long), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(&wkey[k], cmp.d_cpkey.p + ctl[C_VERDICT + k], sizeof(unsigned long long), hipMemcpyDeviceToHost, v.stream));
         }
     HIPCHK(hipStreamSynchronize(v.stream));
     std::vector<uint32_t> path;
@@ -1649,15 +1606,15 @@ int AutomatonServices::compare(const AutomatonView &view, const stcsp_compare_re
                 return fail(STCSP_E_INTERNAL, "compare: the record of pair %u does not lead to the root", q);
             path.push_back(plabel[q]);
         }
-        for (size_t i = path.size(); i-- > 0;) c_witness.insert(c_witness.end(), rows.begin() + path[i] * n_obs, rows.begin() + (path[i] + 1) * n_obs);
+        for (size_t i = path.size(); i-- > 0;) cmp.c_witness.insert(cmp.c_witness.end(), rows.begin() + path[i] * n_obs, rows.begin() + (path[i] + 1) * n_obs);
         const uint32_t l = (uint32_t)(wkey[k] >> 32), r = (uint32_t)wkey[k];
         out->witness_len[k] = (int32_t)path.size();
         out->witness_left[k] = l == left.n_states ? -1 : (int32_t)l;
         out->witness_right[k] = r == right.n_states ? -1 : (int32_t)r;
         out->witness_off[k + 1] += (int64_t)path.size();
     }
-    c_witness.reserve(1);
-    out->witness_values = c_witness.data();
+    cmp.c_witness.reserve(1);
+    out->witness_values = cmp.c_witness.data();
     out->n_pairs = (int64_t)n_pairs;
     out->n_pair_edges = (int64_t)edges;
     out->levels = levels;
@@ -1678,11 +1635,11 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
     if (max_lassos < -1) return fail(STCSP_E_INVALID, "components: max_lassos is 0 (none), -1 (all) or a positive count");
     if (v.exp_edges > 0x7fffffffull || S > 0x3fffffffu) return fail(STCSP_E_NOMEM, "automaton too large for the device component pass");
     if (int rc = live_set()) return rc;
-    HIPCHK(reserve_all(S, 1, d_scomp, d_scolour, d_sin, d_sout, d_sdepth, d_soff));
-    HIPCHK(d_sinfo.reserve(4 * (size_t)S));
-    HIPCHK(d_somega.reserve(S));
-    HIPCHK(d_sctl.reserve_exact(S_WORDS));
-    HIPCHK(d_ssel.reserve_exact(64));
+    HIPCHK(reserve_all(S, 1, scc.d_scomp, scc.d_scolour, scc.d_sin, scc.d_sout, scc.d_sdepth, scc.d_soff));
+    HIPCHK(scc.d_sinfo.reserve(4 * (size_t)S));
+    HIPCHK(scc.d_somega.reserve(S));
+    HIPCHK(scc.d_sctl.reserve_exact(S_WORDS));
+    HIPCHK(scc.d_ssel.reserve_exact(64));
     HIPCHK(ev.ready(2));
     const unsigned sb = (S + 255) / 256, eb = (E + 255) / 256;
     const size_t sw = (size_t)S * sizeof(uint32_t);
@@ -1699,7 +1656,7 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
         if (int rc = begin()) return rc;
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev[1], v.stream));
-        HIPCHK(hipMemcpyAsync(ctl, d_sctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(ctl, scc.d_sctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
         HIPCHK(hipStreamSynchronize(v.stream));
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
@@ -1710,27 +1667,27 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
     // the live edges as CSR by source
     uint32_t L = 0;
     if (int rc = begin()) return rc;
-    HIPCHK(hipMemsetAsync(d_sctl.p, 0, sizeof ctl, v.stream));
-    HIPCHK(hipMemsetAsync(d_sin.p, 0, sw, v.stream));
+    HIPCHK(hipMemsetAsync(scc.d_sctl.p, 0, sizeof ctl, v.stream));
+    HIPCHK(hipMemsetAsync(scc.d_sin.p, 0, sw, v.stream));
     if (E)
-        hipLaunchKernelGGL(k_s_count, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)d_palive.p, (const uint8_t *)d_live.p,
-                           d_sin.p);
-    hipLaunchKernelGGL(k_s_scan, dim3(1), dim3(256), 0, v.stream, S, (S + 255) / 256, (const uint32_t *)d_sin.p, d_soff.p, d_sout.p);
-    HIPCHK(hipMemcpyAsync(&L, d_soff.p + S, sizeof L, hipMemcpyDeviceToHost, v.stream));
+        hipLaunchKernelGGL(k_s_count, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p, (const uint8_t *)post.d_live.p,
+                           scc.d_sin.p);
+    hipLaunchKernelGGL(k_s_scan, dim3(1), dim3(256), 0, v.stream, S, (S + 255) / 256, (const uint32_t *)scc.d_sin.p, scc.d_soff.p, scc.d_sout.p);
+    HIPCHK(hipMemcpyAsync(&L, scc.d_soff.p + S, sizeof L, hipMemcpyDeviceToHost, v.stream));
     if (int rc = flush()) return rc;
     if (L > E) return fail(STCSP_E_INTERNAL, "components: %u live edges of %u", L, E);
-    HIPCHK(reserve_all(L, 1, d_ssrc, d_sdst, d_seid));
+    HIPCHK(reserve_all(L, 1, scc.d_ssrc, scc.d_sdst, scc.d_seid));
     const unsigned lb = (L + 255) / 256;
-    const uint32_t *csrc = d_ssrc.p, *cdst = d_sdst.p;
+    const uint32_t *csrc = scc.d_ssrc.p, *cdst = scc.d_sdst.p;
     if (L)
-        hipLaunchKernelGGL(k_s_fill, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)d_palive.p, (const uint8_t *)d_live.p,
-                           d_sout.p, L, d_ssrc.p, d_sdst.p, d_seid.p);
+        hipLaunchKernelGGL(k_s_fill, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p, (const uint8_t *)post.d_live.p,
+                           scc.d_sout.p, L, scc.d_ssrc.p, scc.d_sdst.p, scc.d_seid.p);
     // step(i) launches sweep i; a batch of sweeps, then one look at the changed word; past the fixpoint a sweep changes nothing
     const int kBatch = 4;
     auto fixpoint = [&](const char *what, auto &&step) -> int {
         for (uint32_t done = 0;;) {
             if (int rc = begin()) return rc;
-            HIPCHK(hipMemsetAsync(d_sctl.p + S_CHANGED, 0, sizeof(uint32_t), v.stream));
+            HIPCHK(hipMemsetAsync(scc.d_sctl.p + S_CHANGED, 0, sizeof(uint32_t), v.stream));
             for (int b = 0; b < kBatch; b++, sweeps++)
                 if (int rc = step(done++)) return rc;
             if (int rc = flush()) return rc;
@@ -1739,76 +1696,76 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
         }
     };
     // trim and colour until every live state has a component
-    HIPCHK(hipMemsetAsync(d_scomp.p, 0xff, sw, v.stream));
-    while ((int64_t)ctl[S_ASSIGNED] < n_live) {
+    HIPCHK(hipMemsetAsync(scc.d_scomp.p, 0xff, sw, v.stream));
+    while ((int64_t)ctl[S_ASSIGNED] < post.n_live) {
         if (!(flags & STCSP_SCC_NO_TRIM)) {
             const int rc = fixpoint("trimming", [&](uint32_t) -> int {
-                HIPCHK(hipMemsetAsync(d_sin.p, 0, sw, v.stream));
-                HIPCHK(hipMemsetAsync(d_sout.p, 0, sw, v.stream));
-                if (L) hipLaunchKernelGGL(k_s_deg, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, (const uint32_t *)d_scomp.p, d_sin.p, d_sout.p);
-                hipLaunchKernelGGL(k_s_trim, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint32_t *)d_sin.p,
-                                   (const uint32_t *)d_sout.p, d_scomp.p, d_sctl.p);
+                HIPCHK(hipMemsetAsync(scc.d_sin.p, 0, sw, v.stream));
+                HIPCHK(hipMemsetAsync(scc.d_sout.p, 0, sw, v.stream));
+                if (L) hipLaunchKernelGGL(k_s_deg, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, (const uint32_t *)scc.d_scomp.p, scc.d_sin.p, scc.d_sout.p);
+                hipLaunchKernelGGL(k_s_trim, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)post.d_live.p, (const uint32_t *)scc.d_sin.p,
+                                   (const uint32_t *)scc.d_sout.p, scc.d_scomp.p, scc.d_sctl.p);
                 trim_rounds++;
                 return STCSP_OK;
             });
             if (rc) return rc;
-            if ((int64_t)ctl[S_ASSIGNED] >= n_live) break;
+            if ((int64_t)ctl[S_ASSIGNED] >= post.n_live) break;
         }
         if ((uint32_t)colour_rounds++ > S + 8) return fail(STCSP_E_INTERNAL, "components: the colouring rounds did not converge");
         if (int rc = begin()) return rc;
-        hipLaunchKernelGGL(k_s_colour_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint32_t *)d_scomp.p, d_scolour.p);
+        hipLaunchKernelGGL(k_s_colour_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)post.d_live.p, (const uint32_t *)scc.d_scomp.p, scc.d_scolour.p);
         int rc = fixpoint("colouring", [&](uint32_t) -> int {
-            if (L) hipLaunchKernelGGL(k_s_colour_fwd, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, d_scolour.p, d_sctl.p);
+            if (L) hipLaunchKernelGGL(k_s_colour_fwd, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, scc.d_scolour.p, scc.d_sctl.p);
             return STCSP_OK;
         });
         if (rc) return rc;
         if (int rc2 = begin()) return rc2;
-        hipLaunchKernelGGL(k_s_roots, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)d_scolour.p, d_scomp.p, d_sctl.p);
+        hipLaunchKernelGGL(k_s_roots, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)scc.d_scolour.p, scc.d_scomp.p, scc.d_sctl.p);
         rc = fixpoint("collecting", [&](uint32_t) -> int {
-            if (L) hipLaunchKernelGGL(k_s_colour_back, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, (const uint32_t *)d_scolour.p, d_scomp.p, d_sctl.p);
+            if (L) hipLaunchKernelGGL(k_s_colour_back, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, (const uint32_t *)scc.d_scolour.p, scc.d_scomp.p, scc.d_sctl.p);
             return STCSP_OK;
         });
         if (rc) return rc;
     }
-    if ((int64_t)ctl[S_ASSIGNED] != n_live) return fail(STCSP_E_INTERNAL, "components: %u of %lld live states have a component", ctl[S_ASSIGNED], (long long)n_live);
+    if ((int64_t)ctl[S_ASSIGNED] != post.n_live) return fail(STCSP_E_INTERNAL, "components: %u of %lld live states have a component", ctl[S_ASSIGNED], (long long)post.n_live);
     // depths, the facts of every component, omega
     if (int rc = begin()) return rc;
-    HIPCHK(hipMemsetAsync(d_sdepth.p, 0xff, sw, v.stream));
-    if (root_live) HIPCHK(hipMemsetAsync(d_sdepth.p, 0, sizeof(uint32_t), v.stream));
+    HIPCHK(hipMemsetAsync(scc.d_sdepth.p, 0xff, sw, v.stream));
+    if (post.root_live) HIPCHK(hipMemsetAsync(scc.d_sdepth.p, 0, sizeof(uint32_t), v.stream));
     if (int rc = fixpoint("the depths", [&](uint32_t level) -> int {
-            if (L) hipLaunchKernelGGL(k_s_bfs, dim3(lb), dim3(256), 0, v.stream, L, level, csrc, cdst, d_sdepth.p, d_sctl.p);
+            if (L) hipLaunchKernelGGL(k_s_bfs, dim3(lb), dim3(256), 0, v.stream, L, level, csrc, cdst, scc.d_sdepth.p, scc.d_sctl.p);
             return STCSP_OK;
         }))
         return rc;
     if (int rc = begin()) return rc;
-    HIPCHK(hipMemsetAsync(d_sinfo.p, 0, 2 * sw, v.stream));
-    HIPCHK(hipMemsetAsync(d_sinfo.p + 2 * (size_t)S, 0xff, 2 * sw, v.stream));
-    hipLaunchKernelGGL(k_s_state_info, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint8_t *)d_pfinal.p,
-                       (const uint32_t *)d_scomp.p, (const uint32_t *)d_sdepth.p, d_sinfo.p);
-    if (L) hipLaunchKernelGGL(k_s_edge_info, dim3(lb), dim3(256), 0, v.stream, L, S, csrc, cdst, (const uint32_t *)d_scomp.p, d_sinfo.p);
-    hipLaunchKernelGGL(k_s_omega_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint32_t *)d_scomp.p,
-                       (const uint32_t *)d_sinfo.p, d_somega.p);
+    HIPCHK(hipMemsetAsync(scc.d_sinfo.p, 0, 2 * sw, v.stream));
+    HIPCHK(hipMemsetAsync(scc.d_sinfo.p + 2 * (size_t)S, 0xff, 2 * sw, v.stream));
+    hipLaunchKernelGGL(k_s_state_info, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)post.d_live.p, (const uint8_t *)post.d_pfinal.p,
+                       (const uint32_t *)scc.d_scomp.p, (const uint32_t *)scc.d_sdepth.p, scc.d_sinfo.p);
+    if (L) hipLaunchKernelGGL(k_s_edge_info, dim3(lb), dim3(256), 0, v.stream, L, S, csrc, cdst, (const uint32_t *)scc.d_scomp.p, scc.d_sinfo.p);
+    hipLaunchKernelGGL(k_s_omega_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)post.d_live.p, (const uint32_t *)scc.d_scomp.p,
+                       (const uint32_t *)scc.d_sinfo.p, scc.d_somega.p);
     if (int rc = fixpoint("omega", [&](uint32_t) -> int {
-            if (L) hipLaunchKernelGGL(k_s_omega_back, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, d_somega.p, d_sctl.p);
+            if (L) hipLaunchKernelGGL(k_s_omega_back, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, scc.d_somega.p, scc.d_sctl.p);
             return STCSP_OK;
         }))
         return rc;
     std::vector<uint32_t> raw(S), info(4 * (size_t)S);
-    s_omega.assign(S, 0);
-    HIPCHK(hipMemcpyAsync(raw.data(), d_scomp.p, sw, hipMemcpyDeviceToHost, v.stream));
-    HIPCHK(hipMemcpyAsync(info.data(), d_sinfo.p, 4 * sw, hipMemcpyDeviceToHost, v.stream));
-    HIPCHK(hipMemcpyAsync(s_omega.data(), d_somega.p, S, hipMemcpyDeviceToHost, v.stream));
+    scc.s_omega.assign(S, 0);
+    HIPCHK(hipMemcpyAsync(raw.data(), scc.d_scomp.p, sw, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(info.data(), scc.d_sinfo.p, 4 * sw, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(scc.s_omega.data(), scc.d_somega.p, S, hipMemcpyDeviceToHost, v.stream));
     if (int rc = flush()) return rc;
     // component numbers by least member: a component's raw name is its least member, so the first state that shows it is that member
-    s_component.assign(S, -1);
-    s_size.clear();
-    s_depth.clear();
-    s_flags.clear();
+    scc.s_component.assign(S, -1);
+    scc.s_size.clear();
+    scc.s_depth.clear();
+    scc.s_flags.clear();
     std::vector<int32_t> number(S, -1);
     std::vector<uint32_t> least;
     memset(out, 0, sizeof *out);
     for (uint32_t s = 0; s < S; s++) {
-        if (!live[s]) continue;
+        if (!post.live[s]) continue;
         const uint32_t r = raw[s];
         if (r >= S || (number[r] < 0 && r != s)) return fail(STCSP_E_INTERNAL, "components: state %u is named after %u, not its component's least member", s, r);
         if (number[r] < 0) {
@@ -1817,37 +1774,37 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
             const uint32_t f = info[(size_t)S + r];
             int32_t cf = (f & S_INFO_CYCLIC ? STCSP_SCC_CYCLIC : 0) | (f & S_INFO_FINAL ? STCSP_SCC_FINAL : 0) | (f & S_INFO_LEAVES ? 0 : STCSP_SCC_BOTTOM);
             if ((f & S_INFO_CYCLIC) && (f & S_INFO_FINAL)) cf |= STCSP_SCC_ACCEPTING;
-            s_size.push_back((int32_t)info[r]);
-            s_depth.push_back((int32_t)info[2 * (size_t)S + r]);
-            s_flags.push_back(cf);
+            scc.s_size.push_back((int32_t)info[r]);
+            scc.s_depth.push_back((int32_t)info[2 * (size_t)S + r]);
+            scc.s_flags.push_back(cf);
             out->n_cyclic += (cf & STCSP_SCC_CYCLIC) != 0;
             out->n_accepting += (cf & STCSP_SCC_ACCEPTING) != 0;
             out->n_bottom += (cf & STCSP_SCC_BOTTOM) != 0;
         }
-        s_component[s] = number[r];
-        out->n_omega += s_omega[s];
+        scc.s_component[s] = number[r];
+        out->n_omega += scc.s_omega[s];
     }
     // lassos: the accepting components by (depth, number), 64 stems per pass, then every loop at once
-    s_lcomp.clear();
-    s_lstem.clear();
-    s_lvalues.clear();
-    s_loff.assign(1, 0);
+    scc.s_lcomp.clear();
+    scc.s_lstem.clear();
+    scc.s_lvalues.clear();
+    scc.s_loff.assign(1, 0);
     std::vector<int32_t> wanted;
     if (max_lassos != 0)
-        for (int32_t c = 0; c < (int32_t)s_flags.size(); c++)
-            if ((s_flags[c] & STCSP_SCC_ACCEPTING) && (!(flags & STCSP_SCC_LASSO_BOTTOM) || (s_flags[c] & STCSP_SCC_BOTTOM))) wanted.push_back(c);
-    std::stable_sort(wanted.begin(), wanted.end(), [&](int32_t a, int32_t b) { return s_depth[a] < s_depth[b]; });
+        for (int32_t c = 0; c < (int32_t)scc.s_flags.size(); c++)
+            if ((scc.s_flags[c] & STCSP_SCC_ACCEPTING) && (!(flags & STCSP_SCC_LASSO_BOTTOM) || (scc.s_flags[c] & STCSP_SCC_BOTTOM))) wanted.push_back(c);
+    std::stable_sort(wanted.begin(), wanted.end(), [&](int32_t a, int32_t b) { return scc.s_depth[a] < scc.s_depth[b]; });
     if (max_lassos > 0 && (int64_t)wanted.size() > max_lassos) wanted.resize((size_t)max_lassos);
     if (!wanted.empty()) {
         std::vector<uint32_t> depth(S), off((size_t)S + 1), heid(L), dist(S), anchors(wanted.size());
         auto hdst = [&](uint32_t k) { return (uint32_t)v.h_odst[heid[k]]; };  // (the destinations are in the pinned export already)
         std::vector<unsigned long long> mark(S);
         std::vector<std::vector<int32_t>> stems(wanted.size());
-        HIPCHK(d_smark.reserve(S));
-        HIPCHK(d_sdist.reserve(S));
-        HIPCHK(hipMemcpyAsync(depth.data(), d_sdepth.p, sw, hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(hipMemcpyAsync(off.data(), d_soff.p, sw + sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(hipMemcpyAsync(heid.data(), d_seid.p, (size_t)L * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(scc.d_smark.reserve(S));
+        HIPCHK(scc.d_sdist.reserve(S));
+        HIPCHK(hipMemcpyAsync(depth.data(), scc.d_sdepth.p, sw, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(off.data(), scc.d_soff.p, sw + sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(heid.data(), scc.d_seid.p, (size_t)L * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
         bool twice = false;
         // the position of the live out-edge of u with the least full row among those whose destination `ok` admits; L when there is none
         auto least_edge = [&](uint32_t u, auto &&ok) {
@@ -1873,13 +1830,13 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
             }
             if (deepest > S) return fail(STCSP_E_INTERNAL, "components: an accepting component without a final state");
             if (int rc = begin()) return rc;
-            HIPCHK(hipMemcpyAsync(d_ssel.p, sel, (size_t)n_sel * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
-            hipLaunchKernelGGL(k_s_stem_init, dim3(sb), dim3(256), 0, v.stream, S, n_sel, (const uint32_t *)d_ssel.p, (const uint8_t *)d_live.p,
-                               (const uint8_t *)d_pfinal.p, (const uint32_t *)d_scomp.p, (const uint32_t *)d_sdepth.p, (const uint32_t *)d_sinfo.p,
-                               d_smark.p);
+            HIPCHK(hipMemcpyAsync(scc.d_ssel.p, sel, (size_t)n_sel * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+            hipLaunchKernelGGL(k_s_stem_init, dim3(sb), dim3(256), 0, v.stream, S, n_sel, (const uint32_t *)scc.d_ssel.p, (const uint8_t *)post.d_live.p,
+                               (const uint8_t *)post.d_pfinal.p, (const uint32_t *)scc.d_scomp.p, (const uint32_t *)scc.d_sdepth.p, (const uint32_t *)scc.d_sinfo.p,
+                               scc.d_smark.p);
             for (uint32_t level = deepest; level-- > 0; sweeps++)
-                hipLaunchKernelGGL(k_s_stem_back, dim3(lb), dim3(256), 0, v.stream, L, level, csrc, cdst, (const uint32_t *)d_sdepth.p, d_smark.p);
-            HIPCHK(hipMemcpyAsync(mark.data(), d_smark.p, (size_t)S * sizeof(unsigned long long), hipMemcpyDeviceToHost, v.stream));
+                hipLaunchKernelGGL(k_s_stem_back, dim3(lb), dim3(256), 0, v.stream, L, level, csrc, cdst, (const uint32_t *)scc.d_sdepth.p, scc.d_smark.p);
+            HIPCHK(hipMemcpyAsync(mark.data(), scc.d_smark.p, (size_t)S * sizeof(unsigned long long), hipMemcpyDeviceToHost, v.stream));
             if (int rc = flush()) return rc;
             for (int j = 0; j < n_sel; j++) {
                 const uint32_t len = info[3 * (size_t)S + sel[j]];
@@ -1897,16 +1854,16 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
         }
         // the anchors' buffer: the colours are no longer needed (as many anchors as components at the most)
         if (int rc = begin()) return rc;
-        HIPCHK(hipMemcpyAsync(d_scolour.p, anchors.data(), anchors.size() * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
-        HIPCHK(hipMemsetAsync(d_sdist.p, 0xff, sw, v.stream));
+        HIPCHK(hipMemcpyAsync(scc.d_scolour.p, anchors.data(), anchors.size() * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+        HIPCHK(hipMemsetAsync(scc.d_sdist.p, 0xff, sw, v.stream));
         hipLaunchKernelGGL(k_s_loop_init, dim3(((unsigned)anchors.size() + 255) / 256), dim3(256), 0, v.stream, (uint32_t)anchors.size(), S,
-                           (const uint32_t *)d_scolour.p, d_sdist.p);
+                           (const uint32_t *)scc.d_scolour.p, scc.d_sdist.p);
         if (int rc = fixpoint("the loop distances", [&](uint32_t level) -> int {
-                if (L) hipLaunchKernelGGL(k_s_loop_back, dim3(lb), dim3(256), 0, v.stream, L, level, csrc, cdst, (const uint32_t *)d_scomp.p, d_sdist.p, d_sctl.p);
+                if (L) hipLaunchKernelGGL(k_s_loop_back, dim3(lb), dim3(256), 0, v.stream, L, level, csrc, cdst, (const uint32_t *)scc.d_scomp.p, scc.d_sdist.p, scc.d_sctl.p);
                 return STCSP_OK;
             }))
             return rc;
-        HIPCHK(hipMemcpyAsync(dist.data(), d_sdist.p, sw, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(dist.data(), scc.d_sdist.p, sw, hipMemcpyDeviceToHost, v.stream));
         if (int rc = flush()) return rc;
         for (size_t i = 0; i < wanted.size(); i++) {
             const uint32_t a = anchors[i], r = raw[a];
@@ -1914,37 +1871,37 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
             for (uint32_t k = off[a]; k < off[a + 1]; k++)
                 if (raw[hdst(k)] == r && dist[hdst(k)] != kSNone) loop_len = std::min(loop_len, dist[hdst(k)] + 1);
             if (loop_len == kSNone) return fail(STCSP_E_INTERNAL, "components: no loop through state %u of component %d", a, wanted[i]);
-            s_lvalues.insert(s_lvalues.end(), stems[i].begin(), stems[i].end());
+            scc.s_lvalues.insert(scc.s_lvalues.end(), stems[i].begin(), stems[i].end());
             uint32_t u = a;
             for (uint32_t rem = loop_len; rem > 0; rem--) {
                 const uint32_t k = least_edge(u, [&](uint32_t w) { return raw[w] == r && dist[w] == rem - 1; });
                 if (twice) return fail(STCSP_E_INTERNAL, "components: two live out-edges of state %u carry the same full row", u);
                 if (k == L) return fail(STCSP_E_INTERNAL, "components: the loop of component %d stops at state %u", wanted[i], u);
-                s_lvalues.insert(s_lvalues.end(), v.h_oval + (size_t)heid[k] * N, v.h_oval + ((size_t)heid[k] + 1) * N);
+                scc.s_lvalues.insert(scc.s_lvalues.end(), v.h_oval + (size_t)heid[k] * N, v.h_oval + ((size_t)heid[k] + 1) * N);
                 u = hdst(k);
             }
             if (u != a) return fail(STCSP_E_INTERNAL, "components: the loop of component %d ends in state %u, not in %u", wanted[i], u, a);
-            s_lcomp.push_back(wanted[i]);
-            s_lstem.push_back((int32_t)(stems[i].size() / (size_t)std::max(N, 1)));
-            s_loff.push_back(s_loff.back() + (int64_t)(stems[i].size() / (size_t)std::max(N, 1)) + loop_len);
+            scc.s_lcomp.push_back(wanted[i]);
+            scc.s_lstem.push_back((int32_t)(stems[i].size() / (size_t)std::max(N, 1)));
+            scc.s_loff.push_back(scc.s_loff.back() + (int64_t)(stems[i].size() / (size_t)std::max(N, 1)) + loop_len);
         }
     }
-    for (auto *vec : {&s_component, &s_size, &s_depth, &s_flags, &s_lcomp, &s_lstem, &s_lvalues}) vec->reserve(1);
-    s_omega.reserve(1);
-    out->n_states = n_live;
-    out->n_components = (int64_t)s_size.size();
-    out->state_component = s_component.data();
-    out->state_omega = s_omega.data();
-    out->comp_size = s_size.data();
-    out->comp_depth = s_depth.data();
-    out->comp_flags = s_flags.data();
-    out->n_lassos = (int64_t)s_lcomp.size();
-    out->lasso_component = s_lcomp.data();
-    out->lasso_off = s_loff.data();
-    out->lasso_stem_len = s_lstem.data();
-    out->lasso_values = s_lvalues.data();
+    for (auto *vec : {&scc.s_component, &scc.s_size, &scc.s_depth, &scc.s_flags, &scc.s_lcomp, &scc.s_lstem, &scc.s_lvalues}) vec->reserve(1);
+    scc.s_omega.reserve(1);
+    out->n_states = post.n_live;
+    out->n_components = (int64_t)scc.s_size.size();
+    out->state_component = scc.s_component.data();
+    out->state_omega = scc.s_omega.data();
+    out->comp_size = scc.s_size.data();
+    out->comp_depth = scc.s_depth.data();
+    out->comp_flags = scc.s_flags.data();
+    out->n_lassos = (int64_t)scc.s_lcomp.size();
+    out->lasso_component = scc.s_lcomp.data();
+    out->lasso_off = scc.s_loff.data();
+    out->lasso_stem_len = scc.s_lstem.data();
+    out->lasso_values = scc.s_lvalues.data();
     out->n_vars = N;
-    out->root_omega = root_live && s_omega[0];
+    out->root_omega = post.root_live && scc.s_omega[0];
     out->rounds[0] = trim_rounds;
     out->rounds[1] = colour_rounds;
     out->rounds[2] = sweeps;
@@ -1985,17 +1942,17 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
         const stcsp_components_options co = {0, 0, 0};
         stcsp_components_result cres;
         if (int rc = components(view, &co, &cres)) return rc;
-        n_comp = (uint32_t)s_size.size();
+        n_comp = (uint32_t)scc.s_size.size();
         n_of.assign(S, 0);
         comp_of.assign(S, kOptIdxNone);
         least.assign(n_comp, kOptIdxNone);
         for (uint32_t s = 0; s < S; s++) {
-            const int32_t c = s_component[s];
+            const int32_t c = scc.s_component[s];
             if (c < 0) continue;
             comp_of[s] = (uint32_t)c;
             if (least[c] == kOptIdxNone) least[c] = s;
-            if (s_flags[c] & STCSP_SCC_CYCLIC) {
-                n_of[s] = (uint32_t)s_size[c];
+            if (scc.s_flags[c] & STCSP_SCC_CYCLIC) {
+                n_of[s] = (uint32_t)scc.s_size[c];
                 nmax = std::max(nmax, n_of[s]);
             }
         }
@@ -2009,18 +1966,18 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
     const size_t row_bytes = n_rows * (size_t)S * sizeof(long long);
     if (row_bytes > budget)
         return fail(STCSP_E_NOMEM, "optimise: %zu value rows of %u states need %zu bytes, the budget (STCSP_OPTIMISE_BYTES) is %zu", n_rows, S, row_bytes, budget);
-    opt_best.assign((size_t)horizon + 1, kOptNone);
-    opt_state_best.clear();
-    opt_woff.assign((size_t)n_len + 1, 0);
-    opt_wvalues.clear();
-    opt_wstates.clear();
-    opt_component.clear();
-    opt_num.assign(n_comp, 0);
-    opt_den.assign(n_comp, 0);
-    HIPCHK(reserve_all(S, 1, d_opt_deg, d_opt_off, d_opt_cur));
-    HIPCHK(d_opt_ctl.reserve_exact(OPT_WORDS));
-    HIPCHK(d_opt_w.reserve_exact((size_t)std::max(N, 1)));
-    HIPCHK(d_opt_best.reserve((size_t)horizon + 1));
+    opt.opt_best.assign((size_t)horizon + 1, kOptNone);
+    opt.opt_state_best.clear();
+    opt.opt_woff.assign((size_t)n_len + 1, 0);
+    opt.opt_wvalues.clear();
+    opt.opt_wstates.clear();
+    opt.opt_component.clear();
+    opt.opt_num.assign(n_comp, 0);
+    opt.opt_den.assign(n_comp, 0);
+    HIPCHK(reserve_all(S, 1, opt.d_opt_deg, opt.d_opt_off, opt.d_opt_cur));
+    HIPCHK(opt.d_opt_ctl.reserve_exact(OPT_WORDS));
+    HIPCHK(opt.d_opt_w.reserve_exact((size_t)std::max(N, 1)));
+    HIPCHK(opt.d_opt_best.reserve((size_t)horizon + 1));
     HIPCHK(ev.ready(2));
     const unsigned sb = (S + 255) / 256, eb = (E + 255) / 256;
     uint32_t ctl[OPT_WORDS] = {0, 0, 0, 0};
@@ -2036,7 +1993,7 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
         if (int rc = begin()) return rc;
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev[1], v.stream));
-        HIPCHK(hipMemcpyAsync(ctl, d_opt_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(ctl, opt.d_opt_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
         HIPCHK(hipStreamSynchronize(v.stream));
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
@@ -2053,14 +2010,14 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
     uint32_t L = 0;
     if (S) {
         if (int rc = begin()) return rc;
-        HIPCHK(hipMemsetAsync(d_opt_ctl.p, 0, sizeof ctl, v.stream));
-        HIPCHK(hipMemsetAsync(d_opt_deg.p, 0, (size_t)S * sizeof(uint32_t), v.stream));
-        if (N) HIPCHK(hipMemcpyAsync(d_opt_w.p, w.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+        HIPCHK(hipMemsetAsync(opt.d_opt_ctl.p, 0, sizeof ctl, v.stream));
+        HIPCHK(hipMemsetAsync(opt.d_opt_deg.p, 0, (size_t)S * sizeof(uint32_t), v.stream));
+        if (N) HIPCHK(hipMemcpyAsync(opt.d_opt_w.p, w.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
         if (E)
-            hipLaunchKernelGGL(k_s_count, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)d_palive.p, (const uint8_t *)d_live.p,
-                               d_opt_deg.p);
-        hipLaunchKernelGGL(k_s_scan, dim3(1), dim3(256), 0, v.stream, S, (S + 255) / 256, (const uint32_t *)d_opt_deg.p, d_opt_off.p, d_opt_cur.p);
-        HIPCHK(hipMemcpyAsync(&L, d_opt_off.p + S, sizeof L, hipMemcpyDeviceToHost, v.stream));
+            hipLaunchKernelGGL(k_s_count, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p, (const uint8_t *)post.d_live.p,
+                               opt.d_opt_deg.p);
+        hipLaunchKernelGGL(k_s_scan, dim3(1), dim3(256), 0, v.stream, S, (S + 255) / 256, (const uint32_t *)opt.d_opt_deg.p, opt.d_opt_off.p, opt.d_opt_cur.p);
+        HIPCHK(hipMemcpyAsync(&L, opt.d_opt_off.p + S, sizeof L, hipMemcpyDeviceToHost, v.stream));
         if (int rc = flush()) return rc;
         if (L > E) return fail(STCSP_E_INTERNAL, "optimise: %u live edges of %u", L, E);
     }
@@ -2070,61 +2027,61 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
     if (need > budget)
         return fail(STCSP_E_NOMEM, "optimise: %zu value rows of %u states, %u live edges%s need %zu bytes, the budget (STCSP_OPTIMISE_BYTES) is %zu", n_rows, S, L,
                     mean ? " and the cycle-mean tables" : "", need, budget);
-    if (!d_opt_rows.reserve_or_release(n_rows * (size_t)S)) return fail(STCSP_E_NOMEM, "optimise: no room for %zu bytes of value rows", row_bytes);
-    HIPCHK(reserve_all(L, 1, d_opt_src, d_opt_dst, d_opt_eid));
-    HIPCHK(d_opt_cost.reserve(L, 1));
+    if (!opt.d_opt_rows.reserve_or_release(n_rows * (size_t)S)) return fail(STCSP_E_NOMEM, "optimise: no room for %zu bytes of value rows", row_bytes);
+    HIPCHK(reserve_all(L, 1, opt.d_opt_src, opt.d_opt_dst, opt.d_opt_eid));
+    HIPCHK(opt.d_opt_cost.reserve(L, 1));
     const unsigned lb = (L + 255) / 256;
-    const uint32_t *csrc = d_opt_src.p, *cdst = d_opt_dst.p;
+    const uint32_t *csrc = opt.d_opt_src.p, *cdst = opt.d_opt_dst.p;
     if (S) {
         // finite horizon: V_0, then a relaxation and a clearing launch per level
-        auto row = [&](int32_t k) { return d_opt_rows.p + (size_t)(witnesses ? k : k % 2) * S; };
+        auto row = [&](int32_t k) { return opt.d_opt_rows.p + (size_t)(witnesses ? k : k % 2) * S; };
         auto next_row = [&](int32_t k) { return k + 1 <= horizon ? row(k + 1) : (long long *)nullptr; };
         if (int rc = begin()) return rc;
         if (L) {
-            hipLaunchKernelGGL(k_s_fill, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)d_palive.p, (const uint8_t *)d_live.p,
-                               d_opt_cur.p, L, d_opt_src.p, d_opt_dst.p, d_opt_eid.p);
-            hipLaunchKernelGGL(k_opt_cost, dim3(lb), dim3(256), 0, v.stream, L, N, (const uint32_t *)d_opt_eid.p, v.d_oval, (const int32_t *)d_opt_w.p, d_opt_cost.p);
+            hipLaunchKernelGGL(k_s_fill, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p, (const uint8_t *)post.d_live.p,
+                               opt.d_opt_cur.p, L, opt.d_opt_src.p, opt.d_opt_dst.p, opt.d_opt_eid.p);
+            hipLaunchKernelGGL(k_opt_cost, dim3(lb), dim3(256), 0, v.stream, L, N, (const uint32_t *)opt.d_opt_eid.p, v.d_oval, (const int32_t *)opt.d_opt_w.p, opt.d_opt_cost.p);
         }
-        hipLaunchKernelGGL(k_opt_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)d_live.p, (const uint8_t *)d_pfinal.p, end_final, row(0));
-        hipLaunchKernelGGL(k_opt_clear, dim3(sb), dim3(256), 0, v.stream, S, next_row(0), (const long long *)row(0), d_opt_best.p);
+        hipLaunchKernelGGL(k_opt_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)post.d_live.p, (const uint8_t *)post.d_pfinal.p, end_final, row(0));
+        hipLaunchKernelGGL(k_opt_clear, dim3(sb), dim3(256), 0, v.stream, S, next_row(0), (const long long *)row(0), opt.d_opt_best.p);
         launches_dp += 2;
         for (int32_t k = 1; k <= horizon; k++, launches_dp += 2) {
             if (L)
-                hipLaunchKernelGGL(k_opt_relax_back, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, (const long long *)d_opt_cost.p,
+                hipLaunchKernelGGL(k_opt_relax_back, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, (const long long *)opt.d_opt_cost.p,
                                    (const long long *)row(k - 1), row(k));
-            hipLaunchKernelGGL(k_opt_clear, dim3(sb), dim3(256), 0, v.stream, S, next_row(k), (const long long *)row(k), d_opt_best.p + k);
+            hipLaunchKernelGGL(k_opt_clear, dim3(sb), dim3(256), 0, v.stream, S, next_row(k), (const long long *)row(k), opt.d_opt_best.p + k);
         }
-        HIPCHK(hipMemcpyAsync(opt_best.data(), d_opt_best.p, ((size_t)horizon + 1) * sizeof(long long), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(opt.opt_best.data(), opt.d_opt_best.p, ((size_t)horizon + 1) * sizeof(long long), hipMemcpyDeviceToHost, v.stream));
         if (flags & STCSP_OPT_STATE_BEST) {
-            opt_state_best.resize(S);
-            HIPCHK(hipMemcpyAsync(opt_state_best.data(), row(horizon), (size_t)S * sizeof(long long), hipMemcpyDeviceToHost, v.stream));
+            opt.opt_state_best.resize(S);
+            HIPCHK(hipMemcpyAsync(opt.opt_state_best.data(), row(horizon), (size_t)S * sizeof(long long), hipMemcpyDeviceToHost, v.stream));
         }
         if (int rc = flush()) return rc;
         // witnesses: one wavefront per requested length walks the rows; the host gathers the label rows from the pinned export
-        for (int32_t i = 0; i < n_len; i++) opt_woff[(size_t)i + 1] = opt_woff[i] + (opt_best[rq->lengths[i]] == kOptNone ? 0 : rq->lengths[i]);
-        const size_t T = (size_t)opt_woff[n_len];
+        for (int32_t i = 0; i < n_len; i++) opt.opt_woff[(size_t)i + 1] = opt.opt_woff[i] + (opt.opt_best[rq->lengths[i]] == kOptNone ? 0 : rq->lengths[i]);
+        const size_t T = (size_t)opt.opt_woff[n_len];
         if (T) {
             std::vector<uint32_t> weid(T);
-            opt_wstates.resize(T);
-            HIPCHK(d_opt_len.reserve((size_t)n_len));
-            HIPCHK(d_opt_woff.reserve((size_t)n_len + 1));
-            HIPCHK(reserve_all(T, 0, d_opt_weid, d_opt_wstate));
+            opt.opt_wstates.resize(T);
+            HIPCHK(opt.d_opt_len.reserve((size_t)n_len));
+            HIPCHK(opt.d_opt_woff.reserve((size_t)n_len + 1));
+            HIPCHK(reserve_all(T, 0, opt.d_opt_weid, opt.d_opt_wstate));
             if (int rc = begin()) return rc;
-            HIPCHK(hipMemcpyAsync(d_opt_len.p, rq->lengths, (size_t)n_len * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-            HIPCHK(hipMemcpyAsync(d_opt_woff.p, opt_woff.data(), ((size_t)n_len + 1) * sizeof(long long), hipMemcpyHostToDevice, v.stream));
-            hipLaunchKernelGGL(k_opt_walk, dim3((unsigned)n_len), dim3(64), 0, v.stream, S, N, (int)n_len, (const int32_t *)d_opt_len.p, (const long long *)d_opt_woff.p,
-                               (const long long *)d_opt_rows.p, (const uint32_t *)d_opt_off.p, cdst, (const uint32_t *)d_opt_eid.p, (const long long *)d_opt_cost.p,
-                               v.d_oval, d_opt_weid.p, d_opt_wstate.p, d_opt_ctl.p);
+            HIPCHK(hipMemcpyAsync(opt.d_opt_len.p, rq->lengths, (size_t)n_len * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+            HIPCHK(hipMemcpyAsync(opt.d_opt_woff.p, opt.opt_woff.data(), ((size_t)n_len + 1) * sizeof(long long), hipMemcpyHostToDevice, v.stream));
+            hipLaunchKernelGGL(k_opt_walk, dim3((unsigned)n_len), dim3(64), 0, v.stream, S, N, (int)n_len, (const int32_t *)opt.d_opt_len.p, (const long long *)opt.d_opt_woff.p,
+                               (const long long *)opt.d_opt_rows.p, (const uint32_t *)opt.d_opt_off.p, cdst, (const uint32_t *)opt.d_opt_eid.p, (const long long *)opt.d_opt_cost.p,
+                               v.d_oval, opt.d_opt_weid.p, opt.d_opt_wstate.p, opt.d_opt_ctl.p);
             launches_dp++;
-            HIPCHK(hipMemcpyAsync(weid.data(), d_opt_weid.p, T * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
-            HIPCHK(hipMemcpyAsync(opt_wstates.data(), d_opt_wstate.p, T * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(weid.data(), opt.d_opt_weid.p, T * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(opt.opt_wstates.data(), opt.d_opt_wstate.p, T * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
             if (int rc = flush()) return rc;
             if (ctl[OPT_DUPLICATE]) return fail(STCSP_E_INTERNAL, "optimise: two live out-edges of state %u carry the same full row", ctl[OPT_DUPLICATE] - 1);
             if (ctl[OPT_STUCK]) return fail(STCSP_E_INTERNAL, "optimise: the walk stops at state %u", ctl[OPT_STUCK] - 1);
-            opt_wvalues.resize(T * (size_t)N);
+            opt.opt_wvalues.resize(T * (size_t)N);
             for (size_t t = 0; t < T; t++) {
                 if (weid[t] >= E) return fail(STCSP_E_INTERNAL, "optimise: the walk names edge %u of %u", weid[t], E);
-                std::copy(v.h_oval + (size_t)weid[t] * N, v.h_oval + ((size_t)weid[t] + 1) * N, opt_wvalues.begin() + t * (size_t)N);
+                std::copy(v.h_oval + (size_t)weid[t] * N, v.h_oval + ((size_t)weid[t] + 1) * N, opt.opt_wvalues.begin() + t * (size_t)N);
             }
         }
     }
@@ -2132,52 +2089,52 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
     int64_t omega_num = 0, omega_den = 0;
     int32_t omega_comp = -1;
     if (mean) {
-        opt_component = s_component;
+        opt.opt_component = scc.s_component;
         if (nmax) {
             std::vector<long long> num(S);
             std::vector<uint32_t> den(S), arg(n_comp);
-            HIPCHK(reserve_all(S, 0, d_opt_nof, d_opt_comp, d_opt_den));
-            HIPCHK(reserve_all(n_comp, 0, d_opt_least, d_opt_arg));
-            HIPCHK(reserve_all(S, 0, d_opt_dn, d_opt_num));
-            HIPCHK(d_opt_d.reserve(2 * (size_t)S));
-            long long *d[2] = {d_opt_d.p, d_opt_d.p + S};
+            HIPCHK(reserve_all(S, 0, opt.d_opt_nof, opt.d_opt_comp, opt.d_opt_den));
+            HIPCHK(reserve_all(n_comp, 0, opt.d_opt_least, opt.d_opt_arg));
+            HIPCHK(reserve_all(S, 0, opt.d_opt_dn, opt.d_opt_num));
+            HIPCHK(opt.d_opt_d.reserve(2 * (size_t)S));
+            long long *d[2] = {opt.d_opt_d.p, opt.d_opt_d.p + S};
             if (int rc = begin()) return rc;
-            HIPCHK(hipMemcpyAsync(d_opt_nof.p, n_of.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
-            HIPCHK(hipMemcpyAsync(d_opt_comp.p, comp_of.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
-            HIPCHK(hipMemcpyAsync(d_opt_least.p, least.data(), (size_t)n_comp * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
-            HIPCHK(hipMemsetAsync(d_opt_den.p, 0, (size_t)S * sizeof(uint32_t), v.stream));
-            HIPCHK(hipMemsetAsync(d_opt_num.p, 0, (size_t)S * sizeof(long long), v.stream));
-            HIPCHK(hipMemsetAsync(d_opt_arg.p, 0xff, (size_t)n_comp * sizeof(uint32_t), v.stream));
-            const uint32_t *nof = d_opt_nof.p, *comp = d_opt_comp.p;
+            HIPCHK(hipMemcpyAsync(opt.d_opt_nof.p, n_of.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+            HIPCHK(hipMemcpyAsync(opt.d_opt_comp.p, comp_of.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+            HIPCHK(hipMemcpyAsync(opt.d_opt_least.p, least.data(), (size_t)n_comp * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+            HIPCHK(hipMemsetAsync(opt.d_opt_den.p, 0, (size_t)S * sizeof(uint32_t), v.stream));
+            HIPCHK(hipMemsetAsync(opt.d_opt_num.p, 0, (size_t)S * sizeof(long long), v.stream));
+            HIPCHK(hipMemsetAsync(opt.d_opt_arg.p, 0xff, (size_t)n_comp * sizeof(uint32_t), v.stream));
+            const uint32_t *nof = opt.d_opt_nof.p, *comp = opt.d_opt_comp.p;
             auto fwd = [&](uint32_t k) {
                 if (L)
-                    hipLaunchKernelGGL(k_opt_karp_fwd, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, comp, (const long long *)d_opt_cost.p,
+                    hipLaunchKernelGGL(k_opt_karp_fwd, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, comp, (const long long *)opt.d_opt_cost.p,
                                        (const long long *)d[(k - 1) % 2], d[k % 2]);
                 launches_karp++;
             };
             // pass 1: D_n of every state, n the size of its component
-            hipLaunchKernelGGL(k_opt_karp_init, dim3(sb), dim3(256), 0, v.stream, S, nof, comp, (const uint32_t *)d_opt_least.p, d[0], d[1], d_opt_dn.p);
+            hipLaunchKernelGGL(k_opt_karp_init, dim3(sb), dim3(256), 0, v.stream, S, nof, comp, (const uint32_t *)opt.d_opt_least.p, d[0], d[1], opt.d_opt_dn.p);
             for (uint32_t k = 1; k <= nmax; k++, launches_karp++) {
                 fwd(k);
-                hipLaunchKernelGGL(k_opt_karp_keep, dim3(sb), dim3(256), 0, v.stream, S, k, nof, (const long long *)d[k % 2], d[(k - 1) % 2], d_opt_dn.p);
+                hipLaunchKernelGGL(k_opt_karp_keep, dim3(sb), dim3(256), 0, v.stream, S, k, nof, (const long long *)d[k % 2], d[(k - 1) % 2], opt.d_opt_dn.p);
             }
             // pass 2: D_k again, level by level, and per state the greatest (D_n - D_k) / (n - k)
-            hipLaunchKernelGGL(k_opt_karp_init, dim3(sb), dim3(256), 0, v.stream, S, nof, comp, (const uint32_t *)d_opt_least.p, d[0], d[1], (long long *)nullptr);
+            hipLaunchKernelGGL(k_opt_karp_init, dim3(sb), dim3(256), 0, v.stream, S, nof, comp, (const uint32_t *)opt.d_opt_least.p, d[0], d[1], (long long *)nullptr);
             for (uint32_t k = 0; k < nmax; k++, launches_karp++) {
                 if (k) fwd(k);
                 hipLaunchKernelGGL(k_opt_karp_ratio, dim3(sb), dim3(256), 0, v.stream, S, k, nof, (const long long *)d[k % 2], d[(k + 1) % 2],
-                                   (const long long *)d_opt_dn.p, d_opt_num.p, d_opt_den.p);
+                                   (const long long *)opt.d_opt_dn.p, opt.d_opt_num.p, opt.d_opt_den.p);
             }
-            hipLaunchKernelGGL(k_opt_karp_min, dim3(sb), dim3(256), 0, v.stream, S, S, comp, (const long long *)d_opt_num.p, (const uint32_t *)d_opt_den.p,
-                               d_opt_arg.p, d_opt_ctl.p);
+            hipLaunchKernelGGL(k_opt_karp_min, dim3(sb), dim3(256), 0, v.stream, S, S, comp, (const long long *)opt.d_opt_num.p, (const uint32_t *)opt.d_opt_den.p,
+                               opt.d_opt_arg.p, opt.d_opt_ctl.p);
             launches_karp += 3;
-            HIPCHK(hipMemcpyAsync(num.data(), d_opt_num.p, (size_t)S * sizeof(long long), hipMemcpyDeviceToHost, v.stream));
-            HIPCHK(hipMemcpyAsync(den.data(), d_opt_den.p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
-            HIPCHK(hipMemcpyAsync(arg.data(), d_opt_arg.p, (size_t)n_comp * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(num.data(), opt.d_opt_num.p, (size_t)S * sizeof(long long), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(den.data(), opt.d_opt_den.p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(hipMemcpyAsync(arg.data(), opt.d_opt_arg.p, (size_t)n_comp * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
             if (int rc = flush()) return rc;
             if (ctl[OPT_STUCK]) return fail(STCSP_E_INTERNAL, "optimise: the least mean of the component of state %u did not settle", ctl[OPT_STUCK] - 1);
             for (uint32_t c = 0; c < n_comp; c++) {
-                if (!(s_flags[c] & STCSP_SCC_CYCLIC)) continue;
+                if (!(scc.s_flags[c] & STCSP_SCC_CYCLIC)) continue;
                 const uint32_t a = arg[c];
                 if (a >= S || den[a] == 0 || comp_of[a] != c) return fail(STCSP_E_INTERNAL, "optimise: cyclic component %u has no cycle mean", c);
                 long long p = num[a], q = (long long)den[a], x = std::llabs(p), y = q;
@@ -2186,43 +2143,43 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
                     x = y;
                     y = r;
                 }
-                opt_num[c] = p / x;
-                opt_den[c] = q / x;
+                opt.opt_num[c] = p / x;
+                opt.opt_den[c] = q / x;
             }
         }
         for (uint32_t c = 0; c < n_comp; c++) {
-            if (!(s_flags[c] & STCSP_SCC_ACCEPTING)) continue;
-            if (omega_comp < 0 || (__int128)opt_num[c] * omega_den < (__int128)omega_num * opt_den[c]) {
-                omega_num = opt_num[c];
-                omega_den = opt_den[c];
+            if (!(scc.s_flags[c] & STCSP_SCC_ACCEPTING)) continue;
+            if (omega_comp < 0 || (__int128)opt.opt_num[c] * omega_den < (__int128)omega_num * opt.opt_den[c]) {
+                omega_num = opt.opt_num[c];
+                omega_den = opt.opt_den[c];
                 omega_comp = (int32_t)c;
             }
         }
     }
     if (maximise) {
-        for (int64_t &x : opt_best)
+        for (int64_t &x : opt.opt_best)
             if (x != kOptNone) x = -x;
-        for (int64_t &x : opt_state_best)
+        for (int64_t &x : opt.opt_state_best)
             if (x != kOptNone) x = -x;
-        for (int64_t &x : opt_num) x = -x;
+        for (int64_t &x : opt.opt_num) x = -x;
         omega_num = -omega_num;
     }
-    opt_wvalues.reserve(1);
-    opt_wstates.reserve(1);
-    opt_num.reserve(1);
-    opt_den.reserve(1);
+    opt.opt_wvalues.reserve(1);
+    opt.opt_wstates.reserve(1);
+    opt.opt_num.reserve(1);
+    opt.opt_den.reserve(1);
     memset(out, 0, sizeof *out);
-    out->n_states = n_live;
-    out->best = opt_best.data();
-    out->state_best = (flags & STCSP_OPT_STATE_BEST) ? opt_state_best.data() : nullptr;
+    out->n_states = post.n_live;
+    out->best = opt.opt_best.data();
+    out->state_best = (flags & STCSP_OPT_STATE_BEST) ? opt.opt_state_best.data() : nullptr;
     out->n_witnesses = n_len;
-    out->witness_off = opt_woff.data();
-    out->witness_values = opt_wvalues.data();
-    out->witness_states = opt_wstates.data();
+    out->witness_off = opt.opt_woff.data();
+    out->witness_values = opt.opt_wvalues.data();
+    out->witness_states = opt.opt_wstates.data();
     out->n_components = n_comp;
-    out->state_component = mean ? opt_component.data() : nullptr;
-    out->comp_mean_num = opt_num.data();
-    out->comp_mean_den = opt_den.data();
+    out->state_component = mean ? opt.opt_component.data() : nullptr;
+    out->comp_mean_num = opt.opt_num.data();
+    out->comp_mean_den = opt.opt_den.data();
     out->omega_mean_num = omega_num;
     out->omega_mean_den = omega_den;
     out->omega_component = omega_comp;

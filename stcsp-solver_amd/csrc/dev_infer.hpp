@@ -4,7 +4,7 @@
 // over (time x automaton) and the third member of a family: dev_generate.hpp sums the weights of all edges, dev_repair.hpp
 // takes minima of costs, this one sums over the edges that MATCH the stream's step and then sweeps forward. It runs over
 // the canonical CSR of the last generator_build() (off / eid / dstp, live states only) and the label ids of dev_repair.hpp
-// (lid / rep, built once for both calls).
+// (lid / rep, built once for both calls), one dev_repair.hpp BatchStream per stream of the batch.
 //
 // Once per generator_build(), on the first infer:
 //   k_i_rows      one lane per (label, observable variable): the representative's value, for the host to build the sorted
@@ -16,7 +16,8 @@
 //   k_i_backward  once per level r = 1 .. the longest stream of the batch, blockIdx.y = stream, one lane per state: pulls over
 //                 the segment IN ORDER, 4 B lid + 4 B dst streamed, 1 B match gathered, 8 B B_{r-1}(dst) gathered for a
 //                 matching edge, one 8 B store per state. The order of the sum is the contract, so there is no wave-wide
-//                 reduction here, not even for a long segment (k_g_weights does the same).
+//                 reduction here, not even for a long segment (k_g_weights does the same). <true>: dev_posterior.hpp's, with
+//                 one 8 B gather of w[lid] per matching edge, one multiply and one add per term.
 //   k_i_root      one lane per stream: count = B_len(root), F_0[root] = count > 0.
 //   k_i_forward   once per level t = 0 .. longest - 1, one lane per (state, stream): for s in F_t every matching edge whose
 //                 destination has weight to go marks F_{t+1}[dst] and feas[step][lid], by plain vector byte stores of the
@@ -45,14 +46,6 @@ constexpr int32_t kInfMissing = INT32_MIN;  // STCSP_INFER_MISSING
 enum { I_ERROR = 0, I_WORDS = 4 };
 enum { I_ERR_NO_EDGE = 8 };
 
-// what the kernels need to know of one stream of the batch
-struct InfStream {
-    unsigned long long table;  // first entry of its [len + 1][S] tables (B and F)
-    unsigned long long step;   // its first step among the steps of the batch
-    uint32_t len;
-    uint32_t index;            // its place in the batch: n_states of level t sits at step + index + t
-};
-
 // out: [n_labels][n_obs]
 __global__ void k_i_rows(uint32_t n_labels, const uint32_t *rep, const int32_t *values, int N, const int32_t *obs, int n_obs, int32_t *out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -80,32 +73,48 @@ __global__ void k_i_match(uint32_t n_labels, uint32_t steps, const uint32_t *rep
 }
 
 // blockIdx.y = stream of the batch
-__global__ void k_i_level0(uint32_t S, const InfStream *streams, const uint8_t *live, const uint8_t *fin, int end_final, double *B) {
+__global__ void k_i_level0(uint32_t S, const BatchStream *streams, const uint8_t *live, const uint8_t *fin, int end_final, double *B) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S) return;
     B[streams[blockIdx.y].table + s] = live[s] && (!end_final || fin[s]) ? 1.0 : 0.0;
 }
 
-// Level r: B_r(s) for every stream of the batch with len >= r. blockIdx.y = stream.
-__global__ __launch_bounds__(256) void k_i_backward(uint32_t S, uint32_t r, const InfStream *streams, const uint32_t *off, const uint32_t *lid,
-                                                    const uint32_t *dstp, uint32_t n_labels, const uint8_t *match, double *B) {
+// Level r: B_r(s) for every stream of the batch with len >= r. blockIdx.y = stream. <true, const double *> (dev_posterior.hpp)
+// takes w, [n_labels], after match: every term times w[label], terms that are not positive left out. <false> has no such argument.
+// W is a pack so that <false> keeps k_i_backward's argument list, and with it the kernarg layout and registers, of before the merge.
+template <bool WEIGHTED, typename... W>
+__global__ __launch_bounds__(256) void k_i_backward(uint32_t S, uint32_t r, const BatchStream *streams, const uint32_t *off, const uint32_t *lid,
+                                                    const uint32_t *dstp, uint32_t n_labels, const uint8_t *match, W... w, double *B) {
 #pragma clang fp contract(off)
+    static_assert(sizeof...(W) == (WEIGHTED ? 1 : 0), "k_i_backward<false> or k_i_backward<true, const double *>");
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    const InfStream st = streams[blockIdx.y];
+    const BatchStream st = streams[blockIdx.y];
     if (s >= S || r > st.len) return;
     const double *B_prev = B + st.table + (size_t)(r - 1) * S;
     const uint8_t *m = match + (st.step + (st.len - r)) * n_labels;
     double acc = 0.0;
-    for (uint32_t k = off[s], end = off[s + 1]; k < end; k++)
-        if (m[lid[k]]) acc = acc + B_prev[dstp[k]];
+    for (uint32_t k = off[s], end = off[s + 1]; k < end; k++) {
+        if constexpr (!WEIGHTED) {
+            if (m[lid[k]]) acc = acc + B_prev[dstp[k]];
+        } else {
+            const uint32_t l = lid[k];
+            if (!m[l]) continue;
+            const double wl = (w, ...)[l];
+            if (!(wl > 0.0)) continue;
+            const double b = B_prev[dstp[k]];
+            if (!(b > 0.0)) continue;
+            const double term = wl * b;
+            acc = acc + term;
+        }
+    }
     B[st.table + (size_t)r * S + s] = acc;
 }
 
 // One lane per stream of the batch: the count and F_0. A root that is not live has B == 0 on every level.
-__global__ void k_i_root(uint32_t n, const InfStream *streams, uint32_t S, const double *B, uint8_t *F, double *count) {
+__global__ void k_i_root(uint32_t n, const BatchStream *streams, uint32_t S, const double *B, uint8_t *F, double *count) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const InfStream st = streams[i];
+    const BatchStream st = streams[i];
     const double c = B[st.table + (size_t)st.len * S];
     count[i] = c;
     if (c > 0.0) F[st.table] = 1;
@@ -126,11 +135,11 @@ __device__ inline void i_segment_mark(uint32_t k, uint32_t end, uint32_t stride,
 }
 
 // Level t: F_{t+1} and the feasible labels of step t for every stream of the batch with len > t. blockIdx.y = stream.
-__global__ __launch_bounds__(256) void k_i_forward(uint32_t S, uint32_t t, const InfStream *streams, const uint32_t *off, const uint32_t *lid,
+__global__ __launch_bounds__(256) void k_i_forward(uint32_t S, uint32_t t, const BatchStream *streams, const uint32_t *off, const uint32_t *lid,
                                                    const uint32_t *dstp, uint32_t n_labels, const uint8_t *match, const double *B,
                                                    uint32_t wave_segment, uint8_t *F, uint8_t *feas) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    const InfStream st = streams[blockIdx.y];
+    const BatchStream st = streams[blockIdx.y];
     if (s >= S || t >= st.len) return;
     if (!F[st.table + (size_t)t * S + s]) return;
     const uint32_t b = off[s], end = off[s + 1];
@@ -142,10 +151,10 @@ __global__ __launch_bounds__(256) void k_i_forward(uint32_t S, uint32_t t, const
 
 // One wavefront per (long state, stream): blocks of 256 lanes take 4 long states. blockIdx.y = stream.
 __global__ __launch_bounds__(256) void k_i_forward_long(uint32_t n_long, const uint32_t *long_states, uint32_t S, uint32_t t,
-                                                        const InfStream *streams, const uint32_t *off, const uint32_t *lid, const uint32_t *dstp,
+                                                        const BatchStream *streams, const uint32_t *off, const uint32_t *lid, const uint32_t *dstp,
                                                         uint32_t n_labels, const uint8_t *match, const double *B, uint8_t *F, uint8_t *feas) {
     const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const InfStream st = streams[blockIdx.y];
+    const BatchStream st = streams[blockIdx.y];
     if (i >= n_long || t >= st.len) return;
     const uint32_t s = long_states[i];
     if (!F[st.table + (size_t)t * S + s]) return;
@@ -156,9 +165,9 @@ __global__ __launch_bounds__(256) void k_i_forward_long(uint32_t n_long, const u
 
 // |F_t| for t = 0 .. len of every stream: blockIdx.y = stream, one lane per state; n_states zeroed by the host beforehand.
 // Every lane of a wavefront stays to the end (the ballot is wave-wide); a lane past S counts nothing.
-__global__ __launch_bounds__(256) void k_i_count(uint32_t S, const InfStream *streams, const uint8_t *F, int32_t *n_states) {
+__global__ __launch_bounds__(256) void k_i_count(uint32_t S, const BatchStream *streams, const uint8_t *F, int32_t *n_states) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
-    const InfStream st = streams[blockIdx.y];
+    const BatchStream st = streams[blockIdx.y];
     const uint8_t *T = F + st.table;
     int32_t *out = n_states + st.step + st.index;
     for (uint32_t t = 0; t <= st.len; t++) {
@@ -188,13 +197,13 @@ __global__ void k_i_support(uint32_t n_labels, uint32_t steps, const uint8_t *fe
 // out: the batch's draws, [stream][draw][len][n_obs], filled with MISSING by the host beforehand; end_final zeroed.
 template <bool UNRANK>
 __global__ void k_i_walk(uint32_t n_q, uint32_t draws, unsigned long long q0, unsigned long long seed, const unsigned long long *ranks,
-                         const InfStream *streams, uint32_t S, const double *B, const uint32_t *off, const uint32_t *lid, const uint32_t *dstp,
+                         const BatchStream *streams, uint32_t S, const double *B, const uint32_t *off, const uint32_t *lid, const uint32_t *dstp,
                          const uint32_t *eid, uint32_t n_labels, const uint8_t *match, const int32_t *values, int N, const int32_t *obs, int n_obs,
                          const uint8_t *fin, int32_t *out, uint8_t *end_final, uint32_t *ctl) {
 #pragma clang fp contract(off)
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n_q) return;
-    const InfStream st = streams[q / draws];
+    const BatchStream st = streams[q / draws];
     const double *T = B + st.table;
     if (!(T[(size_t)st.len * S] > 0.0)) return;  // infeasible: rows of MISSING, end_final 0
     int32_t *rows = out + (st.step * draws + (size_t)(q % draws) * st.len) * n_obs;

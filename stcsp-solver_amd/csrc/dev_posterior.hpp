@@ -6,15 +6,13 @@
 // a forward sweep of uint64 (exact streams only: every quantity is an integer below 2^53, so integer atomics in any order
 // give the one answer), and a scatter of the per-edge products A * w * B into per-(step, variable, value) bins. It runs
 // over the canonical CSR of the last generator_build(), the label ids of dev_repair.hpp and the dictionaries of
-// dev_infer.hpp; k_i_match, k_i_rows, InfStream and the long-state list are used as they are.
+// dev_infer.hpp. From dev_infer.hpp it takes k_i_match, k_i_rows, k_i_level0 and k_i_backward<true, const double *> as they are, from
+// dev_repair.hpp BatchStream and the long-state list.
 //
 // Per call:
 //   k_p_label_weight  one lane per label: w(l) = the product, in variable order, of the weights of its dictionary entries.
 // Per batch of streams:
-//   k_i_match         (dev_infer.hpp)
-//   k_p_level0        B_0.
-//   k_p_backward      once per level r, blockIdx.y = stream, one lane per state: k_i_backward with one 8 B gather of w[lid]
-//                     per matching edge, one multiply and one add per term, in canonical order.
+//   k_i_match, k_i_level0, k_i_backward<true, ...>  (dev_infer.hpp) the weighted B, in canonical order.
 //   k_p_root          one lane per stream: mass, exact, A_0[root] = 1 for an exact feasible stream.
 //   k_p_forward_long  one wavefront per (long state, stream), lanes stride the segment; launched BEFORE
 //   k_p_forward       of the same level: one lane per (state, stream) with A_t > 0. Per feasible edge one 64-bit atomicAdd
@@ -48,41 +46,11 @@ __global__ void k_p_label_weight(uint32_t n_labels, const uint32_t *vidx, const 
     w[l] = acc;
 }
 
-// blockIdx.y = stream of the batch
-__global__ void k_p_level0(uint32_t S, const InfStream *streams, const uint8_t *live, const uint8_t *fin, int end_final, double *B) {
-    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= S) return;
-    B[streams[blockIdx.y].table + s] = live[s] && (!end_final || fin[s]) ? 1.0 : 0.0;
-}
-
-// Level r: B_r(s) for every stream of the batch with len >= r. blockIdx.y = stream.
-__global__ __launch_bounds__(256) void k_p_backward(uint32_t S, uint32_t r, const InfStream *streams, const uint32_t *off, const uint32_t *lid,
-                                                    const uint32_t *dstp, uint32_t n_labels, const uint8_t *match, const double *w, double *B) {
-#pragma clang fp contract(off)
-    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    const InfStream st = streams[blockIdx.y];
-    if (s >= S || r > st.len) return;
-    const double *B_prev = B + st.table + (size_t)(r - 1) * S;
-    const uint8_t *m = match + (st.step + (st.len - r)) * n_labels;
-    double acc = 0.0;
-    for (uint32_t k = off[s], end = off[s + 1]; k < end; k++) {
-        const uint32_t l = lid[k];
-        if (!m[l]) continue;
-        const double wl = w[l];
-        if (!(wl > 0.0)) continue;
-        const double b = B_prev[dstp[k]];
-        if (!(b > 0.0)) continue;
-        const double term = wl * b;
-        acc = acc + term;
-    }
-    B[st.table + (size_t)r * S + s] = acc;
-}
-
 // One lane per stream of the batch. A: [stream][2][S], zeroed by the host beforehand.
-__global__ void k_p_root(uint32_t n, const InfStream *streams, uint32_t S, const double *B, p_u64 *A, double *mass, uint8_t *exact) {
+__global__ void k_p_root(uint32_t n, const BatchStream *streams, uint32_t S, const double *B, p_u64 *A, double *mass, uint8_t *exact) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const InfStream st = streams[i];
+    const BatchStream st = streams[i];
     const double c = B[st.table + (size_t)st.len * S];
     const bool ex = c < 0x1.0p53;
     mass[i] = c;
@@ -110,11 +78,11 @@ __device__ inline void p_segment_add(uint32_t k, uint32_t end, uint32_t stride, 
 
 // Level t: A_{t+1} and the per-label masses of step t for every stream of the batch with len > t. blockIdx.y = stream.
 // Launched after k_p_forward_long of the level: it clears A_t(s) for every state, which is then level t + 1's target.
-__global__ __launch_bounds__(256) void k_p_forward(uint32_t S, uint32_t t, const InfStream *streams, const uint32_t *off, const uint32_t *lid,
+__global__ __launch_bounds__(256) void k_p_forward(uint32_t S, uint32_t t, const BatchStream *streams, const uint32_t *off, const uint32_t *lid,
                                                    const uint32_t *dstp, uint32_t n_labels, const uint8_t *match, const double *w, const double *B,
                                                    uint32_t wave_segment, p_u64 *A, p_u64 *lab) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    const InfStream st = streams[blockIdx.y];
+    const BatchStream st = streams[blockIdx.y];
     if (s >= S || t >= st.len) return;
     p_u64 *A_cur = A + ((size_t)st.index * 2 + (t & 1)) * S;
     const p_u64 a = A_cur[s];
@@ -130,11 +98,11 @@ __global__ __launch_bounds__(256) void k_p_forward(uint32_t S, uint32_t t, const
 // One wavefront per (long state, stream): blocks of 256 lanes take 4 long states. blockIdx.y = stream. Integer sums have no
 // order, so the lanes may stride the segment. Reads A_t only: k_p_forward clears it afterwards.
 __global__ __launch_bounds__(256) void k_p_forward_long(uint32_t n_long, const uint32_t *long_states, uint32_t S, uint32_t t,
-                                                        const InfStream *streams, const uint32_t *off, const uint32_t *lid, const uint32_t *dstp,
+                                                        const BatchStream *streams, const uint32_t *off, const uint32_t *lid, const uint32_t *dstp,
                                                         uint32_t n_labels, const uint8_t *match, const double *w, const double *B, p_u64 *A,
                                                         p_u64 *lab) {
     const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const InfStream st = streams[blockIdx.y];
+    const BatchStream st = streams[blockIdx.y];
     if (i >= n_long || t >= st.len) return;
     const uint32_t s = long_states[i];
     const p_u64 a = A[((size_t)st.index * 2 + (t & 1)) * S + s];
@@ -146,9 +114,9 @@ __global__ __launch_bounds__(256) void k_p_forward_long(uint32_t n_long, const u
 
 // final_mass[stream] = the sum of A_len(s) over the final states: blockIdx.y = stream, one lane per state; final_mass zeroed
 // by the host beforehand. Every lane of a wavefront stays to the end (the shuffles are wave-wide).
-__global__ __launch_bounds__(256) void k_p_final(uint32_t S, const InfStream *streams, const uint8_t *fin, const p_u64 *A, p_u64 *final_mass) {
+__global__ __launch_bounds__(256) void k_p_final(uint32_t S, const BatchStream *streams, const uint8_t *fin, const p_u64 *A, p_u64 *final_mass) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
-    const InfStream st = streams[blockIdx.y];
+    const BatchStream st = streams[blockIdx.y];
     p_u64 x = s < S && fin[s] ? A[((size_t)st.index * 2 + (st.len & 1)) * S + s] : 0;
     for (int d = 32; d; d >>= 1) x += __shfl_xor(x, d, 64);
     if (lane == 0 && x) atomicAdd(&final_mass[blockIdx.y], x);

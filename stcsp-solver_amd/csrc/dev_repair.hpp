@@ -42,12 +42,12 @@ constexpr uint32_t kRepWaveSegment = 128;
 enum { R_LABELS = 0, R_LONG = 1, R_ERROR = 2, R_WORDS = 4 };
 enum { R_ERR_TABLE_FULL = 1, R_ERR_NO_EDGE = 8 };
 
-// what the kernels need to know of one stream of the batch
-struct RepStream {
-    unsigned long long table;  // first word of its [len + 1][S] table
+// what the kernels of repair, inference and posterior need to know of one stream of the batch
+struct BatchStream {
+    unsigned long long table;  // first entry of its [len + 1][S] tables
     unsigned long long step;   // its first step among the steps of the batch
     uint32_t len;
-    uint32_t pad;
+    uint32_t index;            // its place in the batch
 };
 
 __global__ void k_r_labels(uint32_t total, const uint32_t *eid, const int32_t *values, int N, const int32_t *obs, int n_obs, uint32_t *table,
@@ -117,7 +117,7 @@ __global__ void k_r_cost(uint32_t n_labels, uint32_t steps, const uint32_t *rep,
 }
 
 // blockIdx.y = stream of the batch
-__global__ void k_r_level0(uint32_t S, const RepStream *streams, const uint8_t *live, const uint8_t *fin, int end_final, uint32_t *G) {
+__global__ void k_r_level0(uint32_t S, const BatchStream *streams, const uint8_t *live, const uint8_t *fin, int end_final, uint32_t *G) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S) return;
     G[streams[blockIdx.y].table + s] = live[s] && (!end_final || fin[s]) ? 0u : kRepInf;
@@ -137,11 +137,11 @@ __device__ inline uint32_t r_segment_min(uint32_t k, uint32_t end, uint32_t stri
 }
 
 // Level r: G_r(s) for every stream of the batch with len >= r. blockIdx.y = stream.
-__global__ __launch_bounds__(256) void k_r_relax(uint32_t S, uint32_t r, const RepStream *streams, const uint32_t *off, const uint32_t *lid,
+__global__ __launch_bounds__(256) void k_r_relax(uint32_t S, uint32_t r, const BatchStream *streams, const uint32_t *off, const uint32_t *lid,
                                                  const uint32_t *dstp, uint32_t n_labels, const uint32_t *cost, uint32_t wave_segment,
                                                  uint32_t *G) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    const RepStream st = streams[blockIdx.y];
+    const BatchStream st = streams[blockIdx.y];
     if (s >= S || r > st.len) return;
     const uint32_t b = off[s], end = off[s + 1];
     if (end - b > wave_segment) return;  // k_r_relax_long's
@@ -152,10 +152,10 @@ __global__ __launch_bounds__(256) void k_r_relax(uint32_t S, uint32_t r, const R
 
 // One wavefront per (long state, stream): blocks of 256 lanes take 4 long states. blockIdx.y = stream.
 __global__ __launch_bounds__(256) void k_r_relax_long(uint32_t n_long, const uint32_t *long_states, uint32_t S, uint32_t r,
-                                                      const RepStream *streams, const uint32_t *off, const uint32_t *lid, const uint32_t *dstp,
+                                                      const BatchStream *streams, const uint32_t *off, const uint32_t *lid, const uint32_t *dstp,
                                                       uint32_t n_labels, const uint32_t *cost, uint32_t *G) {
     const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const RepStream st = streams[blockIdx.y];
+    const BatchStream st = streams[blockIdx.y];
     if (i >= n_long || r > st.len) return;  // (wave-uniform)
     const uint32_t s = long_states[i];
     const uint32_t *G_prev = G + st.table + (size_t)(r - 1) * S;
@@ -169,13 +169,13 @@ __global__ __launch_bounds__(256) void k_r_relax_long(uint32_t n_long, const uin
 }
 
 // One lane per stream of the batch. rows / out: [steps of the batch][n_obs], out zeroed by the host beforehand.
-__global__ void k_r_walk(uint32_t n, const RepStream *streams, uint32_t S, const uint32_t *G, const uint32_t *off, const uint32_t *lid,
+__global__ void k_r_walk(uint32_t n, const BatchStream *streams, uint32_t S, const uint32_t *G, const uint32_t *off, const uint32_t *lid,
                          const uint32_t *dstp, const uint32_t *eid, uint32_t n_labels, const uint32_t *cost, const int32_t *values, int N,
                          const int32_t *obs, int n_obs, const uint8_t *fin, const int32_t *rows, int32_t *out, int32_t *distance,
                          uint8_t *end_final, int32_t *n_changed, uint32_t *ctl) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const RepStream st = streams[i];
+    const BatchStream st = streams[i];
     const uint32_t *T = G + st.table;
     const uint32_t total = T[(size_t)st.len * S];  // G_len(root)
     if (total == kRepInf) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <vector>
 
 #include "stcsp_engine.h"
@@ -54,6 +55,16 @@ hipError_t reserve_all(size_t count, size_t tail, Bufs &...bufs) {
     return e;
 }
 
+// reserve_or_release(count) for every (buffer, count) pair, or for none: false with every buffer of the list released, those
+// behind the one that failed too. ok: none has failed so far (true from outside)
+template <typename T, typename... Rest>
+bool reserve_or_release_all(bool ok, DevBuf<T> &buf, size_t count, Rest &&...rest) {
+    ok = ok && buf.reserve_or_release(count);
+    if constexpr (sizeof...(rest) > 0) ok = reserve_or_release_all(ok, rest...);
+    if (!ok) buf.release();
+    return ok;
+}
+
 // hipEvent_t's created on first use and destroyed with their owner
 struct DevEvents {
     hipEvent_t ev[8] = {};
@@ -68,6 +79,18 @@ struct DevEvents {
         return e;
     }
     hipEvent_t operator[](int i) const { return ev[i]; }
+    hipError_t mark(int k, hipStream_t stream) { return hipEventRecord(ev[k], stream); }
+    // after the synchronise: *into[i] += the seconds from mark first + i to mark first + i + 1
+    hipError_t add_spans(int first, std::initializer_list<double *> into) {
+        hipError_t e = hipSuccess;
+        for (double *seconds : into) {
+            float ms = 0;
+            if ((e = hipEventElapsedTime(&ms, ev[first], ev[first + 1])) != hipSuccess) break;
+            *seconds += ms * 1e-3;
+            first++;
+        }
+        return e;
+    }
 };
 
 }  // namespace stcsp

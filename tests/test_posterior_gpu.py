@@ -131,6 +131,25 @@ def test_live_state_counts_around_a_wavefront_a_block_and_a_grid_row(stcsp, RefO
         assert dev[5][3][20][c0] == ([(20, 2 ** 40)] if ws is None else []) and len(dev[4][3][7][c0]) == 1
 
 
+def test_unweighted_backward_is_infers_backward_on_the_device(stcsp):
+    """The two instantiations of k_i_backward on one generator build: without weights every label weighs 1.0, so the weighted
+    sweep must leave the bits of the unweighted one's counts, and the values of non-zero mass are infer's supports. The row of
+    65 states is two wavefronts of lanes; streams of 0, 1 and 7 steps, which stay among the first states, and one of 70 steps,
+    whose count at the root comes through state 64, the one lane of the second wavefront, where it loops. About 30 % of the
+    entries are unobserved; x is free, so every count is a power of two far below 2^53."""
+    m = stcsp.Model(text=counter(65))
+    e, r, post, host = solved(stcsp, m)
+    e.generator("all", 0)
+    path = host.repair_streams([np.full((70, m.n_vars), X, np.int32)], "all")[1][0]
+    streams = blanked([path[:0], path[:1], path[:7], path], 0.3, 65)
+    mass, exact, fmass, marginals = e.posterior_streams(streams, weights=None)
+    count, supports = e.infer_streams(streams)[:2]
+    assert mass.view(np.uint64).tolist() == count.view(np.uint64).tolist()
+    assert exact.tolist() == [1, 1, 1, 1] and (mass > 0).all()
+    for i in range(len(streams)):
+        assert [[[value for value, _ in pairs] for pairs in step] for step in marginals[i]] == supports[i]
+
+
 @pytest.mark.parametrize("n", [1, 257])
 def test_stream_counts(stcsp, n):
     """1 stream, and 257: blockIdx.y of every per-(state, stream) kernel, a second block of k_p_root."""

@@ -54,7 +54,7 @@ for name in args or ["partialorder_14", "digitinvader9"]:
               f"{res.table_bytes / 1e6:.1f} MB, wave segment {os.environ.get('STCSP_REPAIR_WAVE_SEGMENT', 'default')}, median log2 mass "
               f"{np.median(np.log2(dev[0])):.1f}", flush=True)
         print(f"    posterior {total * 1e3:.2f} ms (first call, with label ids and dictionaries: {first * 1e3:.2f} ms): k_p_label_weight + k_i_match "
-              f"{wts * 1e3:.3f} ms, k_p_level0 + k_p_backward + k_p_root {back * 1e3:.3f} ms = {STREAMS * STEPS * info.n_edges / back / 1e9:.2f} G edge visits/s, "
+              f"{wts * 1e3:.3f} ms, k_i_level0 + k_i_backward<true> + k_p_root {back * 1e3:.3f} ms = {STREAMS * STEPS * info.n_edges / back / 1e9:.2f} G edge visits/s, "
               f"k_p_forward(_long) + k_p_final {fwd * 1e3:.3f} ms, k_p_bins {bins * 1e3:.3f} ms", flush=True)
         print(f"    the same request through stcsp_engine_infer (no draws): {statistics.median(infer) * 1e3:.2f} ms = {statistics.median(infer) / total:.2f} x the "
               f"posterior call", flush=True)
