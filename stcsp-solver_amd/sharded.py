@@ -26,6 +26,7 @@ uses tensor collectives too.  PyTorch is used for device buffers and the process
 from __future__ import annotations
 
 import ctypes as C
+import zlib
 
 import numpy as np
 import torch
@@ -161,13 +162,17 @@ def solve_sharded(engine, rank: int, world: int, device: torch.device, stage_thr
 
     guarded(engine.set_expand_budget, budget_rounds if world > 1 else 0, share_per_rank * world)
     guarded(engine.begin)
-    # every shard starts from the same registry (the model's own sets, plus whatever earlier solves
-    # on these engines exchanged), so the definitions only travel once somebody's count moves
-    last_sets = [guarded(engine.sets_count) or 0] * world
+    # The set definitions travel when somebody's count moves. Whether they travel is decided from the all-gathered table
+    # alone, so that every rank takes the same branch: the shards need not start from the same registry (an engine that
+    # translates sets ahead of need knows more of them than a peer that does not, and earlier solves leave what they
+    # exchanged), so in the first superstep the ranks compare (count, blob length, blob checksum) with rank 0's instead of
+    # each with a count of its own -- a rank that found the table equal to its own start while a peer did not would sit
+    # in the next collective alone.
+    last_sets = None
     rounds = 0
     moved = received = 0
     keep = None
-    W = world + 4  # per-rank row of the meta table: candidates per peer, open nodes, set count, set blob length, status
+    W = world + 5  # per-rank row of the meta table: candidates per peer, open nodes, set count, set blob length, status, blob checksum
     while True:
         rounds += 1
         if rounds > max_rounds and pending is None:
@@ -175,11 +180,13 @@ def solve_sharded(engine, rank: int, world: int, device: torch.device, stage_thr
         left = guarded(engine.expand_local)
         outs = [guarded(engine.outbox, p) for p in range(world)]  # (ptr, record count) per peer
         n_sets = guarded(engine.sets_count)
-        blob_len = guarded(lambda: len(engine.sets_blob()))
+        blob = guarded(engine.sets_blob) if last_sets is None else None
+        blob_len = len(blob) if blob is not None else guarded(lambda: len(engine.sets_blob()))
+        blob_sum = zlib.crc32(np.asarray(blob, dtype=np.int32).tobytes()) if blob is not None else 0
         if pending is not None:
-            row = [0] * world + [0, 0, 0, 1]
+            row = [0] * world + [0, 0, 0, 1, 0]
         else:
-            row = [c for _, c in outs] + [left, n_sets, blob_len, 0]
+            row = [c for _, c in outs] + [left, n_sets, blob_len, 0, blob_sum]
         t0 = time.perf_counter()
         meta = torch.tensor(row, dtype=torch.int64, device=comm_dev)
         gathered = torch.empty(world * W, dtype=torch.int64, device=comm_dev)
@@ -193,6 +200,9 @@ def solve_sharded(engine, rank: int, world: int, device: torch.device, stage_thr
                 raise ShardedSolveError(f"rank {rank}: engine failed in superstep {rounds}: {pending}") from pending
             raise ShardedSolveError(f"rank {rank}: rank(s) {bad} failed in superstep {rounds}")
         sets_now = [m[world + 1] for m in allmeta]
+        if last_sets is None:  # first superstep: do the registries differ anywhere?
+            same = all((m[world + 1], m[world + 2], m[world + 4]) == (allmeta[0][world + 1], allmeta[0][world + 2], allmeta[0][world + 4]) for m in allmeta)
+            last_sets = sets_now if same else [-1] * world
         if sets_now != last_sets:  # somebody met a new constraint set: everyone learns all of them
             t0 = time.perf_counter()
             err = None

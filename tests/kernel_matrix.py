@@ -302,7 +302,7 @@ for name, (dr, form, kr, cs), text, K, words, key in BIG_SCOPE:
 
 
 ROW = {r.name: r for r in ROWS}
-# one row per commit kernel (none with interval domains: run_local passes its own flags)
+# one row per commit kernel
 COMMIT_ROWS = ["variant_dr1_l1_cs0_lite1", "variant_dr2_l1_cs0_lite1", "variant_dr4_l1_cs0_lite1", "block8_cs", "long_key_w2", "block8_plain_kr2",
                "until_dr4_plain_kr1", "until_dr4_w2_kr2", "until_dr8_cs_kr1", "until_dr8_plain_kr2"]
 # one row per family and DR for the run with small pools and 64-node batches (records of every stride)

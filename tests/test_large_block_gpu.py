@@ -103,18 +103,24 @@ def test_large_block_same_engine_twice(stcsp, RefOracle):
 
 
 @pytest.mark.parametrize("name", ["bools250", "ring100", "w4_walk"])
-def test_large_blocks_two_shards(stcsp, RefOracle, name):
-    """Candidate records and transfer records of 2-KB blocks through k_commit<8, KR>, k_donate / k_adopt and LocalGroup."""
-    from test_native_sharded_gpu import run_local
-    m = stcsp.Model(text=MODELS[name])
+def test_large_blocks_two_shards(stcsp, RefOracle, monkeypatch, name):
+    """Candidate records and transfer records of 2-KB blocks through k_commit<8, KR>, k_donate / k_adopt and LocalGroup. The
+    ring's search holds one open node at a time (on the scalar model two shards donate nothing), so every model gets four free
+    booleans (still at most 512 words), the shards share from the first round on and expand once per slot and round: open
+    nodes really move."""
+    from mixed_rows import free_booleans
+    from test_native_sharded_gpu import SHARE, one_expansion_per_round, run_local
+    m = stcsp.Model(text=MODELS[name] + free_booleans(4))
+    assert 256 < block_words(m) <= 512
     o = RefOracle(m)
     ro = o.solve()
     ao, _ = finish(o, ro)
-    a, merged, stats, nodes, engines, g = run_local(stcsp, m, 2)
+    one_expansion_per_round(monkeypatch)
+    a, merged, stats, nodes, engines, g = run_local(stcsp, m, 2, knobs=SHARE)
     assert a.canonical() == ao.canonical()
     assert merged.counters.dominance == ro.counters.dominance
     assert sum(s["candidates_sent"] for s in stats) == sum(s["candidates_received"] for s in stats) > 0
-    assert sum(s["nodes_donated"] for s in stats) == sum(s["nodes_adopted"] for s in stats)
+    assert sum(s["nodes_donated"] for s in stats) == sum(s["nodes_adopted"] for s in stats) > 0
 
 
 @pytest.mark.parametrize("name", ["bools140", "ring100"])

@@ -20,13 +20,14 @@ def free_port():
     return p
 
 
-def launch(world, name, kind, tmp_path, timeout=300, env=None):
+def launch(world, name, kind, tmp_path, timeout=300, env=None, prefix_k=None):
     import os
     port = free_port()
     out = tmp_path / "merged.json"
+    extra = [] if prefix_k is None else [str(prefix_k)]
     procs = [subprocess.Popen([sys.executable, str(REPO / "tests" / "_sharded_worker.py"), str(r), str(world), str(port),
-                               name, kind, str(out)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
-                              env=dict(os.environ, **(env or {})))
+                               name, kind, str(out), *extra], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                              env=dict(os.environ, STCSP_TEST_STACKS_AFTER=str(timeout * 5 // 6), **(env or {})))
              for r in range(world)]
     logs = []
     for p in procs:
@@ -35,7 +36,8 @@ def launch(world, name, kind, tmp_path, timeout=300, env=None):
         except subprocess.TimeoutExpired:
             for q in procs:
                 q.kill()
-            raise
+            tails = [q.communicate()[0][-4000:] for q in procs]  # what every rank wrote, its stacks at 5/6 of the limit included
+            raise AssertionError(f"{kind} run of {name} did not end in {timeout} s; the ranks wrote:\n" + "\n----\n".join(tails)) from None
         logs.append(o)
     assert all(p.returncode == 0 for p in procs), "\n".join(logs)
     return json.loads(out.read_text())
