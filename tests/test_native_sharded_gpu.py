@@ -7,14 +7,13 @@ donated is adopted, and a failing rank ends every rank.
 Below them the record shapes the scalar frontier model cannot take (wide and interval domains, more than 32 until constraints,
 big scopes): redistribution between engines that really moves nodes, and the donate / adopt round-trip law with a plain Python
 decoder of the transfer record (tests/xfer_ref.py)."""
-import ctypes as C
 import importlib
 from collections import namedtuple
 
-import numpy as np
 import pytest
 
 from conftest import finish
+from node_seam import DeviceWords, one_expansion_per_round  # (they moved to the node-level seam, which shares them)
 
 pytestmark = pytest.mark.gpu
 
@@ -194,12 +193,6 @@ def oracle_of(stcsp, RefOracle, name):
     return _oracle[name]
 
 
-def one_expansion_per_round(monkeypatch):
-    """One expansion per slot and round: the frontier is wide when expand_local hands control back (test_many_until_sharded)."""
-    monkeypatch.setenv("STCSP_CHAIN_SMALL", "1")
-    monkeypatch.setenv("STCSP_CHAIN_BIG", "1")
-
-
 @pytest.mark.parametrize("world", [2, 3])
 @pytest.mark.parametrize("name", list(ENGINE_ROWS))
 def test_native_sharded_moves_nodes_of_every_stride(stcsp, RefOracle, monkeypatch, name, world):
@@ -219,43 +212,6 @@ def test_native_sharded_moves_nodes_of_every_stride(stcsp, RefOracle, monkeypatc
     for e in engines:
         e.close()
     g.close()
-
-
-class DeviceWords:
-    """A device buffer of the test's own (the engine's runtime, reached through the engine library: no second runtime in the
-    process). The engine reads adopted and committed records after the call returns, so they must not stay in the buffers
-    the engine reuses; `load` copies them here. `load` may free and replace the buffer, which is safe only because every call
-    of it comes after an engine call that waits for the engine's stream -- donate(), outbox() and expand_local() all
-    synchronise before they return (engine.hip), so no adopt or commit kernel is still reading the old buffer."""
-    D2H, D2D = 2, 3  # hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice (hip_runtime_api.h: enum hipMemcpyKind)
-
-    def __init__(self, lib):
-        self.lib, self.ptr, self.cap = lib, None, 0
-        lib.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        lib.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        lib.hipFree.argtypes = [C.c_void_p]
-
-    def load(self, src: int, n_words: int):
-        if n_words > self.cap:
-            self.free()
-            p = C.c_void_p()
-            assert self.lib.hipMalloc(C.byref(p), n_words * 2 * 4) == 0
-            self.ptr, self.cap = p.value, n_words * 2
-        if n_words:
-            assert self.lib.hipMemcpy(self.ptr, src, n_words * 4, self.D2D) == 0
-        self.n = n_words
-        return self.ptr or 0
-
-    def host(self):
-        out = np.zeros(self.n, dtype=np.uint32)
-        if self.n:
-            assert self.lib.hipMemcpy(out.ctypes.data, self.ptr, self.n * 4, self.D2H) == 0
-        return out
-
-    def free(self):
-        if self.ptr:
-            assert self.lib.hipFree(self.ptr) == 0
-        self.ptr, self.cap = None, 0
 
 
 def stepped_to_the_end(e, cands, on_open=None):
