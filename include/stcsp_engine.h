@@ -488,6 +488,102 @@ typedef struct stcsp_repair_result {
 
 int stcsp_engine_repair(stcsp_engine *engine, const stcsp_repair_request *request, stcsp_repair_result *result);
 
+/* ---- aligning observed streams: repair with dropped and spurious steps, on the device (no reference counterpart) ----
+ * The repair keeps step t of the stream at step t of the solution. A recorder that loses a sample or records one twice
+ * shifts every later step; this is the weighted edit distance between a stream and the solution language, with the
+ * aligned solution prefix. Live automaton, projected label, default mask, canonical order of a state's live out-edges,
+ * STCSP_REPAIR_MISSING and the step cost c_t(e) are exactly those of stcsp_engine_repair().
+ *
+ * Input. Streams in the monitor's format; weights[n_observable] (int32, each >= 0; NULL = all 1); skip_cost (int32 >= 1),
+ * the price of dropping one observed step as spurious; gap_cost (int32 >= 1), the price of one solution step the
+ * recorder missed; flags.
+ *
+ * Cost to go, for a stream x_0 .. x_{m-1}: G[t][s], with t steps consumed in the live state s; uint32, infinity is
+ * 0xffffffff, infinite terms stay out of every minimum.
+ *   base(s)  = 0 for a live state (with STCSP_ALIGN_END_FINAL: 0 if final[s], else infinity).
+ *   G[m][s]  = the least fixpoint of G = min(base(s), gap_cost + min over the live out-edges e of s of G[dst(e)]):
+ *              base without END_FINAL, gap_cost times the edge distance from s to a final state with it.
+ *   B[t][s]  = min(skip_cost + G[t+1][s], min over e of c_t(e) + G[t+1][dst(e)])                      for t < m,
+ *   G[t][s]  = the least fixpoint of G = min(B[t][s], gap_cost + min over e of G[dst(e)]).
+ * The fixpoint is unique because gap_cost >= 1, so every relaxation order reaches it. A request with
+ *   max(the sum of the weights, skip_cost) * (the longest len) + gap_cost * n_states > 2^31 - 2
+ * (n_states counts every state of the automaton, live or not) is STCSP_E_INVALID; under that bound no finite value, those
+ * in the middle of a relaxation included, reaches infinity.
+ *
+ * Answer per stream i.
+ *   distance[i]  G[0][root] as int32; -1 if it is infinite or the root is not live. That is no error: the stream's other
+ *                outputs are then 0 or empty.
+ *   The walk starts at (t, s) = (0, root) and takes the FIRST rule that applies:
+ *     1. t == m and G[m][s] == base(s): stop.
+ *     2. match (t < m): the first live out-edge in canonical order with c_t(e) + G[t+1][dst] == G[t][s]: its projected row
+ *        is emitted, op M, go to (t + 1, dst).
+ *     3. skip (t < m): skip_cost + G[t+1][s] == G[t][s]: op D, go to (t + 1, s).
+ *     4. insert: the first live out-edge in canonical order with gap_cost + G[t][dst] == G[t][s]: its row is emitted,
+ *        op I, go to (t, dst).
+ *   An insert strictly lowers G within a level, so the walk ends.
+ *   out_offsets [n_streams + 1], values: the emitted rows of stream i are the rows out_offsets[i] .. out_offsets[i + 1].
+ *   op_offsets [n_streams + 1], ops: uint8, 0 = M, 1 = D, 2 = I, in the order of the walk.
+ *   n_changed[i]   the (step, variable) positions of MATCHED steps that were observed and whose emitted value differs.
+ *   n_skipped[i], n_inserted[i]   the D and the I ops.  end_final[i]   final[the last s].
+ * Everything is integer arithmetic, and no output depends on a state number or on scheduling: the device, the host twin
+ * (stcsp_automaton_align_streams() of stcsp_host.h) and any implementation of this text agree exactly.
+ *
+ * Consequences. #M + #D == len and #M + #I == the number of emitted rows. distance == the matched steps' costs +
+ * skip_cost * n_skipped + gap_cost * n_inserted. Every emitted prefix is accepted whole by the monitor under the same
+ * mask. With every weight > 0, no MISSING entry and without END_FINAL, distance == 0 exactly when the monitor accepts the
+ * stream whole. With skip_cost = gap_cost = d + 1, d the stream's finite repair distance, distance, rows, n_changed and
+ * end_final are the repair's and every op is M. With END_FINAL a stream of length 0 yields a shortest path from the root
+ * to a final state. One step deleted from a solution prefix: distance <= gap_cost; one duplicated: distance <= skip_cost.
+ *
+ * align() needs a valid stcsp_engine_generator_build(); without one: STCSP_E_STATE; on a sharded engine
+ * STCSP_E_UNSUPPORTED (the host twin takes the merged automaton). Malformed offsets, a negative weight, a cost below 1
+ * and the bound: STCSP_E_INVALID. Label ids, costs per (step, label), the table [stream][len + 1][n_states] of uint32,
+ * the batches and STCSP_E_NOMEM are the repair's; the byte budget is STCSP_ALIGN_BYTES. Two roads fill the table with the
+ * same values (path_kernel): the fused kernel, one workgroup per stream with two rows in LDS and every level in one
+ * launch, when n_states <= 20,352 (160 KiB of LDS less 1 KiB, 8 bytes per state); else one launch per level and per
+ * closure sweep, the host reading a changed word through pinned memory once per group of sweeps. STCSP_ALIGN_FUSED=0
+ * forces the second road; STCSP_ALIGN_FUSED_STATES lowers the capacity of the first (tests). STCSP_REPAIR_WAVE_SEGMENT
+ * applies as in the repair. Results are owned by the engine until the next call on it. The call invalidates no other
+ * structure and builds none that a later call relies on: its device buffers and one small pinned block are scratch that the
+ * engine keeps for reuse until it is destroyed. */
+#define STCSP_ALIGN_END_FINAL 1 /* the aligned prefix must end in a final state */
+
+typedef struct stcsp_align_request {
+    int64_t n_streams;
+    const int64_t *offsets; /* [n_streams + 1] in steps, as for the repair         */
+    const int32_t *values;  /* [offsets[n_streams] * n_observable]                 */
+    const int32_t *weights; /* [n_observable], each >= 0; NULL = all 1             */
+    int32_t skip_cost;      /* >= 1                                                */
+    int32_t gap_cost;       /* >= 1                                                */
+    int32_t flags;          /* STCSP_ALIGN_*                                       */
+    int32_t reserved;
+} stcsp_align_request;
+
+typedef struct stcsp_align_result {
+    int64_t n_streams;
+    const int32_t *distance;    /* [n_streams] owned by the engine, valid until the next call on it */
+    const int64_t *out_offsets; /* [n_streams + 1] in rows                                          */
+    const int32_t *values;      /* [out_offsets[n_streams] * n_observable] the emitted rows         */
+    const int64_t *op_offsets;  /* [n_streams + 1]                                                  */
+    const uint8_t *ops;         /* [op_offsets[n_streams]] 0 = M, 1 = D, 2 = I                      */
+    const int32_t *n_changed;   /* [n_streams]                                                      */
+    const int32_t *n_skipped;   /* [n_streams]                                                      */
+    const int32_t *n_inserted;  /* [n_streams]                                                      */
+    const uint8_t *end_final;   /* [n_streams]                                                      */
+    int64_t n_labels;           /* distinct projected labels of the live automaton                  */
+    int64_t table_bytes;        /* HBM of the largest batch: tables and costs                       */
+    int32_t n_batches;
+    int32_t n_observable;
+    int32_t path_kernel;        /* 0 = no batch ran, 1 = fused, 2 = general                         */
+    int32_t reserved;
+    double seconds;             /* wall time from the host input to the host output                 */
+    double seconds_levels;      /* HIP-event time of the levels (either road), all batches          */
+    double seconds_walk;        /* HIP-event time of the walk kernel, all batches                   */
+    double seconds_cost;        /* HIP-event time of the cost kernel, all batches                   */
+} stcsp_align_result;
+
+int stcsp_engine_align(stcsp_engine *engine, const stcsp_align_request *request, stcsp_align_result *result);
+
 /* ---- inferring the unobserved entries of a stream: supports, counts, draws, on the device (no reference counterpart) ----
  * The monitor says whether a stream is a prefix of a solution, the generator gives some solution, the repair the nearest
  * one. This says, for a PARTIALLY observed stream, what the entries that were not seen can be and how many solutions

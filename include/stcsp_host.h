@@ -151,6 +151,18 @@ int stcsp_automaton_repair_streams(const stcsp_automaton *a, const uint8_t *obse
                                    const int64_t *offsets, const int32_t *values, int32_t *distance, int32_t *out_values, uint8_t *end_final,
                                    int32_t *n_changed);
 
+/* ---- aligning observed streams: dropped and spurious steps (definition: stcsp_engine.h, stcsp_engine_align) ----
+ * The same contract written plainly, on the automaton's current flags: the checker of the device pass in the tests, and
+ * the path for automata whose flags live on the host (sharded runs, host adversarial passes, read_binary). observable,
+ * weights, offsets / values: as for stcsp_automaton_repair_streams(); flags: STCSP_ALIGN_*; skip_cost, gap_cost >= 1.
+ * distance, end_final, n_changed, n_skipped, n_inserted: [n_streams]; out_offsets, op_offsets: [n_streams + 1], in rows
+ * and in ops; *out_values and *ops receive the emitted rows and the ops, each in one block the caller releases with
+ * stcsp_host_free(). The bound of the contract counts every state of the automaton. STCSP_E_INVALID as there. */
+int stcsp_automaton_align_streams(const stcsp_automaton *a, const uint8_t *observable, int32_t flags, const int32_t *weights, int32_t skip_cost,
+                                  int32_t gap_cost, int64_t n_streams, const int64_t *offsets, const int32_t *values, int32_t *distance,
+                                  int64_t *out_offsets, int32_t **out_values, int64_t *op_offsets, uint8_t **ops, uint8_t *end_final,
+                                  int32_t *n_changed, int32_t *n_skipped, int32_t *n_inserted);
+
 /* ---- inferring the unobserved entries of a stream (definition: stcsp_engine.h, stcsp_engine_infer) ----
  * The same contract written plainly, on the automaton's current flags: the checker of the device pass in the tests, and
  * the path for automata whose flags live on the host (sharded runs, host adversarial passes, read_binary). observable:

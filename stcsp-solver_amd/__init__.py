@@ -192,6 +192,40 @@ def _repair_weights(weights, n_obs):
     return np.ascontiguousarray(w, dtype=np.int32) if n_obs else np.zeros(1, np.int32)
 
 
+class AlignRequest(C.Structure):
+    _fields_ = [("n_streams", C.c_int64), ("offsets", C.POINTER(C.c_int64)), ("values", C.POINTER(C.c_int32)),
+                ("weights", C.POINTER(C.c_int32)), ("skip_cost", C.c_int32), ("gap_cost", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class AlignResult(C.Structure):
+    _fields_ = [("n_streams", C.c_int64), ("distance", C.POINTER(C.c_int32)), ("out_offsets", C.POINTER(C.c_int64)),
+                ("values", C.POINTER(C.c_int32)), ("op_offsets", C.POINTER(C.c_int64)), ("ops", C.POINTER(C.c_uint8)),
+                ("n_changed", C.POINTER(C.c_int32)), ("n_skipped", C.POINTER(C.c_int32)), ("n_inserted", C.POINTER(C.c_int32)),
+                ("end_final", C.POINTER(C.c_uint8)), ("n_labels", C.c_int64), ("table_bytes", C.c_int64), ("n_batches", C.c_int32),
+                ("n_observable", C.c_int32), ("path_kernel", C.c_int32), ("reserved", C.c_int32), ("seconds", C.c_double),
+                ("seconds_levels", C.c_double), ("seconds_walk", C.c_double), ("seconds_cost", C.c_double)]
+
+
+ALIGN_END_FINAL = 1                      # align_streams(end_final=True): the aligned prefix must end in a final state
+ALIGN_MATCH, ALIGN_SKIP, ALIGN_INSERT = 0, 1, 2   # the ops of an alignment: M, D, I
+ALIGN_FUSED, ALIGN_GENERAL = 1, 2        # AlignResult.path_kernel
+
+
+def _align_costs(skip_cost, gap_cost):
+    for c in (skip_cost, gap_cost):
+        if not -2 ** 31 <= int(c) < 2 ** 31:
+            raise StcspError(-1, "a cost does not fit an int32")
+    return int(skip_cost), int(gap_cost)
+
+
+def _align_unpack(n, n_obs, dist, out_off, values, op_off, ops, nchg, nskip, nins, fin):
+    """The arrays of an alignment -> (distance int32, list of emitted rows int32 [out_len, n_observable], list of ops uint8,
+    n_changed, n_skipped, n_inserted int32, end_final uint8)."""
+    rows = [values[int(out_off[i]) * n_obs:int(out_off[i + 1]) * n_obs].reshape(-1, n_obs) for i in range(n)]
+    return dist, rows, [ops[int(op_off[i]):int(op_off[i + 1])] for i in range(n)], nchg, nskip, nins, fin
+
+
 def _repair_unpack(values, offsets, n_obs):
     return [values[int(offsets[i]) * n_obs:int(offsets[i + 1]) * n_obs].reshape(-1, n_obs) for i in range(len(offsets) - 1)]
 
@@ -536,7 +570,7 @@ ENGINE_SYMBOLS = [
     "stcsp_engine_propagate", "stcsp_engine_set_expand_budget", "stcsp_engine_node_bytes", "stcsp_engine_donate",
     "stcsp_engine_adopt", "stcsp_engine_expand_variant", "stcsp_engine_kernel_choice", "stcsp_engine_quotient",
     "stcsp_engine_monitor_build", "stcsp_engine_monitor_check", "stcsp_engine_generator_build", "stcsp_engine_generate",
-    "stcsp_engine_repair", "stcsp_engine_infer", "stcsp_engine_posterior", "stcsp_engine_observer", "stcsp_engine_compare",
+    "stcsp_engine_repair", "stcsp_engine_align", "stcsp_engine_infer", "stcsp_engine_posterior", "stcsp_engine_observer", "stcsp_engine_compare",
     "stcsp_engine_components", "stcsp_engine_optimise",
 ]
 # include/stcsp_sharded.h: the superstep loop + in-process transport (libstcsp_hip.so), the RCCL transport (libstcsp_rccl.so)
@@ -553,7 +587,7 @@ HOST_SYMBOLS = [
     "stcsp_merge_shards", "stcsp_merged_result", "stcsp_merged_free", "stcsp_host_free",
     "stcsp_automaton_bisimulation", "stcsp_automaton_set_observable", "stcsp_automaton_quotient",
     "stcsp_automaton_check_streams", "stcsp_automaton_num_observable", "stcsp_automaton_generate", "stcsp_automaton_count_streams",
-    "stcsp_automaton_repair_streams", "stcsp_automaton_infer_streams", "stcsp_automaton_posterior_streams",
+    "stcsp_automaton_repair_streams", "stcsp_automaton_align_streams", "stcsp_automaton_infer_streams", "stcsp_automaton_posterior_streams",
     "stcsp_automaton_observer", "stcsp_observer_get", "stcsp_observer_free", "stcsp_automaton_from_observer",
     "stcsp_compare_observers", "stcsp_comparison_get", "stcsp_comparison_free", "stcsp_automaton_num_vars", "stcsp_automaton_var_name",
     "stcsp_automaton_components", "stcsp_components_get", "stcsp_components_free",
@@ -637,6 +671,9 @@ def host_lib() -> C.CDLL:
         lib.stcsp_automaton_count_streams.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         lib.stcsp_automaton_repair_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.stcsp_automaton_align_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p),
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.stcsp_automaton_infer_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                                       C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]
         lib.stcsp_automaton_posterior_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -716,6 +753,8 @@ def bind_engine_api(lib: C.CDLL, prefix: str = "stcsp_engine") -> None:
         g("generate").argtypes = [C.c_void_p, C.POINTER(GenerateRequest), C.POINTER(GenerateResult)]
     if hasattr(lib, f"{prefix}_repair"):
         g("repair").argtypes = [C.c_void_p, C.POINTER(RepairRequest), C.POINTER(RepairResult)]
+    if hasattr(lib, f"{prefix}_align"):
+        g("align").argtypes = [C.c_void_p, C.POINTER(AlignRequest), C.POINTER(AlignResult)]
     if hasattr(lib, f"{prefix}_infer"):
         g("infer").argtypes = [C.c_void_p, C.POINTER(InferRequest), C.POINTER(InferResult)]
     if hasattr(lib, f"{prefix}_posterior"):
@@ -1004,6 +1043,41 @@ class Automaton:
         if rc != 0:
             raise StcspError(rc, "repair_streams failed: malformed offsets, a negative weight, or (sum of the weights) x (longest stream) above 2^31 - 2")
         return dist[:n], _repair_unpack(out[:values.size], offsets, n_obs), fin[:n], nchg[:n]
+
+    def align_streams(self, streams, observable=None, weights=None, skip_cost=1, gap_cost=1, end_final=False):
+        """The weighted edit distance of every observed stream to the solution language and the aligned solution prefix, by the
+        host twin of Engine.align_streams() (contract: include/stcsp_engine.h, stcsp_engine_align), on the automaton's current
+        flags. `streams`, `observable` and `weights` as in repair_streams(); `skip_cost` drops an observed step, `gap_cost`
+        inserts a solution step the recorder missed. Returns (distance int32, list of emitted rows int32 [out_len,
+        n_observable], list of ops uint8 (ALIGN_MATCH / ALIGN_SKIP / ALIGN_INSERT), n_changed, n_skipped, n_inserted int32,
+        end_final uint8); distance -1 = no alignment (its rows and ops are empty)."""
+        import numpy as np
+        lib = host_lib()
+        m = self._mask(observable)
+        mp = m.ctypes.data if m is not None else None
+        n_obs = lib.stcsp_automaton_num_observable(self._h, mp)
+        values, offsets = pack_streams(streams, n_obs)
+        w = _repair_weights(weights, n_obs)
+        skip_cost, gap_cost = _align_costs(skip_cost, gap_cost)
+        n = len(offsets) - 1
+        dist, nchg, nskip, nins = (np.zeros(max(n, 1), np.int32) for _ in range(4))
+        fin = np.zeros(max(n, 1), np.uint8)
+        out_off, op_off = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+        pv, po = C.c_void_p(), C.c_void_p()
+        rc = lib.stcsp_automaton_align_streams(self._h, mp, ALIGN_END_FINAL if end_final else 0, w.ctypes.data if w is not None else None,
+                                               skip_cost, gap_cost, n, offsets.ctypes.data, values.ctypes.data if values.size else None,
+                                               dist.ctypes.data, out_off.ctypes.data, C.byref(pv), op_off.ctypes.data, C.byref(po),
+                                               fin.ctypes.data, nchg.ctypes.data, nskip.ctypes.data, nins.ctypes.data)
+        if rc != 0:
+            raise StcspError(rc, "align_streams failed: malformed offsets, a negative weight, a cost below 1, or max(sum of the weights, skip) x "
+                                 "(longest stream) + gap x (states) above 2^31 - 2")
+        try:
+            rows = _copy_array(C.cast(pv, C.POINTER(C.c_int32)), int(out_off[n]) * n_obs, np.int32)
+            ops = _copy_array(C.cast(po, C.POINTER(C.c_uint8)), int(op_off[n]), np.uint8)
+        finally:
+            lib.stcsp_host_free(pv)
+            lib.stcsp_host_free(po)
+        return _align_unpack(n, n_obs, dist[:n], out_off, rows, op_off, ops, nchg[:n], nskip[:n], nins[:n], fin[:n])
 
     def infer_streams(self, streams, observable=None, end_final=False, draws=0, seed=0, ranks=None):
         """What the unobserved entries of partially observed streams can be, by the host twin of Engine.infer_streams()
@@ -1421,6 +1495,30 @@ class EngineBase:
         rows = np.ctypeslib.as_array(out.values, shape=(values.size,)).copy() if values.size else np.zeros(0, np.int32)
         return (np.ctypeslib.as_array(out.distance, shape=(n,)).copy(), _repair_unpack(rows, offsets, n_obs),
                 np.ctypeslib.as_array(out.end_final, shape=(n,)).copy(), np.ctypeslib.as_array(out.n_changed, shape=(n,)).copy())
+
+    def align_streams(self, streams, weights=None, skip_cost=1, gap_cost=1, end_final=False):
+        """The weighted edit distance of every observed stream to the solution language and the aligned solution prefix, on the
+        device, after generator() (its mask; its horizon does not limit the streams). `streams` and `weights` as for
+        repair_streams(); `skip_cost` drops an observed step as spurious, `gap_cost` inserts a solution step the recorder
+        missed. Returns what Automaton.align_streams() returns; the whole AlignResult of the call is kept in
+        self.align_result. Contract: include/stcsp_engine.h, stcsp_engine_align."""
+        import numpy as np
+        self._needs_generator("align_streams")
+        n_obs = self.generator_info.n_observable
+        values, offsets = pack_streams(streams, n_obs)
+        w = _repair_weights(weights, n_obs)
+        skip_cost, gap_cost = _align_costs(skip_cost, gap_cost)
+        n = len(offsets) - 1
+        rq = AlignRequest(*_stream_head(values, offsets), w.ctypes.data_as(C.POINTER(C.c_int32)) if w is not None else None,
+                          skip_cost, gap_cost, ALIGN_END_FINAL if end_final else 0, 0)
+        out = AlignResult()
+        self._check(self._f("align")(self._h, C.byref(rq), C.byref(out)))
+        self.align_result = out
+        arr = _copy_array
+        out_off, op_off = arr(out.out_offsets, n + 1, np.int64), arr(out.op_offsets, n + 1, np.int64)
+        return _align_unpack(n, n_obs, arr(out.distance, n, np.int32), out_off, arr(out.values, int(out_off[n]) * n_obs, np.int32), op_off,
+                             arr(out.ops, int(op_off[n]), np.uint8), arr(out.n_changed, n, np.int32), arr(out.n_skipped, n, np.int32),
+                             arr(out.n_inserted, n, np.int32), arr(out.end_final, n, np.uint8))
 
     def infer_streams(self, streams, end_final=False, draws=0, seed=0, ranks=None):
         """What the unobserved entries of partially observed streams can be, on the device, after generator() (its mask; its

@@ -1,5 +1,5 @@
 // automaton.hip -- the host side of the services on the exported automaton: post-processing, bisimulation quotient, stream monitor,
-// generator, repair, inference, posterior marginals, observer and comparison, with the kernels they launch. No kernel is shared with the search (engine.hip).
+// generator, repair, alignment, inference, posterior marginals, observer and comparison, with the kernels they launch. No kernel is shared with the search (engine.hip).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -16,6 +16,7 @@
 #include "dev_generate.hpp"
 #include "generate_host.hpp"
 #include "dev_repair.hpp"
+#include "dev_align.hpp"
 #include "dev_infer.hpp"
 #include "dev_posterior.hpp"
 #include "dev_observer.hpp"
@@ -23,6 +24,7 @@
 #include "dev_components.hpp"
 #include "dev_optimise.hpp"
 #include "repair_host.hpp"
+#include "align_host.hpp"
 #include "infer_host.hpp"
 #include "posterior_host.hpp"
 
@@ -40,7 +42,9 @@ static std::vector<int32_t> observed_columns(const uint8_t *mask, int N) {
 }
 
 AutomatonServices::AutomatonServices() = default;
-AutomatonServices::~AutomatonServices() = default;
+AutomatonServices::~AutomatonServices() {
+    if (aln.h_ctl) (void)hipHostFree(aln.h_ctl);
+}
 
 int AutomatonServices::fail(int code, const char *fmt, ...) {
     char buf[512];
@@ -757,6 +761,172 @@ int AutomatonServices::repair(const AutomatonView &view, const stcsp_repair_requ
         return STCSP_OK;
     };
     if (int rc = stream_batches("repair", "STCSP_REPAIR_BYTES", rq->n_streams, rq->offsets, rq->values, false, need, out, body)) return rc;
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return STCSP_OK;
+}
+
+// Stream alignment: the weighted edit distance of every stream to the solution language and the aligned prefix
+// (contract: stcsp_engine.h).
+int AutomatonServices::align(const AutomatonView &view, const stcsp_align_request *rq, stcsp_align_result *out) {
+    if (int rc = enter(view, "align", NEED_GENERATOR, "stcsp_automaton_align_streams")) return rc;
+    if (!align_request_ok(rq->n_streams, rq->offsets, rq->weights, gen.n_obs, rq->skip_cost, rq->gap_cost, v.n_states))
+        return fail(STCSP_E_INVALID, "align: malformed stream offsets, a negative weight, a cost below 1, or max(sum of the weights, skip) x (longest "
+                                     "stream) + gap x (states) above 2^31 - 2");
+    auto t0 = std::chrono::steady_clock::now();
+    const size_t n = (size_t)rq->n_streams, n_obs = (size_t)gen.n_obs;
+    const size_t steps = n ? (size_t)rq->offsets[n] : 0;
+    if (steps && n_obs && !rq->values) return fail(STCSP_E_INVALID, "align: no step values");
+    aln.a_dist.assign(n, -1);
+    aln.a_fin.assign(n, 0);
+    aln.a_nchg.assign(n, 0);
+    aln.a_nskip.assign(n, 0);
+    aln.a_nins.assign(n, 0);
+    aln.a_ooff.assign(n + 1, 0);
+    aln.a_poff.assign(n + 1, 0);
+    aln.a_values.clear();
+    aln.a_ops.clear();
+    auto publish = [&] {  // (the two grow batch by batch)
+        out->values = aln.a_values.data();
+        out->ops = aln.a_ops.data();
+    };
+    memset(out, 0, sizeof *out);
+    out->n_streams = rq->n_streams;
+    out->distance = aln.a_dist.data();
+    out->out_offsets = aln.a_ooff.data();
+    out->op_offsets = aln.a_poff.data();
+    out->end_final = aln.a_fin.data();
+    out->n_changed = aln.a_nchg.data();
+    out->n_skipped = aln.a_nskip.data();
+    out->n_inserted = aln.a_nins.data();
+    out->n_observable = gen.n_obs;
+    publish();
+    const uint32_t S = v.n_states;
+    const uint32_t &nL = lab.n_labels;  // a reference: stream_batches() may build the labels, need() and body() read them after that
+    const int end_final = (rq->flags & STCSP_ALIGN_END_FINAL) ? 1 : 0;
+    const uint32_t skip = (uint32_t)rq->skip_cost, gap = (uint32_t)rq->gap_cost;
+    const unsigned sb = (S + 255) / 256;
+    uint32_t capacity = kAlnFusedStates;
+    if (const char *e = getenv("STCSP_ALIGN_FUSED_STATES")) capacity = (uint32_t)std::max(0ll, std::min<long long>(atoll(e), kAlnFusedStates));
+    const char *road = getenv("STCSP_ALIGN_FUSED");
+    const bool fused = S <= capacity && !(road && strcmp(road, "0") == 0);  // (only "0" forces the general road)
+    auto need = [&](size_t len) { return ((len + 1) * (size_t)S + len * (size_t)nL) * sizeof(uint32_t); };
+    std::vector<int32_t> w(n_obs, 1);
+    if (rq->weights) w.assign(rq->weights, rq->weights + n_obs);
+    std::vector<long long> room;
+    std::vector<int32_t> rows_h, nrows, nops;
+    std::vector<uint8_t> ops_h;
+    auto body = [&](const Batch &b, size_t nb, size_t first_step, const BatchStream *streams, const int32_t *rows) -> int {
+        (void)first_step;
+        const size_t b0 = b.b0, words_c = b.steps * (size_t)nL;
+        const SweepCsr csr = sweep_csr();
+        const LabelRows L = label_rows();
+        if (int rc = reserve_tables("align", b.bytes, aln.d_aG, b.entries, aln.d_acost, words_c)) return rc;
+        HIPCHK(reserve_all(nb, 0, aln.d_adist, aln.d_anrows, aln.d_anops, aln.d_anchg, aln.d_anskip, aln.d_anins, aln.d_afin));
+        HIPCHK(aln.d_aroom.reserve(nb + 1));
+        HIPCHK(aln.d_actl.reserve_exact(A_WORDS));
+        if (!aln.h_ctl) HIPCHK(hipHostMalloc((void **)&aln.h_ctl, A_WORDS * sizeof(uint32_t), hipHostMallocDefault));
+        if (!b0) {
+            HIPCHK(aln.d_aweights.reserve_exact(n_obs));
+            if (n_obs) HIPCHK(hipMemcpyAsync(aln.d_aweights.p, w.data(), n_obs * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+        }
+        HIPCHK(hipMemsetAsync(aln.d_actl.p, 0, A_WORDS * sizeof(uint32_t), v.stream));
+        HIPCHK(ev.mark(0, v.stream));
+        if (words_c)
+            hipLaunchKernelGGL(k_r_cost, dim3((nL + 255) / 256, (unsigned)std::min<size_t>(b.steps, 65535)), dim3(256), 0, v.stream, nL,
+                               (uint32_t)b.steps, L.rep, L.values, L.N, L.obs, L.n_obs, (const int32_t *)aln.d_aweights.p, rows, aln.d_acost.p);
+        HIPCHK(ev.mark(1, v.stream));
+        const uint8_t *live = post.d_live.p, *fin = post.d_pfinal.p;
+        const uint32_t *cost = aln.d_acost.p, *long_states = lab.d_rlong.p;
+        if (fused) {
+            const size_t lds = 2 * (size_t)S * sizeof(uint32_t);
+            if (lds > (64u << 10)) HIPCHK(hipFuncSetAttribute((const void *)k_a_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(k_a_fused, dim3((unsigned)nb), dim3(kAlnFusedThreads), lds, v.stream, S, streams, csr.off, csr.lid, csr.dstp, nL, cost,
+                               lab.wave_segment, lab.n_long, long_states, live, fin, end_final, skip, gap, aln.d_aG.p, aln.d_actl.p);
+            out->path_kernel = 1;
+        } else {
+            // the closure of level r: groups of sweeps until a group stores nothing (a sweep too many changes nothing)
+            auto close_level = [&](uint32_t r) -> int {
+                for (uint32_t sweeps = 0;; sweeps += kAlnSweepGroup) {
+                    HIPCHK(hipMemsetAsync(aln.d_actl.p + A_CHANGED, 0, sizeof(uint32_t), v.stream));
+                    for (uint32_t g = 0; g < kAlnSweepGroup; g++) {
+                        hipLaunchKernelGGL(k_a_sweep, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, r, streams, csr.off, csr.dstp, lab.wave_segment,
+                                           gap, aln.d_aG.p, aln.d_actl.p);
+                        if (lab.n_long)
+                            hipLaunchKernelGGL(k_a_sweep_long, dim3((lab.n_long + 3) / 4, (unsigned)nb), dim3(256), 0, v.stream, lab.n_long, long_states,
+                                               S, r, streams, csr.off, csr.dstp, gap, aln.d_aG.p, aln.d_actl.p);
+                    }
+                    HIPCHK(hipMemcpyAsync(aln.h_ctl, aln.d_actl.p, A_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+                    HIPCHK(hipStreamSynchronize(v.stream));
+                    if (!aln.h_ctl[A_CHANGED]) return STCSP_OK;
+                    if (sweeps > S) return fail(STCSP_E_INTERNAL, "align: the closure of a level did not converge");
+                }
+            };
+            hipLaunchKernelGGL(k_r_level0, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, streams, live, fin, end_final, aln.d_aG.p);
+            if (end_final)
+                if (int rc = close_level(0)) return rc;
+            for (uint32_t r = 1; r <= (uint32_t)b.longest; r++) {
+                hipLaunchKernelGGL(k_a_base, dim3(sb, (unsigned)nb), dim3(256), 0, v.stream, S, r, streams, csr.off, csr.lid, csr.dstp, nL, cost,
+                                   lab.wave_segment, skip, aln.d_aG.p);
+                if (lab.n_long)
+                    hipLaunchKernelGGL(k_a_base_long, dim3((lab.n_long + 3) / 4, (unsigned)nb), dim3(256), 0, v.stream, lab.n_long, long_states, S, r,
+                                       streams, csr.off, csr.lid, csr.dstp, nL, cost, skip, aln.d_aG.p);
+                if (int rc = close_level(r)) return rc;
+            }
+            out->path_kernel = 2;
+        }
+        hipLaunchKernelGGL(k_a_distance, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)nb, streams, S,
+                           (const uint32_t *)aln.d_aG.p, aln.d_adist.p);
+        HIPCHK(ev.mark(2, v.stream));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(aln.a_dist.data() + b0, aln.d_adist.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        // room for len + distance / gap rows and ops per stream
+        room.assign(nb + 1, 0);
+        for (size_t i = 0; i < nb; i++) {
+            const int32_t d = aln.a_dist[b0 + i];
+            room[i + 1] = room[i] + (d < 0 ? 0 : (long long)(rq->offsets[b0 + i + 1] - rq->offsets[b0 + i]) + d / rq->gap_cost);
+        }
+        const size_t cap = (size_t)room[nb];
+        HIPCHK(aln.d_aout.reserve(cap * n_obs));
+        HIPCHK(aln.d_aops.reserve(cap));
+        HIPCHK(hipMemcpyAsync(aln.d_aroom.p, room.data(), (nb + 1) * sizeof(long long), hipMemcpyHostToDevice, v.stream));
+        HIPCHK(ev.mark(3, v.stream));
+        hipLaunchKernelGGL(k_a_walk, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v.stream, (uint32_t)nb, streams, S, (const uint32_t *)aln.d_aG.p,
+                           csr.off, csr.lid, csr.dstp, csr.eid, nL, cost, L.values, L.N, L.obs, L.n_obs, fin, rows, skip, gap,
+                           (const long long *)aln.d_aroom.p, (const int32_t *)aln.d_adist.p, aln.d_aout.p, aln.d_aops.p, aln.d_anrows.p, aln.d_anops.p,
+                           aln.d_afin.p, aln.d_anchg.p, aln.d_anskip.p, aln.d_anins.p, aln.d_actl.p);
+        HIPCHK(ev.mark(4, v.stream));
+        HIPCHK(hipGetLastError());
+        rows_h.resize(cap * n_obs);
+        ops_h.resize(cap);
+        nrows.resize(nb);
+        nops.resize(nb);
+        if (cap * n_obs) HIPCHK(hipMemcpyAsync(rows_h.data(), aln.d_aout.p, cap * n_obs * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        if (cap) HIPCHK(hipMemcpyAsync(ops_h.data(), aln.d_aops.p, cap, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(nrows.data(), aln.d_anrows.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(nops.data(), aln.d_anops.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(aln.a_nchg.data() + b0, aln.d_anchg.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(aln.a_nskip.data() + b0, aln.d_anskip.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(aln.a_nins.data() + b0, aln.d_anins.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(aln.a_fin.data() + b0, aln.d_afin.p, nb, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(aln.h_ctl, aln.d_actl.p, A_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        HIPCHK(ev.add_spans(0, {&out->seconds_cost, &out->seconds_levels}));
+        HIPCHK(ev.add_spans(3, {&out->seconds_walk}));
+        if (aln.h_ctl[A_ERROR])
+            return fail(STCSP_E_INTERNAL, "align: a state with a finite cost to go and no rule that attains it (error word %u)", aln.h_ctl[A_ERROR]);
+        for (size_t i = 0; i < nb; i++) {  // the streams' rows and ops, packed
+            const size_t at = (size_t)room[i];
+            aln.a_values.insert(aln.a_values.end(), rows_h.begin() + at * n_obs, rows_h.begin() + (at + (size_t)nrows[i]) * n_obs);
+            aln.a_ops.insert(aln.a_ops.end(), ops_h.begin() + at, ops_h.begin() + at + (size_t)nops[i]);
+            aln.a_ooff[b0 + i + 1] = aln.a_ooff[b0 + i] + nrows[i];
+            aln.a_poff[b0 + i + 1] = aln.a_poff[b0 + i] + nops[i];
+        }
+        return STCSP_OK;
+    };
+    const int rc = stream_batches("align", "STCSP_ALIGN_BYTES", rq->n_streams, rq->offsets, rq->values, false, need, out, body);
+    publish();
+    if (rc) return rc;
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;
 }

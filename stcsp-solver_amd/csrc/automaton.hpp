@@ -44,6 +44,7 @@ struct AutomatonServices {
     int generator_build(const AutomatonView &view, const stcsp_generator_options *go, stcsp_generator_info *info);
     int generate(const AutomatonView &view, const stcsp_generate_request *rq, stcsp_generate_result *out);
     int repair(const AutomatonView &view, const stcsp_repair_request *rq, stcsp_repair_result *out);
+    int align(const AutomatonView &view, const stcsp_align_request *rq, stcsp_align_result *out);
     int infer(const AutomatonView &view, const stcsp_infer_request *rq, stcsp_infer_result *out);
     int posterior(const AutomatonView &view, const stcsp_posterior_request *rq, stcsp_posterior_result *out);
     int observer(const AutomatonView &view, const stcsp_observer_options *oo, stcsp_observer_result *out);
@@ -181,6 +182,16 @@ private:
         std::vector<int32_t> r_dist, r_values, r_nchg;
         std::vector<uint8_t> r_fin;
     } rep;
+    struct Align {  // stream alignment (dev_align.hpp): nothing is kept between calls; the vectors back the result
+        DevBuf<uint32_t> d_aG, d_acost, d_actl;
+        DevBuf<int32_t> d_aweights, d_aout, d_adist, d_anrows, d_anops, d_anchg, d_anskip, d_anins;
+        DevBuf<uint8_t> d_aops, d_afin;
+        DevBuf<long long> d_aroom;
+        uint32_t *h_ctl = nullptr;  // pinned, A_WORDS: where the host reads the changed word of a group of sweeps
+        std::vector<int32_t> a_dist, a_values, a_nchg, a_nskip, a_nins;
+        std::vector<int64_t> a_ooff, a_poff;
+        std::vector<uint8_t> a_ops, a_fin;
+    } aln;
     struct Infer {  // stream inference (dev_infer.hpp)
         DevBuf<uint32_t> d_ibits, d_ictl;
         DevBuf<double> d_iB, d_icount;

@@ -2457,6 +2457,10 @@ int stcsp_engine_repair(stcsp_engine *e, const stcsp_repair_request *request, st
     if (!e || !request || !result) return STCSP_E_INVALID;
     return e->services.repair(e->view(), request, result);
 }
+int stcsp_engine_align(stcsp_engine *e, const stcsp_align_request *request, stcsp_align_result *result) {
+    if (!e || !request || !result) return STCSP_E_INVALID;
+    return e->services.align(e->view(), request, result);
+}
 int stcsp_engine_infer(stcsp_engine *e, const stcsp_infer_request *request, stcsp_infer_result *result) {
     if (!e || !request || !result) return STCSP_E_INVALID;
     return e->services.infer(e->view(), request, result);

@@ -25,6 +25,7 @@
 #include "monitor_host.hpp"
 #include <chrono>
 #include "repair_host.hpp"
+#include "align_host.hpp"
 #include "observer_host.hpp"
 #include "components_host.hpp"
 #include "optimise_host.hpp"
@@ -1207,6 +1208,55 @@ int stcsp_automaton_repair_streams(const stcsp_automaton *a, const uint8_t *obse
         for (int64_t i = 0; i < n_streams; i++)
             rep.repair_one(values + offsets[i] * n_obs, offsets[i + 1] - offsets[i], flags, &distance[i], out_values + offsets[i] * n_obs, &end_final[i],
                            &n_changed[i]);
+    } catch (const std::bad_alloc &) {
+        return STCSP_E_NOMEM;
+    }
+    return STCSP_OK;
+}
+int stcsp_automaton_align_streams(const stcsp_automaton *a, const uint8_t *observable, int32_t flags, const int32_t *weights, int32_t skip_cost,
+                                  int32_t gap_cost, int64_t n_streams, const int64_t *offsets, const int32_t *values, int32_t *distance,
+                                  int64_t *out_offsets, int32_t **out_values, int64_t *op_offsets, uint8_t **ops, uint8_t *end_final,
+                                  int32_t *n_changed, int32_t *n_skipped, int32_t *n_inserted) {
+    if (!a || !out_values || !ops) return STCSP_E_INVALID;
+    *out_values = nullptr;
+    *ops = nullptr;
+    try {
+        stcsp::HostAlign aln;
+        const std::vector<uint8_t> mask = a->a.observable_mask(observable);
+        int n_obs = 0;
+        for (uint8_t m : mask) n_obs += m != 0;
+        if (!stcsp::align_request_ok(n_streams, offsets, weights, n_obs, skip_cost, gap_cost, a->a.n_states)) return STCSP_E_INVALID;
+        if (!out_offsets || !op_offsets) return STCSP_E_INVALID;
+        if (n_streams > 0 && (!distance || !end_final || !n_changed || !n_skipped || !n_inserted)) return STCSP_E_INVALID;
+        if (n_streams > 0 && offsets[n_streams] * n_obs > 0 && !values) return STCSP_E_INVALID;
+        aln.build(generator_view(a->a), mask.data(), weights, skip_cost, gap_cost);
+        std::vector<int32_t> rows;
+        std::vector<uint8_t> all_ops;
+        stcsp::AlignedStream one;
+        out_offsets[0] = op_offsets[0] = 0;
+        for (int64_t i = 0; i < n_streams; i++) {
+            aln.align_one(values + offsets[i] * n_obs, offsets[i + 1] - offsets[i], flags, one);
+            distance[i] = one.distance;
+            end_final[i] = one.end_final;
+            n_changed[i] = one.n_changed;
+            n_skipped[i] = one.n_skipped;
+            n_inserted[i] = one.n_inserted;
+            rows.insert(rows.end(), one.rows.begin(), one.rows.end());
+            all_ops.insert(all_ops.end(), one.ops.begin(), one.ops.end());
+            op_offsets[i + 1] = (int64_t)all_ops.size();
+            out_offsets[i + 1] = out_offsets[i] + (int64_t)one.ops.size() - one.n_skipped;
+        }
+        int32_t *vals = (int32_t *)malloc(std::max<size_t>(rows.size(), 1) * sizeof(int32_t));
+        uint8_t *o = (uint8_t *)malloc(std::max<size_t>(all_ops.size(), 1));
+        if (!vals || !o) {
+            free(vals);
+            free(o);
+            return STCSP_E_NOMEM;
+        }
+        std::copy(rows.begin(), rows.end(), vals);
+        std::copy(all_ops.begin(), all_ops.end(), o);
+        *out_values = vals;
+        *ops = o;
     } catch (const std::bad_alloc &) {
         return STCSP_E_NOMEM;
     }

@@ -4,7 +4,7 @@
 //
 //   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--observer[=all|NAME[,NAME...]] [--compare=<file>]] [--components[=bottom|all|<N>]] [--optimise=<spec>] [--check=<file>]
 //         [--sample=<N>:<L>[:<seed>] [--sample-final] [--sample-mask=all]] [--count=<L>]
-//         [--repair=<file> [--repair-final]] [--infer=<file> [--infer-final] [--infer-draws=<D>[:<seed>]]]
+//         [--repair=<file> [--repair-final]] [--align=<file> [--align-costs=<skip>:<gap>] [--align-final]] [--infer=<file> [--infer-final] [--infer-draws=<D>[:<seed>]]]
 //         [--posterior=<file> [--posterior-final] [--posterior-weights=<name>=<value>:<weight>[,...]]] input.csp
 //
 // --observer (not in the reference) writes the observer of the automaton instead of the automaton itself, to solutions.dot and
@@ -82,6 +82,14 @@
 // that end in a final state. The work is done on the device, or by the host twin where the flags live on the host (--shards=N,
 // host adversarial passes). --repair excludes --check, --sample and --count.
 //
+// --align=<file> (not in the reference) aligns observed streams whose recorder may have lost or repeated steps: the weighted edit
+// distance of each stream of the file (the format of --repair=, "?" = not observed) to the solution language, and the aligned solution
+// prefix (include/stcsp_engine.h, stcsp_engine_align; every weight 1). --align-costs=<skip>:<gap> (default 1:1) prices a dropped
+// observed step and an inserted solution step; --align-final asks for prefixes that end in a final state. For each stream stdout holds
+//   # <index> distance <d> len <L> out_len <L2> n_changed <k> n_skipped <a> n_inserted <b> end_final <f> ops <MMDIM...>
+// and the L2 emitted rows in the format --check= reads (M = matched, D = observed step dropped, I = solution step inserted). On the
+// device after an unsharded solve, by the host twin otherwise. --align excludes --check, --repair, --infer, --posterior, --sample, --count.
+//
 // --infer=<file> (not in the reference) infers what the entries of partially observed streams that were not seen can be
 // (include/stcsp_engine.h, stcsp_engine_infer). The file has the format of --repair=: "?" is a value that was not observed. For
 // each stream stdout holds the comment line
@@ -147,6 +155,9 @@ struct Flags {
     const char *check = nullptr;
     const char *repair = nullptr;
     bool repair_final = false;
+    const char *align = nullptr;
+    bool align_final = false;
+    int align_skip = 1, align_gap = 1;
     const char *infer = nullptr;
     bool infer_final = false;
     int infer_draws = 0;
@@ -157,7 +168,7 @@ struct Flags {
     bool sample = false, sample_final = false, sample_all = false;
     long long sample_n = 0, sample_seed = 0;
     int sample_len = 0, count_len = -1;
-    bool quiet() const { return check || repair || infer || posterior || sample || count_len >= 0; }  // stdout holds the answers only
+    bool quiet() const { return check || repair || align || infer || posterior || sample || count_len >= 0; }  // stdout holds the answers only
 };
 
 // --check=<file>, --repair=<file>: the streams of the file, columns reordered to variable order
@@ -315,6 +326,64 @@ static int repair_on_device(const Flags &f, const stcsp_problem *p, const Stream
     stcsp_repair_result rr;
     if (stcsp_engine_repair(eng, &rq, &rr) != STCSP_OK) return 1;
     print_repairs(p, st, rr.distance, rr.values, rr.end_final, rr.n_changed);
+    return 0;
+}
+
+// --align: the lines on stdout
+static void print_alignments(const stcsp_problem *p, const Streams &st, const int32_t *distance, const int64_t *out_off, const int32_t *values,
+                             const int64_t *op_off, const uint8_t *ops, const int32_t *n_changed, const int32_t *n_skipped, const int32_t *n_inserted,
+                             const uint8_t *fin) {
+    size_t n_obs = 0;
+    printf("#");
+    for (int v = 0; v < p->n_vars; v++)
+        if (st.mask[(size_t)v]) {
+            printf(" %s", p->var_names[v]);
+            n_obs++;
+        }
+    printf("\n");
+    for (size_t i = 0; i + 1 < st.offsets.size(); i++) {
+        printf("# %zu distance %d len %lld out_len %lld n_changed %d n_skipped %d n_inserted %d end_final %d ops ", i, distance[i],
+               (long long)(st.offsets[i + 1] - st.offsets[i]), (long long)(out_off[i + 1] - out_off[i]), n_changed[i], n_skipped[i], n_inserted[i],
+               (int)fin[i]);
+        for (int64_t k = op_off[i]; k < op_off[i + 1]; k++) putchar("MDI"[ops[k] < 3 ? ops[k] : 0]);
+        printf("\n");
+        for (int64_t t = out_off[i]; t < out_off[i + 1]; t++) {
+            for (size_t k = 0; k < n_obs; k++) printf(k ? " %d" : "%d", values[(size_t)t * n_obs + k]);
+            printf("\n");
+        }
+        printf("\n");
+    }
+    fflush(stdout);
+}
+
+// --align on the host twin: the automaton's current flags
+static int align_on_host(const Flags &f, const stcsp_problem *p, const Streams &st, const stcsp_automaton *a) {
+    const size_t n = st.offsets.size() - 1;
+    std::vector<int32_t> distance(n + 1), n_changed(n + 1), n_skipped(n + 1), n_inserted(n + 1);
+    std::vector<int64_t> out_off(n + 1), op_off(n + 1);
+    std::vector<uint8_t> fin(n + 1);
+    int32_t *values = nullptr;
+    uint8_t *ops = nullptr;
+    if (stcsp_automaton_align_streams(a, st.mask.data(), f.align_final ? STCSP_ALIGN_END_FINAL : 0, nullptr, f.align_skip, f.align_gap, (int64_t)n,
+                                      st.offsets.data(), st.values.data(), distance.data(), out_off.data(), &values, op_off.data(), &ops, fin.data(),
+                                      n_changed.data(), n_skipped.data(), n_inserted.data()) != STCSP_OK)
+        return 1;
+    print_alignments(p, st, distance.data(), out_off.data(), values, op_off.data(), ops, n_changed.data(), n_skipped.data(), n_inserted.data(), fin.data());
+    stcsp_host_free(values);
+    stcsp_host_free(ops);
+    return 0;
+}
+
+// ... and on the device, over the flags postprocess() has just left
+static int align_on_device(const Flags &f, const stcsp_problem *p, const Streams &st, stcsp_engine *eng) {
+    stcsp_generator_options go = {st.mask.data(), 0, 0, {0, 0}};
+    stcsp_generator_info gi;
+    if (stcsp_engine_generator_build(eng, &go, &gi) != STCSP_OK) return 1;
+    stcsp_align_request rq = {(int64_t)st.offsets.size() - 1, st.offsets.data(), st.values.data(), nullptr, f.align_skip, f.align_gap,
+                              f.align_final ? STCSP_ALIGN_END_FINAL : 0, 0};
+    stcsp_align_result ar;
+    if (stcsp_engine_align(eng, &rq, &ar) != STCSP_OK) return 1;
+    print_alignments(p, st, ar.distance, ar.out_offsets, ar.values, ar.op_offsets, ar.ops, ar.n_changed, ar.n_skipped, ar.n_inserted, ar.end_final);
     return 0;
 }
 
@@ -905,6 +974,7 @@ static int run_once(const Flags &f, bool print_line, double *total) {
     Streams streams;
     if (f.check && read_streams(f.check, p, streams)) return 1;
     if (f.repair && read_streams(f.repair, p, streams, true)) return 1;
+    if (f.align && read_streams(f.align, p, streams, true)) return 1;
     if (f.infer && read_streams(f.infer, p, streams, true)) return 1;
     if (f.posterior && read_streams(f.posterior, p, streams, true)) return 1;
     FILE *info = f.quiet() ? stderr : stdout;  // --check, --sample, --count: stdout holds the answers only
@@ -951,6 +1021,10 @@ static int run_once(const Flags &f, bool print_line, double *total) {
         }
         if (f.repair && repair_on_host(f, p, streams, a)) {
             fprintf(stderr, "the streams could not be repaired\n");
+            return 1;
+        }
+        if (f.align && align_on_host(f, p, streams, a)) {
+            fprintf(stderr, "the streams could not be aligned\n");
             return 1;
         }
         if (f.infer && infer_on_host(f, p, streams, a)) {
@@ -1000,6 +1074,10 @@ static int run_once(const Flags &f, bool print_line, double *total) {
             return 1;
         }
         if (f.repair && repair_on_device(f, p, streams, eng)) {
+            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
+            return 1;
+        }
+        if (f.align && align_on_device(f, p, streams, eng)) {
             fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
             return 1;
         }
@@ -1068,6 +1146,7 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
     Streams streams;
     if (f.check && read_streams(f.check, p, streams)) return 1;
     if (f.repair && read_streams(f.repair, p, streams, true)) return 1;
+    if (f.align && read_streams(f.align, p, streams, true)) return 1;
     if (f.infer && read_streams(f.infer, p, streams, true)) return 1;
     if (f.posterior && read_streams(f.posterior, p, streams, true)) return 1;
     FILE *info = f.quiet() ? stderr : stdout;  // --check, --sample, --count: stdout holds the answers only
@@ -1140,6 +1219,10 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
     }
     if (f.repair && repair_on_host(f, p, streams, a)) {  // (host twin likewise)
         fprintf(stderr, "the streams could not be repaired\n");
+        return 1;
+    }
+    if (f.align && align_on_host(f, p, streams, a)) {  // (host twin likewise)
+        fprintf(stderr, "the streams could not be aligned\n");
         return 1;
     }
     if (f.infer && infer_on_host(f, p, streams, a)) {  // (host twin likewise)
@@ -1240,6 +1323,22 @@ int main(int argc, char **argv) {
         }
         if (strcmp(a, "--repair-final") == 0) {
             f.repair_final = true;
+            continue;
+        }
+        if (strncmp(a, "--align=", 8) == 0) {
+            f.align = a + 8;
+            continue;
+        }
+        if (strcmp(a, "--align-final") == 0) {
+            f.align_final = true;
+            continue;
+        }
+        if (strncmp(a, "--align-costs=", 14) == 0) {
+            char tail = 0;
+            if (sscanf(a + 14, "%d:%d%c", &f.align_skip, &f.align_gap, &tail) != 2 || f.align_skip < 1 || f.align_gap < 1) {
+                fprintf(stderr, "--align-costs=SKIP:GAP takes two integers of at least 1\n");
+                return 1;
+            }
             continue;
         }
         if (strncmp(a, "--infer=", 8) == 0) {
@@ -1358,8 +1457,8 @@ int main(int argc, char **argv) {
             }
         }
     }
-    if ((f.check != nullptr) + (f.repair != nullptr) + (f.infer != nullptr) + (f.posterior != nullptr) + f.sample + (f.count_len >= 0) > 1) {
-        fprintf(stderr, "--check, --repair, --infer, --posterior, --sample and --count exclude each other\n");
+    if ((f.check != nullptr) + (f.repair != nullptr) + (f.align != nullptr) + (f.infer != nullptr) + (f.posterior != nullptr) + f.sample + (f.count_len >= 0) > 1) {
+        fprintf(stderr, "--check, --repair, --align, --infer, --posterior, --sample and --count exclude each other\n");
         return 1;
     }
     if (f.compare && !f.observer) {
