@@ -974,20 +974,28 @@ class Automaton:
         q._h, q._model, q._n_edges = h, self._model, 0
         return q
 
+    def _observed(self, observable, streams=None):
+        """What every stream service of the host twin starts from: (host library, pointer to the mask or None, n_observable,
+        values, offsets, number of streams), the streams packed as in pack_streams(); None, None, 0 without streams."""
+        lib = host_lib()
+        m = self._mask(observable)
+        mp = m.ctypes.data_as(C.c_void_p) if m is not None else None  # (the pointer keeps the array alive)
+        n_obs = lib.stcsp_automaton_num_observable(self._h, mp)
+        if streams is None:
+            return lib, mp, n_obs, None, None, 0
+        values, offsets = pack_streams(streams, n_obs)
+        return lib, mp, n_obs, values, offsets, len(offsets) - 1
+
     def check_streams(self, streams, observable=None):
         """Check observed streams against the live automaton by the host twin of Engine.check_streams() (contract:
         include/stcsp_engine.h, stcsp_engine_monitor_check), on the automaton's current flags. `streams` as in
         pack_streams(); `observable` as in bisimulation(). Returns (accepted_len int32, n_end int32, end_final uint8,
         max_set_size): one entry per stream, and the largest state set met."""
         import numpy as np
-        lib = host_lib()
-        m = self._mask(observable)
-        n_obs = lib.stcsp_automaton_num_observable(self._h, m.ctypes.data if m is not None else None)
-        values, offsets = pack_streams(streams, n_obs)
-        n = len(offsets) - 1
+        lib, mp, n_obs, values, offsets, n = self._observed(observable, streams)
         acc, nend, fin = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
         largest = C.c_int64()
-        rc = lib.stcsp_automaton_check_streams(self._h, m.ctypes.data if m is not None else None, n, offsets.ctypes.data,
+        rc = lib.stcsp_automaton_check_streams(self._h, mp, n, offsets.ctypes.data,
                                                values.ctypes.data if values.size else None, acc.ctypes.data, nend.ctypes.data,
                                                fin.ctypes.data, C.byref(largest))
         if rc != 0:
@@ -1000,10 +1008,7 @@ class Automaton:
         bisimulation(); `horizon` defaults to `length`. Returns (values int32 [n, length, n_observable], end_final uint8 [n],
         count float64 [horizon + 1])."""
         import numpy as np
-        lib = host_lib()
-        m = self._mask(observable)
-        mp = m.ctypes.data if m is not None else None
-        n_obs = lib.stcsp_automaton_num_observable(self._h, mp)
+        lib, mp, n_obs = self._observed(observable)[:3]
         horizon = length if horizon is None else horizon
         rk = None
         if ranks is not None:
@@ -1028,13 +1033,8 @@ class Automaton:
         variable (None: all 1). Returns (distance int32, list of repaired streams int32 [len, n_observable], end_final uint8,
         n_changed int32); distance -1 = no solution prefix of that length (its repaired stream is all 0)."""
         import numpy as np
-        lib = host_lib()
-        m = self._mask(observable)
-        mp = m.ctypes.data if m is not None else None
-        n_obs = lib.stcsp_automaton_num_observable(self._h, mp)
-        values, offsets = pack_streams(streams, n_obs)
+        lib, mp, n_obs, values, offsets, n = self._observed(observable, streams)
         w = _repair_weights(weights, n_obs)
-        n = len(offsets) - 1
         dist, nchg, fin = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
         out = np.zeros(max(values.size, 1), np.int32)
         rc = lib.stcsp_automaton_repair_streams(self._h, mp, REPAIR_END_FINAL if end_final else 0, w.ctypes.data if w is not None else None, n,
@@ -1052,14 +1052,9 @@ class Automaton:
         n_observable], list of ops uint8 (ALIGN_MATCH / ALIGN_SKIP / ALIGN_INSERT), n_changed, n_skipped, n_inserted int32,
         end_final uint8); distance -1 = no alignment (its rows and ops are empty)."""
         import numpy as np
-        lib = host_lib()
-        m = self._mask(observable)
-        mp = m.ctypes.data if m is not None else None
-        n_obs = lib.stcsp_automaton_num_observable(self._h, mp)
-        values, offsets = pack_streams(streams, n_obs)
+        lib, mp, n_obs, values, offsets, n = self._observed(observable, streams)
         w = _repair_weights(weights, n_obs)
         skip_cost, gap_cost = _align_costs(skip_cost, gap_cost)
-        n = len(offsets) - 1
         dist, nchg, nskip, nins = (np.zeros(max(n, 1), np.int32) for _ in range(4))
         fin = np.zeros(max(n, 1), np.uint8)
         out_off, op_off = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
@@ -1087,12 +1082,7 @@ class Automaton:
         draws, end_final): per stream the supports as a [len][n_observable] list of sorted lists of ints, |F_t| as int32
         [len + 1], the draws as int32 [draws, len, n_observable] and their end_final as uint8 [draws]."""
         import numpy as np
-        lib = host_lib()
-        m = self._mask(observable)
-        mp = m.ctypes.data if m is not None else None
-        n_obs = lib.stcsp_automaton_num_observable(self._h, mp)
-        values, offsets = pack_streams(streams, n_obs)
-        n = len(offsets) - 1
+        lib, mp, n_obs, values, offsets, n = self._observed(observable, streams)
         steps = max(int(offsets[n]), 0) if n else 0
         rk = _infer_ranks(ranks, n, draws)
         count = np.zeros(max(n, 1), np.float64)
@@ -1121,12 +1111,7 @@ class Automaton:
         Returns (mass float64 [n], exact uint8 [n], final_mass list of ints, marginals): marginals[i][t][v] is the list of
         (value, mass) pairs of Python ints in value order; empty for a stream that is not exact or not feasible."""
         import numpy as np
-        lib = host_lib()
-        m = self._mask(observable)
-        mp = m.ctypes.data if m is not None else None
-        n_obs = lib.stcsp_automaton_num_observable(self._h, mp)
-        values, offsets = pack_streams(streams, n_obs)
-        n = len(offsets) - 1
+        lib, mp, n_obs, values, offsets, n = self._observed(observable, streams)
         steps = max(int(offsets[n]), 0) if n else 0
         woff, wval, ww = _posterior_weights(weights, n_obs)
         mass, exact, fmass = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint64)
@@ -1450,6 +1435,14 @@ class EngineBase:
         if getattr(self, "generator_info", None) is None:
             raise StcspError(-6, f"{who}() needs generator() first")
 
+    def _generator_streams(self, who, streams):
+        """What every stream service on the generator's structures starts from: (n_observable of its mask, values, offsets,
+        number of streams), the streams packed as in pack_streams()."""
+        self._needs_generator(who)
+        n_obs = self.generator_info.n_observable
+        values, offsets = pack_streams(streams, n_obs)
+        return n_obs, values, offsets, len(offsets) - 1
+
     def generate(self, n, length, seed=0, ranks=None):
         """`n` solution prefixes of `length` steps from the device, after generator(): sampled with `seed` (uniform over the
         paths of that length), or the ranks[i]-th in lexicographic order. Returns (values int32 [n, length, n_observable],
@@ -1480,11 +1473,8 @@ class EngineBase:
         [len, n_observable], end_final uint8, n_changed int32); distance -1 = no solution prefix of that length. The whole
         RepairResult of the call is kept in self.repair_result. Contract: include/stcsp_engine.h, stcsp_engine_repair."""
         import numpy as np
-        self._needs_generator("repair_streams")
-        n_obs = self.generator_info.n_observable
-        values, offsets = pack_streams(streams, n_obs)
+        n_obs, values, offsets, n = self._generator_streams("repair_streams", streams)
         w = _repair_weights(weights, n_obs)
-        n = len(offsets) - 1
         rq = RepairRequest(*_stream_head(values, offsets), w.ctypes.data_as(C.POINTER(C.c_int32)) if w is not None else None,
                            REPAIR_END_FINAL if end_final else 0, 0)
         out = RepairResult()
@@ -1503,12 +1493,9 @@ class EngineBase:
         missed. Returns what Automaton.align_streams() returns; the whole AlignResult of the call is kept in
         self.align_result. Contract: include/stcsp_engine.h, stcsp_engine_align."""
         import numpy as np
-        self._needs_generator("align_streams")
-        n_obs = self.generator_info.n_observable
-        values, offsets = pack_streams(streams, n_obs)
+        n_obs, values, offsets, n = self._generator_streams("align_streams", streams)
         w = _repair_weights(weights, n_obs)
         skip_cost, gap_cost = _align_costs(skip_cost, gap_cost)
-        n = len(offsets) - 1
         rq = AlignRequest(*_stream_head(values, offsets), w.ctypes.data_as(C.POINTER(C.c_int32)) if w is not None else None,
                           skip_cost, gap_cost, ALIGN_END_FINAL if end_final else 0, 0)
         out = AlignResult()
@@ -1527,10 +1514,7 @@ class EngineBase:
         supports, n_states, draws, end_final) as Automaton.infer_streams() does; the whole InferResult of the call is kept in
         self.infer_result. Contract: include/stcsp_engine.h, stcsp_engine_infer."""
         import numpy as np
-        self._needs_generator("infer_streams")
-        n_obs = self.generator_info.n_observable
-        values, offsets = pack_streams(streams, n_obs)
-        n = len(offsets) - 1
+        n_obs, values, offsets, n = self._generator_streams("infer_streams", streams)
         steps = max(int(offsets[n]), 0) if n else 0
         rk = _infer_ranks(ranks, n, draws)
         rq = InferRequest(*_stream_head(values, offsets), rk.ctypes.data_as(C.POINTER(C.c_uint64)) if rk is not None else None, seed,
@@ -1551,10 +1535,7 @@ class EngineBase:
         does; the whole PosteriorResult of the call is kept in self.posterior_result. Contract: include/stcsp_engine.h,
         stcsp_engine_posterior."""
         import numpy as np
-        self._needs_generator("posterior_streams")
-        n_obs = self.generator_info.n_observable
-        values, offsets = pack_streams(streams, n_obs)
-        n = len(offsets) - 1
+        n_obs, values, offsets, n = self._generator_streams("posterior_streams", streams)
         steps = max(int(offsets[n]), 0) if n else 0
         woff, wval, ww = _posterior_weights(weights, n_obs)
         rq = PosteriorRequest(*_stream_head(values, offsets),

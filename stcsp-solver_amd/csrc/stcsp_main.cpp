@@ -169,13 +169,21 @@ struct Flags {
     long long sample_n = 0, sample_seed = 0;
     int sample_len = 0, count_len = -1;
     bool quiet() const { return check || repair || align || infer || posterior || sample || count_len >= 0; }  // stdout holds the answers only
+    // the one streams file (the five options exclude each other) or NULL, and whether it may hold "?": all but --check's
+    const char *streams_file(bool *missing_ok) const {
+        *missing_ok = !check;
+        return check ? check : repair ? repair : align ? align : infer ? infer : posterior;
+    }
 };
 
-// --check=<file>, --repair=<file>: the streams of the file, columns reordered to variable order
+// --check=<file>, --repair=<file>, ...: the streams of the file, columns reordered to variable order
 struct Streams {
     std::vector<uint8_t> mask;
     std::vector<int64_t> offsets{0};
     std::vector<int32_t> values;
+    size_t n() const { return offsets.size() - 1; }
+    long long len(size_t i) const { return (long long)(offsets[i + 1] - offsets[i]); }
+    size_t n_obs() const { return (size_t)std::count_if(mask.begin(), mask.end(), [](uint8_t m) { return m != 0; }); }
 };
 
 static int read_streams(const char *path, const stcsp_problem *p, Streams &out, bool missing_ok = false) {
@@ -265,193 +273,245 @@ static int read_streams(const char *path, const stcsp_problem *p, Streams &out, 
     return 0;
 }
 
-static void print_streams(const Streams &st, const int32_t *acc, const int32_t *n_end, const uint8_t *fin) {
-    for (size_t i = 0; i + 1 < st.offsets.size(); i++)
-        printf("%zu %d %lld %d %d\n", i, acc[i], (long long)(st.offsets[i + 1] - st.offsets[i]), n_end[i], (int)fin[i]);
-    fflush(stdout);
-}
+// ---- what the printers share
+// the default mask: the variables whose name does not start with "_V"
+static bool in_default_mask(const stcsp_problem *p, int v) { return !(p->var_names && p->var_names[v] && strncmp(p->var_names[v], "_V", 2) == 0); }
+static bool is_observable(const stcsp_problem *p, const uint8_t *mask, int v) { return mask ? mask[v] != 0 : in_default_mask(p, v); }
 
-// --check on the host twin: the automaton's current flags
-static int check_on_host(const Streams &st, const stcsp_automaton *a) {
-    const size_t n = st.offsets.size() - 1;
-    std::vector<int32_t> acc(n + 1), n_end(n + 1);
-    std::vector<uint8_t> fin(n + 1);
-    if (stcsp_automaton_check_streams(a, st.mask.data(), (int64_t)n, st.offsets.data(), st.values.data(), acc.data(), n_end.data(), fin.data(), nullptr) != STCSP_OK)
-        return 1;
-    print_streams(st, acc.data(), n_end.data(), fin.data());
-    return 0;
-}
-
-// --repair: the lines on stdout
-static void print_repairs(const stcsp_problem *p, const Streams &st, const int32_t *distance, const int32_t *values, const uint8_t *fin,
-                          const int32_t *n_changed) {
+// the line "# name name ..." of the variables of `mask` (NULL: the default mask); returns their number
+static size_t print_header(FILE *out, const stcsp_problem *p, const uint8_t *mask) {
     size_t n_obs = 0;
-    printf("#");
+    fprintf(out, "#");
     for (int v = 0; v < p->n_vars; v++)
-        if (st.mask[(size_t)v]) {
-            printf(" %s", p->var_names[v]);
+        if (is_observable(p, mask, v)) {
+            fprintf(out, " %s", p->var_names[v]);
             n_obs++;
         }
-    printf("\n");
-    for (size_t i = 0; i + 1 < st.offsets.size(); i++) {
-        printf("# %zu distance %d len %lld n_changed %d end_final %d\n", i, distance[i], (long long)(st.offsets[i + 1] - st.offsets[i]), n_changed[i],
-               (int)fin[i]);
-        for (int64_t t = st.offsets[i]; distance[i] >= 0 && t < st.offsets[i + 1]; t++) {
-            for (size_t k = 0; k < n_obs; k++) printf(k ? " %d" : "%d", values[(size_t)t * n_obs + k]);
-            printf("\n");
-        }
-        printf("\n");
+    fprintf(out, "\n");
+    return n_obs;
+}
+
+// one step of a stream in the format --check= reads
+static void print_row(FILE *out, const int32_t *row, size_t n_obs) {
+    for (size_t k = 0; k < n_obs; k++) fprintf(out, k ? " %d" : "%d", row[k]);
+    fprintf(out, "\n");
+}
+
+// the steps b .. e of rows over all `n_vars` variables as one line " v v; v v": the variables of the default mask
+static void print_steps(FILE *out, const stcsp_problem *p, const int32_t *values, int64_t n_vars, int64_t b, int64_t e) {
+    for (int64_t t = b; t < e; t++) {
+        if (t > b) fprintf(out, ";");
+        for (int v = 0; v < p->n_vars; v++)
+            if (in_default_mask(p, v)) fprintf(out, " %d", values[t * n_vars + v]);
     }
-    fflush(stdout);
+    fprintf(out, "\n");
 }
 
-// --repair on the host twin: the automaton's current flags
-static int repair_on_host(const Flags &f, const stcsp_problem *p, const Streams &st, const stcsp_automaton *a) {
-    const size_t n = st.offsets.size() - 1;
-    std::vector<int32_t> distance(n + 1), n_changed(n + 1), values(st.values.size() + 1);
-    std::vector<uint8_t> fin(n + 1);
-    if (stcsp_automaton_repair_streams(a, st.mask.data(), f.repair_final ? STCSP_REPAIR_END_FINAL : 0, nullptr, (int64_t)n, st.offsets.data(),
-                                       st.values.data(), distance.data(), values.data(), fin.data(), n_changed.data()) != STCSP_OK)
-        return 1;
-    print_repairs(p, st, distance.data(), values.data(), fin.data(), n_changed.data());
-    return 0;
+// ---- the services. Each is one function: with `eng` (a finished postprocess()) it runs on the device, over the flags postprocess()
+// has just left, and with eng NULL by the host twin on `a`'s current flags; one printer follows both. A service prints its own
+// error, the engine's message on the device and a fixed sentence on the host, and returns non-zero.
+static int engine_error(stcsp_engine *eng) {
+    fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
+    return 1;
+}
+static int host_error(const char *sentence) {
+    fprintf(stderr, "%s\n", sentence);
+    return 1;
 }
 
-// ... and on the device, over the flags postprocess() has just left
-static int repair_on_device(const Flags &f, const stcsp_problem *p, const Streams &st, stcsp_engine *eng) {
-    stcsp_generator_options go = {st.mask.data(), 0, 0, {0, 0}};
+// the stream services of the device run on the generator's structures under the streams' mask
+static int build_generator(stcsp_engine *eng, const uint8_t *mask) {
+    stcsp_generator_options go = {mask, 0, 0, {0, 0}};
     stcsp_generator_info gi;
-    if (stcsp_engine_generator_build(eng, &go, &gi) != STCSP_OK) return 1;
-    stcsp_repair_request rq = {(int64_t)st.offsets.size() - 1, st.offsets.data(), st.values.data(), nullptr, f.repair_final ? STCSP_REPAIR_END_FINAL : 0, 0};
-    stcsp_repair_result rr;
-    if (stcsp_engine_repair(eng, &rq, &rr) != STCSP_OK) return 1;
-    print_repairs(p, st, rr.distance, rr.values, rr.end_final, rr.n_changed);
+    return stcsp_engine_generator_build(eng, &go, &gi);
+}
+
+// --check
+static int check(const Flags &, const stcsp_problem *, const Streams &st, const stcsp_automaton *a, stcsp_engine *eng) {
+    const stcsp_monitor_streams ms = {(int64_t)st.n(), st.offsets.data(), st.values.data(), 0, 0};
+    stcsp_monitor_result r = {};
+    std::vector<int32_t> acc, n_end;  // (the twin's output)
+    std::vector<uint8_t> fin;
+    if (eng) {
+        stcsp_monitor_options mo = {st.mask.data(), {0, 0}};
+        stcsp_monitor_info mi;
+        if (stcsp_engine_monitor_build(eng, &mo, &mi) != STCSP_OK || stcsp_engine_monitor_check(eng, &ms, &r) != STCSP_OK) return engine_error(eng);
+    } else {
+        acc.resize(st.n() + 1), n_end.resize(st.n() + 1), fin.resize(st.n() + 1);
+        if (stcsp_automaton_check_streams(a, st.mask.data(), ms.n_streams, ms.offsets, ms.values, acc.data(), n_end.data(), fin.data(), nullptr) != STCSP_OK)
+            return host_error("the streams could not be checked");
+        r.accepted_len = acc.data(), r.n_end = n_end.data(), r.end_final = fin.data();
+    }
+    for (size_t i = 0; i < st.n(); i++) printf("%zu %d %lld %d %d\n", i, r.accepted_len[i], st.len(i), r.n_end[i], (int)r.end_final[i]);
+    fflush(stdout);
     return 0;
 }
 
-// --align: the lines on stdout
-static void print_alignments(const stcsp_problem *p, const Streams &st, const int32_t *distance, const int64_t *out_off, const int32_t *values,
-                             const int64_t *op_off, const uint8_t *ops, const int32_t *n_changed, const int32_t *n_skipped, const int32_t *n_inserted,
-                             const uint8_t *fin) {
-    size_t n_obs = 0;
-    printf("#");
-    for (int v = 0; v < p->n_vars; v++)
-        if (st.mask[(size_t)v]) {
-            printf(" %s", p->var_names[v]);
-            n_obs++;
-        }
-    printf("\n");
-    for (size_t i = 0; i + 1 < st.offsets.size(); i++) {
-        printf("# %zu distance %d len %lld out_len %lld n_changed %d n_skipped %d n_inserted %d end_final %d ops ", i, distance[i],
-               (long long)(st.offsets[i + 1] - st.offsets[i]), (long long)(out_off[i + 1] - out_off[i]), n_changed[i], n_skipped[i], n_inserted[i],
-               (int)fin[i]);
-        for (int64_t k = op_off[i]; k < op_off[i + 1]; k++) putchar("MDI"[ops[k] < 3 ? ops[k] : 0]);
-        printf("\n");
-        for (int64_t t = out_off[i]; t < out_off[i + 1]; t++) {
-            for (size_t k = 0; k < n_obs; k++) printf(k ? " %d" : "%d", values[(size_t)t * n_obs + k]);
-            printf("\n");
-        }
+// --sample / --count
+static void print_samples(const Flags &f, const stcsp_problem *p, const uint8_t *mask, const stcsp_generate_result &r) {
+    const size_t n_obs = print_header(stdout, p, mask);
+    for (long long i = 0; i < f.sample_n; i++) {
+        for (int t = 0; t < f.sample_len; t++) print_row(stdout, r.values + ((size_t)i * (size_t)f.sample_len + (size_t)t) * n_obs, n_obs);
         printf("\n");
     }
     fflush(stdout);
 }
 
-// --align on the host twin: the automaton's current flags
-static int align_on_host(const Flags &f, const stcsp_problem *p, const Streams &st, const stcsp_automaton *a) {
-    const size_t n = st.offsets.size() - 1;
-    std::vector<int32_t> distance(n + 1), n_changed(n + 1), n_skipped(n + 1), n_inserted(n + 1);
-    std::vector<int64_t> out_off(n + 1), op_off(n + 1);
-    std::vector<uint8_t> fin(n + 1);
+static int generate(const Flags &f, const stcsp_problem *p, const stcsp_automaton *a, stcsp_engine *eng) {
+    static const char *const failed = "the streams could not be generated: no solution prefix of that length, or their number overflows a double";
+    const bool counting = f.count_len >= 0;
+    const int32_t horizon = counting ? f.count_len : f.sample_len, flags = f.sample_final ? STCSP_GEN_END_FINAL : 0;
+    std::vector<uint8_t> mask((size_t)p->n_vars, 1);
+    for (int v = 0; v < p->n_vars; v++) mask[(size_t)v] = f.sample_all || in_default_mask(p, v);
+    const double *count = nullptr;
+    stcsp_generate_result r = {};
+    std::vector<double> host_count;  // (the twin's output)
+    std::vector<int32_t> values;
+    std::vector<uint8_t> fin;
+    if (eng) {
+        stcsp_generator_options go = {mask.data(), horizon, flags, {0, 0}};
+        stcsp_generator_info gi;
+        if (stcsp_engine_generator_build(eng, &go, &gi) != STCSP_OK) return engine_error(eng);
+        count = gi.count;
+        stcsp_generate_request rq = {f.sample_n, nullptr, (uint64_t)f.sample_seed, f.sample_len, 0};
+        if (!counting && stcsp_engine_generate(eng, &rq, &r) != STCSP_OK) return engine_error(eng);
+    } else if (counting) {
+        host_count.resize((size_t)horizon + 1);
+        if (stcsp_automaton_count_streams(a, horizon, flags, host_count.data()) != STCSP_OK) return host_error(failed);
+        count = host_count.data();
+    } else {
+        const size_t n_obs = (size_t)std::count(mask.begin(), mask.end(), 1);
+        values.resize((size_t)f.sample_n * (size_t)f.sample_len * n_obs + 1), fin.resize((size_t)f.sample_n + 1);
+        if (stcsp_automaton_generate(a, mask.data(), horizon, flags, f.sample_n, f.sample_len, (uint64_t)f.sample_seed, nullptr, nullptr, values.data(),
+                                     fin.data()) != STCSP_OK)
+            return host_error(failed);
+        r.values = values.data(), r.end_final = fin.data();
+    }
+    if (counting) {
+        for (int t = 0; t <= horizon; t++) printf("%d %.0f\n", t, count[t]);
+        fflush(stdout);
+    } else {
+        print_samples(f, p, mask.data(), r);
+    }
+    return 0;
+}
+
+// --repair
+static void print_repairs(const stcsp_problem *p, const Streams &st, const stcsp_repair_result &r) {
+    const size_t n_obs = print_header(stdout, p, st.mask.data());
+    for (size_t i = 0; i < st.n(); i++) {
+        printf("# %zu distance %d len %lld n_changed %d end_final %d\n", i, r.distance[i], st.len(i), r.n_changed[i], (int)r.end_final[i]);
+        for (int64_t t = st.offsets[i]; r.distance[i] >= 0 && t < st.offsets[i + 1]; t++) print_row(stdout, r.values + (size_t)t * n_obs, n_obs);
+        printf("\n");
+    }
+    fflush(stdout);
+}
+
+static int repair(const Flags &f, const stcsp_problem *p, const Streams &st, const stcsp_automaton *a, stcsp_engine *eng) {
+    const stcsp_repair_request rq = {(int64_t)st.n(), st.offsets.data(), st.values.data(), nullptr, f.repair_final ? STCSP_REPAIR_END_FINAL : 0, 0};
+    stcsp_repair_result r = {};
+    std::vector<int32_t> distance, n_changed, values;  // (the twin's output)
+    std::vector<uint8_t> fin;
+    if (eng) {
+        if (build_generator(eng, st.mask.data()) != STCSP_OK || stcsp_engine_repair(eng, &rq, &r) != STCSP_OK) return engine_error(eng);
+    } else {
+        distance.resize(st.n() + 1), n_changed.resize(st.n() + 1), values.resize(st.values.size() + 1), fin.resize(st.n() + 1);
+        if (stcsp_automaton_repair_streams(a, st.mask.data(), rq.flags, rq.weights, rq.n_streams, rq.offsets, rq.values, distance.data(), values.data(),
+                                           fin.data(), n_changed.data()) != STCSP_OK)
+            return host_error("the streams could not be repaired");
+        r.distance = distance.data(), r.values = values.data(), r.end_final = fin.data(), r.n_changed = n_changed.data();
+    }
+    print_repairs(p, st, r);
+    return 0;
+}
+
+// --align
+static void print_alignments(const stcsp_problem *p, const Streams &st, const stcsp_align_result &r) {
+    const size_t n_obs = print_header(stdout, p, st.mask.data());
+    for (size_t i = 0; i < st.n(); i++) {
+        printf("# %zu distance %d len %lld out_len %lld n_changed %d n_skipped %d n_inserted %d end_final %d ops ", i, r.distance[i], st.len(i),
+               (long long)(r.out_offsets[i + 1] - r.out_offsets[i]), r.n_changed[i], r.n_skipped[i], r.n_inserted[i], (int)r.end_final[i]);
+        for (int64_t k = r.op_offsets[i]; k < r.op_offsets[i + 1]; k++) putchar("MDI"[r.ops[k] < 3 ? r.ops[k] : 0]);
+        printf("\n");
+        for (int64_t t = r.out_offsets[i]; t < r.out_offsets[i + 1]; t++) print_row(stdout, r.values + (size_t)t * n_obs, n_obs);
+        printf("\n");
+    }
+    fflush(stdout);
+}
+
+static int align(const Flags &f, const stcsp_problem *p, const Streams &st, const stcsp_automaton *a, stcsp_engine *eng) {
+    const stcsp_align_request rq = {(int64_t)st.n(), st.offsets.data(), st.values.data(), nullptr, f.align_skip, f.align_gap,
+                                    f.align_final ? STCSP_ALIGN_END_FINAL : 0, 0};
+    stcsp_align_result r = {};
+    std::vector<int32_t> distance, n_changed, n_skipped, n_inserted;  // (the twin's output; it allocates the rows and the ops)
+    std::vector<int64_t> out_off, op_off;
+    std::vector<uint8_t> fin;
     int32_t *values = nullptr;
     uint8_t *ops = nullptr;
-    if (stcsp_automaton_align_streams(a, st.mask.data(), f.align_final ? STCSP_ALIGN_END_FINAL : 0, nullptr, f.align_skip, f.align_gap, (int64_t)n,
-                                      st.offsets.data(), st.values.data(), distance.data(), out_off.data(), &values, op_off.data(), &ops, fin.data(),
-                                      n_changed.data(), n_skipped.data(), n_inserted.data()) != STCSP_OK)
-        return 1;
-    print_alignments(p, st, distance.data(), out_off.data(), values, op_off.data(), ops, n_changed.data(), n_skipped.data(), n_inserted.data(), fin.data());
+    if (eng) {
+        if (build_generator(eng, st.mask.data()) != STCSP_OK || stcsp_engine_align(eng, &rq, &r) != STCSP_OK) return engine_error(eng);
+    } else {
+        distance.resize(st.n() + 1), n_changed.resize(st.n() + 1), n_skipped.resize(st.n() + 1), n_inserted.resize(st.n() + 1);
+        out_off.resize(st.n() + 1), op_off.resize(st.n() + 1), fin.resize(st.n() + 1);
+        if (stcsp_automaton_align_streams(a, st.mask.data(), rq.flags, rq.weights, rq.skip_cost, rq.gap_cost, rq.n_streams, rq.offsets, rq.values,
+                                          distance.data(), out_off.data(), &values, op_off.data(), &ops, fin.data(), n_changed.data(), n_skipped.data(),
+                                          n_inserted.data()) != STCSP_OK)
+            return host_error("the streams could not be aligned");
+        r.distance = distance.data(), r.out_offsets = out_off.data(), r.values = values, r.op_offsets = op_off.data(), r.ops = ops;
+        r.n_changed = n_changed.data(), r.n_skipped = n_skipped.data(), r.n_inserted = n_inserted.data(), r.end_final = fin.data();
+    }
+    print_alignments(p, st, r);
     stcsp_host_free(values);
     stcsp_host_free(ops);
     return 0;
 }
 
-// ... and on the device, over the flags postprocess() has just left
-static int align_on_device(const Flags &f, const stcsp_problem *p, const Streams &st, stcsp_engine *eng) {
-    stcsp_generator_options go = {st.mask.data(), 0, 0, {0, 0}};
-    stcsp_generator_info gi;
-    if (stcsp_engine_generator_build(eng, &go, &gi) != STCSP_OK) return 1;
-    stcsp_align_request rq = {(int64_t)st.offsets.size() - 1, st.offsets.data(), st.values.data(), nullptr, f.align_skip, f.align_gap,
-                              f.align_final ? STCSP_ALIGN_END_FINAL : 0, 0};
-    stcsp_align_result ar;
-    if (stcsp_engine_align(eng, &rq, &ar) != STCSP_OK) return 1;
-    print_alignments(p, st, ar.distance, ar.out_offsets, ar.values, ar.op_offsets, ar.ops, ar.n_changed, ar.n_skipped, ar.n_inserted, ar.end_final);
-    return 0;
-}
-
-// --infer: the lines on stdout
-static void print_inferences(const stcsp_problem *p, const Streams &st, int draws, const double *count, const int64_t *support_off,
-                             const int32_t *support_val, const int32_t *values) {
-    size_t n_obs = 0;
-    printf("#");
-    for (int v = 0; v < p->n_vars; v++)
-        if (st.mask[(size_t)v]) {
-            printf(" %s", p->var_names[v]);
-            n_obs++;
-        }
-    printf("\n");
-    for (size_t i = 0; i + 1 < st.offsets.size(); i++) {
-        const int64_t len = st.offsets[i + 1] - st.offsets[i];
-        printf("# %zu count %.0f len %lld feasible %d\n", i, count[i], (long long)len, count[i] > 0.0 ? 1 : 0);
+// --infer
+static void print_inferences(const stcsp_problem *p, const Streams &st, int draws, const stcsp_infer_result &r) {
+    const size_t n_obs = print_header(stdout, p, st.mask.data());
+    for (size_t i = 0; i < st.n(); i++) {
+        printf("# %zu count %.0f len %lld feasible %d\n", i, r.count[i], st.len(i), r.count[i] > 0.0 ? 1 : 0);
         for (int64_t t = st.offsets[i]; t < st.offsets[i + 1]; t++) {
             printf("#");
             for (size_t k = 0; k < n_obs; k++) {
-                const int64_t b = support_off[(size_t)t * n_obs + k], e = support_off[(size_t)t * n_obs + k + 1];
+                const int64_t b = r.support_off[(size_t)t * n_obs + k], e = r.support_off[(size_t)t * n_obs + k + 1];
                 printf(" {");
-                for (int64_t j = b; j < e; j++) printf(j > b ? ",%d" : "%d", support_val[j]);
+                for (int64_t j = b; j < e; j++) printf(j > b ? ",%d" : "%d", r.support_val[j]);
                 printf("}");
             }
             printf("\n");
         }
-        for (int j = 0; j < draws && count[i] > 0.0; j++) {
-            const int32_t *rows = values + ((size_t)st.offsets[i] * (size_t)draws + (size_t)j * (size_t)len) * n_obs;
-            for (int64_t t = 0; t < len; t++) {
-                for (size_t k = 0; k < n_obs; k++) printf(k ? " %d" : "%d", rows[(size_t)t * n_obs + k]);
-                printf("\n");
-            }
+        for (int j = 0; j < draws && r.count[i] > 0.0; j++) {
+            const int32_t *rows = r.values + ((size_t)st.offsets[i] * (size_t)draws + (size_t)j * (size_t)st.len(i)) * n_obs;
+            for (long long t = 0; t < st.len(i); t++) print_row(stdout, rows + (size_t)t * n_obs, n_obs);
             printf("\n");
         }
     }
     fflush(stdout);
 }
 
-// --infer on the host twin: the automaton's current flags
-static int infer_on_host(const Flags &f, const stcsp_problem *p, const Streams &st, const stcsp_automaton *a) {
-    const size_t n = st.offsets.size() - 1, steps = (size_t)st.offsets[n], draws = (size_t)f.infer_draws;
-    size_t n_obs = 0;
-    for (uint8_t m : st.mask) n_obs += m != 0;
-    std::vector<double> count(n + 1);
-    std::vector<int64_t> support_off(steps * n_obs + 1);
-    std::vector<int32_t> n_states(steps + n + 1), values(steps * draws * n_obs + 1);
-    std::vector<uint8_t> fin(n * draws + 1);
+static int infer(const Flags &f, const stcsp_problem *p, const Streams &st, const stcsp_automaton *a, stcsp_engine *eng) {
+    const stcsp_infer_request rq = {(int64_t)st.n(), st.offsets.data(), st.values.data(), nullptr, (uint64_t)f.infer_seed,
+                                    f.infer_final ? STCSP_INFER_END_FINAL : 0, f.infer_draws};
+    stcsp_infer_result r = {};
+    std::vector<double> count;  // (the twin's output; it allocates the support values)
+    std::vector<int64_t> support_off;
+    std::vector<int32_t> n_states, values;
+    std::vector<uint8_t> fin;
     int32_t *support_val = nullptr;
-    if (stcsp_automaton_infer_streams(a, st.mask.data(), f.infer_final ? STCSP_INFER_END_FINAL : 0, (int64_t)n, st.offsets.data(), st.values.data(),
-                                      f.infer_draws, nullptr, (uint64_t)f.infer_seed, count.data(), support_off.data(), &support_val, n_states.data(),
-                                      values.data(), fin.data()) != STCSP_OK)
-        return 1;
-    print_inferences(p, st, f.infer_draws, count.data(), support_off.data(), support_val, values.data());
+    if (eng) {
+        if (build_generator(eng, st.mask.data()) != STCSP_OK || stcsp_engine_infer(eng, &rq, &r) != STCSP_OK) return engine_error(eng);
+    } else {
+        const size_t steps = (size_t)st.offsets.back(), draws = (size_t)f.infer_draws;
+        count.resize(st.n() + 1), support_off.resize(steps * st.n_obs() + 1), n_states.resize(steps + st.n() + 1);
+        values.resize(steps * draws * st.n_obs() + 1), fin.resize(st.n() * draws + 1);
+        if (stcsp_automaton_infer_streams(a, st.mask.data(), rq.flags, rq.n_streams, rq.offsets, rq.values, rq.draws, rq.ranks, rq.seed, count.data(),
+                                          support_off.data(), &support_val, n_states.data(), values.data(), fin.data()) != STCSP_OK)
+            return host_error("the streams could not be inferred: draws from a count that overflows a double");
+        r.count = count.data(), r.support_off = support_off.data(), r.support_val = support_val, r.values = values.data();
+    }
+    print_inferences(p, st, f.infer_draws, r);
     stcsp_host_free(support_val);
-    return 0;
-}
-
-// ... and on the device, over the flags postprocess() has just left
-static int infer_on_device(const Flags &f, const stcsp_problem *p, const Streams &st, stcsp_engine *eng) {
-    stcsp_generator_options go = {st.mask.data(), 0, 0, {0, 0}};
-    stcsp_generator_info gi;
-    if (stcsp_engine_generator_build(eng, &go, &gi) != STCSP_OK) return 1;
-    stcsp_infer_request rq = {(int64_t)st.offsets.size() - 1, st.offsets.data(), st.values.data(), nullptr, (uint64_t)f.infer_seed,
-                              f.infer_final ? STCSP_INFER_END_FINAL : 0, f.infer_draws};
-    stcsp_infer_result ir;
-    if (stcsp_engine_infer(eng, &rq, &ir) != STCSP_OK) return 1;
-    print_inferences(p, st, f.infer_draws, ir.count, ir.support_off, ir.support_val, ir.values);
     return 0;
 }
 
@@ -500,26 +560,17 @@ static int parse_value_weights(const char *text, const stcsp_problem *p, const S
     return 0;
 }
 
-// --posterior: the lines on stdout
-static void print_posteriors(const stcsp_problem *p, const Streams &st, const double *mass, const uint8_t *exact, const uint64_t *final_mass,
-                             const int64_t *marg_off, const int32_t *marg_val, const uint64_t *marg_mass) {
-    size_t n_obs = 0;
-    printf("#");
-    for (int v = 0; v < p->n_vars; v++)
-        if (st.mask[(size_t)v]) {
-            printf(" %s", p->var_names[v]);
-            n_obs++;
-        }
-    printf("\n");
-    for (size_t i = 0; i + 1 < st.offsets.size(); i++) {
-        printf("# %zu mass %.0f len %lld exact %d final_mass %llu\n", i, mass[i], (long long)(st.offsets[i + 1] - st.offsets[i]), exact[i] ? 1 : 0,
-               (unsigned long long)final_mass[i]);
+// --posterior
+static void print_posteriors(const stcsp_problem *p, const Streams &st, const stcsp_posterior_result &r) {
+    const size_t n_obs = print_header(stdout, p, st.mask.data());
+    for (size_t i = 0; i < st.n(); i++) {
+        printf("# %zu mass %.0f len %lld exact %d final_mass %llu\n", i, r.mass[i], st.len(i), r.exact[i] ? 1 : 0, (unsigned long long)r.final_mass[i]);
         for (int64_t t = st.offsets[i]; t < st.offsets[i + 1]; t++) {
             printf("#");
             for (size_t k = 0; k < n_obs; k++) {
-                const int64_t b = marg_off[(size_t)t * n_obs + k], e = marg_off[(size_t)t * n_obs + k + 1];
+                const int64_t b = r.marg_off[(size_t)t * n_obs + k], e = r.marg_off[(size_t)t * n_obs + k + 1];
                 printf(" {");
-                for (int64_t j = b; j < e; j++) printf(j > b ? ",%d:%llu" : "%d:%llu", marg_val[j], (unsigned long long)marg_mass[j]);
+                for (int64_t j = b; j < e; j++) printf(j > b ? ",%d:%llu" : "%d:%llu", r.marg_val[j], (unsigned long long)r.marg_mass[j]);
                 printf("}");
             }
             printf("\n");
@@ -528,136 +579,61 @@ static void print_posteriors(const stcsp_problem *p, const Streams &st, const do
     fflush(stdout);
 }
 
-// --posterior on the host twin: the automaton's current flags
-static int posterior_on_host(const Flags &f, const stcsp_problem *p, const Streams &st, const stcsp_automaton *a) {
-    const size_t n = st.offsets.size() - 1, steps = (size_t)st.offsets[n];
-    size_t n_obs = 0;
-    for (uint8_t m : st.mask) n_obs += m != 0;
+static int posterior(const Flags &f, const stcsp_problem *p, const Streams &st, const stcsp_automaton *a, stcsp_engine *eng) {
+    static const char *const failed = "the posterior marginals could not be computed: malformed weights";
     ValueWeights vw;
-    if (f.posterior_weights && parse_value_weights(f.posterior_weights, p, st, vw)) return 1;
-    std::vector<double> mass(n + 1);
-    std::vector<uint8_t> exact(n + 1);
-    std::vector<uint64_t> final_mass(n + 1);
-    std::vector<int64_t> marg_off(steps * n_obs + 1);
+    const bool weighted = f.posterior_weights != nullptr;
+    // weights the command line cannot read are the host's to refuse: this sentence on the device road too, not the engine's message
+    if (weighted && parse_value_weights(f.posterior_weights, p, st, vw)) return host_error(failed);
+    const stcsp_posterior_request rq = {(int64_t)st.n(), st.offsets.data(), st.values.data(), weighted ? vw.off.data() : nullptr,
+                                        weighted ? vw.val.data() : nullptr, weighted ? vw.w.data() : nullptr,
+                                        f.posterior_final ? STCSP_POSTERIOR_END_FINAL : 0, 0};
+    stcsp_posterior_result r = {};
+    std::vector<double> mass;  // (the twin's output; it allocates the marginals)
+    std::vector<uint8_t> exact;
+    std::vector<uint64_t> final_mass;
+    std::vector<int64_t> marg_off;
     int32_t *marg_val = nullptr;
     uint64_t *marg_mass = nullptr;
-    const bool weighted = f.posterior_weights != nullptr;
-    if (stcsp_automaton_posterior_streams(a, st.mask.data(), f.posterior_final ? STCSP_POSTERIOR_END_FINAL : 0, (int64_t)n, st.offsets.data(),
-                                          st.values.data(), weighted ? vw.off.data() : nullptr, weighted ? vw.val.data() : nullptr,
-                                          weighted ? vw.w.data() : nullptr, mass.data(), exact.data(), final_mass.data(), marg_off.data(), &marg_val,
-                                          &marg_mass) != STCSP_OK)
-        return 1;
-    print_posteriors(p, st, mass.data(), exact.data(), final_mass.data(), marg_off.data(), marg_val, marg_mass);
+    if (eng) {
+        if (build_generator(eng, st.mask.data()) != STCSP_OK || stcsp_engine_posterior(eng, &rq, &r) != STCSP_OK) return engine_error(eng);
+    } else {
+        mass.resize(st.n() + 1), exact.resize(st.n() + 1), final_mass.resize(st.n() + 1), marg_off.resize((size_t)st.offsets.back() * st.n_obs() + 1);
+        if (stcsp_automaton_posterior_streams(a, st.mask.data(), rq.flags, rq.n_streams, rq.offsets, rq.values, rq.weight_off, rq.weight_val, rq.weight_w,
+                                              mass.data(), exact.data(), final_mass.data(), marg_off.data(), &marg_val, &marg_mass) != STCSP_OK)
+            return host_error(failed);
+        r.mass = mass.data(), r.exact = exact.data(), r.final_mass = final_mass.data(), r.marg_off = marg_off.data();
+        r.marg_val = marg_val, r.marg_mass = marg_mass;
+    }
+    print_posteriors(p, st, r);
     stcsp_host_free(marg_val);
     stcsp_host_free(marg_mass);
     return 0;
 }
 
-// ... and on the device, over the flags postprocess() has just left
-static int posterior_on_device(const Flags &f, const stcsp_problem *p, const Streams &st, stcsp_engine *eng) {
-    ValueWeights vw;
-    if (f.posterior_weights && parse_value_weights(f.posterior_weights, p, st, vw)) return 2;
-    stcsp_generator_options go = {st.mask.data(), 0, 0, {0, 0}};
-    stcsp_generator_info gi;
-    if (stcsp_engine_generator_build(eng, &go, &gi) != STCSP_OK) return 1;
-    const bool weighted = f.posterior_weights != nullptr;
-    stcsp_posterior_request rq = {(int64_t)st.offsets.size() - 1, st.offsets.data(), st.values.data(), weighted ? vw.off.data() : nullptr,
-                                  weighted ? vw.val.data() : nullptr, weighted ? vw.w.data() : nullptr,
-                                  f.posterior_final ? STCSP_POSTERIOR_END_FINAL : 0, 0};
-    stcsp_posterior_result pr;
-    if (stcsp_engine_posterior(eng, &rq, &pr) != STCSP_OK) return 1;
-    print_posteriors(p, st, pr.mass, pr.exact, pr.final_mass, pr.marg_off, pr.marg_val, pr.marg_mass);
-    return 0;
-}
-
-// --sample / --count: the mask, and the lines on stdout
-static std::vector<uint8_t> sample_mask(const Flags &f, const stcsp_problem *p) {
-    std::vector<uint8_t> mask((size_t)p->n_vars, 1);
-    for (int v = 0; v < p->n_vars; v++)
-        if (!f.sample_all && p->var_names && p->var_names[v] && strncmp(p->var_names[v], "_V", 2) == 0) mask[(size_t)v] = 0;
-    return mask;
-}
-
-static void print_counts(const double *count, int horizon) {
-    for (int t = 0; t <= horizon; t++) printf("%d %.0f\n", t, count[t]);
-    fflush(stdout);
-}
-
-static void print_samples(const stcsp_problem *p, const std::vector<uint8_t> &mask, long long n, int len, const int32_t *values) {
-    int n_obs = 0;
-    printf("#");
-    for (int v = 0; v < p->n_vars; v++)
-        if (mask[(size_t)v]) {
-            printf(" %s", p->var_names[v]);
-            n_obs++;
-        }
-    printf("\n");
-    for (long long i = 0; i < n; i++) {
-        for (int t = 0; t < len; t++) {
-            const int32_t *row = values + ((size_t)i * (size_t)len + (size_t)t) * (size_t)n_obs;
-            for (int k = 0; k < n_obs; k++) printf(k ? " %d" : "%d", row[k]);
-            printf("\n");
-        }
-        printf("\n");
-    }
-    fflush(stdout);
-}
-
-// --sample / --count on the host twin: the automaton's current flags
-static int generate_on_host(const Flags &f, const stcsp_problem *p, const stcsp_automaton *a) {
-    const int flags = f.sample_final ? STCSP_GEN_END_FINAL : 0;
-    if (f.count_len >= 0) {
-        std::vector<double> count((size_t)f.count_len + 1);
-        if (stcsp_automaton_count_streams(a, f.count_len, flags, count.data()) != STCSP_OK) return 1;
-        print_counts(count.data(), f.count_len);
-        return 0;
-    }
-    const std::vector<uint8_t> mask = sample_mask(f, p);
-    size_t n_obs = 0;
-    for (uint8_t m : mask) n_obs += m;
-    std::vector<int32_t> values((size_t)f.sample_n * (size_t)f.sample_len * n_obs + 1);
-    std::vector<uint8_t> fin((size_t)f.sample_n + 1);
-    if (stcsp_automaton_generate(a, mask.data(), f.sample_len, flags, f.sample_n, f.sample_len, (uint64_t)f.sample_seed, nullptr, nullptr,
-                                 values.data(), fin.data()) != STCSP_OK)
-        return 1;
-    print_samples(p, mask, f.sample_n, f.sample_len, values.data());
-    return 0;
-}
-
-// ... and on the device, over the flags postprocess() has just left
-static int generate_on_device(const Flags &f, const stcsp_problem *p, stcsp_engine *eng) {
-    const std::vector<uint8_t> mask = sample_mask(f, p);
-    stcsp_generator_options go = {mask.data(), f.count_len >= 0 ? f.count_len : f.sample_len, f.sample_final ? STCSP_GEN_END_FINAL : 0, {0, 0}};
-    stcsp_generator_info gi;
-    if (stcsp_engine_generator_build(eng, &go, &gi) != STCSP_OK) return 1;
-    if (f.count_len >= 0) {
-        print_counts(gi.count, f.count_len);
-        return 0;
-    }
-    stcsp_generate_request rq = {f.sample_n, nullptr, (uint64_t)f.sample_seed, f.sample_len, 0};
-    stcsp_generate_result gr;
-    if (stcsp_engine_generate(eng, &rq, &gr) != STCSP_OK) return 1;
-    print_samples(p, mask, f.sample_n, f.sample_len, gr.values);
-    return 0;
-}
-
-// --quotient: replace *a by its quotient under `state_class` (from the device pass), or under the host twin's partition when
-// state_class is NULL
-static int fold(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, const int32_t *state_class, int64_t n_live, int64_t n_classes) {
+// --quotient: replace *a by its quotient. The one service whose roads differ in more than where the work is done: with an engine
+// the partition is the device pass's (stcsp_engine_quotient), without one the host twin's.
+static int fold(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, stcsp_engine *eng) {
+    static const char *const failed = "the quotient could not be built";
     std::vector<uint8_t> all((size_t)p->n_vars, 1);
     const uint8_t *mask = f.quotient_all ? all.data() : nullptr;
     std::vector<int32_t> host_class;
-    if (!state_class) {
-        host_class.assign((size_t)stcsp_automaton_num_states(*a) + 1, -1);
-        if (stcsp_automaton_bisimulation(*a, mask, host_class.data(), &n_classes) < 0) return 1;
-        state_class = host_class.data();
-        n_live = 0;
-        for (int32_t c : host_class) n_live += c >= 0;
-    } else {
+    const int32_t *state_class = nullptr;
+    int64_t n_live = 0, n_classes = 0;
+    if (eng) {
+        stcsp_quotient_options qo = {mask, {0, 0}};
+        stcsp_quotient_result qr;
+        if (stcsp_engine_quotient(eng, &qo, &qr) != STCSP_OK) return engine_error(eng);
+        state_class = qr.state_class, n_live = qr.n_states, n_classes = qr.n_classes;
         stcsp_automaton_set_observable(*a, mask);
+    } else {
+        host_class.assign((size_t)stcsp_automaton_num_states(*a) + 1, -1);
+        if (stcsp_automaton_bisimulation(*a, mask, host_class.data(), &n_classes) < 0) return host_error(failed);
+        state_class = host_class.data();
+        for (int32_t c : host_class) n_live += c >= 0;
     }
     stcsp_automaton *q = nullptr;
-    if (stcsp_automaton_quotient(*a, state_class, n_classes, &q) != STCSP_OK) return 1;
+    if (stcsp_automaton_quotient(*a, state_class, n_classes, &q) != STCSP_OK) return host_error(failed);
     stcsp_automaton_free(*a);
     *a = q;
     fprintf(stderr, "quotient: %lld -> %lld\n", (long long)n_live, (long long)n_classes);
@@ -676,7 +652,7 @@ static int compare_with_file(const Flags &f, const stcsp_problem *p, const uint8
     std::vector<uint8_t> other_mask((size_t)n_other, 0);
     std::vector<int> index_there;  // per observable variable of this model, in its order: the variable's index in FILE
     for (int v = 0; v < p->n_vars; v++) {
-        if (!(mask ? mask[v] != 0 : strncmp(p->var_names[v], "_V", 2) != 0)) continue;
+        if (!is_observable(p, mask, v)) continue;
         int u = 0;
         while (u < n_other && strcmp(stcsp_automaton_var_name(other, u), p->var_names[v]) != 0) u++;
         if (u == n_other) {
@@ -764,12 +740,9 @@ static int report_components(const Flags &f, const stcsp_problem *p, const stcsp
     stcsp_components *twin = nullptr;
     const stcsp_components_result *r = &dev;
     if (eng) {
-        if (stcsp_engine_components(eng, &co, &dev) != STCSP_OK) {
-            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
-            return 1;
-        }
+        if (stcsp_engine_components(eng, &co, &dev) != STCSP_OK) return engine_error(eng);
     } else {
-        if (stcsp_automaton_components(a, co.max_lassos, co.flags, &twin) != STCSP_OK) return 1;
+        if (stcsp_automaton_components(a, co.max_lassos, co.flags, &twin) != STCSP_OK) return host_error("the components could not be computed");
         r = stcsp_components_get(twin);
     }
     fprintf(stderr, "components: %lld states, %lld components, %lld cyclic, %lld accepting, %lld bottom, %lld omega-live, infinite solution: %s\n",
@@ -782,33 +755,26 @@ static int report_components(const Flags &f, const stcsp_problem *p, const stcsp
                 cf ? "" : "-");
     }
     if (r->n_lassos) {
-        fprintf(stderr, "components: #");
-        for (int v = 0; v < p->n_vars; v++)
-            if (!(p->var_names && p->var_names[v] && strncmp(p->var_names[v], "_V", 2) == 0)) fprintf(stderr, " %s", p->var_names[v]);
-        fprintf(stderr, "\n");
+        fprintf(stderr, "components: ");
+        print_header(stderr, p, nullptr);
     }
     for (int64_t i = 0; i < r->n_lassos; i++) {
         const int64_t b = r->lasso_off[i], m = b + r->lasso_stem_len[i], e = r->lasso_off[i + 1];
         fprintf(stderr, "components: lasso of component %d: %lld + %lld steps\n", r->lasso_component[i], (long long)(m - b), (long long)(e - m));
         for (int part = 0; part < 2; part++) {
             fprintf(stderr, part ? "components: loop:" : "components: stem:");
-            for (int64_t t = part ? m : b; t < (part ? e : m); t++) {
-                if (t > (part ? m : b)) fprintf(stderr, ";");
-                for (int v = 0; v < p->n_vars; v++)
-                    if (!(p->var_names && p->var_names[v] && strncmp(p->var_names[v], "_V", 2) == 0)) fprintf(stderr, " %d", r->lasso_values[t * r->n_vars + v]);
-            }
-            fprintf(stderr, "\n");
+            print_steps(stderr, p, r->lasso_values, r->n_vars, part ? m : b, part ? e : m);
         }
     }
     stcsp_components_free(twin);
     return 0;
 }
 
-// --optimise=min|max:NAME=W[,NAME=W...][:HORIZON][:mean]: the best prefixes and the least long-run mean; on the device (eng: a finished
-// postprocess()) or by the host twin on `a`'s current flags (eng NULL). stderr.
-static int report_optimum(const Flags &f, const stcsp_problem *p, const stcsp_automaton *a, stcsp_engine *eng) {
-    std::vector<int32_t> w((size_t)p->n_vars, 0);
-    std::string spec = f.optimise;
+// --optimise=min|max:NAME=W[,NAME=W...][:HORIZON][:mean]: the weights per variable, STCSP_OPT_* and the horizon of the spec; says what is
+// wrong with one it cannot read
+static int parse_optimise(const char *text, const stcsp_problem *p, std::vector<int32_t> &w, int32_t &flags, int32_t &horizon) {
+    w.assign((size_t)p->n_vars, 0);
+    std::string spec = text;
     std::vector<std::string> parts;
     for (size_t at = 0;;) {
         const size_t colon = spec.find(':', at);
@@ -821,7 +787,8 @@ static int report_optimum(const Flags &f, const stcsp_problem *p, const stcsp_au
         fprintf(stderr, "%s\n", usage);
         return 1;
     }
-    int32_t flags = parts[0] == "max" ? STCSP_OPT_MAXIMISE : 0, horizon = 0;
+    flags = parts[0] == "max" ? STCSP_OPT_MAXIMISE : 0;
+    horizon = 0;
     for (size_t at = 0; at <= parts[1].size();) {
         const size_t comma = std::min(parts[1].find(',', at), parts[1].size());
         const std::string item = parts[1].substr(at, comma - at);
@@ -850,17 +817,25 @@ static int report_optimum(const Flags &f, const stcsp_problem *p, const stcsp_au
             return 1;
         }
     }
+    return 0;
+}
+
+// --optimise: the best prefixes and the least long-run mean; on the device (eng: a finished postprocess()) or by the host twin on
+// `a`'s current flags (eng NULL). stderr.
+static int report_optimum(const Flags &f, const stcsp_problem *p, const stcsp_automaton *a, stcsp_engine *eng) {
+    static const char *const failed = "the optimum could not be computed";
+    std::vector<int32_t> w;
+    int32_t flags = 0, horizon = 0;
+    // a spec that cannot be read: after the parser's complaint the host roads add their sentence, the device road adds nothing
+    if (parse_optimise(f.optimise, p, w, flags, horizon)) return eng ? 1 : host_error(failed);
     const stcsp_optimise_request rq = {w.data(), &horizon, horizon, 1, flags, 0};
     stcsp_optimise_result dev;
     stcsp_optimise *twin = nullptr;
     const stcsp_optimise_result *r = &dev;
     if (eng) {
-        if (stcsp_engine_optimise(eng, &rq, &dev) != STCSP_OK) {
-            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
-            return 1;
-        }
+        if (stcsp_engine_optimise(eng, &rq, &dev) != STCSP_OK) return engine_error(eng);
     } else {
-        if (stcsp_automaton_optimise(a, &rq, &twin) != STCSP_OK) return 1;
+        if (stcsp_automaton_optimise(a, &rq, &twin) != STCSP_OK) return host_error(failed);
         r = stcsp_optimise_get(twin);
     }
     for (int32_t L = 0; L <= horizon; L++) {
@@ -870,17 +845,10 @@ static int report_optimum(const Flags &f, const stcsp_problem *p, const stcsp_au
             fprintf(stderr, "optimise: best[%d] = %lld\n", L, (long long)r->best[L]);
     }
     if (r->best[horizon] != STCSP_OPT_NONE) {
-        auto shown = [&](int v) { return !(p->var_names && p->var_names[v] && strncmp(p->var_names[v], "_V", 2) == 0); };
-        fprintf(stderr, "optimise: #");
-        for (int v = 0; v < p->n_vars; v++)
-            if (shown(v)) fprintf(stderr, " %s", p->var_names[v]);
-        fprintf(stderr, "\noptimise: witness:");
-        for (int64_t t = r->witness_off[0]; t < r->witness_off[1]; t++) {
-            if (t > r->witness_off[0]) fprintf(stderr, ";");
-            for (int v = 0; v < p->n_vars; v++)
-                if (shown(v)) fprintf(stderr, " %d", r->witness_values[t * r->n_vars + v]);
-        }
-        fprintf(stderr, "\n");
+        fprintf(stderr, "optimise: ");
+        print_header(stderr, p, nullptr);
+        fprintf(stderr, "optimise: witness:");
+        print_steps(stderr, p, r->witness_values, r->n_vars, r->witness_off[0], r->witness_off[1]);
     }
     if (flags & STCSP_OPT_MEAN) {
         for (int64_t c = 0; c < r->n_components; c++)
@@ -897,7 +865,7 @@ static int report_optimum(const Flags &f, const stcsp_problem *p, const stcsp_au
 
 // --observer: replace *a by its observer, built on the device (eng: a finished postprocess()) or by the host twin (eng NULL);
 // with --quotient, folded by the host bisimulation under the same mask
-static int observe(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, stcsp_engine *eng) {
+static int replace_by_observer(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, stcsp_engine *eng) {
     std::vector<uint8_t> named((size_t)p->n_vars, strcmp(f.observer_mask, "all") == 0 ? 1 : 0);
     const uint8_t *mask = f.observer_mask[0] ? named.data() : nullptr;
     if (f.observer_mask[0] && strcmp(f.observer_mask, "all") != 0) {
@@ -920,13 +888,8 @@ static int observe(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, 
     stcsp_observer_result dev;
     const stcsp_observer_result *res = &dev;
     if (eng) {
-        stcsp_generator_options go = {mask, 0, 0, {0, 0}};
-        stcsp_generator_info gi;
         stcsp_observer_options oo = {0, {0, 0}};
-        if (stcsp_engine_generator_build(eng, &go, &gi) != STCSP_OK || stcsp_engine_observer(eng, &oo, &dev) != STCSP_OK) {
-            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
-            return 1;
-        }
+        if (build_generator(eng, mask) != STCSP_OK || stcsp_engine_observer(eng, &oo, &dev) != STCSP_OK) return engine_error(eng);
     } else {
         if (stcsp_automaton_observer(*a, mask, 0, &twin) != STCSP_OK) return 1;
         res = stcsp_observer_get(twin);
@@ -956,11 +919,40 @@ static int observe(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, 
     return 0;
 }
 
-static int run_once(const Flags &f, bool print_line, double *total) {
-    double t_init = cpu_time();
+// --observer: whatever failed has been named above, by the parser, the engine or --compare; on both roads this sentence follows it
+static int observe(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, stcsp_engine *eng) {
+    return replace_by_observer(f, p, a, eng) ? host_error("the observer could not be built") : 0;
+}
+
+// Every service the flags ask for, in this order, on the device (eng: a finished postprocess() whose flags *a has adopted) or by
+// the host twins on *a's current flags (eng NULL). The one list of services: a new one is entered here and nowhere else.
+static int run_services(const Flags &f, const stcsp_problem *p, const Streams &streams, stcsp_automaton **a, stcsp_engine *eng) {
+    if (f.check && check(f, p, streams, *a, eng)) return 1;
+    if ((f.sample || f.count_len >= 0) && generate(f, p, *a, eng)) return 1;
+    if (f.repair && repair(f, p, streams, *a, eng)) return 1;
+    if (f.align && align(f, p, streams, *a, eng)) return 1;
+    if (f.infer && infer(f, p, streams, *a, eng)) return 1;
+    if (f.posterior && posterior(f, p, streams, *a, eng)) return 1;
+    if (f.components && report_components(f, p, *a, eng)) return 1;
+    if (f.optimise && report_optimum(f, p, *a, eng)) return 1;
+    if (f.observer && observe(f, p, a, eng)) return 1;
+    if (f.quotient && !f.observer && fold(f, p, a, eng)) return 1;  // (with --observer, observe() has folded the observer)
+    return 0;
+}
+
+// ---- one run: load(), a solve that leaves (result, automaton, engine or NULL), run_services(), finish()
+struct Run {
     stcsp_model *model = nullptr;
-    int rc = f.file ? stcsp_model_load_file(f.file, f.prefix_k, &model) : STCSP_E_INVALID;
-    if (rc != STCSP_OK) {
+    const stcsp_problem *p = nullptr;
+    Streams streams;       // of the one streams file, if any
+    FILE *info = stdout;   // the adver and statistics lines: stderr when stdout holds a service's answers only
+    double init_time = 0;
+    ~Run() { stcsp_model_free(model); }  // (on the early returns too; after the engines, which are destroyed before a return 0)
+};
+
+static int load(const Flags &f, Run &run) {
+    const double t_init = cpu_time();
+    if (stcsp_model_load_file(f.file, f.prefix_k, &run.model) != STCSP_OK) {
         // syntax errors go to stdout like yyerror (stcsp.y:221-224); the rest to error.txt in the
         // reference (myLog) -- stderr here
         const char *msg = stcsp_host_last_error();
@@ -970,192 +962,85 @@ static int run_once(const Flags &f, bool print_line, double *total) {
             fprintf(stderr, "%s\n", msg);
         return 1;
     }
-    const stcsp_problem *p = stcsp_model_problem(model);
-    Streams streams;
-    if (f.check && read_streams(f.check, p, streams)) return 1;
-    if (f.repair && read_streams(f.repair, p, streams, true)) return 1;
-    if (f.align && read_streams(f.align, p, streams, true)) return 1;
-    if (f.infer && read_streams(f.infer, p, streams, true)) return 1;
-    if (f.posterior && read_streams(f.posterior, p, streams, true)) return 1;
-    FILE *info = f.quiet() ? stderr : stdout;  // --check, --sample, --count: stdout holds the answers only
-    double init_time = cpu_time() - t_init;
+    run.p = stcsp_model_problem(run.model);
+    bool missing_ok = false;
+    const char *path = f.streams_file(&missing_ok);
+    if (path && read_streams(path, run.p, run.streams, missing_ok)) return 1;
+    run.info = f.quiet() ? stderr : stdout;
+    run.init_time = cpu_time() - t_init;
+    return 0;
+}
+
+// graphTraverse / adversarialTraverse / adversarialTraverse2 (solveralgorithm.cpp:974-983) by the host passes
+static void host_passes(const Flags &f, stcsp_automaton *a, FILE *info) {
+    stcsp_automaton_traverse(a);
+    if (f.adv1) fprintf(info, "adver1: %d; ", stcsp_automaton_adversarial(a, 5));
+    if (f.adv2) fprintf(info, "adver2: %d\n", stcsp_automaton_adversarial2(a, 5, 6));
+}
+
+// the tail of a run: the files, the statistics line of `res`'s counters, and the automaton's release
+static void finish(const Flags &f, const Run &run, stcsp_automaton *a, const stcsp_result &res, double solve_time, double t_proc, bool print_line,
+                   double *total) {
+    if (f.print_solution || f.binary) stcsp_automaton_order_by_label(a);  // reproducible files whatever the GPU's scheduling
+    stcsp_automaton_renumber(a);
+    const double proc_time = cpu_time() - t_proc;
+    if (f.print_solution) stcsp_automaton_write_dot(a, "solutions.dot");
+    if (f.binary && stcsp_automaton_write_binary(a, f.binary) != STCSP_OK) fprintf(stderr, "cannot write %s\n", f.binary);
+    if (print_line) {
+        // init_time, var, con, dom, node, fail, solve_time, processTime (solveralgorithm.cpp:1001)
+        fprintf(run.info, "%.2f\t%d\t%d\t%d\t%d\t%d\t%.2f\t%.5f\n", run.init_time, run.p->n_vars, run.p->n_constraints, (int)res.counters.dominance,
+                (int)res.n_states, (int)res.counters.fails, solve_time, proc_time);
+        fflush(run.info);
+    }
+    if (total) *total = solve_time + proc_time;
+    stcsp_automaton_free(a);
+}
+
+static int run_once(const Flags &f, bool print_line, double *total) {
+    Run run;
+    if (load(f, run)) return 1;
     stcsp_options opt;
     memset(&opt, 0, sizeof opt);
     opt.world = 1;
     opt.flags = f.intervals ? STCSP_F_INTERVAL_DOMAINS : 0;
     opt.time_limit_s = f.time_limit;  // -m: the reference exit(0)s silently on SIGALRM (solver.cpp:190-193)
     stcsp_engine *eng = nullptr;
-    rc = stcsp_engine_create(p, &opt, &eng);
-    if (rc != STCSP_OK) {
-        fprintf(stderr, "%s\n", stcsp_engine_last_error(nullptr));
-        return 1;
-    }
-    double t_solve = cpu_time();
+    if (stcsp_engine_create(run.p, &opt, &eng) != STCSP_OK) return engine_error(nullptr);
+    const double t_solve = cpu_time();
     stcsp_result res;
-    rc = stcsp_engine_solve(eng, &res);
-    if (rc != STCSP_OK) {
-        fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
-        return 1;
-    }
+    if (stcsp_engine_solve(eng, &res) != STCSP_OK) return engine_error(eng);
     if (res.truncated) exit(0);  // time limit: silent exit 0, like the reference
-    double solve_time = cpu_time() - t_solve;
-    double t_proc = cpu_time();
+    const double solve_time = cpu_time() - t_solve, t_proc = cpu_time();
     stcsp_automaton *a = nullptr;
-    stcsp_automaton_build(p, &res, &a);
-    // graphTraverse / adversarialTraverse / adversarialTraverse2 (solveralgorithm.cpp:974-983) run on
-    // the device over the automaton the export left in HBM; the host only adopts the flags
+    stcsp_automaton_build(run.p, &res, &a);
+    // the traversals run on the device over the automaton the export left in HBM; the host only adopts the flags
     stcsp_post_options po = {f.adv1 ? 5 : -1, f.adv2 ? 5 : -1, f.adv2 ? 6 : -1, 0};
     stcsp_post_result post;
-    rc = stcsp_engine_postprocess(eng, &po, &post);
-    if (rc == STCSP_E_UNSUPPORTED) {  // an adversarial variable wider than the device passes take: the host passes
-        stcsp_automaton_traverse(a);
-        if (f.adv1) fprintf(info, "adver1: %d; ", stcsp_automaton_adversarial(a, 5));
-        if (f.adv2) fprintf(info, "adver2: %d\n", stcsp_automaton_adversarial2(a, 5, 6));
-        if (f.check && check_on_host(streams, a)) {
-            fprintf(stderr, "the streams could not be checked\n");
-            return 1;
-        }
-        if ((f.sample || f.count_len >= 0) && generate_on_host(f, p, a)) {
-            fprintf(stderr, "the streams could not be generated: no solution prefix of that length, or their number overflows a double\n");
-            return 1;
-        }
-        if (f.repair && repair_on_host(f, p, streams, a)) {
-            fprintf(stderr, "the streams could not be repaired\n");
-            return 1;
-        }
-        if (f.align && align_on_host(f, p, streams, a)) {
-            fprintf(stderr, "the streams could not be aligned\n");
-            return 1;
-        }
-        if (f.infer && infer_on_host(f, p, streams, a)) {
-            fprintf(stderr, "the streams could not be inferred: draws from a count that overflows a double\n");
-            return 1;
-        }
-        if (f.posterior && posterior_on_host(f, p, streams, a)) {
-            fprintf(stderr, "the posterior marginals could not be computed: malformed weights\n");
-            return 1;
-        }
-        if (f.components && report_components(f, p, a, nullptr)) {
-            fprintf(stderr, "the components could not be computed\n");
-            return 1;
-        }
-        if (f.optimise && report_optimum(f, p, a, nullptr)) {
-            fprintf(stderr, "the optimum could not be computed\n");
-            return 1;
-        }
-        if (f.observer && observe(f, p, &a, nullptr)) {
-            fprintf(stderr, "the observer could not be built\n");
-            return 1;
-        }
-        if (f.quotient && !f.observer && fold(f, p, &a, nullptr, 0, 0)) {
-            fprintf(stderr, "the quotient could not be built\n");
-            return 1;
-        }
+    stcsp_engine *device = eng;  // where the services run
+    const int rc = stcsp_engine_postprocess(eng, &po, &post);
+    if (rc == STCSP_E_UNSUPPORTED) {  // an adversarial variable wider than the device passes take: the host passes and twins
+        host_passes(f, a, run.info);
+        device = nullptr;
     } else if (rc != STCSP_OK) {
-        fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
-        return 1;
+        return engine_error(eng);
     } else {
         stcsp_automaton_import_flags(a, post.state_valid, post.state_final, post.edge_alive);
-        if (f.adv1) fprintf(info, "adver1: %d; ", post.adver1);
-        if (f.adv2) fprintf(info, "adver2: %d\n", post.adver2);
-        if (f.check) {  // on the device, over the flags postprocess() has just left
-            stcsp_monitor_options mo = {streams.mask.data(), {0, 0}};
-            stcsp_monitor_info mi;
-            stcsp_monitor_streams ms = {(int64_t)streams.offsets.size() - 1, streams.offsets.data(), streams.values.data(), 0, 0};
-            stcsp_monitor_result mr;
-            if (stcsp_engine_monitor_build(eng, &mo, &mi) != STCSP_OK || stcsp_engine_monitor_check(eng, &ms, &mr) != STCSP_OK) {
-                fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
-                return 1;
-            }
-            print_streams(streams, mr.accepted_len, mr.n_end, mr.end_final);
-        }
-        if ((f.sample || f.count_len >= 0) && generate_on_device(f, p, eng)) {
-            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
-            return 1;
-        }
-        if (f.repair && repair_on_device(f, p, streams, eng)) {
-            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
-            return 1;
-        }
-        if (f.align && align_on_device(f, p, streams, eng)) {
-            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
-            return 1;
-        }
-        if (f.infer && infer_on_device(f, p, streams, eng)) {
-            fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
-            return 1;
-        }
-        if (f.posterior) {
-            const int rc = posterior_on_device(f, p, streams, eng);
-            if (rc) {
-                fprintf(stderr, "%s\n", rc == 2 ? "the posterior marginals could not be computed: malformed weights" : stcsp_engine_last_error(eng));
-                return 1;
-            }
-        }
-        if (f.components && report_components(f, p, a, eng)) return 1;
-        if (f.optimise && report_optimum(f, p, a, eng)) return 1;
-        if (f.observer && observe(f, p, &a, eng)) {
-            fprintf(stderr, "the observer could not be built\n");
-            return 1;
-        }
-        if (f.quotient && !f.observer) {
-            std::vector<uint8_t> all((size_t)p->n_vars, 1);
-            stcsp_quotient_options qo = {f.quotient_all ? all.data() : nullptr, {0, 0}};
-            stcsp_quotient_result qr;
-            if (stcsp_engine_quotient(eng, &qo, &qr) != STCSP_OK) {
-                fprintf(stderr, "%s\n", stcsp_engine_last_error(eng));
-                return 1;
-            }
-            if (fold(f, p, &a, qr.state_class, qr.n_states, qr.n_classes)) {
-                fprintf(stderr, "the quotient could not be built\n");
-                return 1;
-            }
-        }
+        if (f.adv1) fprintf(run.info, "adver1: %d; ", post.adver1);
+        if (f.adv2) fprintf(run.info, "adver2: %d\n", post.adver2);
     }
-    if (f.print_solution || f.binary) stcsp_automaton_order_by_label(a);  // reproducible files whatever the GPU's scheduling
-    stcsp_automaton_renumber(a);
-    double proc_time = cpu_time() - t_proc;
-    if (f.print_solution) stcsp_automaton_write_dot(a, "solutions.dot");
-    if (f.binary && stcsp_automaton_write_binary(a, f.binary) != STCSP_OK) fprintf(stderr, "cannot write %s\n", f.binary);
-    if (print_line) {
-        // init_time, var, con, dom, node, fail, solve_time, processTime (solveralgorithm.cpp:1001)
-        fprintf(info, "%.2f\t%d\t%d\t%d\t%d\t%d\t%.2f\t%.5f\n", init_time, p->n_vars, p->n_constraints, (int)res.counters.dominance,
-               (int)res.n_states, (int)res.counters.fails, solve_time, proc_time);
-        fflush(info);
-    }
-    if (total) *total = solve_time + proc_time;
-    stcsp_automaton_free(a);
+    if (run_services(f, run.p, run.streams, &a, device)) return 1;
+    finish(f, run, a, res, solve_time, t_proc, print_line, total);
     stcsp_engine_destroy(eng);
-    stcsp_model_free(model);
     return 0;
 }
 
-// --shards=N: the same run with the frontier and the state table sharded over N engines (see the header comment)
+// --shards=N: the same run with the frontier and the state table sharded over N engines (see the header comment); the merged
+// automaton lives on the host, so the host passes and the host twins work on it
 static int run_sharded(const Flags &f, bool print_line, double *total) {
-    double t_init = cpu_time();
-    stcsp_model *model = nullptr;
-    if (stcsp_model_load_file(f.file, f.prefix_k, &model) != STCSP_OK) {
-        const char *msg = stcsp_host_last_error();
-        if (strncmp(msg, "Line ", 5) == 0)
-            printf("%s\n", msg);
-        else
-            fprintf(stderr, "%s\n", msg);
-        return 1;
-    }
-    const stcsp_problem *p = stcsp_model_problem(model);
-    Streams streams;
-    if (f.check && read_streams(f.check, p, streams)) return 1;
-    if (f.repair && read_streams(f.repair, p, streams, true)) return 1;
-    if (f.align && read_streams(f.align, p, streams, true)) return 1;
-    if (f.infer && read_streams(f.infer, p, streams, true)) return 1;
-    if (f.posterior && read_streams(f.posterior, p, streams, true)) return 1;
-    FILE *info = f.quiet() ? stderr : stdout;  // --check, --sample, --count: stdout holds the answers only
-    double init_time = cpu_time() - t_init;
+    Run run;
+    if (load(f, run)) return 1;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        fprintf(stderr, "no HIP device available\n");
-        return 1;
-    }
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return host_error("no HIP device available");
     const int world = f.shards;
     std::vector<stcsp_engine *> eng((size_t)world, nullptr);
     for (int r = 0; r < world; r++) {
@@ -1166,14 +1051,11 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
         opt.world = world;
         opt.flags = f.intervals ? STCSP_F_INTERVAL_DOMAINS : 0;
         opt.time_limit_s = f.time_limit;
-        if (stcsp_engine_create(p, &opt, &eng[(size_t)r]) != STCSP_OK) {
-            fprintf(stderr, "%s\n", stcsp_engine_last_error(nullptr));
-            return 1;
-        }
+        if (stcsp_engine_create(run.p, &opt, &eng[(size_t)r]) != STCSP_OK) return engine_error(nullptr);
     }
     stcsp_local_group *group = nullptr;
     if (stcsp_local_group_create(world, &group) != STCSP_OK) return 1;
-    double t_solve = cpu_time();
+    const double t_solve = cpu_time();
     std::vector<int> rcs((size_t)world, 0);
     {
         std::vector<std::thread> th;
@@ -1197,74 +1079,16 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
         resp.push_back(&res[(size_t)r]);
     }
     stcsp_merged *mg = nullptr;
-    if (stcsp_merge_shards(resp.data(), world, &mg) != STCSP_OK) {
-        fprintf(stderr, "merging the shards failed\n");
-        return 1;
-    }
-    const stcsp_result *merged = stcsp_merged_result(mg);
-    double solve_time = cpu_time() - t_solve;
-    double t_proc = cpu_time();
+    if (stcsp_merge_shards(resp.data(), world, &mg) != STCSP_OK) return host_error("merging the shards failed");
+    const double solve_time = cpu_time() - t_solve, t_proc = cpu_time();
     stcsp_automaton *a = nullptr;
-    stcsp_automaton_build(p, merged, &a);
-    stcsp_automaton_traverse(a);  // (host passes: the merged automaton lives on the host)
-    if (f.adv1) fprintf(info, "adver1: %d; ", stcsp_automaton_adversarial(a, 5));
-    if (f.adv2) fprintf(info, "adver2: %d\n", stcsp_automaton_adversarial2(a, 5, 6));
-    if (f.check && check_on_host(streams, a)) {  // (host twin: the merged automaton lives on the host)
-        fprintf(stderr, "the streams could not be checked\n");
-        return 1;
-    }
-    if ((f.sample || f.count_len >= 0) && generate_on_host(f, p, a)) {  // (host twin likewise)
-        fprintf(stderr, "the streams could not be generated: no solution prefix of that length, or their number overflows a double\n");
-        return 1;
-    }
-    if (f.repair && repair_on_host(f, p, streams, a)) {  // (host twin likewise)
-        fprintf(stderr, "the streams could not be repaired\n");
-        return 1;
-    }
-    if (f.align && align_on_host(f, p, streams, a)) {  // (host twin likewise)
-        fprintf(stderr, "the streams could not be aligned\n");
-        return 1;
-    }
-    if (f.infer && infer_on_host(f, p, streams, a)) {  // (host twin likewise)
-        fprintf(stderr, "the streams could not be inferred: draws from a count that overflows a double\n");
-        return 1;
-    }
-    if (f.posterior && posterior_on_host(f, p, streams, a)) {  // (host twin likewise)
-        fprintf(stderr, "the posterior marginals could not be computed: malformed weights\n");
-        return 1;
-    }
-    if (f.components && report_components(f, p, a, nullptr)) {  // (host twin likewise)
-        fprintf(stderr, "the components could not be computed\n");
-        return 1;
-    }
-    if (f.optimise && report_optimum(f, p, a, nullptr)) {  // (host twin likewise)
-        fprintf(stderr, "the optimum could not be computed\n");
-        return 1;
-    }
-    if (f.observer && observe(f, p, &a, nullptr)) {  // (host twin likewise)
-        fprintf(stderr, "the observer could not be built\n");
-        return 1;
-    }
-    if (f.quotient && !f.observer && fold(f, p, &a, nullptr, 0, 0)) {  // (host twin: the merged automaton lives on the host)
-        fprintf(stderr, "the quotient could not be built\n");
-        return 1;
-    }
-    if (f.print_solution || f.binary) stcsp_automaton_order_by_label(a);
-    stcsp_automaton_renumber(a);
-    double proc_time = cpu_time() - t_proc;
-    if (f.print_solution) stcsp_automaton_write_dot(a, "solutions.dot");
-    if (f.binary && stcsp_automaton_write_binary(a, f.binary) != STCSP_OK) fprintf(stderr, "cannot write %s\n", f.binary);
-    if (print_line) {
-        fprintf(info, "%.2f\t%d\t%d\t%d\t%d\t%d\t%.2f\t%.5f\n", init_time, p->n_vars, p->n_constraints, (int)merged->counters.dominance,
-                (int)merged->n_states, (int)merged->counters.fails, solve_time, proc_time);
-        fflush(info);
-    }
-    if (total) *total = solve_time + proc_time;
-    stcsp_automaton_free(a);
+    stcsp_automaton_build(run.p, stcsp_merged_result(mg), &a);
+    host_passes(f, a, run.info);
+    if (run_services(f, run.p, run.streams, &a, nullptr)) return 1;
+    finish(f, run, a, *stcsp_merged_result(mg), solve_time, t_proc, print_line, total);
     stcsp_merged_free(mg);
     stcsp_local_group_destroy(group);
     for (stcsp_engine *e : eng) stcsp_engine_destroy(e);
-    stcsp_model_free(model);
     return 0;
 }
 
