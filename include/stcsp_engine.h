@@ -1077,6 +1077,118 @@ typedef struct stcsp_optimise_result {
 
 int stcsp_engine_optimise(stcsp_engine *engine, const stcsp_optimise_request *request, stcsp_optimise_result *result);
 
+/* ---- temporal queries over the infinite solutions on the device: fair CTL (no reference counterpart) ------------------
+ * "Can GAMEOVER == 1 always be avoided", "is it inevitable", "can the system always get back to m == 0": properties of the
+ * branching structure of the INFINITE solutions, the streams stcsp_engine_components() speaks about.
+ *
+ * ONLY SOLUTIONS ARE QUANTIFIED OVER. A prefix that cannot be continued to an infinite solution does not exist for this
+ * call: it is neither a witness of an E nor a counterexample of an A.
+ *
+ * Worlds. A world is one step on an infinite solution: a live edge e (alive, both ends live) with state_omega[dst(e)] == 1.
+ * Live, flags and validity are exactly those of stcsp_engine_components(). The successors of a world e are the worlds f
+ * with src(f) == dst(e); every world has at least one. The initial worlds are the worlds that leave the root (state 0).
+ * Solutions. A solution from w is an infinite sequence of worlds w0 = w, w(i+1) a successor of w(i), with
+ * final[dst(w(i))] set for infinitely many i (the Buechi condition of stcsp_engine_components()). Every world starts at
+ * least one. A model without an infinite solution has 0 worlds: every query on it is vacuous (n_initial == 0), not an error.
+ *
+ * Atoms hold on a world and are read from that edge's full value row: NAME op INT and NAME op NAME with op one of
+ * == != < <= > >=, compared as int32 (INT_MIN is a value), and true and false. Formulas: the connectives ! & | -> and the
+ * temporal operators EX f, EF f, EG f, E[f U g], AX f, AF f, AG f, A[f U g] with their standard CTL meaning, the path
+ * quantifiers ranging over the solutions from the world.
+ *
+ * Request: a postfix program of int32 words. An atom is its token followed by its operands:
+ *   STCSP_CTL_TRUE | STCSP_CTL_FALSE
+ *   STCSP_CTL_CMP_CONST var op value      STCSP_CTL_CMP_VAR var op var2      (op: STCSP_CTL_OP_*)
+ *   STCSP_CTL_NOT (1 operand)  STCSP_CTL_AND | OR | IMPLIES (2)  STCSP_CTL_EX | EF | EG | AX | AF | AG (1)
+ *   STCSP_CTL_EU | STCSP_CTL_AU (2: f then g)
+ * (stcsp_ctl_parse() of stcsp_host.h writes it from text). A malformed program is STCSP_E_INVALID: stack underflow, a
+ * variable index or comparison outside its range, an unknown token, leftover operands, an empty program.
+ *
+ * Lowering, on the host, to the basis {atoms, !, &, |, EX, EU, EG}:  f -> g = !f | g,  EF f = E[true U f],
+ * AX f = !EX !f,  AG f = !E[true U !f],  AF f = !EG !f,  A[f U g] = !E[!g U (!f & !g)] & !EG !g.  Double negations are
+ * not removed. Limits, on the LOWERED program (STCSP_E_UNSUPPORTED beyond them, with a message): STCSP_CTL_MAX_NODES atoms
+ * and operators in all (A[f U g] counts f once and g three times), a maximal temporal-free subformula whose postfix
+ * evaluation needs a stack deeper than 64, and STCSP_CTL_MAX_SLOTS sets of worlds held at once (an operand pair holds the
+ * first set while the second is computed; EG holds three).
+ *
+ * Evaluation (every world is fair: it starts a solution):  EX f: some successor is in f.  E[f U g]: the least fixpoint
+ * Z = g | (f & EX Z).  EG f: Emerson-Lei, the greatest fixpoint Z = f & EX E[f U (Z & Fin)] with Fin(e) = final[dst(e)];
+ * every outer round runs an inner EU to its own fixpoint. A fixpoint that has not converged after n_worlds + 8 rounds is
+ * STCSP_E_INTERNAL.
+ *
+ * Verdict. n_worlds, n_initial, n_initial_sat and per exported edge two bytes: edge_world[e] (e is a world) and edge_sat[e]
+ * (the formula holds there; 0 outside the worlds). "Holds for the model" is n_initial_sat == n_initial; "possible" is
+ * n_initial_sat > 0.
+ *
+ * Witness (flags & STCSP_CTL_WITNESS). When the lowered top operator is EX or EU and some initial world satisfies it, a
+ * witness; when the top is !EX or !EU and some initial world fails it, a counterexample (a witness of the operand). For EU
+ * it is the shortest sequence of worlds from an initial world that stays in sat(f) and ends in sat(g); for EX, two worlds,
+ * the second in sat(f). Among the shortest the lexicographically least by full rows, the choice of the initial world being
+ * part of the minimisation (the walk of stcsp_engine_components()). witness_kind is STCSP_CTL_NONE, STCSP_CTL_IS_WITNESS or
+ * STCSP_CTL_IS_COUNTEREXAMPLE; witness_values holds witness_len full rows. Two equal full rows among the candidates of a
+ * step give STCSP_E_INTERNAL. No lasso is built for EG / AF: the result says STCSP_CTL_NONE.
+ *
+ * Errors. STCSP_E_STATE before stcsp_engine_postprocess() and after a truncated solve; STCSP_E_UNSUPPORTED on sharded
+ * engines (run stcsp_automaton_ctl() of stcsp_host.h on the merged automaton) and over the limits; STCSP_E_INVALID as above;
+ * STCSP_E_NOMEM over the byte budget (the environment's STCSP_CTL_BYTES, else half of the free device memory), checked once
+ * the worlds are counted and before any set is computed, with a message that names the need and the limit. Memory: 12 B per
+ * world, 14 B per state, 2 B per exported edge, one bit per world and held set, 8 B per world with a witness.
+ *
+ * The call runs the component pass of stcsp_engine_components() itself (no lassos): the result pointers of an earlier
+ * stcsp_engine_components() call are then no longer valid. It invalidates nothing else. Results are owned by the engine
+ * until the next call on it. */
+#define STCSP_CTL_TRUE 1
+#define STCSP_CTL_FALSE 2
+#define STCSP_CTL_CMP_CONST 3
+#define STCSP_CTL_CMP_VAR 4
+#define STCSP_CTL_NOT 10
+#define STCSP_CTL_AND 11
+#define STCSP_CTL_OR 12
+#define STCSP_CTL_IMPLIES 13
+#define STCSP_CTL_EX 20
+#define STCSP_CTL_EF 21
+#define STCSP_CTL_EG 22
+#define STCSP_CTL_EU 23
+#define STCSP_CTL_AX 24
+#define STCSP_CTL_AF 25
+#define STCSP_CTL_AG 26
+#define STCSP_CTL_AU 27
+#define STCSP_CTL_OP_EQ 0
+#define STCSP_CTL_OP_NE 1
+#define STCSP_CTL_OP_LT 2
+#define STCSP_CTL_OP_LE 3
+#define STCSP_CTL_OP_GT 4
+#define STCSP_CTL_OP_GE 5
+#define STCSP_CTL_WITNESS 1 /* request.flags */
+#define STCSP_CTL_NONE 0    /* witness_kind */
+#define STCSP_CTL_IS_WITNESS 1
+#define STCSP_CTL_IS_COUNTEREXAMPLE 2
+#define STCSP_CTL_MAX_NODES 256
+#define STCSP_CTL_MAX_SLOTS 16
+
+typedef struct stcsp_ctl_request {
+    const int32_t *program; /* [n_words] postfix                        */
+    int32_t n_words;
+    int32_t flags; /* STCSP_CTL_WITNESS                                 */
+} stcsp_ctl_request;
+
+typedef struct stcsp_ctl_result {
+    int64_t n_worlds;
+    int64_t n_initial, n_initial_sat;
+    int64_t n_edges;               /* stcsp_result::n_edges: the length of the two byte arrays                         */
+    const uint8_t *edge_world;     /* [n_edges]                                                                        */
+    const uint8_t *edge_sat;       /* [n_edges]                                                                        */
+    const int32_t *witness_values; /* [witness_len * n_vars]                                                           */
+    int32_t witness_kind;          /* STCSP_CTL_NONE | IS_WITNESS | IS_COUNTEREXAMPLE                                  */
+    int32_t witness_len;           /* in rows                                                                          */
+    int32_t n_vars;
+    int32_t rounds[3];      /* sweeps in all, the most outer rounds of any EG, launches (0 on the host twin)           */
+    double seconds;         /* wall time from the flags in HBM to the result on the host                               */
+    double seconds_kernels; /* HIP-event time of the launches, the component pass included (0 on the host twin)        */
+} stcsp_ctl_result;
+
+int stcsp_engine_ctl(stcsp_engine *engine, const stcsp_ctl_request *request, stcsp_ctl_result *result);
+
 void stcsp_engine_destroy(stcsp_engine *engine);
 
 /* Message of the last error on this engine (or of the last failed create when engine==NULL). */

@@ -245,6 +245,27 @@ int stcsp_automaton_optimise(const stcsp_automaton *a, const stcsp_optimise_requ
 const stcsp_optimise_result *stcsp_optimise_get(const stcsp_optimise *o);
 void stcsp_optimise_free(stcsp_optimise *o);
 
+/* ---- temporal queries over the infinite solutions: fair CTL (definition: stcsp_engine.h, stcsp_engine_ctl) ----
+ * stcsp_ctl_parse() turns formula text into the postfix program of stcsp_ctl_request. Of `problem` it reads n_vars and
+ * var_names only. Grammar, loosest first:  f -> g (right associative),  f | g,  f & g,  then the prefix operators
+ * ! EX EF EG AX AF AG,  E[f U g],  A[f U g],  ( f ),  true,  false  and the atoms NAME op INT and NAME op NAME with op one
+ * of == != < <= > >= (INT: a decimal int32, with a sign if negative). A word followed by a comparison is a variable, whatever
+ * its spelling. *program receives the words in one block the caller releases with stcsp_host_free(), *n_words their count.
+ * On an error (STCSP_E_INVALID: a syntax error, an unknown variable name, an integer outside int32) *error_pos receives the
+ * 0-based offset into text and message (message_len bytes, may be NULL) what is wrong there.
+ *
+ * stcsp_automaton_ctl() is the same contract written plainly, on the automaton's current flags: the same lowering (shared
+ * with the device pass, limits included), the same fixpoints over one byte per world, the same witness rule. The checker of
+ * the device pass in the tests, and the path for automata whose flags live on the host (merged sharded runs, host
+ * adversarial passes, read_binary, import_flags). Errors as there, without a message. The result (stcsp_ctl_get(): rounds
+ * and seconds_kernels are 0) lives until stcsp_ctl_free(). */
+int stcsp_ctl_parse(const char *text, const stcsp_problem *problem, int32_t **program, int32_t *n_words, int32_t *error_pos, char *message,
+                    size_t message_len);
+typedef struct stcsp_ctl stcsp_ctl;
+int stcsp_automaton_ctl(const stcsp_automaton *a, const stcsp_ctl_request *request, stcsp_ctl **out);
+const stcsp_ctl_result *stcsp_ctl_get(const stcsp_ctl *c);
+void stcsp_ctl_free(stcsp_ctl *c);
+
 /* Merge the per-shard results of a sharded run (global state ids, see stcsp_engine.h) into
  * one result with dense ids; runs the ok-fixpoint over the union. The merged result is owned
  * by the returned handle. */

@@ -562,6 +562,85 @@ F_STEPPED = 8
 F_INTERVAL_DOMAINS = 16  # every variable held as an interval (any width in [INT_MIN, INT_MAX]); include/stcsp_engine.h
 GID_SHIFT = 40
 
+class CtlRequest(C.Structure):
+    _fields_ = [("program", C.POINTER(C.c_int32)), ("n_words", C.c_int32), ("flags", C.c_int32)]
+
+
+class CtlResult(C.Structure):
+    _fields_ = [("n_worlds", C.c_int64), ("n_initial", C.c_int64), ("n_initial_sat", C.c_int64), ("n_edges", C.c_int64),
+                ("edge_world", C.POINTER(C.c_uint8)), ("edge_sat", C.POINTER(C.c_uint8)), ("witness_values", C.POINTER(C.c_int32)),
+                ("witness_kind", C.c_int32), ("witness_len", C.c_int32), ("n_vars", C.c_int32), ("rounds", C.c_int32 * 3),
+                ("seconds", C.c_double), ("seconds_kernels", C.c_double)]
+
+
+# the tokens of a CTL program and the comparisons of its atoms (include/stcsp_engine.h, STCSP_CTL_*)
+CTL_TRUE, CTL_FALSE, CTL_CMP_CONST, CTL_CMP_VAR = 1, 2, 3, 4
+CTL_NOT, CTL_AND, CTL_OR, CTL_IMPLIES = 10, 11, 12, 13
+CTL_EX, CTL_EF, CTL_EG, CTL_EU, CTL_AX, CTL_AF, CTL_AG, CTL_AU = 20, 21, 22, 23, 24, 25, 26, 27
+CTL_OPS = ("==", "!=", "<", "<=", ">", ">=")  # op k of an atom
+CTL_WITNESS = 1
+CTL_KINDS = ("none", "witness", "counterexample")
+CTL_MAX_NODES, CTL_MAX_SLOTS = 256, 16
+
+
+class CtlSyntaxError(ValueError):
+    """A formula stcsp_ctl_parse() refuses: .position is the 0-based offset into the text, .message what is wrong there."""
+
+    def __init__(self, position, message):
+        super().__init__(f"{position}: {message}")
+        self.position, self.message = position, message
+
+
+def _ctl_parse_names(names, text):
+    import numpy as np
+    lib = host_lib()
+    enc = [n.encode() for n in names]
+    arr = (C.c_char_p * max(len(enc), 1))(*enc)
+    p = Problem()
+    p.n_vars = len(enc)
+    p.var_names = C.cast(arr, C.POINTER(C.c_char_p))
+    words, n, pos = C.POINTER(C.c_int32)(), C.c_int32(), C.c_int32()
+    msg = C.create_string_buffer(256)
+    rc = lib.stcsp_ctl_parse(text.encode(), C.byref(p), C.byref(words), C.byref(n), C.byref(pos), msg, len(msg))
+    if rc == -1:
+        raise CtlSyntaxError(pos.value, msg.value.decode())
+    if rc != 0:
+        raise StcspError(rc, "ctl_parse failed")
+    try:
+        return _copy_array(words, n.value, np.int32)
+    finally:
+        lib.stcsp_host_free(words)
+
+
+def ctl_parse(model, text):
+    """Formula text -> the postfix program of Engine.ctl() / Automaton.ctl(), an int32 array (grammar: include/stcsp_host.h,
+    stcsp_ctl_parse). `model` is a Model, or a list of variable names. CtlSyntaxError with a position and a message for a
+    formula that does not parse or names an unknown variable."""
+    return _ctl_parse_names(model.var_names if isinstance(model, Model) else list(model), text)
+
+
+def _ctl_request(formula, names, witness):
+    import numpy as np
+    prog = _ctl_parse_names(names, formula) if isinstance(formula, str) else np.ascontiguousarray(formula, dtype=np.int32).reshape(-1)
+    rq = CtlRequest(prog.ctypes.data_as(C.POINTER(C.c_int32)), prog.size, CTL_WITNESS if witness else 0)
+    return rq, prog
+
+
+def _ctl_unpack(res):
+    """A CtlResult -> dict: n_worlds, n_initial, n_initial_sat, n_vars, seconds, seconds_kernels; "holds" (n_initial_sat == n_initial),
+    "possible" (n_initial_sat > 0), "vacuous" (n_initial == 0); rounds int32 [3]; copies of edge_world / edge_sat uint8 [n_edges of the
+    Result]; "witness": (kind, rows) with kind "none", "witness" or "counterexample" and rows an int32 array of full rows [len, n_vars]."""
+    import numpy as np
+    d = {k: getattr(res, k) for k in ("n_worlds", "n_initial", "n_initial_sat", "n_vars", "seconds", "seconds_kernels")}
+    d["holds"], d["possible"], d["vacuous"] = res.n_initial_sat == res.n_initial, res.n_initial_sat > 0, res.n_initial == 0
+    d["rounds"] = np.array(res.rounds[:], np.int32)
+    d["edge_world"] = _copy_array(res.edge_world, res.n_edges, np.uint8)
+    d["edge_sat"] = _copy_array(res.edge_sat, res.n_edges, np.uint8)
+    rows = _copy_array(res.witness_values, res.witness_len * res.n_vars, np.int32).reshape(res.witness_len, res.n_vars)
+    d["witness"] = (CTL_KINDS[res.witness_kind], rows)
+    return d
+
+
 ENGINE_SYMBOLS = [
     "stcsp_engine_create", "stcsp_engine_solve", "stcsp_engine_export", "stcsp_engine_destroy",
     "stcsp_engine_last_error", "stcsp_engine_begin", "stcsp_engine_expand_local",
@@ -571,7 +650,7 @@ ENGINE_SYMBOLS = [
     "stcsp_engine_adopt", "stcsp_engine_expand_variant", "stcsp_engine_kernel_choice", "stcsp_engine_quotient",
     "stcsp_engine_monitor_build", "stcsp_engine_monitor_check", "stcsp_engine_generator_build", "stcsp_engine_generate",
     "stcsp_engine_repair", "stcsp_engine_align", "stcsp_engine_infer", "stcsp_engine_posterior", "stcsp_engine_observer", "stcsp_engine_compare",
-    "stcsp_engine_components", "stcsp_engine_optimise",
+    "stcsp_engine_components", "stcsp_engine_optimise", "stcsp_engine_ctl",
 ]
 # include/stcsp_sharded.h: the superstep loop + in-process transport (libstcsp_hip.so), the RCCL transport (libstcsp_rccl.so)
 SHARDED_SYMBOLS_HIP = ["stcsp_engine_solve_sharded", "stcsp_local_group_create", "stcsp_local_group_transport", "stcsp_local_group_destroy"]
@@ -592,6 +671,7 @@ HOST_SYMBOLS = [
     "stcsp_compare_observers", "stcsp_comparison_get", "stcsp_comparison_free", "stcsp_automaton_num_vars", "stcsp_automaton_var_name",
     "stcsp_automaton_components", "stcsp_components_get", "stcsp_components_free",
     "stcsp_automaton_optimise", "stcsp_optimise_get", "stcsp_optimise_free",
+    "stcsp_ctl_parse", "stcsp_automaton_ctl", "stcsp_ctl_get", "stcsp_ctl_free",
 ]
 
 
@@ -696,6 +776,12 @@ def host_lib() -> C.CDLL:
         lib.stcsp_optimise_get.argtypes = [C.c_void_p]
         lib.stcsp_optimise_get.restype = C.POINTER(OptimiseResult)
         lib.stcsp_optimise_free.argtypes = [C.c_void_p]
+        lib.stcsp_ctl_parse.argtypes = [C.c_char_p, C.POINTER(Problem), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.c_char_p, C.c_size_t]
+        lib.stcsp_automaton_ctl.argtypes = [C.c_void_p, C.POINTER(CtlRequest), C.POINTER(C.c_void_p)]
+        lib.stcsp_ctl_get.argtypes = [C.c_void_p]
+        lib.stcsp_ctl_get.restype = C.POINTER(CtlResult)
+        lib.stcsp_ctl_free.argtypes = [C.c_void_p]
         lib.stcsp_automaton_num_vars.argtypes = [C.c_void_p]
         lib.stcsp_automaton_var_name.argtypes = [C.c_void_p, C.c_int]
         lib.stcsp_automaton_var_name.restype = C.c_char_p
@@ -767,6 +853,8 @@ def bind_engine_api(lib: C.CDLL, prefix: str = "stcsp_engine") -> None:
         g("components").argtypes = [C.c_void_p, C.POINTER(ComponentsOptions), C.POINTER(ComponentsResult)]
     if hasattr(lib, f"{prefix}_optimise"):
         g("optimise").argtypes = [C.c_void_p, C.POINTER(OptimiseRequest), C.POINTER(OptimiseResult)]
+    if hasattr(lib, f"{prefix}_ctl"):
+        g("ctl").argtypes = [C.c_void_p, C.POINTER(CtlRequest), C.POINTER(CtlResult)]
     if hasattr(lib, f"{prefix}_propagate"):
         g("propagate").argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64)]
@@ -1179,6 +1267,24 @@ class Automaton:
             return _optimise_unpack(lib.stcsp_optimise_get(h).contents, keep[1], int(lib.stcsp_automaton_num_states(self._h)))
         finally:
             lib.stcsp_optimise_free(h)
+
+    def ctl(self, formula, witness=False):
+        """A fair CTL query over the infinite solutions by the host twin of Engine.ctl() (contract: include/stcsp_engine.h,
+        stcsp_engine_ctl), on the automaton's current flags. formula: text (grammar: ctl_parse()) or a postfix program. Returns
+        the dict of _ctl_unpack()."""
+        lib = host_lib()
+        names = [lib.stcsp_automaton_var_name(self._h, i).decode() for i in range(lib.stcsp_automaton_num_vars(self._h))]
+        rq, keep = _ctl_request(formula, names, witness)
+        h = C.c_void_p()
+        rc = lib.stcsp_automaton_ctl(self._h, C.byref(rq), C.byref(h))
+        if rc != 0:
+            raise StcspError(rc, {-1: "ctl failed: a malformed program",
+                                  -2: f"ctl failed: the lowered formula is over a limit ({CTL_MAX_NODES} atoms and operators, {CTL_MAX_SLOTS} sets, a predicate stack of 64)",
+                                  -5: "ctl failed: a fixpoint did not converge, or two worlds out of one state carry the same full row"}.get(rc, "ctl failed"))
+        try:
+            return _ctl_unpack(lib.stcsp_ctl_get(h).contents)
+        finally:
+            lib.stcsp_ctl_free(h)
 
     def from_observer(self, obs, observable=None) -> "Automaton":
         """The observer `obs` (the dict of Engine.observer() or observer() for this automaton under `observable`) as an
@@ -1602,6 +1708,17 @@ class EngineBase:
         out = OptimiseResult()
         self._check(self._f("optimise")(self._h, C.byref(rq), C.byref(out)))
         return _optimise_unpack(out, keep[1], self.result.n_states)
+
+    def ctl(self, formula, witness=False):
+        """A fair CTL query over the infinite solutions on the device, after postprocess(): does `formula` hold on the first steps of
+        the solutions, where does it hold, and with witness=True a shortest witness (top EX / EU / EF) or counterexample (top AX / AG).
+        Only infinite solutions are quantified over; a model without one has 0 worlds and every query on it is vacuous. formula:
+        text (grammar: ctl_parse()) or a postfix program. Returns the dict of _ctl_unpack(); it replaces the result of an earlier
+        components() and touches no other service's state. Contract: include/stcsp_engine.h, stcsp_engine_ctl."""
+        rq, keep = _ctl_request(formula, self._model.var_names, witness)
+        out = CtlResult()
+        self._check(self._f("ctl")(self._h, C.byref(rq), C.byref(out)))
+        return _ctl_unpack(out)
 
     def automaton(self, result: Result | None = None) -> Automaton:
         return Automaton(self._model, result if result is not None else self.result)

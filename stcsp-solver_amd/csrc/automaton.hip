@@ -1,5 +1,5 @@
 // automaton.hip -- the host side of the services on the exported automaton: post-processing, bisimulation quotient, stream monitor,
-// generator, repair, alignment, inference, posterior marginals, observer and comparison, with the kernels they launch. No kernel is shared with the search (engine.hip).
+// generator, repair, alignment, inference, posterior marginals, observer, comparison, components, optimisation and fair CTL, with the kernels they launch. No kernel is shared with the search (engine.hip).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -23,6 +23,8 @@
 #include "dev_compare.hpp"
 #include "dev_components.hpp"
 #include "dev_optimise.hpp"
+#include "dev_ctl.hpp"
+#include "ctl_host.hpp"
 #include "repair_host.hpp"
 #include "align_host.hpp"
 #include "infer_host.hpp"
@@ -2358,6 +2360,275 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
     out->largest_cyclic = (int32_t)nmax;
     out->rounds[0] = launches_dp;
     out->rounds[1] = launches_karp;
+    out->seconds_kernels = ms_kernels * 1e-3;
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return STCSP_OK;
+}
+
+// Fair CTL over the infinite solutions (contract: stcsp_engine.h, stcsp_engine_ctl; dev_ctl.hpp). The
+// lowering is CtlProgram's, shared with the host twin. The component pass above runs first and its result is replaced; every
+// other device buffer is this call's own. A set of worlds is a slot of d_ctl_sets; the evaluation is a walk over the lowered
+// tree that holds at most the slots CtlProgram measured.
+int AutomatonServices::ctl(const AutomatonView &view, const stcsp_ctl_request *rq, stcsp_ctl_result *out) {
+    if (int rc = enter(view, "ctl", NEED_FLAGS, "stcsp_automaton_ctl")) return rc;
+    auto t0 = std::chrono::steady_clock::now();
+    const int N = v.N;
+    const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
+    CtlProgram prog;
+    if (int rc = prog.build(rq->program, rq->n_words, N)) return fail(rc, "%s", prog.error.c_str());
+    if (v.exp_edges > 0x7fffffffull || S > 0x3fffffffu) return fail(STCSP_E_NOMEM, "automaton too large for the device CTL pass");
+    double ms_kernels = 0;
+    {  // omega first: the call takes the view again
+        const stcsp_components_options co = {0, 0, 0};
+        stcsp_components_result cres;
+        if (int rc = components(view, &co, &cres)) return rc;
+        ms_kernels = cres.seconds_kernels * 1e3;
+    }
+    size_t budget = 0;
+    if (int rc = table_budget("STCSP_CTL_BYTES", budget)) return rc;
+    bool negated = false;
+    const int32_t wit = (rq->flags & STCSP_CTL_WITNESS) ? prog.witness_node(&negated) : -1;
+    // the slices of the maximal temporal-free subtrees, uploaded once: node -> (first word, length)
+    std::vector<int32_t> words_h, slice_off(prog.nodes.size(), -1), slice_len(prog.nodes.size(), 0);
+    {
+        std::vector<int32_t> todo{prog.root};
+        while (!todo.empty()) {
+            const int32_t r = todo.back();
+            todo.pop_back();
+            const CtlNode &n = prog.nodes[(size_t)r];
+            if (!n.temporal) {
+                slice_off[(size_t)r] = (int32_t)words_h.size();
+                prog.slice(r, words_h);
+                slice_len[(size_t)r] = (int32_t)words_h.size() - slice_off[(size_t)r];
+                continue;
+            }
+            if (n.a >= 0) todo.push_back(n.a);
+            if (n.b >= 0) todo.push_back(n.b);
+        }
+    }
+    HIPCHK(reserve_all(S, 1, ctlq.d_ctl_deg, ctlq.d_ctl_off, ctlq.d_ctl_cur));
+    HIPCHK(ctlq.d_ctl_ctl.reserve_exact(CTL_WORDS));
+    HIPCHK(ctlq.d_ctl_prog.reserve(words_h.size(), 1));
+    HIPCHK(ev.ready(2));
+    const unsigned eb = (E + 255) / 256;
+    uint32_t cw[CTL_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool open = false;
+    int32_t sweeps = 0, launches = 0, most_outer = 0;
+    auto begin = [&]() -> int {
+        if (!open) HIPCHK(hipEventRecord(ev[0], v.stream));
+        open = true;
+        return STCSP_OK;
+    };
+    auto flush = [&]() -> int {  // ends a batch of launches: the control words, and the batch's time on the device
+        if (int rc = begin()) return rc;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev[1], v.stream));
+        HIPCHK(hipMemcpyAsync(cw, ctlq.d_ctl_ctl.p, sizeof cw, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipStreamSynchronize(v.stream));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        ms_kernels += ms;
+        open = false;
+        return STCSP_OK;
+    };
+    // the worlds as CSR by source, in this call's buffers: the omega bytes stand where the builder takes `live`
+    uint32_t W = 0;
+    if (S) {
+        if (int rc = begin()) return rc;
+        HIPCHK(hipMemsetAsync(ctlq.d_ctl_ctl.p, 0, sizeof cw, v.stream));
+        HIPCHK(hipMemsetAsync(ctlq.d_ctl_deg.p, 0, (size_t)S * sizeof(uint32_t), v.stream));
+        if (E)
+            hipLaunchKernelGGL(k_s_count, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p, (const uint8_t *)scc.d_somega.p,
+                               ctlq.d_ctl_deg.p);
+        hipLaunchKernelGGL(k_s_scan, dim3(1), dim3(256), 0, v.stream, S, (S + 255) / 256, (const uint32_t *)ctlq.d_ctl_deg.p, ctlq.d_ctl_off.p, ctlq.d_ctl_cur.p);
+        HIPCHK(hipMemcpyAsync(&W, ctlq.d_ctl_off.p + S, sizeof W, hipMemcpyDeviceToHost, v.stream));
+        launches += 2;
+        if (int rc = flush()) return rc;
+        if (W > E) return fail(STCSP_E_INTERNAL, "ctl: %u worlds of %u edges", W, E);
+    }
+    const size_t nw = ((size_t)W + 63) / 64;
+    const int n_slots = prog.nodes[(size_t)prog.root].slots;
+    const size_t need = 3 * ((size_t)S + 1) * sizeof(uint32_t) + (size_t)W * 3 * sizeof(uint32_t) + 2 * (size_t)S + 2 * (size_t)E +
+                        ((size_t)n_slots + 1) * nw * sizeof(unsigned long long) + (wit >= 0 ? 2 * ((size_t)W + 16) * sizeof(uint32_t) : 0) +
+                        words_h.size() * sizeof(int32_t);
+    if (need > budget)
+        return fail(STCSP_E_NOMEM, "ctl: %u worlds, %u states, %u edges and %d sets need %zu bytes, the budget (STCSP_CTL_BYTES) is %zu", W, S, E, n_slots, need, budget);
+    ctlq.ctl_world.assign(E, 0);
+    ctlq.ctl_sat.assign(E, 0);
+    ctlq.ctl_witness.clear();
+    int32_t witness_kind = STCSP_CTL_NONE, witness_len = 0;
+    if (W) {
+        HIPCHK(reserve_all(W, 1, ctlq.d_ctl_src, ctlq.d_ctl_dst, ctlq.d_ctl_eid));
+        HIPCHK(ctlq.d_ctl_sets.reserve(((size_t)n_slots + 1) * nw));
+        HIPCHK(ctlq.d_ctl_some.reserve(2 * (size_t)S));
+        HIPCHK(reserve_all(E, 1, ctlq.d_ctl_world, ctlq.d_ctl_sat));
+        if (wit >= 0) HIPCHK(reserve_all((size_t)W + 16, 0, ctlq.d_ctl_dist, ctlq.d_ctl_weid));
+        const unsigned wb = (W + 255) / 256, bb = (unsigned)((nw + 255) / 256);
+        const uint32_t *csrc = ctlq.d_ctl_src.p, *cdst = ctlq.d_ctl_dst.p, *ceid = ctlq.d_ctl_eid.p;
+        auto set = [&](int slot) { return ctlq.d_ctl_sets.p + (size_t)slot * nw; };
+        const unsigned long long *fin = set(n_slots);
+        std::vector<uint8_t> used((size_t)n_slots, 0);
+        auto take = [&](int &slot) -> int {
+            for (slot = 0; slot < n_slots; slot++)
+                if (!used[(size_t)slot]) {
+                    used[(size_t)slot] = 1;
+                    return STCSP_OK;
+                }
+            return fail(STCSP_E_INTERNAL, "ctl: more than the %d set slots measured", n_slots);
+        };
+        if (int rc = begin()) return rc;
+        hipLaunchKernelGGL(k_s_fill, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p, (const uint8_t *)scc.d_somega.p,
+                           ctlq.d_ctl_cur.p, W, ctlq.d_ctl_src.p, ctlq.d_ctl_dst.p, ctlq.d_ctl_eid.p);
+        hipLaunchKernelGGL(k_ctl_fin, dim3(wb), dim3(256), 0, v.stream, W, cdst, (const uint8_t *)post.d_pfinal.p, set(n_slots));
+        HIPCHK(hipMemsetAsync(ctlq.d_ctl_some.p, 0, 2 * (size_t)S, v.stream));
+        if (!words_h.empty()) HIPCHK(hipMemcpyAsync(ctlq.d_ctl_prog.p, words_h.data(), words_h.size() * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+        launches += 2;
+        int parity = 0;  // which half of some[] the next sweep marks; the other half is the one its second launch clears
+        // one sweep: EX of `from`, combined into `to` (k_ctl_pre); two launches
+        auto sweep = [&](int from, const unsigned long long *f, int or_old, int to, uint32_t *dist, uint32_t level) {
+            uint8_t *mark = ctlq.d_ctl_some.p + (size_t)parity * S, *other = ctlq.d_ctl_some.p + (size_t)(parity ^ 1) * S;
+            hipLaunchKernelGGL(k_ctl_mark, dim3(wb), dim3(256), 0, v.stream, W, csrc, (const unsigned long long *)set(from), mark);
+            hipLaunchKernelGGL(k_ctl_pre, dim3(wb), dim3(256), 0, v.stream, W, csrc, cdst, (const uint8_t *)mark, other, f, or_old, set(to), dist, level,
+                               ctlq.d_ctl_ctl.p);
+            parity ^= 1;
+            sweeps++;
+            launches += 2;
+        };
+        auto boolean = [&](int op, int a, int b, int to) {
+            hipLaunchKernelGGL(k_ctl_bool, dim3(bb), dim3(256), 0, v.stream, W, op, (const unsigned long long *)set(a), (const unsigned long long *)set(b), set(to));
+            launches++;
+        };
+        const int kBatch = 4;
+        // z = the least fixpoint of z | (f & EX z); a batch of sweeps, then one look at the changed word; *levels: the sweeps run
+        auto until = [&](int f, int z, uint32_t *dist, uint32_t *levels) -> int {
+            for (uint32_t done = 0;;) {
+                if (int rc = begin()) return rc;
+                HIPCHK(hipMemsetAsync(ctlq.d_ctl_ctl.p + CTL_CHANGED, 0, sizeof(uint32_t), v.stream));
+                for (int b = 0; b < kBatch; b++) sweep(z, set(f), 1, z, dist, ++done);
+                if (int rc = flush()) return rc;
+                if (levels) *levels = done;
+                if (!cw[CTL_CHANGED]) return STCSP_OK;
+                if (done > W + 8) return fail(STCSP_E_INTERNAL, "ctl: an EU fixpoint did not converge in %u rounds", done);
+            }
+        };
+        // the witness walk, at the node it belongs to (the ! above it works in place afterwards)
+        auto walk = [&](uint32_t max_len, const uint32_t *dist, const unsigned long long *set_a, const unsigned long long *set_b) -> int {
+            std::vector<uint32_t> weid(max_len);
+            if (int rc = begin()) return rc;
+            hipLaunchKernelGGL(k_ctl_walk, dim3(1), dim3(64), 0, v.stream, W, N, max_len, (const uint32_t *)ctlq.d_ctl_off.p, cdst, ceid, dist, set_a, set_b, v.d_oval,
+                               ctlq.d_ctl_weid.p, ctlq.d_ctl_ctl.p);
+            launches++;
+            HIPCHK(hipMemcpyAsync(weid.data(), ctlq.d_ctl_weid.p, (size_t)max_len * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+            if (int rc = flush()) return rc;
+            if (cw[CTL_DUPLICATE]) return fail(STCSP_E_INTERNAL, "ctl: two worlds out of state %u carry the same full row", cw[CTL_DUPLICATE] - 1);
+            if (cw[CTL_STUCK]) return fail(STCSP_E_INTERNAL, "ctl: the witness walk stops at state %u", cw[CTL_STUCK] - 1);
+            const uint32_t len = cw[CTL_WITNESS_LEN];
+            if (len > max_len) return fail(STCSP_E_INTERNAL, "ctl: a witness of %u worlds, %u at the most", len, max_len);
+            for (uint32_t t = 0; t < len; t++) {
+                if (weid[t] >= E) return fail(STCSP_E_INTERNAL, "ctl: the witness names edge %u of %u", weid[t], E);
+                ctlq.ctl_witness.insert(ctlq.ctl_witness.end(), v.h_oval + (size_t)weid[t] * N, v.h_oval + ((size_t)weid[t] + 1) * N);
+            }
+            witness_len = (int32_t)len;
+            if (len) witness_kind = negated ? STCSP_CTL_IS_COUNTEREXAMPLE : STCSP_CTL_IS_WITNESS;
+            return STCSP_OK;
+        };
+        // the set of node r into a slot it takes
+        auto eval = [&](auto &&self, int32_t r, int &slot) -> int {
+            const CtlNode &n = prog.nodes[(size_t)r];
+            if (!n.temporal) {
+                if (int rc = take(slot)) return rc;
+                hipLaunchKernelGGL(k_ctl_pred, dim3(wb), dim3(256), 0, v.stream, W, N, ceid, v.d_oval, (const int32_t *)ctlq.d_ctl_prog.p + slice_off[(size_t)r],
+                                   (int)slice_len[(size_t)r], set(slot));
+                launches++;
+                return STCSP_OK;
+            }
+            int a = -1, b = -1;
+            if (int rc = self(self, n.a, a)) return rc;
+            if (n.b >= 0)
+                if (int rc = self(self, n.b, b)) return rc;
+            slot = a;
+            switch (n.kind) {
+            case STCSP_CTL_NOT: boolean(CTL_B_NOT, a, a, a); return STCSP_OK;
+            case STCSP_CTL_AND:
+            case STCSP_CTL_OR:
+                boolean(n.kind == STCSP_CTL_AND ? CTL_B_AND : CTL_B_OR, a, b, a);
+                used[(size_t)b] = 0;
+                return STCSP_OK;
+            case STCSP_CTL_EX:
+                if (r != wit) {
+                    sweep(a, nullptr, 0, a, nullptr, 0);
+                    return STCSP_OK;
+                }
+                if (int rc = take(slot)) return rc;
+                boolean(CTL_B_COPY, a, a, slot);  // (the second launch compares with what the target holds)
+                sweep(a, nullptr, 0, slot, nullptr, 0);
+                used[(size_t)a] = 0;
+                return walk(2, nullptr, set(slot), set(a));
+            case STCSP_CTL_EU: {
+                slot = b;
+                uint32_t levels = 0;
+                uint32_t *dist = r == wit ? ctlq.d_ctl_dist.p : nullptr;
+                if (dist) {
+                    hipLaunchKernelGGL(k_ctl_dist_init, dim3(wb), dim3(256), 0, v.stream, W, (const unsigned long long *)set(b), dist);
+                    launches++;
+                }
+                if (int rc = until(a, b, dist, &levels)) return rc;
+                used[(size_t)a] = 0;
+                return dist ? walk(std::min<uint32_t>(levels + 1, W + 16), dist, nullptr, nullptr) : (int)STCSP_OK;
+            }
+            default: {  // EG, Emerson-Lei: z = f & EX E[f U (z & Fin)] from z = f down
+                int z = -1, t = -1;
+                if (int rc = take(z)) return rc;
+                if (int rc = take(t)) return rc;
+                boolean(CTL_B_COPY, a, a, z);
+                for (int32_t round = 1;; round++) {
+                    most_outer = std::max(most_outer, round);
+                    hipLaunchKernelGGL(k_ctl_bool, dim3(bb), dim3(256), 0, v.stream, W, (int)CTL_B_AND, (const unsigned long long *)set(z), fin, set(t));
+                    launches++;
+                    if (int rc = until(a, t, nullptr, nullptr)) return rc;
+                    if (int rc = begin()) return rc;
+                    HIPCHK(hipMemsetAsync(ctlq.d_ctl_ctl.p + CTL_CHANGED, 0, sizeof(uint32_t), v.stream));
+                    sweep(t, set(a), 0, z, nullptr, 0);
+                    if (int rc = flush()) return rc;
+                    if (!cw[CTL_CHANGED]) break;
+                    if ((uint32_t)round > W + 8) return fail(STCSP_E_INTERNAL, "ctl: an EG fixpoint did not converge in %d rounds", round);
+                }
+                used[(size_t)a] = used[(size_t)t] = 0;
+                slot = z;
+                return STCSP_OK;
+            }
+            }
+        };
+        int top = -1;
+        if (int rc = eval(eval, prog.root, top)) return rc;
+        if (int rc = begin()) return rc;
+        HIPCHK(hipMemsetAsync(ctlq.d_ctl_world.p, 0, E, v.stream));
+        HIPCHK(hipMemsetAsync(ctlq.d_ctl_sat.p, 0, E, v.stream));
+        HIPCHK(hipMemsetAsync(ctlq.d_ctl_ctl.p, 0, sizeof cw, v.stream));
+        hipLaunchKernelGGL(k_ctl_scatter, dim3(wb), dim3(256), 0, v.stream, W, csrc, ceid, (const unsigned long long *)set(top), ctlq.d_ctl_world.p, ctlq.d_ctl_sat.p,
+                           ctlq.d_ctl_ctl.p);
+        launches++;
+        HIPCHK(hipMemcpyAsync(ctlq.ctl_world.data(), ctlq.d_ctl_world.p, E, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(ctlq.ctl_sat.data(), ctlq.d_ctl_sat.p, E, hipMemcpyDeviceToHost, v.stream));
+        if (int rc = flush()) return rc;
+    }
+    ctlq.ctl_world.reserve(1);
+    ctlq.ctl_sat.reserve(1);
+    ctlq.ctl_witness.reserve(1);
+    memset(out, 0, sizeof *out);
+    out->n_worlds = W;
+    out->n_initial = W ? cw[CTL_INITIAL] : 0;
+    out->n_initial_sat = W ? cw[CTL_INITIAL_SAT] : 0;
+    out->n_edges = E;
+    out->edge_world = ctlq.ctl_world.data();
+    out->edge_sat = ctlq.ctl_sat.data();
+    out->witness_values = ctlq.ctl_witness.data();
+    out->witness_kind = witness_kind;
+    out->witness_len = witness_len;
+    out->n_vars = N;
+    out->rounds[0] = sweeps;
+    out->rounds[1] = most_outer;
+    out->rounds[2] = launches;
     out->seconds_kernels = ms_kernels * 1e-3;
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;

@@ -51,6 +51,7 @@ struct AutomatonServices {
     int compare(const AutomatonView &view, const stcsp_compare_request *rq, stcsp_compare_result *out);
     int components(const AutomatonView &view, const stcsp_components_options *co, stcsp_components_result *out);
     int optimise(const AutomatonView &view, const stcsp_optimise_request *rq, stcsp_optimise_result *out);
+    int ctl(const AutomatonView &view, const stcsp_ctl_request *rq, stcsp_ctl_result *out);
 
 private:
     enum Need { NEED_EXPORT, NEED_FLAGS, NEED_MONITOR, NEED_GENERATOR };
@@ -232,6 +233,14 @@ private:
         std::vector<int64_t> opt_best, opt_state_best, opt_woff, opt_num, opt_den;
         std::vector<int32_t> opt_wvalues, opt_wstates, opt_component;
     } opt;
+    struct Ctl {  // fair CTL (dev_ctl.hpp): nothing is kept between calls; the vectors back the result
+        DevBuf<uint32_t> d_ctl_deg, d_ctl_off, d_ctl_cur, d_ctl_src, d_ctl_dst, d_ctl_eid, d_ctl_dist, d_ctl_weid, d_ctl_ctl;
+        DevBuf<unsigned long long> d_ctl_sets;  // the set slots, then Fin
+        DevBuf<uint8_t> d_ctl_some, d_ctl_world, d_ctl_sat;
+        DevBuf<int32_t> d_ctl_prog;
+        std::vector<uint8_t> ctl_world, ctl_sat;
+        std::vector<int32_t> ctl_witness;
+    } ctlq;
 };
 
 }  // namespace stcsp

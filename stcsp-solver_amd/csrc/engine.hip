@@ -2485,6 +2485,10 @@ int stcsp_engine_optimise(stcsp_engine *e, const stcsp_optimise_request *request
     if (!e || !request || !result) return STCSP_E_INVALID;
     return e->services.optimise(e->view(), request, result);
 }
+int stcsp_engine_ctl(stcsp_engine *e, const stcsp_ctl_request *request, stcsp_ctl_result *result) {
+    if (!e || !request || !result) return STCSP_E_INVALID;
+    return e->services.ctl(e->view(), request, result);
+}
 
 void stcsp_engine_destroy(stcsp_engine *e) { delete e; }
 

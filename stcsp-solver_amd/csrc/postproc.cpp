@@ -29,6 +29,7 @@
 #include "observer_host.hpp"
 #include "components_host.hpp"
 #include "optimise_host.hpp"
+#include "ctl_host.hpp"
 #include "compare_host.hpp"
 #include "infer_host.hpp"
 #include "posterior_host.hpp"
@@ -1016,6 +1017,10 @@ struct stcsp_optimise {
     stcsp::HostOptimise o;
     stcsp_optimise_result res;
 };
+struct stcsp_ctl {
+    stcsp::HostCtl c;
+    stcsp_ctl_result res;
+};
 
 extern "C" {
 
@@ -1582,6 +1587,68 @@ int stcsp_automaton_optimise(const stcsp_automaton *a, const stcsp_optimise_requ
 }
 const stcsp_optimise_result *stcsp_optimise_get(const stcsp_optimise *o) { return o ? &o->res : nullptr; }
 void stcsp_optimise_free(stcsp_optimise *o) { delete o; }
+
+int stcsp_ctl_parse(const char *text, const stcsp_problem *problem, int32_t **program, int32_t *n_words, int32_t *error_pos, char *message,
+                    size_t message_len) {
+    if (!text || !problem || !program || !n_words) return STCSP_E_INVALID;
+    *program = nullptr;
+    *n_words = 0;
+    try {
+        stcsp::CtlParser parser(text, problem->n_vars, problem->var_names);
+        if (!parser.parse()) {
+            if (error_pos) *error_pos = (int32_t)parser.error_pos;
+            if (message && message_len) snprintf(message, message_len, "%s", parser.error.c_str());
+            return STCSP_E_INVALID;
+        }
+        int32_t *w = (int32_t *)malloc(parser.out.size() * sizeof(int32_t));
+        if (!w) return STCSP_E_NOMEM;
+        memcpy(w, parser.out.data(), parser.out.size() * sizeof(int32_t));
+        *program = w;
+        *n_words = (int32_t)parser.out.size();
+    } catch (const std::bad_alloc &) {
+        return STCSP_E_NOMEM;
+    }
+    return STCSP_OK;
+}
+
+int stcsp_automaton_ctl(const stcsp_automaton *a, const stcsp_ctl_request *request, stcsp_ctl **out) {
+    if (!a || !request || !out) return STCSP_E_INVALID;
+    stcsp_ctl *h = nullptr;
+    try {
+        h = new stcsp_ctl();
+        const auto t0 = std::chrono::steady_clock::now();
+        stcsp::CtlProgram prog;
+        int rc = prog.build(request->program, request->n_words, a->a.n_vars);
+        if (rc == STCSP_OK) rc = h->c.run(generator_view(a->a), prog, request->flags);
+        if (rc != STCSP_OK) {
+            delete h;
+            return rc;
+        }
+        stcsp::HostCtl &c = h->c;
+        c.edge_world.reserve(1);  // (empty vectors still give valid pointers)
+        c.edge_sat.reserve(1);
+        c.witness_values.reserve(1);
+        memset(&h->res, 0, sizeof h->res);
+        h->res.n_worlds = c.n_worlds;
+        h->res.n_initial = c.n_initial;
+        h->res.n_initial_sat = c.n_initial_sat;
+        h->res.n_edges = (int64_t)c.edge_world.size();
+        h->res.edge_world = c.edge_world.data();
+        h->res.edge_sat = c.edge_sat.data();
+        h->res.witness_values = c.witness_values.data();
+        h->res.witness_kind = c.witness_kind;
+        h->res.witness_len = c.witness_len;
+        h->res.n_vars = c.n_vars;
+        h->res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    } catch (const std::bad_alloc &) {
+        delete h;
+        return STCSP_E_NOMEM;
+    }
+    *out = h;
+    return STCSP_OK;
+}
+const stcsp_ctl_result *stcsp_ctl_get(const stcsp_ctl *c) { return c ? &c->res : nullptr; }
+void stcsp_ctl_free(stcsp_ctl *c) { delete c; }
 
 char *stcsp_automaton_canonical(const stcsp_automaton *a, size_t *len) {
     if (!a) return nullptr;

@@ -2,7 +2,7 @@
 // (src/stcsp.y:180-219 main, src/solver.cpp:195-359 solve): same flags, same stdout contract,
 // same solutions.dot. The search itself runs on the MI355X engine behind the C-ABI.
 //
-//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--observer[=all|NAME[,NAME...]] [--compare=<file>]] [--components[=bottom|all|<N>]] [--optimise=<spec>] [--check=<file>]
+//   stcsp [-s] [-m<sec>] [-t] [-a] [-z] [-k<K>] [-l<level>] [--binary=<file>] [--shards=<N>] [--intervals] [--quotient[=all]] [--observer[=all|NAME[,NAME...]] [--compare=<file>]] [--components[=bottom|all|<N>]] [--optimise=<spec>] [--ctl=<formula>] [--check=<file>]
 //         [--sample=<N>:<L>[:<seed>] [--sample-final] [--sample-mask=all]] [--count=<L>]
 //         [--repair=<file> [--repair-final]] [--align=<file> [--align-costs=<skip>:<gap>] [--align-final]] [--infer=<file> [--infer-final] [--infer-draws=<D>[:<seed>]]]
 //         [--posterior=<file> [--posterior-final] [--posterior-weights=<name>=<value>:<weight>[,...]]] input.csp
@@ -30,6 +30,14 @@
 // <num>/<den>" per cyclic component and "optimise: omega: mean <num>/<den> in component <c>" (or "optimise: omega: none"), the
 // infimum of the long-run mean cost over the infinite solutions. stdout and the written files are unchanged. On the device for an
 // unsharded solve, by the host twin otherwise.
+//
+// --ctl=<formula> (not in the reference) asks a temporal question about the INFINITE solutions in fair CTL (include/stcsp_engine.h,
+// stcsp_engine_ctl; the grammar: include/stcsp_host.h, stcsp_ctl_parse), e.g. --ctl='AG EF m == 0'. To stderr: a line "ctl: <n> steps
+// on infinite solutions, holds at <k> of <n> first steps: yes|no|vacuous" and, where the contract gives one, a line "ctl: # name
+// name ..." of the variables of the default mask and a line "ctl: witness:" or "ctl: counterexample:" with the rows in the format
+// --check= reads, separated by ';'. A formula that does not parse ends the run with status 1 and "--ctl: <position>: <message>"
+// before anything is solved. stdout and the written files are unchanged. On the device for an unsharded solve, by the host twin
+// otherwise.
 //
 // --compare=<file> (not in the reference; only together with --observer) compares what this model shows with what another one
 // shows (include/stcsp_engine.h, stcsp_engine_compare). The file is a binary automaton written by --binary= of any run: it
@@ -149,6 +157,7 @@ struct Flags {
     long long components_lassos = 0;  // 0 none, -1 all, n the first n
     bool components_bottom = false;
     const char *optimise = nullptr;  // the text after --optimise=
+    const char *ctl = nullptr;       // the text after --ctl=
     int prefix_k = 2, time_limit = 0, shards = 1;
     const char *file = nullptr;
     const char *binary = nullptr;
@@ -863,6 +872,31 @@ static int report_optimum(const Flags &f, const stcsp_problem *p, const stcsp_au
     return 0;
 }
 
+// --ctl: a fair CTL query over the infinite solutions; on the device (eng: a finished postprocess()) or by the host twin on `a`'s
+// current flags (eng NULL). program: what load() parsed. stderr.
+static int report_ctl(const stcsp_problem *p, const std::vector<int32_t> &program, const stcsp_automaton *a, stcsp_engine *eng) {
+    const stcsp_ctl_request rq = {program.data(), (int32_t)program.size(), STCSP_CTL_WITNESS};
+    stcsp_ctl_result dev;
+    stcsp_ctl *twin = nullptr;
+    const stcsp_ctl_result *r = &dev;
+    if (eng) {
+        if (stcsp_engine_ctl(eng, &rq, &dev) != STCSP_OK) return engine_error(eng);
+    } else {
+        if (stcsp_automaton_ctl(a, &rq, &twin) != STCSP_OK) return host_error("the formula could not be evaluated");
+        r = stcsp_ctl_get(twin);
+    }
+    fprintf(stderr, "ctl: %lld steps on infinite solutions, holds at %lld of %lld first steps: %s\n", (long long)r->n_worlds, (long long)r->n_initial_sat,
+            (long long)r->n_initial, r->n_initial == 0 ? "vacuous" : r->n_initial_sat == r->n_initial ? "yes" : "no");
+    if (r->witness_kind != STCSP_CTL_NONE) {
+        fprintf(stderr, "ctl: ");
+        print_header(stderr, p, nullptr);
+        fprintf(stderr, r->witness_kind == STCSP_CTL_IS_WITNESS ? "ctl: witness:" : "ctl: counterexample:");
+        print_steps(stderr, p, r->witness_values, r->n_vars, 0, r->witness_len);
+    }
+    stcsp_ctl_free(twin);
+    return 0;
+}
+
 // --observer: replace *a by its observer, built on the device (eng: a finished postprocess()) or by the host twin (eng NULL);
 // with --quotient, folded by the host bisimulation under the same mask
 static int replace_by_observer(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, stcsp_engine *eng) {
@@ -926,7 +960,8 @@ static int observe(const Flags &f, const stcsp_problem *p, stcsp_automaton **a, 
 
 // Every service the flags ask for, in this order, on the device (eng: a finished postprocess() whose flags *a has adopted) or by
 // the host twins on *a's current flags (eng NULL). The one list of services: a new one is entered here and nowhere else.
-static int run_services(const Flags &f, const stcsp_problem *p, const Streams &streams, stcsp_automaton **a, stcsp_engine *eng) {
+static int run_services(const Flags &f, const stcsp_problem *p, const Streams &streams, const std::vector<int32_t> &ctl_program, stcsp_automaton **a,
+                        stcsp_engine *eng) {
     if (f.check && check(f, p, streams, *a, eng)) return 1;
     if ((f.sample || f.count_len >= 0) && generate(f, p, *a, eng)) return 1;
     if (f.repair && repair(f, p, streams, *a, eng)) return 1;
@@ -935,6 +970,7 @@ static int run_services(const Flags &f, const stcsp_problem *p, const Streams &s
     if (f.posterior && posterior(f, p, streams, *a, eng)) return 1;
     if (f.components && report_components(f, p, *a, eng)) return 1;
     if (f.optimise && report_optimum(f, p, *a, eng)) return 1;
+    if (f.ctl && report_ctl(p, ctl_program, *a, eng)) return 1;
     if (f.observer && observe(f, p, a, eng)) return 1;
     if (f.quotient && !f.observer && fold(f, p, a, eng)) return 1;  // (with --observer, observe() has folded the observer)
     return 0;
@@ -945,6 +981,7 @@ struct Run {
     stcsp_model *model = nullptr;
     const stcsp_problem *p = nullptr;
     Streams streams;       // of the one streams file, if any
+    std::vector<int32_t> ctl_program;  // of --ctl
     FILE *info = stdout;   // the adver and statistics lines: stderr when stdout holds a service's answers only
     double init_time = 0;
     ~Run() { stcsp_model_free(model); }  // (on the early returns too; after the engines, which are destroyed before a return 0)
@@ -966,6 +1003,16 @@ static int load(const Flags &f, Run &run) {
     bool missing_ok = false;
     const char *path = f.streams_file(&missing_ok);
     if (path && read_streams(path, run.p, run.streams, missing_ok)) return 1;
+    if (f.ctl) {  // before anything is solved: a formula that does not parse ends the run
+        int32_t *words = nullptr, n_words = 0, at = 0;
+        char message[256] = "";
+        if (stcsp_ctl_parse(f.ctl, run.p, &words, &n_words, &at, message, sizeof message) != STCSP_OK) {
+            fprintf(stderr, "--ctl: %d: %s\n", at, message);
+            return 1;
+        }
+        run.ctl_program.assign(words, words + n_words);
+        stcsp_host_free(words);
+    }
     run.info = f.quiet() ? stderr : stdout;
     run.init_time = cpu_time() - t_init;
     return 0;
@@ -1028,7 +1075,7 @@ static int run_once(const Flags &f, bool print_line, double *total) {
         if (f.adv1) fprintf(run.info, "adver1: %d; ", post.adver1);
         if (f.adv2) fprintf(run.info, "adver2: %d\n", post.adver2);
     }
-    if (run_services(f, run.p, run.streams, &a, device)) return 1;
+    if (run_services(f, run.p, run.streams, run.ctl_program, &a, device)) return 1;
     finish(f, run, a, res, solve_time, t_proc, print_line, total);
     stcsp_engine_destroy(eng);
     return 0;
@@ -1084,7 +1131,7 @@ static int run_sharded(const Flags &f, bool print_line, double *total) {
     stcsp_automaton *a = nullptr;
     stcsp_automaton_build(run.p, stcsp_merged_result(mg), &a);
     host_passes(f, a, run.info);
-    if (run_services(f, run.p, run.streams, &a, nullptr)) return 1;
+    if (run_services(f, run.p, run.streams, run.ctl_program, &a, nullptr)) return 1;
     finish(f, run, a, *stcsp_merged_result(mg), solve_time, t_proc, print_line, total);
     stcsp_merged_free(mg);
     stcsp_local_group_destroy(group);
@@ -1126,6 +1173,14 @@ int main(int argc, char **argv) {
         }
         if (strncmp(a, "--optimise=", 11) == 0) {
             f.optimise = a + 11;
+            continue;
+        }
+        if (strcmp(a, "--ctl") == 0 || strncmp(a, "--ctl=", 6) == 0) {
+            if (a[5] != '=') {
+                fprintf(stderr, "--ctl takes a formula, as in --ctl='AG EF m == 0'\n");
+                return 1;
+            }
+            f.ctl = a + 6;
             continue;
         }
         if (strncmp(a, "--compare=", 10) == 0) {
