@@ -1378,6 +1378,31 @@ __device__ __forceinline__ void until_flags(const Ctx &c, int lane, unsigned lon
     if (KR == 2 && u1 >= 0 && u1 < nu) kw2 = (uint32_t)((u1 < 64 ? f0 >> u1 : f1 >> (u1 - 64)) & 1ull);
 }
 
+// 1: the one-register shape builds a leaf's successor block only once table_commit has said that the leaf opens a new state
+// (expand_node): 95 % of partialorder_14's leaves open none. 0: at every leaf, inside process_node, like the other kernels (whose
+// sharded candidates need the block before the owner is known). Measured: 1 takes 1.2 % off the kernel's launches
+// and three VGPRs off its 79, moves the benchmark's figure by less than its spread and puts three more scalars into spill lanes,
+// over the kernel's budget of 75 -- so it is off.
+#ifndef STCSP_LEAF_SUCCESSOR_ON_DEMAND
+#define STCSP_LEAF_SUCCESSOR_ON_DEMAND 0
+#endif
+// Word `idx` (per lane) of a leaf's time-advanced block (variableAdvanceOneTimeStep, variable.cpp:94-108): point p <- point p+1,
+// last point <- the initial domains under the next constraint set. Every lane calls it (the gather is a cross-lane read).
+// "Last point" is idx + N >= NK and its variable idx - (K-1)*N: no division by the run-time N.
+template <int DR, int L>
+__device__ __forceinline__ uint32_t successor_word(const Ctx &c, const Img<L> &P, const Dom<DR> &dom, int next_set, int idx) {
+    const bool inner = idx + c.N < c.NK;
+    const uint32_t shifted = dom.gather(inner ? idx + c.N : 0);
+    uint32_t nb = 0;
+    if (idx < c.NK) nb = inner ? shifted : (uint32_t)P.v(c.o.var_init + next_set * c.o.init_stride + idx - (c.K - 1) * c.N);
+    return nb;
+}
+template <int DR, int L>
+__device__ __forceinline__ void successor_block(const Ctx &c, const Img<L> &P, const Dom<DR> &dom, int next_set, int lane, uint32_t (&nblk)[DR]) {
+#pragma unroll
+    for (int q = 0; q < DR; q++) nblk[q] = successor_word<DR, L>(c, P, dom, next_set, q * 64 + lane);
+}
+
 // SHP: the one-register LITE shape (engine.hip shape1) -- DR = 1, image in LDS, no until constraint, at most 64 lane-revised items
 // per set (one sweep pass) of at most three variables, unsharded. What only other programs need is compiled out: the pass loop of
 // the sweep, the fourth gather and the fourth table dimension, the until check items and the leaf's until flags.
@@ -1863,19 +1888,13 @@ __device__ int process_node(const Ctx &c, const Img<L> &P, int lane, int *lds_va
     lo.next_tag = next_tag;
     lo.new_expire = new_expire;
     lo.owner = SHP ? 0 : key_owner(h, c.world, c.KL, next_tag);  // (SHP: unsharded)
-    // edge label (Edge::values) and the time-advanced block (variableAdvanceOneTimeStep,
-    // variable.cpp:94-108: point p <- point p+1, last point <- [lb,ub]), lane-striped
+    // edge label (Edge::values) and the time-advanced block (successor_word), lane-striped (STCSP_LEAF_SUCCESSOR_ON_DEMAND: SHP
+    // commits every leaf in place, and expand_node builds the block after the commit, for new states only)
 #pragma unroll
     for (int q = 0; q < DR; q++) {
         int idx = q * 64 + lane;
         lo.evals[q] = idx < c.N ? (uint32_t)(P.v(c.o.var_lb + idx) + __ffs((int)dom.r[q]) - 1) : 0u;
-        uint32_t shifted = dom.gather(idx + c.N < c.NK ? idx + c.N : 0);
-        uint32_t nb = 0;
-        if (idx < c.NK) {
-            int p = idx / c.N, v = idx - p * c.N;
-            nb = (p + 1 < c.K) ? shifted : (uint32_t)P.v(c.o.var_init + next_set * c.o.init_stride + v);
-        }
-        lo.nblk[q] = nb;
+        if constexpr (!(STCSP_LEAF_SUCCESSOR_ON_DEMAND && SHP)) lo.nblk[q] = successor_word<DR, L>(c, P, dom, next_set, idx);
     }
     S.n_leaves++;
 #ifdef STCSP_PHASES
