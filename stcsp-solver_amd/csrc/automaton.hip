@@ -176,6 +176,78 @@ int AutomatonServices::reserve_tables(const char *who, size_t bytes, Tables &&..
     return reserve_or_release_all(true, tables...) ? (int)STCSP_OK : fail(STCSP_E_NOMEM, "%s: no room for %zu bytes of tables", who, bytes);
 }
 
+// What components(), optimise() and ctl() share: the timed batch of launches, ...
+hipError_t AutomatonServices::LaunchBatch::begin() {
+    hipError_t e = open ? hipSuccess : ev.ready(2);
+    if (e == hipSuccess && !open) e = hipEventRecord(ev[0], stream);
+    open = true;
+    return e;
+}
+hipError_t AutomatonServices::LaunchBatch::flush() {
+    float batch_ms = 0;
+    hipError_t e = begin();
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_ctl, d_ctl, words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = hipEventElapsedTime(&batch_ms, ev[0], ev[1]);
+    ms += batch_ms;
+    open = false;
+    return e;
+}
+
+// ... the fixpoint of sweeps: a batch clears the control word `changed`, launches step(i) for the next kBatch sweeps i (from 0) and ends
+// with one look at the word; past the fixpoint a sweep changes nothing. Past `bound` sweeps: `diverged`, which may print them (%u).
+template <typename Step>
+int AutomatonServices::batched_fixpoint(LaunchBatch &run, int changed, uint32_t bound, const char *diverged, Step step) {
+    for (uint32_t done = 0;;) {
+        HIPCHK(run.begin());
+        HIPCHK(hipMemsetAsync(run.d_ctl + changed, 0, sizeof(uint32_t), v.stream));
+        for (int b = 0; b < kBatch; b++)
+            if (int rc = step(done++)) return rc;
+        HIPCHK(run.flush());
+        if (!run.h_ctl[changed]) return STCSP_OK;
+        if (done > bound) return fail(STCSP_E_INTERNAL, diverged, done);
+    }
+}
+
+// ... the CSR group, first half: the out-degrees over the edges that are alive with both ends in `states`, their scan, and the total read
+// back at the end of the batch (too_many: the caller's message for one past the export, %u of %u). A byte budget is checked here ...
+int AutomatonServices::csr_count(LaunchBatch &run, const uint8_t *states, const char *too_many, uint32_t &count) {
+    const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
+    HIPCHK(reserve_all(S, 1, csr.deg, csr.off, csr.cur));
+    csr.states = states;
+    HIPCHK(run.begin());
+    HIPCHK(hipMemsetAsync(csr.deg.p, 0, (size_t)S * sizeof(uint32_t), v.stream));
+    if (E)
+        hipLaunchKernelGGL(k_s_count, dim3((E + 255) / 256), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p, states, csr.deg.p);
+    hipLaunchKernelGGL(k_s_scan, dim3(1), dim3(256), 0, v.stream, S, (S + 255) / 256, (const uint32_t *)csr.deg.p, csr.off.p, csr.cur.p);
+    HIPCHK(hipMemcpyAsync(&csr.n, csr.off.p + S, sizeof csr.n, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(run.flush());
+    if ((count = csr.n) > E) return fail(STCSP_E_INTERNAL, too_many, count, E);
+    return STCSP_OK;
+}
+
+// ... before the second half: room for the positions, and the launch that fills them
+int AutomatonServices::csr_fill() {
+    const uint32_t E = (uint32_t)v.exp_edges;
+    HIPCHK(reserve_all(csr.n, 1, csr.src, csr.dst, csr.eid));
+    if (csr.n)
+        hipLaunchKernelGGL(k_s_fill, dim3((E + 255) / 256), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p, csr.states,
+                           csr.cur.p, csr.n, csr.src.p, csr.dst.p, csr.eid.p);
+    return STCSP_OK;
+}
+
+// ... and the label rows of the n export edges a walk wrote, from the pinned export (past_export: the caller's message, %u of %u)
+int AutomatonServices::walked_rows(const uint32_t *eid, size_t n, const char *past_export, std::vector<int32_t> &rows) {
+    const size_t E = v.exp_edges, N = (size_t)v.N;
+    for (size_t t = 0; t < n; t++) {
+        if (eid[t] >= E) return fail(STCSP_E_INTERNAL, past_export, eid[t], (uint32_t)E);
+        rows.insert(rows.end(), v.h_oval + eid[t] * N, v.h_oval + (eid[t] + 1) * N);
+    }
+    return STCSP_OK;
+}
+
 // graphTraverse / adversarialTraverse / adversarialTraverse2 on the device (dev_postproc.hpp)
 int AutomatonServices::postprocess(const AutomatonView &view, const stcsp_post_options *po, stcsp_post_result *out) {
     if (int rc = enter(view, "postprocess", NEED_EXPORT, nullptr)) return rc;
@@ -1796,82 +1868,43 @@ int AutomatonServices::compare(const AutomatonView &view, const stcsp_compare_re
 }
 
 // Strongly connected components of the live automaton, omega-liveness and lasso solutions (contract: stcsp_engine.h;
-// dev_components.hpp). Every device buffer lives for the call; no other service's state is touched.
+// dev_components.hpp). Every device buffer lives for the call, the shared CSR group too; no other service's state is touched.
 int AutomatonServices::components(const AutomatonView &view, const stcsp_components_options *co, stcsp_components_result *out) {
     if (int rc = enter(view, "components", NEED_FLAGS, "stcsp_automaton_components")) return rc;
     auto t0 = std::chrono::steady_clock::now();
     const int N = v.N;
-    const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
+    const uint32_t S = v.n_states;
     const int64_t max_lassos = co ? co->max_lassos : 0;
     const int32_t flags = co ? co->flags : 0;
     if (max_lassos < -1) return fail(STCSP_E_INVALID, "components: max_lassos is 0 (none), -1 (all) or a positive count");
     if (v.exp_edges > 0x7fffffffull || S > 0x3fffffffu) return fail(STCSP_E_NOMEM, "automaton too large for the device component pass");
     if (int rc = live_set()) return rc;
-    HIPCHK(reserve_all(S, 1, scc.d_scomp, scc.d_scolour, scc.d_sin, scc.d_sout, scc.d_sdepth, scc.d_soff));
+    HIPCHK(reserve_all(S, 1, scc.d_scomp, scc.d_scolour, scc.d_sin, scc.d_sout, scc.d_sdepth));
     HIPCHK(scc.d_sinfo.reserve(4 * (size_t)S));
     HIPCHK(scc.d_somega.reserve(S));
     HIPCHK(scc.d_sctl.reserve_exact(S_WORDS));
     HIPCHK(scc.d_ssel.reserve_exact(64));
-    HIPCHK(ev.ready(2));
-    const unsigned sb = (S + 255) / 256, eb = (E + 255) / 256;
+    const unsigned sb = (S + 255) / 256;
     const size_t sw = (size_t)S * sizeof(uint32_t);
     uint32_t ctl[S_WORDS] = {0, 0, 0, 0};
-    double ms_kernels = 0;
-    bool open = false;  // between the event before a batch of launches and the one after it
+    LaunchBatch run{v.stream, ev, scc.d_sctl.p, ctl, S_WORDS};
     int32_t sweeps = 0, trim_rounds = 0, colour_rounds = 0;
-    auto begin = [&]() -> int {
-        if (!open) HIPCHK(hipEventRecord(ev[0], v.stream));
-        open = true;
-        return STCSP_OK;
-    };
-    auto flush = [&]() -> int {  // ends a batch: the control words, and the batch's time on the device
-        if (int rc = begin()) return rc;
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev[1], v.stream));
-        HIPCHK(hipMemcpyAsync(ctl, scc.d_sctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(hipStreamSynchronize(v.stream));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        ms_kernels += ms;
-        open = false;
-        return STCSP_OK;
-    };
     // the live edges as CSR by source
     uint32_t L = 0;
-    if (int rc = begin()) return rc;
+    HIPCHK(run.begin());
     HIPCHK(hipMemsetAsync(scc.d_sctl.p, 0, sizeof ctl, v.stream));
-    HIPCHK(hipMemsetAsync(scc.d_sin.p, 0, sw, v.stream));
-    if (E)
-        hipLaunchKernelGGL(k_s_count, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p, (const uint8_t *)post.d_live.p,
-                           scc.d_sin.p);
-    hipLaunchKernelGGL(k_s_scan, dim3(1), dim3(256), 0, v.stream, S, (S + 255) / 256, (const uint32_t *)scc.d_sin.p, scc.d_soff.p, scc.d_sout.p);
-    HIPCHK(hipMemcpyAsync(&L, scc.d_soff.p + S, sizeof L, hipMemcpyDeviceToHost, v.stream));
-    if (int rc = flush()) return rc;
-    if (L > E) return fail(STCSP_E_INTERNAL, "components: %u live edges of %u", L, E);
-    HIPCHK(reserve_all(L, 1, scc.d_ssrc, scc.d_sdst, scc.d_seid));
+    if (int rc = csr_count(run, post.d_live.p, "components: %u live edges of %u", L)) return rc;
+    if (int rc = csr_fill()) return rc;
     const unsigned lb = (L + 255) / 256;
-    const uint32_t *csrc = scc.d_ssrc.p, *cdst = scc.d_sdst.p;
-    if (L)
-        hipLaunchKernelGGL(k_s_fill, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p, (const uint8_t *)post.d_live.p,
-                           scc.d_sout.p, L, scc.d_ssrc.p, scc.d_sdst.p, scc.d_seid.p);
-    // step(i) launches sweep i; a batch of sweeps, then one look at the changed word; past the fixpoint a sweep changes nothing
-    const int kBatch = 4;
-    auto fixpoint = [&](const char *what, auto &&step) -> int {
-        for (uint32_t done = 0;;) {
-            if (int rc = begin()) return rc;
-            HIPCHK(hipMemsetAsync(scc.d_sctl.p + S_CHANGED, 0, sizeof(uint32_t), v.stream));
-            for (int b = 0; b < kBatch; b++, sweeps++)
-                if (int rc = step(done++)) return rc;
-            if (int rc = flush()) return rc;
-            if (!ctl[S_CHANGED]) return STCSP_OK;
-            if (done > S + 8) return fail(STCSP_E_INTERNAL, "components: %s did not converge", what);
-        }
+    const uint32_t *csrc = csr.src.p, *cdst = csr.dst.p;
+    auto fixpoint = [&](const char *diverged, auto &&step) -> int {  // step(i) launches sweep i
+        return batched_fixpoint(run, S_CHANGED, S + 8, diverged, [&](uint32_t i) -> int { return sweeps++, step(i); });
     };
     // trim and colour until every live state has a component
     HIPCHK(hipMemsetAsync(scc.d_scomp.p, 0xff, sw, v.stream));
     while ((int64_t)ctl[S_ASSIGNED] < post.n_live) {
         if (!(flags & STCSP_SCC_NO_TRIM)) {
-            const int rc = fixpoint("trimming", [&](uint32_t) -> int {
+            const int rc = fixpoint("components: trimming did not converge", [&](uint32_t) -> int {
                 HIPCHK(hipMemsetAsync(scc.d_sin.p, 0, sw, v.stream));
                 HIPCHK(hipMemsetAsync(scc.d_sout.p, 0, sw, v.stream));
                 if (L) hipLaunchKernelGGL(k_s_deg, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, (const uint32_t *)scc.d_scomp.p, scc.d_sin.p, scc.d_sout.p);
@@ -1884,16 +1917,16 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
             if ((int64_t)ctl[S_ASSIGNED] >= post.n_live) break;
         }
         if ((uint32_t)colour_rounds++ > S + 8) return fail(STCSP_E_INTERNAL, "components: the colouring rounds did not converge");
-        if (int rc = begin()) return rc;
+        HIPCHK(run.begin());
         hipLaunchKernelGGL(k_s_colour_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)post.d_live.p, (const uint32_t *)scc.d_scomp.p, scc.d_scolour.p);
-        int rc = fixpoint("colouring", [&](uint32_t) -> int {
+        int rc = fixpoint("components: colouring did not converge", [&](uint32_t) -> int {
             if (L) hipLaunchKernelGGL(k_s_colour_fwd, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, scc.d_scolour.p, scc.d_sctl.p);
             return STCSP_OK;
         });
         if (rc) return rc;
-        if (int rc2 = begin()) return rc2;
+        HIPCHK(run.begin());
         hipLaunchKernelGGL(k_s_roots, dim3(sb), dim3(256), 0, v.stream, S, (const uint32_t *)scc.d_scolour.p, scc.d_scomp.p, scc.d_sctl.p);
-        rc = fixpoint("collecting", [&](uint32_t) -> int {
+        rc = fixpoint("components: collecting did not converge", [&](uint32_t) -> int {
             if (L) hipLaunchKernelGGL(k_s_colour_back, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, (const uint32_t *)scc.d_scolour.p, scc.d_scomp.p, scc.d_sctl.p);
             return STCSP_OK;
         });
@@ -1901,15 +1934,15 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
     }
     if ((int64_t)ctl[S_ASSIGNED] != post.n_live) return fail(STCSP_E_INTERNAL, "components: %u of %lld live states have a component", ctl[S_ASSIGNED], (long long)post.n_live);
     // depths, the facts of every component, omega
-    if (int rc = begin()) return rc;
+    HIPCHK(run.begin());
     HIPCHK(hipMemsetAsync(scc.d_sdepth.p, 0xff, sw, v.stream));
     if (post.root_live) HIPCHK(hipMemsetAsync(scc.d_sdepth.p, 0, sizeof(uint32_t), v.stream));
-    if (int rc = fixpoint("the depths", [&](uint32_t level) -> int {
+    if (int rc = fixpoint("components: the depths did not converge", [&](uint32_t level) -> int {
             if (L) hipLaunchKernelGGL(k_s_bfs, dim3(lb), dim3(256), 0, v.stream, L, level, csrc, cdst, scc.d_sdepth.p, scc.d_sctl.p);
             return STCSP_OK;
         }))
         return rc;
-    if (int rc = begin()) return rc;
+    HIPCHK(run.begin());
     HIPCHK(hipMemsetAsync(scc.d_sinfo.p, 0, 2 * sw, v.stream));
     HIPCHK(hipMemsetAsync(scc.d_sinfo.p + 2 * (size_t)S, 0xff, 2 * sw, v.stream));
     hipLaunchKernelGGL(k_s_state_info, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)post.d_live.p, (const uint8_t *)post.d_pfinal.p,
@@ -1917,7 +1950,7 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
     if (L) hipLaunchKernelGGL(k_s_edge_info, dim3(lb), dim3(256), 0, v.stream, L, S, csrc, cdst, (const uint32_t *)scc.d_scomp.p, scc.d_sinfo.p);
     hipLaunchKernelGGL(k_s_omega_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)post.d_live.p, (const uint32_t *)scc.d_scomp.p,
                        (const uint32_t *)scc.d_sinfo.p, scc.d_somega.p);
-    if (int rc = fixpoint("omega", [&](uint32_t) -> int {
+    if (int rc = fixpoint("components: omega did not converge", [&](uint32_t) -> int {
             if (L) hipLaunchKernelGGL(k_s_omega_back, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, scc.d_somega.p, scc.d_sctl.p);
             return STCSP_OK;
         }))
@@ -1927,7 +1960,7 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
     HIPCHK(hipMemcpyAsync(raw.data(), scc.d_scomp.p, sw, hipMemcpyDeviceToHost, v.stream));
     HIPCHK(hipMemcpyAsync(info.data(), scc.d_sinfo.p, 4 * sw, hipMemcpyDeviceToHost, v.stream));
     HIPCHK(hipMemcpyAsync(scc.s_omega.data(), scc.d_somega.p, S, hipMemcpyDeviceToHost, v.stream));
-    if (int rc = flush()) return rc;
+    HIPCHK(run.flush());
     // component numbers by least member: a component's raw name is its least member, so the first state that shows it is that member
     scc.s_component.assign(S, -1);
     scc.s_size.clear();
@@ -1975,8 +2008,8 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
         HIPCHK(scc.d_smark.reserve(S));
         HIPCHK(scc.d_sdist.reserve(S));
         HIPCHK(hipMemcpyAsync(depth.data(), scc.d_sdepth.p, sw, hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(hipMemcpyAsync(off.data(), scc.d_soff.p, sw + sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(hipMemcpyAsync(heid.data(), scc.d_seid.p, (size_t)L * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(off.data(), csr.off.p, sw + sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(hipMemcpyAsync(heid.data(), csr.eid.p, (size_t)L * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
         bool twice = false;
         // the position of the live out-edge of u with the least full row among those whose destination `ok` admits; L when there is none
         auto least_edge = [&](uint32_t u, auto &&ok) {
@@ -2001,7 +2034,7 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
                 deepest = std::max(deepest, info[3 * (size_t)S + sel[j]]);
             }
             if (deepest > S) return fail(STCSP_E_INTERNAL, "components: an accepting component without a final state");
-            if (int rc = begin()) return rc;
+            HIPCHK(run.begin());
             HIPCHK(hipMemcpyAsync(scc.d_ssel.p, sel, (size_t)n_sel * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
             hipLaunchKernelGGL(k_s_stem_init, dim3(sb), dim3(256), 0, v.stream, S, n_sel, (const uint32_t *)scc.d_ssel.p, (const uint8_t *)post.d_live.p,
                                (const uint8_t *)post.d_pfinal.p, (const uint32_t *)scc.d_scomp.p, (const uint32_t *)scc.d_sdepth.p, (const uint32_t *)scc.d_sinfo.p,
@@ -2009,7 +2042,7 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
             for (uint32_t level = deepest; level-- > 0; sweeps++)
                 hipLaunchKernelGGL(k_s_stem_back, dim3(lb), dim3(256), 0, v.stream, L, level, csrc, cdst, (const uint32_t *)scc.d_sdepth.p, scc.d_smark.p);
             HIPCHK(hipMemcpyAsync(mark.data(), scc.d_smark.p, (size_t)S * sizeof(unsigned long long), hipMemcpyDeviceToHost, v.stream));
-            if (int rc = flush()) return rc;
+            HIPCHK(run.flush());
             for (int j = 0; j < n_sel; j++) {
                 const uint32_t len = info[3 * (size_t)S + sel[j]];
                 uint32_t u = 0;
@@ -2025,18 +2058,18 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
             }
         }
         // the anchors' buffer: the colours are no longer needed (as many anchors as components at the most)
-        if (int rc = begin()) return rc;
+        HIPCHK(run.begin());
         HIPCHK(hipMemcpyAsync(scc.d_scolour.p, anchors.data(), anchors.size() * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
         HIPCHK(hipMemsetAsync(scc.d_sdist.p, 0xff, sw, v.stream));
         hipLaunchKernelGGL(k_s_loop_init, dim3(((unsigned)anchors.size() + 255) / 256), dim3(256), 0, v.stream, (uint32_t)anchors.size(), S,
                            (const uint32_t *)scc.d_scolour.p, scc.d_sdist.p);
-        if (int rc = fixpoint("the loop distances", [&](uint32_t level) -> int {
+        if (int rc = fixpoint("components: the loop distances did not converge", [&](uint32_t level) -> int {
                 if (L) hipLaunchKernelGGL(k_s_loop_back, dim3(lb), dim3(256), 0, v.stream, L, level, csrc, cdst, (const uint32_t *)scc.d_scomp.p, scc.d_sdist.p, scc.d_sctl.p);
                 return STCSP_OK;
             }))
             return rc;
         HIPCHK(hipMemcpyAsync(dist.data(), scc.d_sdist.p, sw, hipMemcpyDeviceToHost, v.stream));
-        if (int rc = flush()) return rc;
+        HIPCHK(run.flush());
         for (size_t i = 0; i < wanted.size(); i++) {
             const uint32_t a = anchors[i], r = raw[a];
             uint32_t loop_len = kSNone;
@@ -2077,19 +2110,19 @@ int AutomatonServices::components(const AutomatonView &view, const stcsp_compone
     out->rounds[0] = trim_rounds;
     out->rounds[1] = colour_rounds;
     out->rounds[2] = sweeps;
-    out->seconds_kernels = ms_kernels * 1e-3;
+    out->seconds_kernels = run.ms * 1e-3;
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;
 }
 
 // Optimal solution streams: the least cost of a solution prefix per length with its lexicographically least witness, and the
 // minimum cycle mean of every cyclic component (contract: stcsp_engine.h; dev_optimise.hpp). Every
-// device buffer is this call's own; with STCSP_OPT_MEAN the component pass above runs first and its result is replaced.
+// device buffer is this call's own or, the CSR group, built anew by it; with STCSP_OPT_MEAN the component pass above runs first and its result is replaced.
 int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_request *rq, stcsp_optimise_result *out) {
     if (int rc = enter(view, "optimise", NEED_FLAGS, "stcsp_automaton_optimise")) return rc;
     auto t0 = std::chrono::steady_clock::now();
     const int N = v.N;
-    const uint32_t E = (uint32_t)v.exp_edges, S = v.n_states;
+    const uint32_t S = v.n_states;
     const int32_t horizon = rq->horizon, n_len = rq->n_lengths, flags = rq->flags;
     if (!rq->weights) return fail(STCSP_E_INVALID, "optimise: weights is null");
     if (horizon < 0) return fail(STCSP_E_INVALID, "optimise: horizon %d is negative", horizon);
@@ -2146,52 +2179,25 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
     opt.opt_component.clear();
     opt.opt_num.assign(n_comp, 0);
     opt.opt_den.assign(n_comp, 0);
-    HIPCHK(reserve_all(S, 1, opt.d_opt_deg, opt.d_opt_off, opt.d_opt_cur));
     HIPCHK(opt.d_opt_ctl.reserve_exact(OPT_WORDS));
     HIPCHK(opt.d_opt_w.reserve_exact((size_t)std::max(N, 1)));
     HIPCHK(opt.d_opt_best.reserve((size_t)horizon + 1));
-    HIPCHK(ev.ready(2));
-    const unsigned sb = (S + 255) / 256, eb = (E + 255) / 256;
-    uint32_t ctl[OPT_WORDS] = {0, 0, 0, 0};
-    double ms_kernels = 0;
-    bool open = false;
+    const unsigned sb = (S + 255) / 256;
+    uint32_t ctl[OPT_WORDS] = {0, 0, 0, 0};  // the error words
+    LaunchBatch run{v.stream, ev, opt.d_opt_ctl.p, ctl, OPT_WORDS};
     int32_t launches_dp = 0, launches_karp = 0;
-    auto begin = [&]() -> int {
-        if (!open) HIPCHK(hipEventRecord(ev[0], v.stream));
-        open = true;
-        return STCSP_OK;
-    };
-    auto flush = [&]() -> int {  // ends a batch of launches: the error words, and the batch's time on the device
-        if (int rc = begin()) return rc;
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev[1], v.stream));
-        HIPCHK(hipMemcpyAsync(ctl, opt.d_opt_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(hipStreamSynchronize(v.stream));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        ms_kernels += ms;
-        open = false;
-        return STCSP_OK;
-    };
     std::vector<int32_t> w(rq->weights, rq->weights + N);
     for (int x = 0; x < N && maximise; x++) {
         if (w[x] == INT32_MIN) return fail(STCSP_E_INVALID, "optimise: weights[%d] = INT32_MIN cannot be negated to maximise", x);
         w[x] = -w[x];
     }
-    // the live edges as CSR by source, in this call's buffers
+    // the live edges as CSR by source, built anew (the component pass above has left its own in the group)
     uint32_t L = 0;
     if (S) {
-        if (int rc = begin()) return rc;
+        HIPCHK(run.begin());
         HIPCHK(hipMemsetAsync(opt.d_opt_ctl.p, 0, sizeof ctl, v.stream));
-        HIPCHK(hipMemsetAsync(opt.d_opt_deg.p, 0, (size_t)S * sizeof(uint32_t), v.stream));
         if (N) HIPCHK(hipMemcpyAsync(opt.d_opt_w.p, w.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-        if (E)
-            hipLaunchKernelGGL(k_s_count, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p, (const uint8_t *)post.d_live.p,
-                               opt.d_opt_deg.p);
-        hipLaunchKernelGGL(k_s_scan, dim3(1), dim3(256), 0, v.stream, S, (S + 255) / 256, (const uint32_t *)opt.d_opt_deg.p, opt.d_opt_off.p, opt.d_opt_cur.p);
-        HIPCHK(hipMemcpyAsync(&L, opt.d_opt_off.p + S, sizeof L, hipMemcpyDeviceToHost, v.stream));
-        if (int rc = flush()) return rc;
-        if (L > E) return fail(STCSP_E_INTERNAL, "optimise: %u live edges of %u", L, E);
+        if (int rc = csr_count(run, post.d_live.p, "optimise: %u live edges of %u", L)) return rc;
     }
     const size_t need = row_bytes + 3 * ((size_t)S + 1) * sizeof(uint32_t) + (size_t)L * (3 * sizeof(uint32_t) + sizeof(long long)) +
                         ((size_t)horizon + 1) * sizeof(long long) +
@@ -2200,26 +2206,21 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
         return fail(STCSP_E_NOMEM, "optimise: %zu value rows of %u states, %u live edges%s need %zu bytes, the budget (STCSP_OPTIMISE_BYTES) is %zu", n_rows, S, L,
                     mean ? " and the cycle-mean tables" : "", need, budget);
     if (!opt.d_opt_rows.reserve_or_release(n_rows * (size_t)S)) return fail(STCSP_E_NOMEM, "optimise: no room for %zu bytes of value rows", row_bytes);
-    HIPCHK(reserve_all(L, 1, opt.d_opt_src, opt.d_opt_dst, opt.d_opt_eid));
     HIPCHK(opt.d_opt_cost.reserve(L, 1));
     const unsigned lb = (L + 255) / 256;
-    const uint32_t *csrc = opt.d_opt_src.p, *cdst = opt.d_opt_dst.p;
     if (S) {
         // finite horizon: V_0, then a relaxation and a clearing launch per level
         auto row = [&](int32_t k) { return opt.d_opt_rows.p + (size_t)(witnesses ? k : k % 2) * S; };
         auto next_row = [&](int32_t k) { return k + 1 <= horizon ? row(k + 1) : (long long *)nullptr; };
-        if (int rc = begin()) return rc;
-        if (L) {
-            hipLaunchKernelGGL(k_s_fill, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p, (const uint8_t *)post.d_live.p,
-                               opt.d_opt_cur.p, L, opt.d_opt_src.p, opt.d_opt_dst.p, opt.d_opt_eid.p);
-            hipLaunchKernelGGL(k_opt_cost, dim3(lb), dim3(256), 0, v.stream, L, N, (const uint32_t *)opt.d_opt_eid.p, v.d_oval, (const int32_t *)opt.d_opt_w.p, opt.d_opt_cost.p);
-        }
+        HIPCHK(run.begin());
+        if (int rc = csr_fill()) return rc;
+        if (L) hipLaunchKernelGGL(k_opt_cost, dim3(lb), dim3(256), 0, v.stream, L, N, (const uint32_t *)csr.eid.p, v.d_oval, (const int32_t *)opt.d_opt_w.p, opt.d_opt_cost.p);
         hipLaunchKernelGGL(k_opt_init, dim3(sb), dim3(256), 0, v.stream, S, (const uint8_t *)post.d_live.p, (const uint8_t *)post.d_pfinal.p, end_final, row(0));
         hipLaunchKernelGGL(k_opt_clear, dim3(sb), dim3(256), 0, v.stream, S, next_row(0), (const long long *)row(0), opt.d_opt_best.p);
         launches_dp += 2;
         for (int32_t k = 1; k <= horizon; k++, launches_dp += 2) {
             if (L)
-                hipLaunchKernelGGL(k_opt_relax_back, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, (const long long *)opt.d_opt_cost.p,
+                hipLaunchKernelGGL(k_opt_relax_back, dim3(lb), dim3(256), 0, v.stream, L, (const uint32_t *)csr.src.p, (const uint32_t *)csr.dst.p, (const long long *)opt.d_opt_cost.p,
                                    (const long long *)row(k - 1), row(k));
             hipLaunchKernelGGL(k_opt_clear, dim3(sb), dim3(256), 0, v.stream, S, next_row(k), (const long long *)row(k), opt.d_opt_best.p + k);
         }
@@ -2228,7 +2229,7 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
             opt.opt_state_best.resize(S);
             HIPCHK(hipMemcpyAsync(opt.opt_state_best.data(), row(horizon), (size_t)S * sizeof(long long), hipMemcpyDeviceToHost, v.stream));
         }
-        if (int rc = flush()) return rc;
+        HIPCHK(run.flush());
         // witnesses: one wavefront per requested length walks the rows; the host gathers the label rows from the pinned export
         for (int32_t i = 0; i < n_len; i++) opt.opt_woff[(size_t)i + 1] = opt.opt_woff[i] + (opt.opt_best[rq->lengths[i]] == kOptNone ? 0 : rq->lengths[i]);
         const size_t T = (size_t)opt.opt_woff[n_len];
@@ -2238,23 +2239,19 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
             HIPCHK(opt.d_opt_len.reserve((size_t)n_len));
             HIPCHK(opt.d_opt_woff.reserve((size_t)n_len + 1));
             HIPCHK(reserve_all(T, 0, opt.d_opt_weid, opt.d_opt_wstate));
-            if (int rc = begin()) return rc;
+            HIPCHK(run.begin());
             HIPCHK(hipMemcpyAsync(opt.d_opt_len.p, rq->lengths, (size_t)n_len * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
             HIPCHK(hipMemcpyAsync(opt.d_opt_woff.p, opt.opt_woff.data(), ((size_t)n_len + 1) * sizeof(long long), hipMemcpyHostToDevice, v.stream));
             hipLaunchKernelGGL(k_opt_walk, dim3((unsigned)n_len), dim3(64), 0, v.stream, S, N, (int)n_len, (const int32_t *)opt.d_opt_len.p, (const long long *)opt.d_opt_woff.p,
-                               (const long long *)opt.d_opt_rows.p, (const uint32_t *)opt.d_opt_off.p, cdst, (const uint32_t *)opt.d_opt_eid.p, (const long long *)opt.d_opt_cost.p,
+                               (const long long *)opt.d_opt_rows.p, (const uint32_t *)csr.off.p, (const uint32_t *)csr.dst.p, (const uint32_t *)csr.eid.p, (const long long *)opt.d_opt_cost.p,
                                v.d_oval, opt.d_opt_weid.p, opt.d_opt_wstate.p, opt.d_opt_ctl.p);
             launches_dp++;
             HIPCHK(hipMemcpyAsync(weid.data(), opt.d_opt_weid.p, T * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
             HIPCHK(hipMemcpyAsync(opt.opt_wstates.data(), opt.d_opt_wstate.p, T * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
-            if (int rc = flush()) return rc;
+            HIPCHK(run.flush());
             if (ctl[OPT_DUPLICATE]) return fail(STCSP_E_INTERNAL, "optimise: two live out-edges of state %u carry the same full row", ctl[OPT_DUPLICATE] - 1);
             if (ctl[OPT_STUCK]) return fail(STCSP_E_INTERNAL, "optimise: the walk stops at state %u", ctl[OPT_STUCK] - 1);
-            opt.opt_wvalues.resize(T * (size_t)N);
-            for (size_t t = 0; t < T; t++) {
-                if (weid[t] >= E) return fail(STCSP_E_INTERNAL, "optimise: the walk names edge %u of %u", weid[t], E);
-                std::copy(v.h_oval + (size_t)weid[t] * N, v.h_oval + ((size_t)weid[t] + 1) * N, opt.opt_wvalues.begin() + t * (size_t)N);
-            }
+            if (int rc = walked_rows(weid.data(), T, "optimise: the walk names edge %u of %u", opt.opt_wvalues)) return rc;
         }
     }
     // long run: Karp's minimum cycle mean of every cyclic component in two passes over two rows
@@ -2270,7 +2267,7 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
             HIPCHK(reserve_all(S, 0, opt.d_opt_dn, opt.d_opt_num));
             HIPCHK(opt.d_opt_d.reserve(2 * (size_t)S));
             long long *d[2] = {opt.d_opt_d.p, opt.d_opt_d.p + S};
-            if (int rc = begin()) return rc;
+            HIPCHK(run.begin());
             HIPCHK(hipMemcpyAsync(opt.d_opt_nof.p, n_of.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
             HIPCHK(hipMemcpyAsync(opt.d_opt_comp.p, comp_of.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
             HIPCHK(hipMemcpyAsync(opt.d_opt_least.p, least.data(), (size_t)n_comp * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
@@ -2280,7 +2277,7 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
             const uint32_t *nof = opt.d_opt_nof.p, *comp = opt.d_opt_comp.p;
             auto fwd = [&](uint32_t k) {
                 if (L)
-                    hipLaunchKernelGGL(k_opt_karp_fwd, dim3(lb), dim3(256), 0, v.stream, L, csrc, cdst, comp, (const long long *)opt.d_opt_cost.p,
+                    hipLaunchKernelGGL(k_opt_karp_fwd, dim3(lb), dim3(256), 0, v.stream, L, (const uint32_t *)csr.src.p, (const uint32_t *)csr.dst.p, comp, (const long long *)opt.d_opt_cost.p,
                                        (const long long *)d[(k - 1) % 2], d[k % 2]);
                 launches_karp++;
             };
@@ -2303,7 +2300,7 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
             HIPCHK(hipMemcpyAsync(num.data(), opt.d_opt_num.p, (size_t)S * sizeof(long long), hipMemcpyDeviceToHost, v.stream));
             HIPCHK(hipMemcpyAsync(den.data(), opt.d_opt_den.p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
             HIPCHK(hipMemcpyAsync(arg.data(), opt.d_opt_arg.p, (size_t)n_comp * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
-            if (int rc = flush()) return rc;
+            HIPCHK(run.flush());
             if (ctl[OPT_STUCK]) return fail(STCSP_E_INTERNAL, "optimise: the least mean of the component of state %u did not settle", ctl[OPT_STUCK] - 1);
             for (uint32_t c = 0; c < n_comp; c++) {
                 if (!(scc.s_flags[c] & STCSP_SCC_CYCLIC)) continue;
@@ -2360,14 +2357,14 @@ int AutomatonServices::optimise(const AutomatonView &view, const stcsp_optimise_
     out->largest_cyclic = (int32_t)nmax;
     out->rounds[0] = launches_dp;
     out->rounds[1] = launches_karp;
-    out->seconds_kernels = ms_kernels * 1e-3;
+    out->seconds_kernels = run.ms * 1e-3;
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;
 }
 
 // Fair CTL over the infinite solutions (contract: stcsp_engine.h, stcsp_engine_ctl; dev_ctl.hpp). The
 // lowering is CtlProgram's, shared with the host twin. The component pass above runs first and its result is replaced; every
-// other device buffer is this call's own. A set of worlds is a slot of d_ctl_sets; the evaluation is a walk over the lowered
+// other device buffer is this call's own (the CSR group: built anew). A set of worlds is a slot of d_ctl_sets; the evaluation is a walk over the lowered
 // tree that holds at most the slots CtlProgram measured.
 int AutomatonServices::ctl(const AutomatonView &view, const stcsp_ctl_request *rq, stcsp_ctl_result *out) {
     if (int rc = enter(view, "ctl", NEED_FLAGS, "stcsp_automaton_ctl")) return rc;
@@ -2377,13 +2374,9 @@ int AutomatonServices::ctl(const AutomatonView &view, const stcsp_ctl_request *r
     CtlProgram prog;
     if (int rc = prog.build(rq->program, rq->n_words, N)) return fail(rc, "%s", prog.error.c_str());
     if (v.exp_edges > 0x7fffffffull || S > 0x3fffffffu) return fail(STCSP_E_NOMEM, "automaton too large for the device CTL pass");
-    double ms_kernels = 0;
-    {  // omega first: the call takes the view again
-        const stcsp_components_options co = {0, 0, 0};
-        stcsp_components_result cres;
-        if (int rc = components(view, &co, &cres)) return rc;
-        ms_kernels = cres.seconds_kernels * 1e3;
-    }
+    const stcsp_components_options co = {0, 0, 0};  // omega first: the call takes the view again
+    stcsp_components_result cres;
+    if (int rc = components(view, &co, &cres)) return rc;
     size_t budget = 0;
     if (int rc = table_budget("STCSP_CTL_BYTES", budget)) return rc;
     bool negated = false;
@@ -2406,45 +2399,18 @@ int AutomatonServices::ctl(const AutomatonView &view, const stcsp_ctl_request *r
             if (n.b >= 0) todo.push_back(n.b);
         }
     }
-    HIPCHK(reserve_all(S, 1, ctlq.d_ctl_deg, ctlq.d_ctl_off, ctlq.d_ctl_cur));
     HIPCHK(ctlq.d_ctl_ctl.reserve_exact(CTL_WORDS));
     HIPCHK(ctlq.d_ctl_prog.reserve(words_h.size(), 1));
-    HIPCHK(ev.ready(2));
-    const unsigned eb = (E + 255) / 256;
     uint32_t cw[CTL_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
-    bool open = false;
+    LaunchBatch run{v.stream, ev, ctlq.d_ctl_ctl.p, cw, CTL_WORDS, cres.seconds_kernels * 1e3};  // (the component pass's time counts)
     int32_t sweeps = 0, launches = 0, most_outer = 0;
-    auto begin = [&]() -> int {
-        if (!open) HIPCHK(hipEventRecord(ev[0], v.stream));
-        open = true;
-        return STCSP_OK;
-    };
-    auto flush = [&]() -> int {  // ends a batch of launches: the control words, and the batch's time on the device
-        if (int rc = begin()) return rc;
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev[1], v.stream));
-        HIPCHK(hipMemcpyAsync(cw, ctlq.d_ctl_ctl.p, sizeof cw, hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(hipStreamSynchronize(v.stream));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        ms_kernels += ms;
-        open = false;
-        return STCSP_OK;
-    };
-    // the worlds as CSR by source, in this call's buffers: the omega bytes stand where the builder takes `live`
+    // the worlds as CSR by source, built anew over the component pass's: the omega bytes are the state filter
     uint32_t W = 0;
     if (S) {
-        if (int rc = begin()) return rc;
+        HIPCHK(run.begin());
         HIPCHK(hipMemsetAsync(ctlq.d_ctl_ctl.p, 0, sizeof cw, v.stream));
-        HIPCHK(hipMemsetAsync(ctlq.d_ctl_deg.p, 0, (size_t)S * sizeof(uint32_t), v.stream));
-        if (E)
-            hipLaunchKernelGGL(k_s_count, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p, (const uint8_t *)scc.d_somega.p,
-                               ctlq.d_ctl_deg.p);
-        hipLaunchKernelGGL(k_s_scan, dim3(1), dim3(256), 0, v.stream, S, (S + 255) / 256, (const uint32_t *)ctlq.d_ctl_deg.p, ctlq.d_ctl_off.p, ctlq.d_ctl_cur.p);
-        HIPCHK(hipMemcpyAsync(&W, ctlq.d_ctl_off.p + S, sizeof W, hipMemcpyDeviceToHost, v.stream));
+        if (int rc = csr_count(run, scc.d_somega.p, "ctl: %u worlds of %u edges", W)) return rc;
         launches += 2;
-        if (int rc = flush()) return rc;
-        if (W > E) return fail(STCSP_E_INTERNAL, "ctl: %u worlds of %u edges", W, E);
     }
     const size_t nw = ((size_t)W + 63) / 64;
     const int n_slots = prog.nodes[(size_t)prog.root].slots;
@@ -2458,13 +2424,11 @@ int AutomatonServices::ctl(const AutomatonView &view, const stcsp_ctl_request *r
     ctlq.ctl_witness.clear();
     int32_t witness_kind = STCSP_CTL_NONE, witness_len = 0;
     if (W) {
-        HIPCHK(reserve_all(W, 1, ctlq.d_ctl_src, ctlq.d_ctl_dst, ctlq.d_ctl_eid));
         HIPCHK(ctlq.d_ctl_sets.reserve(((size_t)n_slots + 1) * nw));
         HIPCHK(ctlq.d_ctl_some.reserve(2 * (size_t)S));
         HIPCHK(reserve_all(E, 1, ctlq.d_ctl_world, ctlq.d_ctl_sat));
         if (wit >= 0) HIPCHK(reserve_all((size_t)W + 16, 0, ctlq.d_ctl_dist, ctlq.d_ctl_weid));
         const unsigned wb = (W + 255) / 256, bb = (unsigned)((nw + 255) / 256);
-        const uint32_t *csrc = ctlq.d_ctl_src.p, *cdst = ctlq.d_ctl_dst.p, *ceid = ctlq.d_ctl_eid.p;
         auto set = [&](int slot) { return ctlq.d_ctl_sets.p + (size_t)slot * nw; };
         const unsigned long long *fin = set(n_slots);
         std::vector<uint8_t> used((size_t)n_slots, 0);
@@ -2476,9 +2440,9 @@ int AutomatonServices::ctl(const AutomatonView &view, const stcsp_ctl_request *r
                 }
             return fail(STCSP_E_INTERNAL, "ctl: more than the %d set slots measured", n_slots);
         };
-        if (int rc = begin()) return rc;
-        hipLaunchKernelGGL(k_s_fill, dim3(eb), dim3(256), 0, v.stream, E, v.d_osrc, v.d_odst, (const uint8_t *)post.d_palive.p, (const uint8_t *)scc.d_somega.p,
-                           ctlq.d_ctl_cur.p, W, ctlq.d_ctl_src.p, ctlq.d_ctl_dst.p, ctlq.d_ctl_eid.p);
+        HIPCHK(run.begin());
+        if (int rc = csr_fill()) return rc;
+        const uint32_t *csrc = csr.src.p, *cdst = csr.dst.p, *ceid = csr.eid.p;
         hipLaunchKernelGGL(k_ctl_fin, dim3(wb), dim3(256), 0, v.stream, W, cdst, (const uint8_t *)post.d_pfinal.p, set(n_slots));
         HIPCHK(hipMemsetAsync(ctlq.d_ctl_some.p, 0, 2 * (size_t)S, v.stream));
         if (!words_h.empty()) HIPCHK(hipMemcpyAsync(ctlq.d_ctl_prog.p, words_h.data(), words_h.size() * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
@@ -2498,36 +2462,28 @@ int AutomatonServices::ctl(const AutomatonView &view, const stcsp_ctl_request *r
             hipLaunchKernelGGL(k_ctl_bool, dim3(bb), dim3(256), 0, v.stream, W, op, (const unsigned long long *)set(a), (const unsigned long long *)set(b), set(to));
             launches++;
         };
-        const int kBatch = 4;
-        // z = the least fixpoint of z | (f & EX z); a batch of sweeps, then one look at the changed word; *levels: the sweeps run
+        // z = the least fixpoint of z | (f & EX z): sweep i is level i + 1; *levels: the sweeps run
         auto until = [&](int f, int z, uint32_t *dist, uint32_t *levels) -> int {
-            for (uint32_t done = 0;;) {
-                if (int rc = begin()) return rc;
-                HIPCHK(hipMemsetAsync(ctlq.d_ctl_ctl.p + CTL_CHANGED, 0, sizeof(uint32_t), v.stream));
-                for (int b = 0; b < kBatch; b++) sweep(z, set(f), 1, z, dist, ++done);
-                if (int rc = flush()) return rc;
-                if (levels) *levels = done;
-                if (!cw[CTL_CHANGED]) return STCSP_OK;
-                if (done > W + 8) return fail(STCSP_E_INTERNAL, "ctl: an EU fixpoint did not converge in %u rounds", done);
-            }
+            return batched_fixpoint(run, CTL_CHANGED, W + 8, "ctl: an EU fixpoint did not converge in %u rounds", [&](uint32_t i) -> int {
+                sweep(z, set(f), 1, z, dist, i + 1);
+                if (levels) *levels = i + 1;
+                return STCSP_OK;
+            });
         };
         // the witness walk, at the node it belongs to (the ! above it works in place afterwards)
         auto walk = [&](uint32_t max_len, const uint32_t *dist, const unsigned long long *set_a, const unsigned long long *set_b) -> int {
             std::vector<uint32_t> weid(max_len);
-            if (int rc = begin()) return rc;
-            hipLaunchKernelGGL(k_ctl_walk, dim3(1), dim3(64), 0, v.stream, W, N, max_len, (const uint32_t *)ctlq.d_ctl_off.p, cdst, ceid, dist, set_a, set_b, v.d_oval,
+            HIPCHK(run.begin());
+            hipLaunchKernelGGL(k_ctl_walk, dim3(1), dim3(64), 0, v.stream, W, N, max_len, (const uint32_t *)csr.off.p, cdst, ceid, dist, set_a, set_b, v.d_oval,
                                ctlq.d_ctl_weid.p, ctlq.d_ctl_ctl.p);
             launches++;
             HIPCHK(hipMemcpyAsync(weid.data(), ctlq.d_ctl_weid.p, (size_t)max_len * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
-            if (int rc = flush()) return rc;
+            HIPCHK(run.flush());
             if (cw[CTL_DUPLICATE]) return fail(STCSP_E_INTERNAL, "ctl: two worlds out of state %u carry the same full row", cw[CTL_DUPLICATE] - 1);
             if (cw[CTL_STUCK]) return fail(STCSP_E_INTERNAL, "ctl: the witness walk stops at state %u", cw[CTL_STUCK] - 1);
             const uint32_t len = cw[CTL_WITNESS_LEN];
             if (len > max_len) return fail(STCSP_E_INTERNAL, "ctl: a witness of %u worlds, %u at the most", len, max_len);
-            for (uint32_t t = 0; t < len; t++) {
-                if (weid[t] >= E) return fail(STCSP_E_INTERNAL, "ctl: the witness names edge %u of %u", weid[t], E);
-                ctlq.ctl_witness.insert(ctlq.ctl_witness.end(), v.h_oval + (size_t)weid[t] * N, v.h_oval + ((size_t)weid[t] + 1) * N);
-            }
+            if (int rc = walked_rows(weid.data(), len, "ctl: the witness names edge %u of %u", ctlq.ctl_witness)) return rc;
             witness_len = (int32_t)len;
             if (len) witness_kind = negated ? STCSP_CTL_IS_COUNTEREXAMPLE : STCSP_CTL_IS_WITNESS;
             return STCSP_OK;
@@ -2586,10 +2542,10 @@ int AutomatonServices::ctl(const AutomatonView &view, const stcsp_ctl_request *r
                     hipLaunchKernelGGL(k_ctl_bool, dim3(bb), dim3(256), 0, v.stream, W, (int)CTL_B_AND, (const unsigned long long *)set(z), fin, set(t));
                     launches++;
                     if (int rc = until(a, t, nullptr, nullptr)) return rc;
-                    if (int rc = begin()) return rc;
+                    HIPCHK(run.begin());
                     HIPCHK(hipMemsetAsync(ctlq.d_ctl_ctl.p + CTL_CHANGED, 0, sizeof(uint32_t), v.stream));
                     sweep(t, set(a), 0, z, nullptr, 0);
-                    if (int rc = flush()) return rc;
+                    HIPCHK(run.flush());
                     if (!cw[CTL_CHANGED]) break;
                     if ((uint32_t)round > W + 8) return fail(STCSP_E_INTERNAL, "ctl: an EG fixpoint did not converge in %d rounds", round);
                 }
@@ -2601,7 +2557,7 @@ int AutomatonServices::ctl(const AutomatonView &view, const stcsp_ctl_request *r
         };
         int top = -1;
         if (int rc = eval(eval, prog.root, top)) return rc;
-        if (int rc = begin()) return rc;
+        HIPCHK(run.begin());
         HIPCHK(hipMemsetAsync(ctlq.d_ctl_world.p, 0, E, v.stream));
         HIPCHK(hipMemsetAsync(ctlq.d_ctl_sat.p, 0, E, v.stream));
         HIPCHK(hipMemsetAsync(ctlq.d_ctl_ctl.p, 0, sizeof cw, v.stream));
@@ -2610,7 +2566,7 @@ int AutomatonServices::ctl(const AutomatonView &view, const stcsp_ctl_request *r
         launches++;
         HIPCHK(hipMemcpyAsync(ctlq.ctl_world.data(), ctlq.d_ctl_world.p, E, hipMemcpyDeviceToHost, v.stream));
         HIPCHK(hipMemcpyAsync(ctlq.ctl_sat.data(), ctlq.d_ctl_sat.p, E, hipMemcpyDeviceToHost, v.stream));
-        if (int rc = flush()) return rc;
+        HIPCHK(run.flush());
     }
     ctlq.ctl_world.reserve(1);
     ctlq.ctl_sat.reserve(1);
@@ -2629,7 +2585,7 @@ int AutomatonServices::ctl(const AutomatonView &view, const stcsp_ctl_request *r
     out->rounds[0] = sweeps;
     out->rounds[1] = most_outer;
     out->rounds[2] = launches;
-    out->seconds_kernels = ms_kernels * 1e-3;
+    out->seconds_kernels = run.ms * 1e-3;
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return STCSP_OK;
 }

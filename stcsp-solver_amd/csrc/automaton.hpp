@@ -65,6 +65,22 @@ private:
     template <typename Result, typename NeedFn, typename Body>
     int stream_batches(const char *who, const char *budget_env, int64_t n_streams, const int64_t *offsets, const int32_t *values, bool dictionaries,
                        NeedFn need, Result *out, Body body);
+    // A timed batch of launches of a graph service (components, optimise, ctl): begin() before its launches (nothing while one is open);
+    // flush() after them copies the service's control words to their host copy, waits, and adds the batch's time on the device to ms.
+    struct LaunchBatch {
+        hipStream_t stream;
+        DevEvents &ev;  // [0], [1]
+        uint32_t *d_ctl, *h_ctl;
+        size_t words;
+        double ms = 0;
+        bool open = false;
+        hipError_t begin(), flush();
+    };
+    static constexpr int kBatch = 4;  // the sweeps of a fixpoint between two looks at the changed word
+    template <typename Step>
+    int batched_fixpoint(LaunchBatch &run, int changed, uint32_t bound, const char *diverged, Step step);
+    int csr_count(LaunchBatch &run, const uint8_t *states, const char *too_many, uint32_t &count), csr_fill();
+    int walked_rows(const uint32_t *eid, size_t n, const char *past_export, std::vector<int32_t> &rows);
     template <typename... Tables>
     int reserve_tables(const char *who, size_t bytes, Tables &&...tables);
     // the two argument lists the stream kernels share, cast once: the generator's CSR with the label id of every position ...
@@ -217,8 +233,17 @@ private:
         std::vector<int64_t> y_moff;
         std::vector<int32_t> y_mval;
     } pos;
-    struct Components {  // components (dev_components.hpp)
-        DevBuf<uint32_t> d_scomp, d_scolour, d_sin, d_sout, d_sdepth, d_sdist, d_soff, d_sinfo, d_ssrc, d_sdst, d_seid, d_ssel, d_sctl;
+    // The live edges as 32-bit CSR by source (dev_csr.hpp), for the graph services. It lives for one call: csr_count() and
+    // csr_fill() build it anew, under the state filter of the caller, and nothing reads it after the call returns. optimise(mean)
+    // and ctl() run components() first, which builds and uses its CSR to the end; they then build their own into this same
+    // group (ctl under scc.d_somega, which stays in scc). No call may rely on the CSR an earlier call left here.
+    struct LiveCsr {
+        DevBuf<uint32_t> deg, off, cur, src, dst, eid;  // [S + 1] out-degrees, offsets, fill cursors; [n] source, destination, export index
+        const uint8_t *states = nullptr;                // the filter csr_count() ran under, for csr_fill()
+        uint32_t n = 0;                                 // positions: off[S]
+    } csr;
+    struct Components {  // components (dev_components.hpp); d_sin / d_sout: the has_in / has_out marks of the trim rounds, arrays of their own
+        DevBuf<uint32_t> d_scomp, d_scolour, d_sin, d_sout, d_sdepth, d_sdist, d_sinfo, d_ssel, d_sctl;
         DevBuf<uint8_t> d_somega;
         DevBuf<unsigned long long> d_smark;
         std::vector<int32_t> s_component, s_size, s_depth, s_flags, s_lcomp, s_lstem, s_lvalues;
@@ -226,7 +251,7 @@ private:
         std::vector<int64_t> s_loff;
     } scc;
     struct Optimise {  // optimisation (dev_optimise.hpp)
-        DevBuf<uint32_t> d_opt_deg, d_opt_off, d_opt_cur, d_opt_src, d_opt_dst, d_opt_eid, d_opt_weid, d_opt_wstate, d_opt_ctl;
+        DevBuf<uint32_t> d_opt_weid, d_opt_wstate, d_opt_ctl;
         DevBuf<uint32_t> d_opt_nof, d_opt_comp, d_opt_least, d_opt_den, d_opt_arg;
         DevBuf<int32_t> d_opt_w, d_opt_len;
         DevBuf<long long> d_opt_cost, d_opt_rows, d_opt_best, d_opt_woff, d_opt_d, d_opt_dn, d_opt_num;
@@ -234,7 +259,7 @@ private:
         std::vector<int32_t> opt_wvalues, opt_wstates, opt_component;
     } opt;
     struct Ctl {  // fair CTL (dev_ctl.hpp): nothing is kept between calls; the vectors back the result
-        DevBuf<uint32_t> d_ctl_deg, d_ctl_off, d_ctl_cur, d_ctl_src, d_ctl_dst, d_ctl_eid, d_ctl_dist, d_ctl_weid, d_ctl_ctl;
+        DevBuf<uint32_t> d_ctl_dist, d_ctl_weid, d_ctl_ctl;
         DevBuf<unsigned long long> d_ctl_sets;  // the set slots, then Fin
         DevBuf<uint8_t> d_ctl_some, d_ctl_world, d_ctl_sat;
         DevBuf<int32_t> d_ctl_prog;

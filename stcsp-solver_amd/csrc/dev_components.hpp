@@ -7,8 +7,8 @@
 // a racing reader can only see a value that is already correct or the older one, which the next sweep mends. Every loop
 // in a kernel is bounded by a launch parameter.
 //
-//   k_s_count / k_s_scan / k_s_fill   once: the live edges (alive, both ends live) compacted into 32-bit CSR by source:
-//                      off[S + 1], and per position source, destination and the edge's index in the export (12 B per edge)
+//   k_s_count / k_s_scan / k_s_fill   (dev_csr.hpp) once: the live edges (alive, both ends live) compacted into 32-bit CSR by
+//                      source: off[S + 1], and per position source, destination and the edge's index in the export
 //   trim round         k_s_deg marks the states that have an in-edge / an out-edge inside the remaining set (self-loops
 //                      do not count), k_s_trim gives every other remaining state its own component
 //   colouring round    (Orzan) k_s_colour_init colours the remaining states with their own index; k_s_colour_fwd sweeps
@@ -29,65 +29,14 @@
 
 #include <cstdint>
 
+#include "dev_csr.hpp"
+
 namespace stcsp {
 namespace dev {
 
 constexpr uint32_t kSNone = 0xffffffffu;  // no component yet / not in the remaining set / not reached
 enum { S_CHANGED = 0, S_ASSIGNED = 1, S_WORDS = 4 };  // the words the host reads between batches of sweeps
 enum { S_INFO_CYCLIC = 1, S_INFO_FINAL = 2, S_INFO_LEAVES = 4 };
-
-// ctr += the number of lanes of the wavefront for which pred holds: one atomic per wavefront
-__device__ inline void s_tally(bool pred, uint32_t *ctr) {
-    const unsigned long long m = __ballot(pred);
-    if (pred && (int)__lane_id() == __ffsll((long long)m) - 1) atomicAdd(ctr, (uint32_t)__popcll(m));
-}
-
-__device__ inline bool s_live_edge(uint32_t e, const long long *src, const long long *dst, const uint8_t *alive, const uint8_t *live) {
-    return alive[e] && live[src[e]] && live[dst[e]];
-}
-
-__global__ void k_s_count(uint32_t E, const long long *src, const long long *dst, const uint8_t *alive, const uint8_t *live, uint32_t *deg) {
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E || !s_live_edge(e, src, dst, alive, live)) return;
-    atomicAdd(&deg[src[e]], 1u);
-}
-
-// Exclusive scan of deg[0 .. S) by one workgroup of 256: lane t owns the states [t * chunk, (t + 1) * chunk). off[S] = the total.
-__global__ void k_s_scan(uint32_t S, uint32_t chunk, const uint32_t *deg, uint32_t *off, uint32_t *cursor) {
-    __shared__ uint32_t part[256];
-    const uint32_t t = threadIdx.x;
-    const unsigned long long base = (unsigned long long)t * chunk;
-    uint32_t sum = 0;
-    for (uint32_t i = 0; i < chunk; i++)
-        if (base + i < S) sum += deg[base + i];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256; d <<= 1) {
-        const uint32_t x = t >= d ? part[t - d] : 0u;
-        __syncthreads();
-        part[t] += x;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - sum;
-    for (uint32_t i = 0; i < chunk; i++)
-        if (base + i < S) {
-            off[base + i] = run;
-            cursor[base + i] = run;
-            run += deg[base + i];
-        }
-    if (t == 255) off[S] = part[255];
-}
-
-__global__ void k_s_fill(uint32_t E, const long long *src, const long long *dst, const uint8_t *alive, const uint8_t *live, uint32_t *cursor,
-                         uint32_t L, uint32_t *csrc, uint32_t *cdst, uint32_t *ceid) {
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E || !s_live_edge(e, src, dst, alive, live)) return;
-    const uint32_t u = (uint32_t)src[e], k = atomicAdd(&cursor[u], 1u);
-    if (k >= L) return;  // (cannot happen: the counts are of the same edges)
-    csrc[k] = u;
-    cdst[k] = (uint32_t)dst[e];
-    ceid[k] = e;
-}
 
 // Trim. has_in / has_out are zeroed before the launch.
 __global__ void k_s_deg(uint32_t L, const uint32_t *csrc, const uint32_t *cdst, const uint32_t *comp, uint32_t *has_in, uint32_t *has_out) {

@@ -2,7 +2,7 @@
 // section 4.23). There is no reference counterpart.
 //
 // The worlds (live edges into omega-live states) are the positions of a CSR by source built by k_s_count / k_s_scan /
-// k_s_fill (dev_components.hpp) on this service's own buffers. A set of worlds is a bit set over the positions: the wavefront
+// k_s_fill (dev_csr.hpp) into the services' one CSR group, for this call. A set of worlds is a bit set over the positions: the wavefront
 // of the lanes [64 j, 64 j + 64) owns word j and writes it whole from __ballot, so no set word is ever written by two
 // wavefronts and none needs an atomic; a lane past n_worlds votes 0, which keeps the tail bits of the last word 0.
 // Everything is level-synchronous: launch boundaries are the only ordering, no workgroup waits for another, and every loop
@@ -18,14 +18,14 @@
 //                   after this one: the two buffers alternate, so a sweep is two launches and no memset.
 //   k_ctl_dist_init the distances of an EU that keeps them, before its first level
 //   k_ctl_walk      the witness: one wavefront, lanes striding over a state's CSR segment, the least full row among the
-//                   candidates of the distance wanted, a __shfl_xor butterfly for the least of 64
+//                   candidates of the distance wanted, a __shfl_xor butterfly for the least of 64 (walk_least_row of dev_csr.hpp)
 //   k_ctl_scatter   the final set to bytes by export index, and the tallies of the initial worlds
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "dev_components.hpp"
+#include "dev_csr.hpp"
 #include "stcsp_engine.h"
 
 namespace stcsp {
@@ -114,15 +114,6 @@ __global__ void k_ctl_pre(uint32_t W, const uint32_t *csrc, const uint32_t *cdst
     }
 }
 
-// true when the full row of export edge a is lexicographically below that of b; *equal when the rows are the same
-__device__ inline bool ctl_row_less(const int32_t *val, int N, uint32_t a, uint32_t b, bool *equal) {
-    const int32_t *x = val + (size_t)a * N, *y = val + (size_t)b * N;
-    for (int i = 0; i < N; i++)
-        if (x[i] != y[i]) return x[i] < y[i];
-    *equal = true;
-    return false;
-}
-
 // The witness walk, one wavefront. With dist (EU): the candidates of a step with `rem` worlds to go are the worlds of the
 // segment with dist == rem - 1; len = 1 + the least dist among the initial worlds (found here). Without (EX): set_a at
 // rem == 2 and set_b at rem == 1; len = 2 when an initial world is in set_a. Writes the export edges to out_eid[0 .. len)
@@ -142,25 +133,15 @@ __global__ void __launch_bounds__(64) k_ctl_walk(uint32_t W, int N, uint32_t max
     }
     uint32_t s = 0;
     for (uint32_t rem = len; rem > 0; rem--) {
-        uint32_t best = kCtlNone;  // a CSR position
         bool dup = false;
-        for (uint32_t k = off[s] + lane; k < off[s + 1]; k += 64) {
-            if (!(dist ? dist[k] == rem - 1 : ctl_bit(rem == 2 ? set_a : set_b, k))) continue;
-            if (best == kCtlNone || ctl_row_less(val, N, ceid[k], ceid[best], &dup)) best = k;
-        }
-        for (int step = 32; step > 0; step >>= 1) {
-            const uint32_t other = (uint32_t)__shfl_xor((int)best, step);
-            if (other == kCtlNone || other == best) continue;
-            if (best == kCtlNone || ctl_row_less(val, N, ceid[other], ceid[best], &dup))
-                best = other;
-            else if (dup && other < best)
-                best = other;  // (equal rows: an error anyway; keeps the lanes in step)
-        }
-        if (__any(dup)) {
+        const uint32_t best = walk_least_row(off, s, lane, ceid, val, N, [&](uint32_t k) {  // the worlds of the distance, or the set, wanted
+            return dist ? dist[k] == rem - 1 : ctl_bit(rem == 2 ? set_a : set_b, k);
+        }, &dup);
+        if (dup) {
             if (lane == 0) ctl[CTL_DUPLICATE] = 1u + s;
             return;
         }
-        if (best == kCtlNone || best >= W) {  // (cannot happen: a world of distance d > 0 has a successor of distance d - 1)
+        if (best == kRowNone || best >= W) {  // (cannot happen: a world of distance d > 0 has a successor of distance d - 1)
             if (lane == 0) ctl[CTL_STUCK] = 1u + s;
             return;
         }

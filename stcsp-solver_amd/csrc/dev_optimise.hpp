@@ -8,15 +8,15 @@
 // another: launch boundaries are the only ordering between workgroups. Every loop is bounded by a launch parameter.
 // The kernels only ever minimise; the host negates the weights to maximise.
 //
-// The live edges come as 32-bit CSR by source (k_s_count / k_s_scan / k_s_fill of dev_components.hpp, in this service's
-// own buffers): off[S + 1], and per position source, destination and the edge's index in the export.
+// The live edges come as 32-bit CSR by source (k_s_count / k_s_scan / k_s_fill of dev_csr.hpp, built for this call into the
+// services' one CSR group): off[S + 1], and per position source, destination and the edge's index in the export.
 //
 //   k_opt_cost           per position: c = sum_v weights[v] * values[eid][v] in int64, once per call
 //   k_opt_init           V_0[s] = 0 on the live states (the live final ones under END_FINAL), kOptNone elsewhere
 //   k_opt_relax_back     level k: V_k[src] = min(V_k[src], c + V_{k-1}[dst]), skipping kOptNone
 //   k_opt_clear          after level k: sets the row of level k + 1 to kOptNone and keeps best[k] = V_k[root]
 //   k_opt_walk           one wavefront per requested length: the greedy walk over the rows V_0 .. V_L; the lanes stride over
-//                      the state's CSR segment, a wave reduction picks the least full row among the tight edges
+//                      the state's CSR segment, walk_least_row (dev_csr.hpp) picks the least full row among the tight edges
 //   k_opt_karp_init      all cyclic components at once (they are disjoint, so one pair of rows serves them all):
 //                      D_0 = 0 at every component's least member, kOptNone elsewhere
 //   k_opt_karp_fwd       level k: D_k[dst] = min(D_k[dst], D_{k-1}[src] + c) over the edges whose two ends share a component
@@ -29,6 +29,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "dev_csr.hpp"
 
 namespace stcsp {
 namespace dev {
@@ -68,15 +70,6 @@ __global__ void k_opt_clear(uint32_t S, long long *next, const long long *cur, l
     if (s == 0) *best_slot = cur[0];
 }
 
-// true when the full row of export edge a is lexicographically below that of b; *equal when the rows are the same
-__device__ inline bool opt_row_less(const int32_t *val, int N, uint32_t a, uint32_t b, bool *equal) {
-    const int32_t *x = val + (size_t)a * N, *y = val + (size_t)b * N;
-    for (int i = 0; i < N; i++)
-        if (x[i] != y[i]) return x[i] < y[i];
-    *equal = true;
-    return false;
-}
-
 // One wavefront per requested length: block j walks lengths[j] steps from the root over the rows V_0 .. V_L (rows[k * S + s])
 // and writes the CSR positions' export edge indices to out_eid[woff[j] + t] and the entered states to out_state. A length
 // whose best is kOptNone writes nothing (its witness is empty: woff[j + 1] == woff[j]).
@@ -91,26 +84,16 @@ __global__ void __launch_bounds__(64) k_opt_walk(uint32_t S, int N, int n_length
     for (int left = len; left > 0; left--) {
         const long long want = rows[(size_t)left * S + s];
         const long long *below = rows + (size_t)(left - 1) * S;
-        uint32_t best = kOptIdxNone;  // a CSR position
         bool dup = false;
-        for (uint32_t k = off[s] + lane; k < off[s + 1]; k += 64) {
+        const uint32_t best = walk_least_row(off, s, lane, ceid, val, N, [&](uint32_t k) {  // the tight edges
             const long long d = below[cdst[k]];
-            if (d == kOptNone || cost[k] + d != want) continue;
-            if (best == kOptIdxNone || opt_row_less(val, N, ceid[k], ceid[best], &dup)) best = k;
-        }
-        for (int step = 32; step > 0; step >>= 1) {
-            const uint32_t other = __shfl_xor(best, step);
-            if (other == kOptIdxNone || other == best) continue;
-            if (best == kOptIdxNone || opt_row_less(val, N, ceid[other], ceid[best], &dup))
-                best = other;
-            else if (dup && other < best)
-                best = other;  // (equal rows: an error anyway; keeps the lanes in step)
-        }
-        if (__any(dup)) {
+            return d != kOptNone && cost[k] + d == want;
+        }, &dup);
+        if (dup) {
             if (lane == 0) ctl[OPT_DUPLICATE] = 1u + s;
             return;
         }
-        if (best == kOptIdxNone) {  // (cannot happen: V_k[s] is the minimum over exactly these edges)
+        if (best == kRowNone) {  // (cannot happen: V_k[s] is the minimum over exactly these edges)
             if (lane == 0) ctl[OPT_STUCK] = 1u + s;
             return;
         }
